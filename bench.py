@@ -14,7 +14,8 @@ Default workload = BASELINE.json configs[3] (the config the metric "MS-BFS MTEPS
 1/2/4/8 GPU" is quoted on; it fits one GPU): synthetic LDBC-SNB-SF100-shaped Person-knows-Person graph (V=448,626,
 39.88 M symmetric CSR entries), iterativelength on 65,536 random pairs (`default_rng(4)`).
   N = 1:  the top-level fields describe that workload (= leg "prepass": every row is answered by the pair-centric
-          kernels); `legs` holds it next to one leg per other BASELINE config and call shape (`legs_by_config` maps them):
+          kernels); `legs` holds it next to one leg per other BASELINE config and call shape (`legs_by_config` maps them;
+          `legs` itself is printed as its own JSON line on stderr, the result line keeps `legs_summary`):
             msbfs_cross       the same graph in the binder's call shape (match.cpp:467-495: a cross product of endpoints —
                               2048 distinct sources x 1024 destinations = 2.1 M rows, grouped by source), as the library routes
                               it (round 6: the source-centric kernel k_src_ball, one two-hop ball per source run)
@@ -117,7 +118,15 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, count them with one all_reduce and print {n_gpus}: the CPU test of the "
                          "launcher (no GPU work)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the main workload's last timed step returned as DIR/<name>.npy "
+                         "(float64, at most 64 MB: larger outputs as a fixed, seeded sample of rows)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.gpus > 1:
+        ap.error("--dump-outputs writes one GPU's results: use it with --gpus 1")
+    return a
 
 
 def self_launch(a):
@@ -326,9 +335,13 @@ class Bench:
         stats = pgq.get_stats()
         last = (steps - 1) & 1
         out_len = d_len[last].clone()
+        out_off = out_child = None
+        if paths:  # the lists of the last timed step, before the isolated pass below reuses the buffers
+            out_off, out_child = d_off[last].clone(), d_child[last].clone()
+        out_ok = None
         if cheapest:
             reach = int(d_ok.sum().item())
-            out_val = d_val[last].clone()
+            out_val, out_ok = d_val[last].clone(), d_ok.clone()
         else:
             assert bool((out_len == ref_len).all()), "timed output differs from the traversed-edge accounting pass"
             if steps > 1:
@@ -357,10 +370,10 @@ class Bench:
         pgq.set_option("streams", n_streams)
         pgq.set_option("relax_streams", n_relax_streams)
         res = {"n": n, "elapsed": elapsed, "stats": stats, "iso": iso, "iso_steps": iso_steps, "iso_elapsed": iso_elapsed,
-               "te_local": te_local, "reach": reach, "out_len": out_len, "out_val": out_val, "d_ok": d_ok, "d_te": d_te,
+               "te_local": te_local, "reach": reach, "out_len": out_len, "out_val": out_val, "out_ok": out_ok, "d_ok": d_ok, "d_te": d_te,
                "steps": steps}
-        if paths:  # what the isolated pass (same rows, same answers) left in buffer 0: offsets + payload of every list
-            res["out_off"], res["out_child"] = d_off[(iso_steps - 1) & 1].clone(), d_child[(iso_steps - 1) & 1].clone()
+        if paths:  # offsets + payload of every list of the last timed step; the isolated pass gave the same answers
+            res["out_off"], res["out_child"] = out_off, out_child
             assert bool((d_len[(iso_steps - 1) & 1] == out_len).all())
         return res
 
@@ -567,6 +580,51 @@ def config_leg(bench, a, wl, copy_gbps, snb_graph, snb_csr):
     return out
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: most bytes written in all
+DUMP_SEED = 11           # --dump-outputs: the row sample of an output larger than that
+
+
+def dump_outputs(dirname, m, paths=False, cheapest=False, weights="int64"):
+    """Writes what the timed path returned in its last timed step as float64 .npy files under `dirname`:
+      length       iterativelength / shortestpath: hop count per row (-1 = NULL)
+      path         shortestpath: the lists of the non-NULL rows, concatenated in row order (2 * length + 1 entries each)
+      cost, valid  cheapest_path_length: the path cost (-1 where NULL) and 1 / 0 validity per row
+      rows         the row indices written, ascending (every row when the output fits DUMP_BYTES; else a sample
+                   drawn with DUMP_SEED, so that runs with the same arguments write the same rows)
+    Lists are repacked in row order: the device packs them at offsets the reply does not fix."""
+    if cheapest:
+        val = m["out_val"].cpu().numpy()
+        ok = m["out_ok"].cpu().numpy().astype(bool)
+        val = val.view(np.float64) if weights == "double" else val.astype(np.float64)
+        out = {"cost": np.where(ok, val, -1.0), "valid": ok.astype(np.float64)}
+    else:
+        out = {"length": m["out_len"].cpu().numpy().astype(np.float64)}
+    n = len(next(iter(out.values())))
+    if paths:
+        ln = m["out_len"].cpu().numpy()
+        cnt = np.where(ln >= 0, 2 * ln + 1, 0)
+        off = m["out_off"].cpu().numpy()
+        used = int((off + cnt)[ln >= 0].max(initial=0))
+        child = m["out_child"][:used].cpu().numpy()
+    row_bytes = 8 * (len(out) + (int(cnt.max(initial=0)) if paths else 0))
+    rows = np.arange(n, dtype=np.int64)
+    if 8 * n + n * row_bytes > DUMP_BYTES:
+        keep = DUMP_BYTES // (8 + row_bytes)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+    if paths:
+        c = cnt[rows]
+        first = np.repeat(off[rows], c)  # start of each entry's own list
+        within = np.arange(int(c.sum()), dtype=np.int64) - np.repeat(np.cumsum(c) - c, c)
+        out["path"] = child[first + within].astype(np.float64)
+    out["rows"] = rows.astype(np.float64)
+    assert sum(v.nbytes for v in out.values()) <= DUMP_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return out
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -634,6 +692,8 @@ def main():
     if world == 1 and not a.no_first_call and a.workload != "snb_cross_allv":
         first_main = bench.first_call(fresh_csr, mine_t, a.first_call_handles, paths=paths, cheapest=cheapest)
     m = bench.run(a.workload, csr, mine_t, total_pairs, a.steps, a.warmup, paths=paths, cheapest=cheapest)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, m, paths=paths, cheapest=cheapest, weights=a.weights)
     try:
         copy_gbps = pgq.copy_bandwidth_gbps(1 << 30, 5) if rank == 0 else None
     except Exception:
@@ -739,7 +799,7 @@ def main():
             "ms_per_step": main_leg["ms_per_step"], "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             "dtype": "u64" if not cheapest else ("f64" if a.weights == "double" else "int64"),
             "data": "synthetic",
-            "schema": 6,  # round 6: legs_summary / first_call / msbfs_cross_lanes / msbfs_cross_rmat22; round 5: `roofline` = the leg's launch chain (round 4: its dominant kernel, now `roofline.dominant_kernel`)
+            "schema": 7,  # 7: `legs` on stderr, not in this line; round 6: legs_summary / first_call / msbfs_cross_lanes / msbfs_cross_rmat22; round 5: `roofline` = the leg's launch chain (round 4: its dominant kernel, now `roofline.dominant_kernel`)
             "value_kind": "pairs answered per second, whole job; mteps_physical = adjacency entries scanned per second / 1e6; "
                           "mteps_logical = reference-lane traversed edges per second / 1e6 (work avoided, not a hardware rate)",
             "mteps_logical": main_leg["mteps_logical"],
@@ -837,6 +897,8 @@ def main():
                     out["leg_%s_first_ms" % nm] = round(fc, 3)
             out["legs_summary_format"] = "[ms_per_step, chain frac of 8 TB/s, whole-step frac, rows compared with the CPU port, rows equal, first_call_ms]"
             out["legs_summary"] = summ
+        if "legs" in out:  # the per-leg detail (~29 KB) goes to stderr: line readers of stdout stopped parsing it at 35 KB
+            print(json.dumps({"legs": out.pop("legs")}), file=sys.stderr, flush=True)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

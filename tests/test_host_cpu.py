@@ -264,6 +264,50 @@ def test_bench_strided_sample_of_the_cross_product_covers_every_source():
     assert len(np.unique(cp[:8192, 0])) == 8
 
 
+def test_bench_dump_outputs_writes_the_reply_in_row_order(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 arrays of what the timed step returned; path lists repacked in row order whatever
+    offsets the device packed them at; cheapest costs masked by validity; an output over the byte budget becomes the same
+    seeded row sample on every run."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    ln = np.array([2, -1, 0, 1], dtype=np.int64)
+    off = np.array([3, 77, 0, 8], dtype=np.int64)  # row 1 is NULL: its offset is garbage and must not be read
+    child = np.full(12, -5, dtype=np.int64)
+    child[3:8], child[0:1], child[8:11] = [10, 100, 11, 101, 12], [20], [30, 300, 31]
+    m = {"out_len": torch.from_numpy(ln), "out_off": torch.from_numpy(off), "out_child": torch.from_numpy(child)}
+    out = bench.dump_outputs(str(tmp_path / "p"), m, paths=True)
+    assert out["path"].tolist() == [10, 100, 11, 101, 12, 20, 30, 300, 31]
+    assert out["length"].tolist() == [2, -1, 0, 1] and out["rows"].tolist() == [0, 1, 2, 3]
+    for k, v in out.items():
+        got = np.load(tmp_path / "p" / (k + ".npy"))
+        assert got.dtype == np.float64 and (got == v).all()
+
+    val, ok = np.array([7, -1, 12], dtype=np.int64), np.array([1, 0, 1], dtype=np.uint8)
+    out = bench.dump_outputs(str(tmp_path / "c"), {"out_val": torch.from_numpy(val), "out_ok": torch.from_numpy(ok)}, cheapest=True)
+    assert out["cost"].tolist() == [7, -1, 12] and out["valid"].tolist() == [1, 0, 1]
+    dv = np.array([0.5, 2.25])
+    out = bench.dump_outputs(str(tmp_path / "d"), {"out_val": torch.from_numpy(dv.view(np.int64)),
+                                                   "out_ok": torch.from_numpy(np.ones(2, dtype=np.uint8))}, cheapest=True, weights="double")
+    assert out["cost"].tolist() == [0.5, 2.25]
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 16 * 1000)
+    big = {"out_len": torch.arange(5000, dtype=torch.int64)}
+    a = bench.dump_outputs(str(tmp_path / "s1"), big)
+    b = bench.dump_outputs(str(tmp_path / "s2"), big)
+    assert len(a["rows"]) == 1000 and (a["rows"] == b["rows"]).all() and (a["length"] == a["rows"]).all()
+    assert sum(v.nbytes for v in a.values()) <= 16 * 1000
+
+
+def test_bench_rejects_a_run_without_timed_steps():
+    """--steps sets the number of timed steps, so ms_per_step = the timed region / --steps: zero steps is refused."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_stats_struct_layout_matches_the_header(tmp_path):
     """pgq_stats_t grew at its end in round 5 (spec_batches ... host_waits): the ctypes mirror must have the header's size
     and field offsets, or every statistic after the first mismatch reads garbage."""
