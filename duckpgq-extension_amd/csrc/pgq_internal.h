@@ -272,7 +272,6 @@ struct pgq_csr {
 	int64_t hub_threshold = 0;
 	int64_t max_out_degree = 0, max_in_degree = 0;
 	double two_hop_mean = 0; // mean over vertices of in-degree x out-degree = expected two-hop walk of a random endpoint
-	std::atomic<double> meet_bpr { 0.0 }; // bytes per row the pre-pass has been measured to move on this CSR (0: not yet; pgq_msbfs.hip)
 	int64_t bytes = 0;
 	bool has_negative_weight = false;
 	// multi-GPU: copies of this CSR on the other enabled devices (pgq_csr_replicate), indexed like enabled_devices();
@@ -317,19 +316,40 @@ struct pgq_csr {
 		bool ball_yes = false;
 		bool sorted_yes = false; // ... or took them after a sort by source (rows of a source scattered over the input)
 	} route_memo;
-	// share of a call's rows the source-centric kernel left open, last time it ran on this CSR (half the weight to the newest
-	// call): above ~2 % those rows drag the lane batches along anyway (R-MAT: far and unreachable pairs), and the kernel
-	// stays out of the chain until the CSR is uploaded again
-	std::atomic<double> ball_open_frac { 0.0 };
-	// large grouped calls, wall time per row in ns as measured on this graph shape (0: not yet): through the source-centric
-	// kernel (everything it took: its own kernels and the search of the rows it left open) and through the lane batches
-	// (the BEST time seen, not a mean: a process's first call of a kind also pays for allocations, kernel attributes, the
-	// calibration — 26 ms where the call takes 0.3; the first version took that sample for the route's cost and left the SF100
-	// cross product on the lane batches, 7 x slower, for good)
-	std::atomic<double> route_ball_ns { 0.0 }, route_lanes_ns { 0.0 };
-	std::atomic<int> route_ball_samples { 0 }, route_lanes_samples { 0 };
-	std::atomic<int64_t> route_rows { 0 }; // rows of the calls the figures come from: they speak for calls of at least half that size
-	std::atomic<int> route_try_lanes { 0 }; // the former cost far more than the byte model's price of the latter: time the latter (twice)
+	// What the routes have measured on this graph shape (pgq_route.hip).  Relaxed atomics: read on every call without a
+	// lock; the calibration cache keeps a snapshot per graph shape for the next handle (calibration_load / _store).
+	struct RouteCalibration {
+		struct Figures {
+			double meet_bpr, ball_open_frac, route_ball_ns, route_lanes_ns;
+			int route_ball_samples, route_lanes_samples, route_try_lanes;
+			int64_t route_rows;
+		};
+		std::atomic<double> meet_bpr { 0.0 }; // bytes per row the pre-pass has been measured to move on this CSR (0: not yet)
+		// share of a call's rows the source-centric kernel left open, last time it ran on this CSR (half the weight to the newest
+		// call): above ~2 % those rows drag the lane batches along anyway (R-MAT: far and unreachable pairs), and the kernel
+		// stays out of the chain until the CSR is uploaded again
+		std::atomic<double> ball_open_frac { 0.0 };
+		// large grouped calls, wall time per row in ns as measured on this graph shape (0: not yet): through the source-centric
+		// kernel (everything it took: its own kernels and the search of the rows it left open) and through the lane batches
+		// (the BEST time seen, not a mean: a process's first call of a kind also pays for allocations, kernel attributes, the
+		// calibration — 26 ms where the call takes 0.3; the first version took that sample for the route's cost and left the SF100
+		// cross product on the lane batches, 7 x slower, for good)
+		std::atomic<double> route_ball_ns { 0.0 }, route_lanes_ns { 0.0 };
+		std::atomic<int> route_ball_samples { 0 }, route_lanes_samples { 0 };
+		std::atomic<int64_t> route_rows { 0 }; // rows of the calls the figures come from: they speak for calls of at least half that size
+		std::atomic<int> route_try_lanes { 0 }; // the former cost far more than the byte model's price of the latter: time the latter (twice)
+		Figures snapshot() const {
+			auto ld = [](const auto &a) { return a.load(std::memory_order_relaxed); };
+			return { ld(meet_bpr), ld(ball_open_frac), ld(route_ball_ns), ld(route_lanes_ns), ld(route_ball_samples),
+			         ld(route_lanes_samples), ld(route_try_lanes), ld(route_rows) };
+		}
+		void restore(const Figures &f) {
+			auto st = [](auto &a, auto v) { a.store(v, std::memory_order_relaxed); };
+			st(meet_bpr, f.meet_bpr), st(ball_open_frac, f.ball_open_frac), st(route_ball_ns, f.route_ball_ns), st(route_lanes_ns, f.route_lanes_ns);
+			st(route_ball_samples, f.route_ball_samples), st(route_lanes_samples, f.route_lanes_samples), st(route_try_lanes, f.route_try_lanes);
+			st(route_rows, f.route_rows);
+		}
+	} cal;
 	bool is_replica = false;
 };
 

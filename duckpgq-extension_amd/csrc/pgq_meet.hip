@@ -974,7 +974,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 	// with the static stride of round 3 a slot could draw two long rows, or a long one last.  Thread 0 draws the NEXT
 	// position while the current row is processed (the atomic's round trip is off the critical path).
 	// the sampled decision of the distinct sources rides here when the chain runs on the route memo's word (meet_prepass,
-	// decide_mode 2): the LAST workgroup — its first row is one of the short ones, and the rows are handed out dynamically —
+	// DecideMode::Ride): the LAST workgroup — its first row is one of the short ones, and the rows are handed out dynamically —
 	// takes the sample in the bit map's LDS before its first row clears it
 	if (!GM && sm.h_go && blockIdx.x == gridDim.x - 1 && bm_words >= kSampleSlots && !db->ball.go)
 		sample_distinct_sources(sm.n, sm.src, sm.V, sm.meet_bytes, sm.edge_bytes, sm.out, sm.h_go, s_map);
@@ -1466,7 +1466,7 @@ __global__ __launch_bounds__(256) void k_emit_paths(int64_t n, const int64_t *__
 // strided sample of the rows goes through an LDS hash set, thread 0 inverts E[distinct] = U (1 - (1 - 1/U)^sample) and
 // compares the two cost estimates ON THE DEVICE: the pre-pass kernels are launched straight behind and return at once
 // when the flag says no, so the host waits once per call instead of once for the decision and once for the result.
-// Ends a chain that holds the source-centric kernels alone (meet_prepass, ball_mode 3): reports like the last stage kernel would.
+// Ends a chain that holds the source-centric kernels alone (meet_prepass, BallMode::Only): reports like the last stage kernel would.
 __global__ void k_chain_end(MeetDevBlock *__restrict__ db, MeetHostBlock *__restrict__ fin) { meet_finalize(db, fin); }
 
 // ball_go (nullable): the source-centric kernel in front of this one has taken the call: no sample, no pre-pass.
@@ -1566,44 +1566,48 @@ static int print_ball_trace(const unsigned long long *b_trace, u32 nseg, u32 ope
 
 // Runs the pre-pass over n rows (device memory, or pinned host memory the device can address: the chunk entry points
 // hand their staging block over as it is); rows it answers get their hop count (or -1 for NULL) in d_out, the others end
-// up in ws->open_src / open_dst / open_idx and are counted in *n_open.  The whole chain — decision (large inputs),
+// up in ws->open_src / open_dst / open_idx and are counted in r->n_open.  The whole chain — decision (large inputs),
 // k_meet3, the bit-map kernel, the bidirectional search for a handful of leftovers — is launched back to back; every
 // kernel reads what it needs (the go flag, the number of rows still open) from device memory and appends what it leaves
 // open to the next one's queue, the last one reports into the pinned block: the host launches 2-4 kernels and waits ONCE.
-// decide: k_meet_decide compares `meet_bytes` with the lanes' cost for the sampled number of distinct sources
-// (lanes_cost_bytes) first; *ran = false when it said no (nothing was written to d_out).
-// ball_mode (round 6): 1 = k_ball_segments + k_src_ball open the chain and the device decides from the number of source
-// runs whether the source-centric kernel takes the call (then every stage kernel behind it returns at once and *ball_ran
-// = true: the open rows are what IT left); 2 = it always does (tests); 0 = the chain starts with the stage kernels.
-int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out,
-                 u32 *n_open, MeetPathsOut *po, int decide_mode, double meet_bytes, double edge_bytes, bool *ran, int *observed_go,
-                 int ball_mode, bool *ball_ran, double *est_sources) {
+// DecideMode::Gate: k_meet_decide compares `meet_bytes` with the lanes' cost for the sampled number of distinct sources
+// (lanes_cost_bytes) first; r->answered = false when it said no (nothing was written to d_out).
+// BallMode (round 6): Decide = k_ball_segments + k_src_ball open the chain and the device decides from the number of source
+// runs whether the source-centric kernel takes the call (then every stage kernel behind it returns at once and
+// r->ball_took = true: the open rows are what IT left); Always = it always does (tests); Off = the chain starts with the
+// stage kernels.  r->ball_attempted: the two kernels were launched (there was room for their vertex bit maps).
+int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult *r) {
+	const int64_t n = a.n;
+	const int64_t *d_src = a.d_src, *d_dst = a.d_dst;
+	int64_t *d_out = a.d_out;
+	MeetPathsOut *po = a.po;
+	const double meet_bytes = a.meet_bytes, edge_bytes = a.edge_bytes;
 	const bool paths = po != nullptr;
-	if (ball_ran) *ball_ran = false;
-	if (est_sources) *est_sources = -1.0; // the decision kernel's estimate of the distinct sources, when it ran
+	*r = PrepassResult();
+	int ball_mode = a.ball == BallMode::Off ? 0 : (a.ball == BallMode::Always ? 2 : 1);
 	if (paths || !c->rseg || !c->fdesc || !c->rdesc || n < 2) ball_mode = 0;
-	// ball_mode 3: the route memo says the source-centric kernel took these buffers last time — the chain is its two kernels
-	// and a one-thread report, without the stage kernels that would only return at once behind it (65,536 one-wavefront
-	// workgroups of k_meet3 and 256 of k_meet4d starting up to read one word: 28 us of a 0.36-ms call).  If it declines this
-	// time, *ball_ran stays false, *ran = false, and the caller runs the chain again without it.
-	const bool ball_only = ball_mode == 3;
-	if (ball_only) ball_mode = 1;
-	// decide_mode 1: k_meet_decide in front of the chain, its flag gates every stage kernel on the device.  2: the route
-	// memo says the last call on these buffers was answered here: the chain runs ungated and the sample rides in k_meet4d's
-	// launch (its last workgroup, in the bit map's LDS) — *observed_go gets its verdict for the memo, -1 when none was taken
-	// (12 us of kernel + a launch gap in front of every 65,536-row call otherwise; tried first: the sample on a second
-	// stream beside the chain — the extra launch and wait on the host cost what the kernel did)
-	if (observed_go) *observed_go = -1;
+	// BallMode::Only: the route memo says the source-centric kernel took these buffers last time — the chain is its two
+	// kernels and a one-thread report, without the stage kernels that would only return at once behind it (65,536
+	// one-wavefront workgroups of k_meet3 and 256 of k_meet4d starting up to read one word: 28 us of a 0.36-ms call).  If it
+	// declines this time, r->answered = false and the caller runs the chain again without it.  If there is no room for its
+	// maps it is not attempted and the chain below (the stage kernels) answers the call.
+	const bool ball_only = a.ball == BallMode::Only;
+	// DecideMode::Ride: the route memo says the last call on these buffers was answered here: the chain runs ungated and the
+	// sample rides in k_meet4d's launch (its last workgroup, in the bit map's LDS) — r->observed_go gets its verdict for the
+	// memo, -1 when none was taken (12 us of kernel + a launch gap in front of every 65,536-row call otherwise; tried first:
+	// the sample on a second stream beside the chain — the extra launch and wait on the host cost what the kernel did)
+	DecideMode decide_mode = a.decide;
 	{ // the ride needs k_meet4d (distance-only flow) with its bit map in LDS and large enough to lend: else the gate again
 		const Options &o = options();
 		const int bmw = (int)((c->V + 127) / 128) * 4;
 		const size_t budget = (size_t)std::min(150, std::max(0, o.meet4_lds_kb)) * 1024;
-		if (decide_mode == 2 && !(o.meet4 && !paths && (size_t)bmw * 4 + 2048 <= budget && bmw >= kSampleSlots)) decide_mode = 1;
+		if (decide_mode == DecideMode::Ride && !(o.meet4 && !paths && (size_t)bmw * 4 + 2048 <= budget && bmw >= kSampleSlots))
+			decide_mode = DecideMode::Gate;
 	}
-	const bool decide = decide_mode == 1;
+	const bool decide = decide_mode == DecideMode::Gate;
 	u32 *h_go = reinterpret_cast<u32 *>(static_cast<char *>(ws->h_meet) + 4104);
 	SampleArgs ride { meet_bytes, edge_bytes, nullptr, nullptr, n, d_src, c->V };
-	if (decide_mode == 2) {
+	if (decide_mode == DecideMode::Ride) {
 		PGQ_TRY(ws->route_dec.reserve(sizeof(MeetDecision)));
 		*h_go = 0;
 		ride.out = ws->route_dec.as<MeetDecision>();
@@ -1612,7 +1616,6 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	hipStream_t st = ws->stream;
 	pgq_stats_t &S = tstats().s;
 	const Options &opt = options();
-	if (ran) *ran = true;
 	MeetQueue q[2];
 	MeetDevBlock *db = nullptr;
 	MeetHostBlock *hb = nullptr;
@@ -1703,6 +1706,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		if (grid_b == 0) {
 			ball_mode = 0; // no room for the maps: the older routes
 		} else {
+			r->ball_attempted = true;
 			if (ball_maps > ws->meet_maps.cap) {
 				PGQ_TRY(ws->meet_maps.reserve(std::max(ball_maps, maps_bytes + bi_bytes + 64)));
 				gmaps = ws->meet_maps.as<u32>();
@@ -1727,8 +1731,8 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 			// rows the last call on this graph shape left open (0 before the first) prices it.  R-MAT-22, 2048 x 1024: 1.7 % open x
 			// 1.7 MB per row = 28 KB per row — the lane batches (12 ms) are then the cheaper route, not this one (16.7 ms).
 			{
-				const double bpr = meet_bytes > 0 && n > 0 ? meet_bytes / (double)n : c->meet_bpr.load(std::memory_order_relaxed);
-				rule.row_bytes += c->ball_open_frac.load(std::memory_order_relaxed) * std::max(0.0, bpr);
+				const double bpr = meet_bytes > 0 && n > 0 ? meet_bytes / (double)n : c->cal.meet_bpr.load(std::memory_order_relaxed);
+				rule.row_bytes += c->cal.ball_open_frac.load(std::memory_order_relaxed) * std::max(0.0, bpr);
 			}
 			rule.meet_bytes = meet_bytes;
 			rule.edge_bytes = edge_bytes > 0 ? edge_bytes : (double)c->E;
@@ -1769,11 +1773,11 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
 		if (!h.ball_go) { // not this time: nothing was answered
 			S.algo_bytes[K_BALL] += 16.0 * (double)n;
-			if (ran) *ran = false;
-			*n_open = (u32)n;
+			r->answered = false;
+			r->n_open = (u32)n;
 			return PGQ_OK;
 		}
-		if (ball_ran) *ball_ran = true;
+		r->ball_took = true;
 		if (b_trace) PGQ_TRY(print_ball_trace(b_trace, h.ball_nseg, h.ball_open));
 		ws->open_src = q[0].src;
 		ws->open_dst = q[0].dst;
@@ -1783,8 +1787,8 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		S.algo_bytes[K_BALL] += 4.0 * (double)h.ball_entries + 16.0 * (double)h.ball_descs + 32.0 * (double)n + 24.0 * (double)h.ball_nseg;
 		S.ball_segments += h.ball_nseg;
 		S.ball_calls++;
-		if (est_sources) *est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
-		*n_open = h.ball_open;
+		r->est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
+		r->n_open = h.ball_open;
 		return PGQ_OK;
 	}
 	// (tried in round 4: the decision kernel on a stream of its own beside k_meet3, which polls a stop flag — the event
@@ -1906,7 +1910,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		kt.stop();
 	}
 	PGQ_TRY(meet_wait(ws, hb, !paths));
-	if (decide_mode == 2 && observed_go && *h_go) *observed_go = (int)*h_go - 1;
+	if (decide_mode == DecideMode::Ride && *h_go) r->observed_go = (int)*h_go - 1;
 	if (paths) po->total = *h_total;
 	const MeetHostBlock &h = *hb;
 	if (d_trace) { // debugging aid: where k_meet4d's time goes
@@ -1931,7 +1935,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	if (b_trace && h.ball_go) PGQ_TRY(print_ball_trace(b_trace, h.ball_nseg, h.ball_open));
 	if (ball_mode && h.ball_go) { // the source-centric kernel took the call: what is open sits in region 0, counted by itself
 		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
-		if (ball_ran) *ball_ran = true;
+		r->ball_took = true;
 		ws->open_src = q[0].src;
 		ws->open_dst = q[0].dst;
 		ws->open_idx = q[0].idx;
@@ -1942,16 +1946,16 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		S.algo_bytes[K_BALL] += 4.0 * (double)h.ball_entries + 16.0 * (double)h.ball_descs + 32.0 * (double)n + 24.0 * (double)h.ball_nseg;
 		S.ball_segments += h.ball_nseg;
 		S.ball_calls++;
-		if (est_sources) *est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
-		*n_open = h.ball_open;
+		r->est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
+		r->n_open = h.ball_open;
 		return PGQ_OK;
 	}
 	if (ball_mode) // it looked at the rows (8 B per row, twice) and declined
 		S.algo_bytes[K_BALL] += 16.0 * (double)n;
-	if (decide && est_sources) *est_sources = h.dec.estimate;
+	if (decide) r->est_sources = h.dec.estimate;
 	if (decide && !h.dec.go) {
-		if (ran) *ran = false;
-		*n_open = (u32)n;
+		r->answered = false;
+		r->n_open = (u32)n;
 		return PGQ_OK;
 	}
 	if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
@@ -1968,7 +1972,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	S.algo_bytes[K_MEET] += 4.0 * (double)h.entries[0] + 16.0 * (double)h.vertices[0] + 64.0 * (double)n;
 	S.algo_bytes[K_MEET4] += 4.0 * (double)h.entries[1] + 16.0 * (double)h.vertices[1] + 56.0 * (double)(h.count[0] + h.count_back);
 	S.algo_bytes[K_BIBFS] += 4.0 * (double)h.entries[2] + 16.0 * (double)h.vertices[2];
-	*n_open = open;
+	r->n_open = open;
 	return PGQ_OK;
 }
 

@@ -1379,9 +1379,7 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 struct CalEntry {
 	int64_t V, E, max_out, max_in;
 	double two_hop_mean;
-	double meet_bpr, ball_open_frac, route_ball_ns, route_lanes_ns;
-	int route_try_lanes, route_ball_samples, route_lanes_samples;
-	int64_t route_rows;
+	pgq_csr::RouteCalibration::Figures figures;
 	std::vector<uint8_t> level_plan[6];
 };
 static std::mutex g_cal_lock;
@@ -1394,14 +1392,7 @@ void calibration_load(pgq_csr *c) {
 	std::lock_guard<std::mutex> g(g_cal_lock);
 	for (const CalEntry &e : g_cal)
 		if (cal_same(e, c)) {
-			c->meet_bpr.store(e.meet_bpr, std::memory_order_relaxed);
-			c->ball_open_frac.store(e.ball_open_frac, std::memory_order_relaxed);
-			c->route_ball_ns.store(e.route_ball_ns, std::memory_order_relaxed);
-			c->route_lanes_ns.store(e.route_lanes_ns, std::memory_order_relaxed);
-			c->route_try_lanes.store(e.route_try_lanes, std::memory_order_relaxed);
-			c->route_ball_samples.store(e.route_ball_samples, std::memory_order_relaxed);
-			c->route_lanes_samples.store(e.route_lanes_samples, std::memory_order_relaxed);
-			c->route_rows.store(e.route_rows, std::memory_order_relaxed);
+			c->cal.restore(e.figures);
 			std::lock_guard<std::mutex> g2(c->plan_lock);
 			for (int k = 0; k < 6; k++) c->level_plan[k] = e.level_plan[k];
 			return;
@@ -1409,12 +1400,8 @@ void calibration_load(pgq_csr *c) {
 }
 void calibration_store(pgq_csr *c) {
 	if (!c || c->is_replica || !options().calibration_cache) return;
-	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->meet_bpr.load(std::memory_order_relaxed),
-		         c->ball_open_frac.load(std::memory_order_relaxed), c->route_ball_ns.load(std::memory_order_relaxed),
-		         c->route_lanes_ns.load(std::memory_order_relaxed), c->route_try_lanes.load(std::memory_order_relaxed),
-		         c->route_ball_samples.load(std::memory_order_relaxed), c->route_lanes_samples.load(std::memory_order_relaxed),
-		         c->route_rows.load(std::memory_order_relaxed), {} };
-	bool any = n.meet_bpr > 0 || n.ball_open_frac > 0 || n.route_ball_ns > 0;
+	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {} };
+	bool any = n.figures.meet_bpr > 0 || n.figures.ball_open_frac > 0 || n.figures.route_ball_ns > 0;
 	{
 		std::lock_guard<std::mutex> g2(c->plan_lock);
 		for (int k = 0; k < 6; k++) {

@@ -314,7 +314,7 @@ int pull_lanes_level(pgq_csr *c, Workspace *ws, int wd, const u64 *front, const 
 
 // Pair-centric pre-pass (pgq_meet.hip): answers rows at distance <= 3 (and NULL / trivial / dead-end rows) into d_out,
 // compacts the others into ws->def_src/def_dst/def_idx; meet_apply scatters their lengths back.  decide: whether the
-// pre-pass pays (distinct sources, sampled) is settled on the device in the same launch chain; *ran = false: it did not run.
+// pre-pass pays (distinct sources, sampled) is settled on the device in the same launch chain (DecideMode::Gate).
 // shortestpath through the pre-pass: where the lists of the rows it answers go ([src, e, v, ..., dst], first-slot edges;
 // entry i at the scanned offset, also stored in d_out_off[i]; a list that does not fit child_cap is not written) and how
 // many elements they take
@@ -326,9 +326,30 @@ struct MeetPathsOut {
 };
 // the lists of the rows the last meet_prepass(po) on this workspace answered, written again into po's (now larger) buffer
 int meet_reemit_paths(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const int64_t *d_out, MeetPathsOut *po);
-int meet_prepass(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out,
-                 u32 *n_open, MeetPathsOut *po, int decide_mode, double meet_bytes, double edge_bytes, bool *ran, int *observed_go,
-                 int ball_mode = 0, bool *ball_ran = nullptr, double *est_sources = nullptr);
+// Decision in front of the chain: None = the pre-pass runs; Gate = the sampled decision (k_meet_decide) gates it on the
+// device; Ride = it runs ungated and the sample rides in k_meet4d's launch, for the route memo (Gate when it cannot ride).
+enum class DecideMode { None, Gate, Ride };
+// The source-centric kernels (pgq_ball.h) at the head of the chain: Off; Decide = the device decides whether they take the
+// call; Always = they do (tests); Only = the chain is those kernels alone, the stage kernels are not launched behind them.
+enum class BallMode { Off, Decide, Always, Only };
+struct PrepassArgs {
+	int64_t n = 0;
+	const int64_t *d_src = nullptr, *d_dst = nullptr;
+	int64_t *d_out = nullptr;
+	MeetPathsOut *po = nullptr; // shortestpath: where the lists go
+	double meet_bytes = 0, edge_bytes = 0; // the byte rule's two sides (decision kernel, source-centric kernel)
+	DecideMode decide = DecideMode::None;
+	BallMode ball = BallMode::Off;
+};
+struct PrepassResult {
+	u32 n_open = 0;              // rows left in ws->open_src / open_dst / open_idx
+	bool answered = true;        // false: called off (decision, or BallMode::Only declined); nothing was written
+	bool ball_attempted = false; // the source-centric kernels were launched
+	bool ball_took = false;      // ... and took the call: the open rows are what they left
+	double est_sources = -1.0;   // distinct sources: the decision kernel's estimate, or the source runs the ball counted
+	int observed_go = -1;        // DecideMode::Ride: the sample's verdict (1 = the pre-pass pays), -1 when none was taken
+};
+int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult *r);
 // the pre-pass's sampled decision alone, waited for (*go: the pre-pass pays)
 int meet_decide_alone(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, double meet_bytes, double edge_bytes, bool *go);
 // iterativelengthbidirectional: every row through k_bibfs (forward CSR from src, transposed CSR from dst); rows over its
@@ -346,5 +367,103 @@ int prepare_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, co
 // bstart (pinned host) <- sorted-row boundaries of nb batches of L lanes (+ trivial / NULL tails)
 int batch_bounds(Workspace *ws, int64_t n, int64_t L, int nb);
 void merge_stats(pgq_stats_t &into, const pgq_stats_t &from); // a worker thread's counters into the caller's
+
+// ---- the BFS driver (pgq_route.hip picks the route, pgq_msbfs.hip runs the lane batches) ------------------------------
+// What a search_device call is asked for beside the lengths, and what it reports back.  with_paths: [src,e,v,...,dst]
+// lists go into the caller's child buffer (d_child_ext) or ws->child, with per-row offsets.
+struct SearchOutput {
+	int64_t child_used = 0;
+	bool want_te = false; // fill ws->ste with per-row traversed-edge counts
+	int depth = 0;        // nesting level of the straggler pass
+	bool deferred = false;
+	bool overflow = false; // the caller's child buffer was too small (lengths are still complete)
+	bool bidir = false;    // iterativelengthbidirectional: every row through the per-row bidirectional search first
+	bool from_meet = false; // these rows are what the pair-centric pre-pass left open: do not run it on them again
+	bool no_ball = false;   // these rows are what the source-centric kernel left open: the pre-pass may take them, that kernel not again
+	int ball_hint = -1;     // the caller has looked at the rows (chunk entry points: they sit in host memory): 0 = not grouped by source
+	// chunk entry points: the rows sit in a staging buffer whose address is the same for every chunk, so what the route memo
+	// remembers about "these buffers" says nothing about THESE rows (round-5 advisor finding: unrelated chunks hit the memo,
+	// and every change of shape was routed one call late) — such calls neither read nor write it
+	bool no_memo = false;
+	bool prefer_lanes = false; // (in) large grouped call on a graph where the lane batches measured faster than the source-centric route, or their trial
+	int route = 0;             // (out) 1: the source-centric kernel took the call (as it lay, or sorted by source)
+	double source_runs = -1;   // (out) ... and counted this many source runs
+};
+// every wait of the lane-batched search on its stream is counted (pgq_stats_t::host_waits)
+#define PGQ_WAIT(stream)                                                                                               \
+	do {                                                                                                               \
+		PGQ_TRY(wait_stream(stream, thread_wait_event()));                                                          \
+		tstats().s.host_waits++;                                                                                       \
+	} while (0)
+// A bigger buffer with the first `keep` bytes of the old one (waited for).
+int grow_keeping(DevBuf &buf, size_t bytes, size_t keep, hipStream_t st);
+// Answers n rows resident in device memory (d_src/d_dst, -1 src = NULL row) by whichever route pays: the per-row
+// bidirectional search, the source-centric kernel, the pair-centric pre-pass, the lane batches (pgq_route.hip).
+int search_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
+                  bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp);
+// The lane-batched MS-BFS (pgq_msbfs.hip): lane assignment, the batches, the straggler pass, results back to row order.
+// sampled: the route memo sent the rows here without the pre-pass (the sample rides in the lane assignment's first launch);
+// ahead_wd: the memo's width for stage 2 ahead of the wait (MemoVerdict; -1: not looked up yet).
+int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
+                 bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp,
+                 bool sampled, int ahead_wd, double meet_bytes, double edge_bytes);
+// The route memo (pgq_csr::RouteMemo): what it says about n rows on these buffers, and what a call records there
+// (fields left at -1 / false are not written; an empty outcome takes no lock).
+struct MemoVerdict {
+	int ball = -1, go = -1; // the source-centric kernels took (1) / declined (0) these buffers; the pre-pass (1) / lanes (0) took them
+	bool sorted = false;    // ... the source-centric kernels took them after a sort by source
+	int ahead_wd = -1;      // width of the last one-batch call of n rows whose rows stayed in place (0: none)
+};
+MemoVerdict memo_lookup(pgq_csr *c, int64_t n, const void *src, const void *dst);
+struct MemoOutcome {
+	int ball = -1, go = -1, sorted = -1; // ball_yes; go (the entry becomes these buffers, sorted_yes cleared); sorted_yes
+	bool go_again = false;               // go = 1: the sample of a call the memo sent to the lanes says the pre-pass pays again
+	int id_wd = -1;                      // the lanes' width and whether the rows stayed in place (id_n / id_wd)
+	bool in_place = false;
+};
+void memo_record(pgq_csr *c, int64_t n, const void *src, const void *dst, const MemoOutcome &o);
+
+// The rows a route left open (nd at src / dst), searched again one level deeper on a workspace of their own with the
+// caller's flags in `child`; S.pairs counts them once.  Lengths land in ws->def_len; with_paths: offsets in ws->def_off,
+// lists appended behind `base` elements of the caller's child buffer (d_child_ext, else ws->child grown to fit;
+// outp.overflow / outp.child_used as for the caller's own lists).  apply(lists appended) puts the results in place; the
+// stream is waited for before the inner workspace goes back when `wait` says so or lists were appended.
+template <typename Apply>
+int search_open_rows(pgq_csr *c, Workspace *ws, u32 nd, const int64_t *src, const int64_t *dst, SearchOutput child, SearchOutput &outp,
+                     bool with_paths, int64_t *d_child_ext, int64_t child_cap_ext, int64_t base, bool wait, Apply &&apply) {
+	hipStream_t st = ws->stream;
+	WorkspaceLease inner;
+	if (nd > 0) {
+		PGQ_TRY(ws->def_len.reserve((size_t)nd * 8));
+		if (with_paths) PGQ_TRY(ws->def_off.reserve((size_t)nd * 8));
+		PGQ_TRY(inner.acquire());
+		child.depth = outp.depth + 1;
+		tstats().s.pairs -= nd; // counted once
+		PGQ_TRY(search_device(c, inner.ws, nd, src, dst, ws->def_len.as<int64_t>(), with_paths, with_paths ? ws->def_off.as<int64_t>() : nullptr,
+		                      nullptr, 0, child));
+	}
+	bool lists = false;
+	if (with_paths) { // the open rows' lists land in the inner workspace's child buffer: appended behind the caller's
+		const int64_t need = base + child.child_used;
+		int64_t *d_child = d_child_ext;
+		if (d_child_ext) {
+			if (need > child_cap_ext) outp.overflow = true;
+		} else {
+			if ((size_t)need * 8 > ws->child.cap) PGQ_TRY(grow_keeping(ws->child, (size_t)need * 8, (size_t)base * 8, st));
+			d_child = ws->child.as<int64_t>();
+		}
+		lists = !outp.overflow; // (lengths are still reported when the lists did not fit)
+		if (lists && child.child_used > 0)
+			PGQ_HIP_TRY(hipMemcpyAsync(d_child + base, inner.ws->child.p, (size_t)child.child_used * 8, hipMemcpyDeviceToDevice, st));
+		outp.child_used = need;
+	}
+	if (nd == 0) return PGQ_OK;
+	PGQ_TRY(apply(lists));
+	if (wait || lists) {
+		PGQ_WAIT(st); // the inner workspace goes back to the pool after this
+		KernelTimer::flush();
+	}
+	return PGQ_OK;
+}
 
 } // namespace pgq

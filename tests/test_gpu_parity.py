@@ -17,7 +17,7 @@ def _defaults():
                  ("relax_small_limit", 2048), ("chain", 1), ("chain_cap", 4096), ("probe2", 1), ("probe2_abs", 512), ("lanes", 1), ("lanes_unroll", 2),
                  # the pair-centric pre-pass would answer most pairs of these small graphs before the level kernels
                  # under test see them; the tests that exercise it switch it on themselves
-                 ("meet", 0), ("meet_cap", 1 << 14), ("meet_cap_paths", 1 << 14), ("meet_cap_small", 1 << 14), ("meet_small_rows", 16384), ("meet_wide_rows", 2048), ("meet_wide_rows_always", 0), ("meet_spin_wait", 0), ("paths_reserve_mb", 1024), ("chunk_zero_copy", 1), ("meet_bias", 1.0), ("meet4", 1), ("meet4_cap", 1 << 20), ("meet4_lds_kb", 150),
+                 ("meet", 0), ("meet_cap", 1 << 14), ("meet_cap_paths", 1 << 14), ("meet_cap_small", 1 << 14), ("meet_small_rows", 16384), ("meet_wide_rows", 2048), ("meet_wide_rows_always", 0), ("meet_spin_wait", 0), ("paths_reserve_mb", 1024), ("chunk_zero_copy", 1), ("meet_bias", 1.0), ("meet4", 1), ("meet4_cap", 1 << 20), ("meet4_lds_kb", 150), ("meet4_global_mb", 256),
                  ("bibfs_rows", 256), ("bibfs_cap", 8 << 20), ("bibfs_queue", 1 << 17),
                  # the per-row weighted search would answer every int64 row before the relaxation kernels under test run
                  ("wbibfs", 0), ("wbibfs_cap", 64 << 20), ("wbibfs_queue", 1 << 17), ("wbibfs_far", 1 << 21), ("wbibfs_delta_div", 64), ("wbibfs_mem_mb", 2048),
@@ -1693,6 +1693,33 @@ def test_levels_enqueued_ahead_match_the_round_trip_loop():
         assert lens(ln, ok) == lens(o1, o2)
     # traversed-edge accounting and paths stay on the round-trip loop and still agree
     assert st.shortestpath(0, V, ps[:800], pd[:800]) == ora.lean_shortestpath(V, ps[:800], pd[:800])
+
+
+def test_source_centric_kernel_without_room_for_its_maps_leaves_the_chain_to_run_once():
+    # ball = 1 and rows grouped by source: the chunk entry point's hint asks for the source-centric kernels alone.  With no room
+    # for their vertex bit map (neither LDS nor the global budget) they are not attempted, and the stage chain that runs
+    # instead is the call's answer: not run a second time as if the kernels had declined.  Same answers and the same work as
+    # ball = 0 (the second of two calls under each setting: the handle's meet_far_rows decides whether k_bibfs runs).
+    rng = np.random.default_rng(67)
+    V, E = 20000, 400000
+    st, ora = both(V, random_graph(rng, V, E))
+    pgq.set_option("meet", 1)
+    pgq.set_option("meet4_lds_kb", 0)
+    pgq.set_option("meet4_global_mb", 0)
+    ps = np.repeat(rng.choice(V, 64, replace=False), 32)
+    pd = rng.integers(0, V, len(ps))
+    oln, ook = ora.lean_iterativelength(V, ps, pd, nthreads=4)
+    seen = {}
+    for ball in (1, 0):
+        pgq.set_option("ball", ball)
+        for rep in range(2):
+            pgq.reset_stats()
+            ln, ok = st.iterativelength(0, V, ps, pd)
+            assert lens(ln, ok) == [int(v) if k else None for v, k in zip(oln, ook)], (ball, rep)
+        stats = pgq.get_stats()
+        seen[ball] = {k: stats[k] for k in ("meet_pairs", "edges_scanned", "host_waits")}
+    assert seen[1] == seen[0], seen
+    assert seen[0]["meet_pairs"] > 0
 
 
 def test_route_memo_follows_the_rows():
