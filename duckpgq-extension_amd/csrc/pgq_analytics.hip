@@ -515,6 +515,33 @@ __global__ void k_pr_gather(int64_t n, const int64_t *__restrict__ src, int64_t 
 	out[i] = valid ? rank[s] : 0.0;
 }
 
+// the chunk entry points of the vertex functions: a handle of V vertices and the outputs when there are rows
+static int check_vertex_chunk(const pgq_csr_t *csr, int64_t V, int64_t n, const void *out, const uint64_t *out_valid) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
+	if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
+	if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+	return PGQ_OK;
+}
+static int check_vertex_table(const pgq_csr_t *csr) {
+	return csr ? PGQ_OK : fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
+}
+
+// One value per row from a table of V + 2 entries: the rows' ids (NULL -> -1) go to ws->in_src, gather(ids, values, ok)
+// launches the kernel that looks them up on ws->stream (ids outside the table -> NULL, payload 0), the values come back
+// with their validity.
+template <typename Gather>
+static int gather_rows(Workspace *ws, int64_t n, const pgq_vec_t &src, void *out, uint64_t *out_valid, Gather &&gather) {
+	std::vector<int64_t> ids((size_t)n);
+	flatten_ids(n, src, ids.data());
+	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
+	PGQ_TRY(ws->out_val.reserve((size_t)n * 8));
+	PGQ_TRY(ws->out_ok.reserve((size_t)n));
+	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
+	gather(ws->in_src.as<int64_t>(), ws->out_val.p, ws->out_ok.as<uint8_t>());
+	PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
+	return download_valid(ws, n, out, out_valid);
+}
+
 } // namespace pgq
 
 using namespace pgq;
@@ -522,129 +549,69 @@ using namespace pgq;
 extern "C" {
 
 int pgq_local_clustering_coefficient_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, float *d_out) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!d_src || !d_out))) return fail(PGQ_ERR_INVALID_ARG, "NULL device array");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	return lcc_device(csr, lease.ws, n, d_src, d_out);
+	return c_entry<false>(csr, [&] { return check_arrays(csr, n, d_src && d_out, "NULL device array"); },
+	                      [&](Workspace *ws) { return lcc_device(csr, ws, n, d_src, d_out); });
 }
 
 int pgq_local_clustering_coefficient(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, float *out, uint64_t *out_valid) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
-	if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-	if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-	if (n == 0) return PGQ_OK;
-	FlatPairs fp;
-	PGQ_TRY(flatten_pairs(V, n, src, src, fp, false)); // NULL rows come back as -1; out-of-range ids are rejected
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	Workspace *ws = lease.ws;
-	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_val.reserve((size_t)n * 4));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, fp.src.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	PGQ_TRY(lcc_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->out_val.as<float>()));
-	PGQ_TRY(staged_download(out, ws->out_val.p, (size_t)n * 4, ws->stream));
-	mask_fill_valid(out_valid, n);
-	for (int64_t i = 0; i < n; i++)
-		if (fp.src[i] < 0) mask_set_invalid(out_valid, i); // local_clustering_coefficient.cpp:39-41
-	return PGQ_OK;
+	auto check = [&] {
+		PGQ_TRY(check_vertex_chunk(csr, V, n, out, out_valid));
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	return c_entry<false>(csr, check, [&](Workspace *ws) -> int {
+		FlatPairs fp;
+		PGQ_TRY(flatten_pairs(V, n, src, src, fp, false)); // NULL rows come back as -1; out-of-range ids are rejected
+		PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
+		PGQ_TRY(ws->out_val.reserve((size_t)n * 4));
+		PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, fp.src.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
+		PGQ_TRY(lcc_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->out_val.as<float>()));
+		PGQ_TRY(staged_download(out, ws->out_val.p, (size_t)n * 4, ws->stream));
+		mask_fill_valid(out_valid, n);
+		for (int64_t i = 0; i < n; i++)
+			if (fp.src[i] < 0) mask_set_invalid(out_valid, i); // local_clustering_coefficient.cpp:39-41
+		return PGQ_OK;
+	});
 }
 
 int pgq_pagerank_device(pgq_csr_t *csr, double *d_rank, int *iterations) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	PGQ_TRY(pagerank_compute(csr, lease.ws));
-	if (d_rank) PGQ_HIP_TRY(hipMemcpy(d_rank, csr->pagerank, (size_t)(csr->V + 2) * 8, hipMemcpyDeviceToDevice));
-	if (iterations) *iterations = csr->pagerank_iterations;
-	return PGQ_OK;
+	return c_entry<false>(csr, [&] { return check_vertex_table(csr); }, [&](Workspace *ws) -> int {
+		PGQ_TRY(pagerank_compute(csr, ws));
+		if (d_rank) PGQ_HIP_TRY(hipMemcpy(d_rank, csr->pagerank, (size_t)(csr->V + 2) * 8, hipMemcpyDeviceToDevice));
+		if (iterations) *iterations = csr->pagerank_iterations;
+		return PGQ_OK;
+	});
 }
 
 int pgq_pagerank(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, double *out, uint64_t *out_valid) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
-	if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-	if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	Workspace *ws = lease.ws;
-	PGQ_TRY(pagerank_compute(csr, ws));
-	if (n == 0) return PGQ_OK;
-	// rows: NULL -> NULL; ids outside [0, V + 2) -> NULL (pagerank.cpp:93-104)
-	std::vector<int64_t> ids((size_t)n);
-	const int64_t *data = static_cast<const int64_t *>(src.data);
-	for (int64_t r = 0; r < n; r++) {
-		const int64_t p = src.sel ? (int64_t)src.sel[r] : r;
-		const bool valid = !src.validity || ((src.validity[p >> 6] >> (p & 63)) & 1ULL);
-		ids[(size_t)r] = valid ? data[p] : -1;
-	}
-	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_val.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_ok.reserve((size_t)n));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	hipLaunchKernelGGL(k_pr_gather, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ws->in_src.as<int64_t>(), V + 2,
-	                   csr->pagerank, ws->out_val.as<double>(), ws->out_ok.as<uint8_t>());
-	std::vector<uint8_t> ok((size_t)n);
-	PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
-	PGQ_TRY(staged_download(out, ws->out_val.p, (size_t)n * 8, ws->stream));
-	PGQ_TRY(staged_download(ok.data(), ws->out_ok.p, (size_t)n, ws->stream));
-	mask_fill_valid(out_valid, n);
-	for (int64_t i = 0; i < n; i++)
-		if (!ok[(size_t)i]) mask_set_invalid(out_valid, i);
-	return PGQ_OK;
+	return c_entry<false>(csr, [&] { return check_vertex_chunk(csr, V, n, out, out_valid); }, [&](Workspace *ws) -> int {
+		PGQ_TRY(pagerank_compute(csr, ws));
+		if (n == 0) return PGQ_OK;
+		// rows: NULL -> NULL; ids outside [0, V + 2) -> NULL (pagerank.cpp:93-104)
+		return gather_rows(ws, n, src, out, out_valid, [&](const int64_t *ids, void *val, uint8_t *ok) {
+			hipLaunchKernelGGL(k_pr_gather, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ids, V + 2, csr->pagerank,
+			                   static_cast<double *>(val), ok);
+		});
+	});
 }
 
 int pgq_weakly_connected_component_device(pgq_csr_t *csr, int64_t *d_ids) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	PGQ_TRY(wcc_compute(csr, lease.ws));
-	if (d_ids) PGQ_HIP_TRY(hipMemcpy(d_ids, csr->wcc, (size_t)(csr->V + 2) * 8, hipMemcpyDeviceToDevice));
-	return PGQ_OK;
+	return c_entry<false>(csr, [&] { return check_vertex_table(csr); }, [&](Workspace *ws) -> int {
+		PGQ_TRY(wcc_compute(csr, ws));
+		if (d_ids) PGQ_HIP_TRY(hipMemcpy(d_ids, csr->wcc, (size_t)(csr->V + 2) * 8, hipMemcpyDeviceToDevice));
+		return PGQ_OK;
+	});
 }
 
 int pgq_weakly_connected_component(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, int64_t *out, uint64_t *out_valid) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: CSR not found. Is the graph populated?");
-	if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-	if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	Workspace *ws = lease.ws;
-	PGQ_TRY(wcc_compute(csr, ws));
-	if (n == 0) return PGQ_OK;
-	// rows: NULL -> NULL; ids outside [0, V + 2) -> NULL (weakly_connected_component.cpp:94-100)
-	std::vector<int64_t> ids((size_t)n);
-	const int64_t *data = static_cast<const int64_t *>(src.data);
-	for (int64_t r = 0; r < n; r++) {
-		const int64_t p = src.sel ? (int64_t)src.sel[r] : r;
-		const bool valid = !src.validity || ((src.validity[p >> 6] >> (p & 63)) & 1ULL);
-		ids[(size_t)r] = valid ? data[p] : -1;
-	}
-	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_val.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_ok.reserve((size_t)n));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	hipLaunchKernelGGL(k_wcc_gather, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ws->in_src.as<int64_t>(), V + 2,
-	                   csr->wcc, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>());
-	std::vector<uint8_t> ok((size_t)n);
-	PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
-	PGQ_TRY(staged_download(out, ws->out_val.p, (size_t)n * 8, ws->stream));
-	PGQ_TRY(staged_download(ok.data(), ws->out_ok.p, (size_t)n, ws->stream));
-	mask_fill_valid(out_valid, n);
-	for (int64_t i = 0; i < n; i++)
-		if (!ok[(size_t)i]) mask_set_invalid(out_valid, i);
-	return PGQ_OK;
+	return c_entry<false>(csr, [&] { return check_vertex_chunk(csr, V, n, out, out_valid); }, [&](Workspace *ws) -> int {
+		PGQ_TRY(wcc_compute(csr, ws));
+		if (n == 0) return PGQ_OK;
+		// rows: NULL -> NULL; ids outside [0, V + 2) -> NULL (weakly_connected_component.cpp:94-100)
+		return gather_rows(ws, n, src, out, out_valid, [&](const int64_t *ids, void *val, uint8_t *ok) {
+			hipLaunchKernelGGL(k_wcc_gather, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ids, V + 2, csr->wcc,
+			                   static_cast<int64_t *>(val), ok);
+		});
+	});
 }
 
 } // extern "C"

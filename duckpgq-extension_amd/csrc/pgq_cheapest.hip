@@ -1871,40 +1871,8 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	} else {
 		std::vector<WorkspaceLease> leases((size_t)workers - 1);
 		for (auto &l : leases) PGQ_TRY(l.acquire());
-		std::vector<int> rcs((size_t)workers, PGQ_OK);
-		std::vector<std::string> errs((size_t)workers);
-		std::vector<pgq_stats_t> wstats((size_t)workers);
-		std::vector<std::shared_ptr<WorkerTask>> pool;
-		const int dev = current_device();
-		Options *const parent_opt = options_override();
-		for (int t = 1; t < workers; t++)
-			pool.push_back(worker_submit(dev, [&, t]() {
-				OptionScope opt_scope(parent_opt);
-				bind_thread_device(dev);
-				int r = ensure_init();
-				if (r == PGQ_OK) {
-					(void)pgq_reset_stats();
-					r = run_relax(leases[(size_t)t - 1].ws, t, workers);
-				}
-				rcs[(size_t)t] = r;
-				if (r != PGQ_OK) errs[(size_t)t] = pgq_last_error();
-				wstats[(size_t)t] = tstats().s;
-			}));
-		rcs[0] = run_relax(ws, 0, workers);
-		for (size_t k = 0; k < pool.size(); k++) { // a job that threw never wrote its return code: take the pool's word for it
-			const int wr = worker_wait(pool[k]);
-			if (wr != PGQ_OK) {
-				rcs[k + 1] = wr;
-				errs[k + 1] = pgq_last_error();
-			}
-		}
-		for (int t = 0; t < workers; t++) {
-			if (rcs[(size_t)t] != PGQ_OK && rc == PGQ_OK) {
-				rc = rcs[(size_t)t];
-				if (t > 0) set_error(errs[(size_t)t]);
-			}
-			if (t > 0) merge_stats(S, wstats[(size_t)t]);
-		}
+		rc = fan_out(std::vector<int>((size_t)workers, current_device()),
+		             [&](int t) { return run_relax(t == 0 ? ws : leases[(size_t)t - 1].ws, t, workers); });
 	}
 	if (rc != PGQ_OK) return rc;
 	const int64_t lo_t = bs[nb + 1], lo_n = bs[nb + 2];
@@ -1933,55 +1901,40 @@ extern "C" {
 
 int pgq_cheapest_path_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                          void *d_out, uint8_t *d_out_valid) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	PGQ_TRY(check_weighted(csr));
-	if (n < 0 || (n > 0 && (!d_src || !d_dst || !d_out || !d_out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL device array");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	if (csr->w_type == PGQ_W_INT64)
-		return cheapest_device<int64_t>(csr, lease.ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true);
-	return cheapest_device<double>(csr, lease.ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true);
+	const bool arrays = d_src && d_dst && d_out && d_out_valid;
+	auto check = [&] {
+		PGQ_TRY(check_weighted(csr));
+		return check_arrays(csr, n, arrays, "NULL device array");
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) {
+		if (csr->w_type == PGQ_W_INT64)
+			return cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true);
+		return cheapest_device<double>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true);
+	});
 }
 
 int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
                              uint64_t *out_valid) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	PGQ_TRY(check_weighted(csr));
-	if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-	if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-	if (n == 0) return PGQ_OK;
-	FlatPairs fp;
-	PGQ_TRY(flatten_pairs(V, n, src, dst, fp, true));
-	for (int64_t i = 0; i < n; i++)
-		if (!fp.dst_valid[i]) fp.src[i] = -1; // NULL dst -> NULL (cheapest_path_length.cpp:74-76)
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	Workspace *ws = lease.ws;
-	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
-	PGQ_TRY(ws->in_dst.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_val.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_ok.reserve((size_t)n));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, fp.src.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_dst.p, fp.dst.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	int rc;
-	if (csr->w_type == PGQ_W_INT64)
-		rc = cheapest_device<int64_t>(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(),
-		                              ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true);
-	else
-		rc = cheapest_device<double>(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(),
-		                             ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true);
-	PGQ_TRY(rc);
-	std::vector<uint8_t> ok(n);
-	PGQ_TRY(staged_download(out, ws->out_val.p, (size_t)n * 8, ws->stream));
-	PGQ_TRY(staged_download(ok.data(), ws->out_ok.p, (size_t)n, ws->stream));
-	mask_fill_valid(out_valid, n);
-	for (int64_t i = 0; i < n; i++)
-		if (!ok[i]) mask_set_invalid(out_valid, i);
-	return PGQ_OK;
+	auto check = [&] {
+		PGQ_TRY(check_weighted(csr));
+		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
+		if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		FlatPairs fp;
+		PGQ_TRY(flatten_pairs(V, n, src, dst, fp, true));
+		for (int64_t i = 0; i < n; i++)
+			if (!fp.dst_valid[i]) fp.src[i] = -1; // NULL dst -> NULL (cheapest_path_length.cpp:74-76)
+		PGQ_TRY(ws->out_val.reserve((size_t)n * 8));
+		PGQ_TRY(ws->out_ok.reserve((size_t)n));
+		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
+		const int64_t *d_src = ws->in_src.as<int64_t>(), *d_dst = ws->in_dst.as<int64_t>();
+		PGQ_TRY(csr->w_type == PGQ_W_INT64
+		            ? cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true)
+		            : cheapest_device<double>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true));
+		return download_valid(ws, n, out, out_valid);
+	});
 }
 
 } // extern "C"

@@ -190,6 +190,11 @@ Options &options();
 struct WorkerTask;
 std::shared_ptr<WorkerTask> worker_submit(int device, std::function<void()> fn);
 int worker_wait(const std::shared_ptr<WorkerTask> &t); // PGQ_OK, or the error of a job that threw (its results are missing)
+// One call on several host threads: body(k) for k = 0 on the calling thread and for k >= 1 on pool workers, thread k bound
+// to devices[k] (at least one entry) under the caller's options, ensure_init done.  Workers start from reset statistics,
+// which are added to the caller's afterwards.  Returns the first failing code in worker order, with that worker's message
+// as the last error (a job that threw failed); the calling thread's device binding is left as it was.
+int fan_out(const std::vector<int> &devices, const std::function<int(int)> &body);
 Options *options_override();
 void set_options_override(Options *o);
 
@@ -373,6 +378,9 @@ int flatten_pairs(int64_t V, int64_t n, const pgq_vec_t &src, const pgq_vec_t &d
                   bool check_dst_validity);
 
 int flatten_pairs_into(int64_t V, int64_t n, const pgq_vec_t &src, const pgq_vec_t &dst, int64_t *out_src, int64_t *out_dst);
+// one id column (pagerank, weakly_connected_component): NULL rows -> -1, ids passed on unchecked (the kernels that read them
+// answer ids outside their table with NULL)
+void flatten_ids(int64_t n, const pgq_vec_t &src, int64_t *out);
 
 inline void mask_fill_valid(uint64_t *mask, int64_t n) {
 	for (int64_t i = 0; i < (n + 63) / 64; i++) mask[i] = ~0ULL;
@@ -394,7 +402,7 @@ struct KernelTimer {
 int dev_alloc(void **out, size_t bytes);
 void dev_free(void *p);
 void dev_cache_trim();
-void drop_idle_workspaces(); // frees the pooled (not leased) per-call workspaces (pgq_msbfs.hip)
+void drop_idle_workspaces(); // frees the pooled (not leased) per-call workspaces (pgq_runtime.hip)
 template <typename T> inline int dev_alloc_as(T **out, size_t count) {
 	void *p = nullptr;
 	int rc = dev_alloc(&p, count * sizeof(T));

@@ -1587,81 +1587,6 @@ __global__ void k_trivial_paths(int64_t lo, int64_t hi, const int32_t *__restric
 	child[base_off + (i - lo)] = ssrc[i];
 }
 
-// ---- workspace ---------------------------------------------------------------------------------------------------
-
-Workspace::~Workspace() {
-	if (ev_block) (void)hipEventDestroy(ev_block);
-	if (stream) (void)hipStreamDestroy(stream);
-	if (h_cnt) (void)hipHostFree(h_cnt);
-	if (h_bi) (void)hipHostFree(h_bi);
-	if (h_log) (void)hipHostFree(h_log);
-	if (h_meet) (void)hipHostFree(h_meet);
-	if (h_io) (void)hipHostFree(h_io);
-	if (h_bstart) (void)hipHostFree(h_bstart);
-	for (DevBuf *b : { &seen, &qbuf[0], &qbuf[1], &qflag, &counters, &flag, &rank, &usrc, &key, &idx, &skey,
-	                   &sidx, &ssrc, &sdst, &sres, &soff, &sort_tmp, &scan_tmp, &bstart, &levels_tab, &child, &in_src,
-	                   &in_dst, &out_len, &out_off, &dist, &dirty[0], &dirty[1], &touched, &tflag, &out_val, &out_ok, &lane_sums, &ste, &def_src, &def_dst, &def_len,
-	                   &def_idx, &def_off, &def_ent, &cbits, &cbbase, &cmeta, &cwords, &lblk, &lrec, &meet_cnt, &meet_rec, &meet_poff, &meet_maps, &meet_trace,
-	                   &wb_scratch, &hv, &hmask, &hstart, &hmap, &route_dec, &ball_segs, &ball_trace, &sort_src, &sort_dst, &sort_out, &dist_b, &dirty_b[0], &dirty_b[1], &qbuf_b[0], &qbuf_b[1],
-	                   &touched_b, &tflag_b, &bi_block, &dpart })
-		b->release();
-	for (auto *v : { &levels, &pool })
-		for (auto &l : *v) {
-			l->buf.release();
-			l->nz.release();
-		}
-}
-
-static std::mutex g_ws_lock;
-static std::vector<Workspace *> g_ws_free; // every workspace remembers the device its buffers live on
-
-void drop_idle_workspaces() { // of the calling thread's device: another device's pool does not help an allocation here
-	std::vector<Workspace *> drop;
-	{
-		std::lock_guard<std::mutex> g(g_ws_lock);
-		const int dev = current_device();
-		for (size_t k = g_ws_free.size(); k-- > 0;)
-			if (g_ws_free[k]->device == dev) {
-				drop.push_back(g_ws_free[k]);
-				g_ws_free.erase(g_ws_free.begin() + (long)k);
-			}
-	}
-	for (Workspace *w : drop) delete w;
-}
-
-int WorkspaceLease::acquire() {
-	{
-		std::lock_guard<std::mutex> g(g_ws_lock);
-		const int dev = current_device();
-		for (size_t k = g_ws_free.size(); k-- > 0;)
-			if (g_ws_free[k]->device == dev) {
-				ws = g_ws_free[k];
-				g_ws_free.erase(g_ws_free.begin() + (long)k);
-				break;
-			}
-	}
-	if (!ws) {
-		ws = new Workspace();
-		ws->device = current_device();
-		// a half-built workspace never reaches the pool
-		if (hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking) != hipSuccess ||
-		    hipHostMalloc((void **)&ws->h_cnt, sizeof(Counters)) != hipSuccess ||
-		    hipHostMalloc((void **)&ws->h_log, sizeof(LevelLog) * (kSpecLevels + 3)) != hipSuccess ||
-		    hipHostMalloc(&ws->h_meet, 8192) != hipSuccess) {
-			delete ws;
-			ws = nullptr;
-			return fail(PGQ_ERR_HIP, "cannot create a search workspace (stream / pinned counter block)");
-		}
-	}
-	return PGQ_OK;
-}
-WorkspaceLease::~WorkspaceLease() {
-	if (!ws) return;
-	std::lock_guard<std::mutex> g(g_ws_lock);
-	if (g_ws_free.size() < 8 * std::max<size_t>(1, enabled_devices().size())) g_ws_free.push_back(ws);
-	else delete ws;
-}
-
 // ---- lane assignment (host side) ------------------------------------------------------------------------------------
 // Stage 1: flag the distinct sources of the rows that need a search, rank them (= global lane ids), list them; the number
 // of distinct sources and the range check come back with ONE wait.
@@ -2456,28 +2381,6 @@ static int run_batches(pgq_csr *c, Workspace *sh, Workspace *ws, int b0, int bst
 	return PGQ_OK;
 }
 
-void merge_stats(pgq_stats_t &into, const pgq_stats_t &from) {
-	into.batches += from.batches;
-	into.levels += from.levels;
-	into.push_levels += from.push_levels;
-	into.pull_levels += from.pull_levels;
-	into.edges_scanned += from.edges_scanned;
-	into.word_gathers += from.word_gathers;
-	into.frontier_vertices += from.frontier_vertices;
-	into.deferred_pairs += from.deferred_pairs;
-	into.spec_batches += from.spec_batches;
-	into.spec_levels += from.spec_levels;
-	into.spec_aborts += from.spec_aborts;
-	into.host_waits += from.host_waits;
-	into.ball_segments += from.ball_segments;
-	into.ball_calls += from.ball_calls;
-	for (int k = 0; k < PGQ_KCLASS_MAX; k++) {
-		into.algo_bytes[k] += from.algo_bytes[k];
-		into.kernel_ms[k] += from.kernel_ms[k];
-		into.launches[k] += from.launches[k];
-	}
-}
-
 int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
                  bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp,
                  bool sampled, int ahead_wd, double meet_bytes, double edge_bytes) {
@@ -2551,42 +2454,10 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	} else {
 		std::vector<WorkspaceLease> leases((size_t)workers - 1);
 		for (auto &l : leases) PGQ_TRY(l.acquire());
-		std::vector<int> rcs((size_t)workers, PGQ_OK);
-		std::vector<std::string> errs((size_t)workers);
 		std::vector<SearchOutput> outs((size_t)workers, outp);
-		std::vector<pgq_stats_t> wstats((size_t)workers);
-		std::vector<std::shared_ptr<WorkerTask>> pool;
-		const int dev = current_device();
-		Options *const parent_opt = options_override();
-		for (int t = 1; t < workers; t++)
-			pool.push_back(worker_submit(dev, [&, t]() {
-				OptionScope opt_scope(parent_opt); // the handle's own options, if the call runs under them
-				bind_thread_device(dev); // the caller's device (a multi-GPU shard may not be on the default one)
-				int r = ensure_init(); // binds the device for this host thread
-				if (r == PGQ_OK) {
-					(void)pgq_reset_stats();
-					r = run(leases[(size_t)t - 1].ws, t, workers, outs[(size_t)t]);
-				}
-				rcs[(size_t)t] = r;
-				if (r != PGQ_OK) errs[(size_t)t] = pgq_last_error();
-				wstats[(size_t)t] = tstats().s;
-			}));
-		rcs[0] = run(ws, 0, workers, outs[0]);
-		for (size_t k = 0; k < pool.size(); k++) { // a job that threw never wrote its return code: take the pool's word for it
-			const int wr = worker_wait(pool[k]);
-			if (wr != PGQ_OK) {
-				rcs[k + 1] = wr;
-				errs[k + 1] = pgq_last_error();
-			}
-		}
-		for (int t = 0; t < workers; t++) {
-			if (rcs[(size_t)t] != PGQ_OK && rc == PGQ_OK) {
-				rc = rcs[(size_t)t];
-				if (t > 0) set_error(errs[(size_t)t]);
-			}
-			outp.deferred = outp.deferred || outs[(size_t)t].deferred;
-			if (t > 0) merge_stats(S, wstats[(size_t)t]);
-		}
+		rc = fan_out(std::vector<int>((size_t)workers, current_device()),
+		             [&](int t) { return run(t == 0 ? ws : leases[(size_t)t - 1].ws, t, workers, outs[(size_t)t]); });
+		for (const SearchOutput &o : outs) outp.deferred = outp.deferred || o.deferred;
 	}
 	if (rc == PGQ_OK && outp.deferred) {
 		// second, narrow pass over the stragglers

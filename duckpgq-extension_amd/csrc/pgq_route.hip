@@ -447,47 +447,13 @@ static int run_shards(pgq_csr_t *csr, int64_t n, Body body) {
 		if (!replicas[(size_t)k] || replicas[(size_t)k]->device != devs[(size_t)k])
 			return fail(PGQ_ERR_INVALID_ARG, "CSR replica on the wrong device");
 	const int64_t per = (n + W - 1) / W;
-	std::vector<int> rcs((size_t)W, PGQ_OK);
-	std::vector<std::string> errs((size_t)W);
-	std::vector<pgq_stats_t> wstats((size_t)W);
-	auto shard = [&](int k) -> int {
+	return fan_out(devs, [&](int k) -> int {
 		const int64_t lo = std::min<int64_t>((int64_t)k * per, n), hi = std::min<int64_t>(lo + per, n);
 		if (hi == lo) return PGQ_OK;
-		bind_thread_device(devs[(size_t)k]);
-		PGQ_TRY(ensure_init());
 		WorkspaceLease lease;
 		PGQ_TRY(lease.acquire());
 		return body(k, lo, hi, replicas[(size_t)k], lease.ws);
-	};
-	std::vector<std::shared_ptr<WorkerTask>> pool;
-	Options *const parent_opt = options_override();
-	for (int k = 1; k < W; k++)
-		pool.push_back(worker_submit(devs[(size_t)k], [&, k]() {
-			OptionScope opt_scope(parent_opt);
-			(void)pgq_reset_stats();
-			rcs[(size_t)k] = shard(k);
-			if (rcs[(size_t)k] != PGQ_OK) errs[(size_t)k] = pgq_last_error();
-			wstats[(size_t)k] = tstats().s;
-		}));
-	rcs[0] = shard(0);
-	bind_thread_device(-1);
-	(void)ensure_init();
-	for (size_t k = 0; k < pool.size(); k++) { // a job that threw never wrote its return code: take the pool's word for it
-		const int wr = worker_wait(pool[k]);
-		if (wr != PGQ_OK) {
-			rcs[k + 1] = wr;
-			errs[k + 1] = pgq_last_error();
-		}
-	}
-	int rc = PGQ_OK;
-	for (int k = 0; k < W; k++) {
-		if (rcs[(size_t)k] != PGQ_OK && rc == PGQ_OK) {
-			rc = rcs[(size_t)k];
-			if (k > 0) set_error(errs[(size_t)k]);
-		}
-		if (k > 0) merge_stats(tstats().s, wstats[(size_t)k]);
-	}
-	return rc;
+	});
 }
 
 extern "C" {
@@ -506,62 +472,47 @@ int pgq_release_cached_memory(void) {
 
 static int iterativelength_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
                                 bool bidir) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!d_src || !d_dst || !d_out_len))) return fail(PGQ_ERR_INVALID_ARG, "NULL device array");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	SearchOutput so;
-	so.bidir = bidir;
-	return search_device(csr, lease.ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so);
+	const bool arrays = d_src && d_dst && d_out_len;
+	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) {
+		SearchOutput so;
+		so.bidir = bidir;
+		return search_device(csr, ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so);
+	});
 }
 int pgq_iterativelength_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                     int64_t *d_out_len) {
-	OptionScope opt_scope(csr);
 	return iterativelength_bulk(csr, n, d_src, d_dst, d_out_len, false);
 }
 int pgq_iterativelength_bidirectional_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                                   int64_t *d_out_len) {
-	OptionScope opt_scope(csr);
 	return iterativelength_bulk(csr, n, d_src, d_dst, d_out_len, true);
 }
 int pgq_traversed_edges_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                     int64_t *d_out_len, int64_t *d_out_te) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!d_src || !d_dst || !d_out_len || !d_out_te))) return fail(PGQ_ERR_INVALID_ARG, "NULL device array");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	SearchOutput so;
-	so.want_te = true;
-	PGQ_TRY(search_device(csr, lease.ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so));
-	if (n > 0) {
-		hipLaunchKernelGGL(k_scatter_te, dim3(blocks_for(n)), dim3(256), 0, lease.ws->stream, n, lease.ws->sidx.as<u32>(),
-		                   lease.ws->ste.as<int64_t>(), d_out_te);
-		PGQ_HIP_TRY(hipStreamSynchronize(lease.ws->stream));
-	}
-	return PGQ_OK;
+	const bool arrays = d_src && d_dst && d_out_len && d_out_te;
+	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) -> int {
+		SearchOutput so;
+		so.want_te = true;
+		PGQ_TRY(search_device(csr, ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so));
+		if (n > 0) {
+			hipLaunchKernelGGL(k_scatter_te, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ws->sidx.as<u32>(),
+			                   ws->ste.as<int64_t>(), d_out_te);
+			PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
+		}
+		return PGQ_OK;
+	});
 }
 
 int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                  int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
                                  int64_t *child_used) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!d_src || !d_dst || !d_out_len || !d_out_offset || !d_child)))
-		return fail(PGQ_ERR_INVALID_ARG, "NULL device array");
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	SearchOutput so;
-	int rc = search_device(csr, lease.ws, n, d_src, d_dst, d_out_len, true, d_out_offset, d_child, child_cap, so);
-	if (child_used) *child_used = so.child_used;
-	return rc;
+	const bool arrays = d_src && d_dst && d_out_len && d_out_offset && d_child;
+	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) {
+		SearchOutput so;
+		int rc = search_device(csr, ws, n, d_src, d_dst, d_out_len, true, d_out_offset, d_child, child_cap, so);
+		if (child_used) *child_used = so.child_used;
+		return rc;
+	});
 }
 
 // Multi-GPU inside one process (the single DuckDB process the boundary targets): rows are cut into contiguous shards,
@@ -569,23 +520,20 @@ int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src
 // the CSR, and the results land in the caller's host array (the gather).  No collective inside the search
 // (results are a pure function of (CSR, src, dst)).
 int pgq_iterativelength_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t *out_len) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!src || !dst || !out_len))) return fail(PGQ_ERR_INVALID_ARG, "NULL array");
-	if (n == 0) return PGQ_OK;
-	return run_shards(csr, n, [&](int, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
+	auto check = [&] {
+		PGQ_TRY(check_arrays(csr, n, src && dst && out_len, "NULL array"));
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	auto shard = [&](int, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
 		const size_t bytes = (size_t)(hi - lo) * 8;
-		PGQ_TRY(ws->in_src.reserve(bytes));
-		PGQ_TRY(ws->in_dst.reserve(bytes));
 		PGQ_TRY(ws->out_len.reserve(bytes));
-		PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, src + lo, bytes, hipMemcpyHostToDevice, ws->stream));
-		PGQ_HIP_TRY(hipMemcpyAsync(ws->in_dst.p, dst + lo, bytes, hipMemcpyHostToDevice, ws->stream));
+		PGQ_TRY(stage_pairs(ws, hi - lo, src + lo, dst + lo));
 		SearchOutput so;
 		PGQ_TRY(search_device(replica, ws, hi - lo, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(),
 		                      ws->out_len.as<int64_t>(), false, nullptr, nullptr, 0, so));
 		return staged_download(out_len + lo, ws->out_len.p, bytes, ws->stream);
-	});
+	};
+	return c_entry<false>(csr, check, [&] { return run_shards(csr, n, shard); });
 }
 
 // shortestpath on all enabled devices: every shard writes its lists into its own device buffer (grown once if the first
@@ -593,25 +541,20 @@ int pgq_iterativelength_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, con
 // the preceding shards' sizes — the gather of the ragged [v,e,v,...] lists.
 int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t *out_len,
                            int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!src || !dst || !out_len || !out_offset)) || child_cap < 0 || (child_cap > 0 && !child))
-		return fail(PGQ_ERR_INVALID_ARG, "NULL array");
-	if (child_used) *child_used = 0;
-	if (n == 0) return PGQ_OK;
-	const size_t W = enabled_devices().size();
-	std::vector<std::vector<int64_t>> payload(W);
-	std::vector<int64_t> shard_lo(W, 0), shard_hi(W, 0);
-	PGQ_TRY(run_shards(csr, n, [&](int k, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
+	auto check = [&] {
+		PGQ_TRY(check_arrays(csr, n, src && dst && out_len && out_offset, "NULL array"));
+		if (child_cap < 0 || (child_cap > 0 && !child)) return fail(PGQ_ERR_INVALID_ARG, "NULL array");
+		if (child_used) *child_used = 0;
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	std::vector<std::vector<int64_t>> payload;
+	std::vector<int64_t> shard_lo, shard_hi;
+	auto shard = [&](int k, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
 		const int64_t m = hi - lo;
 		const size_t bytes = (size_t)m * 8;
-		PGQ_TRY(ws->in_src.reserve(bytes));
-		PGQ_TRY(ws->in_dst.reserve(bytes));
 		PGQ_TRY(ws->out_len.reserve(bytes));
 		PGQ_TRY(ws->out_off.reserve(bytes));
-		PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, src + lo, bytes, hipMemcpyHostToDevice, ws->stream));
-		PGQ_HIP_TRY(hipMemcpyAsync(ws->in_dst.p, dst + lo, bytes, hipMemcpyHostToDevice, ws->stream));
+		PGQ_TRY(stage_pairs(ws, m, src + lo, dst + lo));
 		DevBuf dchild; // not a workspace buffer: search_device uses ws->child for its own staging
 		int64_t cap = std::max<int64_t>(16 * m, 1024), used = 0;
 		int rc = PGQ_OK;
@@ -635,32 +578,38 @@ int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const 
 		shard_hi[(size_t)k] = hi;
 		dchild.release();
 		return rc;
-	}));
-	int64_t total = 0;
-	for (size_t k = 0; k < W; k++) total += (int64_t)payload[k].size();
-	if (child_used) *child_used = total;
-	if (total > child_cap) return fail(PGQ_ERR_INVALID_ARG, "child buffer too small for the path lists (see *child_used)");
-	int64_t base = 0;
-	for (size_t k = 0; k < W; k++) {
-		if (!payload[k].empty()) memcpy(child + base, payload[k].data(), payload[k].size() * 8);
-		if (base)
-			for (int64_t i = shard_lo[k]; i < shard_hi[k]; i++)
-				if (out_len[i] >= 0) out_offset[i] += base;
-		base += (int64_t)payload[k].size();
-	}
-	return PGQ_OK;
+	};
+	return c_entry<false>(csr, check, [&]() -> int {
+		const size_t W = enabled_devices().size();
+		payload.resize(W);
+		shard_lo.assign(W, 0);
+		shard_hi.assign(W, 0);
+		PGQ_TRY(run_shards(csr, n, shard));
+		int64_t total = 0;
+		for (size_t k = 0; k < W; k++) total += (int64_t)payload[k].size();
+		if (child_used) *child_used = total;
+		if (total > child_cap) return fail(PGQ_ERR_INVALID_ARG, "child buffer too small for the path lists (see *child_used)");
+		int64_t base = 0;
+		for (size_t k = 0; k < W; k++) {
+			if (!payload[k].empty()) memcpy(child + base, payload[k].data(), payload[k].size() * 8);
+			if (base)
+				for (int64_t i = shard_lo[k]; i < shard_hi[k]; i++)
+					if (out_len[i] >= 0) out_offset[i] += base;
+			base += (int64_t)payload[k].size();
+		}
+		return PGQ_OK;
+	});
 }
 
 // cheapest_path_length on all enabled devices: out = n values (int64 or double by the CSR's weight type), out_valid = n
 // bytes (1 = a path exists)
 int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, void *out,
                                    uint8_t *out_valid) {
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (n < 0 || (n > 0 && (!src || !dst || !out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL array");
-	if (n == 0) return PGQ_OK;
-	return run_shards(csr, n, [&](int, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
+	auto check = [&] {
+		PGQ_TRY(check_arrays(csr, n, src && dst && out && out_valid, "NULL array"));
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	auto shard = [&](int, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
 		const int64_t m = hi - lo;
 		const size_t bytes = (size_t)m * 8;
 		DevBuf d_src, d_dst, d_val, d_ok; // the bulk entry point leases its own workspace
@@ -679,7 +628,8 @@ int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src
 		if (rc == PGQ_OK) rc = staged_download(out_valid + lo, d_ok.p, (size_t)m, ws->stream);
 		for (DevBuf *b : { &d_src, &d_dst, &d_val, &d_ok }) b->release();
 		return rc;
-	});
+	};
+	return c_entry<false>(csr, check, [&] { return run_shards(csr, n, shard); });
 }
 
 // pinned, device-addressable staging block of a workspace (grown on demand)
@@ -699,120 +649,108 @@ static int io_block(Workspace *ws, size_t bytes, void **host, void **dev) {
 
 static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
                                  uint64_t *out_valid, bool bidir) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	PGQ_TRY(check_csr(csr, V));
-	if (n < 0 || (n > 0 && (!out_len || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-	if (n == 0) return PGQ_OK;
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	Workspace *ws = lease.ws;
-	if (!bidir && options().chunk_zero_copy && prepass_takes(csr, n, SearchOutput()) && n <= kMeetDecideRows) {
-		// One DuckDB chunk through the pair-centric kernels: they read the rows straight out of a pinned staging block and
-		// write the hop counts straight back into it (2048 rows = 32 KB in, 16 KB out over PCIe, one access per row), so the
-		// call is two or three kernel launches and ONE wait — no copy commands (each is a stream operation of its own:
-		// two in, two out cost more than the search of a chunk).
-		void *hp = nullptr, *dp = nullptr;
-		PGQ_TRY(io_block(ws, (size_t)n * 24, &hp, &dp));
-		int64_t *h = static_cast<int64_t *>(hp), *d = static_cast<int64_t *>(dp);
-		PGQ_TRY(flatten_pairs_into(V, n, src, dst, h, h + n));
-		SearchOutput so;
-		so.no_memo = true;
-		{ // the rows are in host memory: whether they are grouped by source costs a pass over 2048 words here, two launches there
-			int64_t runs = 1;
-			for (int64_t i = 1; i < n; i++) runs += h[i] != h[i - 1];
-			so.ball_hint = runs * 8 <= n ? 1 : 0;
-		}
-		PGQ_TRY(search_device(csr, ws, n, d, d + n, d + 2 * n, false, nullptr, nullptr, 0, so));
-		const int64_t *res = h + 2 * n;
-		for (int64_t w = 0; w < (n + 63) / 64; w++) { // payload of a NULL row stays -1 like iterativelength.cpp:100,137
-			uint64_t m = 0;
-			const int64_t lo = w * 64, cnt = std::min<int64_t>(64, n - lo);
-			for (int64_t k = 0; k < cnt; k++) {
-				const int64_t v = res[lo + k];
-				out_len[lo + k] = v;
-				m |= (uint64_t)(v >= 0) << k;
+	auto check = [&] {
+		PGQ_TRY(check_csr(csr, V));
+		if (n < 0 || (n > 0 && (!out_len || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		if (!bidir && options().chunk_zero_copy && prepass_takes(csr, n, SearchOutput()) && n <= kMeetDecideRows) {
+			// One DuckDB chunk through the pair-centric kernels: they read the rows straight out of a pinned staging block and
+			// write the hop counts straight back into it (2048 rows = 32 KB in, 16 KB out over PCIe, one access per row), so the
+			// call is two or three kernel launches and ONE wait — no copy commands (each is a stream operation of its own:
+			// two in, two out cost more than the search of a chunk).
+			void *hp = nullptr, *dp = nullptr;
+			PGQ_TRY(io_block(ws, (size_t)n * 24, &hp, &dp));
+			int64_t *h = static_cast<int64_t *>(hp), *d = static_cast<int64_t *>(dp);
+			PGQ_TRY(flatten_pairs_into(V, n, src, dst, h, h + n));
+			SearchOutput so;
+			so.no_memo = true;
+			{ // the rows are in host memory: whether they are grouped by source costs a pass over 2048 words here, two launches there
+				int64_t runs = 1;
+				for (int64_t i = 1; i < n; i++) runs += h[i] != h[i - 1];
+				so.ball_hint = runs * 8 <= n ? 1 : 0;
 			}
-			out_valid[w] = cnt == 64 ? m : (m | (~0ULL << cnt)); // bits past n stay set, as mask_fill_valid leaves them
+			PGQ_TRY(search_device(csr, ws, n, d, d + n, d + 2 * n, false, nullptr, nullptr, 0, so));
+			const int64_t *res = h + 2 * n;
+			for (int64_t w = 0; w < (n + 63) / 64; w++) { // payload of a NULL row stays -1 like iterativelength.cpp:100,137
+				uint64_t m = 0;
+				const int64_t lo = w * 64, cnt = std::min<int64_t>(64, n - lo);
+				for (int64_t k = 0; k < cnt; k++) {
+					const int64_t v = res[lo + k];
+					out_len[lo + k] = v;
+					m |= (uint64_t)(v >= 0) << k;
+				}
+				out_valid[w] = cnt == 64 ? m : (m | (~0ULL << cnt)); // bits past n stay set, as mask_fill_valid leaves them
+			}
+			return PGQ_OK;
 		}
+		FlatPairs fp;
+		PGQ_TRY(flatten_pairs(V, n, src, dst, fp, false));
+		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
+		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
+		SearchOutput so;
+		so.bidir = bidir;
+		so.no_memo = true;
+		PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
+		                      false, nullptr, nullptr, 0, so));
+		PGQ_TRY(staged_download(out_len, ws->out_len.p, (size_t)n * 8, ws->stream));
+		mask_fill_valid(out_valid, n);
+		for (int64_t i = 0; i < n; i++)
+			if (out_len[i] < 0) mask_set_invalid(out_valid, i); // payload stays -1 like iterativelength.cpp:100,137
 		return PGQ_OK;
-	}
-	FlatPairs fp;
-	PGQ_TRY(flatten_pairs(V, n, src, dst, fp, false));
-	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
-	PGQ_TRY(ws->in_dst.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, fp.src.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_dst.p, fp.dst.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	SearchOutput so;
-	so.bidir = bidir;
-	so.no_memo = true;
-	PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
-	                      false, nullptr, nullptr, 0, so));
-	PGQ_TRY(staged_download(out_len, ws->out_len.p, (size_t)n * 8, ws->stream));
-	mask_fill_valid(out_valid, n);
-	for (int64_t i = 0; i < n; i++)
-		if (out_len[i] < 0) mask_set_invalid(out_valid, i); // payload stays -1 like iterativelength.cpp:100,137
-	return PGQ_OK;
+	});
 }
 int pgq_iterativelength(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
                         uint64_t *out_valid) {
-	OptionScope opt_scope(csr);
 	return iterativelength_chunk(csr, V, n, src, dst, out_len, out_valid, false);
 }
 int pgq_iterativelength_bidirectional(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
                                       uint64_t *out_valid) {
-	OptionScope opt_scope(csr);
 	return iterativelength_chunk(csr, V, n, src, dst, out_len, out_valid, true);
 }
 
 int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
                      uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
-	CallScope in_flight;
-	OptionScope opt_scope(csr);
-	PGQ_TRY(ensure_init());
-	PGQ_TRY(check_csr(csr, V));
-	if (n < 0 || (n > 0 && (!out_offset || !out_length || !out_valid)) || !out_child || !out_child_len)
-		return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-	*out_child = nullptr;
-	*out_child_len = 0;
-	if (n == 0) return PGQ_OK;
-	FlatPairs fp;
-	PGQ_TRY(flatten_pairs(V, n, src, dst, fp, false));
-	WorkspaceLease lease;
-	PGQ_TRY(lease.acquire());
-	Workspace *ws = lease.ws;
-	PGQ_TRY(ws->in_src.reserve((size_t)n * 8));
-	PGQ_TRY(ws->in_dst.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
-	PGQ_TRY(ws->out_off.reserve((size_t)n * 8));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, fp.src.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_dst.p, fp.dst.data(), (size_t)n * 8, hipMemcpyHostToDevice, ws->stream));
-	SearchOutput so;
-	so.no_memo = true;
-	PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
-	                      true, ws->out_off.as<int64_t>(), nullptr, 0, so));
-	std::vector<int64_t> len(n), off(n);
-	PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
-	PGQ_TRY(staged_download(off.data(), ws->out_off.p, (size_t)n * 8, ws->stream));
-	t_child.resize((size_t)so.child_used);
-	if (so.child_used > 0)
-		PGQ_TRY(staged_download(t_child.data(), ws->child.p, (size_t)so.child_used * 8, ws->stream));
-	mask_fill_valid(out_valid, n);
-	for (int64_t i = 0; i < n; i++) {
-		if (len[i] < 0) {
-			mask_set_invalid(out_valid, i);
-			out_offset[i] = 0;
-			out_length[i] = 0;
-		} else {
-			out_offset[i] = (uint64_t)off[i];
-			out_length[i] = (uint64_t)(2 * len[i] + 1);
+	auto check = [&] {
+		PGQ_TRY(check_csr(csr, V));
+		if (n < 0 || (n > 0 && (!out_offset || !out_length || !out_valid)) || !out_child || !out_child_len)
+			return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		*out_child = nullptr;
+		*out_child_len = 0;
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		FlatPairs fp;
+		PGQ_TRY(flatten_pairs(V, n, src, dst, fp, false));
+		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
+		PGQ_TRY(ws->out_off.reserve((size_t)n * 8));
+		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
+		SearchOutput so;
+		so.no_memo = true;
+		PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
+		                      true, ws->out_off.as<int64_t>(), nullptr, 0, so));
+		std::vector<int64_t> len(n), off(n);
+		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
+		PGQ_TRY(staged_download(off.data(), ws->out_off.p, (size_t)n * 8, ws->stream));
+		t_child.resize((size_t)so.child_used);
+		if (so.child_used > 0)
+			PGQ_TRY(staged_download(t_child.data(), ws->child.p, (size_t)so.child_used * 8, ws->stream));
+		mask_fill_valid(out_valid, n);
+		for (int64_t i = 0; i < n; i++) {
+			if (len[i] < 0) {
+				mask_set_invalid(out_valid, i);
+				out_offset[i] = 0;
+				out_length[i] = 0;
+			} else {
+				out_offset[i] = (uint64_t)off[i];
+				out_length[i] = (uint64_t)(2 * len[i] + 1);
+			}
 		}
-	}
-	*out_child = t_child.data();
-	*out_child_len = (uint64_t)so.child_used;
-	return PGQ_OK;
+		*out_child = t_child.data();
+		*out_child_len = (uint64_t)so.child_used;
+		return PGQ_OK;
+	});
 }
 
 } // extern "C"

@@ -1,4 +1,5 @@
-// pgq_runtime.hip — process state, error/option/stat plumbing and the device CSR (upload, reverse CSR, hubs).
+// pgq_runtime.hip — process state, error/option/stat plumbing, host workers and per-call workspaces, and the device CSR
+// (upload, reverse CSR, hubs).
 //
 // Replaces, on the device side, the CSR object of the reference
 // (src/include/duckpgq/core/utils/compressed_sparse_row.hpp:25-47): the host CSR built by
@@ -20,7 +21,7 @@
 #include <immintrin.h>
 #include <unordered_map>
 
-#include "pgq_internal.h"
+#include "pgq_search.h"
 
 namespace pgq {
 
@@ -132,6 +133,79 @@ int worker_wait(const std::shared_ptr<WorkerTask> &t) {
 	std::unique_lock<std::mutex> lk(t->m);
 	t->cv.wait(lk, [&] { return t->done; });
 	return t->failed == PGQ_OK ? PGQ_OK : fail(t->failed, t->what);
+}
+
+// every field of pgq_stats_t: 17 counters and three per-kernel-class arrays.  A field added to the public struct without a
+// line here fails this assertion.
+static_assert(sizeof(pgq_stats_t) == 17 * sizeof(int64_t) + PGQ_KCLASS_MAX * (2 * sizeof(double) + sizeof(int64_t)),
+              "pgq_stats_t changed: merge_stats must add the new field");
+static void merge_stats(pgq_stats_t &into, const pgq_stats_t &from) {
+	into.batches += from.batches;
+	into.levels += from.levels;
+	into.push_levels += from.push_levels;
+	into.pull_levels += from.pull_levels;
+	into.edges_scanned += from.edges_scanned;
+	into.word_gathers += from.word_gathers;
+	into.frontier_vertices += from.frontier_vertices;
+	into.unique_sources += from.unique_sources;
+	into.pairs += from.pairs;
+	into.deferred_pairs += from.deferred_pairs;
+	into.meet_pairs += from.meet_pairs;
+	for (int k = 0; k < PGQ_KCLASS_MAX; k++) {
+		into.algo_bytes[k] += from.algo_bytes[k];
+		into.kernel_ms[k] += from.kernel_ms[k];
+		into.launches[k] += from.launches[k];
+	}
+	into.spec_batches += from.spec_batches;
+	into.spec_levels += from.spec_levels;
+	into.spec_aborts += from.spec_aborts;
+	into.host_waits += from.host_waits;
+	into.ball_segments += from.ball_segments;
+	into.ball_calls += from.ball_calls;
+}
+
+int fan_out(const std::vector<int> &devices, const std::function<int(int)> &body) {
+	const size_t W = devices.size();
+	std::vector<int> rcs(W, PGQ_OK);
+	std::vector<std::string> errs(W);
+	std::vector<pgq_stats_t> wstats(W);
+	std::vector<std::shared_ptr<WorkerTask>> pool;
+	pool.reserve(W);
+	Options *const parent_opt = options_override();
+	auto run = [&](size_t k) {
+		bind_thread_device(devices[k]);
+		int r = ensure_init(); // binds the device for this host thread
+		if (r == PGQ_OK) r = body((int)k);
+		rcs[k] = r;
+		if (r != PGQ_OK) errs[k] = pgq_last_error();
+	};
+	try {
+		for (size_t k = 1; k < W; k++)
+			pool.push_back(worker_submit(devices[k], [&, k]() {
+				OptionScope opt_scope(parent_opt); // the handle's own options, if the call runs under them
+				(void)pgq_reset_stats();
+				run(k);
+				wstats[k] = tstats().s;
+			}));
+	} catch (const std::exception &) { // a worker thread could not be started: the jobs handed out already are waited for
+		for (const auto &t : pool) (void)worker_wait(t);
+		return fail(PGQ_ERR_OOM, "cannot start the worker threads of a call");
+	}
+	const int bound = t_device;
+	run(0);
+	bind_thread_device(bound);
+	(void)ensure_init();
+	for (size_t k = 1; k < W; k++) { // a job that threw never wrote its return code: take the pool's word for it
+		const int wr = worker_wait(pool[k - 1]);
+		if (wr != PGQ_OK) {
+			rcs[k] = wr;
+			errs[k] = pgq_last_error();
+		}
+	}
+	for (size_t k = 1; k < W; k++) merge_stats(tstats().s, wstats[k]);
+	for (size_t k = 0; k < W; k++)
+		if (rcs[k] != PGQ_OK) return fail(rcs[k], errs[k]);
+	return PGQ_OK;
 }
 
 static std::atomic<int> g_calls { 0 };
@@ -497,6 +571,81 @@ void DevBuf::release() {
 	cap = 0;
 }
 
+// ---- workspace ---------------------------------------------------------------------------------------------------
+
+Workspace::~Workspace() {
+	if (ev_block) (void)hipEventDestroy(ev_block);
+	if (stream) (void)hipStreamDestroy(stream);
+	if (h_cnt) (void)hipHostFree(h_cnt);
+	if (h_bi) (void)hipHostFree(h_bi);
+	if (h_log) (void)hipHostFree(h_log);
+	if (h_meet) (void)hipHostFree(h_meet);
+	if (h_io) (void)hipHostFree(h_io);
+	if (h_bstart) (void)hipHostFree(h_bstart);
+	for (DevBuf *b : { &seen, &qbuf[0], &qbuf[1], &qflag, &counters, &flag, &rank, &usrc, &key, &idx, &skey,
+	                   &sidx, &ssrc, &sdst, &sres, &soff, &sort_tmp, &scan_tmp, &bstart, &levels_tab, &child, &in_src,
+	                   &in_dst, &out_len, &out_off, &dist, &dirty[0], &dirty[1], &touched, &tflag, &out_val, &out_ok, &lane_sums, &ste, &def_src, &def_dst, &def_len,
+	                   &def_idx, &def_off, &def_ent, &cbits, &cbbase, &cmeta, &cwords, &lblk, &lrec, &meet_cnt, &meet_rec, &meet_poff, &meet_maps, &meet_trace,
+	                   &wb_scratch, &hv, &hmask, &hstart, &hmap, &route_dec, &ball_segs, &ball_trace, &sort_src, &sort_dst, &sort_out, &dist_b, &dirty_b[0], &dirty_b[1], &qbuf_b[0], &qbuf_b[1],
+	                   &touched_b, &tflag_b, &bi_block, &dpart })
+		b->release();
+	for (auto *v : { &levels, &pool })
+		for (auto &l : *v) {
+			l->buf.release();
+			l->nz.release();
+		}
+}
+
+static std::mutex g_ws_lock;
+static std::vector<Workspace *> g_ws_free; // every workspace remembers the device its buffers live on
+
+void drop_idle_workspaces() { // of the calling thread's device: another device's pool does not help an allocation here
+	std::vector<Workspace *> drop;
+	{
+		std::lock_guard<std::mutex> g(g_ws_lock);
+		const int dev = current_device();
+		for (size_t k = g_ws_free.size(); k-- > 0;)
+			if (g_ws_free[k]->device == dev) {
+				drop.push_back(g_ws_free[k]);
+				g_ws_free.erase(g_ws_free.begin() + (long)k);
+			}
+	}
+	for (Workspace *w : drop) delete w;
+}
+
+int WorkspaceLease::acquire() {
+	{
+		std::lock_guard<std::mutex> g(g_ws_lock);
+		const int dev = current_device();
+		for (size_t k = g_ws_free.size(); k-- > 0;)
+			if (g_ws_free[k]->device == dev) {
+				ws = g_ws_free[k];
+				g_ws_free.erase(g_ws_free.begin() + (long)k);
+				break;
+			}
+	}
+	if (!ws) {
+		ws = new Workspace();
+		ws->device = current_device();
+		// a half-built workspace never reaches the pool
+		if (hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking) != hipSuccess ||
+		    hipHostMalloc((void **)&ws->h_cnt, sizeof(Counters)) != hipSuccess ||
+		    hipHostMalloc((void **)&ws->h_log, sizeof(LevelLog) * (kSpecLevels + 3)) != hipSuccess ||
+		    hipHostMalloc(&ws->h_meet, 8192) != hipSuccess) {
+			delete ws;
+			ws = nullptr;
+			return fail(PGQ_ERR_HIP, "cannot create a search workspace (stream / pinned counter block)");
+		}
+	}
+	return PGQ_OK;
+}
+WorkspaceLease::~WorkspaceLease() {
+	if (!ws) return;
+	std::lock_guard<std::mutex> g(g_ws_lock);
+	if (g_ws_free.size() < 8 * std::max<size_t>(1, enabled_devices().size())) g_ws_free.push_back(ws);
+	else delete ws;
+}
+
 // ---- UnifiedVectorFormat -> flat arrays --------------------------------------------------------------------
 // The same resolution straight into caller-provided arrays (the pinned staging block of the chunk entry points), dst
 // validity not consulted (iterativelength.cpp:98,122); flat vectors without selection or validity take a branch-free loop.
@@ -561,6 +710,35 @@ int flatten_pairs(int64_t V, int64_t n, const pgq_vec_t &src, const pgq_vec_t &d
 		out.src[r] = s;
 		out.dst[r] = d;
 	}
+	return PGQ_OK;
+}
+
+void flatten_ids(int64_t n, const pgq_vec_t &src, int64_t *out) {
+	const int64_t *data = static_cast<const int64_t *>(src.data);
+	for (int64_t r = 0; r < n; r++) {
+		const int64_t p = src.sel ? (int64_t)src.sel[r] : r;
+		const bool valid = !src.validity || ((src.validity[p >> 6] >> (p & 63)) & 1ULL);
+		out[r] = valid ? data[p] : -1;
+	}
+}
+
+// ---- host staging of the entry points (pgq_search.h) ----------------------------------------------------------------
+int stage_pairs(Workspace *ws, int64_t n, const int64_t *src, const int64_t *dst) {
+	const size_t bytes = (size_t)n * 8;
+	PGQ_TRY(ws->in_src.reserve(bytes));
+	PGQ_TRY(ws->in_dst.reserve(bytes));
+	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_src.p, src, bytes, hipMemcpyHostToDevice, ws->stream));
+	PGQ_HIP_TRY(hipMemcpyAsync(ws->in_dst.p, dst, bytes, hipMemcpyHostToDevice, ws->stream));
+	return PGQ_OK;
+}
+
+int download_valid(Workspace *ws, int64_t n, void *out, uint64_t *out_valid) {
+	std::vector<uint8_t> ok((size_t)n);
+	PGQ_TRY(staged_download(out, ws->out_val.p, (size_t)n * 8, ws->stream));
+	PGQ_TRY(staged_download(ok.data(), ws->out_ok.p, (size_t)n, ws->stream));
+	mask_fill_valid(out_valid, n);
+	for (int64_t i = 0; i < n; i++)
+		if (!ok[(size_t)i]) mask_set_invalid(out_valid, i);
 	return PGQ_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <cmath>
 #include <memory>
+#include <type_traits>
 
 #include "pgq_internal.h"
 
@@ -303,6 +304,42 @@ struct WorkspaceLease {
 	~WorkspaceLease();
 };
 
+// The opening of a C entry point: the handle's options for the whole call, ensure_init before any argument check (without
+// a device every call answers PGQ_ERR_NO_DEVICE first), the entry's own checks, then the body.  check() returns PGQ_OK, an
+// error, or kNoRows when the call is answered without a search.  body(ws) runs on a workspace leased for the call, body()
+// without one (the *_multi entry points lease one per shard).  Search: the call counts towards `block_above` (wait_stream).
+constexpr int kNoRows = 1;
+struct NoCallScope {};
+template <bool Search, typename Check, typename Body>
+int c_entry(const pgq_csr *csr, Check &&check, Body &&body) {
+	[[maybe_unused]] std::conditional_t<Search, CallScope, NoCallScope> in_flight;
+	OptionScope opt_scope(csr);
+	PGQ_TRY(ensure_init());
+	const int rc = check();
+	if (rc != PGQ_OK) return rc == kNoRows ? PGQ_OK : rc;
+	if constexpr (std::is_invocable_v<Body &, Workspace *>) {
+		WorkspaceLease lease;
+		PGQ_TRY(lease.acquire());
+		return body(lease.ws);
+	} else {
+		return body();
+	}
+}
+
+// The usual checks: a handle, and the caller's arrays when there are rows (`arrays`: none of them NULL; `missing`: the
+// message otherwise).
+inline int check_arrays(const pgq_csr *csr, int64_t n, bool arrays, const char *missing) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	if (n < 0 || (n > 0 && !arrays)) return fail(PGQ_ERR_INVALID_ARG, missing);
+	return PGQ_OK;
+}
+
+// Host staging of the entry points (pgq_runtime.hip).  n host rows into ws->in_src / ws->in_dst, queued on ws->stream.
+int stage_pairs(Workspace *ws, int64_t n, const int64_t *src, const int64_t *dst);
+// n 8-byte values at ws->out_val and their ok bytes at ws->out_ok into the caller's array and validity mask (a row whose ok
+// byte is 0 is NULL; its payload is whatever the kernel left there); waits for ws->stream.
+int download_valid(Workspace *ws, int64_t n, void *out, uint64_t *out_valid);
+
 static inline unsigned blocks_for(int64_t n, int block = 256) {
 	return (unsigned)std::max<int64_t>(1, (n + block - 1) / block);
 }
@@ -366,7 +403,6 @@ int prepare_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, co
                   bool dst_rule = true);
 // bstart (pinned host) <- sorted-row boundaries of nb batches of L lanes (+ trivial / NULL tails)
 int batch_bounds(Workspace *ws, int64_t n, int64_t L, int nb);
-void merge_stats(pgq_stats_t &into, const pgq_stats_t &from); // a worker thread's counters into the caller's
 
 // ---- the BFS driver (pgq_route.hip picks the route, pgq_msbfs.hip runs the lane batches) ------------------------------
 // What a search_device call is asked for beside the lengths, and what it reports back.  with_paths: [src,e,v,...,dst]

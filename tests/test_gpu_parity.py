@@ -1347,7 +1347,8 @@ def test_two_ranks_on_one_gpu_product_path():
 def test_in_library_multi_gpu_shards_and_gathers():
     """pgq_init_devices + pgq_csr_replicate + pgq_iterativelength_multi: one host thread and one CSR replica per enabled
     device, contiguous shards, results gathered into one host array.  On a one-GPU box the device list names device 0
-    twice: two replicas (peer copy onto the same device), two shard threads, two workspaces."""
+    twice: two replicas (peer copy onto the same device), two shard threads, two workspaces.  The caller's statistics
+    count every shard's rows (a shard thread's counters are merged into them)."""
     rng = np.random.default_rng(31)
     V, E = 40000, 600000
     s, d, e = random_graph(rng, V, E)
@@ -1360,18 +1361,37 @@ def test_in_library_multi_gpu_shards_and_gathers():
     ps[:5] = -1  # NULL rows
     oln, ook = ora.lean_iterativelength(V, np.maximum(ps, 0), pd, nthreads=8)
     want = np.where(ook & (ps >= 0), oln, -1)
+    # the rows of shard 0 alone, on one device: what the pre-pass answers there
+    h = (n + 1) // 2
+    pgq.set_option("meet", 1)
+    pgq.set_option("meet_bias", 1e9)  # the pre-pass runs on every shard
+    pgq.reset_stats()
+    ln0, ok0 = dev.iterativelength(np.maximum(ps[:h], 0), pd[:h], src_valid=ps[:h] >= 0)
+    assert (np.where(ok0, ln0, -1) == want[:h]).all()
+    shard0_meet = pgq.get_stats()["meet_pairs"]
+    assert shard0_meet > 0
     assert pgq.init_devices([0, 0]) == 2
     try:
+        pgq.reset_stats()
+        assert (dev.iterativelength_multi(ps, pd) == want).all()
+        st = pgq.get_stats()
+        assert st["pairs"] == n
+        assert st["meet_pairs"] > shard0_meet  # shard 1's answers count too
+        pgq.set_option("meet_bias", 1)
         for meet in (1, 0):
             pgq.set_option("meet", meet)
+            pgq.reset_stats()
             got = dev.iterativelength_multi(ps, pd)
             assert (got == want).all()
+            assert pgq.get_stats()["pairs"] == n
         # paths: every shard's ragged lists gathered behind each other, offsets shifted by the preceding shards' sizes
         m = 3001
         opaths = ora.lean_shortestpath(V, np.maximum(ps[:m], 0), pd[:m])
         for meet in (1, 0):
             pgq.set_option("meet", meet)
+            pgq.reset_stats()
             ln, off, child = dev.shortestpath_multi(ps[:m], pd[:m])
+            assert pgq.get_stats()["pairs"] == m
             got = [None if ln[i] < 0 else child[off[i]:off[i] + 2 * ln[i] + 1].tolist() for i in range(m)]
             assert got == [p if ps[i] >= 0 else None for i, p in enumerate(opaths)]
             assert len(child) == sum(len(p) for p in got if p is not None)
@@ -1384,7 +1404,9 @@ def test_in_library_multi_gpu_shards_and_gathers():
             oraw = OracleCSR.adopt(V, off_, adj, eid, w)
             k = 600
             want_w, want_ok = oraw.lean_cheapest_path_length(V, ps[5:5 + k], pd[5:5 + k])
+            pgq.reset_stats()
             got_w, got_ok = devw.cheapest_path_length_multi(ps[5:5 + k], pd[5:5 + k])
+            assert pgq.get_stats()["pairs"] == k
             assert (got_ok == want_ok).all() and (got_w[want_ok] == want_w[want_ok]).all()
             devw.close()
     finally:
