@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — DuckPGQ's path-finding hot path on MI355X (contract: one JSON line on rank 0).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts its N ranks itself)
+    python bench.py --gpus N --steps K --warmup W [--full]  (N > 1 without a launcher: bench.py starts its N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs: it generates the graph and the pairs, uploads the CSR, runs the untimed
+accounting pass (traversed edges + the lengths the timed output is checked against), warms up, times the K steps, writes
+--dump-outputs and prints the result line (`metric`, `value`, `ms_per_step`, `mteps_*`, `config`, ...).  Everything
+else needs --full: `first_call` (fresh handles), the isolated profiled pass behind `roofline` / `roofline_by_kernel`,
+the copy-bandwidth probe, the other scaling mode for N > 1, the legs below and the CPU baselines.  Graphs are generated
+in the process: graphgen's on-disk cache is bypassed, so no run reads what an earlier one wrote.
 
 A "step" is one pass of the hot path over this rank's batch of (src,dst) pairs, inputs resident in HBM:
 pgq_iterativelength_bulk_device (pair-centric pre-pass for scattered pairs, lane-batched MS-BFS for cross products and
@@ -14,8 +21,8 @@ Default workload = BASELINE.json configs[3] (the config the metric "MS-BFS MTEPS
 1/2/4/8 GPU" is quoted on; it fits one GPU): synthetic LDBC-SNB-SF100-shaped Person-knows-Person graph (V=448,626,
 39.88 M symmetric CSR entries), iterativelength on 65,536 random pairs (`default_rng(4)`).
   N = 1:  the top-level fields describe that workload (= leg "prepass": every row is answered by the pair-centric
-          kernels); `legs` holds it next to one leg per other BASELINE config and call shape (`legs_by_config` maps them;
-          `legs` itself is printed as its own JSON line on stderr, the result line keeps `legs_summary`):
+          kernels); with --full `legs` holds it next to one leg per other BASELINE config and call shape (`legs_by_config`
+          maps them; `legs` itself is printed as its own JSON line on stderr, the result line keeps `legs_summary`):
             msbfs_cross       the same graph in the binder's call shape (match.cpp:467-495: a cross product of endpoints —
                               2048 distinct sources x 1024 destinations = 2.1 M rows, grouped by source), as the library routes
                               it (round 6: the source-centric kernel k_src_ball, one two-hop ball per source run)
@@ -29,14 +36,14 @@ Default workload = BASELINE.json configs[3] (the config the metric "MS-BFS MTEPS
             forest_cheapest   configs[4]: weighted cheapest path on a 2^24-vertex reply forest, 4096 pairs
             cheapest_general  cheapest_path_length of 4096 pairs on the knows graph with int64 weights (one step)
           each with its own ms/step, pairs/s, MTEPS, roofline and a bounded CPU comparison of the TIMED output
-          (--config-legs '' / --no-legs / --cheapest-pairs 0 drop them; the whole default command takes ~2-3 minutes).
+          (--config-legs '' / --no-legs / --cheapest-pairs 0 drop them; `--full` with the defaults takes ~2-3 minutes).
           `first_call_ms` (per leg): a FRESH CSR handle (pgq_csr_upload_device) -> its first search, no warm-up call, median
           over 5 handles — the reference's CSR lives for one query (iterative_length_function_data.cpp:27), so this is what a
           query sees; `ms_per_step` is the steady state of a handle that has answered the same call before.
           `legs_summary` (LAST key of the line, and mirrored as top-level scalars leg_<name>_ms / _frac / _first_ms):
           {leg: [ms_per_step, chain frac, whole-step frac, rows compared with the CPU port, rows equal, first_call_ms]}.
-  N > 1:  --scaling strong by default (configs[3] is 65,536 pairs in total, cut across the GPUs); the weak figure
-          (65,536 pairs on every GPU) is measured in the same run and reported under "weak".
+  N > 1:  --scaling strong by default (configs[3] is 65,536 pairs in total, cut across the GPUs); with --full the weak
+          figure (65,536 pairs on every GPU) is measured in the same run and reported under "weak".
 Other workloads as the main line: --workload rmat22 | snb_paths | forest_cheapest (--scale 28 = configs[4]'s named size) |
 snb_cross | snb_cross_allv | snb_cheapest.
 
@@ -48,12 +55,12 @@ value    = (src, dst) pairs answered per second, whole job (metric "src_dst_pair
            src, dst), counted once on the GPU outside the timed region (pgq_traversed_edges_bulk_device) and pinned
            against the CPU oracle in tests/.  The logical figure counts work the pair-centric kernels AVOID: it is not
            a hardware throughput and is not the headline (it was round 3's `value`; kept as `msbfs_mteps`).
-roofline = the leg's whole LAUNCH CHAIN (schema 5): the algorithmic bytes of all its kernel classes (DESIGN.md has the
+roofline = (--full) the leg's whole LAUNCH CHAIN (schema 5): the algorithmic bytes of all its kernel classes (DESIGN.md has the
            formulas) over the sum of their launch durations, measured in an untimed pass with one batch in flight and HIP
            events around every launch on the library's own stream; `dominant_kernel` = the single class with the most
            time (round 4's top level), `step` = the same bytes over the wall time of the timed region, `traffic` = HBM
            bytes per step of that chain from the committed PMC passes (profiles/pmc_<workload>.json).
-cpu_baseline = the literal restatement of the reference UDF (oracle/, 512-lane bitsets, 2048-row chunks) timed on this
+cpu_baseline = (--full) the literal restatement of the reference UDF (oracle/, 512-lane bitsets, 2048-row chunks) timed on this
            box's host cores on a bounded sample of the same pairs, same MTEPS definition, compared row by row with
            the output of the TIMED steps (the output buffer is poisoned before the timed loop).
 """
@@ -103,6 +110,10 @@ def parse():
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="pgq_set_option before the run (experiments; recorded in config.options)")
     ap.add_argument("--trace-steps", action="store_true", help="debugging: print every timed step's end time and counters to stderr")
     ap.add_argument("--cross-shuffle", action="store_true", help="snb_cross / rmat22_cross: rows in random order (a hash join's output) instead of grouped by source")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: first-call figures, the profiled pass behind the roofline, the copy-bandwidth "
+                         "probe, the other scaling mode (N > 1), the legs and the CPU baselines (the --no-* options below "
+                         "trim a --full run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="N = 1 default workload: skip the msbfs_cross and cheapest_general legs")
     ap.add_argument("--cheapest-pairs", type=int, default=4096, help="cheapest_general leg: pairs (0: skip the leg)")
@@ -126,6 +137,8 @@ def parse():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.dump_outputs and a.gpus > 1:
         ap.error("--dump-outputs writes one GPU's results: use it with --gpus 1")
+    if not a.full:  # a plain run: the headline only
+        a.no_first_call = a.no_legs = a.no_cpu_baseline = True
     return a
 
 
@@ -164,8 +177,15 @@ def launch_check(a):
 
 
 def build_graph(a):
-    """(name, V, offsets, adj, edge ids, weights or None, seconds) of a.workload's graph (numpy, seeded)."""
+    """(name, V, offsets, adj, edge ids, weights or None, seconds) of a.workload's graph (numpy, seeded), generated in
+    this process: graphgen's on-disk cache is bypassed, so that no run reads what an earlier run wrote."""
+    from unittest import mock
     from duckpgq_extension_amd import graphgen
+    with mock.patch.object(graphgen, "_cached", lambda name, gen: gen()):
+        return _build_graph(a, graphgen)
+
+
+def _build_graph(a, graphgen):
     t0 = time.time()
     w = None
     if a.workload in SNB:
@@ -258,10 +278,10 @@ class Bench:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def run(self, wl, csr, mine_t, total_pairs, steps, warmup, paths=False, cheapest=False):
+    def run(self, wl, csr, mine_t, total_pairs, steps, warmup, paths=False, cheapest=False, profile=True):
         """Times `steps` passes over this rank's rows `mine_t` ([n, 2] device tensor) and returns the measurements:
-        wall time of the timed region, statistics of the timed region and of an isolated profiled pass, the output of
-        the timed steps and the traversed-edge counts."""
+        wall time of the timed region, statistics of the timed region and (profile) of an isolated profiled pass after
+        it, the output of the timed steps and the traversed-edge counts."""
         torch, dist, pgq, sharding = self.torch, self.dist, self.pgq, self.sharding
         world, dev = self.world, self.dev
         n = mine_t.shape[0]
@@ -348,6 +368,13 @@ class Bench:
                 assert bool((d_len[last ^ 1] == ref_len).all()), "timed output differs from the accounting pass"
             reach = int((out_len >= 0).sum().item())
             out_val = None
+        res = {"n": n, "elapsed": elapsed, "stats": stats, "iso": None, "iso_steps": 0, "iso_elapsed": None,
+               "te_local": te_local, "reach": reach, "out_len": out_len, "out_val": out_val, "out_ok": out_ok, "d_ok": d_ok, "d_te": d_te,
+               "steps": steps}
+        if paths:  # offsets + payload of every list of the last timed step
+            res["out_off"], res["out_child"] = out_off, out_child
+        if not profile:
+            return res
         # Untimed pass with one batch in flight and HIP events around every launch (recorded on the library's own stream):
         # nothing overlaps, so a launch's event duration is that kernel's duration.
         n_streams, n_relax_streams = int(pgq.get_option("streams")), int(pgq.get_option("relax_streams"))
@@ -369,11 +396,8 @@ class Bench:
         pgq.set_option("profile", 0)
         pgq.set_option("streams", n_streams)
         pgq.set_option("relax_streams", n_relax_streams)
-        res = {"n": n, "elapsed": elapsed, "stats": stats, "iso": iso, "iso_steps": iso_steps, "iso_elapsed": iso_elapsed,
-               "te_local": te_local, "reach": reach, "out_len": out_len, "out_val": out_val, "out_ok": out_ok, "d_ok": d_ok, "d_te": d_te,
-               "steps": steps}
-        if paths:  # offsets + payload of every list of the last timed step; the isolated pass gave the same answers
-            res["out_off"], res["out_child"] = out_off, out_child
+        res.update(iso=iso, iso_steps=iso_steps, iso_elapsed=iso_elapsed)
+        if paths:  # the isolated pass gave the same answers
             assert bool((d_len[(iso_steps - 1) & 1] == out_len).all())
         return res
 
@@ -494,16 +518,17 @@ def roofline_of(m, workload, copy_gbps, elapsed):
 def leg_summary(bench, m, workload, total_pairs, copy_gbps):
     elapsed, te_total, scanned, reach = bench.reduce(m)
     steps, stats = m["steps"], m["stats"]
-    roof, by_kernel = roofline_of(m, workload, copy_gbps, elapsed)
-    return {"ms_per_step": elapsed / steps * 1e3, "pairs_per_s": total_pairs * steps / elapsed,
-            "mteps_logical": te_total * steps / elapsed / 1e6, "mteps_physical": scanned / elapsed / 1e6,
-            "traversed_edges_per_step": te_total, "physical_edges_scanned_per_step": scanned / steps,
-            "reachable_pairs": reach,
-            "rows_answered_by_prepass_per_step": stats["meet_pairs"] / max(steps, 1),
-            "levels_per_step": stats["levels"] / max(steps, 1),
-            "push_pull_levels": [stats["push_levels"] // max(steps, 1), stats["pull_levels"] // max(steps, 1)],
-            "deferred_pairs_per_step": stats["deferred_pairs"] / max(steps, 1),
-            "roofline": roof, "roofline_by_kernel": by_kernel}, elapsed
+    leg = {"ms_per_step": elapsed / steps * 1e3, "pairs_per_s": total_pairs * steps / elapsed,
+           "mteps_logical": te_total * steps / elapsed / 1e6, "mteps_physical": scanned / elapsed / 1e6,
+           "traversed_edges_per_step": te_total, "physical_edges_scanned_per_step": scanned / steps,
+           "reachable_pairs": reach,
+           "rows_answered_by_prepass_per_step": stats["meet_pairs"] / max(steps, 1),
+           "levels_per_step": stats["levels"] / max(steps, 1),
+           "push_pull_levels": [stats["push_levels"] // max(steps, 1), stats["pull_levels"] // max(steps, 1)],
+           "deferred_pairs_per_step": stats["deferred_pairs"] / max(steps, 1)}
+    if m["iso"] is not None:  # the run's isolated profiled pass
+        leg["roofline"], leg["roofline_by_kernel"] = roofline_of(m, workload, copy_gbps, elapsed)
+    return leg, elapsed
 
 
 def config_leg(bench, a, wl, copy_gbps, snb_graph, snb_csr):
@@ -691,16 +716,18 @@ def main():
     first_main = None
     if world == 1 and not a.no_first_call and a.workload != "snb_cross_allv":
         first_main = bench.first_call(fresh_csr, mine_t, a.first_call_handles, paths=paths, cheapest=cheapest)
-    m = bench.run(a.workload, csr, mine_t, total_pairs, a.steps, a.warmup, paths=paths, cheapest=cheapest)
+    m = bench.run(a.workload, csr, mine_t, total_pairs, a.steps, a.warmup, paths=paths, cheapest=cheapest, profile=a.full)
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, m, paths=paths, cheapest=cheapest, weights=a.weights)
-    try:
-        copy_gbps = pgq.copy_bandwidth_gbps(1 << 30, 5) if rank == 0 else None
-    except Exception:
-        copy_gbps = None
+    copy_gbps = None
+    if a.full and rank == 0:  # the measured copy ceiling the rooflines are printed beside
+        try:
+            copy_gbps = pgq.copy_bandwidth_gbps(1 << 30, 5)
+        except Exception:
+            copy_gbps = None
     main_leg, elapsed = leg_summary(bench, m, a.workload, total_pairs, copy_gbps)
     other = None
-    if world > 1 and a.workload != "snb_cross_allv":  # the other scaling mode, measured in the same run
+    if a.full and world > 1 and a.workload != "snb_cross_allv":  # the other scaling mode, measured in the same run
         mode2 = "weak" if scaling == "strong" else "strong"
         mine2, total2, _, _ = shard(mode2)
         m2 = bench.run(a.workload, csr, mine2, total2, a.steps, a.warmup, paths=paths, cheapest=cheapest)
@@ -823,12 +850,13 @@ def main():
             "levels_per_step": main_leg["levels_per_step"],
             "push_pull_levels": main_leg["push_pull_levels"],
             "deferred_pairs_per_step": main_leg["deferred_pairs_per_step"],
+        }
+        if "roofline" in main_leg:  # --full
             # dominant kernel class of the one-batch-in-flight pass (no overlap: event time = kernel time)
-            "roofline": main_leg["roofline"],
+            out["roofline"] = main_leg["roofline"]
             # every kernel class of that pass: event ms per step (they add up to less than its wall time: host round
             # trips and copies are not kernels), algorithmic GB/s, launches per step
-            "roofline_by_kernel": main_leg["roofline_by_kernel"],
-        }
+            out["roofline_by_kernel"] = main_leg["roofline_by_kernel"]
         if other is not None:
             out[other[0]] = dict(other[1], pairs_total=other[2], scaling=other[0])
         if cross_multi is not None:

@@ -1328,7 +1328,7 @@ def test_two_ranks_on_one_gpu_product_path():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", "29631", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
                "--warmup", "1", "--backend", "gloo", "--pairs-per-gpu", "3000", "--snb-vertices", "20000",
-               "--snb-friendships", "400000", "--no-cpu-baseline"] + extra
+               "--snb-friendships", "400000", "--full", "--no-cpu-baseline"] + extra
         if len(extra) == 2 and "strong" not in extra and "weak" not in extra:
             # the bare form `python bench.py --gpus 2 ...`: bench.py starts the two ranks itself (round 4 ran one)
             cmd = [sys.executable] + cmd[cmd.index(os.path.join(root, "bench.py")):]

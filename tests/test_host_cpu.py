@@ -308,6 +308,37 @@ def test_bench_rejects_a_run_without_timed_steps():
     assert r.returncode == 2 and "--steps" in r.stderr
 
 
+def test_bench_plain_run_is_the_headline_only(monkeypatch):
+    """Without --full the bench runs no first-call handles, legs or CPU baselines; --full runs them, and the --no-*
+    options still trim a --full run."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.no_first_call and a.no_legs and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not (a.no_first_call or a.no_legs or a.no_cpu_baseline)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-legs"])
+    a = bench.parse()
+    assert a.full and a.no_legs and not a.no_cpu_baseline
+
+
+def test_bench_generates_its_graph_without_the_disk_cache(tmp_path, monkeypatch):
+    """bench.py neither reads nor writes graphgen's on-disk cache: no run reads what an earlier run wrote."""
+    import sys
+    import bench
+    from duckpgq_extension_amd import graphgen
+    monkeypatch.setattr(graphgen, "_CACHE", str(tmp_path))
+    V, F = 2000, 20000
+    planted = tmp_path / ("snbknows_V%d_F%d_seed100.npz" % (V, F))
+    np.savez(planted, np.array([0, 1]), np.array([1, 0]))  # what graphgen would load in place of generating
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--snb-vertices", str(V), "--snb-friendships", str(F)])
+    name, V2, off, adj, eid, w, _ = bench.build_graph(bench.parse())
+    assert V2 == V and len(adj) > 2 * F * 0.9 and w is None
+    assert sorted(p.name for p in tmp_path.iterdir()) == [planted.name]
+
+
 def test_stats_struct_layout_matches_the_header(tmp_path):
     """pgq_stats_t grew at its end in round 5 (spec_batches ... host_waits): the ctypes mirror must have the header's size
     and field offsets, or every statistic after the first mismatch reads garbage."""

@@ -31,8 +31,8 @@ def fmt(x, spec="{:,.0f}"):
 
 
 L = ["# profiles — round %s measurements (MI355X, one GPU per gpurun box)" % rnd.lstrip("r0"), "",
-     "Produced by committed tooling only: `tools/measure_pass_%s.sh` on the GPU box (PART=1: `bench.py` with the driver's own "
-     "command — every BASELINE config and call shape is a leg of that one line — and the shapes beside it on their routes, "
+     "Produced by committed tooling only: `tools/measure_pass_%s.sh` on an MI355X (PART=1: `bench.py --full --steps 20 --warmup 5` "
+     "— every BASELINE config and call shape is a leg of that one line — and the shapes beside it on their routes, "
      "`rocprofv3 --kernel-trace --stats` of the default workload without its legs, of the SF100 cross product as routed "
      "(`k_src_ball`) and forced through the lane batches (`PGQ_BALL=0`), and of the R-MAT-22 cross product, "
      "`tools/chunk_latency.py`; PART=2: separate `--pmc` passes of those four workloads, summarised by `tools/pmc_summary.py` "

@@ -8,7 +8,7 @@ PMC=0; if [ "${1:-}" = "pmc" ]; then PMC=1; shift; fi
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"
+B="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"
 PGQ_STREAMS=${PGQ_STREAMS:-1} timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- $B > $O/stats.log 2>&1
 rm -f $O/stats/*kernel_trace.csv
 python - <<PY

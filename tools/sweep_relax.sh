@@ -12,7 +12,7 @@ for lib in "" build_variants/libpgq_hip_relax_*.so; do
 	tag=${lib:-shipped}
 	for cfg in "512 1" "4096 6"; do
 		set -- $cfg
-		PGQ_HIP_LIB=${lib:+$R/$lib} PGQ_RELAX_STREAMS=$2 timeout 300 python bench.py --workload snb_cheapest --steps 1 --warmup 1 --no-cpu-baseline --pairs-per-gpu $1 > $O/b.json 2> $O/b.err
+		PGQ_HIP_LIB=${lib:+$R/$lib} PGQ_RELAX_STREAMS=$2 timeout 300 python bench.py --full --workload snb_cheapest --steps 1 --warmup 1 --no-cpu-baseline --pairs-per-gpu $1 > $O/b.json 2> $O/b.err
 		python -c "
 import json; d=json.load(open('$O/b.json')); print('$tag', 'pairs=$1 streams=$2', round(d['ms_per_step'],1), 'ms', round(d['pairs_per_s']), 'pairs/s', d['roofline_by_kernel'].get('relax'))"
 	done
