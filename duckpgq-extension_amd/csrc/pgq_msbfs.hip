@@ -1754,7 +1754,7 @@ int grow_keeping(DevBuf &buf, size_t bytes, size_t keep, hipStream_t st) {
 
 // The start of a lane batch that keeps no per-level frontiers: `seen`, the counter block and the open-lane copies zeroed,
 // the sparse pool's buffers clean (k_batch_reset; a buffer that is new, was laid out for another (V, WD), or belongs to a
-// batch that did not end normally has no nz to be trusted and is zeroed whole, once).  Called by run_batches at a batch's
+// batch that did not end normally has no nz to be trusted and is zeroed whole, once).  Called by LaneBatches at a batch's
 // start — or EARLIER, by search_device, in front of the lane assignment's wait when the CSR remembers the width of the
 // last one-batch call (`prereset_*` says so: the GPU then does this while the host waits for the source count).
 static int batch_state_reset(Workspace *ws, int64_t V, int WD) {
@@ -1799,82 +1799,149 @@ static int batch_state_reset(Workspace *ws, int64_t V, int WD) {
 // ---- the batch driver ----------------------------------------------------------------------------------------------
 static constexpr int kMaxTeLevels = 1024;
 
+// One worker's lane batches b0, b0 + bstride, ... of one call.  sh: the call's shared arrays (rows sorted by lane, per-row
+// results, batch bounds); ws: this worker's private search state (seen, frontiers, queues, counters, stream).
 template <int WD>
-static int run_batches(pgq_csr *c, Workspace *sh, Workspace *ws, int b0, int bstride, int64_t n, int64_t U,
-                       bool with_paths, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp) {
-	// sh: the call's shared arrays (rows sorted by lane, per-row results, batch bounds); ws: this worker's private
-	// search state (seen, frontiers, queues, counters, stream).  Workers take batches b0, b0+bstride, ...
-	hipStream_t st = ws->stream;
-	const int64_t V = c->V, E = c->E;
-	const Options &opt = options();
-	const int64_t L = 64 * WD;
-	const int nb = (int)((U + L - 1) / L);
-	const int64_t chunk = c->hub_threshold;                       // bottom-up: in-degree above this = hub
-	const int64_t pchunk = std::max(64, options().push_chunk);    // top-down: out-edges per queue item
-	const size_t words = (size_t)std::max<int64_t>(V, 1) * WD;
-	const u32 qcap = (u32)std::min<int64_t>(V + E / pchunk + 128, 0xFFFFFF00ll);
-	pgq_stats_t &S = tstats().s;
+class LaneBatches {
+public:
+	LaneBatches(pgq_csr *c, Workspace *sh, Workspace *ws, int64_t n, int64_t U, bool with_paths, int64_t *d_child_ext,
+	            int64_t child_cap_ext, SearchOutput &outp)
+	    : c(c), sh(sh), ws(ws), outp(outp), n(n), U(U), with_paths(with_paths), d_child_ext(d_child_ext), child_cap_ext(child_cap_ext) {}
 
-	PGQ_TRY(ws->seen.reserve(words * 8));
-	PGQ_TRY(ws->qbuf[0].reserve((size_t)qcap * 8));
-	PGQ_TRY(ws->qbuf[1].reserve((size_t)qcap * 8));
-	PGQ_TRY(ws->counters.reserve(sizeof(Counters)));
-	PGQ_TRY(ws->dpart.reserve((size_t)kOpenRep * WD * 8));
-	if (outp.want_te) {
-		PGQ_TRY(ws->lane_sums.reserve((size_t)kMaxTeLevels * L * 8));
-		PGQ_TRY(sh->ste.reserve((size_t)n * 8));
-		PGQ_HIP_TRY(hipMemsetAsync(sh->ste.p, 0, (size_t)n * 8, st));
+	int run(int b0, int bstride) {
+		PGQ_TRY(ws->seen.reserve(words * 8));
+		for (DevBuf &q : ws->qbuf) PGQ_TRY(q.reserve((size_t)qcap * 8));
+		PGQ_TRY(ws->counters.reserve(sizeof(Counters)));
+		PGQ_TRY(ws->dpart.reserve((size_t)kOpenRep * WD * 8));
+		if (outp.want_te) {
+			PGQ_TRY(ws->lane_sums.reserve((size_t)kMaxTeLevels * L * 8));
+			PGQ_TRY(sh->ste.reserve((size_t)n * 8));
+			PGQ_HIP_TRY(hipMemsetAsync(sh->ste.p, 0, (size_t)n * 8, st));
+		}
+		d_cnt = ws->counters.as<Counters>();
+		if (ws != sh) PGQ_WAIT(st); // (the caller's own stream orders its batches behind the lane assignment)
+		for (int b = b0; b < nb; b += bstride)
+			if (sh->h_bstart[b] != sh->h_bstart[b + 1]) PGQ_TRY(run_batch(b));
+		if (with_paths && b0 == 0) PGQ_TRY(trivial_paths());
+		PGQ_WAIT(st); // other workers / the caller read sres next
+		KernelTimer::flush();
+		return PGQ_OK;
 	}
-	Counters *d_cnt = ws->counters.as<Counters>();
-	if (ws != sh) PGQ_WAIT(st); // (the caller's own stream orders its batches behind the lane assignment)
-	const int64_t *bs = sh->h_bstart;
+
+private:
+	// What enqueueing a level changes on the host, snapshotted per enqueued-ahead level.  queue_valid: qbuf[par] describes
+	// `cur`; dirty: the sparse pool's flags; pending_fold: the last level's open-lane words are still in the copies (k_detect).
+	struct HostState {
+		LevelBuf *cur;
+		int par, act_sel;
+		bool queue_valid, dirty[2], pending_fold;
+	};
+
+	// per call
+	pgq_csr *const c;
+	Workspace *const sh, *const ws;
+	SearchOutput &outp;
+	const int64_t n, U;
+	const bool with_paths;
+	int64_t *const d_child_ext; // the caller's buffer for the path lists, else sh->child
+	const int64_t child_cap_ext;
+	const hipStream_t st = ws->stream;
+	const Options &opt = options();
+	pgq_stats_t &S = tstats().s;
+	const int64_t V = c->V, E = c->E, L = 64 * WD;
+	const int nb = (int)((U + L - 1) / L);
+	const int64_t pchunk = std::max(64, opt.push_chunk); // top-down: out-edges per queue item
+	const size_t words = (size_t)std::max<int64_t>(V, 1) * WD, nz_bytes = (size_t)std::max<int64_t>(V, 1) * 4;
+	const u32 qcap = (u32)std::min<int64_t>(V + E / pchunk + 128, 0xFFFFFF00ll);
+	const int ncu = device_cus();
+	const unsigned pull_grid = (unsigned)std::max(1, opt.blocks_per_cu) * ncu, push_grid = 8 * ncu;
+	// The destination probe answers a pair one expansion early; it costs one in-neighbour scan per open pair, so it is used
+	// while the batch has few pairs relative to the graph (not for cross products) and never in the traversed-edge
+	// accounting pass (which needs every level of every lane).  Whether a level is probed is decided per level (decide_level).
+	const bool use_probe = opt.probe && !outp.want_te;
+	const bool lanes_ok = opt.lanes && c->rpk != nullptr;
 	// levels enqueued ahead of the host under the plan of the last batch of this width; paths keep every
 	// level's frontier and the accounting pass its per-level sums: they stay on the round trip per level
 	const bool spec_ok = opt.spec_levels && !with_paths && !outp.want_te;
 	const int plan_slot = WD == 1 ? 0 : (WD == 2 ? 1 : (WD == 4 ? 2 : (WD == 8 ? 3 : (WD == 16 ? 4 : 5))));
-
-	int64_t child_base = 0;
-	int64_t *d_child = d_child_ext;
+	const LevelRule rule { (double)E, (double)V, opt.push_div, opt.sparse_below, WD, opt.force_mode, opt.force_pull,
+	                       opt.probe_always, use_probe ? 1 : 0 };
+	Counters *d_cnt = nullptr;
+	int64_t child_base = 0, *d_child = d_child_ext;
 	bool child_overflow = false;
 	std::vector<int32_t> h_res;
 	std::vector<int64_t> h_off;
 
-	const int ncu = device_cus();
-	const unsigned pull_grid = (unsigned)std::max(1, opt.blocks_per_cu) * ncu;
-	const unsigned push_grid = 8 * ncu;
+	// per batch (start_batch)
+	int b = 0, levels_run = 0;
+	int64_t lo = 0, hi = 0;
+	u32 base_lane = 0, last_cw_cap = 0;
+	int stop = -1;              // open pairs at or below this count stop the batch: 0 = everything answered, > 0 = defer the stragglers
+	u32 open_before = 0;        // rows open before the level whose counters are being looked at (byte model of detection)
+	u32 sparse_front_words = 0; // k_pull_sparse sizes its packed-word buffer from the frontier's words
+	std::vector<uint8_t> ran_plan; // the levels this batch really ran: the next batch's plan
+	HostState hs {};
 
-	for (int b = b0; b < nb; b += bstride) {
-		const int64_t lo = bs[b], hi = bs[b + 1];
-		if (lo == hi) continue;
-		const u32 base_lane = (u32)((int64_t)b * L);
+	u64 *act(int sel) const { return &d_cnt->act[sel][0]; }
+	u32 *spec_status() const { return reinterpret_cast<u32 *>(ws->h_log + kSpecLevels + 2); }
+
+	HostState snapshot() const {
+		HostState h = hs;
+		for (size_t k = 0; k < 2 && k < ws->pool.size(); k++) h.dirty[k] = ws->pool[k]->dirty;
+		return h;
+	}
+	void restore(const HostState &h) {
+		hs = h;
+		for (size_t k = 0; k < 2 && k < ws->pool.size(); k++) ws->pool[k]->dirty = h.dirty[k];
+	}
+	// Frontier buffers.  shortestpath keeps every level's frontier (ws->levels[t]).  Otherwise two pools (ws->pool):
+	// [0], [1] "sparse" — level 0 and the targets of top-down levels, written through atomics only, kept all-zero between
+	// uses by walking their nz (k_batch_reset / k_clean_by_nz / k_clear_items); [2], [3] "dense" — targets of bottom-up
+	// levels, which write every row, so they are never zeroed.  A level's target is the buffer of its pool that is not
+	// the current frontier.
+	LevelBuf *level_buf(int t, bool push_target, const LevelBuf *not_this) {
+		if (with_paths) {
+			while (ws->levels.size() <= (size_t)t) ws->levels.emplace_back(new LevelBuf());
+			return ws->levels[(size_t)t].get();
+		}
+		while (ws->pool.size() < 4) ws->pool.emplace_back(new LevelBuf());
+		LevelBuf *a = ws->pool[push_target ? 0 : 2].get();
+		return a != not_this ? a : ws->pool[push_target ? 1 : 3].get();
+	}
+	int make_zero(LevelBuf *lb) { // shortestpath: a level's own buffer before a top-down level writes into it
+		PGQ_TRY(lb->buf.reserve(words * 8));
+		PGQ_TRY(lb->nz.reserve(nz_bytes));
+		if (lb->dirty) {
+			PGQ_HIP_TRY(hipMemsetAsync(lb->buf.p, 0, words * 8, st));
+			PGQ_HIP_TRY(hipMemsetAsync(lb->nz.p, 0, nz_bytes, st));
+			lb->dirty = false;
+		}
+		return PGQ_OK;
+	}
+
+	int run_batch(int batch) {
+		PGQ_TRY(start_batch(batch));
+		LevelLog last {}; // the counters after the last level the host knows about
+		int t = 1;
+		const std::vector<uint8_t> plan = take_plan();
+		// without a plan, the counters after level 0: k_init_batch opened every row (level 1 decides with all WD words)
+		int r = plan.empty() ? read_counters(last) : levels_ahead(plan, last, t);
+		if (r == 0) r = round_trips(last, t);
+		if (r < 0) return r;
+		store_plan();
+		ws->pool_trusted = true; // the dirty flags of the sparse pool say what the device did
+		if (outp.want_te)
+			hipLaunchKernelGGL(k_pair_te, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, sh->skey.as<u32>(),
+			                   sh->sres.as<int32_t>(), base_lane, ws->lane_sums.as<u64>(), (int)L, levels_run + 1,
+			                   sh->ste.as<int64_t>());
+		return with_paths ? batch_paths() : PGQ_OK;
+	}
+	int start_batch(int batch) {
+		b = batch;
+		lo = sh->h_bstart[b];
+		hi = sh->h_bstart[b + 1];
+		base_lane = (u32)((int64_t)b * L);
 		S.batches++;
-		// -- reset per-batch state
-		const size_t nz_bytes = (size_t)std::max<int64_t>(V, 1) * 4;
-		// Frontier buffers.  shortestpath keeps every level's frontier (ws->levels[t]).  Otherwise two pools (ws->pool):
-		// [0], [1] "sparse" — level 0 and the targets of top-down levels, written through atomics only, kept all-zero between
-		// uses by walking their nz (k_batch_reset / k_clean_by_nz / k_clear_items); [2], [3] "dense" — targets of bottom-up
-		// levels, which write every row, so they are never zeroed.  A level's target is the buffer of its pool that is not
-		// the current frontier.  (Round 4: two buffers alternating, the top-down targets zeroed by a 115-MB memset per use.)
-		auto level_buf = [&](int t, bool push_target, const LevelBuf *not_this) -> LevelBuf * {
-			if (with_paths) {
-				while (ws->levels.size() <= (size_t)t) ws->levels.emplace_back(new LevelBuf());
-				return ws->levels[(size_t)t].get();
-			}
-			while (ws->pool.size() < 4) ws->pool.emplace_back(new LevelBuf());
-			LevelBuf *a = ws->pool[push_target ? 0 : 2].get();
-			return a != not_this ? a : ws->pool[push_target ? 1 : 3].get();
-		};
-		auto make_zero = [&](LevelBuf *lb) -> int { // shortestpath: a level's own buffer before a top-down level writes into it
-			PGQ_TRY(lb->buf.reserve(words * 8));
-			PGQ_TRY(lb->nz.reserve(nz_bytes));
-			if (lb->dirty) {
-				PGQ_HIP_TRY(hipMemsetAsync(lb->buf.p, 0, words * 8, st));
-				PGQ_HIP_TRY(hipMemsetAsync(lb->nz.p, 0, nz_bytes, st));
-				lb->dirty = false;
-			}
-			return PGQ_OK;
-		};
-		LevelBuf *cur = nullptr;
 		const bool start_done = !with_paths && ws->prereset_V == V && ws->prereset_WD == WD; // in front of the lane assignment's wait
 		ws->prereset_V = -1; // one batch's worth, whoever uses `seen` next
 		if (with_paths) {
@@ -1882,504 +1949,436 @@ static int run_batches(pgq_csr *c, Workspace *sh, Workspace *ws, int b0, int bst
 			PGQ_HIP_TRY(hipMemsetAsync(ws->counters.p, 0, sizeof(Counters), st));
 			PGQ_HIP_TRY(hipMemsetAsync(ws->dpart.p, 0, (size_t)kOpenRep * WD * 8, st)); // the copies of the open-lane mask (publish_open_lanes)
 			for (auto &lb : ws->levels) lb->dirty = true; // previous batch / call left them in an unknown state
-			cur = level_buf(0, true, nullptr);
-			PGQ_TRY(make_zero(cur));
-		} else {
-			if (!start_done) PGQ_TRY(batch_state_reset(ws, V, WD));
-			cur = level_buf(0, true, nullptr);
+			PGQ_TRY(make_zero(level_buf(0, true, nullptr)));
+		} else if (!start_done) {
+			PGQ_TRY(batch_state_reset(ws, V, WD));
 		}
-		u64 *act_cur = &d_cnt->act[0][0]; // zeroed with the counter block above
-		u32 open_before = (u32)(hi - lo); // rows open before the level whose counters are being looked at (byte model of detection)
-		u32 sparse_front_words = 0;       // k_pull_sparse sizes its packed-word buffer from the frontier's words
-		{
-			KernelTimer kt(st, K_PREP);
-			hipLaunchKernelGGL(k_init_batch<WD>, dim3(blocks_for(L)), dim3(256), 0, st, sh->usrc.as<int32_t>(), U,
-			                   (int64_t)base_lane, c->off, cur->buf.as<u64>(), cur->nz.as<u32>(), ws->seen.as<u64>(),
-			                   act_cur, ws->qbuf[0].as<u64>(), qcap, pchunk, (u32)(hi - lo), d_cnt);
-			kt.stop();
-		}
+		LevelBuf *cur = level_buf(0, true, nullptr);
+		open_before = (u32)(hi - lo);
+		sparse_front_words = 0;
+		KernelTimer kt(st, K_PREP);
+		hipLaunchKernelGGL(k_init_batch<WD>, dim3(blocks_for(L)), dim3(256), 0, st, sh->usrc.as<int32_t>(), U,
+		                   (int64_t)base_lane, c->off, cur->buf.as<u64>(), cur->nz.as<u32>(), ws->seen.as<u64>(),
+		                   act(0), ws->qbuf[0].as<u64>(), qcap, pchunk, (u32)(hi - lo), d_cnt); // act[0]: zeroed with the counter block
+		kt.stop();
 		cur->dirty = true;
 		if (outp.want_te) {
 			PGQ_HIP_TRY(hipMemsetAsync(ws->lane_sums.p, 0, (size_t)kMaxTeLevels * L * 8, st));
 			hipLaunchKernelGGL(k_lane_degree_sums<WD>, dim3(4 * ncu), dim3(256), 0, st, cur->buf.as<u64>(), c->off, V,
 			                   ws->lane_sums.as<u64>());
 		}
-		// The destination probe answers a pair one expansion early; it costs one in-neighbour scan per open pair,
-		// so it is used while the batch has few pairs relative to the graph (not for cross products) and never in
-		// the traversed-edge accounting pass (which needs every level of every lane).
-		const bool use_probe = opt.probe && !outp.want_te; // whether a level is probed is decided per level (decide_level)
-		// open pairs at or below this count stop the batch: 0 = everything answered, > 0 = defer the stragglers
-		int stop = -1;
-		if (use_probe) {
-			stop = 0;
-			// a narrow batch is scan-bound: re-running its stragglers costs as much as finishing them here
-			if (opt.defer && outp.depth < 2 && WD >= 8) stop = (int)std::min<int64_t>(L / opt.defer, (hi - lo) / opt.defer);
+		stop = use_probe ? 0 : -1;
+		// a narrow batch is scan-bound: re-running its stragglers costs as much as finishing them here
+		if (use_probe && opt.defer && outp.depth < 2 && WD >= 8) stop = (int)std::min<int64_t>(L / opt.defer, (hi - lo) / opt.defer);
+		hs = HostState { cur, 0, 0, true, { false, false }, false };
+		last_cw_cap = 0;
+		levels_run = 0;
+		ran_plan.clear();
+		return PGQ_OK;
+	}
+
+	// reset the per-level counters but keep the queue counts
+	void level_reset(int t, u32 bits, bool spec, int prev_stop) {
+		const bool push = bits & kLvPush;
+		const bool zq_cur = push && !hs.queue_valid; // queue rebuilt from the dense frontier below
+		const int q_cur = hs.par, q_nxt = hs.par ^ 1;
+		const SpecArgs sp { spec ? ws->h_log : nullptr, spec ? spec_status() : nullptr, t, bits, prev_stop };
+		KernelTimer kt(st, K_QUEUE); // bookkeeping between levels: no byte model, its time counts in the chain
+		hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(256), 0, st, d_cnt, hs.act_sel ^ 1,
+		                   (int)((push && q_nxt == 0) || (zq_cur && q_cur == 0)),
+		                   (int)((push && q_nxt == 1) || (zq_cur && q_cur == 1)), rule, sp,
+		                   hs.pending_fold ? ws->dpart.as<u64>() : (u64 *)nullptr);
+		kt.stop();
+		hs.pending_fold = false;
+	}
+	// The probe answers the rows still open before the expansion; the expansion then only serves lanes that still have open
+	// pairs.  The two-hop probe replaces an expansion for those rows while it is the cheaper of the two: a row walks the
+	// in-lists of its destination's in-neighbours (the graph's mean two-hop walk, at most probe2_cap entries), two gathered
+	// 64-byte sectors per entry, one workgroup per row; a dense level moves E x (8 + 6 WD) bytes.  R-MAT-22 (mean two-hop
+	// walk over the cap): 4096 open rows made each probe 2.3 ms where a level takes 1.9, five times per call, without saving
+	// a level — 11 of the cross product's 23.8 ms through the lanes.
+	void probe(int t) {
+		LevelBuf *cur = hs.cur;
+		const int64_t probe2_rows_worth = std::max<int64_t>(
+		    64, (int64_t)((double)E * (8.0 + 6.0 * WD) / (128.0 * std::max(64.0, std::min((double)opt.probe2_cap, c->two_hop_mean)))));
+		KernelTimer kt(st, K_DETECT);
+		// up to one wavefront per row (few rows: the wavefronts of a 64-row chunk share its open rows), at most 8192
+		hipLaunchKernelGGL(k_probe<WD>, dim3(std::min(blocks_for((hi - lo) * 64, 1024), (unsigned)kOpenGrid)), dim3(1024), 0, st, lo, hi,
+		                   sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(), base_lane,
+		                   cur->buf.as<u64>(), cur->nz.as<u32>(), c->roff, c->radj, t, ws->dpart.as<u64>(), d_cnt, std::max(64, opt.probe_max_in));
+		if (opt.probe2 && !with_paths)
+			hipLaunchKernelGGL(k_probe2<WD>, dim3((unsigned)std::min<int64_t>(hi - lo, 2 * ncu)), dim3(1024), 0, st, lo, hi,
+			                   sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(), base_lane,
+			                   cur->buf.as<u64>(), cur->nz.as<u32>(), c->roff, c->radj, t,
+			                   (u32)std::min<int64_t>(probe2_rows_worth,
+			                                          std::max<int64_t>(std::min<int64_t>(L / std::max(1, opt.probe2_div), (hi - lo) / std::max(1, opt.probe2_div)),
+			                                                            std::min<int64_t>(hi - lo, opt.probe2_abs))),
+			                   (int64_t)opt.probe2_cap, ws->dpart.as<u64>(), act(hs.act_sel ^ 1), d_cnt);
+		else
+			hipLaunchKernelGGL(k_open_merge, dim3(1), dim3(256), 0, st, ws->dpart.as<u64>(), act(hs.act_sel ^ 1), WD, d_cnt);
+		kt.stop();
+		hs.act_sel ^= 1;
+	}
+	// top-down: the queue of the frontier (rebuilt from its nz unless the level before was top-down too), then k_push
+	int push_level(LevelBuf *nxt, bool spec, int stop_lvl) {
+		LevelBuf *cur = hs.cur;
+		const int par = hs.par;
+		if (!hs.queue_valid) {
+			KernelTimer kt(st, K_QUEUE);
+			hipLaunchKernelGGL(k_queue_from_dense<WD>, dim3(std::min(blocks_for(V), 16u * ncu)), dim3(256), 0, st,
+			                   cur->nz.as<u32>(), V, c->off, pchunk, ws->qbuf[par].as<u64>(), qcap, par, d_cnt);
+			kt.stop();
 		}
-		LevelRule rule;
-		rule.E = (double)E;
-		rule.V = (double)V;
-		rule.push_div = opt.push_div;
-		rule.sparse_below = opt.sparse_below;
-		rule.wd = WD;
-		rule.force_mode = opt.force_mode;
-		rule.force_pull = opt.force_pull;
-		rule.probe_always = opt.probe_always;
-		rule.use_probe = use_probe ? 1 : 0;
-		const bool lanes_ok = opt.lanes && c->rpk != nullptr;
+		if (with_paths) PGQ_TRY(make_zero(nxt));
+		else if (nxt->dirty) { // (its buffers exist and are laid out for this batch: the batch's start saw to both pool members)
+			hipLaunchKernelGGL(k_clean_by_nz, dim3(4 * ncu), dim3(256), 0, st, nxt->buf.as<u64>(), nxt->nz.as<u32>(), V, (int)WD,
+			                   spec ? (const Counters *)d_cnt : (const Counters *)nullptr);
+			nxt->dirty = false;
+		}
+		KernelTimer kp(st, K_PUSH);
+		hipLaunchKernelGGL(k_push<WD>, dim3(push_grid), dim3(256), 0, st, c->off, c->adj, cur->buf.as<u64>(),
+		                   ws->seen.as<u64>(), nxt->buf.as<u64>(), nxt->nz.as<u32>(), act(hs.act_sel),
+		                   ws->qbuf[par].as<u64>(), par, qcap, pchunk, stop_lvl, d_cnt);
+		kp.stop();
+		nxt->dirty = true;
+		if (!with_paths) {
+			KernelTimer kt(st, K_QUEUE);
+			hipLaunchKernelGGL(k_clear_items<WD>, dim3(4 * ncu), dim3(256), 0, st, ws->qbuf[par].as<u64>(), par,
+			                   qcap, cur->buf.as<u64>(), cur->nz.as<u32>(), d_cnt);
+			kt.stop();
+			cur->dirty = false;
+		}
+		hs.queue_valid = false; // rebuilt from nz if the next level is top-down too
+		return PGQ_OK;
+	}
+	// bottom-up: the hub slices (in-degree above c->hub_threshold), then the lanes: lane-list, packed sparse or dense
+	int pull_level(LevelBuf *nxt, bool sparse_level, int stop_lvl) {
+		LevelBuf *cur = hs.cur;
+		u64 *active = act(hs.act_sel);
+		PGQ_TRY(nxt->buf.reserve(words * 8));
+		PGQ_TRY(nxt->nz.reserve(nz_bytes));
+		if (c->n_pull_hub_vertices > 0) {
+			KernelTimer kt(st, K_PULL_HUB);
+			hipLaunchKernelGGL(k_pull_hub_zero<WD>, dim3(blocks_for(c->n_pull_hub_vertices * WD)), dim3(256), 0,
+			                   st, c->pull_hub_vertices, c->n_pull_hub_vertices, nxt->buf.as<u64>(), stop_lvl, d_cnt);
+			hipLaunchKernelGGL(k_pull_hub<WD>, dim3(blocks_for(c->n_pull_hub_items * 64)), dim3(256), 0, st,
+			                   c->pull_hubs, c->n_pull_hub_items, c->radj, cur->buf.as<u64>(), cur->nz.as<u32>(),
+			                   ws->seen.as<u64>(), nxt->buf.as<u64>(), active, stop_lvl, d_cnt);
+			hipLaunchKernelGGL(k_pull_hub_fold<WD>, dim3(blocks_for(c->n_pull_hub_vertices)), dim3(256), 0, st,
+			                   c->pull_hub_vertices, c->n_pull_hub_vertices, c->off, ws->seen.as<u64>(),
+			                   nxt->buf.as<u64>(), nxt->nz.as<u32>(), stop_lvl, d_cnt);
+			kt.stop();
+		}
+		// frontier sparse in lane-words, or few lane-words still wanted -> edge-organised sparse kernel
+		if (sparse_level && lanes_ok) {
+			KernelTimer kt(st, K_PULL_SPARSE);
+			PGQ_TRY(pull_lanes_level(c, ws, WD, cur->buf.as<u64>(), cur->nz.as<u32>(), ws->seen.as<u64>(),
+			                         nxt->buf.as<u64>(), nxt->nz.as<u32>(), active, stop_lvl, d_cnt));
+			kt.stop();
+		} else if (sparse_level) {
+			PGQ_TRY(pull_sparse(nxt, active, stop_lvl));
+		} else {
+			KernelTimer kt(st, K_PULL);
+			hipLaunchKernelGGL(k_pull<WD>, dim3(pull_grid), dim3(256), 0, st, c->roff, c->radj, c->off,
+			                   c->pull_parts, c->n_pull_parts, cur->buf.as<u64>(), cur->nz.as<u32>(),
+			                   ws->seen.as<u64>(), nxt->buf.as<u64>(), nxt->nz.as<u32>(), active, (int)V, c->hub_threshold,
+			                   stop_lvl, d_cnt);
+			kt.stop();
+		}
+		nxt->dirty = true;
+		hs.queue_valid = false;
+		return PGQ_OK;
+	}
+	// the packed sparse bottom-up level: only after a host round trip (never enqueued ahead), because the packed-word buffer
+	// is sized from the frontier's words
+	int pull_sparse(LevelBuf *nxt, u64 *active, int stop_lvl) {
+		LevelBuf *cur = hs.cur;
+		const u32 cw_cap = last_cw_cap = (u32)std::min<int64_t>((int64_t)sparse_front_words + 64, 0x7FFFFFF0ll);
+		const int bit_words = (int)(((V + 63) / 64) * 2 + 2); // even: 64-vertex blocks
+		PGQ_TRY(ws->cbits.reserve((size_t)bit_words * 4 + 64));
+		PGQ_TRY(ws->cbbase.reserve((size_t)bit_words * 2 + 64));
+		PGQ_TRY(ws->cmeta.reserve((size_t)std::max<int64_t>(V, 1) * sizeof(FrontMeta)));
+		// sized generously once (2 words per vertex) so that growing frontiers do not reallocate per level
+		PGQ_TRY(ws->cwords.reserve(std::max<size_t>((size_t)cw_cap, 2 * (size_t)std::max<int64_t>(V, 1)) * 8));
+		u32 *d_total = reinterpret_cast<u32 *>(&d_cnt->pad); // {frontier vertices, packed words}
+		KernelTimer kt(st, K_PULL_SPARSE);
+		// >= 512 vertices per wavefront: two claims (atomicAdd) per wavefront, keep them few
+		hipLaunchKernelGGL(k_compact_frontier<WD>, dim3(std::min(blocks_for(V / 8 + 1), 2u * ncu)), dim3(256), 0, st,
+		                   cur->nz.as<u32>(), cur->buf.as<u64>(), V, ws->cmeta.as<FrontMeta>(),
+		                   ws->cwords.as<u64>(), ws->cbits.as<u32>(), ws->cbbase.as<u32>(), d_total, cw_cap,
+		                   stop_lvl, d_cnt);
+		const int un = opt.sparse_unroll >= 4 ? 4 : (opt.sparse_unroll >= 2 ? 2 : 1), pw = std::max(1, std::min(3, opt.sparse_pw));
+		if (un == 4 && pw == 1) launch_pull_sparse<4, 1>(nxt, active, bit_words, stop_lvl);
+		else if (un == 4 && pw == 2) launch_pull_sparse<4, 2>(nxt, active, bit_words, stop_lvl);
+		else if (un == 4) launch_pull_sparse<4, 3>(nxt, active, bit_words, stop_lvl);
+		else if (un == 2 && pw == 1) launch_pull_sparse<2, 1>(nxt, active, bit_words, stop_lvl);
+		else if (un == 2) launch_pull_sparse<2, 2>(nxt, active, bit_words, stop_lvl);
+		else launch_pull_sparse<1, 2>(nxt, active, bit_words, stop_lvl);
+		kt.stop();
+		return PGQ_OK;
+	}
+	// Graphs whose frontier bit map + block bases fit in LDS beside the accumulators run 1024-thread workgroups that keep
+	// them there (SF100: 56 KB + 28 KB).  The statics are one per kernel instantiation.
+	template <int UN, int PW>
+	void launch_pull_sparse(LevelBuf *nxt, u64 *active, int bit_words, int stop_lvl) {
+		const size_t dyn_bytes = (size_t)bit_words * 4 + (size_t)bit_words * 2;
+		auto kfn = k_pull_sparse<WD, UN, 16, PW>;
+		static std::atomic<size_t> static_lds { 0 };
+		if (!static_lds) {
+			hipFuncAttributes fa;
+			static_lds = hipFuncGetAttributes(&fa, (const void *)kfn) == hipSuccess ? fa.sharedSizeBytes + 1 : 1;
+		}
+		const bool lds_map = opt.sparse_lds && static_lds > 1 && static_lds + dyn_bytes + 256 <= 160 * 1024;
+		if (lds_map) {
+			static std::atomic<size_t> attr_bytes { 0 };
+			if (attr_bytes < dyn_bytes) {
+				(void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - static_lds));
+				attr_bytes = 160 * 1024;
+			}
+		} else {
+			kfn = k_pull_sparse<WD, UN, 4, PW>;
+		}
+		hipLaunchKernelGGL(kfn, dim3(lds_map ? (unsigned)ncu : pull_grid), dim3(lds_map ? 1024 : 256), lds_map ? dyn_bytes : 0, st,
+		                   c->roff, c->radj, c->rown, c->off, c->pull_parts, c->n_pull_parts, ws->cbits.as<u32>(), ws->cbbase.as<u32>(),
+		                   ws->cmeta.as<FrontMeta>(), ws->cwords.as<u64>(), ws->seen.as<u64>(), nxt->buf.as<u64>(), nxt->nz.as<u32>(),
+		                   active, bit_words, opt.sparse_spill, stop_lvl, d_cnt);
+	}
+	// -- detect finished pairs (iterativelength.cpp:119-129) in the frontier just produced, rebuild the active-lane mask
+	void detect(int t, LevelBuf *nxt, bool spec) {
+		KernelTimer kt(st, K_DETECT);
+		const int un = opt.detect_unroll >= 4 ? 4 : (opt.detect_unroll >= 2 ? 2 : 1);
+		const dim3 grid(std::min(blocks_for((hi - lo + un - 1) / un, 1024), (unsigned)std::min(kOpenGrid, std::max(1, opt.detect_grid_mult) * ncu / 4)));
+		auto kfn = k_detect<WD, 4>;
+		if (un == 2) kfn = k_detect<WD, 2>;
+		else if (un == 1) kfn = k_detect<WD, 1>;
+		hipLaunchKernelGGL(kfn, grid, dim3(1024), 0, st, lo, hi, sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(),
+		                   base_lane, nxt->buf.as<u64>(), nxt->nz.as<u32>(), t, (u32)std::min<size_t>(words / 2, 0xFFFFFFFFu),
+		                   ws->dpart.as<u64>(), d_cnt);
+		// the words are folded into the mask by the next level's k_level_reset; the host loop reads the mask itself
+		if (spec) hs.pending_fold = true;
+		else hipLaunchKernelGGL(k_open_merge, dim3(1), dim3(256), 0, st, ws->dpart.as<u64>(), act(hs.act_sel ^ 1), WD, d_cnt);
+		kt.stop();
+		hs.act_sel ^= 1;
+	}
 
-		// ---- host state of the level loop (what enqueueing a level changes; snapshotted per enqueued-ahead level) ----
-		struct HostState {
-			LevelBuf *cur;
-			int par, act_sel;
-			bool queue_valid, dirty[2];
-			bool pending_fold; // the last level ended with k_detect and its open-lane words are still in the copies
-		};
-		HostState hs { cur, 0, 0, true, { false, false }, false }; // queue_valid: qbuf[par] describes `cur`
-		auto save_dirty = [&](HostState &h) {
-			for (size_t k = 0; k < 2 && k < ws->pool.size(); k++) h.dirty[k] = ws->pool[k]->dirty;
-		};
-		auto load_dirty = [&](const HostState &h) {
-			for (size_t k = 0; k < 2 && k < ws->pool.size(); k++) ws->pool[k]->dirty = h.dirty[k];
-		};
-		u32 last_cw_cap = 0;
-		int levels_run = 0;
-		std::vector<uint8_t> ran_plan; // the levels this batch really ran: the next batch's plan
+	// Launches the kernels of level t as `bits` says.  spec: the level runs ahead of the host's knowledge — its
+	// k_level_reset logs and checks on the device (SpecArgs) and its memsets are kernels that honour `done`.
+	int enqueue_level(int t, u32 bits, bool spec, int prev_stop) {
+		const bool push = bits & kLvPush, probe_now = bits & kLvProbe;
+		LevelBuf *nxt = level_buf(t, push, hs.cur);
+		level_reset(t, bits, spec, prev_stop);
+		if (probe_now) probe(t);
+		const int stop_lvl = probe_now ? stop : -1; // the expansion returns at once when the probe left <= stop pairs open
+		PGQ_TRY(push ? push_level(nxt, spec, stop_lvl) : pull_level(nxt, bits & kLvSparse, stop_lvl));
+		if (outp.want_te) {
+			if (t >= kMaxTeLevels) return fail(PGQ_ERR_UNSUPPORTED, "traversed-edge accounting supports at most 1023 levels");
+			hipLaunchKernelGGL(k_lane_degree_sums<WD>, dim3(4 * ncu), dim3(256), 0, st, nxt->buf.as<u64>(), c->off, V,
+			                   ws->lane_sums.as<u64>() + (size_t)t * L);
+		}
+		if (!probe_now) detect(t, nxt, spec);
+		hs.cur = nxt; // the caller takes it back when the level turns out not to have counted (deferral)
+		return PGQ_OK;
+	}
 
-		// Launches the kernels of level t as `bits` says.  spec: the level runs ahead of the host's knowledge — its
-		// k_level_reset logs and checks on the device (SpecArgs) and its memsets are kernels that honour `done`.
-		auto enqueue_level = [&](int t, u32 bits, bool spec, int prev_stop) -> int {
-			LevelBuf *cur = hs.cur;
-			// The two-hop probe replaces an expansion for the rows still open — while it is the cheaper of the two: a row walks the
-			// in-lists of its destination's in-neighbours (the graph's mean two-hop walk, at most probe2_cap entries), two
-			// gathered 64-byte sectors per entry, one workgroup per row; a dense level moves E x (8 + 6 WD) bytes.  R-MAT-22
-			// (mean two-hop walk over the cap): 4096 open rows made each probe 2.3 ms where a level takes 1.9, five times per
-			// call, without saving a level — 11 of the cross product's 23.8 ms through the lanes.
-			const int64_t probe2_rows_worth = std::max<int64_t>(
-			    64, (int64_t)((double)E * (8.0 + 6.0 * WD) / (128.0 * std::max(64.0, std::min((double)opt.probe2_cap, c->two_hop_mean)))));
-			const bool push = bits & kLvPush, sparse_level = bits & kLvSparse, probe_now = bits & kLvProbe;
-			LevelBuf *nxt = level_buf(t, push, cur);
-			const bool lanes_level = sparse_level && lanes_ok;
-			u64 *act_cur = &d_cnt->act[hs.act_sel][0], *act_nxt = &d_cnt->act[hs.act_sel ^ 1][0];
-			const int par = hs.par;
-			auto zero_level = [&](LevelBuf *lb) -> int { // the target of a top-down level
-				if (with_paths) return make_zero(lb);
-				if (lb->dirty) { // (its buffers exist and are laid out for this batch: the batch's start saw to both pool members)
-					hipLaunchKernelGGL(k_clean_by_nz, dim3(4 * ncu), dim3(256), 0, st, lb->buf.as<u64>(), lb->nz.as<u32>(), V, (int)WD,
-					                   spec ? (const Counters *)d_cnt : (const Counters *)nullptr);
-					lb->dirty = false;
-				}
-				return PGQ_OK;
-			};
-			// reset the per-level counters but keep the queue counts
-			{
-				const bool zq_cur = push && !hs.queue_valid; // queue rebuilt from the dense frontier below
-				const int q_cur = par, q_nxt = par ^ 1;
-				SpecArgs sp { nullptr, nullptr, t, bits, prev_stop };
-				if (spec) {
-					sp.log = ws->h_log;
-					sp.status = reinterpret_cast<u32 *>(ws->h_log + kSpecLevels + 2);
-				}
-				KernelTimer kt(st, K_QUEUE); // bookkeeping between levels: no byte model, its time counts in the chain
-				hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(256), 0, st, d_cnt, hs.act_sel ^ 1,
-				                   (int)((push && q_nxt == 0) || (zq_cur && q_cur == 0)),
-				                   (int)((push && q_nxt == 1) || (zq_cur && q_cur == 1)), rule, sp,
-				                   hs.pending_fold ? ws->dpart.as<u64>() : (u64 *)nullptr);
-				kt.stop();
-				hs.pending_fold = false;
+	// What the host does with a level's counters once it has them.  Returns 1 when the batch is over (the probe left at
+	// most `stop` rows open: they are deferred), 0 to go on.
+	int post_level(int t, u32 bits, const LevelLog &hc) {
+		const bool push = bits & kLvPush, sparse_level = bits & kLvSparse, probe_now = bits & kLvProbe;
+		const bool lanes_level = sparse_level && lanes_ok;
+		ran_plan.push_back((uint8_t)bits);
+		if (sparse_level && !lanes_level && hc.pad2 > last_cw_cap)
+			return fail(PGQ_ERR_HIP, "internal error: packed frontier holds " + std::to_string(hc.pad2) +
+			                             " words, expected at most " + std::to_string(last_cw_cap));
+		if (probe_now && hc.unresolved <= (u32)stop) { // the expansion kernels returned immediately
+			if (hc.unresolved > 0) {
+				hipLaunchKernelGGL(k_mark_deferred, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, sh->sres.as<int32_t>());
+				outp.deferred = true;
+				S.deferred_pairs += hc.unresolved;
 			}
-			if (probe_now) {
-				KernelTimer kt(st, K_DETECT);
-				// up to one wavefront per row (few rows: the wavefronts of a 64-row chunk share its open rows), at most 8192
-				hipLaunchKernelGGL(k_probe<WD>, dim3(std::min(blocks_for((hi - lo) * 64, 1024), (unsigned)kOpenGrid)), dim3(1024), 0, st, lo, hi,
-				                   sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(), base_lane,
-				                   cur->buf.as<u64>(), cur->nz.as<u32>(), c->roff, c->radj, t, ws->dpart.as<u64>(), d_cnt, std::max(64, opt.probe_max_in));
-				if (opt.probe2 && !with_paths)
-					hipLaunchKernelGGL(k_probe2<WD>, dim3((unsigned)std::min<int64_t>(hi - lo, 2 * ncu)), dim3(1024), 0, st, lo, hi,
-					                   sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(), base_lane,
-					                   cur->buf.as<u64>(), cur->nz.as<u32>(), c->roff, c->radj, t,
-					                   (u32)std::min<int64_t>(probe2_rows_worth,
-					                                          std::max<int64_t>(std::min<int64_t>(L / std::max(1, opt.probe2_div), (hi - lo) / std::max(1, opt.probe2_div)),
-					                                                            std::min<int64_t>(hi - lo, opt.probe2_abs))),
-					                   (int64_t)opt.probe2_cap, ws->dpart.as<u64>(), act_nxt, d_cnt);
-				else
-					hipLaunchKernelGGL(k_open_merge, dim3(1), dim3(256), 0, st, ws->dpart.as<u64>(), act_nxt, WD, d_cnt);
-				kt.stop();
-				std::swap(act_cur, act_nxt); // the expansion below only serves lanes that still have open pairs
-				hs.act_sel ^= 1;
-			}
-			const int stop_lvl = probe_now ? stop : -1; // the expansion returns at once when the probe left <= stop pairs open
-			if (push) {
-				if (!hs.queue_valid) {
-					KernelTimer kt(st, K_QUEUE);
-					hipLaunchKernelGGL(k_queue_from_dense<WD>, dim3(std::min(blocks_for(V), 16u * ncu)), dim3(256), 0, st,
-					                   cur->nz.as<u32>(), V, c->off, pchunk, ws->qbuf[par].as<u64>(), qcap, par, d_cnt);
-					kt.stop();
-				}
-				PGQ_TRY(zero_level(nxt));
-				{
-					KernelTimer kt(st, K_PUSH);
-					hipLaunchKernelGGL(k_push<WD>, dim3(push_grid), dim3(256), 0, st, c->off, c->adj, cur->buf.as<u64>(),
-					                   ws->seen.as<u64>(), nxt->buf.as<u64>(), nxt->nz.as<u32>(), act_cur,
-					                   ws->qbuf[par].as<u64>(), par, qcap, pchunk, stop_lvl, d_cnt);
-					kt.stop();
-				}
-				nxt->dirty = true;
-				if (!with_paths) {
-					KernelTimer kt(st, K_QUEUE);
-					hipLaunchKernelGGL(k_clear_items<WD>, dim3(4 * ncu), dim3(256), 0, st, ws->qbuf[par].as<u64>(), par,
-					                   qcap, cur->buf.as<u64>(), cur->nz.as<u32>(), d_cnt);
-					kt.stop();
-					cur->dirty = false;
-				}
-				hs.queue_valid = false; // rebuilt from nz if the next level is top-down too
-			} else {
-				PGQ_TRY(nxt->buf.reserve(words * 8));
-				PGQ_TRY(nxt->nz.reserve(nz_bytes));
-				if (c->n_pull_hub_vertices > 0) {
-					KernelTimer kt(st, K_PULL_HUB);
-					hipLaunchKernelGGL(k_pull_hub_zero<WD>, dim3(blocks_for(c->n_pull_hub_vertices * WD)), dim3(256), 0,
-					                   st, c->pull_hub_vertices, c->n_pull_hub_vertices, nxt->buf.as<u64>(), stop_lvl, d_cnt);
-					hipLaunchKernelGGL(k_pull_hub<WD>, dim3(blocks_for(c->n_pull_hub_items * 64)), dim3(256), 0, st,
-					                   c->pull_hubs, c->n_pull_hub_items, c->radj, cur->buf.as<u64>(), cur->nz.as<u32>(),
-					                   ws->seen.as<u64>(), nxt->buf.as<u64>(), act_cur, stop_lvl, d_cnt);
-					hipLaunchKernelGGL(k_pull_hub_fold<WD>, dim3(blocks_for(c->n_pull_hub_vertices)), dim3(256), 0, st,
-					                   c->pull_hub_vertices, c->n_pull_hub_vertices, c->off, ws->seen.as<u64>(),
-					                   nxt->buf.as<u64>(), nxt->nz.as<u32>(), stop_lvl, d_cnt);
-					kt.stop();
-				}
-				// frontier sparse in lane-words, or few lane-words still wanted -> edge-organised sparse kernel
-				if (lanes_level) {
-					KernelTimer kt(st, K_PULL_SPARSE);
-					PGQ_TRY(pull_lanes_level(c, ws, WD, cur->buf.as<u64>(), cur->nz.as<u32>(), ws->seen.as<u64>(),
-					                         nxt->buf.as<u64>(), nxt->nz.as<u32>(), act_cur, stop_lvl, d_cnt));
-					kt.stop();
-				} else if (sparse_level) {
-					// only after a host round trip (never enqueued ahead): the packed-word buffer is sized from the frontier's words
-					const u32 cw_cap = (u32)std::min<int64_t>((int64_t)sparse_front_words + 64, 0x7FFFFFF0ll);
-					last_cw_cap = cw_cap;
-					const int bit_words = (int)(((V + 63) / 64) * 2 + 2); // even: 64-vertex blocks
-					PGQ_TRY(ws->cbits.reserve((size_t)bit_words * 4 + 64));
-					PGQ_TRY(ws->cbbase.reserve((size_t)bit_words * 2 + 64));
-					PGQ_TRY(ws->cmeta.reserve((size_t)std::max<int64_t>(V, 1) * sizeof(FrontMeta)));
-					// sized generously once (2 words per vertex) so that growing frontiers do not reallocate per level
-					PGQ_TRY(ws->cwords.reserve(std::max<size_t>((size_t)cw_cap, 2 * (size_t)std::max<int64_t>(V, 1)) * 8));
-					u32 *d_total = reinterpret_cast<u32 *>(&d_cnt->pad); // {frontier vertices, packed words}
-					KernelTimer kt(st, K_PULL_SPARSE);
-					// >= 512 vertices per wavefront: two claims (atomicAdd) per wavefront, keep them few
-					hipLaunchKernelGGL(k_compact_frontier<WD>, dim3(std::min(blocks_for(V / 8 + 1), 2u * ncu)), dim3(256), 0, st,
-					                   cur->nz.as<u32>(), cur->buf.as<u64>(), V, ws->cmeta.as<FrontMeta>(),
-					                   ws->cwords.as<u64>(), ws->cbits.as<u32>(), ws->cbbase.as<u32>(), d_total, cw_cap,
-					                   stop_lvl, d_cnt);
-					// graphs whose frontier bit map + block bases fit in LDS beside the accumulators run 1024-thread
-					// workgroups that keep them there (SF100: 56 KB + 28 KB)
-					const size_t dyn_bytes = (size_t)bit_words * 4 + (size_t)bit_words * 2;
-#define PGQ_LAUNCH_SPARSE(UNR, VR)                                                                                       \
-	do {                                                                                                               \
-		auto kfn = k_pull_sparse<WD, UNR, 16, VR>;                                                                            \
-		static std::atomic<size_t> static_lds { 0 };                                                                   \
-		if (!static_lds) {                                                                                             \
-			hipFuncAttributes fa;                                                                                      \
-			static_lds = hipFuncGetAttributes(&fa, (const void *)kfn) == hipSuccess ? fa.sharedSizeBytes + 1 : 1;      \
-		}                                                                                                              \
-		const bool lds_map = opt.sparse_lds && static_lds > 1 && static_lds + dyn_bytes + 256 <= 160 * 1024;           \
-		if (lds_map) {                                                                                                 \
-			static std::atomic<size_t> attr_bytes { 0 };                                                               \
-			if (attr_bytes < dyn_bytes) {                                                                              \
-				(void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,               \
-				                          (int)(160 * 1024 - static_lds));                                             \
-				attr_bytes = 160 * 1024;                                                                               \
-			}                                                                                                          \
-			hipLaunchKernelGGL(kfn, dim3(ncu), dim3(1024), dyn_bytes, st, c->roff, c->radj, c->rown, c->off, c->pull_parts,      \
-			                   c->n_pull_parts, ws->cbits.as<u32>(), ws->cbbase.as<u32>(), ws->cmeta.as<FrontMeta>(),  \
-			                   ws->cwords.as<u64>(), ws->seen.as<u64>(), nxt->buf.as<u64>(), nxt->nz.as<u32>(),        \
-			                   act_cur, bit_words, opt.sparse_spill, stop_lvl, d_cnt);                                     \
-		} else {                                                                                                       \
-			hipLaunchKernelGGL((k_pull_sparse<WD, UNR, 4, VR>), dim3(pull_grid), dim3(256), 0, st, c->roff, c->radj,       \
-			                   c->rown, c->off, c->pull_parts, c->n_pull_parts, ws->cbits.as<u32>(), ws->cbbase.as<u32>(),      \
-			                   ws->cmeta.as<FrontMeta>(), ws->cwords.as<u64>(), ws->seen.as<u64>(),                    \
-			                   nxt->buf.as<u64>(), nxt->nz.as<u32>(), act_cur, bit_words, opt.sparse_spill, stop_lvl, d_cnt); \
-		}                                                                                                              \
-	} while (0)
-					const int pw = std::max(1, std::min(3, opt.sparse_pw));
-					if (opt.sparse_unroll >= 4) {
-						if (pw == 1) PGQ_LAUNCH_SPARSE(4, 1);
-						else if (pw == 2) PGQ_LAUNCH_SPARSE(4, 2);
-						else PGQ_LAUNCH_SPARSE(4, 3);
-					} else if (opt.sparse_unroll >= 2) {
-						if (pw == 1) PGQ_LAUNCH_SPARSE(2, 1);
-						else PGQ_LAUNCH_SPARSE(2, 2);
-					} else {
-						PGQ_LAUNCH_SPARSE(1, 2);
-					}
-#undef PGQ_LAUNCH_SPARSE
-					kt.stop();
-				} else {
-					KernelTimer kt(st, K_PULL);
-					hipLaunchKernelGGL(k_pull<WD>, dim3(pull_grid), dim3(256), 0, st, c->roff, c->radj, c->off,
-					                   c->pull_parts, c->n_pull_parts, cur->buf.as<u64>(), cur->nz.as<u32>(),
-					                   ws->seen.as<u64>(), nxt->buf.as<u64>(), nxt->nz.as<u32>(), act_cur, (int)V, chunk,
-					                   stop_lvl, d_cnt);
-					kt.stop();
-				}
-				nxt->dirty = true;
-				hs.queue_valid = false;
-			}
-			if (outp.want_te) {
-				if (t >= kMaxTeLevels) return fail(PGQ_ERR_UNSUPPORTED, "traversed-edge accounting supports at most 1023 levels");
-				hipLaunchKernelGGL(k_lane_degree_sums<WD>, dim3(4 * ncu), dim3(256), 0, st, nxt->buf.as<u64>(), c->off, V,
-				                   ws->lane_sums.as<u64>() + (size_t)t * L);
-			}
-			if (!probe_now) {
-				// -- detect finished pairs (iterativelength.cpp:119-129) in the frontier just produced, rebuild the active-lane mask
-				KernelTimer kt(st, K_DETECT);
-				const int un = opt.detect_unroll >= 4 ? 4 : (opt.detect_unroll >= 2 ? 2 : 1);
-				const dim3 grid(std::min(blocks_for((hi - lo + un - 1) / un, 1024), (unsigned)std::min(kOpenGrid, std::max(1, opt.detect_grid_mult) * ncu / 4)));
-#define PGQ_DETECT(UNR)                                                                                                  \
-	hipLaunchKernelGGL((k_detect<WD, UNR>), grid, dim3(1024), 0, st, lo, hi, sh->skey.as<u32>(), sh->sdst.as<int32_t>(),   \
-	                   sh->sres.as<int32_t>(), base_lane, nxt->buf.as<u64>(), nxt->nz.as<u32>(), t,                       \
-	                   (u32)std::min<size_t>(words / 2, 0xFFFFFFFFu), ws->dpart.as<u64>(), d_cnt)
-				if (un == 4) PGQ_DETECT(4);
-				else if (un == 2) PGQ_DETECT(2);
-				else PGQ_DETECT(1);
-#undef PGQ_DETECT
-				// the words are folded into the mask by the next level's k_level_reset; the host loop reads the mask itself
-				if (spec) hs.pending_fold = true;
-				else hipLaunchKernelGGL(k_open_merge, dim3(1), dim3(256), 0, st, ws->dpart.as<u64>(), act_nxt, WD, d_cnt);
-				kt.stop();
-				hs.act_sel ^= 1;
-			}
-			hs.cur = nxt; // the caller takes it back when the level turns out not to have counted (deferral)
-			return PGQ_OK;
-		};
-
-		// What the host does with a level's counters once it has them.  Returns 1 when the batch is over (the probe left at
-		// most `stop` rows open: they are deferred), 0 to go on.
-		auto post_level = [&](int t, u32 bits, const LevelLog &hc) -> int {
-			const bool push = bits & kLvPush, sparse_level = bits & kLvSparse, probe_now = bits & kLvProbe;
-			const bool lanes_level = sparse_level && lanes_ok;
-			ran_plan.push_back((uint8_t)bits);
-			if (sparse_level && !lanes_level && hc.pad2 > last_cw_cap)
-				return fail(PGQ_ERR_HIP, "internal error: packed frontier holds " + std::to_string(hc.pad2) +
-				                             " words, expected at most " + std::to_string(last_cw_cap));
-			if (probe_now && hc.unresolved <= (u32)stop) { // the expansion kernels returned immediately
-				if (hc.unresolved > 0) {
-					hipLaunchKernelGGL(k_mark_deferred, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, sh->sres.as<int32_t>());
-					outp.deferred = true;
-					S.deferred_pairs += hc.unresolved;
-				}
-				return 1;
-			}
-			if (push) S.push_levels++;
-			else S.pull_levels++;
-			S.levels++;
-			S.edges_scanned += (int64_t)hc.edges_scanned;
-			S.word_gathers += (int64_t)hc.word_gathers;
-			S.frontier_vertices += (int64_t)hc.front_vertices;
-			// algorithmic bytes of this level's kernels
-			if (push) {
-				S.algo_bytes[K_PUSH] += (double)hc.edges_scanned * 4.0 + (double)hc.word_gathers * 16.0;
-			} else {
-				// per scanned in-edge: 4 B adjacency + 4 B non-empty-word mask; per gathered lane-word 8 B; per vertex:
-				// offsets 16 B + seen/next words 16*WD B + mask 4 B (the sparse variant reads seen twice: 24*WD)
-				if (lanes_level) // 4 B per in-slot, one 16-byte record per in-edge leaving a frontier vertex, seen read + next/seen written
-					S.algo_bytes[K_PULL_SPARSE] += (double)hc.edges_scanned * 4.0 + (double)hc.word_gathers * 16.0 + (double)V * (4.0 + 24.0 * WD);
-				else
-					S.algo_bytes[sparse_level ? K_PULL_SPARSE : K_PULL] +=
-					    (double)hc.edges_scanned * 8.0 + (double)hc.word_gathers * 8.0 +
-					    (double)V * (20.0 + 16.0 * WD) + (sparse_level ? (double)hc.word_gathers * 8.0 + (double)V * 4.0 : 0.0);
-			}
-			// detection / probe: the rows' result words, lane ids and destinations (12 B per row of the batch) and, per row
-			// still open, the 4-byte mask look-up and the 8-byte frontier word (detection), or its destination's in-list with
-			// the two look-ups per entry (probe: mean in-degree x 16 B)
-			S.algo_bytes[K_DETECT] += (double)(hi - lo) * 12.0 +
-			                          (double)open_before * (probe_now ? (double)E / (double)std::max<int64_t>(V, 1) * 16.0 : 12.0);
-			if (opt.trace)
-				fprintf(stderr, "[pgq] batch %d level %d %s%s WD=%d front_v=%u front_e=%llu scanned=%llu gathers=%llu unresolved=%u push_ms=%.3f pull_ms=%.3f\n",
-				        b, t, probe_now ? "probe+" : "", push ? "push" : (lanes_level ? "pull_lanes" : (sparse_level ? "pull_sparse" : "pull")), WD, hc.front_vertices, (unsigned long long)hc.front_edges,
-				        (unsigned long long)hc.edges_scanned, (unsigned long long)hc.word_gathers, hc.unresolved,
-				        S.kernel_ms[K_PUSH], S.kernel_ms[K_PULL] + S.kernel_ms[K_PULL_HUB] + S.kernel_ms[K_PULL_SPARSE]);
-			open_before = hc.unresolved;
-			levels_run = t;
-			return 0;
-		};
-
-		LevelLog last {}; // the counters after the last level the host knows about
-		bool batch_over = false;
-		int t = 1;
-		// ---- levels enqueued ahead under the plan of the batch before ----
+			return 1;
+		}
+		if (push) S.push_levels++;
+		else S.pull_levels++;
+		S.levels++;
+		S.edges_scanned += (int64_t)hc.edges_scanned;
+		S.word_gathers += (int64_t)hc.word_gathers;
+		S.frontier_vertices += (int64_t)hc.front_vertices;
+		// algorithmic bytes of this level's kernels
+		if (push) {
+			S.algo_bytes[K_PUSH] += (double)hc.edges_scanned * 4.0 + (double)hc.word_gathers * 16.0;
+		} else {
+			// per scanned in-edge: 4 B adjacency + 4 B non-empty-word mask; per gathered lane-word 8 B; per vertex:
+			// offsets 16 B + seen/next words 16*WD B + mask 4 B (the sparse variant reads seen twice: 24*WD)
+			if (lanes_level) // 4 B per in-slot, one 16-byte record per in-edge leaving a frontier vertex, seen read + next/seen written
+				S.algo_bytes[K_PULL_SPARSE] += (double)hc.edges_scanned * 4.0 + (double)hc.word_gathers * 16.0 + (double)V * (4.0 + 24.0 * WD);
+			else
+				S.algo_bytes[sparse_level ? K_PULL_SPARSE : K_PULL] +=
+				    (double)hc.edges_scanned * 8.0 + (double)hc.word_gathers * 8.0 +
+				    (double)V * (20.0 + 16.0 * WD) + (sparse_level ? (double)hc.word_gathers * 8.0 + (double)V * 4.0 : 0.0);
+		}
+		// detection / probe: the rows' result words, lane ids and destinations (12 B per row of the batch) and, per row
+		// still open, the 4-byte mask look-up and the 8-byte frontier word (detection), or its destination's in-list with
+		// the two look-ups per entry (probe: mean in-degree x 16 B)
+		S.algo_bytes[K_DETECT] += (double)(hi - lo) * 12.0 +
+		                          (double)open_before * (probe_now ? (double)E / (double)std::max<int64_t>(V, 1) * 16.0 : 12.0);
+		if (opt.trace)
+			fprintf(stderr, "[pgq] batch %d level %d %s%s WD=%d front_v=%u front_e=%llu scanned=%llu gathers=%llu unresolved=%u push_ms=%.3f pull_ms=%.3f\n",
+			        b, t, probe_now ? "probe+" : "", push ? "push" : (lanes_level ? "pull_lanes" : (sparse_level ? "pull_sparse" : "pull")), WD, hc.front_vertices, (unsigned long long)hc.front_edges,
+			        (unsigned long long)hc.edges_scanned, (unsigned long long)hc.word_gathers, hc.unresolved,
+			        S.kernel_ms[K_PUSH], S.kernel_ms[K_PULL] + S.kernel_ms[K_PULL_HUB] + S.kernel_ms[K_PULL_SPARSE]);
+		open_before = hc.unresolved;
+		levels_run = t;
+		return 0;
+	}
+	// the plan of the last batch of this width.  A plan whose FIRST level cannot be enqueued — a packed sparse
+	// level without the lane-list kernel — buys nothing: the logging launch and its wait would only be added in front of the
+	// round-trip loop.
+	std::vector<uint8_t> take_plan() const {
 		std::vector<uint8_t> plan;
 		if (spec_ok) {
 			std::lock_guard<std::mutex> g(c->plan_lock);
 			plan = c->level_plan[plan_slot];
 		}
-		bool have_last = false;
-		// (a plan whose FIRST level cannot be enqueued — a packed sparse level without the lane-list kernel — buys nothing: the
-		// logging launch and its wait would only be added in front of the round-trip loop)
 		if (!plan.empty() && (plan[0] & kLvSparse) && !lanes_ok) plan.clear();
-		if (!plan.empty()) {
-			std::vector<HostState> snaps;
-			u32 *status = reinterpret_cast<u32 *>(ws->h_log + kSpecLevels + 2);
-			status[0] = status[1] = 0;
-			int prev_stop = -1, K = 0;
-			for (; K < (int)plan.size() && K < kSpecLevels; K++) {
-				const u32 bits = plan[(size_t)K];
-				if ((bits & kLvSparse) && !lanes_ok) break; // k_pull_sparse sizes a buffer from the frontier's words: not ahead of the host
-				save_dirty(hs);
-				snaps.push_back(hs);
-				PGQ_TRY(enqueue_level(K + 1, bits, true, prev_stop));
-				prev_stop = (bits & kLvProbe) ? stop : -1;
-			}
-			save_dirty(hs);
-			snaps.push_back(hs);
-			{ // behind the last enqueued level: log its counters, say whether the batch is over
-				SpecArgs sp { ws->h_log, status, K + 1, kLvNone, prev_stop };
-				hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(256), 0, st, d_cnt, hs.act_sel ^ 1, 0, 0, rule, sp,
-				                   hs.pending_fold ? ws->dpart.as<u64>() : (u64 *)nullptr);
-			}
-			PGQ_WAIT(st);
-			KernelTimer::flush();
-			S.spec_batches++;
-			const u32 code = status[0];
-			const int t_stop = (int)status[1]; // levels 1 .. t_stop - 1 ran; log[k] = the counters after level k
-			if (code == 0 || t_stop < 1 || t_stop > K + 1) return fail(PGQ_ERR_HIP, "internal error: enqueued-ahead levels left no status");
-			open_before = (u32)(hi - lo);
-			for (int k = 1; k < t_stop && !batch_over; k++) {
-				const int r = post_level(k, plan[(size_t)k - 1], ws->h_log[k]);
-				if (r < 0) return r;
-				batch_over = r == 1;
-			}
-			// what the device really did: levels 1 .. t_stop - 1 (the kernels enqueued behind them returned at once)
-			hs = snaps[(size_t)t_stop - 1];
-			hs.pending_fold = false; // the k_level_reset that called the levels off had folded them already
-			load_dirty(hs);
-			if (!batch_over) {
-				if (code == 1) {
-					batch_over = true; // nothing open or an empty frontier: the loop below would not be entered
-				} else { // the plan did not fit (2) or ran out (3): the host takes over at level t_stop
-					last = ws->h_log[t_stop - 1];
-					have_last = true;
-					t = t_stop;
-					PGQ_HIP_TRY(hipMemsetAsync(&d_cnt->done, 0, 4, st));
-					S.spec_aborts++;
-				}
-			}
-			if (t_stop >= 1) S.spec_levels += t_stop - 1;
+		return plan;
+	}
+	void store_plan() {
+		if (!spec_ok || ran_plan.empty()) return;
+		// (the last batch of a call may hold a handful of lanes: its levels are not what the next FULL batch will run)
+		const bool full = (U - (int64_t)base_lane) * 2 >= L;
+		std::lock_guard<std::mutex> g(c->plan_lock);
+		if (full || c->level_plan[plan_slot].empty()) c->level_plan[plan_slot] = ran_plan;
+	}
+
+	// The levels of `plan` enqueued ahead of the host, then one wait for all of them.  Returns 1 when the batch is over, 0
+	// when the host takes over at level `t` with the counters `last`.
+	int levels_ahead(const std::vector<uint8_t> &plan, LevelLog &last, int &t) {
+		std::vector<HostState> snaps;
+		u32 *status = spec_status();
+		status[0] = status[1] = 0;
+		int prev_stop = -1, K = 0;
+		for (; K < (int)plan.size() && K < kSpecLevels; K++) {
+			const u32 bits = plan[(size_t)K];
+			if ((bits & kLvSparse) && !lanes_ok) break; // k_pull_sparse sizes a buffer from the frontier's words: not ahead of the host
+			snaps.push_back(snapshot());
+			PGQ_TRY(enqueue_level(K + 1, bits, true, prev_stop));
+			prev_stop = (bits & kLvProbe) ? stop : -1;
 		}
-		if (!batch_over && !have_last) {
-			PGQ_HIP_TRY(hipMemcpyAsync(ws->h_cnt, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
-			PGQ_WAIT(st);
-			last.front_edges = ws->h_cnt->front_edges;
-			last.front_words = ws->h_cnt->front_words;
-			last.front_vertices = ws->h_cnt->front_vertices;
-			last.unresolved = (u32)(hi - lo);
-			last.nzw = WD;
-			open_before = last.unresolved;
+		snaps.push_back(snapshot());
+		// behind the last enqueued level: log its counters, say whether the batch is over
+		const SpecArgs sp { ws->h_log, status, K + 1, kLvNone, prev_stop };
+		hipLaunchKernelGGL(k_level_reset, dim3(1), dim3(256), 0, st, d_cnt, hs.act_sel ^ 1, 0, 0, rule, sp,
+		                   hs.pending_fold ? ws->dpart.as<u64>() : (u64 *)nullptr);
+		PGQ_WAIT(st);
+		KernelTimer::flush();
+		S.spec_batches++;
+		const u32 code = status[0];
+		const int t_stop = (int)status[1]; // levels 1 .. t_stop - 1 ran; log[k] = the counters after level k
+		if (code == 0 || t_stop < 1 || t_stop > K + 1) return fail(PGQ_ERR_HIP, "internal error: enqueued-ahead levels left no status");
+		bool over = false;
+		for (int k = 1; k < t_stop && !over; k++) {
+			const int r = post_level(k, plan[(size_t)k - 1], ws->h_log[k]);
+			if (r < 0) return r;
+			over = r == 1;
 		}
-		// ---- one host round trip per level ----
-		for (; !batch_over && last.unresolved > 0 && last.front_edges > 0; t++) {
+		// what the device really did: levels 1 .. t_stop - 1 (the kernels enqueued behind them returned at once)
+		restore(snaps[(size_t)t_stop - 1]);
+		hs.pending_fold = false; // the k_level_reset that called the levels off had folded them already
+		over = over || code == 1; // code 1: nothing open or an empty frontier, the round-trip loop would not be entered
+		if (!over) { // the plan did not fit (2) or ran out (3): the host takes over at level t_stop
+			last = ws->h_log[t_stop - 1];
+			t = t_stop;
+			PGQ_HIP_TRY(hipMemsetAsync(&d_cnt->done, 0, 4, st));
+			S.spec_aborts++;
+		}
+		S.spec_levels += t_stop - 1;
+		return over ? 1 : 0;
+	}
+	int read_counters(LevelLog &last) {
+		PGQ_HIP_TRY(hipMemcpyAsync(ws->h_cnt, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
+		PGQ_WAIT(st);
+		const Counters &hc = *ws->h_cnt;
+		u32 nzw = 0;
+		for (int w = 0; w < WD; w++) nzw += hc.act[hs.act_sel][w] != 0;
+		last = LevelLog { hc.front_edges, hc.edges_scanned, hc.word_gathers, hc.front_vertices, hc.unresolved, hc.front_words, hc.pad2, nzw, 0 };
+		return PGQ_OK;
+	}
+	// one host round trip per level, from level t on
+	int round_trips(LevelLog last, int t) {
+		for (; last.unresolved > 0 && last.front_edges > 0; t++) {
 			const u32 bits = decide_level(rule, last.front_edges, last.front_words, last.front_vertices, last.unresolved,
 			                              t == 1 ? WD : (int)last.nzw);
 			sparse_front_words = last.front_words;
 			PGQ_TRY(enqueue_level(t, bits, false, -1));
-			PGQ_HIP_TRY(hipMemcpyAsync(ws->h_cnt, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st));
-			PGQ_WAIT(st);
+			PGQ_TRY(read_counters(last));
 			KernelTimer::flush();
-			const Counters &hc = *ws->h_cnt;
-			last.front_edges = hc.front_edges;
-			last.edges_scanned = hc.edges_scanned;
-			last.word_gathers = hc.word_gathers;
-			last.front_vertices = hc.front_vertices;
-			last.unresolved = hc.unresolved;
-			last.front_words = hc.front_words;
-			last.pad2 = hc.pad2;
-			last.nzw = 0;
-			for (int w = 0; w < WD; w++) last.nzw += hc.act[hs.act_sel][w] != 0;
 			const int r = post_level(t, bits, last);
-			if (r < 0) return r;
-			batch_over = r == 1;
+			if (r != 0) return r;
 		}
-		if (spec_ok && !ran_plan.empty()) {
-			// (the last batch of a call may hold a handful of lanes: its levels are not what the next FULL batch will run)
-			const bool full = (U - (int64_t)base_lane) * 2 >= L;
-			std::lock_guard<std::mutex> g(c->plan_lock);
-			if (full || c->level_plan[plan_slot].empty()) c->level_plan[plan_slot] = ran_plan;
-		}
-		cur = hs.cur;
-		ws->pool_trusted = true; // the dirty flags of the sparse pool say what the device did
-		if (outp.want_te)
-			hipLaunchKernelGGL(k_pair_te, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, sh->skey.as<u32>(),
-			                   sh->sres.as<int32_t>(), base_lane, ws->lane_sums.as<u64>(), (int)L, levels_run + 1,
-			                   sh->ste.as<int64_t>());
-		// -- paths for this batch
-		if (with_paths) {
-			const int64_t cnt_pairs = hi - lo;
-			h_res.resize(cnt_pairs);
-			h_off.resize(cnt_pairs);
-			PGQ_HIP_TRY(hipMemcpyAsync(h_res.data(), sh->sres.as<int32_t>() + lo, (size_t)cnt_pairs * 4,
-			                           hipMemcpyDeviceToHost, st));
-			PGQ_WAIT(st);
-			int64_t need = child_base;
-			for (int64_t i = 0; i < cnt_pairs; i++) {
-				h_off[i] = need;
-				if (h_res[i] > 0) need += 2 * (int64_t)h_res[i] + 1;
-			}
-			PGQ_HIP_TRY(hipMemcpyAsync(sh->soff.as<int64_t>() + lo, h_off.data(), (size_t)cnt_pairs * 8,
-			                           hipMemcpyHostToDevice, st));
-			bool fits = true;
-			if (d_child_ext) {
-				fits = need <= child_cap_ext;
-			} else if ((size_t)need * 8 > sh->child.cap) {
-				// grow, preserving what earlier batches wrote
-				PGQ_TRY(grow_keeping(sh->child, (size_t)need * 8 * 2, (size_t)child_base * 8, st));
-				d_child = sh->child.as<int64_t>();
-			}
-			if (!d_child_ext) d_child = sh->child.as<int64_t>();
-			if (fits && need > child_base) {
-				std::vector<const u64 *> tab((size_t)levels_run + 1);
-				for (int t = 0; t <= levels_run; t++) tab[t] = ws->levels[t]->buf.as<u64>();
-				PGQ_TRY(sh->levels_tab.reserve(tab.size() * sizeof(u64 *)));
-				PGQ_HIP_TRY(hipMemcpyAsync(sh->levels_tab.p, tab.data(), tab.size() * sizeof(u64 *), hipMemcpyHostToDevice, st));
-				KernelTimer kt(st, K_RECON);
-				hipLaunchKernelGGL(k_reconstruct<WD>, dim3(blocks_for(cnt_pairs * 64)), dim3(256), 0, st, lo, hi,
-				                   sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(),
-				                   sh->soff.as<int64_t>(), base_lane, (const u64 *const *)sh->levels_tab.p, c->roff,
-				                   c->radj, c->off, c->adj, c->edge_ids, d_child);
-				kt.stop();
-				PGQ_WAIT(st); // tab is a stack vector
-				KernelTimer::flush();
-			}
-			if (!fits) child_overflow = true;
-			child_base = need;
-		}
+		return PGQ_OK;
 	}
-	if (with_paths && b0 == 0) {
-		// src == dst rows: [src]
-		const int64_t lo = bs[nb + 1], hi = bs[nb + 2];
-		if (hi > lo) {
-			int64_t need = child_base + (hi - lo);
-			bool fits = true;
-			if (d_child_ext) fits = need <= child_cap_ext;
-			else if ((size_t)need * 8 > sh->child.cap) {
-				PGQ_TRY(grow_keeping(sh->child, (size_t)need * 8, (size_t)child_base * 8, st));
-			}
-			if (!d_child_ext) d_child = sh->child.as<int64_t>();
-			if (fits) {
-				hipLaunchKernelGGL(k_trivial_paths, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi,
+
+	// Room for `need` elements of path lists: the caller's buffer, or sh->child grown to `grow` elements keeping what
+	// earlier batches wrote.  `fits` is false when the caller's buffer is too small.
+	int child_room(int64_t need, int64_t grow, bool &fits) {
+		fits = !d_child_ext || need <= child_cap_ext;
+		if (!d_child_ext) {
+			if ((size_t)need * 8 > sh->child.cap) PGQ_TRY(grow_keeping(sh->child, (size_t)grow * 8, (size_t)child_base * 8, st));
+			d_child = sh->child.as<int64_t>();
+		}
+		if (!fits) child_overflow = true;
+		return PGQ_OK;
+	}
+	int batch_paths() {
+		const int64_t cnt_pairs = hi - lo;
+		h_res.resize(cnt_pairs);
+		h_off.resize(cnt_pairs);
+		PGQ_HIP_TRY(hipMemcpyAsync(h_res.data(), sh->sres.as<int32_t>() + lo, (size_t)cnt_pairs * 4, hipMemcpyDeviceToHost, st));
+		PGQ_WAIT(st);
+		int64_t need = child_base;
+		for (int64_t i = 0; i < cnt_pairs; i++) {
+			h_off[i] = need;
+			if (h_res[i] > 0) need += 2 * (int64_t)h_res[i] + 1;
+		}
+		PGQ_HIP_TRY(hipMemcpyAsync(sh->soff.as<int64_t>() + lo, h_off.data(), (size_t)cnt_pairs * 8, hipMemcpyHostToDevice, st));
+		bool fits;
+		PGQ_TRY(child_room(need, 2 * need, fits));
+		if (fits && need > child_base) {
+			std::vector<const u64 *> tab((size_t)levels_run + 1);
+			for (int t = 0; t <= levels_run; t++) tab[t] = ws->levels[t]->buf.as<u64>();
+			PGQ_TRY(sh->levels_tab.reserve(tab.size() * sizeof(u64 *)));
+			PGQ_HIP_TRY(hipMemcpyAsync(sh->levels_tab.p, tab.data(), tab.size() * sizeof(u64 *), hipMemcpyHostToDevice, st));
+			KernelTimer kt(st, K_RECON);
+			hipLaunchKernelGGL(k_reconstruct<WD>, dim3(blocks_for(cnt_pairs * 64)), dim3(256), 0, st, lo, hi,
+			                   sh->skey.as<u32>(), sh->sdst.as<int32_t>(), sh->sres.as<int32_t>(),
+			                   sh->soff.as<int64_t>(), base_lane, (const u64 *const *)sh->levels_tab.p, c->roff,
+			                   c->radj, c->off, c->adj, c->edge_ids, d_child);
+			kt.stop();
+			PGQ_WAIT(st); // tab is a stack vector
+			KernelTimer::flush();
+		}
+		child_base = need;
+		return PGQ_OK;
+	}
+	// src == dst rows: [src]
+	int trivial_paths() {
+		const int64_t r_lo = sh->h_bstart[nb + 1], r_hi = sh->h_bstart[nb + 2];
+		if (r_hi > r_lo) {
+			const int64_t need = child_base + (r_hi - r_lo);
+			bool fits;
+			PGQ_TRY(child_room(need, need, fits));
+			if (fits)
+				hipLaunchKernelGGL(k_trivial_paths, dim3(blocks_for(r_hi - r_lo)), dim3(256), 0, st, r_lo, r_hi,
 				                   sh->ssrc.as<int32_t>(), child_base, sh->soff.as<int64_t>(), d_child);
-			} else {
-				child_overflow = true;
-			}
 			child_base = need;
 		}
 		outp.child_used = child_base;
 		// not an early return: the straggler pass still has to run so that the lengths are complete and child_used
 		// reports everything the caller must provide
 		if (child_overflow) outp.overflow = true;
+		return PGQ_OK;
 	}
-	PGQ_WAIT(st); // other workers / the caller read sres next
-	KernelTimer::flush();
-	return PGQ_OK;
-}
+};
 
 int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
                  bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp,
@@ -2436,12 +2435,12 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	memo_record(c, n, d_src, d_dst, memo);
 	auto run = [&](Workspace *priv, int b0, int bstride, SearchOutput &o) -> int {
 		switch (wd) {
-		case 1: return run_batches<1>(c, ws, priv, b0, bstride, n, U, with_paths, d_child_ext, child_cap_ext, o);
-		case 2: return run_batches<2>(c, ws, priv, b0, bstride, n, U, with_paths, d_child_ext, child_cap_ext, o);
-		case 4: return run_batches<4>(c, ws, priv, b0, bstride, n, U, with_paths, d_child_ext, child_cap_ext, o);
-		case 8: return run_batches<8>(c, ws, priv, b0, bstride, n, U, with_paths, d_child_ext, child_cap_ext, o);
-		case 16: return run_batches<16>(c, ws, priv, b0, bstride, n, U, with_paths, d_child_ext, child_cap_ext, o);
-		default: return run_batches<32>(c, ws, priv, b0, bstride, n, U, with_paths, d_child_ext, child_cap_ext, o);
+		case 1: return LaneBatches<1>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
+		case 2: return LaneBatches<2>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
+		case 4: return LaneBatches<4>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
+		case 8: return LaneBatches<8>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
+		case 16: return LaneBatches<16>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
+		default: return LaneBatches<32>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
 		}
 	};
 	// Independent batches overlap on several streams (one host thread each): hides the per-level host round trip

@@ -675,7 +675,7 @@ def test_distinct_source_estimate_on_grouped_and_shuffled_inputs():
     assert 3000 / 1.7 <= est <= 3000 * 1.7, est
 
 
-# ---- round 5: levels enqueued ahead of the host (pgq_msbfs.hip: run_batches, k_level_reset) ------------------------------
+# ---- round 5: levels enqueued ahead of the host (pgq_msbfs.hip: LaneBatches, k_level_reset) ------------------------------
 
 def _decide_level(rule, fe, fw, fv, unresolved, nzw):
     """decide_level of pgq_search.h: bit 0 top-down, bit 1 sparse bottom-up, bit 2 probe before the level."""
