@@ -74,6 +74,7 @@ def load_hip():
         getattr(L, f).restype = C.c_int64
         getattr(L, f).argtypes = [C.c_void_p]
     L.pgq_csr_w_type.argtypes = [C.c_void_p]
+    L.pgq_csr_pack_k.argtypes = [C.c_void_p]
     L.pgq_iterativelength.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
     L.pgq_shortestpath.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -331,6 +332,11 @@ class DeviceCSR:
     @property
     def device_bytes(self):
         return self.L.pgq_csr_device_bytes(self.h)
+
+    @property
+    def pack_k(self):
+        """Ids per 16-byte group of the lists the pre-pass walks (6 / 5: bit-packed, 4: 32-bit)."""
+        return self.L.pgq_csr_pack_k(self.h)
 
     # -- chunk form (host arrays) ----------------------------------------------
     def _vecs(self, src, dst, src_valid, src_sel, dst_sel, dst_valid, keep):

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "pgq_hip.h"
+#include "pgq_pack.h"
 
 namespace pgq {
 
@@ -162,6 +163,8 @@ struct Options {
 	int meet_grid_mult = 8; // k_meet3 grid = this many times the 8192 one-wavefront workgroups the chip holds (rows per workgroup = n / grid)
 	int meet_layout = 1;    // build the padded adjacency + slot descriptors at upload (the pre-pass needs them)
 	int meet_align = 32;    // entries a padded list is aligned and padded to (4 = one 16-byte group; 16 / 32 = whole 64 / 128-byte lines: -4 % / -6 % on the pre-pass)
+	int meet_pack = 1;      // bit-packed copy of the padded lists (pgq_pack.h), walked by k_meet3 / k_meet3w: 1 = for V <= 2^21 (six 21-bit ids per group); 2 = also V <= 2^25 (five 25-bit ids; not measured on R-MAT-22 yet); 0: 32-bit lists only
+	int meet_pack_align = 8; // groups a packed list is aligned and padded to (8 = one 128-byte line)
 	// round 6: source-centric search for rows that arrive grouped by source (pgq_ball.h: k_ball_segments + k_src_ball)
 	int ball = 1;               // 1: the device decides per call from the number of source runs; 2: always when allowed (tests); 0: never
 	int ball_cap = 1 << 20;     // adjacency entries the two-hop ball of one source may hold; a segment over it leaves its far rows open
@@ -218,6 +221,9 @@ enum KClass {
 
 struct ThreadStats {
 	pgq_stats_t s;
+	// the pre-pass chain's bytes priced at 4 B per list entry whatever the layout (s.algo_bytes charges 16 / K B per entry
+	// walked over the packed lists): what the routing calibration (meet_bpr) is fed, so that packing moves no route
+	double route_bytes = 0;
 	ThreadStats();
 };
 ThreadStats &tstats();
@@ -261,7 +267,7 @@ struct pgq_csr {
 	// two-hop walk needs no offset look-up
 	int32_t *padj = nullptr, *rpadj = nullptr; // 4 x padj_groups / rpadj_groups entries
 	uint2 *fseg = nullptr, *rseg = nullptr;    // V
-	uint4 *fdesc = nullptr, *rdesc = nullptr;  // E (+ 1): slot order of adj / radj
+	uint4 *fdesc = nullptr, *rdesc = nullptr;  // E (+ 1): slot order of adj / radj; 4th word: see ppadj
 	// entries of a vertex's two-hop walk in either direction (sum of its neighbours' list lengths, saturating): the
 	// pair-centric kernels expand the endpoint whose walk is the shorter one (round 4; it was the shorter one-hop list)
 	uint32_t *fwork = nullptr, *rwork = nullptr; // V
@@ -272,6 +278,12 @@ struct pgq_csr {
 	// sixth of the kernel's traffic) and no dependent round trip.  Built when V x 256 B fits `ball_head_mb`; null otherwise.
 	uint4 *rhead = nullptr; // V x 16
 	int64_t padj_groups = 0, rpadj_groups = 0;
+	// the bit-packed copies of padj / rpadj (pgq_pack.h: pack_k ids of pack_w = 128 / pack_k bits per 16-byte group,
+	// lists aligned to `meet_pack_align` groups); a slot descriptor's 4th word is the neighbour's first packed group.  Null
+	// (and pack_k = 4) when meet_pack = 0, V > 2^25 or the group indices would not fit 32 bits: the walks read padj
+	int32_t *ppadj = nullptr, *prpadj = nullptr; // 4 words x ppadj_groups / prpadj_groups
+	int64_t ppadj_groups = 0, prpadj_groups = 0;
+	int pack_k = 4;
 	std::unique_ptr<pgq::Options> opt;   // this handle's own options (pgq_csr_set_option); null: the process-wide set
 	std::atomic<int> meet_far_rows { 1 }; // the last pre-pass call left rows for k_bibfs (it is launched only then; pgq_meet.hip)
 	int64_t hub_threshold = 0;

@@ -43,6 +43,10 @@ constexpr int kMeetWPB = 1;         // wavefronts per k_meet3 workgroup: one, so
 #ifndef PGQ_MEET3_WAVES
 #define PGQ_MEET3_WAVES 8 // wavefronts per SIMD k_meet3<false> is compiled for (64 VGPRs; 4.2 KB of LDS per wavefront: 8 fit)
 #endif
+#ifndef PGQ_MEET3_WAVES_PACKED
+#define PGQ_MEET3_WAVES_PACKED 7 // ... over the packed lists: 72 VGPRs (at 64 the decoded ids and their filter words spilled: 157 us
+                                 // per launch on the SF100-shaped graph against 143 at 7 wavefronts)
+#endif
 #ifndef PGQ_MEET3_DEPTH
 #define PGQ_MEET3_DEPTH 2 // list requests in flight per wavefront
 #endif
@@ -72,6 +76,7 @@ constexpr int kMeetStatSlots = 256; // statistics are spread over slots: 10^4 at
 struct MeetCounters {
 	unsigned long long entries[kMeetStatSlots];  // adjacency entries scanned (both kinds of list)
 	unsigned long long vertices[kMeetStatSlots]; // vertices expanded (offset pairs fetched)
+	unsigned long long walked[kMeetStatSlots];   // ... of the entries: those walked over the packed lists (pgq_pack.h)
 	u32 bad;                    // an id outside [0, V)
 	u32 pad[3];
 };
@@ -123,6 +128,7 @@ struct MeetDevBlock { // device side; all zero between calls
 };
 struct MeetHostBlock { // pinned host memory, written by the last workgroup of the chain
 	unsigned long long entries[3], vertices[3]; // per stage: k_meet3, the bit-map kernel, k_bibfs
+	unsigned long long walked[3];               // per stage: the entries walked over the packed lists
 	u32 bad, count[3];
 	MeetDecision dec;
 	u32 done, count_back;
@@ -150,12 +156,12 @@ __device__ __forceinline__ u32 queue_pos(const MeetQueue &q, u32 j, u32 nf) { re
 __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *fin) {
 	if (!fin) return;
 	__shared__ u32 s_last;
-	__shared__ unsigned long long s_sum[6];
+	__shared__ unsigned long long s_sum[9];
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		__threadfence_system(); // this workgroup's results (possibly in pinned host memory) before its ticket
 		s_last = atomicAdd(&db->ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
-		for (int k = 0; k < 6; k++) s_sum[k] = 0;
+		for (int k = 0; k < 9; k++) s_sum[k] = 0;
 	}
 	__syncthreads();
 	if (!s_last) return;
@@ -165,17 +171,21 @@ __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *f
 	for (int k = threadIdx.x; k < kMeetStatSlots; k += blockDim.x) {
 		const unsigned long long e = __hip_atomic_load(&db->m.entries[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		const unsigned long long v = __hip_atomic_load(&db->m.vertices[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const unsigned long long pw = __hip_atomic_load(&db->m.walked[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		db->m.entries[k] = 0;
 		db->m.vertices[k] = 0;
+		db->m.walked[k] = 0;
 		const int st = k < 192 ? 0 : (k < 224 ? 1 : 2);
 		if (e) atomicAdd(&s_sum[2 * st], e);
 		if (v) atomicAdd(&s_sum[2 * st + 1], v);
+		if (pw) atomicAdd(&s_sum[6 + st], pw);
 	}
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		for (int k = 0; k < 3; k++) {
 			fin->entries[k] = s_sum[2 * k];
 			fin->vertices[k] = s_sum[2 * k + 1];
+			fin->walked[k] = s_sum[6 + k];
 		}
 		fin->bad = __hip_atomic_load(&db->m.bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		for (int k = 0; k < 3; k++) {
@@ -216,10 +226,13 @@ __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *f
 }
 // per-workgroup statistics: one pair of atomics, spread over the slots of the kernel's stage (k_meet3: 192 slots for up to
 // 65,536 workgroups; the bit-map kernels and k_bibfs: 32 each), so that every kernel's algorithmic bytes can be stated
-__device__ __forceinline__ void meet_add_stats(MeetCounters *mc, int stage, unsigned long long entries, unsigned long long vertices) {
+// walked: how many of `entries` were walked over the packed lists (charged 16 / K bytes each instead of 4)
+__device__ __forceinline__ void meet_add_stats(MeetCounters *mc, int stage, unsigned long long entries, unsigned long long vertices,
+                                               unsigned long long walked = 0) {
 	const int base = stage == 0 ? 0 : (stage == 1 ? 192 : 224), cnt = stage == 0 ? 192 : 32;
 	if (entries) atomicAdd(&mc->entries[base + blockIdx.x % cnt], entries);
 	if (vertices) atomicAdd(&mc->vertices[base + blockIdx.x % cnt], vertices);
+	if (walked) atomicAdd(&mc->walked[base + blockIdx.x % cnt], walked);
 }
 
 } // namespace pgq
@@ -236,9 +249,10 @@ namespace pgq {
 // before): a row over it goes to k_meet4d (16 wavefronts), which takes the walk up in the round it was cut in.
 // `go` (nullable): device flag written by k_meet_decide; 0 = the host will take the lane-batched path, do nothing.
 // PATHS: also record the path's inner vertices (MeetPath); the walk then runs from dst over the source-ordered in-lists.
-// BIGV: V > 2^20, the filter folds the higher id bits in.  DEPTH: list requests in flight.
-template <bool PATHS, bool BIGV, int DEPTH>
-__global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH > 2 ? 5 : PGQ_MEET3_WAVES))) void k_meet3(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
+// BIGV: V > 2^20, the filter folds the higher id bits in.  DEPTH: list requests in flight.  K: ids per list group
+// (pgq_pack.h; K > 4: padj / rpadj are the packed copies).  PATHS walks the 32-bit lists.
+template <bool PATHS, bool BIGV, int DEPTH, int K>
+__global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH > 2 ? 5 : (K > 4 ? PGQ_MEET3_WAVES_PACKED : PGQ_MEET3_WAVES)))) void k_meet3(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                   int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                   const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
                                                   const uint4 *__restrict__ fdesc, const uint4 *__restrict__ rdesc,
@@ -248,6 +262,7 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
                                                   const u32 *__restrict__ go, MeetDevBlock *__restrict__ db, MeetQueue q,
                                                   MeetHostBlock *__restrict__ fin) {
 	static_assert(kMeetWPB == 1, "one wavefront per workgroup: the LDS arrays are addressed statically");
+	static_assert(!PATHS || K == 4, "the path flow walks the 32-bit lists");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
 	__shared__ __attribute__((aligned(16))) unsigned char win[64];
 	MeetCounters *const mc = &db->m;
@@ -257,7 +272,7 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 	}
 	const int lane = threadIdx.x & 63;
 	win[lane] = 0;
-	unsigned long long entries = 0; // wave-uniform
+	unsigned long long entries = 0, walked = 0; // wave-uniform
 	u32 vertices = 0;
 	const int64_t wave0 = (int64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
 	const int64_t nwaves = (int64_t)((gridDim.x * blockDim.x) >> 6);
@@ -405,12 +420,12 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 		const unsigned long long rt1 = wall_clock64();
 		const unsigned long long ent_before = entries;
 #endif
-		entries += seg_walk<DEPTH, PATHS>(
+		const unsigned long long e3 = seg_walk<DEPTH, PATHS, K>(
 		    exp_desc, exp_n, 0, 1, xp, win, true, d0, (unsigned long long)cap, capped, resume,
-		    [&](const int4 &v, bool ok, u32 ev) {
+		    [&](const typename SegGroup<K>::type &v, bool ok, u32 ev) {
 			    // a lane past the round's end re-reads real entries of the last list: no mask needed for membership;
 			    // PATHS masks them (their ev is the last list's, so they would even be right, but cost a verification)
-			    const u32 pass = (PATHS && !ok) ? 0u : flt_pass4<BIGV>(bm, v);
+			    const u32 pass = (PATHS && !ok) ? 0u : flt_pass<BIGV>(bm, v);
 			    verify_candidates(R, pass, v, [&](u32 x, int L) {
 				    if constexpr (PATHS) { // backward walk: expanded vertex = second-to-last, entry = the one before it
 					    const u32 y = (u32)__builtin_amdgcn_readlane((int)ev, L);
@@ -423,6 +438,8 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 			    });
 		    },
 		    [&]() { return best != ~0ull; });
+		entries += e3;
+		if (K > 4) walked += e3;
 		const bool found = best != ~0ull;
 #ifdef PGQ_MEET3_ROWTRACE
 		{
@@ -448,7 +465,7 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 			}
 		}
 	}
-	if (lane == 0) meet_add_stats(mc, 0, entries, (unsigned long long)vertices);
+	if (lane == 0) meet_add_stats(mc, 0, entries, (unsigned long long)vertices, walked);
 	meet_finalize(db, fin);
 }
 
@@ -460,7 +477,7 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 // registers (the same loads, cached), the filter is built once in LDS, distances 1 and 2 are tested by every wavefront alike
 // (so that the branches stay uniform across the workgroup), and the two-hop walk is split request by request (seg_walk's
 // stride); the first witness any of them finds ends the row.  Same tests in the same order as k_meet3: same answers.
-template <bool BIGV, int WPB>
+template <bool BIGV, int WPB, int K>
 __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                     int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                     const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
@@ -481,7 +498,7 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 	const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
 	unsigned char *const win = win_all[wib];
 	win[lane] = 0;
-	unsigned long long entries = 0; // wave-uniform
+	unsigned long long entries = 0, walked = 0; // wave-uniform
 	u32 vertices = 0;
 	// every branch below is taken by all wavefronts of the workgroup alike (it depends on the row alone)
 	for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
@@ -597,10 +614,10 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 		// distance 3: the walk's requests dealt out to the WPB wavefronts; every one may request cap / WPB entries
 		bool mine = false, capped = false;
 		int resume = 0;
-		entries += seg_walk<PGQ_MEET3_DEPTH_SMALL, false>(
+		const unsigned long long e3 = seg_walk<PGQ_MEET3_DEPTH_SMALL, false, K>(
 		    exp_desc, exp_n, wib, WPB, xp, win, true, d0, (unsigned long long)cap / WPB, capped, resume,
-		    [&](const int4 &v, bool, u32) {
-			    const u32 pass = flt_pass4<BIGV>(bm, v);
+		    [&](const typename SegGroup<K>::type &v, bool, u32) {
+			    const u32 pass = flt_pass<BIGV>(bm, v);
 			    verify_candidates(R, pass, v, [&](u32, int) {
 				    mine = true;
 				    return true;
@@ -610,6 +627,8 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 			    if (mine) s_found = 1;
 			    return *(volatile u32 *)&s_found != 0u;
 		    });
+		entries += e3;
+		if (K > 4) walked += e3;
 		if (mine) s_found = 1;
 		if (capped) s_capped = 1;
 		__syncthreads();
@@ -622,7 +641,7 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 			}
 		}
 	}
-	if (lane == 0) meet_add_stats(mc, 0, entries, (unsigned long long)vertices);
+	if (lane == 0) meet_add_stats(mc, 0, entries, (unsigned long long)vertices, walked);
 	meet_finalize(db, fin);
 }
 
@@ -1803,30 +1822,46 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 		const bool small = small_call;
 		const int64_t cap = std::max(1, paths ? opt.meet_cap_paths : (small ? opt.meet_cap_small : opt.meet_cap));
 		const bool bigv = c->V > (1 << 20);
+		const int pk = c->pack_k;
 		KernelTimer kt(st, K_MEET);
 		const unsigned resident = (unsigned)device_cus() * 32 / kMeetWPB; // more workgroups than the chip holds at once: up to 8 rounds
 		const dim3 grid((unsigned)std::min<int64_t>((n + kMeetWPB - 1) / kMeetWPB, (int64_t)std::max(1, opt.meet_grid_mult) * resident));
 		MeetHostBlock *fin = last_stage == 0 ? hb : nullptr;
+		// the hop-count walks read the packed lists (pack_k ids per group) when the upload built them; the path flow the
+		// 32-bit ones.  K = 5 only exists beyond 2^21 vertices: always BIGV
+#define PGQ_MEET3K(P, B, D, K, XF, XR)                                                                                   \
+	hipLaunchKernelGGL((k_meet3<P, B, D, K>), grid, dim3(64 * kMeetWPB), 0, st, n, d_src, d_dst, c->V, c->off, c->adj, c->roff, \
+	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, d_out, rec, cap, d_go, db, q[0], fin)
 #define PGQ_MEET3(P, B, D)                                                                                               \
-	hipLaunchKernelGGL((k_meet3<P, B, D>), grid, dim3(64 * kMeetWPB), 0, st, n, d_src, d_dst, c->V, c->off, c->adj, c->roff,  \
-	                   c->radj, c->fdesc, c->rdesc, c->padj, c->rpadj, c->fwork, c->rwork, d_out, rec, cap, d_go, db, q[0], fin)
+	do {                                                                                                                 \
+		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \
+		else if (!P && pk == 5) PGQ_MEET3K(false, true, D, 5, c->ppadj, c->prpadj);                                    \
+		else PGQ_MEET3K(P, B, D, 4, c->padj, c->rpadj);                                                                 \
+	} while (0)
 		if (paths) {
-			if (bigv) PGQ_MEET3(true, true, PGQ_MEET3_DEPTH);
-			else PGQ_MEET3(true, false, PGQ_MEET3_DEPTH);
+			if (bigv) PGQ_MEET3K(true, true, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
+			else PGQ_MEET3K(true, false, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
 		} else if (small && n <= (int64_t)opt.meet_wide_rows && (opt.meet_wide_rows_always || (double)c->E * 4.0 > 256e6)) {
 			// chunk-sized calls on a graph whose adjacency does not fit the Infinity Cache (a list request is a DRAM round trip,
 			// ~3.5 us under load): several wavefronts per row (k_meet3w: 97 VGPRs, four wavefronts per SIMD = 4096 on the chip) —
 			// four while all rows are resident at once, else two.  Measured: R-MAT-22 x 1024 pairs 49 -> 41 us; the SF100-shaped
 			// graph (160 MB of padded lists, cache resident) 24.1 -> 25.5 us at 1024 rows, 29.1 -> 29.7 at 2048: not taken there
+#define PGQ_MEET3WK(B, W, K, XF, XR)                                                                                      \
+	hipLaunchKernelGGL((k_meet3w<B, W, K>), dim3((unsigned)n), dim3(64 * W), 0, st, n, d_src, d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
+	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, d_out, cap, d_go, db, q[0], fin)
 #define PGQ_MEET3W(B, W)                                                                                                  \
-	hipLaunchKernelGGL((k_meet3w<B, W>), dim3((unsigned)n), dim3(64 * W), 0, st, n, d_src, d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
-	                   c->fdesc, c->rdesc, c->padj, c->rpadj, c->fwork, c->rwork, d_out, cap, d_go, db, q[0], fin)
+	do {                                                                                                                 \
+		if (pk == 6) PGQ_MEET3WK(B, W, 6, c->ppadj, c->prpadj);                                                        \
+		else if (pk == 5) PGQ_MEET3WK(true, W, 5, c->ppadj, c->prpadj);                                                \
+		else PGQ_MEET3WK(B, W, 4, c->padj, c->rpadj);                                                                   \
+	} while (0)
 			const bool four = n * 4 <= (int64_t)device_cus() * 16;
 			if (bigv && four) PGQ_MEET3W(true, 4);
 			else if (bigv) PGQ_MEET3W(true, 2);
 			else if (four) PGQ_MEET3W(false, 4);
 			else PGQ_MEET3W(false, 2);
 #undef PGQ_MEET3W
+#undef PGQ_MEET3WK
 		} else if (small) {
 			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH_SMALL);
 			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH_SMALL);
@@ -1835,6 +1870,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH);
 		}
 #undef PGQ_MEET3
+#undef PGQ_MEET3K
 		kt.stop();
 	}
 	int open_stage = 0; // the stage whose queue holds what is open at the end
@@ -1847,6 +1883,8 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 #define PGQ_MEET4(G)                                                                                                     \
 	hipLaunchKernelGGL((k_meet4<true, G>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj,     \
 	                   c->fdesc, c->rdesc, c->padj, c->rpadj, d_out, rec, cap4, bm_words, db, gmaps, q[1], fin)
+// k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
+// per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
 #define PGQ_MEET4D(G, T)                                                                                                    \
 	hipLaunchKernelGGL((k_meet4d<G, T>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
 	                   c->rpadj, d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), bm_words, db, gmaps, q[1], fin, d_trace, ride)
@@ -1966,12 +2004,18 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 	}
 	S.meet_pairs += n - (int64_t)open;
 	S.edges_scanned += (int64_t)(h.entries[0] + h.entries[1] + h.entries[2]);
-	// 4 B per adjacency entry / one-hop id, 16 B per slot descriptor; k_meet3: per row its ids (16 B), the four offsets and
-	// two walk sizes of its endpoints (40 B) and its result (8 B); the bit-map kernel: per queued row its entry (48 B)
-	// and its result (8 B)
-	S.algo_bytes[K_MEET] += 4.0 * (double)h.entries[0] + 16.0 * (double)h.vertices[0] + 64.0 * (double)n;
-	S.algo_bytes[K_MEET4] += 4.0 * (double)h.entries[1] + 16.0 * (double)h.vertices[1] + 56.0 * (double)(h.count[0] + h.count_back);
-	S.algo_bytes[K_BIBFS] += 4.0 * (double)h.entries[2] + 16.0 * (double)h.vertices[2];
+	// 4 B per adjacency entry / one-hop id and 16 / K B per entry walked over the packed lists (K ids per 16-byte group),
+	// 16 B per slot descriptor; k_meet3: per row its ids (16 B), the four offsets and two walk sizes of its endpoints (40 B)
+	// and its result (8 B); the bit-map kernel: per queued row its entry (48 B) and its result (8 B)
+	auto list_bytes = [&](int k) {
+		const double pw = (double)std::min(h.walked[k], h.entries[k]);
+		return 4.0 * ((double)h.entries[k] - pw) + (16.0 / (double)std::max(4, c->pack_k)) * pw;
+	};
+	S.algo_bytes[K_MEET] += list_bytes(0) + 16.0 * (double)h.vertices[0] + 64.0 * (double)n;
+	S.algo_bytes[K_MEET4] += list_bytes(1) + 16.0 * (double)h.vertices[1] + 56.0 * (double)(h.count[0] + h.count_back);
+	S.algo_bytes[K_BIBFS] += list_bytes(2) + 16.0 * (double)h.vertices[2];
+	tstats().route_bytes += 4.0 * (double)(h.entries[0] + h.entries[1] + h.entries[2]) + 16.0 * (double)(h.vertices[0] + h.vertices[1] + h.vertices[2]) +
+	                        64.0 * (double)n + 56.0 * (double)(h.count[0] + h.count_back);
 	r->n_open = open;
 	return PGQ_OK;
 }
@@ -2082,6 +2126,7 @@ int meet_bidirectional(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_sr
 	S.meet_pairs += n - (int64_t)h.count[1];
 	S.edges_scanned += (int64_t)h.entries[2];
 	S.algo_bytes[K_BIBFS] += 4.0 * (double)h.entries[2] + 16.0 * (double)h.vertices[2];
+	tstats().route_bytes += 4.0 * (double)h.entries[2] + 16.0 * (double)h.vertices[2];
 	*n_open = h.count[1];
 	return PGQ_OK;
 }

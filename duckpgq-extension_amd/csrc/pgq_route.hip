@@ -81,10 +81,10 @@ static int calibrate_prepass(pgq_csr *c) {
 	hipLaunchKernelGGL(k_calibration_pairs, dim3(blocks_for(n0)), dim3(256), 0, w->stream, n0, c->V, w->in_src.as<int64_t>(), w->in_dst.as<int64_t>());
 	pgq_stats_t &S = tstats().s;
 	const pgq_stats_t saved = S; // the caller's statistics are about its own rows
+	const double rb0 = tstats().route_bytes;
 	PrepassResult r;
 	const int rc = meet_prepass(c, w, PrepassArgs { n0, w->in_src.as<int64_t>(), w->in_dst.as<int64_t>(), w->out_len.as<int64_t>() }, &r);
-	const double bytes = (S.algo_bytes[K_MEET] - saved.algo_bytes[K_MEET]) + (S.algo_bytes[K_MEET4] - saved.algo_bytes[K_MEET4]) +
-	                     (S.algo_bytes[K_BIBFS] - saved.algo_bytes[K_BIBFS]);
+	const double bytes = tstats().route_bytes - rb0; // at 4 B per list entry (ThreadStats::route_bytes)
 	S = saved;
 	PGQ_TRY(rc);
 	c->cal.meet_bpr.store(std::max(64.0, bytes / (double)n0));
@@ -247,7 +247,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 
 	// the pre-pass chain over the rows as they lie (lengths)
 	auto run_prepass = [&](PrepassResult &r) -> int {
-		const double b0 = S.algo_bytes[K_MEET] + S.algo_bytes[K_MEET4] + S.algo_bytes[K_BIBFS];
+		const double b0 = tstats().route_bytes;
 		PrepassArgs a { n, d_src, d_dst, d_out_len, nullptr, meet_bytes, edge_bytes, decide_mode, ball };
 		PGQ_TRY(meet_prepass(c, ws, a, &r));
 		if (ball == BallMode::Only && r.ball_attempted && !r.ball_took) { // the kernels-alone chain declined these rows: the stage kernels after all
@@ -265,7 +265,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 		}
 		if (!r.answered) return PGQ_OK;
 		if (n >= 1024 && !r.ball_took) { // what these rows really moved refines the CSR's bytes per row (half the weight to the newest call)
-			const double now = std::max(64.0, (S.algo_bytes[K_MEET] + S.algo_bytes[K_MEET4] + S.algo_bytes[K_BIBFS] - b0) / (double)n);
+			const double now = std::max(64.0, (tstats().route_bytes - b0) / (double)n);
 			const double old = c->cal.meet_bpr.load(std::memory_order_relaxed);
 			c->cal.meet_bpr.store(old > 0 ? 0.5 * old + 0.5 * now : now, std::memory_order_relaxed);
 		}

@@ -337,6 +337,8 @@ static std::vector<OptRef> option_table(Options &o) {
 		{ "meet_trace", &o.meet_trace, nullptr },
 		{ "meet_layout", &o.meet_layout, nullptr },
 		{ "meet_align", &o.meet_align, nullptr },
+		{ "meet_pack", &o.meet_pack, nullptr },
+		{ "meet_pack_align", &o.meet_pack_align, nullptr },
 		{ "ball", &o.ball, nullptr },
 		{ "ball_cap", &o.ball_cap, nullptr },
 		{ "ball_test_cap", &o.ball_test_cap, nullptr },
@@ -1247,12 +1249,86 @@ __global__ __launch_bounds__(256) void k_fill_padded(int64_t V, const int64_t *_
 		reinterpret_cast<int4 *>(padj)[g] = o;
 	}
 }
-__global__ void k_fill_desc(int64_t E, const int32_t *__restrict__ adj, const uint2 *__restrict__ seg, uint4 *__restrict__ desc) {
+// pgroups (nullable): first group of every vertex's packed list (pgq_pack.h), the descriptor's 4th word
+__global__ void k_fill_desc(int64_t E, const int32_t *__restrict__ adj, const uint2 *__restrict__ seg, const u32 *__restrict__ pgroups,
+                            uint4 *__restrict__ desc) {
 	const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (e >= E) return;
 	const u32 u = (u32)adj[e];
 	const uint2 s = seg[u];
-	desc[e] = make_uint4(u, s.x, s.y, 0u);
+	desc[e] = make_uint4(u, s.x, s.y, pgroups ? pgroups[u] : 0u);
+}
+
+// ---- the bit-packed copy (pgq_pack.h): K ids per 16-byte group, lists aligned to `align` groups ----------------------------
+__global__ void k_pack_groups(int64_t V, const int64_t *__restrict__ off, int K, u32 align, u32 *__restrict__ ng) {
+	const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (v < V) ng[v] = pack_list_groups((u32)(off[v + 1] - off[v]), K, align);
+}
+// as k_fill_padded: one workgroup per 256 consecutive vertices, a thread per packed group, its list by binary search
+template <int K>
+__global__ __launch_bounds__(256) void k_fill_packed(int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                     const u32 *__restrict__ gbeg, uint4 *__restrict__ packed) {
+	__shared__ u32 s_beg[257];
+	__shared__ int64_t s_off[257];
+	const int64_t v0 = (int64_t)blockIdx.x * 256;
+	const int nv = (int)min((int64_t)256, V - v0);
+	for (int t = threadIdx.x; t <= nv; t += 256) { // gbeg has V + 1 entries (exclusive scan)
+		s_beg[t] = gbeg[v0 + t];
+		s_off[t] = off[v0 + t];
+	}
+	__syncthreads();
+	const u32 g0 = s_beg[0], g1 = s_beg[nv];
+	for (u32 g = g0 + threadIdx.x; g < g1; g += 256) {
+		int lo = 0, hi = nv; // largest t with s_beg[t] <= g (lists without groups share their start with the next one)
+		while (hi - lo > 1) {
+			const int mid = (lo + hi) >> 1;
+			if (s_beg[mid] <= g) lo = mid;
+			else hi = mid;
+		}
+		const int64_t b = s_off[lo], len = s_off[lo + 1] - b;
+		u32 w[4];
+		pack_list_group<K>(adj + b, len, g - s_beg[lo], w);
+		packed[g] = make_uint4(w[0], w[1], w[2], w[3]);
+	}
+}
+// Builds one direction's packed copy and leaves every vertex's first packed group in *d_gb (V + 1 entries, the caller
+// frees it).  Returns PGQ_OK with *packed == nullptr when the group indices would not fit 32 bits.
+static int build_packed_dir(pgq_csr *c, const int64_t *off, const int32_t *adj, int K, int32_t **packed, u32 **d_gb,
+                            int64_t *groups_out, hipStream_t st) {
+	const int64_t V = c->V, E = c->E;
+	const u32 align = (u32)std::max(1, options().meet_pack_align);
+	*packed = nullptr;
+	if ((double)E / K + (double)V * align >= 4.0e9) return PGQ_OK;
+	u32 *d_ng = nullptr;
+	void *d_tmp = nullptr;
+	struct Temps {
+		u32 *&a;
+		void *&t;
+		hipStream_t st;
+		~Temps() {
+			(void)hipStreamSynchronize(st);
+			dev_free(a);
+			dev_free(t);
+		}
+	} temps { d_ng, d_tmp, st };
+	PGQ_TRY(dev_alloc_as(&d_ng, (size_t)V + 1));
+	PGQ_TRY(dev_alloc_as(d_gb, (size_t)V + 1));
+	PGQ_HIP_TRY(hipMemsetAsync(d_ng + V, 0, sizeof(u32), st));
+	hipLaunchKernelGGL(k_pack_groups, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, K, align, d_ng);
+	size_t sb = 0;
+	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_ng, *d_gb, (int)(V + 1), st));
+	PGQ_TRY(dev_alloc(&d_tmp, sb + 16));
+	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, sb, d_ng, *d_gb, (int)(V + 1), st));
+	u32 total = 0;
+	PGQ_HIP_TRY(hipMemcpyAsync(&total, *d_gb + V, sizeof(u32), hipMemcpyDeviceToHost, st));
+	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	PGQ_TRY(dev_alloc_as(packed, (size_t)total * 4 + 4));
+	const dim3 grid((unsigned)((V + 255) / 256));
+	uint4 *dst = reinterpret_cast<uint4 *>(*packed);
+	if (K == 6) hipLaunchKernelGGL(k_fill_packed<6>, grid, dim3(256), 0, st, V, off, adj, *d_gb, dst);
+	else hipLaunchKernelGGL(k_fill_packed<5>, grid, dim3(256), 0, st, V, off, adj, *d_gb, dst);
+	*groups_out = (int64_t)total;
+	return PGQ_OK;
 }
 
 // entries of every vertex's two-hop walk in one direction = sum of its neighbours' list lengths (saturating u32).  One
@@ -1299,7 +1375,7 @@ __global__ __launch_bounds__(256) void k_two_hop_work(int64_t V, const int64_t *
 }
 
 static int build_meet_layout_dir(pgq_csr *c, const int64_t *off, const int32_t *adj, int32_t **padj, uint2 **seg,
-                                 uint4 **desc, u32 **work, int64_t *groups_out, hipStream_t st) {
+                                 uint4 **desc, u32 **work, int64_t *groups_out, const u32 *pgroups, hipStream_t st) {
 	const int64_t V = c->V, E = c->E;
 	u32 align = (u32)std::max(4, options().meet_align) & ~3u;
 	// group indices are 32-bit: E / 4 + V x align / 4 bounds the padded size; one group per list start always fits
@@ -1333,7 +1409,7 @@ static int build_meet_layout_dir(pgq_csr *c, const int64_t *off, const int32_t *
 	PGQ_TRY(dev_alloc_as(desc, (size_t)E + 1));
 	hipLaunchKernelGGL(k_seg_fill, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, d_gb, *seg);
 	hipLaunchKernelGGL(k_fill_padded, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, adj, *seg, total, *padj);
-	hipLaunchKernelGGL(k_fill_desc, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, E, adj, *seg, *desc);
+	hipLaunchKernelGGL(k_fill_desc, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, E, adj, *seg, pgroups, *desc);
 	PGQ_TRY(dev_alloc_as(work, (size_t)V));
 	hipLaunchKernelGGL(k_two_hop_work, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, adj, *seg, *work);
 	*groups_out = (int64_t)total;
@@ -1367,8 +1443,34 @@ __global__ __launch_bounds__(256) void k_fill_rhead(int64_t V, const uint2 *__re
 }
 static int build_meet_layout(pgq_csr *c, hipStream_t st) {
 	if (!options().meet_layout || c->V <= 0 || c->E <= 0) return PGQ_OK;
-	PGQ_TRY(build_meet_layout_dir(c, c->off, c->adj, &c->padj, &c->fseg, &c->fdesc, &c->fwork, &c->padj_groups, st));
-	PGQ_TRY(build_meet_layout_dir(c, c->roff, c->radj, &c->rpadj, &c->rseg, &c->rdesc, &c->rwork, &c->rpadj_groups, st));
+	// the packed copies first: the slot descriptors carry their first groups.  Both directions or neither
+	const int K = options().meet_pack ? pack_k_for(c->V, options().meet_pack >= 2) : 4;
+	u32 *fpg = nullptr, *rpg = nullptr;
+	struct Temps {
+		u32 *&a, *&b;
+		hipStream_t st;
+		~Temps() {
+			(void)hipStreamSynchronize(st);
+			dev_free(a);
+			dev_free(b);
+		}
+	} temps { fpg, rpg, st };
+	c->pack_k = 4;
+	if (K > 4) {
+		PGQ_TRY(build_packed_dir(c, c->off, c->adj, K, &c->ppadj, &fpg, &c->ppadj_groups, st));
+		if (c->ppadj) PGQ_TRY(build_packed_dir(c, c->roff, c->radj, K, &c->prpadj, &rpg, &c->prpadj_groups, st));
+		if (c->ppadj && c->prpadj) {
+			c->pack_k = K;
+		} else {
+			dev_free(c->ppadj);
+			dev_free(c->prpadj);
+			c->ppadj = c->prpadj = nullptr;
+			c->ppadj_groups = c->prpadj_groups = 0;
+		}
+	}
+	const bool packed = c->pack_k > 4;
+	PGQ_TRY(build_meet_layout_dir(c, c->off, c->adj, &c->padj, &c->fseg, &c->fdesc, &c->fwork, &c->padj_groups, packed ? fpg : nullptr, st));
+	PGQ_TRY(build_meet_layout_dir(c, c->roff, c->radj, &c->rpadj, &c->rseg, &c->rdesc, &c->rwork, &c->rpadj_groups, packed ? rpg : nullptr, st));
 	if (options().ball && (size_t)c->V * 256 <= ((size_t)std::max(0, options().ball_head_mb) << 20)) {
 		if (dev_alloc_as(&c->rhead, (size_t)c->V * 16) == PGQ_OK) // (no memory for it: the kernel gathers the list positions instead)
 			hipLaunchKernelGGL(k_fill_rhead, dim3((unsigned)((c->V * 16 + 255) / 256)), dim3(256), 0, st, c->V, c->rseg, c->rpadj, c->rhead);
@@ -1498,7 +1600,6 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 	c->max_in_degree = us.max_in;
 	c->max_out_degree = us.max_out;
 	c->two_hop_mean = (double)us.two_hop_sum / (double)std::max<int64_t>(V, 1);
-	calibration_load(c); // (max degrees and E are set above)
 	c->n_pull_parts = us.n_parts;
 	if (us.n_parts > 0)
 		hipLaunchKernelGGL(k_fill_rown, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, c->roff, c->pull_parts, c->n_pull_parts, c->radj,
@@ -1539,17 +1640,22 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 		(void)hipGetLastError();
 		if (options().trace) fprintf(stderr, "[pgq] upload: no memory for the pair-centric layout (~40 B per edge): this CSR is searched without the pre-pass\n");
 		for (void **q : { (void **)&c->padj, (void **)&c->rpadj, (void **)&c->fseg, (void **)&c->rseg, (void **)&c->fdesc,
-		                  (void **)&c->rdesc, (void **)&c->fwork, (void **)&c->rwork, (void **)&c->rhead }) {
+		                  (void **)&c->rdesc, (void **)&c->fwork, (void **)&c->rwork, (void **)&c->rhead, (void **)&c->ppadj,
+		                  (void **)&c->prpadj }) {
 			dev_free(*q);
 			*q = nullptr;
 		}
 		c->padj_groups = c->rpadj_groups = 0;
+		c->ppadj_groups = c->prpadj_groups = 0;
+		c->pack_k = 4;
 	}
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
 	tr.mark("padded adjacency + slot descriptors");
+	calibration_load(c); // (max degrees, E and the layout's pack_k are set above)
 	c->bytes = (V + 1) * 16 + 8 * V + E * (4 + 4 + 1 + (c->rpk ? 4 : 0)) + (c->edge_ids ? E * 8 : 0) + (c->w ? E * 8 : 0) +
 	           n_items * (int64_t)sizeof(HubItem) +
-	           (c->fdesc ? 2 * E * 16 + 2 * V * 12 + (c->padj_groups + c->rpadj_groups) * 16 : 0) + (c->rhead ? V * 256 : 0);
+	           (c->fdesc ? 2 * E * 16 + 2 * V * 12 + (c->padj_groups + c->rpadj_groups + c->ppadj_groups + c->prpadj_groups) * 16 : 0) +
+	           (c->rhead ? V * 256 : 0);
 	return PGQ_OK;
 }
 
@@ -1559,11 +1665,13 @@ struct CalEntry {
 	double two_hop_mean;
 	pgq_csr::RouteCalibration::Figures figures;
 	std::vector<uint8_t> level_plan[6];
+	int pack_k;
 };
 static std::mutex g_cal_lock;
 static std::vector<CalEntry> g_cal; // a handful of graph shapes, the most recent last
 static bool cal_same(const CalEntry &e, const pgq_csr *c) {
-	return e.V == c->V && e.E == c->E && e.max_out == c->max_out_degree && e.max_in == c->max_in_degree && e.two_hop_mean == c->two_hop_mean;
+	return e.V == c->V && e.E == c->E && e.max_out == c->max_out_degree && e.max_in == c->max_in_degree && e.two_hop_mean == c->two_hop_mean &&
+	       e.pack_k == c->pack_k; // the route timings differ between the packed and the 32-bit walks
 }
 void calibration_load(pgq_csr *c) {
 	if (!c || !options().calibration_cache) return;
@@ -1578,7 +1686,7 @@ void calibration_load(pgq_csr *c) {
 }
 void calibration_store(pgq_csr *c) {
 	if (!c || c->is_replica || !options().calibration_cache) return;
-	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {} };
+	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {}, c->pack_k };
 	bool any = n.figures.meet_bpr > 0 || n.figures.ball_open_frac > 0 || n.figures.route_ball_ns > 0;
 	{
 		std::lock_guard<std::mutex> g2(c->plan_lock);
@@ -1620,6 +1728,8 @@ static void destroy_csr(pgq_csr *c) {
 	dev_free(c->rpk);
 	dev_free(c->padj);
 	dev_free(c->rpadj);
+	dev_free(c->ppadj);
+	dev_free(c->prpadj);
 	dev_free(c->fseg);
 	dev_free(c->rseg);
 	dev_free(c->rhead);
@@ -1958,6 +2068,11 @@ static int clone_csr(const pgq_csr *c, int dev, pgq_csr **out) {
 	r->rpadj_groups = c->rpadj_groups;
 	PGQ_TRY(copy((void **)&r->padj, c->padj, (size_t)c->padj_groups * 16 + 16));
 	PGQ_TRY(copy((void **)&r->rpadj, c->rpadj, (size_t)c->rpadj_groups * 16 + 16));
+	r->ppadj_groups = c->ppadj_groups;
+	r->prpadj_groups = c->prpadj_groups;
+	r->pack_k = c->pack_k;
+	PGQ_TRY(copy((void **)&r->ppadj, c->ppadj, (size_t)c->ppadj_groups * 16 + 16));
+	PGQ_TRY(copy((void **)&r->prpadj, c->prpadj, (size_t)c->prpadj_groups * 16 + 16));
 	PGQ_TRY(copy((void **)&r->fseg, c->fseg, (size_t)c->V * 8));
 	PGQ_TRY(copy((void **)&r->rseg, c->rseg, (size_t)c->V * 8));
 	PGQ_TRY(copy((void **)&r->rhead, c->rhead, (size_t)c->V * 256));
@@ -2018,6 +2133,7 @@ int64_t pgq_csr_num_edges(const pgq_csr_t *csr) { return csr ? csr->E : -1; }
 int pgq_csr_w_type(const pgq_csr_t *csr) { return csr ? csr->w_type : -1; }
 int64_t pgq_csr_device_bytes(const pgq_csr_t *csr) { return csr ? csr->bytes : -1; }
 int pgq_csr_has_prepass_layout(const pgq_csr_t *csr) { return csr && csr->fdesc != nullptr ? 1 : 0; }
+int pgq_csr_pack_k(const pgq_csr_t *csr) { return csr ? csr->pack_k : -1; }
 
 } // extern "C"
 

@@ -101,9 +101,9 @@ __device__ __forceinline__ u32 wave_incl_max_u32(u32 x) {
 	r = max(r, PGQ_DPP(0u, r, 0x143, 0xc, 0xf));
 	return r;
 }
-__device__ __forceinline__ SegRound seg_round(u32 gbeg, u32 len) {
+template <int K = 4> __device__ __forceinline__ SegRound seg_round(u32 gbeg, u32 len) {
 	SegRound r;
-	r.ng = (len + 3u) >> 2;
+	r.ng = (len + (u32)(K - 1)) / (u32)K;
 	r.P = wave_incl_scan_u32(r.ng);
 	r.D = gbeg - (r.P - r.ng);
 	r.total = (u32)__builtin_amdgcn_readlane((int)r.P, 63);
@@ -131,6 +131,37 @@ __device__ __forceinline__ int4 load_group_nt(const int32_t *__restrict__ xp, u3
 	return make_int4(r.x, r.y, r.z, r.w);
 }
 
+// ---- round 7: the bit-packed lists (pgq_pack.h) ---------------------------------------------------------------------------
+// With K = 6 (V <= 2^21) a 16-byte group carries six 21-bit ids instead of four 32-bit ones: 2.67 bytes per walked entry,
+// a third fewer dependent list requests per row, and lists that shrink from 320 to ~215 MB on the SF100-shaped graph (more
+// of them stay in the Infinity Cache).  The walk keeps the raw group in its request slot and decodes it when the request is
+// processed, and an id only where it is used (a funnel shift and a mask): K decoded registers per slot in flight, or
+// even per group being tested, cost k_meet3 more spills.
+// A walk callback receives the group as `SegGroup<K>::type`: int4 for the 32-bit lists (the code of rounds 3-6), else
+// the raw packed group; grp_get / GrpN address both alike.
+template <int K> struct PGroup {
+	u32 w[4]; // the raw group: an id is decoded where it is used (grp_get), so that only four registers stay live
+};
+template <int K> struct SegGroup {
+	typedef PGroup<K> type;
+	__device__ __forceinline__ static type decode(const int4 &r) { return type { { (u32)r.x, (u32)r.y, (u32)r.z, (u32)r.w } }; }
+};
+template <> struct SegGroup<4> {
+	typedef int4 type;
+	__device__ __forceinline__ static int4 decode(const int4 &r) { return r; }
+};
+template <typename G> struct GrpN;
+template <> struct GrpN<int4> {
+	static constexpr int value = 4;
+};
+template <int K> struct GrpN<PGroup<K>> {
+	static constexpr int value = K;
+};
+__device__ __forceinline__ u32 grp_get(const int4 &v, int k) {
+	return (u32)(k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)));
+}
+template <int K> __device__ __forceinline__ u32 grp_get(const PGroup<K> &v, int k) { return pack_get<K>(v.w, k); }
+
 // Walks the padded lists of the descriptors list[0 .. list_n), DEPTH requests in flight, and calls f(v, ok, ev) per lane
 // and request: v = one 16-byte group (four entries of ONE list), ok = the lane holds a group, ev = the expanded vertex
 // the list belongs to (only when WANT_EV).  The descriptors are taken in rounds of 64 (lane j = descriptor j of the
@@ -141,7 +172,9 @@ __device__ __forceinline__ int4 load_group_nt(const int32_t *__restrict__ xp, u3
 // requested (capped = true when it ended the walk).  `first` (have_first): the caller already holds descriptor `lane` of
 // the first round (requested early, to overlap its latency).  Returns the entries of the requested groups (padding
 // removed pro rata of the round; wave-uniform).
-template <int DEPTH, bool WANT_EV, typename F, typename Stop>
+// K: ids per group (pgq_pack.h).  K = 4: xp is the 32-bit padded adjacency and a list's first group is the descriptor's
+// 2nd word; K > 4: xp is the packed copy and the first group is its 4th word.  `max_entries` counts K entries per group.
+template <int DEPTH, bool WANT_EV, int K = 4, typename F, typename Stop>
 __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__ list, int list_n, int w, int nw,
                                                        const int32_t *__restrict__ xp, unsigned char *win, bool have_first,
                                                        uint4 first, unsigned long long max_entries, bool &capped, int &resume,
@@ -168,7 +201,8 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 	// the end of the branch)
 	uint4 dn = zero4;
 	if (64 < list_n) dn = list[min(64 + lane, list_n - 1)];
-	SegRound r = seg_round(d.y, d.z);
+	auto round_of = [](const uint4 &dd) { return seg_round<K>(K == 4 ? dd.y : dd.w, dd.z); };
+	SegRound r = round_of(d);
 	int nchunk = (int)((r.total + 63u) >> 6);
 	int next = w;   // this wavefront's next request of the round
 	int issued = 0; // ... and how many of the round's it has made
@@ -190,7 +224,7 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 		if constexpr (WANT_EV) xv[u] = (u32)__shfl((int)d.x, j);
 		else xv[u] = 0;
 		xc[u] = pb;
-		requested += 4ull * (unsigned long long)min(64u, r.total - (u32)next * 64u);
+		requested += (unsigned long long)K * (unsigned long long)min(64u, r.total - (u32)next * 64u);
 		next += nw;
 		issued++;
 	};
@@ -220,7 +254,7 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 				if (pb + lane >= list_n) d = zero4;
 				dn = zero4;
 				if (pb + 64 < list_n) dn = list[min(pb + 64 + lane, list_n - 1)];
-				r = seg_round(d.y, d.z);
+				r = round_of(d);
 				nchunk = (int)((r.total + 63u) >> 6);
 				next = w;
 				issued = 0;
@@ -235,12 +269,12 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 		for (int u = 0; u < DEPTH; u++) {
 			if (xc[u] < 0) continue; // wave-uniform
 			any_chunk = true;
-			const int4 v = x[u];
+			const int4 raw = x[u];
 			const bool ok = xok[u];
 			const u32 ev = xv[u];
 			xc[u] = -1;
 			if (open && next < nchunk) issue(u); // refilled before it is processed: everything about the request was copied above
-			f(v, ok, ev);
+			f(SegGroup<K>::decode(raw), ok, ev);
 		}
 		if (!any_chunk) break;
 		if (stop()) {
@@ -300,38 +334,37 @@ __device__ __forceinline__ bool regset_has(const RegSet &s, u32 x) {
 		if (k < s.rounds) in |= s.r[k] == x;
 	return __any(in) != 0;
 }
-// the four filter words of a lane's group: independent LDS reads, no branches.  Bit k of the result: entry k passed.
-template <bool BIGV> __device__ __forceinline__ u32 flt_pass4(const u32 *bm, const int4 v) {
-	const u32 w0 = bm[flt_word((u32)v.x)], w1 = bm[flt_word((u32)v.y)], w2 = bm[flt_word((u32)v.z)], w3 = bm[flt_word((u32)v.w)];
-	const u32 t0 = flt_test<BIGV>(w0, (u32)v.x), t1 = flt_test<BIGV>(w1, (u32)v.y);
-	const u32 t2 = flt_test<BIGV>(w2, (u32)v.z), t3 = flt_test<BIGV>(w3, (u32)v.w);
-	return (t0 & 1u) | ((t1 & 1u) << 1) | ((t2 & 1u) << 2) | ((t3 & 1u) << 3);
+// the filter words of a lane's group (4 or K entries): independent LDS reads, no branches.  Bit k of the result: entry k
+// passed.
+template <bool BIGV, typename G> __device__ __forceinline__ u32 flt_pass(const u32 *bm, const G &v) {
+	constexpr int N = GrpN<G>::value;
+	u32 w[N];
+#pragma unroll
+	for (int k = 0; k < N; k++) w[k] = bm[flt_word(grp_get(v, k))];
+	u32 p = 0;
+#pragma unroll
+	for (int k = 0; k < N; k++) p |= (flt_test<BIGV>(w[k], grp_get(v, k)) & 1u) << k;
+	return p;
 }
+template <bool BIGV> __device__ __forceinline__ u32 flt_pass4(const u32 *bm, const int4 v) { return flt_pass<BIGV>(bm, v); }
 // Calls hit(x, L) for every entry the filter let through (p: bit k = entry k of this lane's group v) that IS in the set;
 // x and the lane L holding it are wave-uniform.  The loop runs over the lanes with candidates only (none, nearly always) and
 // ends when hit() returns true (the caller needs no further witness: on R-MAT-22 a request of 256 two-hop entries holds a
 // hundred members of the set — the same few hubs — and verifying them all, one after the other, took 20-60 us per row).
-template <typename H> __device__ __forceinline__ void verify_candidates(const RegSet &s, u32 p, const int4 &v, H hit) {
+// v: int4 (four entries) or PGroup<K> (K entries), tested in entry order.
+template <typename G, typename H> __device__ __forceinline__ void verify_candidates(const RegSet &s, u32 p, const G &v, H hit) {
+	constexpr int N = GrpN<G>::value;
 	u64 m = __ballot(p != 0);
 	while (m) {
 		const int L = __ffsll((long long)m) - 1;
 		m &= m - 1;
 		const u32 pl = (u32)__builtin_amdgcn_readlane((int)p, L);
-		if (pl & 1u) {
-			const u32 x = (u32)__builtin_amdgcn_readlane(v.x, L);
-			if (regset_has(s, x) && hit(x, L)) return;
-		}
-		if (pl & 2u) {
-			const u32 x = (u32)__builtin_amdgcn_readlane(v.y, L);
-			if (regset_has(s, x) && hit(x, L)) return;
-		}
-		if (pl & 4u) {
-			const u32 x = (u32)__builtin_amdgcn_readlane(v.z, L);
-			if (regset_has(s, x) && hit(x, L)) return;
-		}
-		if (pl & 8u) {
-			const u32 x = (u32)__builtin_amdgcn_readlane(v.w, L);
-			if (regset_has(s, x) && hit(x, L)) return;
+#pragma unroll
+		for (int k = 0; k < N; k++) {
+			if (pl & (1u << k)) {
+				const u32 x = (u32)__builtin_amdgcn_readlane((int)grp_get(v, k), L);
+				if (regset_has(s, x) && hit(x, L)) return;
+			}
 		}
 	}
 }

@@ -124,6 +124,10 @@ int64_t pgq_csr_device_bytes(const pgq_csr_t *csr);
 /* 1: the padded adjacency + slot descriptors of the pair-centric pre-pass were built at upload; 0: they were not (option
  * meet_layout = 0, or no memory for them): searches go through the lane batches only. */
 int pgq_csr_has_prepass_layout(const pgq_csr_t *csr);
+/* ids per 16-byte group of the lists the pre-pass's hop-count walks read: 6 (the bit-packed copy, 21-bit ids, V <= 2^21),
+ * 5 (25-bit ids, V <= 2^25 with option meet_pack = 2) or 4 (the 32-bit padded lists: meet_pack = 0, larger graphs, no
+ * layout); -1 for a NULL handle. */
+int pgq_csr_pack_k(const pgq_csr_t *csr);
 
 /* ---- searches, chunk form (host memory, UnifiedVectorFormat in, FLAT vector out) --------------------- */
 
