@@ -27,7 +27,7 @@ class Stats(C.Structure):
                 ("algo_bytes", C.c_double * KCLASS_MAX), ("kernel_ms", C.c_double * KCLASS_MAX),
                 ("launches", C.c_int64 * KCLASS_MAX), ("spec_batches", C.c_int64), ("spec_levels", C.c_int64),
                 ("spec_aborts", C.c_int64), ("host_waits", C.c_int64), ("ball_segments", C.c_int64),
-                ("ball_calls", C.c_int64)]
+                ("ball_calls", C.c_int64), ("lds_map_launches", C.c_int64 * KCLASS_MAX)]
 
 
 def lib_paths():
@@ -220,6 +220,7 @@ def get_stats():
     d["algo_bytes"] = {n: st.algo_bytes[i] for i, n in enumerate(names)}
     d["kernel_ms"] = {n: st.kernel_ms[i] for i, n in enumerate(names)}
     d["launches"] = {n: st.launches[i] for i, n in enumerate(names)}
+    d["lds_map_launches"] = {n: st.lds_map_launches[i] for i, n in enumerate(names)}
     return d
 
 

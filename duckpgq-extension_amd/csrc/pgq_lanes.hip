@@ -440,6 +440,7 @@ static int launch_lanes(pgq_csr *c, Workspace *ws, const u64 *front, const u32 *
 	const size_t dyn_bytes = (size_t)n_blk * 8 + (size_t)((n_blk + 1) & ~1) * 2 + (size_t)(n_blk / kGroupBlocks + 2) * 4 + 16;
 	const bool lds_map = opt.sparse_lds && sl > 1 && sl + dyn_bytes + 256 <= 160 * 1024;
 	if (lds_map) {
+		tstats().s.lds_map_launches[K_PULL_SPARSE]++; // (the caller counted the launch)
 		static std::atomic<int> attr_set { 0 };
 		if (!attr_set.load()) {
 			(void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - sl));

@@ -1570,6 +1570,18 @@ static void meet_attributes() {
 	attr_set.store(1);
 }
 
+// The bit-map kernels ask for up to 150 KB of dynamic LDS.  A launch over what the kernel's attribute or the CU allows does not
+// run, and the chain behind it would treat its rows as declined or open (the answers stay right, the kernel never ran): the
+// call fails instead, naming the kernel and its request.  clear_launch_error() first drops errors already dealt with (the
+// ignored attribute calls, allocations that fell back), so that what is read after the launch is the launch's own.
+static void clear_launch_error() { (void)hipGetLastError(); }
+static int check_launch(hipStream_t st, const char *kernel, size_t lds_bytes) {
+	const hipError_t e = hipGetLastError();
+	if (e == hipSuccess) return PGQ_OK;
+	(void)hipStreamSynchronize(st); // what the chain launched before it finishes before the workspace is reused
+	return fail(PGQ_ERR_HIP, std::string(kernel) + " launch with " + std::to_string(lds_bytes) + " B of dynamic LDS failed: " + hipGetErrorString(e));
+}
+
 // debugging aid (option meet_trace): where k_src_ball's time goes
 static int print_ball_trace(const unsigned long long *b_trace, u32 nseg, u32 open) {
 	unsigned long long t[17];
@@ -1765,6 +1777,8 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 				while ((int)seg_rows * 2 <= std::min(kBallRows, std::max(64, opt.ball_seg_rows_small))) seg_rows *= 2;
 			}
 			KernelTimer kt(st, K_BALL);
+			if (ball_lds) S.lds_map_launches[K_BALL]++;
+			clear_launch_error();
 			hipLaunchKernelGGL(k_ball_segments, dim3((unsigned)std::min<int64_t>(nwin, (int64_t)device_cus())), dim3(kBallRows), 0, st, n, d_src,
 			                   ws->ball_segs.as<u32>(), db, seg_rows);
 			const int64_t capb = std::max(1, opt.ball_cap), tcap = std::max(1, opt.ball_test_cap);
@@ -1782,6 +1796,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 			else if (b_trace) PGQ_BALL(true, true, 0);
 			else PGQ_BALL(true, false, 0);
 #undef PGQ_BALL
+			PGQ_TRY(check_launch(st, "k_src_ball", ball_lds ? (size_t)bm_words * 4 : 0));
 			kt.stop();
 		}
 	}
@@ -1880,6 +1895,8 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 		MeetHostBlock *fin = last_stage == 1 ? hb : nullptr;
 		{
 			KernelTimer kt(st, K_MEET4);
+			if (lds_map) S.lds_map_launches[K_MEET4]++;
+			clear_launch_error();
 #define PGQ_MEET4(G)                                                                                                     \
 	hipLaunchKernelGGL((k_meet4<true, G>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj,     \
 	                   c->fdesc, c->rdesc, c->padj, c->rpadj, d_out, rec, cap4, bm_words, db, gmaps, q[1], fin)
@@ -1896,6 +1913,7 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 			else PGQ_MEET4D(true, false);
 #undef PGQ_MEET4D
 #undef PGQ_MEET4
+			PGQ_TRY(check_launch(st, paths ? "k_meet4" : "k_meet4d", lds));
 			kt.stop();
 		}
 		open_stage = 1;
@@ -1911,12 +1929,15 @@ int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult 
 		qo2.count_back = nullptr; // one-ended: what k_bibfs leaves open is counted in count[2] alone (q[0] carries k_meet3's two-ended counter)
 		{
 			KernelTimer kt(st, K_BIBFS);
+			if (bi_lds) S.lds_map_launches[K_BIBFS]++;
+			clear_launch_error();
 			if (bi_lds)
 				hipLaunchKernelGGL(k_bibfs<false>, dim3(bi_grid), dim3(1024), (size_t)2 * mwb * 4, st, qi, (u32)bibfs_rows,
 				                   c->off, c->adj, c->roff, c->radj, d_out, capb, bm_words, qcap, db, bi_maps, queues, qo2, hb);
 			else
 				hipLaunchKernelGGL(k_bibfs<true>, dim3(bi_grid), dim3(1024), 0, st, qi, (u32)bibfs_rows, c->off, c->adj,
 				                   c->roff, c->radj, d_out, capb, bm_words, qcap, db, bi_maps, queues, qo2, hb);
+			PGQ_TRY(check_launch(st, "k_bibfs", bi_lds ? (size_t)2 * mwb * 4 : 0));
 			kt.stop();
 		}
 		ws->open_src = qo2.src;
@@ -2109,12 +2130,15 @@ int meet_bidirectional(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_sr
 	const int64_t capb = (int64_t)std::max(1, opt.bibfs_cap);
 	{
 		KernelTimer kt(st, K_BIBFS);
+		if (bi_lds) S.lds_map_launches[K_BIBFS]++;
+		clear_launch_error();
 		if (bi_lds)
 			hipLaunchKernelGGL(k_bibfs<false>, dim3(grid), dim3(1024), (size_t)2 * mwb * 4, st, q[0], 0xFFFFFFFFu, c->off, c->adj,
 			                   c->roff, c->radj, d_out, capb, bm_words, qcap, db, maps, queues, q[1], hb);
 		else
 			hipLaunchKernelGGL(k_bibfs<true>, dim3(grid), dim3(1024), 0, st, q[0], 0xFFFFFFFFu, c->off, c->adj, c->roff, c->radj,
 			                   d_out, capb, bm_words, qcap, db, maps, queues, q[1], hb);
+		PGQ_TRY(check_launch(st, "k_bibfs", bi_lds ? (size_t)2 * mwb * 4 : 0));
 		kt.stop();
 	}
 	ws->open_src = q[1].src;

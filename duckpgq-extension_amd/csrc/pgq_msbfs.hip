@@ -2130,6 +2130,7 @@ private:
 		}
 		const bool lds_map = opt.sparse_lds && static_lds > 1 && static_lds + dyn_bytes + 256 <= 160 * 1024;
 		if (lds_map) {
+			tstats().s.lds_map_launches[K_PULL_SPARSE]++; // (pull_sparse counted the launch)
 			static std::atomic<size_t> attr_bytes { 0 };
 			if (attr_bytes < dyn_bytes) {
 				(void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - static_lds));

@@ -135,9 +135,9 @@ int worker_wait(const std::shared_ptr<WorkerTask> &t) {
 	return t->failed == PGQ_OK ? PGQ_OK : fail(t->failed, t->what);
 }
 
-// every field of pgq_stats_t: 17 counters and three per-kernel-class arrays.  A field added to the public struct without a
+// every field of pgq_stats_t: 17 counters and four per-kernel-class arrays.  A field added to the public struct without a
 // line here fails this assertion.
-static_assert(sizeof(pgq_stats_t) == 17 * sizeof(int64_t) + PGQ_KCLASS_MAX * (2 * sizeof(double) + sizeof(int64_t)),
+static_assert(sizeof(pgq_stats_t) == 17 * sizeof(int64_t) + PGQ_KCLASS_MAX * (2 * sizeof(double) + 2 * sizeof(int64_t)),
               "pgq_stats_t changed: merge_stats must add the new field");
 static void merge_stats(pgq_stats_t &into, const pgq_stats_t &from) {
 	into.batches += from.batches;
@@ -155,6 +155,7 @@ static void merge_stats(pgq_stats_t &into, const pgq_stats_t &from) {
 		into.algo_bytes[k] += from.algo_bytes[k];
 		into.kernel_ms[k] += from.kernel_ms[k];
 		into.launches[k] += from.launches[k];
+		into.lds_map_launches[k] += from.lds_map_launches[k];
 	}
 	into.spec_batches += from.spec_batches;
 	into.spec_levels += from.spec_levels;
@@ -1876,7 +1877,7 @@ int pgq_device_count(void) {
 }
 
 const char *pgq_last_error(void) { return t_err.c_str(); }
-const char *pgq_version(void) { return "pgq_hip 0.6 (gfx950; pgq_stats_t: 65 words)"; }
+const char *pgq_version(void) { return "pgq_hip 0.7 (gfx950; pgq_stats_t: 81 words)"; }
 
 int pgq_csr_upload_ex(int64_t V, const int64_t *offsets, const int64_t *adj, const int64_t *edge_ids, const void *w, int w_type,
                       unsigned flags, pgq_csr_t **out) {

@@ -263,6 +263,9 @@ typedef struct pgq_stats {
 	int64_t host_waits;       /* stream synchronisations of the lane-batched search (lane assignment, levels, results) */
 	int64_t ball_segments;    /* round 6: source runs (cut at 1024-row windows) the source-centric kernel answered, one ball each */
 	int64_t ball_calls;       /* calls (or straggler passes) the source-centric kernel took */
+	/* of launches[], those whose per-vertex (or frontier) bit map sat in LDS rather than in global memory: k_src_ball (ball),
+	 * k_meet4 / k_meet4d (meet4), k_bibfs (bibfs), k_pull_lanes / k_pull_sparse (pull_sparse) */
+	int64_t lds_map_launches[PGQ_KCLASS_MAX];
 } pgq_stats_t;
 const char *pgq_kclass_name(int kclass); /* NULL past the last class */
 /* pgq_stats_t grows at its END from release to release (pgq_version() names the release).  pgq_get_stats_sized writes at most

@@ -346,12 +346,14 @@ def test_stats_struct_layout_matches_the_header(tmp_path):
     import subprocess
     from duckpgq_extension_amd import binding
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pgq_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu\\n", '
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pgq_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu\\n", '
                    'sizeof(pgq_stats_t), offsetof(pgq_stats_t, algo_bytes), offsetof(pgq_stats_t, launches), '
-                   'offsetof(pgq_stats_t, spec_batches), offsetof(pgq_stats_t, host_waits));return 0;}\n')
+                   'offsetof(pgq_stats_t, spec_batches), offsetof(pgq_stats_t, host_waits), offsetof(pgq_stats_t, ball_calls), '
+                   'offsetof(pgq_stats_t, lds_map_launches));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    size, o_algo, o_launch, o_spec, o_waits = (int(x) for x in subprocess.check_output([str(exe)]).split())
+    size, o_algo, o_launch, o_spec, o_waits, o_ball, o_lds = (int(x) for x in subprocess.check_output([str(exe)]).split())
     S = binding.Stats
     assert ctypes.sizeof(S) == size
     assert (S.algo_bytes.offset, S.launches.offset, S.spec_batches.offset, S.host_waits.offset) == (o_algo, o_launch, o_spec, o_waits)
+    assert (S.ball_calls.offset, S.lds_map_launches.offset) == (o_ball, o_lds)

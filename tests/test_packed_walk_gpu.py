@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import duckpgq_extension_amd as pgq
+from helpers import sparse_ids_graph
 from oracle.pgq_oracle import OracleCSR
 
 pytestmark = pytest.mark.gpu
@@ -23,22 +24,6 @@ def _options():
     yield
     for k, v in saved.items():
         pgq.set_option(k, v)
-
-
-def sparse_ids_graph(rng, V, n_active, E, hubs=4):
-    """A graph on n_active vertices spread over [0, V) (V - 1 and the largest ids among them), a few hubs whose lists
-    span a good part of the active set, and multi-edges."""
-    act = np.unique(np.concatenate([rng.integers(0, V, n_active), [0, V - 1, V - 2, V // 2]]))
-    act = act[act < V]
-    n = len(act)
-    s = rng.integers(0, n, E)
-    d = rng.integers(0, n, E)
-    hub = rng.choice(n, hubs, replace=False)
-    hs = np.repeat(hub, n // 3)
-    hd = rng.integers(0, n, len(hs))
-    s = np.concatenate([s, hs, hd, s[:50]])  # hub out- and in-lists, 50 duplicated edges
-    d = np.concatenate([d, hd, hs, d[:50]])
-    return act, act[s].astype(np.int64), act[d].astype(np.int64), act[hub]
 
 
 def run(V, act, s, d, hubs, rng, n_pairs, packs):
@@ -70,7 +55,7 @@ def run(V, act, s, d, hubs, rng, n_pairs, packs):
 @pytest.mark.parametrize("V", [(1 << 16) - 1, 1 << 16, (1 << 16) + 1, (1 << 21) - 1, 1 << 21, (1 << 21) + 1])
 def test_packed_walk_matches_oracle(V):
     rng = np.random.default_rng(V % 1000)
-    act, s, d, hubs = sparse_ids_graph(rng, V, 6000, 60000)
+    act, s, d, hubs, _ = sparse_ids_graph(rng, V, 6000, 60000)
     packed = 6 if V <= 1 << 21 else 4  # meet_pack = 1 packs up to 2^21 vertices
     want = run(V, act, s, d, hubs, rng, 2000, {1: packed, 0: 4, 2: 6 if V <= 1 << 21 else 5})
     assert any(w is not None and w >= 3 for w in want)
@@ -80,5 +65,5 @@ def test_packed_walk_matches_oracle(V):
 def test_packed_walk_matches_oracle_bigv(V):
     # 25-bit ids (K = 5, meet_pack = 2) up to 2^25 vertices; one more and the upload keeps the 32-bit lists only
     rng = np.random.default_rng(V % 1000)
-    act, s, d, hubs = sparse_ids_graph(rng, V, 3000, 24000)
+    act, s, d, hubs, _ = sparse_ids_graph(rng, V, 3000, 24000)
     run(V, act, s, d, hubs, rng, 256, {2: 5 if V <= 1 << 25 else 4, 1: 4, 0: 4})
