@@ -135,7 +135,7 @@ struct MeetHostBlock { // pinned host memory, written by the last workgroup of t
 	unsigned long long ball_entries, ball_descs;
 	u32 ball_go, ball_nseg, ball_nrun, ball_open;
 };
-static_assert(sizeof(MeetHostBlock) <= 8192, "pinned statistics block too small");
+static_assert(sizeof(MeetHostBlock) <= sizeof(MeetPinned::report), "pinned statistics block too small");
 __device__ __forceinline__ void queue_push(const MeetQueue &q, u32 row, const MeetEntry &e) { // one lane
 	u32 p;
 	if (q.count_back && (e.flags & kEntKnown4)) p = q.cap - 1u - atomicAdd(q.count_back, 1u);
@@ -1525,11 +1525,11 @@ static int meet_buffers(Workspace *ws, int64_t n, MeetQueue q[2], MeetDevBlock *
 		q[k].dst = ws->def_dst.as<int64_t>() + (size_t)k * n;
 		q[k].idx = ws->def_idx.as<u32>() + (size_t)k * n;
 		q[k].ent = ws->def_ent.as<MeetEntry>() + (size_t)k * n;
-		q[k].count = nullptr;
+		q[k].count = &(*db)->count[k]; // stage k appends to region k & 1 and counts in db->count[k]
 		q[k].count_back = nullptr;
 		q[k].cap = (u32)n;
 	}
-	*hb = static_cast<MeetHostBlock *>(ws->h_meet);
+	*hb = reinterpret_cast<MeetHostBlock *>(ws->h_meet->report);
 	(*hb)->done = 0;
 	return PGQ_OK;
 }
@@ -1560,14 +1560,39 @@ static int meet_wait(Workspace *ws, MeetHostBlock *hb, bool report_is_last = tru
 	ws->meet_cnt_clean = true;
 	return PGQ_OK;
 }
+// ---- where does the vertex bit map go? ---------------------------------------------------------------------------------
+constexpr size_t kLdsAll = 160 * 1024;      // LDS of a CU
+constexpr int kMapLdsKB = 150;              // cap of option meet4_lds_kb, and the dynamic-LDS attribute of k_meet4 / k_meet4d / k_bibfs
+constexpr size_t kMapLdsReserve = 2048;     // what those kernels' own __shared__ arrays get beside a map
+constexpr size_t kBallRowState = 23 * 1024; // what k_src_ball's own arrays (row state) get beside its map ...
+constexpr int kBallLdsAttr = 137 * 1024;    // ... and its dynamic-LDS attribute
+// One call's answer, from V and the options alone: the vertex bit map sits in LDS when it fits (V <= ~1.2 M for k_meet4 /
+// k_meet4d); above that every workgroup gets a slice of a global buffer (L2-resident: 0.5 MB at V = 4 M).
+struct MapPlan {
+	const int bm_words, mwb;            // words of one map; of one of k_bibfs's two
+	const size_t lds_budget, gm_budget; // options meet4_lds_kb and meet4_global_mb, in bytes
+	const bool lds_map, bi_lds;         // k_meet4 / k_meet4d keep their map in LDS; k_bibfs both sides' maps, when they fit
+	const bool ball_lds, ball_two;      // k_src_ball: one workgroup's map + row state fit; two workgroups per CU do
+	MapPlan(int64_t V, const Options &o)
+	    : bm_words((int)((V + 127) / 128) * 4), mwb(bm_words + 4), lds_budget((size_t)std::min(kMapLdsKB, std::max(0, o.meet4_lds_kb)) * 1024),
+	      gm_budget((size_t)std::max(0, o.meet4_global_mb) << 20), lds_map(map_bytes() + kMapLdsReserve <= lds_budget),
+	      bi_lds(bi_bytes() + kMapLdsReserve <= lds_budget), ball_lds(map_bytes() + kBallRowState <= std::min(kLdsAll, lds_budget + kBallRowState)),
+	      ball_two(PGQ_BALL_WAVES >= 8 && 2 * (map_bytes() + kBallRowState) <= kLdsAll) {}
+	size_t map_bytes() const { return (size_t)bm_words * 4; }
+	size_t bi_bytes() const { return (size_t)2 * mwb * 4; }
+};
+
+// the dynamic-LDS attributes, once per device (an attribute set on one device says nothing about a replica's)
 static void meet_attributes() {
-	static std::atomic<int> attr_set { 0 };
-	if (attr_set.load()) return;
-	(void)hipFuncSetAttribute((const void *)k_meet4d<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-	(void)hipFuncSetAttribute((const void *)k_meet4d<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-	(void)hipFuncSetAttribute((const void *)k_meet4<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-	(void)hipFuncSetAttribute((const void *)k_bibfs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-	attr_set.store(1);
+	static std::atomic<int> attr_set[64] = {};
+	std::atomic<int> &set = attr_set[current_device() & 63];
+	if (set.load()) return;
+	const void *const map_kernels[] = { (const void *)k_meet4d<false, false>, (const void *)k_meet4d<false, true>, (const void *)k_meet4<true, false>,
+		                                    (const void *)k_bibfs<false> };
+	for (const void *k : map_kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsKB * 1024);
+	(void)hipFuncSetAttribute((const void *)k_src_ball<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
+	(void)hipFuncSetAttribute((const void *)k_src_ball<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
+	set.store(1);
 }
 
 // The bit-map kernels ask for up to 150 KB of dynamic LDS.  A launch over what the kernel's attribute or the CU allows does not
@@ -1595,6 +1620,442 @@ static int print_ball_trace(const unsigned long long *b_trace, u32 nseg, u32 ope
 	return PGQ_OK;
 }
 
+// debugging aid (option meet_trace): where k_meet4d's time goes
+static int print_meet4d_trace(const unsigned long long *d_trace, u32 grid4, u32 long_first) {
+	std::vector<unsigned long long> t((size_t)grid4 * 4);
+	PGQ_HIP_TRY(hipMemcpy(t.data(), d_trace, t.size() * 8, hipMemcpyDeviceToHost));
+	unsigned long long t0 = ~0ull, t1 = 0, rows = 0, longest = 0, first_end = ~0ull, last_start = 0, most = 0;
+	for (u32 b = 0; b < grid4; b++) {
+		if (!t[4 * b + 1]) continue;
+		t0 = std::min(t0, t[4 * b]);
+		t1 = std::max(t1, t[4 * b + 1]);
+		first_end = std::min(first_end, t[4 * b + 1]);
+		last_start = std::max(last_start, t[4 * b]);
+		rows += t[4 * b + 2];
+		most = std::max(most, t[4 * b + 2]);
+		longest = std::max(longest, t[4 * b + 3]);
+	}
+	fprintf(stderr, "[pgq] k_meet4d trace: %u workgroups, %llu rows (%u long first), at most %llu per workgroup, span %.1f us, last start +%.1f us, "
+	        "first end +%.1f us, longest row %.1f us\n",
+	        grid4, rows, long_first, most, (double)(t1 - t0) * 0.01, (double)(last_start - t0) * 0.01, (double)(first_end - t0) * 0.01,
+	        (double)longest * 0.01);
+	return PGQ_OK;
+}
+
+// the rows a chain could not answer are handed over in queue region qo (the lane-batched search reads them)
+static void set_open(Workspace *ws, const MeetQueue &qo) {
+	ws->open_src = qo.src;
+	ws->open_dst = qo.dst;
+	ws->open_idx = qo.idx;
+}
+
+// k_bibfs over the first `rows` rows of qi, one workgroup per row: both visited maps in LDS when they fit, else in slices of `maps`
+static int launch_bibfs(pgq_csr *c, Workspace *ws, const MapPlan &mp, u32 grid, const MeetQueue &qi, u32 rows, int64_t *d_out, int qcap,
+                        MeetDevBlock *db, u32 *maps, u32 *queues, const MeetQueue &qo, MeetHostBlock *hb) {
+	hipStream_t st = ws->stream;
+	const int64_t capb = (int64_t)std::max(1, options().bibfs_cap);
+	const size_t lds = mp.bi_lds ? mp.bi_bytes() : 0;
+	KernelTimer kt(st, K_BIBFS);
+	if (mp.bi_lds) tstats().s.lds_map_launches[K_BIBFS]++;
+	clear_launch_error();
+	if (mp.bi_lds)
+		hipLaunchKernelGGL(k_bibfs<false>, dim3(grid), dim3(1024), lds, st, qi, rows, c->off, c->adj, c->roff, c->radj, d_out, capb,
+		                   mp.bm_words, qcap, db, maps, queues, qo, hb);
+	else
+		hipLaunchKernelGGL(k_bibfs<true>, dim3(grid), dim3(1024), 0, st, qi, rows, c->off, c->adj, c->roff, c->radj, d_out, capb,
+		                   mp.bm_words, qcap, db, maps, queues, qo, hb);
+	PGQ_TRY(check_launch(st, "k_bibfs", lds));
+	kt.stop();
+	return PGQ_OK;
+}
+
+// One call of meet_prepass: plan() settles the modes, the grids and every workspace buffer once, each launch_* step enqueues
+// one kernel class, read_report() waits (once) and turns the pinned report into the result and the statistics.
+class PrepassChain {
+public:
+	PrepassChain(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult *r) : c(c), ws(ws), a(a), r(r) {}
+	int run() {
+		PGQ_TRY(plan());
+		if (ball_mode) PGQ_TRY(launch_ball());
+		if (ball_only && ball_mode) return finish_ball_only();
+		// (tried in round 4: the decision kernel on a stream of its own beside k_meet3, which polls a stop flag — the event
+		// record / wait pair costs what the 12 us kernel does, and the polled word must be spread over many lines)
+		if (decide)
+			hipLaunchKernelGGL(k_meet_decide, dim3(1), dim3(1024), 0, st, n, a.d_src, c->V, a.meet_bytes, a.edge_bytes, &db->dec, (u32 *)nullptr, (const u32 *)&db->ball.go);
+		launch_meet3();
+		if (run4) PGQ_TRY(launch_bitmap());
+		if (run_bi) PGQ_TRY(launch_bibfs_stage());
+		else set_open(ws, q[open_stage]);
+		if (paths) PGQ_TRY(emit_paths());
+		return read_report();
+	}
+
+private:
+	// per call
+	pgq_csr *const c;
+	Workspace *const ws;
+	const PrepassArgs &a;
+	PrepassResult *const r;
+	const int64_t n = a.n;
+	const bool paths = a.po != nullptr;
+	const hipStream_t st = ws->stream;
+	const Options &opt = options();
+	pgq_stats_t &S = tstats().s;
+	const MapPlan mp { c->V, opt };
+	const int ncu = device_cus();
+	// BallMode::Only: the route memo says the source-centric kernel took these buffers last time — the chain is its two
+	// kernels and a one-thread report, without the stage kernels that would only return at once behind it (65,536
+	// one-wavefront workgroups of k_meet3 and 256 of k_meet4d starting up to read one word: 28 us of a 0.36-ms call).  If it
+	// declines this time, r->answered = false and the caller runs the chain again without it.  If there is no room for its
+	// maps it is not attempted and the stage kernels answer the call.
+	const bool ball_only = a.ball == BallMode::Only;
+	// DecideMode::Ride: the route memo says the last call on these buffers was answered here: the chain runs ungated and the
+	// sample rides in k_meet4d's launch (its last workgroup, in the bit map's LDS) — r->observed_go gets its verdict for the
+	// memo, -1 when none was taken (12 us of kernel + a launch gap in front of every 65,536-row call otherwise; tried first:
+	// the sample on a second stream beside the chain — the extra launch and wait on the host cost what the kernel did).
+	// The ride needs k_meet4d (distance-only flow) with its bit map in LDS and large enough to lend: else the gate again
+	const bool may_ride = opt.meet4 && !paths && mp.lds_map && mp.bm_words >= kSampleSlots;
+	const DecideMode decide_mode = a.decide == DecideMode::Ride && !may_ride ? DecideMode::Gate : a.decide;
+	const bool decide = decide_mode == DecideMode::Gate;
+	// what is left after k_meet3 (distance >= 4, or over its caps): the bit-map kernels, launched straight behind on a
+	// fixed grid — they read the row count from the device
+	const bool run4 = opt.meet4 && (mp.lds_map || mp.map_bytes() <= mp.gm_budget);
+	// k_bibfs serves the few rows the two-hop kernels leave open (far apart, unreachable, over the caps).  Launching it
+	// costs ~12 us of stream time even when no row is open, so it stays in the chain only while this CSR has shown such
+	// rows: the first call runs it; a call that ends with every row answered before it switches it off, and any later
+	// call that leaves rows open (they go to the lane-batched search, same answers) switches it on again.
+	const bool run_bi = !paths && opt.bibfs_rows > 0 && c->meet_far_rows.load(std::memory_order_relaxed) != 0;
+	const int last_stage = run_bi ? 2 : (run4 ? 1 : 0);
+	const int bibfs_rows = opt.bibfs_rows <= 0 ? 0 : std::max(opt.bibfs_rows, (int)std::min<int64_t>(opt.bibfs_rows_max, c->E / 4096));
+	const int qcap = std::max(1024, opt.bibfs_queue);
+	// k_meet4d hands rows out dynamically: a grid of exactly the workgroups the chip holds (meet4_grid_mult = 2 per CU).
+	// A row alone on its CU is through in ~15 us, beside a second one in ~20 (the phases of a row are short bursts of
+	// instructions from 16 wavefronts, and two workgroups share the CU's issue slots): small calls, whose ~2 % of open rows
+	// do not fill 256 CUs anyway, get one workgroup per CU (8192 rows: 0.086 -> 0.076 ms, 2048 rows: 0.062 -> 0.053 ms)
+	const bool small_call = !paths && n <= (int64_t)opt.meet_small_rows;
+
+	// settled by plan()
+	int ball_mode = a.ball == BallMode::Off ? 0 : (a.ball == BallMode::Always ? 2 : 1); // 0 when the ball kernels are not launched
+	u32 grid4 = 0, bi_grid = 0, grid_b = 0, seg_rows = (u32)kBallRows;
+	size_t maps_bytes = 0, bi_map_words = 0, bi_bytes = 0, ball_maps = 0;
+	SampleArgs ride { a.meet_bytes, a.edge_bytes, nullptr, nullptr, n, a.d_src, c->V };
+	MeetQueue q[2];
+	MeetDevBlock *db = nullptr;
+	MeetHostBlock *hb = nullptr;
+	MeetPath *rec = nullptr; // shortestpath: the inner vertices of the answered rows
+	u32 *gmaps = nullptr, *bi_maps = nullptr;
+	unsigned long long *d_trace = nullptr, *b_trace = nullptr;
+	int open_stage = 0; // the stage whose queue holds what is open at the end
+	// the grids of k_bibfs and the bit-map kernel with the global maps and queues they need, the ball's, then the buffers
+	int plan() {
+		// round 6: how many rows it takes and on how many workgroups follows the graph and what the call before left: on a
+		// graph whose levels are expensive (R-MAT-22: a lane batch for the 15,800 far / unreachable rows of a 2 M-row cross product
+		// costs 19 ms) a bidirectional search per row on every CU is far cheaper than whole-graph levels for a few thousand rows,
+		// while a graph that has never shown more than a handful keeps the 64-workgroup launch (12 us when nothing is open)
+		const int far_rows = c->meet_far_rows.load(std::memory_order_relaxed);
+		// (sized by what the last call left AND by this call's rows: a handle's first call knows nothing of the former, and 64
+		// workgroups for the 35,000 far rows of an R-MAT-22 cross product made that call 11 ms longer than the ones after it)
+		// (on graphs whose maps are global — V past the LDS: there far rows are the rule; a graph with LDS maps keeps the small
+		// grid until a call has left far rows: every workgroup owns 2.6 MB of queues, 512 of them 1.3 GB allocated on first use)
+		const int want_grid = std::max(far_rows / 16, mp.bi_lds ? 0 : (int)std::min<int64_t>(n / 64, 1 << 20));
+		bi_grid = (u32)std::min(std::max(std::max(1, opt.bibfs_grid), std::min(want_grid, 2 * ncu)), std::max(1, bibfs_rows));
+		grid4 = (u32)std::min<int64_t>(n, (int64_t)ncu * std::max(1, paths ? 4 : (small_call ? 1 : opt.meet4_grid_mult)));
+		// round 6: a chunk-sized call leaves a few dozen rows open (2 % of 2048): a workgroup per CU for them starts 256 x 1024
+		// threads that find nothing to do and, worse, fills every CU — the chunk calls of DuckDB's other worker threads (one per
+		// DataChunk per thread, iterativelength.cpp:34) queue behind it instead of running beside it (tools/chunk_mt.cpp: 8 threads
+		// reached 47 M rows/s, 1.7 x one thread).  One workgroup per 16 rows, at least 16: rows are handed out dynamically anyway.
+		if (small_call) grid4 = std::min<u32>(grid4, (u32)std::max<int64_t>(16, n / 16));
+		if (run4 && !mp.lds_map) {
+			grid4 = (u32)std::max<size_t>(1, std::min<size_t>((size_t)std::min<int64_t>(n, ncu), mp.gm_budget / mp.map_bytes()));
+			maps_bytes = (size_t)grid4 * mp.map_bytes();
+		}
+		bi_map_words = (run_bi && !mp.bi_lds) ? (size_t)bi_grid * 2 * mp.mwb : 0;
+		bi_bytes = run_bi ? (bi_map_words + (size_t)bi_grid * 5 * qcap) * 4 + 64 : 0;
+		plan_ball();
+		return reserve();
+	}
+	// round 6: the source-centric kernels open the chain (pgq_ball.h).  Their vertex bit map: LDS when one workgroup's map and
+	// row state fit (two workgroups per CU when both do), else a slice of the global buffer the bit-map kernels use (they run
+	// only when this one declines).  No room for the maps: the older routes.
+	void plan_ball() {
+		if (paths || !c->rseg || !c->fdesc || !c->rdesc || n < 2) ball_mode = 0;
+		if (!ball_mode) return;
+		if (mp.ball_lds) {
+			grid_b = (u32)ncu * (mp.ball_two ? 2u : 1u);
+		} else if (mp.map_bytes() <= mp.gm_budget) {
+			grid_b = (u32)std::max<size_t>(1, std::min<size_t>((size_t)ncu * 2, mp.gm_budget / mp.map_bytes()));
+			ball_maps = (size_t)grid_b * mp.map_bytes();
+		}
+		if (opt.ball_grid > 0) grid_b = std::min(grid_b, (u32)opt.ball_grid);
+		if (small_call) { // (as for k_meet4d: room for the other threads' chunks); shorter segments, more workgroups per source (k_ball_segments)
+			grid_b = std::min<u32>(grid_b, (u32)std::max<int64_t>(8, n / 16));
+			seg_rows = 64;
+			while ((int)seg_rows * 2 <= std::min(kBallRows, std::max(64, opt.ball_seg_rows_small))) seg_rows *= 2;
+		}
+		if (grid_b == 0) ball_mode = 0;
+		else r->ball_attempted = true;
+	}
+	// every workspace buffer of the chain, then the pointers into them; the memsets that open the chain on the stream
+	int reserve() {
+		if (decide_mode == DecideMode::Ride) {
+			PGQ_TRY(ws->route_dec.reserve(sizeof(MeetDecision)));
+			ws->h_meet->sample_go = 0;
+			ride.out = ws->route_dec.as<MeetDecision>();
+			ride.h_go = &ws->h_meet->sample_go; // taken inside k_meet4d's launch when its map is in LDS and large enough; else no verdict this call
+		}
+		PGQ_TRY(meet_buffers(ws, n, q, &db, &hb));
+		if (paths) {
+			PGQ_TRY(ws->meet_rec.reserve((size_t)n * sizeof(MeetPath)));
+			PGQ_TRY(ws->meet_poff.reserve((size_t)(n + 1) * 8 * 2));
+			rec = ws->meet_rec.as<MeetPath>();
+		}
+		// one buffer for the global maps: the ball's slices (the bit-map kernels run only when it declines), or theirs + k_bibfs's
+		size_t maps_need = maps_bytes + bi_bytes > 0 ? maps_bytes + bi_bytes + 64 : 0;
+		if (ball_mode) maps_need = std::max(maps_need, ball_maps);
+		if (maps_need > 0) PGQ_TRY(ws->meet_maps.reserve(maps_need));
+		gmaps = ws->meet_maps.as<u32>();
+		bi_maps = gmaps ? gmaps + (maps_bytes + 15) / 16 * 4 : nullptr;
+		if (ball_mode) PGQ_TRY(ws->ball_segs.reserve((size_t)n * 4));
+		if (ball_mode && opt.meet_trace) {
+			PGQ_TRY(ws->ball_trace.reserve(256));
+			b_trace = ws->ball_trace.as<unsigned long long>();
+		}
+		meet_attributes();
+		if (run4 && !paths) q[0].count_back = &db->count[3]; // k_meet3 -> k_meet4d: long rows from the front, the others from the back
+		if (opt.meet_trace && run4 && !paths) {
+			PGQ_TRY(ws->meet_trace.reserve((size_t)grid4 * 32));
+			d_trace = ws->meet_trace.as<unsigned long long>();
+			PGQ_HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)grid4 * 32, st));
+		}
+		// shortestpath on a large input: if the decision kernel calls the pre-pass off, nothing writes a.d_out — the list layout
+		// (emit_paths) must then see "no list" everywhere (-1 in every row), not what the buffer happened to hold
+		if (decide && paths) PGQ_HIP_TRY(hipMemsetAsync(a.d_out, 0xFF, (size_t)n * 8, st));
+		return PGQ_OK;
+	}
+	int launch_ball() {
+		BallRule rule; // what the device weighs when it decides whether the source-centric kernel takes the call (ball_decides)
+		const double mean_deg = (double)c->E / (double)std::max<int64_t>(c->V, 1);
+		rule.seg_floor = 1024.0 * (double)std::max(0, opt.ball_seg_kb);
+		rule.seg_bytes = 4.0 * c->two_hop_mean + 32.0 * mean_deg + 64.0;
+		rule.row_bytes = 4.0 * std::min(mean_deg, 64.0) + (c->rhead ? 0.0 : 128.0) + 32.0; // the first 64 entries of the in-list, the line its position sits in (without rhead), the row
+		// a ball in a global map: every mark is a look in DRAM and an atomic there (R-MAT-22: ~5 ns per entry and workgroup
+		// against ~1 ns in LDS) ...
+		if (!mp.ball_lds) rule.seg_bytes *= 8.0;
+		// ... and what this kernel leaves open is the pre-pass's to answer, at that kernel's measured bytes per row: the share of
+		// rows the last call on this graph shape left open (0 before the first) prices it.  R-MAT-22, 2048 x 1024: 1.7 % open x
+		// 1.7 MB per row = 28 KB per row — the lane batches (12 ms) are then the cheaper route, not this one (16.7 ms).
+		const double bpr = a.meet_bytes > 0 && n > 0 ? a.meet_bytes / (double)n : c->cal.meet_bpr.load(std::memory_order_relaxed);
+		rule.row_bytes += c->cal.ball_open_frac.load(std::memory_order_relaxed) * std::max(0.0, bpr);
+		rule.meet_bytes = a.meet_bytes;
+		rule.edge_bytes = a.edge_bytes > 0 ? a.edge_bytes : (double)c->E;
+		rule.bias = opt.ball_bias;
+		rule.mode = ball_mode;
+		rule.V = c->V;
+		const int64_t nwin = (n + kBallRows - 1) / kBallRows;
+		const size_t lds = mp.ball_lds ? mp.map_bytes() : 0;
+		KernelTimer kt(st, K_BALL);
+		if (mp.ball_lds) S.lds_map_launches[K_BALL]++;
+		clear_launch_error();
+		hipLaunchKernelGGL(k_ball_segments, dim3((unsigned)std::min<int64_t>(nwin, (int64_t)ncu)), dim3(kBallRows), 0, st, n, a.d_src,
+		                   ws->ball_segs.as<u32>(), db, seg_rows);
+		const int64_t capb = std::max(1, opt.ball_cap), tcap = std::max(1, opt.ball_test_cap);
+		if (b_trace) PGQ_HIP_TRY(hipMemsetAsync(b_trace, 0, 256, st));
+#define PGQ_BALL(G, T)                                                                                                       \
+	hipLaunchKernelGGL((k_src_ball<G, T>), dim3(grid_b), dim3(kBallRows), lds, st, n, a.d_src, a.d_dst, c->V, c->off, c->roff, c->fdesc, \
+	                   c->rdesc, c->padj, c->rpadj, c->rseg, opt.ball_head_mb > 0 ? c->rhead : (const uint4 *)nullptr, ws->ball_segs.as<u32>(), a.d_out, capb, tcap, \
+	                   mp.bm_words, db, gmaps, q[0], rule, b_trace, seg_rows)
+		if (mp.ball_lds && b_trace) PGQ_BALL(false, true);
+		else if (mp.ball_lds) PGQ_BALL(false, false);
+		else if (b_trace) PGQ_BALL(true, true);
+		else PGQ_BALL(true, false);
+#undef PGQ_BALL
+		PGQ_TRY(check_launch(st, "k_src_ball", lds));
+		kt.stop();
+		return PGQ_OK;
+	}
+	// BallMode::Only: the chain ends behind the source-centric kernels
+	int finish_ball_only() {
+		hipLaunchKernelGGL(k_chain_end, dim3(1), dim3(64), 0, st, db, hb);
+		PGQ_TRY(meet_wait(ws, hb));
+		if (hb->bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
+		if (hb->ball_go) return ball_took(*hb);
+		S.algo_bytes[K_BALL] += 16.0 * (double)n; // not this time
+		return called_off();
+	}
+	int called_off() { // nothing was answered
+		r->answered = false;
+		r->n_open = (u32)n;
+		return PGQ_OK;
+	}
+	// the source-centric kernel took the call: what is open sits in region 0, counted by itself
+	int ball_took(const MeetHostBlock &h) {
+		if (b_trace) PGQ_TRY(print_ball_trace(b_trace, h.ball_nseg, h.ball_open));
+		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
+		r->ball_took = true;
+		set_open(ws, q[0]);
+		S.meet_pairs += n - (int64_t)h.ball_open;
+		S.edges_scanned += (int64_t)h.ball_entries;
+		// 4 B per adjacency entry (the balls' lists, the destinations' in-lists, the distance-4 walks), 16 B per slot descriptor,
+		// per row its ids, its destination's list position and its result (32 B), per segment its position and offsets (24 B)
+		S.algo_bytes[K_BALL] += 4.0 * (double)h.ball_entries + 16.0 * (double)h.ball_descs + 32.0 * (double)n + 24.0 * (double)h.ball_nseg;
+		S.ball_segments += h.ball_nseg;
+		S.ball_calls++;
+		r->est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
+		r->n_open = h.ball_open;
+		return PGQ_OK;
+	}
+	void launch_meet3() {
+		// calls too small to fill the chip are bound by the longest row, not by bandwidth: more requests in flight shorten
+		// every row (meet_cap_small is a cap of their own; 4096 .. 16384 measured within 3 % of each other: it ships equal
+		// to meet_cap)
+		const int64_t cap = std::max(1, paths ? opt.meet_cap_paths : (small_call ? opt.meet_cap_small : opt.meet_cap));
+		const bool bigv = c->V > (1 << 20);
+		const int pk = c->pack_k;
+		KernelTimer kt(st, K_MEET);
+		const unsigned resident = (unsigned)ncu * 32 / kMeetWPB; // more workgroups than the chip holds at once: up to 8 rounds
+		const dim3 grid((unsigned)std::min<int64_t>((n + kMeetWPB - 1) / kMeetWPB, (int64_t)std::max(1, opt.meet_grid_mult) * resident));
+		MeetHostBlock *fin = last_stage == 0 ? hb : nullptr;
+		const u32 *d_go = decide ? &db->dec.go : nullptr; // the gate's verdict on the device
+		// the hop-count walks read the packed lists (pack_k ids per group) when the upload built them; the path flow the
+		// 32-bit ones.  K = 5 only exists beyond 2^21 vertices: always BIGV
+#define PGQ_MEET3K(P, B, D, K, XF, XR)                                                                                   \
+	hipLaunchKernelGGL((k_meet3<P, B, D, K>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, \
+	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin)
+#define PGQ_MEET3(P, B, D)                                                                                               \
+	do {                                                                                                                 \
+		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \
+		else if (!P && pk == 5) PGQ_MEET3K(false, true, D, 5, c->ppadj, c->prpadj);                                    \
+		else PGQ_MEET3K(P, B, D, 4, c->padj, c->rpadj);                                                                 \
+	} while (0)
+		if (paths) {
+			if (bigv) PGQ_MEET3K(true, true, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
+			else PGQ_MEET3K(true, false, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
+		} else if (small_call && n <= (int64_t)opt.meet_wide_rows && (opt.meet_wide_rows_always || (double)c->E * 4.0 > 256e6)) {
+			// chunk-sized calls on a graph whose adjacency does not fit the Infinity Cache (a list request is a DRAM round trip,
+			// ~3.5 us under load): several wavefronts per row (k_meet3w: 97 VGPRs, four wavefronts per SIMD = 4096 on the chip) —
+			// four while all rows are resident at once, else two.  Measured: R-MAT-22 x 1024 pairs 49 -> 41 us; the SF100-shaped
+			// graph (160 MB of padded lists, cache resident) 24.1 -> 25.5 us at 1024 rows, 29.1 -> 29.7 at 2048: not taken there
+#define PGQ_MEET3WK(B, W, K, XF, XR)                                                                                      \
+	hipLaunchKernelGGL((k_meet3w<B, W, K>), dim3((unsigned)n), dim3(64 * W), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
+	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin)
+#define PGQ_MEET3W(B, W)                                                                                                  \
+	do {                                                                                                                 \
+		if (pk == 6) PGQ_MEET3WK(B, W, 6, c->ppadj, c->prpadj);                                                        \
+		else if (pk == 5) PGQ_MEET3WK(true, W, 5, c->ppadj, c->prpadj);                                                \
+		else PGQ_MEET3WK(B, W, 4, c->padj, c->rpadj);                                                                   \
+	} while (0)
+			const bool four = n * 4 <= (int64_t)ncu * 16;
+			if (bigv && four) PGQ_MEET3W(true, 4);
+			else if (bigv) PGQ_MEET3W(true, 2);
+			else if (four) PGQ_MEET3W(false, 4);
+			else PGQ_MEET3W(false, 2);
+#undef PGQ_MEET3W
+#undef PGQ_MEET3WK
+		} else if (small_call) {
+			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH_SMALL);
+			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH_SMALL);
+		} else {
+			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH);
+			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH);
+		}
+#undef PGQ_MEET3
+#undef PGQ_MEET3K
+		kt.stop();
+	}
+	// k_meet4d (hop counts) or k_meet4<paths> over what k_meet3 queued
+	int launch_bitmap() {
+		const size_t lds = mp.lds_map ? mp.map_bytes() : 0;
+		const int64_t cap4 = (int64_t)std::max(1, opt.meet4_cap);
+		MeetHostBlock *fin = last_stage == 1 ? hb : nullptr;
+		KernelTimer kt(st, K_MEET4);
+		if (mp.lds_map) S.lds_map_launches[K_MEET4]++;
+		clear_launch_error();
+#define PGQ_MEET4(G)                                                                                                     \
+	hipLaunchKernelGGL((k_meet4<true, G>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj,     \
+	                   c->fdesc, c->rdesc, c->padj, c->rpadj, a.d_out, rec, cap4, mp.bm_words, db, gmaps, q[1], fin)
+// k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
+// per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
+#define PGQ_MEET4D(G, T)                                                                                                    \
+	hipLaunchKernelGGL((k_meet4d<G, T>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
+	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride)
+		if (paths && mp.lds_map) PGQ_MEET4(false);
+		else if (paths) PGQ_MEET4(true);
+		else if (mp.lds_map && d_trace) PGQ_MEET4D(false, true);
+		else if (mp.lds_map) PGQ_MEET4D(false, false);
+		else if (d_trace) PGQ_MEET4D(true, true);
+		else PGQ_MEET4D(true, false);
+#undef PGQ_MEET4D
+#undef PGQ_MEET4
+		PGQ_TRY(check_launch(st, paths ? "k_meet4" : "k_meet4d", lds));
+		kt.stop();
+		open_stage = 1;
+		return PGQ_OK;
+	}
+	// a handful of rows still open (far apart, unreachable, over the caps): one bidirectional search each, so that the
+	// lane-batched search — whole-graph levels — only starts for what really needs it.  The kernel checks the count itself.
+	int launch_bibfs_stage() {
+		MeetQueue qo2 = q[open_stage ^ 1]; // the other region: the stage that filled it has been read by now
+		qo2.count = &db->count[2];
+		qo2.count_back = nullptr; // one-ended: what k_bibfs leaves open is counted in count[2] alone (q[0] carries k_meet3's two-ended counter)
+		PGQ_TRY(launch_bibfs(c, ws, mp, bi_grid, q[open_stage], (u32)bibfs_rows, a.d_out, qcap, db, bi_maps, bi_maps + bi_map_words, qo2, hb));
+		set_open(ws, qo2);
+		open_stage = 2;
+		return PGQ_OK;
+	}
+	// shortestpath: the lists of the rows answered so far are laid out (element counts -> exclusive scan) and written in the
+	// same chain — the total comes back in the pinned block beside the statistics, so the call still waits once (round 3:
+	// three waits — chain, scan total, emission)
+	int emit_paths() {
+		int64_t *cnt = ws->meet_poff.as<int64_t>() + (n + 1), *poff = ws->meet_poff.as<int64_t>();
+		hipLaunchKernelGGL(k_path_counts, dim3(blocks_for(n)), dim3(256), 0, st, n, a.d_out, cnt);
+		PGQ_HIP_TRY(hipMemsetAsync(cnt + n, 0, 8, st));
+		size_t tmp = 0;
+		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cnt, poff, (int)(n + 1), st));
+		PGQ_TRY(ws->scan_tmp.reserve(tmp + 16)); // (the one buffer sized here: the scan names its own scratch)
+		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp, cnt, poff, (int)(n + 1), st));
+		PGQ_HIP_TRY(hipMemcpyAsync(&ws->h_meet->paths_total, poff + n, 8, hipMemcpyDeviceToHost, st));
+		KernelTimer kt(st, K_RECON);
+		hipLaunchKernelGGL(k_emit_paths, dim3((unsigned)n), dim3(256), 0, st, n, a.d_src, a.d_dst, a.d_out, rec, poff, c->off, c->adj,
+		                   c->edge_ids, a.po->d_child, a.po->child_cap, a.po->d_out_off);
+		kt.stop();
+		return PGQ_OK;
+	}
+	int read_report() {
+		PGQ_TRY(meet_wait(ws, hb, !paths));
+		if (decide_mode == DecideMode::Ride && ws->h_meet->sample_go) r->observed_go = (int)ws->h_meet->sample_go - 1;
+		if (paths) a.po->total = ws->h_meet->paths_total;
+		const MeetHostBlock &h = *hb;
+		if (d_trace) PGQ_TRY(print_meet4d_trace(d_trace, grid4, h.count[0]));
+		if (ball_mode && h.ball_go) return ball_took(h);
+		if (ball_mode) // it looked at the rows (8 B per row, twice) and declined
+			S.algo_bytes[K_BALL] += 16.0 * (double)n;
+		if (decide) r->est_sources = h.dec.estimate;
+		if (decide && !h.dec.go) return called_off();
+		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
+		const u32 open = h.count[open_stage];
+		if (!paths && opt.bibfs_rows > 0) {
+			const u32 before_bi = h.count[run4 ? 1 : 0]; // rows open when k_bibfs was (or would have been) launched
+			c->meet_far_rows.store((int)std::min<u32>(before_bi, 1u << 30), std::memory_order_relaxed); // their number sizes the next call's grid
+		}
+		S.meet_pairs += n - (int64_t)open;
+		S.edges_scanned += (int64_t)(h.entries[0] + h.entries[1] + h.entries[2]);
+		// 4 B per adjacency entry / one-hop id and 16 / K B per entry walked over the packed lists (K ids per 16-byte group),
+		// 16 B per slot descriptor; k_meet3: per row its ids (16 B), the four offsets and two walk sizes of its endpoints (40 B)
+		// and its result (8 B); the bit-map kernel: per queued row its entry (48 B) and its result (8 B)
+		auto list_bytes = [&](int k) {
+			const double pw = (double)std::min(h.walked[k], h.entries[k]);
+			return 4.0 * ((double)h.entries[k] - pw) + (16.0 / (double)std::max(4, c->pack_k)) * pw;
+		};
+		S.algo_bytes[K_MEET] += list_bytes(0) + 16.0 * (double)h.vertices[0] + 64.0 * (double)n;
+		S.algo_bytes[K_MEET4] += list_bytes(1) + 16.0 * (double)h.vertices[1] + 56.0 * (double)(h.count[0] + h.count_back);
+		S.algo_bytes[K_BIBFS] += list_bytes(2) + 16.0 * (double)h.vertices[2];
+		tstats().route_bytes += 4.0 * (double)(h.entries[0] + h.entries[1] + h.entries[2]) + 16.0 * (double)(h.vertices[0] + h.vertices[1] + h.vertices[2]) +
+		                        64.0 * (double)n + 56.0 * (double)(h.count[0] + h.count_back);
+		r->n_open = open;
+		return PGQ_OK;
+	}
+};
+
 // Runs the pre-pass over n rows (device memory, or pinned host memory the device can address: the chunk entry points
 // hand their staging block over as it is); rows it answers get their hop count (or -1 for NULL) in d_out, the others end
 // up in ws->open_src / open_dst / open_idx and are counted in r->n_open.  The whole chain — decision (large inputs),
@@ -1608,437 +2069,8 @@ static int print_ball_trace(const unsigned long long *b_trace, u32 nseg, u32 ope
 // r->ball_took = true: the open rows are what IT left); Always = it always does (tests); Off = the chain starts with the
 // stage kernels.  r->ball_attempted: the two kernels were launched (there was room for their vertex bit maps).
 int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult *r) {
-	const int64_t n = a.n;
-	const int64_t *d_src = a.d_src, *d_dst = a.d_dst;
-	int64_t *d_out = a.d_out;
-	MeetPathsOut *po = a.po;
-	const double meet_bytes = a.meet_bytes, edge_bytes = a.edge_bytes;
-	const bool paths = po != nullptr;
 	*r = PrepassResult();
-	int ball_mode = a.ball == BallMode::Off ? 0 : (a.ball == BallMode::Always ? 2 : 1);
-	if (paths || !c->rseg || !c->fdesc || !c->rdesc || n < 2) ball_mode = 0;
-	// BallMode::Only: the route memo says the source-centric kernel took these buffers last time — the chain is its two
-	// kernels and a one-thread report, without the stage kernels that would only return at once behind it (65,536
-	// one-wavefront workgroups of k_meet3 and 256 of k_meet4d starting up to read one word: 28 us of a 0.36-ms call).  If it
-	// declines this time, r->answered = false and the caller runs the chain again without it.  If there is no room for its
-	// maps it is not attempted and the chain below (the stage kernels) answers the call.
-	const bool ball_only = a.ball == BallMode::Only;
-	// DecideMode::Ride: the route memo says the last call on these buffers was answered here: the chain runs ungated and the
-	// sample rides in k_meet4d's launch (its last workgroup, in the bit map's LDS) — r->observed_go gets its verdict for the
-	// memo, -1 when none was taken (12 us of kernel + a launch gap in front of every 65,536-row call otherwise; tried first:
-	// the sample on a second stream beside the chain — the extra launch and wait on the host cost what the kernel did)
-	DecideMode decide_mode = a.decide;
-	{ // the ride needs k_meet4d (distance-only flow) with its bit map in LDS and large enough to lend: else the gate again
-		const Options &o = options();
-		const int bmw = (int)((c->V + 127) / 128) * 4;
-		const size_t budget = (size_t)std::min(150, std::max(0, o.meet4_lds_kb)) * 1024;
-		if (decide_mode == DecideMode::Ride && !(o.meet4 && !paths && (size_t)bmw * 4 + 2048 <= budget && bmw >= kSampleSlots))
-			decide_mode = DecideMode::Gate;
-	}
-	const bool decide = decide_mode == DecideMode::Gate;
-	u32 *h_go = reinterpret_cast<u32 *>(static_cast<char *>(ws->h_meet) + 4104);
-	SampleArgs ride { meet_bytes, edge_bytes, nullptr, nullptr, n, d_src, c->V };
-	if (decide_mode == DecideMode::Ride) {
-		PGQ_TRY(ws->route_dec.reserve(sizeof(MeetDecision)));
-		*h_go = 0;
-		ride.out = ws->route_dec.as<MeetDecision>();
-		ride.h_go = h_go; // taken inside k_meet4d's launch when its map is in LDS and large enough; else no verdict this call
-	}
-	hipStream_t st = ws->stream;
-	pgq_stats_t &S = tstats().s;
-	const Options &opt = options();
-	MeetQueue q[2];
-	MeetDevBlock *db = nullptr;
-	MeetHostBlock *hb = nullptr;
-	PGQ_TRY(meet_buffers(ws, n, q, &db, &hb));
-	if (paths) PGQ_TRY(ws->meet_rec.reserve((size_t)n * sizeof(MeetPath)));
-	MeetPath *rec = paths ? ws->meet_rec.as<MeetPath>() : nullptr;
-	const u32 *d_go = decide ? &db->dec.go : nullptr;
-	// what is left after k_meet3 (distance >= 4, or over its caps): the bit-map kernels, launched straight behind on a
-	// fixed grid — they read the row count from the device.  The vertex bit map sits in LDS when it fits (V <= ~1.2 M);
-	// above that every workgroup gets a slice of a global buffer (L2-resident: 0.5 MB at V = 4 M).
-	const int bm_words = (int)((c->V + 127) / 128) * 4;
-	const size_t lds_budget = (size_t)std::min(150, std::max(0, opt.meet4_lds_kb)) * 1024;
-	const bool lds_map = (size_t)bm_words * 4 + 2048 <= lds_budget;
-	const size_t gm_budget = (size_t)std::max(0, opt.meet4_global_mb) << 20;
-	const bool run4 = opt.meet4 && (lds_map || (size_t)bm_words * 4 <= gm_budget);
-	// k_bibfs serves the few rows the two-hop kernels leave open (far apart, unreachable, over the caps).  Launching it
-	// costs ~12 us of stream time even when no row is open, so it stays in the chain only while this CSR has shown such
-	// rows: the first call runs it; a call that ends with every row answered before it switches it off, and any later
-	// call that leaves rows open (they go to the lane-batched search, same answers) switches it on again.
-	const bool run_bi = !paths && opt.bibfs_rows > 0 && c->meet_far_rows.load(std::memory_order_relaxed) != 0;
-	const int mwb = bm_words + 4;
-	const bool bi_lds = (size_t)2 * mwb * 4 + 2048 <= lds_budget; // k_bibfs: both sides' maps in LDS when they fit
-	const int qcap = std::max(1024, opt.bibfs_queue);
-	// round 6: how many rows it takes and on how many workgroups follows the graph and what the call before left: on a
-	// graph whose levels are expensive (R-MAT-22: a lane batch for the 15,800 far / unreachable rows of a 2 M-row cross product
-	// costs 19 ms) a bidirectional search per row on every CU is far cheaper than whole-graph levels for a few thousand rows,
-	// while a graph that has never shown more than a handful keeps the 64-workgroup launch (12 us when nothing is open)
-	const int far_rows = c->meet_far_rows.load(std::memory_order_relaxed);
-	const int bibfs_rows = opt.bibfs_rows <= 0 ? 0 : std::max(opt.bibfs_rows, (int)std::min<int64_t>(opt.bibfs_rows_max, c->E / 4096));
-	// (sized by what the last call left AND by this call's rows: a handle's first call knows nothing of the former, and 64
-	// workgroups for the 35,000 far rows of an R-MAT-22 cross product made that call 11 ms longer than the ones after it)
-	// (on graphs whose maps are global — V past the LDS: there far rows are the rule; a graph with LDS maps keeps the small
-	// grid until a call has left far rows: every workgroup owns 2.6 MB of queues, 512 of them 1.3 GB allocated on first use)
-	const int want_grid = std::max(far_rows / 16, bi_lds ? 0 : (int)std::min<int64_t>(n / 64, 1 << 20));
-	const u32 bi_grid = (u32)std::min(std::max(std::max(1, opt.bibfs_grid), std::min(want_grid, 2 * device_cus())), std::max(1, bibfs_rows));
-	// k_meet4d hands rows out dynamically: a grid of exactly the workgroups the chip holds (meet4_grid_mult = 2 per CU).
-	// A row alone on its CU is through in ~15 us, beside a second one in ~20 (the phases of a row are short bursts of
-	// instructions from 16 wavefronts, and two workgroups share the CU's issue slots): small calls, whose ~2 % of open rows
-	// do not fill 256 CUs anyway, get one workgroup per CU (8192 rows: 0.086 -> 0.076 ms, 2048 rows: 0.062 -> 0.053 ms)
-	const bool small_call = !paths && n <= (int64_t)opt.meet_small_rows;
-	u32 grid4 = (u32)std::min<int64_t>(n, (int64_t)device_cus() * std::max(1, paths ? 4 : (small_call ? 1 : opt.meet4_grid_mult)));
-	// round 6: a chunk-sized call leaves a few dozen rows open (2 % of 2048): a workgroup per CU for them starts 256 x 1024
-	// threads that find nothing to do and, worse, fills every CU — the chunk calls of DuckDB's other worker threads (one per
-	// DataChunk per thread, iterativelength.cpp:34) queue behind it instead of running beside it (tools/chunk_mt.cpp: 8 threads
-	// reached 47 M rows/s, 1.7 x one thread).  One workgroup per 16 rows, at least 16: rows are handed out dynamically anyway.
-	if (small_call) grid4 = std::min<u32>(grid4, (u32)std::max<int64_t>(16, n / 16));
-	size_t maps_bytes = 0;
-	if (run4 && !lds_map) {
-		grid4 = (u32)std::max<size_t>(1, std::min<size_t>((size_t)std::min<int64_t>(n, device_cus()), gm_budget / ((size_t)bm_words * 4)));
-		maps_bytes = (size_t)grid4 * bm_words * 4;
-	}
-	const size_t bi_map_words = (run_bi && !bi_lds) ? (size_t)bi_grid * 2 * mwb : 0;
-	const size_t bi_bytes = run_bi ? (bi_map_words + (size_t)bi_grid * 5 * qcap) * 4 + 64 : 0;
-	if (maps_bytes + bi_bytes > 0) PGQ_TRY(ws->meet_maps.reserve(maps_bytes + bi_bytes + 64));
-	u32 *gmaps = ws->meet_maps.as<u32>();
-	u32 *bi_maps = gmaps ? gmaps + (maps_bytes + 15) / 16 * 4 : nullptr;
-	meet_attributes();
-	// stage k appends to region k & 1 and counts in db->count[k]
-	for (int k = 0; k < 2; k++) q[k].count = &db->count[k];
-	if (run4 && !paths) q[0].count_back = &db->count[3]; // k_meet3 -> k_meet4d: long rows from the front, the others from the back
-	unsigned long long *d_trace = nullptr;
-	if (opt.meet_trace && run4 && !paths) {
-		PGQ_TRY(ws->meet_trace.reserve((size_t)grid4 * 32));
-		d_trace = ws->meet_trace.as<unsigned long long>();
-		PGQ_HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)grid4 * 32, st));
-	}
-	const int last_stage = run_bi ? 2 : (run4 ? 1 : 0);
-	// shortestpath on a large input: if the decision kernel calls the pre-pass off, nothing writes d_out — the list layout
-	// below must then see "no list" everywhere (-1 in every row), not what the buffer happened to hold
-	if (decide && paths) PGQ_HIP_TRY(hipMemsetAsync(d_out, 0xFF, (size_t)n * 8, st));
-	// ---- round 6: the source-centric kernels open the chain (pgq_ball.h) ----
-	unsigned long long *b_trace = nullptr;
-	if (ball_mode) {
-		// its vertex bit map: LDS when one workgroup's map + 23 KB of row state fit (two workgroups per CU when both do), else a
-		// slice of the global buffer the bit-map kernels use (they run only when this one declines)
-		const size_t row_state = 23 * 1024, lds_all = 160 * 1024;
-		const bool ball_lds = (size_t)bm_words * 4 + row_state <= std::min(lds_all, lds_budget + row_state);
-		unsigned grid_b = 0;
-		size_t ball_maps = 0;
-		if (ball_lds) {
-			grid_b = (unsigned)device_cus() * ((PGQ_BALL_WAVES >= 8 && 2 * ((size_t)bm_words * 4 + row_state) <= lds_all) ? 2u : 1u);
-		} else if ((size_t)bm_words * 4 <= gm_budget) {
-			grid_b = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)device_cus() * 2, gm_budget / ((size_t)bm_words * 4)));
-			ball_maps = (size_t)grid_b * bm_words * 4;
-		}
-		if (opt.ball_grid > 0) grid_b = std::min(grid_b, (unsigned)opt.ball_grid);
-		if (n <= (int64_t)opt.meet_small_rows) grid_b = std::min<unsigned>(grid_b, (unsigned)std::max<int64_t>(8, n / 16)); // (as for k_meet4d below: room for the other threads' chunks)
-		if (grid_b == 0) {
-			ball_mode = 0; // no room for the maps: the older routes
-		} else {
-			r->ball_attempted = true;
-			if (ball_maps > ws->meet_maps.cap) {
-				PGQ_TRY(ws->meet_maps.reserve(std::max(ball_maps, maps_bytes + bi_bytes + 64)));
-				gmaps = ws->meet_maps.as<u32>();
-				bi_maps = gmaps + (maps_bytes + 15) / 16 * 4;
-			}
-			PGQ_TRY(ws->ball_segs.reserve((size_t)n * 4));
-			static std::atomic<int> ball_attr { 0 };
-			if (!ball_attr.load()) {
-				(void)hipFuncSetAttribute((const void *)k_src_ball<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 137 * 1024);
-				(void)hipFuncSetAttribute((const void *)k_src_ball<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 137 * 1024);
-				ball_attr.store(1);
-			}
-			BallRule rule;
-			const double mean_deg = (double)c->E / (double)std::max<int64_t>(c->V, 1);
-			rule.seg_floor = 1024.0 * (double)std::max(0, opt.ball_seg_kb);
-			rule.seg_bytes = 4.0 * c->two_hop_mean + 32.0 * mean_deg + 64.0;
-			rule.row_bytes = 4.0 * std::min(mean_deg, 64.0) + (c->rhead ? 0.0 : 128.0) + 32.0; // the first 64 entries of the in-list, the line its position sits in (without rhead), the row
-			// a ball in a global map: every mark is a look in DRAM and an atomic there (R-MAT-22: ~5 ns per entry and workgroup
-			// against ~1 ns in LDS) ...
-			if (!ball_lds) rule.seg_bytes *= 8.0;
-			// ... and what this kernel leaves open is the pre-pass's to answer, at that kernel's measured bytes per row: the share of
-			// rows the last call on this graph shape left open (0 before the first) prices it.  R-MAT-22, 2048 x 1024: 1.7 % open x
-			// 1.7 MB per row = 28 KB per row — the lane batches (12 ms) are then the cheaper route, not this one (16.7 ms).
-			{
-				const double bpr = meet_bytes > 0 && n > 0 ? meet_bytes / (double)n : c->cal.meet_bpr.load(std::memory_order_relaxed);
-				rule.row_bytes += c->cal.ball_open_frac.load(std::memory_order_relaxed) * std::max(0.0, bpr);
-			}
-			rule.meet_bytes = meet_bytes;
-			rule.edge_bytes = edge_bytes > 0 ? edge_bytes : (double)c->E;
-			rule.bias = opt.ball_bias;
-			rule.mode = ball_mode;
-			rule.V = c->V;
-			const int64_t nwin = (n + kBallRows - 1) / kBallRows;
-			u32 seg_rows = (u32)kBallRows; // chunk-sized calls: shorter segments, more workgroups per source (k_ball_segments)
-			if (n <= (int64_t)opt.meet_small_rows) {
-				seg_rows = 64;
-				while ((int)seg_rows * 2 <= std::min(kBallRows, std::max(64, opt.ball_seg_rows_small))) seg_rows *= 2;
-			}
-			KernelTimer kt(st, K_BALL);
-			if (ball_lds) S.lds_map_launches[K_BALL]++;
-			clear_launch_error();
-			hipLaunchKernelGGL(k_ball_segments, dim3((unsigned)std::min<int64_t>(nwin, (int64_t)device_cus())), dim3(kBallRows), 0, st, n, d_src,
-			                   ws->ball_segs.as<u32>(), db, seg_rows);
-			const int64_t capb = std::max(1, opt.ball_cap), tcap = std::max(1, opt.ball_test_cap);
-			if (opt.meet_trace) {
-				PGQ_TRY(ws->ball_trace.reserve(256));
-				b_trace = ws->ball_trace.as<unsigned long long>();
-				PGQ_HIP_TRY(hipMemsetAsync(b_trace, 0, 256, st));
-			}
-#define PGQ_BALL(G, T, LDS)                                                                                                  \
-	hipLaunchKernelGGL((k_src_ball<G, T>), dim3(grid_b), dim3(kBallRows), LDS, st, n, d_src, d_dst, c->V, c->off, c->roff, c->fdesc, \
-	                   c->rdesc, c->padj, c->rpadj, c->rseg, opt.ball_head_mb > 0 ? c->rhead : (const uint4 *)nullptr, ws->ball_segs.as<u32>(), d_out, capb, tcap, \
-	                   bm_words, db, gmaps, q[0], rule, b_trace, seg_rows)
-			if (ball_lds && b_trace) PGQ_BALL(false, true, (size_t)bm_words * 4);
-			else if (ball_lds) PGQ_BALL(false, false, (size_t)bm_words * 4);
-			else if (b_trace) PGQ_BALL(true, true, 0);
-			else PGQ_BALL(true, false, 0);
-#undef PGQ_BALL
-			PGQ_TRY(check_launch(st, "k_src_ball", ball_lds ? (size_t)bm_words * 4 : 0));
-			kt.stop();
-		}
-	}
-	if (ball_only && ball_mode) {
-		hipLaunchKernelGGL(k_chain_end, dim3(1), dim3(64), 0, st, db, hb);
-		PGQ_TRY(meet_wait(ws, hb));
-		const MeetHostBlock &h = *hb;
-		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
-		if (!h.ball_go) { // not this time: nothing was answered
-			S.algo_bytes[K_BALL] += 16.0 * (double)n;
-			r->answered = false;
-			r->n_open = (u32)n;
-			return PGQ_OK;
-		}
-		r->ball_took = true;
-		if (b_trace) PGQ_TRY(print_ball_trace(b_trace, h.ball_nseg, h.ball_open));
-		ws->open_src = q[0].src;
-		ws->open_dst = q[0].dst;
-		ws->open_idx = q[0].idx;
-		S.meet_pairs += n - (int64_t)h.ball_open;
-		S.edges_scanned += (int64_t)h.ball_entries;
-		S.algo_bytes[K_BALL] += 4.0 * (double)h.ball_entries + 16.0 * (double)h.ball_descs + 32.0 * (double)n + 24.0 * (double)h.ball_nseg;
-		S.ball_segments += h.ball_nseg;
-		S.ball_calls++;
-		r->est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
-		r->n_open = h.ball_open;
-		return PGQ_OK;
-	}
-	// (tried in round 4: the decision kernel on a stream of its own beside k_meet3, which polls a stop flag — the event
-	// record / wait pair costs what the 12 us kernel does, and the polled word must be spread over many lines)
-	if (decide)
-		hipLaunchKernelGGL(k_meet_decide, dim3(1), dim3(1024), 0, st, n, d_src, c->V, meet_bytes, edge_bytes, &db->dec, (u32 *)nullptr,
-		                   (const u32 *)&db->ball.go);
-	{
-		// calls too small to fill the chip are bound by the longest row, not by bandwidth: more requests in flight shorten
-		// every row (meet_cap_small is a cap of their own; 4096 .. 16384 measured within 3 % of each other: it ships equal
-		// to meet_cap)
-		const bool small = small_call;
-		const int64_t cap = std::max(1, paths ? opt.meet_cap_paths : (small ? opt.meet_cap_small : opt.meet_cap));
-		const bool bigv = c->V > (1 << 20);
-		const int pk = c->pack_k;
-		KernelTimer kt(st, K_MEET);
-		const unsigned resident = (unsigned)device_cus() * 32 / kMeetWPB; // more workgroups than the chip holds at once: up to 8 rounds
-		const dim3 grid((unsigned)std::min<int64_t>((n + kMeetWPB - 1) / kMeetWPB, (int64_t)std::max(1, opt.meet_grid_mult) * resident));
-		MeetHostBlock *fin = last_stage == 0 ? hb : nullptr;
-		// the hop-count walks read the packed lists (pack_k ids per group) when the upload built them; the path flow the
-		// 32-bit ones.  K = 5 only exists beyond 2^21 vertices: always BIGV
-#define PGQ_MEET3K(P, B, D, K, XF, XR)                                                                                   \
-	hipLaunchKernelGGL((k_meet3<P, B, D, K>), grid, dim3(64 * kMeetWPB), 0, st, n, d_src, d_dst, c->V, c->off, c->adj, c->roff, \
-	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, d_out, rec, cap, d_go, db, q[0], fin)
-#define PGQ_MEET3(P, B, D)                                                                                               \
-	do {                                                                                                                 \
-		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \
-		else if (!P && pk == 5) PGQ_MEET3K(false, true, D, 5, c->ppadj, c->prpadj);                                    \
-		else PGQ_MEET3K(P, B, D, 4, c->padj, c->rpadj);                                                                 \
-	} while (0)
-		if (paths) {
-			if (bigv) PGQ_MEET3K(true, true, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
-			else PGQ_MEET3K(true, false, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
-		} else if (small && n <= (int64_t)opt.meet_wide_rows && (opt.meet_wide_rows_always || (double)c->E * 4.0 > 256e6)) {
-			// chunk-sized calls on a graph whose adjacency does not fit the Infinity Cache (a list request is a DRAM round trip,
-			// ~3.5 us under load): several wavefronts per row (k_meet3w: 97 VGPRs, four wavefronts per SIMD = 4096 on the chip) —
-			// four while all rows are resident at once, else two.  Measured: R-MAT-22 x 1024 pairs 49 -> 41 us; the SF100-shaped
-			// graph (160 MB of padded lists, cache resident) 24.1 -> 25.5 us at 1024 rows, 29.1 -> 29.7 at 2048: not taken there
-#define PGQ_MEET3WK(B, W, K, XF, XR)                                                                                      \
-	hipLaunchKernelGGL((k_meet3w<B, W, K>), dim3((unsigned)n), dim3(64 * W), 0, st, n, d_src, d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
-	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, d_out, cap, d_go, db, q[0], fin)
-#define PGQ_MEET3W(B, W)                                                                                                  \
-	do {                                                                                                                 \
-		if (pk == 6) PGQ_MEET3WK(B, W, 6, c->ppadj, c->prpadj);                                                        \
-		else if (pk == 5) PGQ_MEET3WK(true, W, 5, c->ppadj, c->prpadj);                                                \
-		else PGQ_MEET3WK(B, W, 4, c->padj, c->rpadj);                                                                   \
-	} while (0)
-			const bool four = n * 4 <= (int64_t)device_cus() * 16;
-			if (bigv && four) PGQ_MEET3W(true, 4);
-			else if (bigv) PGQ_MEET3W(true, 2);
-			else if (four) PGQ_MEET3W(false, 4);
-			else PGQ_MEET3W(false, 2);
-#undef PGQ_MEET3W
-#undef PGQ_MEET3WK
-		} else if (small) {
-			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH_SMALL);
-			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH_SMALL);
-		} else {
-			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH);
-			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH);
-		}
-#undef PGQ_MEET3
-#undef PGQ_MEET3K
-		kt.stop();
-	}
-	int open_stage = 0; // the stage whose queue holds what is open at the end
-	if (run4) {
-		const size_t lds = lds_map ? (size_t)bm_words * 4 : 0;
-		const int64_t cap4 = (int64_t)std::max(1, opt.meet4_cap);
-		MeetHostBlock *fin = last_stage == 1 ? hb : nullptr;
-		{
-			KernelTimer kt(st, K_MEET4);
-			if (lds_map) S.lds_map_launches[K_MEET4]++;
-			clear_launch_error();
-#define PGQ_MEET4(G)                                                                                                     \
-	hipLaunchKernelGGL((k_meet4<true, G>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj,     \
-	                   c->fdesc, c->rdesc, c->padj, c->rpadj, d_out, rec, cap4, bm_words, db, gmaps, q[1], fin)
-// k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
-// per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
-#define PGQ_MEET4D(G, T)                                                                                                    \
-	hipLaunchKernelGGL((k_meet4d<G, T>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
-	                   c->rpadj, d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), bm_words, db, gmaps, q[1], fin, d_trace, ride)
-			if (paths && lds_map) PGQ_MEET4(false);
-			else if (paths) PGQ_MEET4(true);
-			else if (lds_map && d_trace) PGQ_MEET4D(false, true);
-			else if (lds_map) PGQ_MEET4D(false, false);
-			else if (d_trace) PGQ_MEET4D(true, true);
-			else PGQ_MEET4D(true, false);
-#undef PGQ_MEET4D
-#undef PGQ_MEET4
-			PGQ_TRY(check_launch(st, paths ? "k_meet4" : "k_meet4d", lds));
-			kt.stop();
-		}
-		open_stage = 1;
-	}
-	// a handful of rows still open (far apart, unreachable, over the caps): one bidirectional search each, so that the
-	// lane-batched search — whole-graph levels — only starts for what really needs it.  The kernel checks the count itself.
-	if (run_bi) {
-		u32 *queues = bi_maps + bi_map_words;
-		const int64_t capb = (int64_t)std::max(1, opt.bibfs_cap);
-		const MeetQueue &qi = q[open_stage];
-		MeetQueue qo2 = q[open_stage ^ 1]; // the other region: the stage that filled it has been read by now
-		qo2.count = &db->count[2];
-		qo2.count_back = nullptr; // one-ended: what k_bibfs leaves open is counted in count[2] alone (q[0] carries k_meet3's two-ended counter)
-		{
-			KernelTimer kt(st, K_BIBFS);
-			if (bi_lds) S.lds_map_launches[K_BIBFS]++;
-			clear_launch_error();
-			if (bi_lds)
-				hipLaunchKernelGGL(k_bibfs<false>, dim3(bi_grid), dim3(1024), (size_t)2 * mwb * 4, st, qi, (u32)bibfs_rows,
-				                   c->off, c->adj, c->roff, c->radj, d_out, capb, bm_words, qcap, db, bi_maps, queues, qo2, hb);
-			else
-				hipLaunchKernelGGL(k_bibfs<true>, dim3(bi_grid), dim3(1024), 0, st, qi, (u32)bibfs_rows, c->off, c->adj,
-				                   c->roff, c->radj, d_out, capb, bm_words, qcap, db, bi_maps, queues, qo2, hb);
-			PGQ_TRY(check_launch(st, "k_bibfs", bi_lds ? (size_t)2 * mwb * 4 : 0));
-			kt.stop();
-		}
-		ws->open_src = qo2.src;
-		ws->open_dst = qo2.dst;
-		ws->open_idx = qo2.idx;
-		open_stage = 2;
-	} else {
-		ws->open_src = q[open_stage].src;
-		ws->open_dst = q[open_stage].dst;
-		ws->open_idx = q[open_stage].idx;
-	}
-	// shortestpath: the lists of the rows answered so far are laid out (element counts -> exclusive scan) and written in the
-	// same chain — the total comes back in the pinned block beside the statistics, so the call still waits once (round 3:
-	// three waits — chain, scan total, emission)
-	int64_t *h_total = reinterpret_cast<int64_t *>(static_cast<char *>(ws->h_meet) + 4096);
-	if (paths) {
-		PGQ_TRY(ws->meet_poff.reserve((size_t)(n + 1) * 8 * 2));
-		int64_t *cnt = ws->meet_poff.as<int64_t>() + (n + 1), *poff = ws->meet_poff.as<int64_t>();
-		hipLaunchKernelGGL(k_path_counts, dim3(blocks_for(n)), dim3(256), 0, st, n, d_out, cnt);
-		PGQ_HIP_TRY(hipMemsetAsync(cnt + n, 0, 8, st));
-		size_t tmp = 0;
-		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cnt, poff, (int)(n + 1), st));
-		PGQ_TRY(ws->scan_tmp.reserve(tmp + 16));
-		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp, cnt, poff, (int)(n + 1), st));
-		PGQ_HIP_TRY(hipMemcpyAsync(h_total, poff + n, 8, hipMemcpyDeviceToHost, st));
-		KernelTimer kt(st, K_RECON);
-		hipLaunchKernelGGL(k_emit_paths, dim3((unsigned)n), dim3(256), 0, st, n, d_src, d_dst, d_out, rec, poff, c->off, c->adj,
-		                   c->edge_ids, po->d_child, po->child_cap, po->d_out_off);
-		kt.stop();
-	}
-	PGQ_TRY(meet_wait(ws, hb, !paths));
-	if (decide_mode == DecideMode::Ride && *h_go) r->observed_go = (int)*h_go - 1;
-	if (paths) po->total = *h_total;
-	const MeetHostBlock &h = *hb;
-	if (d_trace) { // debugging aid: where k_meet4d's time goes
-		std::vector<unsigned long long> t((size_t)grid4 * 4);
-		PGQ_HIP_TRY(hipMemcpy(t.data(), d_trace, t.size() * 8, hipMemcpyDeviceToHost));
-		unsigned long long t0 = ~0ull, t1 = 0, rows = 0, longest = 0, first_end = ~0ull, last_start = 0, most = 0;
-		for (u32 b = 0; b < grid4; b++) {
-			if (!t[4 * b + 1]) continue;
-			t0 = std::min(t0, t[4 * b]);
-			t1 = std::max(t1, t[4 * b + 1]);
-			first_end = std::min(first_end, t[4 * b + 1]);
-			last_start = std::max(last_start, t[4 * b]);
-			rows += t[4 * b + 2];
-			most = std::max(most, t[4 * b + 2]);
-			longest = std::max(longest, t[4 * b + 3]);
-		}
-		fprintf(stderr, "[pgq] k_meet4d trace: %u workgroups, %llu rows (%u long first), at most %llu per workgroup, span %.1f us, last start +%.1f us, "
-		        "first end +%.1f us, longest row %.1f us\n",
-		        grid4, rows, h.count[0], most, (double)(t1 - t0) * 0.01, (double)(last_start - t0) * 0.01,
-		        (double)(first_end - t0) * 0.01, (double)longest * 0.01);
-	}
-	if (b_trace && h.ball_go) PGQ_TRY(print_ball_trace(b_trace, h.ball_nseg, h.ball_open));
-	if (ball_mode && h.ball_go) { // the source-centric kernel took the call: what is open sits in region 0, counted by itself
-		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
-		r->ball_took = true;
-		ws->open_src = q[0].src;
-		ws->open_dst = q[0].dst;
-		ws->open_idx = q[0].idx;
-		S.meet_pairs += n - (int64_t)h.ball_open;
-		S.edges_scanned += (int64_t)h.ball_entries;
-		// 4 B per adjacency entry (the balls' lists, the destinations' in-lists, the distance-4 walks), 16 B per slot descriptor,
-		// per row its ids, its destination's list position and its result (32 B), per segment its position and offsets (24 B)
-		S.algo_bytes[K_BALL] += 4.0 * (double)h.ball_entries + 16.0 * (double)h.ball_descs + 32.0 * (double)n + 24.0 * (double)h.ball_nseg;
-		S.ball_segments += h.ball_nseg;
-		S.ball_calls++;
-		r->est_sources = (double)h.ball_nrun; // (exact: the source runs it counted)
-		r->n_open = h.ball_open;
-		return PGQ_OK;
-	}
-	if (ball_mode) // it looked at the rows (8 B per row, twice) and declined
-		S.algo_bytes[K_BALL] += 16.0 * (double)n;
-	if (decide) r->est_sources = h.dec.estimate;
-	if (decide && !h.dec.go) {
-		r->answered = false;
-		r->n_open = (u32)n;
-		return PGQ_OK;
-	}
-	if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
-	const u32 open = h.count[open_stage];
-	if (!paths && opt.bibfs_rows > 0) {
-		const u32 before_bi = h.count[run4 ? 1 : 0]; // rows open when k_bibfs was (or would have been) launched
-		c->meet_far_rows.store((int)std::min<u32>(before_bi, 1u << 30), std::memory_order_relaxed); // their number sizes the next call's grid
-	}
-	S.meet_pairs += n - (int64_t)open;
-	S.edges_scanned += (int64_t)(h.entries[0] + h.entries[1] + h.entries[2]);
-	// 4 B per adjacency entry / one-hop id and 16 / K B per entry walked over the packed lists (K ids per 16-byte group),
-	// 16 B per slot descriptor; k_meet3: per row its ids (16 B), the four offsets and two walk sizes of its endpoints (40 B)
-	// and its result (8 B); the bit-map kernel: per queued row its entry (48 B) and its result (8 B)
-	auto list_bytes = [&](int k) {
-		const double pw = (double)std::min(h.walked[k], h.entries[k]);
-		return 4.0 * ((double)h.entries[k] - pw) + (16.0 / (double)std::max(4, c->pack_k)) * pw;
-	};
-	S.algo_bytes[K_MEET] += list_bytes(0) + 16.0 * (double)h.vertices[0] + 64.0 * (double)n;
-	S.algo_bytes[K_MEET4] += list_bytes(1) + 16.0 * (double)h.vertices[1] + 56.0 * (double)(h.count[0] + h.count_back);
-	S.algo_bytes[K_BIBFS] += list_bytes(2) + 16.0 * (double)h.vertices[2];
-	tstats().route_bytes += 4.0 * (double)(h.entries[0] + h.entries[1] + h.entries[2]) + 16.0 * (double)(h.vertices[0] + h.vertices[1] + h.vertices[2]) +
-	                        64.0 * (double)n + 56.0 * (double)(h.count[0] + h.count_back);
-	r->n_open = open;
-	return PGQ_OK;
+	return PrepassChain(c, ws, a, r).run();
 }
 
 // shortestpath: the caller reserved less than 9 elements per row (paths_reserve_mb) and the lists did not fit: the list
@@ -2057,7 +2089,7 @@ int meet_reemit_paths(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src
 // lists of the rows the pre-pass would answer (a cross product is called off: nothing of it would be used).
 int meet_decide_alone(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, double meet_bytes, double edge_bytes, bool *go) {
 	PGQ_TRY(ws->route_dec.reserve(sizeof(MeetDecision)));
-	u32 *h_go = reinterpret_cast<u32 *>(static_cast<char *>(ws->h_meet) + 4104);
+	u32 *h_go = &ws->h_meet->sample_go;
 	*h_go = 0;
 	hipLaunchKernelGGL(k_meet_decide, dim3(1), dim3(1024), 0, ws->stream, n, d_src, c->V, meet_bytes, edge_bytes,
 	                   ws->route_dec.as<MeetDecision>(), h_go, (const u32 *)nullptr);
@@ -2110,40 +2142,20 @@ int meet_bidirectional(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_sr
                        u32 *n_open) {
 	hipStream_t st = ws->stream;
 	pgq_stats_t &S = tstats().s;
-	const Options &opt = options();
 	MeetQueue q[2];
 	MeetDevBlock *db = nullptr;
 	MeetHostBlock *hb = nullptr;
 	PGQ_TRY(meet_buffers(ws, n, q, &db, &hb));
-	for (int k = 0; k < 2; k++) q[k].count = &db->count[k];
 	hipLaunchKernelGGL(k_bidir_classify, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, c->V, c->off, c->roff, d_out, db, q[0]);
-	const int bm_words = (int)((c->V + 127) / 128) * 4, mwb = bm_words + 4;
-	const size_t lds_budget = (size_t)std::min(150, std::max(0, opt.meet4_lds_kb)) * 1024;
-	const bool bi_lds = (size_t)2 * mwb * 4 + 2048 <= lds_budget;
-	const int qcap = std::max(1024, opt.bibfs_queue);
+	const MapPlan mp { c->V, options() };
+	const int qcap = std::max(1024, options().bibfs_queue);
 	const u32 grid = (u32)std::min<int64_t>(n, device_cus());
-	const size_t map_words = bi_lds ? 0 : (size_t)grid * 2 * mwb;
+	const size_t map_words = mp.bi_lds ? 0 : (size_t)grid * 2 * mp.mwb;
 	PGQ_TRY(ws->meet_maps.reserve((map_words + (size_t)grid * 5 * qcap) * 4 + 64));
 	u32 *maps = ws->meet_maps.as<u32>();
-	u32 *queues = maps + map_words;
 	meet_attributes();
-	const int64_t capb = (int64_t)std::max(1, opt.bibfs_cap);
-	{
-		KernelTimer kt(st, K_BIBFS);
-		if (bi_lds) S.lds_map_launches[K_BIBFS]++;
-		clear_launch_error();
-		if (bi_lds)
-			hipLaunchKernelGGL(k_bibfs<false>, dim3(grid), dim3(1024), (size_t)2 * mwb * 4, st, q[0], 0xFFFFFFFFu, c->off, c->adj,
-			                   c->roff, c->radj, d_out, capb, bm_words, qcap, db, maps, queues, q[1], hb);
-		else
-			hipLaunchKernelGGL(k_bibfs<true>, dim3(grid), dim3(1024), 0, st, q[0], 0xFFFFFFFFu, c->off, c->adj, c->roff, c->radj,
-			                   d_out, capb, bm_words, qcap, db, maps, queues, q[1], hb);
-		PGQ_TRY(check_launch(st, "k_bibfs", bi_lds ? (size_t)2 * mwb * 4 : 0));
-		kt.stop();
-	}
-	ws->open_src = q[1].src;
-	ws->open_dst = q[1].dst;
-	ws->open_idx = q[1].idx;
+	PGQ_TRY(launch_bibfs(c, ws, mp, grid, q[0], 0xFFFFFFFFu, d_out, qcap, db, maps, maps + map_words, q[1], hb));
+	set_open(ws, q[1]);
 	PGQ_TRY(meet_wait(ws, hb));
 	const MeetHostBlock &h = *hb;
 	if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");

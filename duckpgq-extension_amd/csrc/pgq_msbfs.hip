@@ -2393,7 +2393,7 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	if (sampled) {
 		PGQ_TRY(ws->route_dec.reserve(sizeof(MeetDecision)));
 		sm.out = ws->route_dec.as<MeetDecision>();
-		sm.h_go = reinterpret_cast<u32 *>(static_cast<char *>(ws->h_meet) + 4104);
+		sm.h_go = &ws->h_meet->sample_go;
 		*sm.h_go = 0;
 	}
 	// Stage 2 ahead of the wait (round 5): when the last call with this row count on this CSR was a ONE-batch call of width
@@ -2421,7 +2421,7 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	PGQ_TRY(lane_ranks(c, ws, n, d_src, d_dst, &U, !outp.want_te, sm, ahead_wd > 0 ? std::function<int()>(pre_wait) : std::function<int()>()));
 	MemoOutcome memo;
 	// (lane_ranks has waited for the stream) what the sample says about these rows decides the next call's route
-	memo.go_again = sampled && *reinterpret_cast<const u32 *>(static_cast<const char *>(ws->h_meet) + 4104) == 2;
+	memo.go_again = sampled && ws->h_meet->sample_go == 2;
 	S.unique_sources += U;
 	if (with_paths) PGQ_HIP_TRY(hipMemsetAsync(ws->soff.p, 0, (size_t)n * 8, st));
 	const int wd = choose_words(U);

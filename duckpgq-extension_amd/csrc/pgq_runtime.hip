@@ -634,7 +634,7 @@ int WorkspaceLease::acquire() {
 		if (hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking) != hipSuccess ||
 		    hipHostMalloc((void **)&ws->h_cnt, sizeof(Counters)) != hipSuccess ||
 		    hipHostMalloc((void **)&ws->h_log, sizeof(LevelLog) * (kSpecLevels + 3)) != hipSuccess ||
-		    hipHostMalloc(&ws->h_meet, 8192) != hipSuccess) {
+		    hipHostMalloc((void **)&ws->h_meet, sizeof(MeetPinned)) != hipSuccess) {
 			delete ws;
 			ws = nullptr;
 			return fail(PGQ_ERR_HIP, "cannot create a search workspace (stream / pinned counter block)");

@@ -260,6 +260,14 @@ struct LevelBuf {
 	int lay_WD = 0;
 };
 
+// The pinned block of a workspace's pre-pass chain: the chain's last workgroup writes its report (a MeetHostBlock,
+// pgq_meet.hip) at the front; two words behind it come back the same way, so that a call still waits once.
+struct MeetPinned {
+	alignas(16) unsigned char report[4096];
+	int64_t paths_total; // shortestpath: elements of the lists the chain wrote (copied behind its scan)
+	u32 sample_go;       // the sampled decision's verdict + 1 (k_meet_decide alone, riding in k_meet4d, lane_ranks); 0: none taken
+};
+
 struct Workspace {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev_block = nullptr; // blocking event of wait_stream (created when the process first has many calls in flight)
@@ -277,7 +285,7 @@ struct Workspace {
 	LevelLog *h_log = nullptr; // pinned: [kSpecLevels + 2] counters per enqueued-ahead level, then two status words
 	int64_t wb_V = -1;  // what wb_scratch's label arrays are initialised for
 	int wb_grid = 0;
-	void *h_meet = nullptr;    // pinned, 8 KB: the last workgroup of the pre-pass chain writes its statistics here
+	MeetPinned *h_meet = nullptr; // pinned: the last workgroup of the pre-pass chain writes its statistics here
 	bool meet_cnt_clean = false; // the device statistics block is all zero (the chain's last kernel leaves it so)
 	// where the pre-pass left the rows it could not answer (one of the two queue regions inside def_src / def_dst / def_idx)
 	int64_t *open_src = nullptr, *open_dst = nullptr;

@@ -19,8 +19,8 @@ ARCH_TRIPLE = "hipv4-amdgcn-amd-amdhsa--gfx950"
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 LDS_ALL = 160 * 1024        # LDS per CU (gfx950)
-MEET4_BUDGET = 150 * 1024   # option meet4_lds_kb, capped at 150 (pgq_meet.hip, meet_prepass: lds_budget; meet_bidirectional)
-BALL_ROW_STATE = 23 * 1024  # what meet_prepass keeps for k_src_ball's own arrays (row_state)
+MEET4_BUDGET = 150 * 1024   # option meet4_lds_kb, capped at 150 (pgq_meet.hip, MapPlan: lds_budget, kMapLdsKB)
+BALL_ROW_STATE = 23 * 1024  # what MapPlan keeps for k_src_ball's own arrays (kBallRowState)
 WDS = (1, 2, 4, 8, 16, 32)
 
 
@@ -103,16 +103,16 @@ def largest(fits):
 
 
 def bm_bytes(V):
-    return ((V + 127) // 128) * 4 * 4  # bm_words = ceil(V / 128) * 4 (pgq_meet.hip, meet_prepass and meet_bidirectional)
+    return ((V + 127) // 128) * 4 * 4  # bm_words = ceil(V / 128) * 4 (pgq_meet.hip, MapPlan)
 
 
 # ---- the host rules, as written in the library ---------------------------------------------------------------------------
 
-def ball_lds(V):  # pgq_meet.hip, meet_prepass: ball_lds
+def ball_lds(V):  # pgq_meet.hip, MapPlan: ball_lds
     return bm_bytes(V) + BALL_ROW_STATE <= min(LDS_ALL, MEET4_BUDGET + BALL_ROW_STATE)
 
 
-def ball_two_per_cu(V):  # ... grid_b: two workgroups per CU when both fit (PGQ_BALL_WAVES = 8)
+def ball_two_per_cu(V):  # ... ball_two: two workgroups per CU when both fit (PGQ_BALL_WAVES = 8)
     return 2 * (bm_bytes(V) + BALL_ROW_STATE) <= LDS_ALL
 
 
@@ -120,7 +120,7 @@ def meet4_lds(V):  # ... lds_map
     return bm_bytes(V) + 2048 <= MEET4_BUDGET
 
 
-def bibfs_lds(V):  # ... bi_lds (and meet_bidirectional): two maps of bm_words + 4 words
+def bibfs_lds(V):  # ... bi_lds: two maps of bm_words + 4 words
     return 2 * (bm_bytes(V) // 4 + 4) * 4 + 2048 <= MEET4_BUDGET
 
 
@@ -142,7 +142,7 @@ def test_src_ball_static_lds_leaves_room_for_its_map(static_lds):
     for gm in (0, 1):  # k_src_ball<GM, TRACE>: the map in LDS / in global memory
         s = one_size(static_lds, "k_src_ball", lambda a, gm=gm: a[0] == gm)
         assert s <= BALL_ROW_STATE, "k_src_ball uses %d B of static LDS, over the %d B row_state of meet_prepass" % (s, BALL_ROW_STATE)
-    assert bm_bytes(LDS_LIMITS["ball_1_per_cu"]) <= 137 * 1024  # the MaxDynamicSharedMemorySize meet_prepass sets
+    assert bm_bytes(LDS_LIMITS["ball_1_per_cu"]) <= 137 * 1024  # the MaxDynamicSharedMemorySize meet_attributes() sets (kBallLdsAttr)
 
 
 @pytest.mark.parametrize("name,pick,maps", [("k_meet4d", lambda a: a[0] == 0, 1), ("k_meet4", lambda a: a[1] == 0, 1),
