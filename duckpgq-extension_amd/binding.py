@@ -76,6 +76,9 @@ def load_hip():
     L.pgq_csr_w_type.argtypes = [C.c_void_p]
     L.pgq_csr_pack_k.argtypes = [C.c_void_p]
     L.pgq_iterativelength.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
+    L.pgq_iterativelength_within.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pgq_iterativelength_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                         C.c_void_p]
     L.pgq_shortestpath.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_cheapest_path_length.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
@@ -133,6 +136,8 @@ def load_udf():
               "pgq_udf_cheapest_path_length",
               "pgq_udf_reachability"):
         getattr(L, f).argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
+    L.pgq_udf_iterativelength_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64,
+                                                 C.c_void_p, C.c_void_p]
     L.pgq_udf_shortestpath.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
@@ -354,6 +359,15 @@ class DeviceCSR:
         _check(self.L.pgq_iterativelength(self.h, self.V, n, sv, dv, _p(out), _p(ov)))
         return out, unpack_validity(ov, n)
 
+    def iterativelength_within(self, src, dst, max_hops, src_valid=None, src_sel=None, dst_sel=None):
+        """iterativelength with the pattern's upper bound: rows more than max_hops hops apart are NULL."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, None, keep)
+        out = np.zeros(n, dtype=np.int64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_iterativelength_within(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
     def shortestpath(self, src, dst, src_valid=None, src_sel=None, dst_sel=None, raw=False):
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, None, keep)
@@ -383,6 +397,10 @@ class DeviceCSR:
     def iterativelength_bulk_ptr(self, n, d_src, d_dst, d_out):
         _check(self.L.pgq_iterativelength_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                       C.c_void_p(d_out)))
+
+    def iterativelength_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out):
+        _check(self.L.pgq_iterativelength_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
+                                                             int(max_hops), C.c_void_p(d_out)))
 
     def local_clustering_coefficient(self, src, src_valid=None):
         keep = []
@@ -539,6 +557,17 @@ class PgqState:
         out = np.zeros(n, dtype=np.int64)
         fn = {1: self.U.pgq_udf_iterativelength, 2: self.U.pgq_udf_iterativelength2,
               3: self.U.pgq_udf_iterativelengthbidirectional}[variant]
+        ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, None, out)
+        return out, ok
+
+    def iterativelength_within(self, csr_id, V, src, dst, max_hops, src_valid=None, src_sel=None, dst_sel=None):
+        n = len(src_sel) if src_sel is not None else len(src)
+        out = np.zeros(n, dtype=np.int64)
+        hops = int(max_hops)
+
+        def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            return self.U.pgq_udf_iterativelength_within(s, csr_id, V, n, sv, dv, hops, out_p, ov_p)
+
         ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, None, out)
         return out, ok
 

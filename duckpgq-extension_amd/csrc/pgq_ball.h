@@ -137,7 +137,12 @@ constexpr int kBallFarRows = 16; // rows per segment whose distance-4 walk all 1
 #ifndef PGQ_BALL_UQ
 #define PGQ_BALL_UQ 2 // row quads (4 rows, 16 lanes each) a wavefront scans per step, all their loads in flight together
 #endif
-template <bool GM, bool TRACE>
+// BND (iterativelength_within): the tests for distances above `bound` are skipped, and a row a COMPLETE test has proved
+// farther than `bound` is NULL: not in S1 (always complete) under bound <= 1; not in a complete S2 under bound <= 2; its whole
+// in-list scanned against a complete S2 under bound <= 3; its distance-4 walk run to the end under bound <= 4.  What a cap
+// leaves undecided — S2 cut at `cap` or not walked for a hub source, a distance-4 walk cut at `test_cap`, the rows past the
+// first kBallFarRows far rows of a segment — stays open, as in the unbounded kernel.
+template <bool GM, bool TRACE, bool BND = false>
 __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                            int64_t V, const int64_t *__restrict__ off, const int64_t *__restrict__ roff,
                                                            const uint4 *__restrict__ fdesc, const uint4 *__restrict__ rdesc,
@@ -146,7 +151,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
                                                            const u32 *__restrict__ segs,
                                                            int64_t *__restrict__ out, int64_t cap, int64_t test_cap, int bm_words,
                                                            MeetDevBlock *__restrict__ db, u32 *__restrict__ gmaps, MeetQueue qopen, BallRule rule,
-                                                           unsigned long long *__restrict__ trace, u32 seg_rows) {
+                                                           unsigned long long *__restrict__ trace, u32 seg_rows, int bound) {
 	extern __shared__ __attribute__((aligned(16))) u32 s_map[]; // bm_words: one bit per vertex (GM: unused)
 	const u32 nseg = db->ball.nseg;
 	// every workgroup takes the same decision from the same two totals; workgroup 0 leaves it for the kernels behind this one
@@ -266,13 +271,16 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 			if (tid == 0) atomicAdd(&s_stat[1], 2ull * (unsigned long long)degS); // once as ids, once as the walk's descriptors
 			__syncthreads();
 			tick(1);
-			if (s_res[tid] == kBallOpenI && bit(di32)) s_res[tid] = 1;
+			if (s_res[tid] == kBallOpenI) {
+				if (bit(di32)) s_res[tid] = (!BND || bound >= 1) ? 1 : -1;
+				else if (BND && bound < 2) s_res[tid] = -1; // S1 is complete: distance >= 2
+			}
 			__syncthreads(); // every test against S1 is done before S2's marks land
 			// S2 = S1 + N_out(S1): the 16 wavefronts share every round of the source's descriptors.  Not for a hub: its walk is a
 			// round of 64 neighbours after the other, each a dependent descriptor read before its few list requests (R-MAT-22:
 			// a source with ~100,000 neighbours of ~16 entries each took 5.4 ms over a thousand rounds to reach the cap, the
 			// whole kernel's duration — for a ball that is cut, i.e. proves nothing beyond its set bits).  Such a ball stays S1.
-			if (degS > kBallMaxS1) {
+			if (degS > kBallMaxS1 || (BND && bound < 2)) { // (bound < 2: no row is open any more)
 				if (tid == 0) s_capped = 1;
 			} else {
 				bool capped = false;
@@ -297,6 +305,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 				bool scan = false;
 				if (s_res[tid] == kBallOpenI) {
 					if (bit(di32)) s_res[tid] = 2;
+					else if (BND && bound < 3 && s_capped == 0) s_res[tid] = -1; // S2 is complete: distance >= 3
 					else scan = s_capped == 0;
 				}
 				const u64 m = __ballot(scan);
@@ -439,7 +448,9 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 			// wavefront walking 32,768 entries alone held its whole workgroup at the barrier for ~130 us: the first version's tail).
 			{
 				constexpr int kOneShot = 1 << 20; // request stride that leaves the wavefront exactly one request (no refill)
-				const u32 n2 = s_n2;
+				if (BND && bound < 4) // their whole in-lists showed no vertex of the complete S2: distance >= 4
+					for (u32 it = (u32)tid; it < s_n2; it += (u32)kBallRows) s_res[s_q2[it]] = -1;
+				const u32 n2 = (BND && bound < 4) ? 0u : s_n2;
 				for (u32 it = (u32)wib; it < n2; it += (u32)(kBallRows / 64)) {
 					const u32 t = (u32)s_q2[it];
 					const int degD = (int)s_in[t].y;
@@ -468,7 +479,10 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 					const u32 t = (u32)s_q1[r];
 					const int degD = (int)s_in[t].y;
 					const uint4 *dl = rdesc + roff[s_d[t]];
-					if (tid == 0) s_flag = 0;
+					if (tid == 0) {
+						s_flag = 0;
+						if (BND) s_capped = 0; // (0 since the scans ran; from here on: this row's walk was cut)
+					}
 					__syncthreads();
 					bool f = false, capped = false;
 					int resume = 0;
@@ -481,11 +495,13 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 						    return *(volatile int *)&s_flag != 0;
 					    });
 					if (__any(f)) s_flag = 1;
+					if (BND && capped) s_capped = 1;
 					if (lane == 0 && e3) atomicAdd(&s_stat[0], e3);
 					__syncthreads();
 					if (tid == 0) {
 						atomicAdd(&s_stat[1], (unsigned long long)degD);
 						if (s_flag) s_res[t] = 4;
+						else if (BND && bound < 5 && s_capped == 0) s_res[t] = -1; // the walk ran to its end: distance >= 5
 					}
 				}
 			}

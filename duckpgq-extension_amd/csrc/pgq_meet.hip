@@ -251,8 +251,13 @@ namespace pgq {
 // PATHS: also record the path's inner vertices (MeetPath); the walk then runs from dst over the source-ordered in-lists.
 // BIGV: V > 2^20, the filter folds the higher id bits in.  DEPTH: list requests in flight.  K: ids per list group
 // (pgq_pack.h; K > 4: padj / rpadj are the packed copies).  PATHS walks the 32-bit lists.
-template <bool PATHS, bool BIGV, int DEPTH, int K>
-__global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH > 2 ? 5 : (K > 4 ? PGQ_MEET3_WAVES_PACKED : PGQ_MEET3_WAVES)))) void k_meet3(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
+// BND (iterativelength_within): rows farther apart than `bound` hops are NULL.  bound <= 2: the one-hop tests decide the row
+// and the two-hop walk is not started; bound == 3: a walk that ran to its END without a witness proves distance >= 4 — NULL
+// here, not queued.  A walk that was CUT proves nothing beyond distance >= 3: that row stays open whatever the bound, and
+// so do the rows whose lists are over the register set (the test that would exclude their distances never ran).
+// (Compiled for PGQ_MEET3_WAVES_PACKED wavefronts per SIMD over the 32-bit lists too: at 64 VGPRs the bound's tests spilled two.)
+template <bool PATHS, bool BIGV, int DEPTH, int K, bool BND = false>
+__global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH > 2 ? 5 : ((K > 4 || BND) ? PGQ_MEET3_WAVES_PACKED : PGQ_MEET3_WAVES)))) void k_meet3(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                   int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                   const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
                                                   const uint4 *__restrict__ fdesc, const uint4 *__restrict__ rdesc,
@@ -260,7 +265,8 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
                                                   const u32 *__restrict__ fwork, const u32 *__restrict__ rwork,
                                                   int64_t *__restrict__ out, MeetPath *__restrict__ rec, int64_t cap,
                                                   const u32 *__restrict__ go, MeetDevBlock *__restrict__ db, MeetQueue q,
-                                                  MeetHostBlock *__restrict__ fin) {
+                                                  MeetHostBlock *__restrict__ fin, int bound) {
+	static_assert(!PATHS || !BND, "a bounded search returns hop counts only");
 	static_assert(kMeetWPB == 1, "one wavefront per workgroup: the LDS arrays are addressed statically");
 	static_assert(!PATHS || K == 4, "the path flow walks the 32-bit lists");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
@@ -369,7 +375,11 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 		__builtin_amdgcn_wave_barrier();
 		{
 			if (__any(hit)) {
-				if (lane == 0) out[i] = 1;
+				if (lane == 0) out[i] = (!BND || bound >= 1) ? 1 : -1;
+				continue;
+			}
+			if (BND && bound < 2) { // distance >= 2 and at most `bound` hops wanted
+				if (lane == 0) out[i] = -1;
 				continue;
 			}
 			// distance 2: the middle vertex is the smallest common one
@@ -406,6 +416,10 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 					if constexpr (PATHS) rec[i].v1 = (int32_t)mid;
 					out[i] = 2;
 				}
+				continue;
+			}
+			if (BND && bound < 3) { // distance >= 3: the two-hop walk is not started
+				if (lane == 0) out[i] = -1;
 				continue;
 			}
 		}
@@ -458,8 +472,9 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 			}
 			// the walk ran to its end without a witness: the distance is at least 4; it was cut short: distances 1 and 2
 			// are excluded and the next stage takes the walk up where it stopped
-			out[i] = found ? 3 : (capped ? kMeetOpen : kMeetOpen4);
-			if (!found) {
+			const bool beyond = BND && bound < 4 && !found && !capped; // distance >= 4 proven under a bound of 3
+			out[i] = found ? 3 : (beyond ? -1 : (capped ? kMeetOpen : kMeetOpen4));
+			if (!found && !beyond) {
 				ent.flags = capped ? (kEntKnown3 | (fwd ? kEntFwd : 0u) | ((u32)resume << kEntResumeShift)) : kEntKnown4;
 				queue_push(q, (u32)i, ent);
 			}
@@ -477,7 +492,8 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 // registers (the same loads, cached), the filter is built once in LDS, distances 1 and 2 are tested by every wavefront alike
 // (so that the branches stay uniform across the workgroup), and the two-hop walk is split request by request (seg_walk's
 // stride); the first witness any of them finds ends the row.  Same tests in the same order as k_meet3: same answers.
-template <bool BIGV, int WPB, int K>
+// BND: as for k_meet3.
+template <bool BIGV, int WPB, int K, bool BND = false>
 __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                     int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                     const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
@@ -485,7 +501,7 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
                                                     const int32_t *__restrict__ padj, const int32_t *__restrict__ rpadj,
                                                     const u32 *__restrict__ fwork, const u32 *__restrict__ rwork,
                                                     int64_t *__restrict__ out, int64_t cap, const u32 *__restrict__ go,
-                                                    MeetDevBlock *__restrict__ db, MeetQueue q, MeetHostBlock *__restrict__ fin) {
+                                                    MeetDevBlock *__restrict__ db, MeetQueue q, MeetHostBlock *__restrict__ fin, int bound) {
 	static_assert(kFltWords / 256 <= 4 && (WPB == 2 || WPB == 4), "the filter is cleared in at most four 1-KB parts");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
 	__shared__ __attribute__((aligned(16))) unsigned char win_all[WPB][64];
@@ -577,8 +593,12 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 			vertices += (u32)exp_n;
 		}
 		__syncthreads();
-		if (__any(hit)) {
-			if (tid == 0) out[i] = 1;
+		if (__any(hit)) { // (workgroup-uniform: every wavefront holds the whole set)
+			if (tid == 0) out[i] = (!BND || bound >= 1) ? 1 : -1;
+			continue;
+		}
+		if (BND && bound < 2) {
+			if (tid == 0) out[i] = -1;
 			continue;
 		}
 		u32 mid = kMeetEmpty; // distance 2: any common neighbour
@@ -611,6 +631,10 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 			if (tid == 0) out[i] = 2;
 			continue;
 		}
+		if (BND && bound < 3) { // the two-hop walk is not started
+			if (tid == 0) out[i] = -1;
+			continue;
+		}
 		// distance 3: the walk's requests dealt out to the WPB wavefronts; every one may request cap / WPB entries
 		bool mine = false, capped = false;
 		int resume = 0;
@@ -634,8 +658,9 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 		__syncthreads();
 		if (tid == 0) {
 			const bool found = s_found != 0u, cut = s_capped != 0u;
-			out[i] = found ? 3 : (cut ? kMeetOpen : kMeetOpen4);
-			if (!found) { // (a cut walk is taken up from its start by the bit-map kernel: the wavefronts stopped in different rounds)
+			const bool beyond = BND && bound < 4 && !found && !cut; // distance >= 4 proven under a bound of 3
+			out[i] = found ? 3 : (beyond ? -1 : (cut ? kMeetOpen : kMeetOpen4));
+			if (!found && !beyond) { // (a cut walk is taken up from its start by the bit-map kernel: the wavefronts stopped in different rounds)
 				ent.flags = cut ? (kEntKnown3 | (fwd ? kEntFwd : 0u)) : kEntKnown4;
 				queue_push(q, (u32)i, ent);
 			}
@@ -901,13 +926,17 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 //     distance 3: two-hop walk of the cheaper endpoint against the map, ended by the first hit
 //     distance 4: map = two-hop set of the cheaper endpoint, two-hop walk of the other one, ended by the first hit
 // Rows with distance >= 4 proven start at the last step (cheaper endpoint: the shorter one-hop list).
-template <bool GM, bool TRACE>
+// BND (iterativelength_within): a test that ran to its END without a witness excludes its distance; when that distance is
+// `bound`, the row is NULL and the later tests are not run.  Unbounded, a row whose distance-4 walks both ended without a
+// witness is left open (k_bibfs's kind of row); under bound <= 4 it is NULL.  A walk over its cap proves nothing: such rows
+// stay open whatever the bound.
+template <bool GM, bool TRACE, bool BND = false>
 __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet4d(MeetQueue qin, const int32_t *__restrict__ adj, const int32_t *__restrict__ radj,
                                                  const uint4 *__restrict__ fdesc, const uint4 *__restrict__ rdesc,
                                                  const int32_t *__restrict__ padj, const int32_t *__restrict__ rpadj,
                                                  int64_t *__restrict__ out_rows, int64_t cap, int64_t test_cap, int bm_words,
                                                  MeetDevBlock *__restrict__ db, u32 *__restrict__ gmaps, MeetQueue qout,
-                                                 MeetHostBlock *__restrict__ fin, unsigned long long *__restrict__ trace, SampleArgs sm) {
+                                                 MeetHostBlock *__restrict__ fin, unsigned long long *__restrict__ trace, SampleArgs sm, int bound) {
 	extern __shared__ __attribute__((aligned(16))) u32 s_map[]; // bm_words: one bit per vertex (GM: the map is this workgroup's slice of `gmaps`)
 	// rows the stage before left open (counted on the device: no host round trip): nf from the front of its queue (the
 	// long ones), the rest from the back
@@ -1034,18 +1063,26 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 			// 270 us for one row — and the walk is taken up where k_meet3 stopped only if the side is the same
 			walk_fwd = workS <= workD;
 			resume3 = walk_fwd == ((flags & kEntFwd) != 0) ? (int)(flags >> kEntResumeShift) : 0;
-			const int32_t *set_list = walk_fwd ? radj + di : adj + so;
-			const int set_n = walk_fwd ? degD : degS;
-			for (int p = tid; p < set_n; p += kM4Threads) mark((u32)set_list[p]);
-			if (wib == 0) entries += (unsigned long long)set_n;
-			__syncthreads();
-			do3 = true;
+			if (BND && bound < 3) { // (k_meet3 starts no walk under such a bound: no row arrives cut)
+				result = -1;
+				do4 = false;
+			} else {
+				const int32_t *set_list = walk_fwd ? radj + di : adj + so;
+				const int set_n = walk_fwd ? degD : degS;
+				for (int p = tid; p < set_n; p += kM4Threads) mark((u32)set_list[p]);
+				if (wib == 0) entries += (unsigned long long)set_n;
+				__syncthreads();
+				do3 = true;
+			}
 		} else if (!known4) {
 			bool hit = false;
 			for (int p = tid; p < degS; p += kM4Threads) hit |= (u32)adj[so + p] == ed;
 			if (__any(hit) && lane == 0) s_flag = 1;
 			if (flag_snapshot()) { // dst in N_out(src)
-				result = 1;
+				result = (!BND || bound >= 1) ? 1 : -1;
+				do4 = false;
+			} else if (BND && bound < 2) {
+				result = -1;
 				do4 = false;
 			} else {
 				const int64_t work_f = (int64_t)workS, work_b = (int64_t)workD; // the two-hop walks' sizes came with the row
@@ -1067,6 +1104,9 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 				if (flag_snapshot()) {
 					result = 2;
 					do4 = false;
+				} else if (BND && bound < 3) {
+					result = -1;
+					do4 = false;
 				} else if (min(work_f, work_b) > cap) {
 					do4 = false; // stays open
 				} else {
@@ -1084,7 +1124,12 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 				result = 3;
 				do4 = false;
 			} else {
-				if (s_capped) do4 = false;
+				if (s_capped) {
+					do4 = false;
+				} else if (BND && bound < 4) { // the walk ran to its end: distance >= 4
+					result = -1;
+					do4 = false;
+				}
 				if (do4) clear_map(); // every wavefront is past its reads of the map (barriers above)
 				__syncthreads();
 			}
@@ -1169,6 +1214,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 				}
 			}
 			if (f4) result = 4;
+			else if (BND && bound <= 4 && !s_capped) result = -1; // both walks ran to their ends: distance >= 5
 		}
 		if (tid == 0) {
 			out_rows[row] = result;
@@ -1216,14 +1262,17 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 // and the search would have ended a round earlier), so the first meeting gives the BFS distance.  An empty new frontier
 // means that side's closure is complete: NULL, like the exhausted search of iterativelength.cpp:133-139.  A frontier over
 // `cap` entries or `qcap` vertices leaves the row open.
-template <bool GM>
+// BND (iterativelength_within): before a side is chosen, a + b >= bound ends the row with NULL.  Exact by the invariant
+// above: before an expansion the distance exceeds a + b, so it exceeds `bound`; and while a + b < bound a meeting reports
+// a + b + 1 <= bound.  The check sits in front of the cap test: a row the bound closes is not left open by a cap.
+template <bool GM, bool BND = false>
 __global__ __launch_bounds__(1024) void k_bibfs(MeetQueue qin, u32 max_rows,
                                                 const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                 const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
                                                 int64_t *__restrict__ out_rows, int64_t cap,
                                                 int bm_words, int qcap, MeetDevBlock *__restrict__ db,
                                                 u32 *__restrict__ gmaps, u32 *__restrict__ queues, MeetQueue qout,
-                                                MeetHostBlock *__restrict__ fin) {
+                                                MeetHostBlock *__restrict__ fin, int bound) {
 	const int64_t *const src = qin.src, *const dst = qin.dst;
 	const u32 *const didx = qin.idx;
 	MeetCounters *const mc = &db->m;
@@ -1314,6 +1363,10 @@ __global__ __launch_bounds__(1024) void k_bibfs(MeetQueue qin, u32 max_rows,
 #endif
 		__syncthreads();
 		for (;;) {
+			if (BND && lvl[0] + lvl[1] >= bound) { // the distance exceeds a + b
+				result = -1;
+				break;
+			}
 			const int side = work[0] <= work[1] ? 0 : 1; // 0: forward from src, 1: backward from dst
 			if (work[side] > cap) break;
 #ifdef PGQ_MEET3_ROWTRACE
@@ -1588,10 +1641,11 @@ static void meet_attributes() {
 	std::atomic<int> &set = attr_set[current_device() & 63];
 	if (set.load()) return;
 	const void *const map_kernels[] = { (const void *)k_meet4d<false, false>, (const void *)k_meet4d<false, true>, (const void *)k_meet4<true, false>,
-		                                    (const void *)k_bibfs<false> };
+		                                    (const void *)k_bibfs<false>, (const void *)k_meet4d<false, false, true>, (const void *)k_bibfs<false, true> };
 	for (const void *k : map_kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsKB * 1024);
 	(void)hipFuncSetAttribute((const void *)k_src_ball<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
 	(void)hipFuncSetAttribute((const void *)k_src_ball<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
+	(void)hipFuncSetAttribute((const void *)k_src_ball<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
 	set.store(1);
 }
 
@@ -1650,20 +1704,23 @@ static void set_open(Workspace *ws, const MeetQueue &qo) {
 }
 
 // k_bibfs over the first `rows` rows of qi, one workgroup per row: both visited maps in LDS when they fit, else in slices of `maps`
+// (bound >= 0: the bounded instantiations, rows farther apart are NULL)
 static int launch_bibfs(pgq_csr *c, Workspace *ws, const MapPlan &mp, u32 grid, const MeetQueue &qi, u32 rows, int64_t *d_out, int qcap,
-                        MeetDevBlock *db, u32 *maps, u32 *queues, const MeetQueue &qo, MeetHostBlock *hb) {
+                        MeetDevBlock *db, u32 *maps, u32 *queues, const MeetQueue &qo, MeetHostBlock *hb, int bound = -1) {
 	hipStream_t st = ws->stream;
 	const int64_t capb = (int64_t)std::max(1, options().bibfs_cap);
 	const size_t lds = mp.bi_lds ? mp.bi_bytes() : 0;
 	KernelTimer kt(st, K_BIBFS);
 	if (mp.bi_lds) tstats().s.lds_map_launches[K_BIBFS]++;
 	clear_launch_error();
-	if (mp.bi_lds)
-		hipLaunchKernelGGL(k_bibfs<false>, dim3(grid), dim3(1024), lds, st, qi, rows, c->off, c->adj, c->roff, c->radj, d_out, capb,
-		                   mp.bm_words, qcap, db, maps, queues, qo, hb);
-	else
-		hipLaunchKernelGGL(k_bibfs<true>, dim3(grid), dim3(1024), 0, st, qi, rows, c->off, c->adj, c->roff, c->radj, d_out, capb,
-		                   mp.bm_words, qcap, db, maps, queues, qo, hb);
+#define PGQ_BIBFS(G, B)                                                                                                      \
+	hipLaunchKernelGGL((k_bibfs<G, B>), dim3(grid), dim3(1024), lds, st, qi, rows, c->off, c->adj, c->roff, c->radj, d_out, capb,   \
+	                   mp.bm_words, qcap, db, maps, queues, qo, hb, bound)
+	if (mp.bi_lds && bound >= 0) PGQ_BIBFS(false, true);
+	else if (mp.bi_lds) PGQ_BIBFS(false, false);
+	else if (bound >= 0) PGQ_BIBFS(true, true);
+	else PGQ_BIBFS(true, false);
+#undef PGQ_BIBFS
 	PGQ_TRY(check_launch(st, "k_bibfs", lds));
 	kt.stop();
 	return PGQ_OK;
@@ -1716,6 +1773,9 @@ private:
 	// The ride needs k_meet4d (distance-only flow) with its bit map in LDS and large enough to lend: else the gate again
 	const bool may_ride = opt.meet4 && !paths && mp.lds_map && mp.bm_words >= kSampleSlots;
 	const DecideMode decide_mode = a.decide == DecideMode::Ride && !may_ride ? DecideMode::Gate : a.decide;
+	// iterativelength_within: the bounded instantiations of every kernel of the chain (hop counts only)
+	const bool bnd = a.max_hops >= 0 && !paths;
+	const int bound = bnd ? (int)std::min<int64_t>(a.max_hops, 1 << 30) : -1;
 	const bool decide = decide_mode == DecideMode::Gate;
 	// what is left after k_meet3 (distance >= 4, or over its caps): the bit-map kernels, launched straight behind on a
 	// fixed grid — they read the row count from the device
@@ -1816,13 +1876,13 @@ private:
 		gmaps = ws->meet_maps.as<u32>();
 		bi_maps = gmaps ? gmaps + (maps_bytes + 15) / 16 * 4 : nullptr;
 		if (ball_mode) PGQ_TRY(ws->ball_segs.reserve((size_t)n * 4));
-		if (ball_mode && opt.meet_trace) {
+		if (ball_mode && opt.meet_trace && !bnd) {
 			PGQ_TRY(ws->ball_trace.reserve(256));
 			b_trace = ws->ball_trace.as<unsigned long long>();
 		}
 		meet_attributes();
 		if (run4 && !paths) q[0].count_back = &db->count[3]; // k_meet3 -> k_meet4d: long rows from the front, the others from the back
-		if (opt.meet_trace && run4 && !paths) {
+		if (opt.meet_trace && run4 && !paths && !bnd) { // (the bounded kernels carry no trace)
 			PGQ_TRY(ws->meet_trace.reserve((size_t)grid4 * 32));
 			d_trace = ws->meet_trace.as<unsigned long long>();
 			PGQ_HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)grid4 * 32, st));
@@ -1845,7 +1905,7 @@ private:
 		// rows the last call on this graph shape left open (0 before the first) prices it.  R-MAT-22, 2048 x 1024: 1.7 % open x
 		// 1.7 MB per row = 28 KB per row — the lane batches (12 ms) are then the cheaper route, not this one (16.7 ms).
 		const double bpr = a.meet_bytes > 0 && n > 0 ? a.meet_bytes / (double)n : c->cal.meet_bpr.load(std::memory_order_relaxed);
-		rule.row_bytes += c->cal.ball_open_frac.load(std::memory_order_relaxed) * std::max(0.0, bpr);
+		if (!bnd) rule.row_bytes += c->cal.ball_open_frac.load(std::memory_order_relaxed) * std::max(0.0, bpr); // (an unbounded call's share: a bound closes most of those rows)
 		rule.meet_bytes = a.meet_bytes;
 		rule.edge_bytes = a.edge_bytes > 0 ? a.edge_bytes : (double)c->E;
 		rule.bias = opt.ball_bias;
@@ -1860,11 +1920,13 @@ private:
 		                   ws->ball_segs.as<u32>(), db, seg_rows);
 		const int64_t capb = std::max(1, opt.ball_cap), tcap = std::max(1, opt.ball_test_cap);
 		if (b_trace) PGQ_HIP_TRY(hipMemsetAsync(b_trace, 0, 256, st));
-#define PGQ_BALL(G, T)                                                                                                       \
-	hipLaunchKernelGGL((k_src_ball<G, T>), dim3(grid_b), dim3(kBallRows), lds, st, n, a.d_src, a.d_dst, c->V, c->off, c->roff, c->fdesc, \
+#define PGQ_BALL(G, T, ...)                                                                                                  \
+	hipLaunchKernelGGL((k_src_ball<G, T, ##__VA_ARGS__>), dim3(grid_b), dim3(kBallRows), lds, st, n, a.d_src, a.d_dst, c->V, c->off, c->roff, c->fdesc, \
 	                   c->rdesc, c->padj, c->rpadj, c->rseg, opt.ball_head_mb > 0 ? c->rhead : (const uint4 *)nullptr, ws->ball_segs.as<u32>(), a.d_out, capb, tcap, \
-	                   mp.bm_words, db, gmaps, q[0], rule, b_trace, seg_rows)
-		if (mp.ball_lds && b_trace) PGQ_BALL(false, true);
+	                   mp.bm_words, db, gmaps, q[0], rule, b_trace, seg_rows, bound)
+		if (bnd && mp.ball_lds) PGQ_BALL(false, false, true);
+		else if (bnd) PGQ_BALL(true, false, true);
+		else if (mp.ball_lds && b_trace) PGQ_BALL(false, true);
 		else if (mp.ball_lds) PGQ_BALL(false, false);
 		else if (b_trace) PGQ_BALL(true, true);
 		else PGQ_BALL(true, false);
@@ -1919,8 +1981,13 @@ private:
 		// the hop-count walks read the packed lists (pack_k ids per group) when the upload built them; the path flow the
 		// 32-bit ones.  K = 5 only exists beyond 2^21 vertices: always BIGV
 #define PGQ_MEET3K(P, B, D, K, XF, XR)                                                                                   \
-	hipLaunchKernelGGL((k_meet3<P, B, D, K>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, \
-	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin)
+	do {                                                                                                                 \
+		if (bnd) PGQ_MEET3KB(P, B, D, K, XF, XR, !P);                                                                   \
+		else PGQ_MEET3KB(P, B, D, K, XF, XR, false);                                                                    \
+	} while (0)
+#define PGQ_MEET3KB(P, B, D, K, XF, XR, BN)                                                                              \
+	hipLaunchKernelGGL((k_meet3<P, B, D, K, BN>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, \
+	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound)
 #define PGQ_MEET3(P, B, D)                                                                                               \
 	do {                                                                                                                 \
 		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \
@@ -1936,8 +2003,13 @@ private:
 			// four while all rows are resident at once, else two.  Measured: R-MAT-22 x 1024 pairs 49 -> 41 us; the SF100-shaped
 			// graph (160 MB of padded lists, cache resident) 24.1 -> 25.5 us at 1024 rows, 29.1 -> 29.7 at 2048: not taken there
 #define PGQ_MEET3WK(B, W, K, XF, XR)                                                                                      \
-	hipLaunchKernelGGL((k_meet3w<B, W, K>), dim3((unsigned)n), dim3(64 * W), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
-	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin)
+	do {                                                                                                                 \
+		if (bnd) PGQ_MEET3WKB(B, W, K, XF, XR, true);                                                                   \
+		else PGQ_MEET3WKB(B, W, K, XF, XR, false);                                                                      \
+	} while (0)
+#define PGQ_MEET3WKB(B, W, K, XF, XR, BN)                                                                                 \
+	hipLaunchKernelGGL((k_meet3w<B, W, K, BN>), dim3((unsigned)n), dim3(64 * W), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
+	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin, bound)
 #define PGQ_MEET3W(B, W)                                                                                                  \
 	do {                                                                                                                 \
 		if (pk == 6) PGQ_MEET3WK(B, W, 6, c->ppadj, c->prpadj);                                                        \
@@ -1951,6 +2023,7 @@ private:
 			else PGQ_MEET3W(false, 2);
 #undef PGQ_MEET3W
 #undef PGQ_MEET3WK
+#undef PGQ_MEET3WKB
 		} else if (small_call) {
 			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH_SMALL);
 			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH_SMALL);
@@ -1960,6 +2033,7 @@ private:
 		}
 #undef PGQ_MEET3
 #undef PGQ_MEET3K
+#undef PGQ_MEET3KB
 		kt.stop();
 	}
 	// k_meet4d (hop counts) or k_meet4<paths> over what k_meet3 queued
@@ -1975,15 +2049,19 @@ private:
 	                   c->fdesc, c->rdesc, c->padj, c->rpadj, a.d_out, rec, cap4, mp.bm_words, db, gmaps, q[1], fin)
 // k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
 // per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
-#define PGQ_MEET4D(G, T)                                                                                                    \
-	hipLaunchKernelGGL((k_meet4d<G, T>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
-	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride)
+#define PGQ_MEET4D(G, T) PGQ_MEET4DB(G, T, false)
+#define PGQ_MEET4DB(G, T, BN)                                                                                               \
+	hipLaunchKernelGGL((k_meet4d<G, T, BN>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
+	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride, bound)
 		if (paths && mp.lds_map) PGQ_MEET4(false);
 		else if (paths) PGQ_MEET4(true);
+		else if (bnd && mp.lds_map) PGQ_MEET4DB(false, false, true);
+		else if (bnd) PGQ_MEET4DB(true, false, true);
 		else if (mp.lds_map && d_trace) PGQ_MEET4D(false, true);
 		else if (mp.lds_map) PGQ_MEET4D(false, false);
 		else if (d_trace) PGQ_MEET4D(true, true);
 		else PGQ_MEET4D(true, false);
+#undef PGQ_MEET4DB
 #undef PGQ_MEET4D
 #undef PGQ_MEET4
 		PGQ_TRY(check_launch(st, paths ? "k_meet4" : "k_meet4d", lds));
@@ -1997,7 +2075,7 @@ private:
 		MeetQueue qo2 = q[open_stage ^ 1]; // the other region: the stage that filled it has been read by now
 		qo2.count = &db->count[2];
 		qo2.count_back = nullptr; // one-ended: what k_bibfs leaves open is counted in count[2] alone (q[0] carries k_meet3's two-ended counter)
-		PGQ_TRY(launch_bibfs(c, ws, mp, bi_grid, q[open_stage], (u32)bibfs_rows, a.d_out, qcap, db, bi_maps, bi_maps + bi_map_words, qo2, hb));
+		PGQ_TRY(launch_bibfs(c, ws, mp, bi_grid, q[open_stage], (u32)bibfs_rows, a.d_out, qcap, db, bi_maps, bi_maps + bi_map_words, qo2, hb, bound));
 		set_open(ws, qo2);
 		open_stage = 2;
 		return PGQ_OK;
@@ -2033,7 +2111,7 @@ private:
 		if (decide && !h.dec.go) return called_off();
 		if (h.bad) return fail(PGQ_ERR_INVALID_ARG, "src/dst rowid out of range [0,V)");
 		const u32 open = h.count[open_stage];
-		if (!paths && opt.bibfs_rows > 0) {
+		if (!paths && opt.bibfs_rows > 0 && !bnd) { // (a bounded call closes rows an unbounded one leaves open: it says nothing about those)
 			const u32 before_bi = h.count[run4 ? 1 : 0]; // rows open when k_bibfs was (or would have been) launched
 			c->meet_far_rows.store((int)std::min<u32>(before_bi, 1u << 30), std::memory_order_relaxed); // their number sizes the next call's grid
 		}

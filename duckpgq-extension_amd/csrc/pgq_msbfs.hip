@@ -40,6 +40,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstddef>
 #include <cstring>
 #include <memory>
@@ -1863,6 +1864,9 @@ private:
 	// levels enqueued ahead of the host under the plan of the last batch of this width; paths keep every
 	// level's frontier and the accounting pass its per-level sums: they stay on the round trip per level
 	const bool spec_ok = opt.spec_levels && !with_paths && !outp.want_te;
+	// iterativelength_within: level t answers the rows at distance t, so no level beyond the bound is launched — by the host's
+	// loop or from a plan — and what is open then keeps the NULL it started with; such a batch's levels are no plan for others
+	const int max_level = outp.max_hops >= 0 ? (int)std::min<int64_t>(outp.max_hops, 1 << 30) : INT_MAX;
 	const int plan_slot = WD == 1 ? 0 : (WD == 2 ? 1 : (WD == 4 ? 2 : (WD == 8 ? 3 : (WD == 16 ? 4 : 5))));
 	const LevelRule rule { (double)E, (double)V, opt.push_div, opt.sparse_below, WD, opt.force_mode, opt.force_pull,
 	                       opt.probe_always, use_probe ? 1 : 0 };
@@ -2240,11 +2244,11 @@ private:
 			std::lock_guard<std::mutex> g(c->plan_lock);
 			plan = c->level_plan[plan_slot];
 		}
-		if (!plan.empty() && (plan[0] & kLvSparse) && !lanes_ok) plan.clear();
+		if (!plan.empty() && (((plan[0] & kLvSparse) && !lanes_ok) || max_level < 1)) plan.clear();
 		return plan;
 	}
 	void store_plan() {
-		if (!spec_ok || ran_plan.empty()) return;
+		if (!spec_ok || ran_plan.empty() || outp.max_hops >= 0) return;
 		// (the last batch of a call may hold a handful of lanes: its levels are not what the next FULL batch will run)
 		const bool full = (U - (int64_t)base_lane) * 2 >= L;
 		std::lock_guard<std::mutex> g(c->plan_lock);
@@ -2258,7 +2262,7 @@ private:
 		u32 *status = spec_status();
 		status[0] = status[1] = 0;
 		int prev_stop = -1, K = 0;
-		for (; K < (int)plan.size() && K < kSpecLevels; K++) {
+		for (; K < (int)plan.size() && K < kSpecLevels && K < max_level; K++) { // (level K + 1)
 			const u32 bits = plan[(size_t)K];
 			if ((bits & kLvSparse) && !lanes_ok) break; // k_pull_sparse sizes a buffer from the frontier's words: not ahead of the host
 			snaps.push_back(snapshot());
@@ -2306,7 +2310,7 @@ private:
 	}
 	// one host round trip per level, from level t on
 	int round_trips(LevelLog last, int t) {
-		for (; last.unresolved > 0 && last.front_edges > 0; t++) {
+		for (; last.unresolved > 0 && last.front_edges > 0 && t <= max_level; t++) {
 			const u32 bits = decide_level(rule, last.front_edges, last.front_words, last.front_vertices, last.unresolved,
 			                              t == 1 ? WD : (int)last.nzw);
 			sparse_front_words = last.front_words;
@@ -2402,7 +2406,8 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	// idle through that wait and its wake-up (~15 us) and then run them (48 us on the 2.1 M-row cross product).  If the count
 	// says otherwise afterwards (more than one batch, another width) the normal path overwrites / redoes both: same answers.
 	const bool may_stay_in_place = !with_paths && !outp.want_te && mopt.sort_single_batch == 0;
-	if (!may_stay_in_place || !mopt.stage2_ahead) ahead_wd = 0;
+	const bool bounded = outp.max_hops >= 0; // off the route memo's record, both ways
+	if (!may_stay_in_place || !mopt.stage2_ahead || bounded) ahead_wd = 0;
 	else if (ahead_wd < 0) ahead_wd = memo_lookup(c, n, d_src, d_dst).ahead_wd; // (the route layer did not look)
 	bool rows_ahead = false;
 	auto pre_wait = [&]() -> int {
@@ -2433,7 +2438,7 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		memo.id_wd = wd;
 		memo.in_place = identity;
 	}
-	memo_record(c, n, d_src, d_dst, memo);
+	if (!bounded) memo_record(c, n, d_src, d_dst, memo);
 	auto run = [&](Workspace *priv, int b0, int bstride, SearchOutput &o) -> int {
 		switch (wd) {
 		case 1: return LaneBatches<1>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);

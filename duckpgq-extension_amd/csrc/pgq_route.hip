@@ -38,6 +38,15 @@ __global__ void k_scatter_te(int64_t n, const u32 *__restrict__ sidx, const int6
 	if (i < n) out[sidx[i]] = ste[i];
 }
 
+// iterativelength_within: whatever a stage reported beyond the bound becomes NULL (SearchOutput::max_hops)
+__global__ void k_clamp_hops(int64_t n, int64_t max_hops, int64_t *__restrict__ len) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n && len[i] > max_hops) len[i] = -1;
+}
+// The bound a search runs under: V - 1 hops and more reach whatever is reachable — the unbounded search (INT64_MAX is what
+// the binder holds for "no upper bound")
+static int64_t search_bound(const pgq_csr *c, int64_t max_hops) { return max_hops >= c->V - 1 ? -1 : max_hops; }
+
 // Whether the pair-centric pre-pass may run for this call at all, and whether the host-side cost model sends n rows
 // (each taken as a distinct source) to it.  Shared by search_device and the chunk entry point (zero-copy staging).
 constexpr int64_t kMeetDecideRows = 16384; // above: the distinct sources are sampled and the decision is taken on the device
@@ -112,7 +121,8 @@ int search_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, co
                   int64_t *d_out_len, bool with_paths, int64_t *d_out_off, int64_t *d_child_ext,
                   int64_t child_cap_ext, SearchOutput &outp) {
 	const Options &o = options();
-	const bool timed = o.route_timing && o.ball == 1 && outp.depth == 0 && !with_paths && !outp.want_te && !outp.bidir && !outp.no_ball &&
+	if (outp.max_hops >= 0) outp.no_memo = true; // a bounded call: off the record (SearchOutput::max_hops)
+	const bool timed = outp.max_hops < 0 && o.route_timing && o.ball == 1 && outp.depth == 0 && !with_paths && !outp.want_te && !outp.bidir && !outp.no_ball &&
 	                   outp.ball_hint != 0 && n >= (int64_t)std::max(1, o.route_timing_rows);
 	if (!timed) return search_device_impl(c, ws, n, d_src, d_dst, d_out_len, with_paths, d_out_off, d_child_ext, child_cap_ext, outp);
 	const double tb = c->cal.route_ball_ns.load(std::memory_order_relaxed), tl = c->cal.route_lanes_ns.load(std::memory_order_relaxed);
@@ -200,7 +210,8 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 	if (with_paths) PGQ_TRY(ensure_edge_ids(c)); // PGQ_UPLOAD_LAZY_EDGE_IDS: the first shortestpath call brings them over
 	const Options &mopt = options();
 	// a large call is about to be routed on the pre-pass's bytes per row: measured first if this CSR has none yet
-	if (prepass_may(c, outp) && n > kMeetDecideRows && mopt.meet_calibrate && c->cal.meet_bpr.load(std::memory_order_relaxed) <= 0)
+	const bool bounded = outp.max_hops >= 0; // neither reads nor feeds the calibration (before it exists: the pre-pass priced by the graph's two-hop mean)
+	if (prepass_may(c, outp) && n > kMeetDecideRows && mopt.meet_calibrate && !bounded && c->cal.meet_bpr.load(std::memory_order_relaxed) <= 0)
 		PGQ_TRY(calibrate_prepass(c));
 	if (outp.bidir && !with_paths && !outp.want_te && outp.depth == 0 && c->E > 0) {
 		u32 nd = 0;
@@ -231,7 +242,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 	BallMode ball = BallMode::Off;
 	if (!(with_paths || outp.no_ball || outp.bidir || outp.prefer_lanes || n < 2) && mopt.ball > 0)
 		ball = mopt.ball == 1 ? BallMode::Decide : BallMode::Always;
-	const bool ball_possible = ball != BallMode::Off && c->cal.ball_open_frac.load(std::memory_order_relaxed) <= 0.02; // before the memo's say on THESE rows as they lie
+	const bool ball_possible = ball != BallMode::Off && (bounded || c->cal.ball_open_frac.load(std::memory_order_relaxed) <= 0.02); // before the memo's say on THESE rows as they lie
 	if (ball == BallMode::Decide && (outp.ball_hint == 0 || !ball_possible)) ball = BallMode::Off;
 	// the caller has counted the source runs on the host and found the rows grouped: the chain is the two kernels alone (if
 	// the device's byte rule declines after all, run_prepass falls back to the stage kernels)
@@ -248,7 +259,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 	// the pre-pass chain over the rows as they lie (lengths)
 	auto run_prepass = [&](PrepassResult &r) -> int {
 		const double b0 = tstats().route_bytes;
-		PrepassArgs a { n, d_src, d_dst, d_out_len, nullptr, meet_bytes, edge_bytes, decide_mode, ball };
+		PrepassArgs a { n, d_src, d_dst, d_out_len, nullptr, meet_bytes, edge_bytes, decide_mode, ball, outp.max_hops };
 		PGQ_TRY(meet_prepass(c, ws, a, &r));
 		if (ball == BallMode::Only && r.ball_attempted && !r.ball_took) { // the kernels-alone chain declined these rows: the stage kernels after all
 			a.ball = BallMode::Off;
@@ -256,7 +267,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 			r.est_sources = -1.0; // (the source-centric kernel has just declined these rows: no sort by source for them)
 		}
 		if (r.ball_took) {
-			if (n >= 1024) {
+			if (n >= 1024 && !bounded) {
 				const double now = (double)r.n_open / (double)n, old = c->cal.ball_open_frac.load(std::memory_order_relaxed);
 				c->cal.ball_open_frac.store(0.5 * old + 0.5 * now, std::memory_order_relaxed);
 			}
@@ -264,7 +275,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 			outp.source_runs = r.est_sources;
 		}
 		if (!r.answered) return PGQ_OK;
-		if (n >= 1024 && !r.ball_took) { // what these rows really moved refines the CSR's bytes per row (half the weight to the newest call)
+		if (n >= 1024 && !r.ball_took && !bounded) { // what these rows really moved refines the CSR's bytes per row (half the weight to the newest call)
 			const double now = std::max(64.0, (tstats().route_bytes - b0) / (double)n);
 			const double old = c->cal.meet_bpr.load(std::memory_order_relaxed);
 			c->cal.meet_bpr.store(old > 0 ? 0.5 * old + 0.5 * now : now, std::memory_order_relaxed);
@@ -353,7 +364,7 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 		}
 		PrepassResult r;
 		PGQ_TRY(meet_prepass(c, ws, PrepassArgs { n, ws->sort_src.as<int64_t>(), ws->sort_dst.as<int64_t>(), ws->sort_out.as<int64_t>(), nullptr,
-		                                          meet_bytes, edge_bytes, DecideMode::None, BallMode::Only }, &r));
+		                                          meet_bytes, edge_bytes, DecideMode::None, BallMode::Only, outp.max_hops }, &r));
 		if (!r.ball_took) return PGQ_OK;
 		outp.route = 1;
 		outp.source_runs = r.est_sources;
@@ -470,14 +481,30 @@ int pgq_release_cached_memory(void) {
 	return PGQ_OK;
 }
 
+// max_hops: null = unbounded
 static int iterativelength_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                                bool bidir) {
+                                bool bidir, const int64_t *max_hops = nullptr) {
 	const bool arrays = d_src && d_dst && d_out_len;
-	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) {
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n, arrays, "NULL device array"));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
+		return PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
 		SearchOutput so;
 		so.bidir = bidir;
-		return search_device(csr, ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so);
+		so.max_hops = max_hops ? search_bound(csr, *max_hops) : -1;
+		PGQ_TRY(search_device(csr, ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so));
+		if (so.max_hops >= 0 && n > 0) {
+			hipLaunchKernelGGL(k_clamp_hops, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, so.max_hops, d_out_len);
+			PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
+		}
+		return PGQ_OK;
 	});
+}
+int pgq_iterativelength_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                           int64_t *d_out_len) {
+	return iterativelength_bulk(csr, n, d_src, d_dst, d_out_len, false, &max_hops);
 }
 int pgq_iterativelength_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                     int64_t *d_out_len) {
@@ -647,14 +674,18 @@ static int io_block(Workspace *ws, size_t bytes, void **host, void **dev) {
 	return PGQ_OK;
 }
 
+// max_hops: null = unbounded; else the rows farther apart are NULL (clamped here, on the host's pass over the results)
 static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
-                                 uint64_t *out_valid, bool bidir) {
+                                 uint64_t *out_valid, bool bidir, const int64_t *max_hops = nullptr) {
 	auto check = [&] {
 		PGQ_TRY(check_csr(csr, V));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		if (n < 0 || (n > 0 && (!out_len || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
 		return n == 0 ? kNoRows : PGQ_OK;
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		const int64_t bound = max_hops ? search_bound(csr, *max_hops) : -1;
+		const int64_t top = bound < 0 ? INT64_MAX : bound; // lengths above it are NULL
 		if (!bidir && options().chunk_zero_copy && prepass_takes(csr, n, SearchOutput()) && n <= kMeetDecideRows) {
 			// One DuckDB chunk through the pair-centric kernels: they read the rows straight out of a pinned staging block and
 			// write the hop counts straight back into it (2048 rows = 32 KB in, 16 KB out over PCIe, one access per row), so the
@@ -666,6 +697,7 @@ static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t
 			PGQ_TRY(flatten_pairs_into(V, n, src, dst, h, h + n));
 			SearchOutput so;
 			so.no_memo = true;
+			so.max_hops = bound;
 			{ // the rows are in host memory: whether they are grouped by source costs a pass over 2048 words here, two launches there
 				int64_t runs = 1;
 				for (int64_t i = 1; i < n; i++) runs += h[i] != h[i - 1];
@@ -677,7 +709,7 @@ static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t
 				uint64_t m = 0;
 				const int64_t lo = w * 64, cnt = std::min<int64_t>(64, n - lo);
 				for (int64_t k = 0; k < cnt; k++) {
-					const int64_t v = res[lo + k];
+					const int64_t v = res[lo + k] > top ? -1 : res[lo + k];
 					out_len[lo + k] = v;
 					m |= (uint64_t)(v >= 0) << k;
 				}
@@ -692,18 +724,25 @@ static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t
 		SearchOutput so;
 		so.bidir = bidir;
 		so.no_memo = true;
+		so.max_hops = bound;
 		PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
 		                      false, nullptr, nullptr, 0, so));
 		PGQ_TRY(staged_download(out_len, ws->out_len.p, (size_t)n * 8, ws->stream));
 		mask_fill_valid(out_valid, n);
-		for (int64_t i = 0; i < n; i++)
+		for (int64_t i = 0; i < n; i++) {
+			if (out_len[i] > top) out_len[i] = -1;
 			if (out_len[i] < 0) mask_set_invalid(out_valid, i); // payload stays -1 like iterativelength.cpp:100,137
+		}
 		return PGQ_OK;
 	});
 }
 int pgq_iterativelength(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
                         uint64_t *out_valid) {
 	return iterativelength_chunk(csr, V, n, src, dst, out_len, out_valid, false);
+}
+int pgq_iterativelength_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, int64_t *out_len,
+                               uint64_t *out_valid) {
+	return iterativelength_chunk(csr, V, n, src, dst, out_len, out_valid, false, &max_hops);
 }
 int pgq_iterativelength_bidirectional(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
                                       uint64_t *out_valid) {

@@ -385,6 +385,7 @@ struct PrepassArgs {
 	double meet_bytes = 0, edge_bytes = 0; // the byte rule's two sides (decision kernel, source-centric kernel)
 	DecideMode decide = DecideMode::None;
 	BallMode ball = BallMode::Off;
+	int64_t max_hops = -1; // iterativelength_within: >= 0 = rows farther apart are NULL (the kernels' bounded instantiations)
 };
 struct PrepassResult {
 	u32 n_open = 0;              // rows left in ws->open_src / open_dst / open_idx
@@ -430,6 +431,12 @@ struct SearchOutput {
 	// and every change of shape was routed one call late) — such calls neither read nor write it
 	bool no_memo = false;
 	bool prefer_lanes = false; // (in) large grouped call on a graph where the lane batches measured faster than the source-centric route, or their trial
+	// iterativelength_within: >= 0 = a row whose distance exceeds it is NULL; negative = unbounded.  Every stage stops where the
+	// bound lets it and the open rows' searches inherit it, but no stage is relied on to: the entry point clamps what comes back
+	// (a lane batch's probes answer rows a level or two ahead, k_meet4d reports 4 for a cut row under a bound of 3).  A bounded
+	// call is off the record of what unbounded calls are routed by (route memo, route timing, ball_open_frac, the refinement of
+	// meet_bpr, meet_far_rows; its lane batches store no level plan): a bounded row costs something else.
+	int64_t max_hops = -1;
 	int route = 0;             // (out) 1: the source-centric kernel took the call (as it lay, or sorted by source)
 	double source_runs = -1;   // (out) ... and counted this many source runs
 };
@@ -482,6 +489,8 @@ int search_open_rows(pgq_csr *c, Workspace *ws, u32 nd, const int64_t *src, cons
 		if (with_paths) PGQ_TRY(ws->def_off.reserve((size_t)nd * 8));
 		PGQ_TRY(inner.acquire());
 		child.depth = outp.depth + 1;
+		child.max_hops = outp.max_hops;
+		if (child.max_hops >= 0) child.no_memo = true;
 		tstats().s.pairs -= nd; // counted once
 		PGQ_TRY(search_device(c, inner.ws, nd, src, dst, ws->def_len.as<int64_t>(), with_paths, with_paths ? ws->def_off.as<int64_t>() : nullptr,
 		                      nullptr, 0, child));

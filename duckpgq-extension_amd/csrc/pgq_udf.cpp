@@ -284,6 +284,17 @@ int pgq_udf_iterativelength(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pg
 	return 0;
 }
 
+int pgq_udf_iterativelength_within(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
+                                   int64_t max_hops, int64_t *out, uint64_t *out_valid) {
+	CsrRef c;
+	pgq_csr_t *d;
+	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
+	if (pgq_iterativelength_within(d, V, n, src, dst, max_hops, out, out_valid) != PGQ_OK) return device_fail();
+	std::lock_guard<std::mutex> g(s->csr_lock);
+	s->csr_to_delete.insert(id); // iterativelength.cpp:142
+	return 0;
+}
+
 int pgq_udf_iterativelength2(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                              int64_t *out, uint64_t *out_valid) {
 	return pgq_udf_iterativelength(s, id, V, n, src, dst, out, out_valid);

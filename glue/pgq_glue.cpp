@@ -96,6 +96,24 @@ void IterativeLengthFunction(DataChunk &args, ExpressionState &state, Vector &re
 	in.state->csr_to_delete.insert(in.csr_id);
 }
 
+// iterativelength(csr_id, V, src, dst, upper): the five-argument overload the binder calls for a quantified edge pattern with
+// an upper bound (match.cpp:658-671 passes subpath->upper).  Rows more than `upper` hops apart are NULL; the BETWEEN filter
+// around the call stays as it is, so the query's result does not change.
+void IterativeLengthWithinFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	UnifiedVectorFormat upper_fmt; // a constant of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto result_data = FlatVector::GetDataMutable<int64_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	if (pgq_iterativelength_within(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src),
+	                               AsVec(in.dst), upper, result_data, validity.GetData()) != PGQ_OK)
+		ThrowDevice();
+	in.state->csr_to_delete.insert(in.csr_id);
+}
+
 void ShortestPathFunction(DataChunk &args, ExpressionState &state, Vector &result) {
 	SearchInputs in = Prepare(args, state, "shortest path");
 	result.SetVectorType(VectorType::FLAT_VECTOR);

@@ -139,6 +139,16 @@ int pgq_csr_pack_k(const pgq_csr_t *csr);
 int pgq_iterativelength(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t *out_len,
                         uint64_t *out_valid);
 
+/* iterativelength(csr_id, V, src, dst, upper) -> BIGINT: pgq_iterativelength, except that a row whose hop count exceeds
+ * max_hops is NULL (payload -1).  This is the call the binder's path-quantifier condition needs: AddPathQuantifierCondition
+ * (src/core/functions/table/match.cpp:658-671) emits `iterativelength(...) BETWEEN lower AND upper` for every quantified edge
+ * pattern, so whatever lies beyond `upper` is discarded by the filter — here the search stops there instead of running the
+ * far and unreachable rows to exhaustion (the lower bound needs nothing from the search and stays with the filter).
+ * src == dst -> 0 for every max_hops >= 0; max_hops >= V - 1 (INT64_MAX: the binder's "no upper bound") is the unbounded
+ * search, same values as pgq_iterativelength; max_hops < 0 -> PGQ_ERR_INVALID_ARG.  Same staging path and cost per call. */
+int pgq_iterativelength_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                               int64_t *out_len, uint64_t *out_valid);
+
 /* iterativelengthbidirectional(csr_id, V, src, dst) -> BIGINT (src/core/functions/scalar/iterativelength_bidirectional.cpp:43-153,
  * intended semantics: the reference's version is unreachable from the binder and indexes its backward CSR wrongly).
  * The same hop counts as pgq_iterativelength, found by one bidirectional BFS per row: forward over the CSR from src,
@@ -167,6 +177,10 @@ int pgq_release_cached_memory(void);
 /* d_src/d_dst/d_out_len: n int64 each in HBM.  d_out_len[i] = hop count, 0 for src==dst, -1 for NULL. */
 int pgq_iterativelength_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                     int64_t *d_out_len);
+/* pgq_iterativelength_within without the chunk ceiling (match.cpp:658-671: the pattern's upper bound): d_out_len[i] = hop
+ * count when it is at most max_hops, 0 for src == dst, -1 for NULL rows, unreachable rows and rows farther apart. */
+int pgq_iterativelength_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
+                                           int64_t max_hops, int64_t *d_out_len);
 /* the same rows through one bidirectional search each (pgq_iterativelength_bidirectional without the chunk ceiling) */
 int pgq_iterativelength_bidirectional_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                                   int64_t *d_out_len);

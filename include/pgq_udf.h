@@ -10,6 +10,7 @@
  *   pgq_udf_create_csr_edge         CreateCsrEdgeFunction        src/core/functions/scalar/csr_creation.cpp:112-198
  *   pgq_udf_bind_search             IterativeLengthBind          src/core/functions/function_data/iterative_length_function_data.cpp:18-30
  *   pgq_udf_iterativelength         IterativeLengthFunction      src/core/functions/scalar/iterativelength.cpp:34-143
+ *   pgq_udf_iterativelength_within  IterativeLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
  *   pgq_udf_iterativelength2        IterativeLength2Function     src/core/functions/scalar/iterativelength2.cpp:33-130 (same results)
  *   pgq_udf_iterativelengthbidirectional  IterativeLengthBidirectionalFunction  src/core/functions/scalar/iterativelength_bidirectional.cpp:43-153 (intended semantics)
  *   pgq_udf_shortestpath            ShortestPathFunction         src/core/functions/scalar/shortest_path.cpp:43-207
@@ -50,6 +51,10 @@ int pgq_udf_create_csr_edge(pgq_state_t *, int32_t id, int64_t V, int64_t e_sum,
 int pgq_udf_bind_search(pgq_state_t *, int32_t id);
 int pgq_udf_iterativelength(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                             int64_t *out, uint64_t *out_valid);
+/* iterativelength(id, V, src, dst, upper): rows more than max_hops hops apart are NULL (pgq_iterativelength_within);
+ * errors as for pgq_udf_iterativelength, max_hops < 0 is the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_iterativelength_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
+                                   int64_t max_hops, int64_t *out, uint64_t *out_valid);
 int pgq_udf_iterativelength2(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                              int64_t *out, uint64_t *out_valid);
 /* iterativelengthbidirectional(id, V, src, dst) -> BIGINT (src/core/functions/scalar/iterativelength_bidirectional.cpp:43-153).
