@@ -93,4 +93,245 @@ LDS_LIMITS = {
     # k_pull_lanes<WD, *, true> (lanes = 1) and k_pull_sparse<WD, *, 16, *> (lanes = 0), by lane words WD
     "pull_lanes": {1: 974_272, 2: 961_792, 4: 836_992, 8: 787_008, 16: 687_168, 32: 487_424},
     "pull_sparse": {1: 803_392, 2: 792_448, 4: 770_624, 8: 726_912, 16: 639_552, 32: 464_768},
+    # k_lcc_big's vertex bit map (pgq_analytics.hip:161, lcc_device: bm_words * 4 + 256 <= 150 KiB with bm_words = ceil(V / 32));
+    # above: a per-workgroup slice of global memory.  No kernel class counts its launches, so test_degree_edges_gpu.py checks
+    # results on both sides and nothing else
+    "lcc_big": 1_226_752,
 }
+
+
+# ---- gadgets whose adjacency-list lengths sit on the kernels' own constants ----------------------------------------------
+
+GADGET_DEGREES = (1, 2, 63, 64, 65, 319, 320, 321, 511, 512, 513, 4095, 4096, 4097)
+GADGET_POSITIONS = ("first", "last", 63, 64, 319, 320)
+GADGET_EXTRA_PAIRINGS = ((513, 4097),)
+_POOL0, _POOL1, _DEAD = 320, 4096, 1024
+# id regions, ascending: dead ends (sinks, roots) | path vertices that sort first | decoy pool 0 | path vertices at a numbered
+# index | decoy pool 1 | path vertices that sort last | everything else (endpoints, inner path vertices)
+_R_DEAD, _R_LOW, _R_P0, _R_MID, _R_P1, _R_HIGH, _R_ENDS = range(7)
+
+
+def decoy_len(j):
+    """List length of decoy j of a pool: 1..7, 0 in a cycle, and 255, 256, 257 three times in every 96 decoys."""
+    return {13: 255, 45: 256, 77: 257}.get(j % 96, (j + 1) % 8)
+
+
+def gadget_index(pos, n):
+    """The list index a position names in a list of n entries, or None where the list is too short for it."""
+    idx = 0 if pos == "first" else n - 1 if pos == "last" else pos
+    return idx if idx < n else None
+
+
+class Gadgets:
+    """V, the edge table (src, dst: table order is slot order), the rows (rs, rd, dist with -1 = unreachable, tag) and one
+    record per gadget: tag, k, a, b, pos, src, dst, paths (vertex lists), tie, row (index of its main row)."""
+
+    def __init__(self, V, src, dst, rs, rd, dist, tag, gadgets):
+        self.V, self.src, self.dst, self.rs, self.rd, self.dist, self.tag, self.gadgets = V, src, dst, rs, rd, dist, tag, gadgets
+
+    def transposed(self):
+        """Every edge and every row reversed: a and b swap, out-lists become in-lists, distances stay."""
+        gs = [dict(g, a=g["b"], b=g["a"], src=g["dst"], dst=g["src"], paths=[p[::-1] for p in g["paths"]]) for g in self.gadgets]
+        return Gadgets(self.V, self.dst, self.src, self.rd, self.rs, self.dist, self.tag, gs)
+
+    def shifted(self, V):
+        """The same graph on the last ids of [0, V)."""
+        o = V - self.V
+        assert o >= 0
+        gs = [dict(g, src=g["src"] + o, dst=g["dst"] + o, paths=[[v + o for v in p] for p in g["paths"]]) for g in self.gadgets]
+        return Gadgets(V, self.src + o, self.dst + o, self.rs + o, self.rd + o, self.dist, self.tag, gs)
+
+    def main_rows(self, pick=lambda g: True):
+        return np.array([g["row"] for g in self.gadgets if pick(g)], dtype=np.int64)
+
+
+def degree_gadgets(degrees=GADGET_DEGREES, positions=GADGET_POSITIONS, extra_pairings=GADGET_EXTRA_PAIRINGS,
+                   tie_degrees=(65, 513)):
+    """One graph of gadgets, each a source `src` of out-degree a and a destination `dst` of in-degree b that are exactly k hops
+    apart (k = 1 .. 4) by ONE shortest path, whose vertex sits at a chosen index of src's out-list and of dst's in-list; every
+    other entry of the two lists is a decoy.  Forward decoys come from a shared pool: each has a short out-list (decoy_len) into
+    a pool of sinks without out-edges.  Backward decoys mirror them: in-lists from roots without in-edges.  No decoy reaches or
+    is reached from an endpoint of another gadget, so rows of different gadgets do not disturb each other, and the path
+    vertices of different gadgets are disjoint.
+
+    Out-lists are in table order (csr_arrays_from_rows), in-lists in source-id order; the path vertex's id comes from a region
+    below, between or above the two decoy pools, and both lists of a gadget are emitted in ascending id order, so a position
+    holds in both directions and in the transposed graph.  Pairings per k and degree x: (x, x) at every position the list is
+    long enough for, (x, 1) and (1, x) at `last`, and `extra_pairings` at `last`.
+
+    Tie gadgets (tag tie<n>_...): n = 2, 3 disjoint shortest paths through the first, the last (and a middle) slot of src's
+    out-list, whose vertex ids DEscend in slot order, and ascend again on the destination's side for k >= 3.
+
+    Extra rows per gadget: src -> a sink of one of its decoys and a root -> dst (distance 2), dst -> src (unreachable)."""
+    enc = lambda region, serial: (np.int64(region) << 32) + np.asarray(serial, dtype=np.int64)
+    count = [0] * 7
+
+    def new(region, n=None):
+        at = count[region]
+        count[region] += 1 if n is None else n
+        return int(enc(region, at)) if n is None else enc(region, np.arange(at, at + n))
+
+    sinks, roots = new(_R_DEAD, _DEAD), new(_R_DEAD, _DEAD)
+    f0, b0 = new(_R_P0, _POOL0), new(_R_P0, _POOL0)
+    f1, b1 = new(_R_P1, _POOL1), new(_R_P1, _POOL1)
+    fdec, bdec = np.concatenate([f0, f1]), np.concatenate([b0, b1])
+    es, ed = [], []  # edge table, in pieces
+
+    def edges(s, d):
+        s, d = np.broadcast_arrays(np.asarray(s, dtype=np.int64), np.asarray(d, dtype=np.int64))
+        es.append(s.ravel())
+        ed.append(d.ravel())
+
+    for j in range(len(fdec)):  # decoy j: decoy_len(j) consecutive dead ends, starting at 7 j
+        dead = (7 * j + np.arange(decoy_len(j))) % _DEAD
+        edges(fdec[j], sinks[dead])
+        edges(roots[dead], bdec[j])
+
+    def region_of(pos):
+        return _R_LOW if pos == "first" else _R_HIGH if pos == "last" else _R_MID
+
+    def side(n, pos, pv, pool0, pool1):
+        """A list of n entries, ascending in id, with pv at gadget_index(pos, n)."""
+        idx = gadget_index(pos, n)
+        if n == 1:
+            return np.array([pv], dtype=np.int64)
+        if isinstance(pos, str):
+            decoys = np.concatenate([pool0, pool1])[:n - 1]
+            return np.concatenate([[pv], decoys] if pos == "first" else [decoys, [pv]]).astype(np.int64)
+        return np.concatenate([pool0[:idx], [pv], pool1[:n - 1 - idx]]).astype(np.int64)
+
+    rs, rd, dist, tag, gadgets = [], [], [], [], []
+
+    def row(s, d, k, t):
+        rs.append(s), rd.append(d), dist.append(k), tag.append(t)
+        return len(rs) - 1
+
+    def finish(t, k, a, b, pos, src, dst, paths, out_list, in_list, tie):
+        if k == 1:  # one table row is the path: it keeps its place among src's rows and among the rows into dst
+            ia, ib = int(np.flatnonzero(out_list == dst)[0]), int(np.flatnonzero(in_list == src)[0])
+            edges(src, out_list[:ia])
+            edges(in_list[:ib], dst)
+            edges(src, dst)
+            edges(src, out_list[ia + 1:])
+            edges(in_list[ib + 1:], dst)
+        else:
+            edges(src, out_list)
+            edges(in_list, dst)
+        edges(dst, sinks[(3 * len(gadgets) + np.arange(3)) % _DEAD])  # the endpoints have lists against the direction too
+        edges(roots[(3 * len(gadgets) + np.arange(3)) % _DEAD], src)
+        r = row(src, dst, k, t)
+        gadgets.append(dict(tag=t, k=k, a=a, b=b, pos=pos, src=src, dst=dst, paths=paths, tie=tie, row=r))
+        for v in out_list:  # distance 2 through a decoy: the first one that has a list
+            j = np.flatnonzero(fdec == v)
+            if len(j) and decoy_len(int(j[0])):
+                row(src, int(sinks[7 * int(j[0]) % _DEAD]), 2, t + "_sink")
+                break
+        for v in in_list:
+            j = np.flatnonzero(bdec == v)
+            if len(j) and decoy_len(int(j[0])):
+                row(int(roots[7 * int(j[0]) % _DEAD]), dst, 2, t + "_root")
+                break
+        row(dst, src, -1, t + "_rev")
+
+    def inner(k, m1, m2, serial):
+        """The path between the two one-hop vertices (k >= 3) and a few dead ends beside it; returns the path's inner part."""
+        t = serial % 4
+        edges(m1, sinks[(5 * serial + np.arange(t)) % _DEAD])
+        x = [new(_R_ENDS)] if k == 4 else []
+        chain = [m1] + x + [m2]
+        edges(chain[:-1], chain[1:])
+        edges(roots[(5 * serial + np.arange(t)) % _DEAD], m2)
+        return chain
+
+    def gadget(k, a, b, pos):
+        if gadget_index(pos, a) is None or gadget_index(pos, b) is None:
+            return
+        t = "k%d_a%d_b%d_%s" % (k, a, b, pos)
+        reg = region_of(pos)
+        if k == 1:
+            src, dst = new(reg), new(reg)
+            path, pv_out, pv_in = [src, dst], dst, src
+        else:
+            src, dst = new(_R_ENDS), new(_R_ENDS)
+            m1 = new(reg)
+            mids = [m1] if k == 2 else inner(k, m1, new(reg), len(gadgets))
+            path, pv_out, pv_in = [src] + mids + [dst], mids[0], mids[-1]
+        finish(t, k, a, b, pos, src, dst, [path], side(a, pos, pv_out, f0, f1), side(b, pos, pv_in, b0, b1), False)
+
+    def tie(k, n, deg):
+        src, dst = new(_R_ENDS), new(_R_ENDS)
+        regs = [_R_HIGH, _R_LOW] if n == 2 else [_R_HIGH, _R_MID, _R_LOW]  # ids descend in slot order
+        slots = [0, deg - 1] if n == 2 else [0, deg // 2, deg - 1]
+        firsts = [new(r) for r in regs]
+        if k == 2:
+            lasts, paths = firsts, [[src, m, dst] for m in firsts]
+        else:
+            lasts = [new(r) for r in regs[::-1]]
+            paths = [[src] + inner(k, m1, m2, 7 * len(gadgets) + i) + [dst] for i, (m1, m2) in enumerate(zip(firsts, lasts))]
+
+        def fill(pvs, pool):
+            out = np.empty(deg, dtype=np.int64)
+            free = np.setdiff1d(np.arange(deg), slots)
+            out[free] = pool[:len(free)]
+            out[slots] = pvs
+            return out
+
+        finish("tie%d_k%d_d%d" % (n, k, deg), k, deg, deg, "tie", src, dst, paths, fill(firsts, fdec), fill(lasts, bdec), True)
+
+    for k in (1, 2, 3, 4):
+        for x in degrees:
+            for pos in positions:  # (where `last` is also a numbered index — x = 64: index 63 — both are built)
+                gadget(k, x, x, pos)
+            if x > 1:
+                gadget(k, x, 1, "last")
+                gadget(k, 1, x, "last")
+        for a, b in extra_pairings:
+            gadget(k, a, b, "last")
+    for k in (2, 3, 4):
+        for n in (2, 3):
+            for deg in tie_degrees:
+                tie(k, n, deg)
+
+    base = np.concatenate([[0], np.cumsum(count)])
+    real = lambda v: base[np.asarray(v, dtype=np.int64) >> 32] + (np.asarray(v, dtype=np.int64) & 0xFFFFFFFF)
+    for g in gadgets:
+        g["src"], g["dst"] = int(real(g["src"])), int(real(g["dst"]))
+        g["paths"] = [[int(v) for v in real(p)] for p in g["paths"]]
+    return Gadgets(int(base[-1]), real(np.concatenate(es)), real(np.concatenate(ed)), real(rs), real(rd),
+                   np.array(dist, dtype=np.int64), np.array(tag), gadgets)
+
+
+LCC_DEGREES = (2, 64, 65, 511, 512, 513)
+
+
+def lcc_gadgets(big_rows=300):
+    """Vertices of out-degree exactly d, d in LCC_DEGREES, whose only triangle-closing edge runs from the neighbour in the last
+    slot to the neighbour in the first slot; the slots between hold leaves from a shared pool without out-edges.  Per degree
+    three variants: plain, the last neighbour twice (slots d - 2 and d - 1), and a self loop in a middle slot.  `big_rows` more
+    plain vertices of degree 513: more long rows than k_lcc_big has workgroups.  The first and last neighbours get the largest
+    ids.  Returns (vertex count, src, dst, the rows' vertices, their degrees)."""
+    pool = np.arange(513, dtype=np.int64)
+    n = len(pool)
+    specs = [(d, v) for d in LCC_DEGREES for v in ("plain", "dup", "loop")] + [(513, "plain")] * big_rows
+    hubs = n + np.arange(len(specs), dtype=np.int64)
+    firsts, lasts = hubs + len(specs), hubs + 2 * len(specs)
+    es, ed = [], []
+    for (d, variant), h, f, l in zip(specs, hubs, firsts, lasts):
+        row = np.concatenate([[f], pool[:d - 2], [l]]) if d > 2 else np.array([f, l])
+        if variant == "dup" and d > 2:
+            row[d - 2] = l
+        if variant == "loop" and d > 2:
+            row[d // 2] = h
+        es += [np.full(len(row), h), [l]]
+        ed += [row, [f]]
+    return int(lasts[-1]) + 1, np.concatenate(es).astype(np.int64), np.concatenate(ed).astype(np.int64), hubs, \
+        np.array([d for d, _ in specs])
+
+
+def spread_ids(rng, n, V):
+    """n ascending ids of [0, V): 0, V // 2, every id of the last 32-vertex word of a V-bit map, random ones between."""
+    top = (V - 1) // 32 * 32
+    fixed = np.concatenate([[0, V // 2], np.arange(top, V)])
+    ids = np.unique(np.concatenate([fixed, rng.choice(top, n, replace=False)]))
+    drop = rng.choice(np.flatnonzero(~np.isin(ids, fixed)), len(ids) - n, replace=False)
+    return np.delete(ids, drop).astype(np.int64)

@@ -135,6 +135,10 @@ def pull_sparse_lds(V, static):  # pgq_msbfs.hip, pull_sparse / launch_pull_spar
     return (static + 1) + bit_words * 6 + 256 <= LDS_ALL
 
 
+def lcc_big_lds(V):  # pgq_analytics.hip, lcc_device: in_lds (bm_words = ceil(V / 32))
+    return ((V + 31) // 32) * 4 + 256 <= 150 * 1024
+
+
 # ---- budgets ------------------------------------------------------------------------------------------------------------
 
 def test_src_ball_static_lds_leaves_room_for_its_map(static_lds):
@@ -171,6 +175,15 @@ def test_meet_kernel_edges_match_the_host_rules():
     assert largest(ball_lds) == LDS_LIMITS["ball_1_per_cu"], msg("ball_1_per_cu")
     assert largest(meet4_lds) == LDS_LIMITS["meet4"], msg("meet4")
     assert largest(bibfs_lds) == LDS_LIMITS["bibfs"], msg("bibfs")
+
+
+def test_lcc_big_edge_matches_the_host_rule(static_lds):
+    # k_lcc_big keeps 256 B for its own __shared__ state beside the map and asks for up to 150 KB of dynamic LDS
+    limit = largest(lcc_big_lds)
+    assert limit == LDS_LIMITS["lcc_big"], msg("lcc_big")
+    s = one_size(static_lds, "k_lcc_big", lambda a: True)
+    assert s <= 256, "k_lcc_big uses %d B of static LDS, over the 256 B lcc_device keeps for it" % s
+    assert s + ((limit + 31) // 32) * 4 <= LDS_ALL
 
 
 @pytest.mark.parametrize("wd", WDS)
