@@ -75,6 +75,8 @@ def load_hip():
         getattr(L, f).argtypes = [C.c_void_p]
     L.pgq_csr_w_type.argtypes = [C.c_void_p]
     L.pgq_csr_pack_k.argtypes = [C.c_void_p]
+    L.pgq_debug_live_device_blocks.restype = C.c_int64
+    L.pgq_debug_live_device_blocks.argtypes = []
     L.pgq_iterativelength.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
     L.pgq_iterativelength_within.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_iterativelength_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
@@ -237,6 +239,11 @@ def init_devices(devices):
 
 def reset_stats():
     _check(load_hip().pgq_reset_stats())
+
+
+def live_device_blocks():
+    """Device blocks handed out by the library's block cache and not freed yet (pgq_debug_live_device_blocks)."""
+    return load_hip().pgq_debug_live_device_blocks()
 
 
 def copy_bandwidth_gbps(nbytes=1 << 30, iters=10):

@@ -439,11 +439,10 @@ static int wcc_compute(pgq_csr *c, Workspace *ws) {
 			lap("Boruvka rounds");
 			// the chosen slots in ascending order (= the order the reference processes them in)
 			PGQ_TRY(sel.reserve((size_t)std::min<int64_t>(E, V) * 4 + 64));
-			size_t sb = 0;
 			hipcub::CountingInputIterator<u32> iota(0u);
-			PGQ_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, sb, iota, msf.as<uint8_t>(), sel.as<u32>(), cnt.as<u32>(), (int)E, st));
-			PGQ_TRY(tmp.reserve(sb + 16));
-			PGQ_HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, sb, iota, msf.as<uint8_t>(), sel.as<u32>(), cnt.as<u32>(), (int)E, st));
+			PGQ_TRY(cub_run(tmp, [&](void *t, size_t &tb) {
+				return hipcub::DeviceSelect::Flagged(t, tb, iota, msf.as<uint8_t>(), sel.as<u32>(), cnt.as<u32>(), (int)E, st);
+			}));
 			PGQ_HIP_TRY(hipMemcpyAsync(&n_msf, cnt.p, 4, hipMemcpyDeviceToHost, st));
 			PGQ_HIP_TRY(hipStreamSynchronize(st));
 			if ((int64_t)n_msf >= V) return fail(PGQ_ERR_HIP, "internal error: spanning forest with more than V - 1 edges");
@@ -476,7 +475,7 @@ static int wcc_compute(pgq_csr *c, Workspace *ws) {
 		// the ids (FindTreeRoot of every entry, :94-96) are read off on the device: the forest goes up as it is (1.8 MB instead
 		// of 3.6 MB of ids after a host pass over every vertex); v = V + 1: forest entry 0 -> the root of vertex 0
 		int64_t *d_ids = nullptr;
-		PGQ_TRY(dev_alloc_as(&d_ids, (size_t)vs));
+		PGQ_TRY(dev_alloc((void **)&d_ids, csr_bytes(c, c->wcc)));
 		hipError_t e0 = hook.reserve((size_t)vs * 4) == PGQ_OK ? hipSuccess : hipErrorOutOfMemory;
 		hipError_t e1 = e0 == hipSuccess ? hipMemcpyAsync(hook.p, f, (size_t)vs * 4, hipMemcpyHostToDevice, st) : e0;
 		if (e1 == hipSuccess) hipLaunchKernelGGL(k_wcc_ids, dim3(blocks_for(vs)), dim3(256), 0, st, vs, hook.as<int32_t>(), d_ids);

@@ -993,37 +993,27 @@ static int ensure_reverse_weights(pgq_csr *c, Workspace *ws) {
 	if (c->rw || c->E == 0) return PGQ_OK;
 	hipStream_t st = ws->stream;
 	const int64_t E = c->E;
-	DevBuf iota, sslot, skey, tmp, sum;
-	auto body = [&]() -> int {
-		for (DevBuf *b : { &iota, &sslot, &skey }) PGQ_TRY(b->reserve((size_t)E * 4));
-		PGQ_TRY(sum.reserve(64));
-		hipLaunchKernelGGL(k_iota32, dim3(blocks_for(E)), dim3(256), 0, st, E, iota.as<u32>());
-		int end_bit = 1;
-		while ((1LL << end_bit) < c->V) end_bit++;
-		size_t sb = 0, rb = 0;
-		const u32 *keys = reinterpret_cast<const u32 *>(c->adj);
-		PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, keys, skey.as<u32>(), iota.as<u32>(), sslot.as<u32>(), (int)E, 0, end_bit, st));
-		PGQ_HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, rb, (const int64_t *)c->w, sum.as<int64_t>(), (int)E, st));
-		PGQ_TRY(tmp.reserve(std::max(sb, rb) + 16));
-		PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, sb, keys, skey.as<u32>(), iota.as<u32>(), sslot.as<u32>(), (int)E, 0, end_bit, st));
-		void *rw = nullptr;
-		PGQ_TRY(dev_alloc(&rw, (size_t)E * 8));
-		hipLaunchKernelGGL(k_gather_weights, dim3(blocks_for(E)), dim3(256), 0, st, E, sslot.as<u32>(), (const int64_t *)c->w, (int64_t *)rw);
-		PGQ_HIP_TRY(hipcub::DeviceReduce::Sum(tmp.p, rb, (const int64_t *)c->w, sum.as<int64_t>(), (int)E, st));
-		int64_t total = 0;
-		hipError_t e1 = hipMemcpyAsync(&total, sum.p, 8, hipMemcpyDeviceToHost, st);
-		hipError_t e2 = hipStreamSynchronize(st);
-		if (e1 != hipSuccess || e2 != hipSuccess) {
-			dev_free(rw);
-			return fail(PGQ_ERR_HIP, "building the reverse weights failed");
-		}
-		c->w_mean = (double)total / (double)E;
-		c->rw = rw;
-		return PGQ_OK;
-	};
-	const int rc = body();
-	for (DevBuf *b : { &iota, &sslot, &skey, &tmp, &sum }) b->release();
-	return rc;
+	DevTemps temps(st);
+	u32 *iota = nullptr, *sslot = nullptr, *skey = nullptr;
+	int64_t *sum = nullptr;
+	void *rw = nullptr;
+	for (u32 **b : { &iota, &sslot, &skey }) PGQ_TRY(temps.alloc(b, (size_t)E));
+	PGQ_TRY(temps.alloc(&sum, 8));
+	hipLaunchKernelGGL(k_iota32, dim3(blocks_for(E)), dim3(256), 0, st, E, iota);
+	int end_bit = 1;
+	while ((1LL << end_bit) < c->V) end_bit++;
+	const u32 *keys = reinterpret_cast<const u32 *>(c->adj);
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, skey, iota, sslot, (int)E, 0, end_bit, st); }));
+	PGQ_TRY(temps.alloc_bytes(&rw, csr_bytes(c, c->rw)));
+	hipLaunchKernelGGL(k_gather_weights, dim3(blocks_for(E)), dim3(256), 0, st, E, sslot, (const int64_t *)c->w, (int64_t *)rw);
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceReduce::Sum(tmp, tb, (const int64_t *)c->w, sum, (int)E, st); }));
+	int64_t total = 0;
+	PGQ_HIP_TRY(hipMemcpyAsync(&total, sum, 8, hipMemcpyDeviceToHost, st));
+	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	c->w_mean = (double)total / (double)E;
+	temps.keep(rw);
+	c->rw = rw;
+	return PGQ_OK;
 }
 
 // a new phase (higher cap on the edge weight): every labelled vertex is expanded again over the longer prefix of its list
@@ -1054,44 +1044,31 @@ static int ensure_weight_sorted(pgq_csr *c, Workspace *ws) {
 	if (c->wadj || c->E == 0 || !c->w) return PGQ_OK;
 	hipStream_t st = ws->stream;
 	const int64_t E = c->E;
-	DevBuf tmp, mx, canon;
+	DevTemps temps(st);
 	int32_t *wadj = nullptr;
 	void *wsorted = nullptr;
-	auto body = [&]() -> int {
-		PGQ_TRY(dev_alloc_as(&wadj, (size_t)E + 4));
-		PGQ_TRY(dev_alloc(&wsorted, (size_t)E * 8));
-		PGQ_TRY(mx.reserve(64));
-		size_t sb = 0, rb = 0;
-		const unsigned long long *keys = (const unsigned long long *)c->w;
-		if (c->w_type == PGQ_W_DOUBLE) {
-			PGQ_TRY(canon.reserve((size_t)E * 8));
-			hipLaunchKernelGGL(k_weight_keys, dim3(blocks_for(E)), dim3(256), 0, st, keys, E, canon.as<unsigned long long>());
-			keys = canon.as<unsigned long long>();
-		}
-		unsigned long long *keys_out = (unsigned long long *)wsorted;
-		PGQ_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, sb, keys, keys_out, c->adj, wadj, (int)E, (int)c->V, c->off,
-		                                                        c->off + 1, 0, 64, st));
-		PGQ_HIP_TRY(hipcub::DeviceReduce::Max(nullptr, rb, keys, mx.as<unsigned long long>(), (int)E, st));
-		PGQ_TRY(tmp.reserve(std::max(sb, rb) + 16));
-		PGQ_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(tmp.p, sb, keys, keys_out, c->adj, wadj, (int)E, (int)c->V, c->off,
-		                                                        c->off + 1, 0, 64, st));
-		PGQ_HIP_TRY(hipcub::DeviceReduce::Max(tmp.p, rb, keys, mx.as<unsigned long long>(), (int)E, st));
-		unsigned long long m = 0;
-		PGQ_HIP_TRY(hipMemcpyAsync(&m, mx.p, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		c->w_max_bits = m; // the largest weight, as its bit pattern (int64: the value)
-		return PGQ_OK;
-	};
-	const int rc = body();
-	(void)hipStreamSynchronize(st);
-	tmp.release();
-	mx.release();
-	canon.release();
-	if (rc != PGQ_OK) {
-		dev_free(wadj);
-		dev_free(wsorted);
-		return rc;
+	unsigned long long *mx = nullptr;
+	PGQ_TRY(temps.alloc_bytes((void **)&wadj, csr_bytes(c, c->wadj)));
+	PGQ_TRY(temps.alloc_bytes(&wsorted, csr_bytes(c, c->wsorted)));
+	PGQ_TRY(temps.alloc(&mx, 8));
+	const unsigned long long *keys = (const unsigned long long *)c->w;
+	if (c->w_type == PGQ_W_DOUBLE) {
+		unsigned long long *canon = nullptr;
+		PGQ_TRY(temps.alloc(&canon, (size_t)E));
+		hipLaunchKernelGGL(k_weight_keys, dim3(blocks_for(E)), dim3(256), 0, st, keys, E, canon);
+		keys = canon;
 	}
+	unsigned long long *keys_out = (unsigned long long *)wsorted;
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) {
+		return hipcub::DeviceSegmentedRadixSort::SortPairs(tmp, tb, keys, keys_out, c->adj, wadj, (int)E, (int)c->V, c->off, c->off + 1, 0, 64, st);
+	}));
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceReduce::Max(tmp, tb, keys, mx, (int)E, st); }));
+	unsigned long long m = 0;
+	PGQ_HIP_TRY(hipMemcpyAsync(&m, mx, 8, hipMemcpyDeviceToHost, st));
+	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	c->w_max_bits = m; // the largest weight, as its bit pattern (int64: the value)
+	temps.keep(wadj);
+	temps.keep(wsorted);
 	c->wsorted = wsorted;
 	c->wadj = wadj;
 	return PGQ_OK;
@@ -1102,33 +1079,23 @@ static int ensure_weight_mean(pgq_csr *c, Workspace *ws) {
 	std::lock_guard<std::mutex> g(g_rw_lock);
 	if (c->w_mean > 0 || c->E == 0 || !c->w) return PGQ_OK;
 	hipStream_t st = ws->stream;
-	DevBuf tmp, sum;
-	auto body = [&]() -> int {
-		PGQ_TRY(sum.reserve(64));
-		size_t rb = 0;
-		double total = 0;
-		if (c->w_type == PGQ_W_DOUBLE) {
-			PGQ_HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, rb, (const double *)c->w, sum.as<double>(), (int)c->E, st));
-			PGQ_TRY(tmp.reserve(rb + 16));
-			PGQ_HIP_TRY(hipcub::DeviceReduce::Sum(tmp.p, rb, (const double *)c->w, sum.as<double>(), (int)c->E, st));
-			PGQ_HIP_TRY(hipMemcpyAsync(&total, sum.p, 8, hipMemcpyDeviceToHost, st));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-		} else {
-			int64_t t = 0;
-			PGQ_HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, rb, (const int64_t *)c->w, sum.as<int64_t>(), (int)c->E, st));
-			PGQ_TRY(tmp.reserve(rb + 16));
-			PGQ_HIP_TRY(hipcub::DeviceReduce::Sum(tmp.p, rb, (const int64_t *)c->w, sum.as<int64_t>(), (int)c->E, st));
-			PGQ_HIP_TRY(hipMemcpyAsync(&t, sum.p, 8, hipMemcpyDeviceToHost, st));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			total = (double)t;
-		}
-		c->w_mean = std::max(total / (double)c->E, 1e-300);
-		return PGQ_OK;
-	};
-	const int rc = body();
-	tmp.release();
-	sum.release();
-	return rc;
+	DevTemps temps(st);
+	void *sum = nullptr;
+	PGQ_TRY(temps.alloc_bytes(&sum, 64));
+	double total = 0;
+	if (c->w_type == PGQ_W_DOUBLE) {
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceReduce::Sum(tmp, tb, (const double *)c->w, (double *)sum, (int)c->E, st); }));
+		PGQ_HIP_TRY(hipMemcpyAsync(&total, sum, 8, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+	} else {
+		int64_t t = 0;
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceReduce::Sum(tmp, tb, (const int64_t *)c->w, (int64_t *)sum, (int)c->E, st); }));
+		PGQ_HIP_TRY(hipMemcpyAsync(&t, sum, 8, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		total = (double)t;
+	}
+	c->w_mean = std::max(total / (double)c->E, 1e-300);
+	return PGQ_OK;
 }
 
 // rows [0, nd) in ws->def_src / def_dst / def_idx (the chain pre-pass's open rows): answered rows get their value and
@@ -1629,30 +1596,19 @@ static int ensure_reverse_sorted(pgq_csr *c, Workspace *ws) {
 	if (c->rwadj || c->E == 0 || !c->rw) return PGQ_OK;
 	hipStream_t st = ws->stream;
 	const int64_t E = c->E;
-	DevBuf tmp;
+	DevTemps temps(st);
 	int32_t *rwadj = nullptr;
 	void *rwsorted = nullptr;
-	auto body = [&]() -> int {
-		PGQ_TRY(dev_alloc_as(&rwadj, (size_t)E + 4));
-		PGQ_TRY(dev_alloc(&rwsorted, (size_t)E * 8));
-		size_t sb = 0;
-		const unsigned long long *keys = (const unsigned long long *)c->rw; // int64 weights >= 0: the bit pattern is the value
-		PGQ_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, sb, keys, (unsigned long long *)rwsorted, c->radj, rwadj, (int)E, (int)c->V,
-		                                                        c->roff, c->roff + 1, 0, 64, st));
-		PGQ_TRY(tmp.reserve(sb + 16));
-		PGQ_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(tmp.p, sb, keys, (unsigned long long *)rwsorted, c->radj, rwadj, (int)E, (int)c->V,
-		                                                        c->roff, c->roff + 1, 0, 64, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		return PGQ_OK;
-	};
-	const int rc = body();
-	(void)hipStreamSynchronize(st);
-	tmp.release();
-	if (rc != PGQ_OK) {
-		dev_free(rwadj);
-		dev_free(rwsorted);
-		return rc;
-	}
+	PGQ_TRY(temps.alloc_bytes((void **)&rwadj, csr_bytes(c, c->rwadj)));
+	PGQ_TRY(temps.alloc_bytes(&rwsorted, csr_bytes(c, c->rwsorted)));
+	const unsigned long long *keys = (const unsigned long long *)c->rw; // int64 weights >= 0: the bit pattern is the value
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) {
+		return hipcub::DeviceSegmentedRadixSort::SortPairs(tmp, tb, keys, (unsigned long long *)rwsorted, c->radj, rwadj, (int)E, (int)c->V, c->roff,
+		                                                   c->roff + 1, 0, 64, st);
+	}));
+	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	temps.keep(rwadj);
+	temps.keep(rwsorted);
 	c->rwsorted = rwsorted;
 	c->rwadj = rwadj;
 	return PGQ_OK;

@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <atomic>
 #include <memory>
@@ -245,8 +247,10 @@ struct pgq_csr {
 	int64_t *off = nullptr;      // V+1
 	int32_t *adj = nullptr;      // E
 	int64_t *edge_ids = nullptr; // E or null (slot index is the id)
-	// PGQ_UPLOAD_LAZY_EDGE_IDS: the caller's host array, copied by ensure_edge_ids on the first call that reads edge ids
-	const int64_t *lazy_edge_ids = nullptr;
+	// PGQ_UPLOAD_LAZY_EDGE_IDS: the caller's host array, copied by ensure_edge_ids on the first call that reads edge ids.
+	// Non-null = not copied yet.  ensure_edge_ids stores `edge_ids` and then null here with release; its fast path loads
+	// this with acquire, so a caller that sees null also sees the array
+	std::atomic<const int64_t *> lazy_edge_ids { nullptr };
 	std::mutex edge_ids_lock;
 	void *w = nullptr;           // E x 8 B or null
 	// reverse CSR (in-neighbours), built on device at upload
@@ -289,7 +293,7 @@ struct pgq_csr {
 	int64_t hub_threshold = 0;
 	int64_t max_out_degree = 0, max_in_degree = 0;
 	double two_hop_mean = 0; // mean over vertices of in-degree x out-degree = expected two-hop walk of a random endpoint
-	int64_t bytes = 0;
+	std::atomic<int64_t> bytes { 0 }; // pgq_csr_device_bytes; grows when ensure_edge_ids copies a lazily uploaded array
 	bool has_negative_weight = false;
 	// multi-GPU: copies of this CSR on the other enabled devices (pgq_csr_replicate), indexed like enabled_devices();
 	// entry = this object for its own device.  Owned by the primary.
@@ -372,6 +376,62 @@ struct pgq_csr {
 
 namespace pgq {
 
+// ---- the device arrays of a handle ------------------------------------------------------------------------------------
+// Every device array a pgq_csr owns, in one table: where its pointer lives, the bytes it is allocated with (and cloned
+// with, for a replica) and when it comes to exist.  destroy_csr, clone_csr, the out-of-memory rollback of the pre-pass
+// layout and every allocation site (csr_alloc) go through it: a new array is one more row here.
+enum class CsrArrayKind {
+	base,        // uploaded, or built from edge rows
+	derived,     // built from the base arrays by every upload
+	meet_layout, // the pair-centric layout: built by every upload that has the memory for it, dropped as a whole otherwise
+	lazy,        // built by the first call that needs it, per handle; a replica builds its own
+};
+struct CsrArray {
+	void **slot;
+	size_t bytes;
+	CsrArrayKind kind;
+};
+constexpr int kCsrArrays = 29;
+inline std::array<CsrArray, kCsrArrays> csr_arrays(pgq_csr *c) {
+	typedef CsrArrayKind K;
+	const size_t V = (size_t)c->V, En = (size_t)(c->E > 0 ? c->E : 1); // (an empty graph still gets one-entry arrays)
+	const size_t adj = (En + 4) * 4;     // +4 entries: k_meet3 / k_pull_sparse read the adjacencies as aligned 16-byte groups
+	const size_t desc = (En + 1) * 16;   // one spare descriptor behind the last slot's
+	auto groups = [](int64_t g) { return (size_t)g * 16 + 16; }; // one spare 16-byte group behind the last list's
+	auto slot = [](auto &member) { return (void **)&member; };
+	return { {
+		{ slot(c->off), (V + 1) * 8, K::base },
+		{ slot(c->adj), adj, K::base },
+		{ slot(c->edge_ids), En * 8, K::base },
+		{ slot(c->w), En * 8, K::base },
+		{ slot(c->roff), (V + 1) * 8, K::derived },
+		{ slot(c->radj), adj, K::derived },
+		{ slot(c->pull_hubs), (size_t)c->n_pull_hub_items * sizeof(HubItem), K::derived },
+		{ slot(c->pull_hub_vertices), (size_t)c->n_pull_hub_vertices * 4, K::derived },
+		{ slot(c->pull_parts), (V > 1 ? V : 1) * 8, K::derived }, // room for a part per vertex; n_pull_parts are filled
+		{ slot(c->rown), En + 8, K::derived },                    // +8: read as aligned 4-byte groups
+		{ slot(c->rpk), (En + 2048) * 4, K::derived },            // +2048: padded for the 4 x 64-entry trips of k_pull_lanes
+		{ slot(c->padj), groups(c->padj_groups), K::meet_layout },
+		{ slot(c->rpadj), groups(c->rpadj_groups), K::meet_layout },
+		{ slot(c->ppadj), groups(c->ppadj_groups), K::meet_layout },
+		{ slot(c->prpadj), groups(c->prpadj_groups), K::meet_layout },
+		{ slot(c->fseg), V * 8, K::meet_layout },
+		{ slot(c->rseg), V * 8, K::meet_layout },
+		{ slot(c->fdesc), desc, K::meet_layout },
+		{ slot(c->rdesc), desc, K::meet_layout },
+		{ slot(c->fwork), V * 4, K::meet_layout },
+		{ slot(c->rwork), V * 4, K::meet_layout },
+		{ slot(c->rhead), V * 256, K::meet_layout },
+		{ slot(c->rw), En * 8, K::lazy },
+		{ slot(c->wadj), adj, K::lazy },
+		{ slot(c->wsorted), En * 8, K::lazy },
+		{ slot(c->rwadj), adj, K::lazy },
+		{ slot(c->rwsorted), En * 8, K::lazy },
+		{ slot(c->wcc), (V + 2) * 8, K::lazy },
+		{ slot(c->pagerank), (V + 2) * 8, K::lazy }, // (pagerank_compute hands over a DevBuf: at least this large)
+	} };
+}
+
 struct OptionScope {
 	Options *saved;
 	explicit OptionScope(const pgq_csr *c) : saved(options_override()) {
@@ -415,12 +475,6 @@ int dev_alloc(void **out, size_t bytes);
 void dev_free(void *p);
 void dev_cache_trim();
 void drop_idle_workspaces(); // frees the pooled (not leased) per-call workspaces (pgq_runtime.hip)
-template <typename T> inline int dev_alloc_as(T **out, size_t count) {
-	void *p = nullptr;
-	int rc = dev_alloc(&p, count * sizeof(T));
-	*out = static_cast<T *>(p);
-	return rc;
-}
 
 // device -> pageable host memory through a pinned block (a pageable hipMemcpy D2H is staged by the runtime at well under
 // 1 GB/s on these boxes); waits for `st`
@@ -433,5 +487,63 @@ struct DevBuf {
 	void release();
 	template <typename T> T *as() { return static_cast<T *>(p); }
 };
+
+// the size of the array of `c` whose pointer member is `member`, from csr_arrays, and its allocation at that size
+template <typename T> inline size_t csr_bytes(pgq_csr *c, T *&member) {
+	for (const CsrArray &a : csr_arrays(c))
+		if (a.slot == (void **)&member) return a.bytes;
+	fprintf(stderr, "[pgq] internal error: a device array of pgq_csr is missing from csr_arrays\n");
+	abort();
+}
+template <typename T> inline int csr_alloc(pgq_csr *c, T *&member) { return dev_alloc((void **)&member, csr_bytes(c, member)); }
+
+// The temporaries of one build step on one stream, taken from the block cache.  They go back when the scope ends, on
+// every path, and only after the stream has drained: an error return may leave a kernel or a sort using them.
+class DevTemps {
+	hipStream_t st;
+	std::vector<void *> blocks;
+
+public:
+	explicit DevTemps(hipStream_t stream) : st(stream) {}
+	DevTemps(const DevTemps &) = delete;
+	DevTemps &operator=(const DevTemps &) = delete;
+	~DevTemps() { free_now(); }
+	int alloc_bytes(void **out, size_t bytes) {
+		PGQ_TRY(dev_alloc(out, bytes));
+		blocks.push_back(*out);
+		return PGQ_OK;
+	}
+	template <typename T> int alloc(T **out, size_t count) { return alloc_bytes((void **)out, count * sizeof(T)); }
+	void keep(void *p) { // an output the caller owns from here on
+		for (void *&b : blocks)
+			if (b == p) b = nullptr;
+	}
+	void free_now() {
+		if (blocks.empty()) return;
+		(void)hipStreamSynchronize(st);
+		for (void *b : blocks) dev_free(b);
+		blocks.clear();
+	}
+};
+
+// hipcub's two-phase call: `call(tmp, bytes)` is run with tmp = nullptr to learn the temporary's size, then again on a
+// temporary of that size (+ 16) drawn from `from`: a DevTemps scope, or a workspace DevBuf that the search paths reuse
+// from call to call.
+inline int cub_temp(DevTemps &from, void **tmp, size_t bytes) { return from.alloc_bytes(tmp, bytes); }
+inline int cub_temp(DevBuf &from, void **tmp, size_t bytes) {
+	PGQ_TRY(from.reserve(bytes));
+	*tmp = from.p;
+	return PGQ_OK;
+}
+template <typename From, typename Call> inline int cub_run(From &from, Call &&call) {
+	size_t bytes = 0;
+	void *tmp = nullptr;
+	for (int phase = 0; phase < 2; phase++) {
+		const hipError_t e = call(tmp, bytes);
+		if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGQ_ERR_OOM : PGQ_ERR_HIP, std::string("hipcub call: ") + hipGetErrorString(e));
+		if (phase == 0) PGQ_TRY(cub_temp(from, &tmp, bytes + 16));
+	}
+	return PGQ_OK;
+}
 
 } // namespace pgq

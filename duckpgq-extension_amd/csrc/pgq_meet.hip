@@ -2087,10 +2087,8 @@ private:
 		int64_t *cnt = ws->meet_poff.as<int64_t>() + (n + 1), *poff = ws->meet_poff.as<int64_t>();
 		hipLaunchKernelGGL(k_path_counts, dim3(blocks_for(n)), dim3(256), 0, st, n, a.d_out, cnt);
 		PGQ_HIP_TRY(hipMemsetAsync(cnt + n, 0, 8, st));
-		size_t tmp = 0;
-		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cnt, poff, (int)(n + 1), st));
-		PGQ_TRY(ws->scan_tmp.reserve(tmp + 16)); // (the one buffer sized here: the scan names its own scratch)
-		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp, cnt, poff, (int)(n + 1), st));
+		// (scan_tmp is the one buffer sized here: the scan names its own scratch)
+		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, poff, (int)(n + 1), st); }));
 		PGQ_HIP_TRY(hipMemcpyAsync(&ws->h_meet->paths_total, poff + n, 8, hipMemcpyDeviceToHost, st));
 		KernelTimer kt(st, K_RECON);
 		hipLaunchKernelGGL(k_emit_paths, dim3((unsigned)n), dim3(256), 0, st, n, a.d_src, a.d_dst, a.d_out, rec, poff, c->off, c->adj,

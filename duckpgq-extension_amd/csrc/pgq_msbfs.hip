@@ -1606,10 +1606,9 @@ static int lane_ranks(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src
 	KernelTimer kt(st, K_PREP);
 	hipLaunchKernelGGL(k_prep_zero, dim3(blocks_for(V + 1)), dim3(256), 0, st, ws->flag.as<u32>(), V + 1, ws->counters.as<u32>(), (int)(sizeof(Counters) / 4));
 	hipLaunchKernelGGL(k_mark_sources, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->flag.as<u32>(), V, c->off, c->roff, dst_rule ? 1 : 0, d_bad, sm);
-	size_t tmp = 0;
-	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, ws->flag.as<u32>(), ws->rank.as<u32>(), (int)(V + 1), st));
-	PGQ_TRY(ws->scan_tmp.reserve(tmp + 16));
-	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp, ws->flag.as<u32>(), ws->rank.as<u32>(), (int)(V + 1), st));
+	PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) {
+		return hipcub::DeviceScan::ExclusiveSum(tmp, tb, ws->flag.as<u32>(), ws->rank.as<u32>(), (int)(V + 1), st);
+	}));
 	// the count and the range-check flag land in two words of the pinned counter block
 	u32 *h2 = reinterpret_cast<u32 *>(ws->h_cnt);
 	h2[0] = h2[1] = 0;
@@ -1647,10 +1646,9 @@ static int lane_rows_sorted(pgq_csr *c, Workspace *ws, int64_t n, const int64_t 
 	KernelTimer kt(st, K_PREP);
 	hipLaunchKernelGGL(k_pair_keys, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->rank.as<u32>(), c->off, c->roff, dst_rule ? 1 : 0, c->V,
 	                   key_trivial, key_nolane, ws->key.as<u32>(), ws->idx.as<u32>());
-	size_t stmp = 0;
-	PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, stmp, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st));
-	PGQ_TRY(ws->sort_tmp.reserve(stmp + 16));
-	PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ws->sort_tmp.p, stmp, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st));
+	PGQ_TRY(cub_run(ws->sort_tmp, [&](void *tmp, size_t &tb) {
+		return hipcub::DeviceRadixSort::SortPairs(tmp, tb, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st);
+	}));
 	hipLaunchKernelGGL(k_gather_sorted, dim3(blocks_for(n)), dim3(256), 0, st, n, ws->skey.as<u32>(), ws->sidx.as<u32>(), d_src, d_dst, key_trivial, key_nolane,
 	                   ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), ws->sres.as<int32_t>());
 	kt.stop();

@@ -352,10 +352,9 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 		{
 			KernelTimer kt(st, K_PREP);
 			hipLaunchKernelGGL(k_sort_keys, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, V, ws->key.as<u32>(), ws->idx.as<u32>());
-			size_t stmp = 0;
-			PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, stmp, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st));
-			PGQ_TRY(ws->sort_tmp.reserve(stmp + 16));
-			PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ws->sort_tmp.p, stmp, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st));
+			PGQ_TRY(cub_run(ws->sort_tmp, [&](void *tmp, size_t &tb) {
+				return hipcub::DeviceRadixSort::SortPairs(tmp, tb, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st);
+			}));
 			hipLaunchKernelGGL(k_sort_gather, dim3(blocks_for(n)), dim3(256), 0, st, n, ws->sidx.as<u32>(), d_src, d_dst, ws->sort_src.as<int64_t>(),
 			                   ws->sort_dst.as<int64_t>());
 			kt.stop();

@@ -1292,43 +1292,30 @@ __global__ __launch_bounds__(256) void k_fill_packed(int64_t V, const int64_t *_
 		packed[g] = make_uint4(w[0], w[1], w[2], w[3]);
 	}
 }
-// Builds one direction's packed copy and leaves every vertex's first packed group in *d_gb (V + 1 entries, the caller
-// frees it).  Returns PGQ_OK with *packed == nullptr when the group indices would not fit 32 bits.
+// Builds one direction's packed copy and leaves every vertex's first packed group in *d_gb (V + 1 entries, a temporary
+// of the caller's scope `outer`).  Returns PGQ_OK with *packed == nullptr when the group indices would not fit 32 bits.
 static int build_packed_dir(pgq_csr *c, const int64_t *off, const int32_t *adj, int K, int32_t **packed, u32 **d_gb,
-                            int64_t *groups_out, hipStream_t st) {
+                            int64_t *groups_out, DevTemps &outer, hipStream_t st) {
 	const int64_t V = c->V, E = c->E;
 	const u32 align = (u32)std::max(1, options().meet_pack_align);
 	*packed = nullptr;
 	if ((double)E / K + (double)V * align >= 4.0e9) return PGQ_OK;
 	u32 *d_ng = nullptr;
-	void *d_tmp = nullptr;
-	struct Temps {
-		u32 *&a;
-		void *&t;
-		hipStream_t st;
-		~Temps() {
-			(void)hipStreamSynchronize(st);
-			dev_free(a);
-			dev_free(t);
-		}
-	} temps { d_ng, d_tmp, st };
-	PGQ_TRY(dev_alloc_as(&d_ng, (size_t)V + 1));
-	PGQ_TRY(dev_alloc_as(d_gb, (size_t)V + 1));
+	DevTemps temps(st);
+	PGQ_TRY(temps.alloc(&d_ng, (size_t)V + 1));
+	PGQ_TRY(outer.alloc(d_gb, (size_t)V + 1));
 	PGQ_HIP_TRY(hipMemsetAsync(d_ng + V, 0, sizeof(u32), st));
 	hipLaunchKernelGGL(k_pack_groups, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, K, align, d_ng);
-	size_t sb = 0;
-	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_ng, *d_gb, (int)(V + 1), st));
-	PGQ_TRY(dev_alloc(&d_tmp, sb + 16));
-	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, sb, d_ng, *d_gb, (int)(V + 1), st));
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, d_ng, *d_gb, (int)(V + 1), st); }));
 	u32 total = 0;
 	PGQ_HIP_TRY(hipMemcpyAsync(&total, *d_gb + V, sizeof(u32), hipMemcpyDeviceToHost, st));
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
-	PGQ_TRY(dev_alloc_as(packed, (size_t)total * 4 + 4));
+	*groups_out = (int64_t)total; // (csr_arrays sizes the packed copy from it)
+	PGQ_TRY(csr_alloc(c, *packed));
 	const dim3 grid((unsigned)((V + 255) / 256));
 	uint4 *dst = reinterpret_cast<uint4 *>(*packed);
 	if (K == 6) hipLaunchKernelGGL(k_fill_packed<6>, grid, dim3(256), 0, st, V, off, adj, *d_gb, dst);
 	else hipLaunchKernelGGL(k_fill_packed<5>, grid, dim3(256), 0, st, V, off, adj, *d_gb, dst);
-	*groups_out = (int64_t)total;
 	return PGQ_OK;
 }
 
@@ -1382,38 +1369,24 @@ static int build_meet_layout_dir(pgq_csr *c, const int64_t *off, const int32_t *
 	// group indices are 32-bit: E / 4 + V x align / 4 bounds the padded size; one group per list start always fits
 	if ((double)E / 4.0 + (double)V * (align / 4.0) >= 4.0e9) align = 4;
 	u32 *d_ng = nullptr, *d_gb = nullptr;
-	void *d_tmp = nullptr;
-	struct Temps {
-		u32 *&a, *&b;
-		void *&t;
-		hipStream_t st;
-		~Temps() {
-			(void)hipStreamSynchronize(st); // the kernels below may still read them on an error return
-			dev_free(a);
-			dev_free(b);
-			dev_free(t);
-		}
-	} temps { d_ng, d_gb, d_tmp, st };
-	PGQ_TRY(dev_alloc_as(&d_ng, (size_t)V + 1));
-	PGQ_TRY(dev_alloc_as(&d_gb, (size_t)V + 1));
+	DevTemps temps(st);
+	PGQ_TRY(temps.alloc(&d_ng, (size_t)V + 1));
+	PGQ_TRY(temps.alloc(&d_gb, (size_t)V + 1));
 	PGQ_HIP_TRY(hipMemsetAsync(d_ng + V, 0, sizeof(u32), st));
 	hipLaunchKernelGGL(k_seg_groups, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, align, d_ng);
-	size_t sb = 0;
-	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_ng, d_gb, (int)(V + 1), st));
-	PGQ_TRY(dev_alloc(&d_tmp, sb + 16));
-	PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, sb, d_ng, d_gb, (int)(V + 1), st));
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, d_ng, d_gb, (int)(V + 1), st); }));
 	u32 total = 0;
 	PGQ_HIP_TRY(hipMemcpyAsync(&total, d_gb + V, sizeof(u32), hipMemcpyDeviceToHost, st));
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
-	PGQ_TRY(dev_alloc_as(seg, (size_t)V));
-	PGQ_TRY(dev_alloc_as(padj, (size_t)total * 4 + 4));
-	PGQ_TRY(dev_alloc_as(desc, (size_t)E + 1));
+	*groups_out = (int64_t)total; // (csr_arrays sizes the padded adjacency from it)
+	PGQ_TRY(csr_alloc(c, *seg));
+	PGQ_TRY(csr_alloc(c, *padj));
+	PGQ_TRY(csr_alloc(c, *desc));
 	hipLaunchKernelGGL(k_seg_fill, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, d_gb, *seg);
 	hipLaunchKernelGGL(k_fill_padded, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, adj, *seg, total, *padj);
 	hipLaunchKernelGGL(k_fill_desc, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, E, adj, *seg, pgroups, *desc);
-	PGQ_TRY(dev_alloc_as(work, (size_t)V));
+	PGQ_TRY(csr_alloc(c, *work));
 	hipLaunchKernelGGL(k_two_hop_work, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, off, adj, *seg, *work);
-	*groups_out = (int64_t)total;
 	return PGQ_OK;
 }
 // rhead (pgq_internal.h): 64 words per vertex = two 128-byte lines.  Word 31 — the last of the FIRST line — is the in-degree;
@@ -1447,19 +1420,11 @@ static int build_meet_layout(pgq_csr *c, hipStream_t st) {
 	// the packed copies first: the slot descriptors carry their first groups.  Both directions or neither
 	const int K = options().meet_pack ? pack_k_for(c->V, options().meet_pack >= 2) : 4;
 	u32 *fpg = nullptr, *rpg = nullptr;
-	struct Temps {
-		u32 *&a, *&b;
-		hipStream_t st;
-		~Temps() {
-			(void)hipStreamSynchronize(st);
-			dev_free(a);
-			dev_free(b);
-		}
-	} temps { fpg, rpg, st };
+	DevTemps temps(st);
 	c->pack_k = 4;
 	if (K > 4) {
-		PGQ_TRY(build_packed_dir(c, c->off, c->adj, K, &c->ppadj, &fpg, &c->ppadj_groups, st));
-		if (c->ppadj) PGQ_TRY(build_packed_dir(c, c->roff, c->radj, K, &c->prpadj, &rpg, &c->prpadj_groups, st));
+		PGQ_TRY(build_packed_dir(c, c->off, c->adj, K, &c->ppadj, &fpg, &c->ppadj_groups, temps, st));
+		if (c->ppadj) PGQ_TRY(build_packed_dir(c, c->roff, c->radj, K, &c->prpadj, &rpg, &c->prpadj_groups, temps, st));
 		if (c->ppadj && c->prpadj) {
 			c->pack_k = K;
 		} else {
@@ -1473,7 +1438,7 @@ static int build_meet_layout(pgq_csr *c, hipStream_t st) {
 	PGQ_TRY(build_meet_layout_dir(c, c->off, c->adj, &c->padj, &c->fseg, &c->fdesc, &c->fwork, &c->padj_groups, packed ? fpg : nullptr, st));
 	PGQ_TRY(build_meet_layout_dir(c, c->roff, c->radj, &c->rpadj, &c->rseg, &c->rdesc, &c->rwork, &c->rpadj_groups, packed ? rpg : nullptr, st));
 	if (options().ball && (size_t)c->V * 256 <= ((size_t)std::max(0, options().ball_head_mb) << 20)) {
-		if (dev_alloc_as(&c->rhead, (size_t)c->V * 16) == PGQ_OK) // (no memory for it: the kernel gathers the list positions instead)
+		if (csr_alloc(c, c->rhead) == PGQ_OK) // (no memory for it: the kernel gathers the list positions instead)
 			hipLaunchKernelGGL(k_fill_rhead, dim3((unsigned)((c->V * 16 + 255) / 256)), dim3(256), 0, st, c->V, c->rseg, c->rpadj, c->rhead);
 		else
 			c->rhead = nullptr;
@@ -1488,29 +1453,15 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 	UploadTrace tr;
 	int *d_flag = nullptr;
 	u32 *d_slot_src = nullptr, *d_skey = nullptr;
-	void *d_tmp = nullptr;
-	struct Temps {
-		int *&flag;
-		u32 *&a, *&b;
-		void *&t;
-		hipStream_t st;
-		~Temps() {
-			(void)hipStreamSynchronize(st); // an error return may leave a sort writing them: not back to the cache before it is done
-			dev_free(flag);
-			dev_free(a);
-			dev_free(b);
-			dev_free(t);
-		}
-	} temps { d_flag, d_slot_src, d_skey, d_tmp, st };
-	PGQ_TRY(dev_alloc_as(&d_flag, 2));
+	DevTemps temps(st);
+	PGQ_TRY(temps.alloc(&d_flag, 2));
 	PGQ_HIP_TRY(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), st));
 	if (V > 0) {
 		hipLaunchKernelGGL(k_check_offsets, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, c->off, V, d_flag);
 	}
-	// +4 entries: k_meet3 / k_pull_sparse read the adjacencies as aligned 16-byte groups
-	if (!c->adj) PGQ_TRY(dev_alloc_as(&c->adj, En + 4));
-	PGQ_TRY(dev_alloc_as(&c->radj, En + 4));
-	PGQ_TRY(dev_alloc_as(&c->roff, (size_t)V + 1));
+	if (!c->adj) PGQ_TRY(csr_alloc(c, c->adj));
+	PGQ_TRY(csr_alloc(c, c->radj));
+	PGQ_TRY(csr_alloc(c, c->roff));
 	if (E > 0 && d_adj64) hipLaunchKernelGGL(k_narrow_adj, dim3(grid_for(E)), dim3(256), 0, st, d_adj64, c->adj, E, V, d_flag);
 	{ // the kernels below index by offsets and adjacency values: stop here if either is malformed
 		int h_bad = 0;
@@ -1520,17 +1471,16 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 	}
 	tr.mark("allocs + narrow");
 	if (E > 0) {
-		PGQ_TRY(dev_alloc_as(&d_slot_src, En));
-		PGQ_TRY(dev_alloc_as(&d_skey, En));
+		PGQ_TRY(temps.alloc(&d_slot_src, En));
+		PGQ_TRY(temps.alloc(&d_skey, En));
 		hipLaunchKernelGGL(k_slot_sources, dim3(grid_for(V, 256, 256 * 8)), dim3(256), 0, st, V, c->off, d_slot_src);
 		int end_bit = 1;
 		while ((1LL << end_bit) < V) end_bit++;
-		size_t sb = 0;
 		const u32 *keys = reinterpret_cast<const u32 *>(c->adj); // range-checked: every key is in [0,V)
 		u32 *vals = reinterpret_cast<u32 *>(c->radj);
-		PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, keys, d_skey, d_slot_src, vals, (int)E, 0, end_bit, st));
-		PGQ_TRY(dev_alloc(&d_tmp, sb + 16));
-		PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sb, keys, d_skey, d_slot_src, vals, (int)E, 0, end_bit, st));
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) {
+			return hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, d_skey, d_slot_src, vals, (int)E, 0, end_bit, st);
+		}));
 		hipLaunchKernelGGL(k_row_bounds, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, d_skey, E, V, c->roff);
 	} else {
 		PGQ_HIP_TRY(hipMemsetAsync(c->roff, 0, (size_t)(V + 1) * sizeof(int64_t), st));
@@ -1552,31 +1502,16 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 	UploadStats *d_us = nullptr;
 	HubRow *d_hub_rows = nullptr;
 	int *d_run = nullptr; // [0,n_runs] counts, [n_runs+1, 2 n_runs+1] bases
-	void *d_scan = nullptr;
-	struct Temps2 {
-		UploadStats *&a;
-		HubRow *&b;
-		int *&c;
-		void *&d;
-		hipStream_t st;
-		~Temps2() {
-			(void)hipStreamSynchronize(st);
-			dev_free(a);
-			dev_free(b);
-			dev_free(c);
-			dev_free(d);
-		}
-	} temps2 { d_us, d_hub_rows, d_run, d_scan, st };
-	PGQ_TRY(dev_alloc_as(&d_us, 1));
-	PGQ_TRY(dev_alloc_as(&d_hub_rows, (size_t)hub_cap));
-	PGQ_TRY(dev_alloc_as(&d_run, (size_t)(2 * n_runs + 2)));
-	PGQ_TRY(dev_alloc_as(&c->pull_parts, (size_t)std::max<int64_t>(2 * V, 2)));
-	PGQ_TRY(dev_alloc((void **)&c->rown, En + 8)); // read as aligned 4-byte groups
+	PGQ_TRY(temps.alloc(&d_us, 1));
+	PGQ_TRY(temps.alloc(&d_hub_rows, (size_t)hub_cap));
+	PGQ_TRY(temps.alloc(&d_run, (size_t)(2 * n_runs + 2)));
+	PGQ_TRY(csr_alloc(c, c->pull_parts));
+	PGQ_TRY(csr_alloc(c, c->rown));
 	PGQ_HIP_TRY(hipMemsetAsync(d_us, 0, sizeof(UploadStats), st));
-	PGQ_HIP_TRY(hipMemsetAsync(c->rown, 0, En + 8, st));
-	if (V < (1ll << 28)) { // in-slots of hubs keep 0 (never read); padded for the 4 x 64-entry trips of k_pull_lanes
-		PGQ_TRY(dev_alloc_as(&c->rpk, En + 2048));
-		PGQ_HIP_TRY(hipMemsetAsync(c->rpk, 0, (En + 2048) * sizeof(uint32_t), st));
+	PGQ_HIP_TRY(hipMemsetAsync(c->rown, 0, csr_bytes(c, c->rown), st));
+	if (V < (1ll << 28)) { // in-slots of hubs keep 0 (never read)
+		PGQ_TRY(csr_alloc(c, c->rpk));
+		PGQ_HIP_TRY(hipMemsetAsync(c->rpk, 0, csr_bytes(c, c->rpk), st));
 	}
 	if (V > 0) {
 		const int64_t wmax = std::max(64, options().part_weight);
@@ -1584,10 +1519,7 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 		                   d_us, d_hub_rows);
 		hipLaunchKernelGGL(k_make_parts<false>, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, st, V, c->roff, chunk,
 		                   wmax, d_run, (const int *)nullptr, (int32_t *)nullptr, d_us);
-		size_t sb = 0;
-		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_run, d_run + n_runs + 1, (int)n_runs, st));
-		PGQ_TRY(dev_alloc(&d_scan, sb + 16));
-		PGQ_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan, sb, d_run, d_run + n_runs + 1, (int)n_runs, st));
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, d_run, d_run + n_runs + 1, (int)n_runs, st); }));
 		hipLaunchKernelGGL(k_make_parts<true>, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, st, V, c->roff, chunk, wmax,
 		                   d_run, d_run + n_runs + 1, c->pull_parts, d_us);
 	}
@@ -1624,9 +1556,9 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 		c->n_pull_hub_items = (int64_t)items.size();
 		c->n_pull_hub_vertices = (int64_t)hubs.size();
 		n_items = (int64_t)items.size();
-		PGQ_TRY(dev_alloc((void **)&c->pull_hubs, items.size() * sizeof(HubItem)));
+		PGQ_TRY(csr_alloc(c, c->pull_hubs));
 		PGQ_HIP_TRY(hipMemcpyAsync(c->pull_hubs, items.data(), items.size() * sizeof(HubItem), hipMemcpyHostToDevice, st));
-		PGQ_TRY(dev_alloc((void **)&c->pull_hub_vertices, hubs.size() * sizeof(int32_t)));
+		PGQ_TRY(csr_alloc(c, c->pull_hub_vertices));
 		PGQ_HIP_TRY(hipMemcpyAsync(c->pull_hub_vertices, hubs.data(), hubs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
 		PGQ_HIP_TRY(hipStreamSynchronize(st)); // the host vectors go out of scope
 	}
@@ -1640,12 +1572,11 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 		if (lrc != PGQ_ERR_OOM) return lrc;
 		(void)hipGetLastError();
 		if (options().trace) fprintf(stderr, "[pgq] upload: no memory for the pair-centric layout (~40 B per edge): this CSR is searched without the pre-pass\n");
-		for (void **q : { (void **)&c->padj, (void **)&c->rpadj, (void **)&c->fseg, (void **)&c->rseg, (void **)&c->fdesc,
-		                  (void **)&c->rdesc, (void **)&c->fwork, (void **)&c->rwork, (void **)&c->rhead, (void **)&c->ppadj,
-		                  (void **)&c->prpadj }) {
-			dev_free(*q);
-			*q = nullptr;
-		}
+		for (const CsrArray &a : csr_arrays(c))
+			if (a.kind == CsrArrayKind::meet_layout) {
+				dev_free(*a.slot);
+				*a.slot = nullptr;
+			}
 		c->padj_groups = c->rpadj_groups = 0;
 		c->ppadj_groups = c->prpadj_groups = 0;
 		c->pack_k = 4;
@@ -1716,54 +1647,27 @@ static void destroy_csr(pgq_csr *c) {
 		for (pgq_csr *r : c->retired)
 			if (r && r != c) destroy_csr(r);
 	}
-	dev_free(c->off);
-	dev_free(c->adj);
-	dev_free(c->edge_ids);
-	dev_free(c->w);
-	dev_free(c->roff);
-	dev_free(c->radj);
-	dev_free(c->pull_hubs);
-	dev_free(c->pull_hub_vertices);
-	dev_free(c->pull_parts);
-	dev_free(c->rown);
-	dev_free(c->rpk);
-	dev_free(c->padj);
-	dev_free(c->rpadj);
-	dev_free(c->ppadj);
-	dev_free(c->prpadj);
-	dev_free(c->fseg);
-	dev_free(c->rseg);
-	dev_free(c->rhead);
-	dev_free(c->fwork);
-	dev_free(c->rwork);
-	dev_free(c->fdesc);
-	dev_free(c->rdesc);
-	dev_free(c->pagerank);
-	dev_free(c->wcc);
-	dev_free(c->rw);
-	dev_free(c->wadj);
-	dev_free(c->wsorted);
-	dev_free(c->rwadj);
-	dev_free(c->rwsorted);
+	for (const CsrArray &a : csr_arrays(c)) dev_free(*a.slot);
 	delete c;
 }
 
 static int staged_upload(void *d_dst, const void *h_src, size_t n_elems, size_t elem_bytes, int mode, int64_t V, std::atomic<int> *bad);
 int ensure_edge_ids(pgq_csr *c) {
-	if (!c || !c->lazy_edge_ids) return PGQ_OK; // (written once under the lock below, read racily here: a stale non-null only costs the lock)
+	if (!c || !c->lazy_edge_ids.load(std::memory_order_acquire)) return PGQ_OK; // null: c->edge_ids is there (or there are no ids)
 	std::lock_guard<std::mutex> g(c->edge_ids_lock);
-	if (!c->lazy_edge_ids) return PGQ_OK;
+	const int64_t *host = c->lazy_edge_ids.load(std::memory_order_relaxed); // (only written under this lock)
+	if (!host) return PGQ_OK;
 	int64_t *d = nullptr;
-	PGQ_TRY(dev_alloc((void **)&d, (size_t)c->E * sizeof(int64_t)));
+	PGQ_TRY(dev_alloc((void **)&d, csr_bytes(c, c->edge_ids)));
 	std::atomic<int> oob { 0 };
-	const int rc = staged_upload(d, c->lazy_edge_ids, (size_t)c->E, 8, 0, c->V, &oob);
+	const int rc = staged_upload(d, host, (size_t)c->E, 8, 0, c->V, &oob);
 	if (rc != PGQ_OK) {
 		dev_free(d);
 		return rc;
 	}
 	c->edge_ids = d;
-	c->bytes += c->E * 8;
-	c->lazy_edge_ids = nullptr;
+	c->bytes.fetch_add(c->E * 8, std::memory_order_relaxed);
+	c->lazy_edge_ids.store(nullptr, std::memory_order_release);
 	return PGQ_OK;
 }
 
@@ -1793,7 +1697,7 @@ static int upload_impl(int64_t V, const int64_t *offsets, const int64_t *adj, co
 	int64_t *d_adj64 = nullptr;
 	auto body = [&]() -> int {
 		PGQ_TRY(g_streams.get(&st));
-		PGQ_TRY(dev_alloc((void **)&c->off, (size_t)(V + 1) * sizeof(int64_t)));
+		PGQ_TRY(csr_alloc(c, c->off));
 		if (on_device) {
 			PGQ_HIP_TRY(hipMemcpyAsync(c->off, offsets, (size_t)(V + 1) * sizeof(int64_t), kind, st));
 		} else { // pageable: through the pinned blocks like the other arrays (a plain hipMemcpy of 3.6 MB of pageable memory took ~2 ms)
@@ -1803,11 +1707,11 @@ static int upload_impl(int64_t V, const int64_t *offsets, const int64_t *adj, co
 		if (E > 0 && on_device) {
 			d_adj64 = const_cast<int64_t *>(adj);
 			if (edge_ids) {
-				PGQ_TRY(dev_alloc((void **)&c->edge_ids, (size_t)E * sizeof(int64_t)));
+				PGQ_TRY(csr_alloc(c, c->edge_ids));
 				PGQ_HIP_TRY(hipMemcpyAsync(c->edge_ids, edge_ids, (size_t)E * sizeof(int64_t), kind, st));
 			}
 			if (w_type != PGQ_W_NONE) {
-				PGQ_TRY(dev_alloc((void **)&c->w, (size_t)E * 8));
+				PGQ_TRY(csr_alloc(c, c->w));
 				PGQ_HIP_TRY(hipMemcpyAsync(c->w, w, (size_t)E * 8, kind, st));
 			}
 		} else if (E > 0) {
@@ -1815,7 +1719,7 @@ static int upload_impl(int64_t V, const int64_t *offsets, const int64_t *adj, co
 			std::atomic<int> oob { 0 };
 			UploadTrace tr;
 			if (options().upload_narrow_host) { // half the PCIe bytes, but the staging threads do the narrowing
-				PGQ_TRY(dev_alloc((void **)&c->adj, (size_t)(E + 4) * sizeof(int32_t))); // +4: k_meet3 reads aligned 16-byte groups
+				PGQ_TRY(csr_alloc(c, c->adj));
 				PGQ_TRY(staged_upload(c->adj, adj, (size_t)E, 8, 1, V, &oob));
 				if (oob.load()) return fail(PGQ_ERR_INVALID_ARG, "CSR is malformed: adjacency out of [0,V)");
 			} else { // raw int64 over PCIe, narrowed and range-checked by k_narrow_adj
@@ -1826,12 +1730,12 @@ static int upload_impl(int64_t V, const int64_t *offsets, const int64_t *adj, co
 			if (edge_ids && lazy_ids) {
 				c->lazy_edge_ids = edge_ids; // copied by ensure_edge_ids when a call reads edge ids
 			} else if (edge_ids) {
-				PGQ_TRY(dev_alloc((void **)&c->edge_ids, (size_t)E * sizeof(int64_t)));
+				PGQ_TRY(csr_alloc(c, c->edge_ids));
 				PGQ_TRY(staged_upload(c->edge_ids, edge_ids, (size_t)E, 8, 0, V, &oob));
 				tr.mark("edge ids staged");
 			}
 			if (w_type != PGQ_W_NONE) {
-				PGQ_TRY(dev_alloc((void **)&c->w, (size_t)E * 8));
+				PGQ_TRY(csr_alloc(c, c->w));
 				PGQ_TRY(staged_upload(c->w, w, (size_t)E, 8, 0, V, &oob));
 			}
 		}
@@ -1911,21 +1815,21 @@ int pgq_csr_build_device(int64_t V, int64_t n_rows, const int64_t *d_src, const 
 	c->E = E;
 	c->w_type = w_type;
 	hipStream_t st = nullptr;
-	u32 *d_key = nullptr, *d_idx = nullptr, *d_skey = nullptr, *d_order = nullptr;
-	int *d_bad = nullptr;
-	void *d_tmp = nullptr;
 	auto body = [&]() -> int {
 		PGQ_TRY(g_streams.get(&st));
 		const size_t En = (size_t)std::max<int64_t>(E, 1);
-		PGQ_TRY(dev_alloc_as(&d_key, En));
-		PGQ_TRY(dev_alloc_as(&d_idx, En));
-		PGQ_TRY(dev_alloc_as(&d_skey, En));
-		PGQ_TRY(dev_alloc_as(&d_order, En));
-		PGQ_TRY(dev_alloc_as(&d_bad, 1));
-		PGQ_TRY(dev_alloc_as(&c->off, (size_t)V + 1));
-		PGQ_TRY(dev_alloc_as(&c->adj, En + 4));
-		PGQ_TRY(dev_alloc_as(&c->edge_ids, En));
-		if (w_type != PGQ_W_NONE) PGQ_TRY(dev_alloc(&c->w, En * 8));
+		u32 *d_key = nullptr, *d_idx = nullptr, *d_skey = nullptr, *d_order = nullptr;
+		int *d_bad = nullptr;
+		DevTemps temps(st);
+		PGQ_TRY(temps.alloc(&d_key, En));
+		PGQ_TRY(temps.alloc(&d_idx, En));
+		PGQ_TRY(temps.alloc(&d_skey, En));
+		PGQ_TRY(temps.alloc(&d_order, En));
+		PGQ_TRY(temps.alloc(&d_bad, 1));
+		PGQ_TRY(csr_alloc(c, c->off));
+		PGQ_TRY(csr_alloc(c, c->adj));
+		PGQ_TRY(csr_alloc(c, c->edge_ids));
+		if (w_type != PGQ_W_NONE) PGQ_TRY(csr_alloc(c, c->w));
 		PGQ_HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
 		if (E > 0) {
 			hipLaunchKernelGGL(k_check_rows, dim3(grid_for(E)), dim3(256), 0, st, d_src, d_dst, E, V, d_key, d_idx, d_bad);
@@ -1933,15 +1837,14 @@ int pgq_csr_build_device(int64_t V, int64_t n_rows, const int64_t *d_src, const 
 			PGQ_HIP_TRY(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
 			PGQ_HIP_TRY(hipStreamSynchronize(st));
 			if (bad) return fail(PGQ_ERR_INVALID_ARG, "edge endpoint out of range [0,V)");
-			size_t sb = 0;
 			int end_bit = 1;
 			while ((1LL << end_bit) < V) end_bit++;
-			PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, d_key, d_skey, d_idx, d_order, (int)E, 0, end_bit, st));
-			PGQ_TRY(dev_alloc(&d_tmp, sb + 16));
 			// stable LSD radix sort by source == arrival order per vertex of the single-threaded reference
 			// (pos = ++v[src+1], csr_creation.cpp:132-138); the offsets (CsrInitializeEdge's prefix sum,
 			// csr_creation.cpp:57-59) are the row boundaries of the sorted keys
-			PGQ_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sb, d_key, d_skey, d_idx, d_order, (int)E, 0, end_bit, st));
+			PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) {
+				return hipcub::DeviceRadixSort::SortPairs(tmp, tb, d_key, d_skey, d_idx, d_order, (int)E, 0, end_bit, st);
+			}));
 			hipLaunchKernelGGL(k_row_bounds, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, st, d_skey, E, V, c->off);
 			hipLaunchKernelGGL(k_gather_rows, dim3(grid_for(E)), dim3(256), 0, st, d_order, E, d_dst, d_edge_id,
 			                   (const int64_t *)d_w, c->adj, c->edge_ids, (int64_t *)c->w);
@@ -1950,10 +1853,7 @@ int pgq_csr_build_device(int64_t V, int64_t n_rows, const int64_t *d_src, const 
 		}
 		// the temporaries go back to the block cache before finish_upload asks for its own (same sizes)
 		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		for (void **p : { (void **)&d_key, (void **)&d_idx, (void **)&d_skey, (void **)&d_order, &d_tmp }) {
-			dev_free(*p);
-			*p = nullptr;
-		}
+		temps.free_now();
 		return finish_upload(c, nullptr, st);
 	};
 	int rc = body();
@@ -1961,7 +1861,6 @@ int pgq_csr_build_device(int64_t V, int64_t n_rows, const int64_t *d_src, const 
 		(void)hipStreamSynchronize(st);
 		g_streams.put(st);
 	}
-	for (void *p : { (void *)d_key, (void *)d_idx, (void *)d_skey, (void *)d_order, (void *)d_bad, d_tmp }) dev_free(p);
 	if (rc != PGQ_OK) {
 		destroy_csr(c);
 		return rc;
@@ -2041,46 +1940,24 @@ static int clone_csr(const pgq_csr *c, int dev, pgq_csr **out) {
 	r->max_out_degree = c->max_out_degree;
 	r->max_in_degree = c->max_in_degree;
 	r->two_hop_mean = c->two_hop_mean;
-	r->bytes = c->bytes;
+	r->bytes = c->bytes.load();
 	r->has_negative_weight = c->has_negative_weight;
 	r->is_replica = true;
 	*out = r;
-	const size_t V1 = (size_t)c->V + 1, En = (size_t)std::max<int64_t>(c->E, 1);
-	auto copy = [&](void **dst, const void *src, size_t bytes) -> int {
-		*dst = nullptr;
-		if (!src || bytes == 0) return PGQ_OK;
-		PGQ_HIP_TRY(hipSetDevice(dev));
-		PGQ_TRY(dev_alloc(dst, bytes));
-		PGQ_HIP_TRY(hipMemcpyPeer(*dst, dev, src, c->device, bytes));
-		return PGQ_OK;
-	};
-	PGQ_TRY(copy((void **)&r->off, c->off, V1 * 8));
-	PGQ_TRY(copy((void **)&r->adj, c->adj, (En + 4) * 4));
-	PGQ_TRY(copy((void **)&r->edge_ids, c->edge_ids, En * 8));
-	PGQ_TRY(copy((void **)&r->w, c->w, En * 8));
-	PGQ_TRY(copy((void **)&r->roff, c->roff, V1 * 8));
-	PGQ_TRY(copy((void **)&r->radj, c->radj, (En + 4) * 4));
-	PGQ_TRY(copy((void **)&r->pull_hubs, c->pull_hubs, (size_t)c->n_pull_hub_items * sizeof(HubItem)));
-	PGQ_TRY(copy((void **)&r->pull_hub_vertices, c->pull_hub_vertices, (size_t)c->n_pull_hub_vertices * 4));
-	PGQ_TRY(copy((void **)&r->pull_parts, c->pull_parts, (size_t)c->n_pull_parts * 2 * 4));
-	PGQ_TRY(copy((void **)&r->rown, c->rown, En + 8));
-	PGQ_TRY(copy((void **)&r->rpk, c->rpk, (En + 2048) * 4));
 	r->padj_groups = c->padj_groups;
 	r->rpadj_groups = c->rpadj_groups;
-	PGQ_TRY(copy((void **)&r->padj, c->padj, (size_t)c->padj_groups * 16 + 16));
-	PGQ_TRY(copy((void **)&r->rpadj, c->rpadj, (size_t)c->rpadj_groups * 16 + 16));
 	r->ppadj_groups = c->ppadj_groups;
 	r->prpadj_groups = c->prpadj_groups;
 	r->pack_k = c->pack_k;
-	PGQ_TRY(copy((void **)&r->ppadj, c->ppadj, (size_t)c->ppadj_groups * 16 + 16));
-	PGQ_TRY(copy((void **)&r->prpadj, c->prpadj, (size_t)c->prpadj_groups * 16 + 16));
-	PGQ_TRY(copy((void **)&r->fseg, c->fseg, (size_t)c->V * 8));
-	PGQ_TRY(copy((void **)&r->rseg, c->rseg, (size_t)c->V * 8));
-	PGQ_TRY(copy((void **)&r->rhead, c->rhead, (size_t)c->V * 256));
-	PGQ_TRY(copy((void **)&r->fwork, c->fwork, (size_t)c->V * 4));
-	PGQ_TRY(copy((void **)&r->rwork, c->rwork, (size_t)c->V * 4));
-	PGQ_TRY(copy((void **)&r->fdesc, c->fdesc, (En + 1) * 16));
-	PGQ_TRY(copy((void **)&r->rdesc, c->rdesc, (En + 1) * 16));
+	// every array but the ones built on first use (a replica builds its own), at the size it was allocated with
+	const auto from = csr_arrays(const_cast<pgq_csr *>(c)), to = csr_arrays(r);
+	for (int k = 0; k < kCsrArrays; k++) {
+		const void *src = *from[k].slot;
+		if (from[k].kind == CsrArrayKind::lazy || !src || from[k].bytes == 0) continue;
+		PGQ_HIP_TRY(hipSetDevice(dev));
+		PGQ_TRY(dev_alloc(to[k].slot, from[k].bytes));
+		PGQ_HIP_TRY(hipMemcpyPeer(*to[k].slot, dev, src, c->device, from[k].bytes));
+	}
 	PGQ_HIP_TRY(hipDeviceSynchronize());
 	return PGQ_OK;
 }
@@ -2132,7 +2009,12 @@ int pgq_csr_replicate(pgq_csr_t *c) {
 int64_t pgq_csr_num_vertices(const pgq_csr_t *csr) { return csr ? csr->V : -1; }
 int64_t pgq_csr_num_edges(const pgq_csr_t *csr) { return csr ? csr->E : -1; }
 int pgq_csr_w_type(const pgq_csr_t *csr) { return csr ? csr->w_type : -1; }
-int64_t pgq_csr_device_bytes(const pgq_csr_t *csr) { return csr ? csr->bytes : -1; }
+int64_t pgq_csr_device_bytes(const pgq_csr_t *csr) { return csr ? csr->bytes.load(std::memory_order_relaxed) : -1; }
+int64_t pgq_debug_live_device_blocks(void) {
+	BlockCache &bc = block_cache();
+	std::lock_guard<std::mutex> g(bc.lock);
+	return (int64_t)bc.live.size();
+}
 int pgq_csr_has_prepass_layout(const pgq_csr_t *csr) { return csr && csr->fdesc != nullptr ? 1 : 0; }
 int pgq_csr_pack_k(const pgq_csr_t *csr) { return csr ? csr->pack_k : -1; }
 

@@ -128,6 +128,10 @@ int pgq_csr_has_prepass_layout(const pgq_csr_t *csr);
  * 5 (25-bit ids, V <= 2^25 with option meet_pack = 2) or 4 (the 32-bit padded lists: meet_pack = 0, larger graphs, no
  * layout); -1 for a NULL handle. */
 int pgq_csr_pack_k(const pgq_csr_t *csr);
+/* Debugging / tests: device blocks the library's block cache has handed out and not got back yet (CSR arrays and build
+ * temporaries of every live handle; cached free blocks, workspaces and pinned memory are not counted).  The same figure
+ * before a handle is created and after it is freed = the handle left nothing behind. */
+int64_t pgq_debug_live_device_blocks(void);
 
 /* ---- searches, chunk form (host memory, UnifiedVectorFormat in, FLAT vector out) --------------------- */
 
