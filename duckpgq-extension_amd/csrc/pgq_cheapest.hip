@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256, PGQ_RELAX_WAVES) void k_relax(const int64_t *_
                                                u64 *__restrict__ hmask, u32 *__restrict__ hstart, u32 *__restrict__ hmap,
                                                const DT *__restrict__ other, long long *__restrict__ mu,
                                                u32 *__restrict__ alive, const long long *__restrict__ thr_ptr) {
-	// `other` != nullptr: one side of the bidirectional search (relax_batches_bidir).  Lane l is one (src, dst) PAIR, `dist` this
+	// `other` != nullptr: one side of the bidirectional search (BidirBatches).  Lane l is one (src, dst) PAIR, `dist` this
 	// side's labels and `other` the other side's; `bound` is the pair's best known src -> dst length mu[l] (both sides prune
 	// with it), `*thr_ptr` the distance cap both sides expand under.  A vertex expanded here that carries a label of the other
 	// side closes a path: mu[l] = min(mu[l], label + other label).  alive[l] = 1: the lane left a labelled vertex unexpanded
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, PGQ_RELAX_WAVES) void k_relax(const int64_t *_
 	if (thr_ptr) {
 		thr = *thr_ptr;
 		// nothing is labelled at or above twice the cap: a pair that needs such a label is not finished in this phase anyway
-		// (exactness: relax_batches_bidir), and an expansion walks the few edges under 2 C - label instead of its whole list
+		// (exactness: BidirBatches), and an expansion walks the few edges under 2 C - label instead of its whole list
 		if (other) my_bound = min(my_bound, 2 * thr);
 	}
 	long long my_mu = 0x7FFFFFFFFFFFFFFFll; // (bidirectional) smallest label + other side's label this wavefront's lane has seen
@@ -1185,9 +1185,14 @@ static int cheapest_with_chains(pgq_csr *c, Workspace *ws, int64_t n, const int6
 	PGQ_TRY(ws->def_idx.reserve((size_t)nd_chain * 4));
 	PGQ_TRY(ws->def_len.reserve((size_t)nd_chain * 8));
 	PGQ_TRY(ws->def_off.reserve((size_t)nd_chain));
-	hipLaunchKernelGGL(k_collect_open_rows, dim3(blocks_for(n)), dim3(256), 0, st, n, d_ok, d_src, d_dst,
-	                   ws->def_src.as<int64_t>(), ws->def_dst.as<int64_t>(), ws->def_idx.as<u32>(), d_cnt + 2);
-	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	auto collect_open = [&]() -> int { // the open rows (ok = 2) compacted into ws->def_src / def_dst / def_idx, waited for
+		PGQ_HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 4, st));
+		hipLaunchKernelGGL(k_collect_open_rows, dim3(blocks_for(n)), dim3(256), 0, st, n, d_ok, d_src, d_dst,
+		                   ws->def_src.as<int64_t>(), ws->def_dst.as<int64_t>(), ws->def_idx.as<u32>(), d_cnt + 2);
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		return PGQ_OK;
+	};
+	PGQ_TRY(collect_open());
 	u32 nd = nd_chain;
 	{ // general graphs: a bidirectional search per row; what it leaves open (caps) is collected again
 		u32 left = nd;
@@ -1198,10 +1203,7 @@ static int cheapest_with_chains(pgq_csr *c, Workspace *ws, int64_t n, const int6
 				tstats().s.pairs += n;
 				return PGQ_OK;
 			}
-			PGQ_HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 4, st));
-			hipLaunchKernelGGL(k_collect_open_rows, dim3(blocks_for(n)), dim3(256), 0, st, n, d_ok, d_src, d_dst,
-			                   ws->def_src.as<int64_t>(), ws->def_dst.as<int64_t>(), ws->def_idx.as<u32>(), d_cnt + 2);
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
+			PGQ_TRY(collect_open());
 		}
 	}
 	{
@@ -1230,249 +1232,300 @@ static bool light_edges_first(const pgq_csr *c) {
 	return (double)c->E >= (double)std::max(1, o.relax_light_min_degree) * (double)std::max<int64_t>(c->V, 1);
 }
 
-// The batches b0, b0 + bstride, ... of a call: `ws` holds the sorted rows and the distinct sources (read-only here),
-// `priv` everything a batch writes (labels, dirty words, queues) and the stream.  Batches are independent, so several
-// host threads run this side by side on their own workspaces (cheapest_device).
 // Whether this CSR's labels are stored as int32 (Lab<int32_t> above): int64 weights, the light-edges-first path (the
 // device-side small rounds of the plain path keep 8-byte labels), and no path sum that could reach 2^31 - 1.
 template <typename T> static bool labels_fit_32(const pgq_csr *c) {
 	if (!std::is_same<T, int64_t>::value || !options().relax_labels32 || !light_edges_first(c) || !c->wadj) return false;
-	if (!(c->w_mean > 0 && c->w_mean < 1e300)) return false; // (plain rounds then: relax_batches' own test)
+	if (!(c->w_mean > 0 && c->w_mean < 1e300)) return false; // (plain rounds then: cheapest_device's own test)
 	const unsigned long long w_max = c->w_max_bits; // int64 weights are non-negative here: the bit pattern is the value
 	return w_max < (1ull << 31) && (double)w_max * (double)std::max<int64_t>(c->V, 1) < 2147483000.0;
 }
 
-template <typename T, typename DT>
-static int relax_batches(pgq_csr *c, Workspace *ws, Workspace *priv, int b0, int bstride, int nb, u32 U, int64_t *d_out,
-                         uint8_t *d_ok, const bool light) {
-	// `light` (and with it the label width DT) was decided ONCE by cheapest_device: a concurrent pgq_set_option between two
-	// evaluations used to leave a worker with 4-byte labels outside the light-edges-first path (an "internal error" return)
-	hipStream_t st = priv->stream;
-	const int64_t V = c->V;
-	const int64_t inf_bits = Inf<T>::bits;
-	const DT inf_label = (DT)Lab<DT>::unlabelled(inf_bits);
-	pgq_stats_t &S = tstats().s;
-	const int64_t *bs = ws->h_bstart;
-	const size_t cells = (size_t)std::max<int64_t>(V, 1) * LC;
-	// distances start at INF; a full fill only when the array is new, afterwards only touched rows are reset
-	// (the INF pattern differs between int64 and double, the cell size between 8- and 4-byte labels)
-	const int type_tag = sizeof(DT) == 4 ? 3 : (std::is_same<T, double>::value ? 2 : 1);
-	const bool fresh = priv->dist.cap < cells * sizeof(DT) || priv->dist_V != V || priv->dist_lanes != type_tag;
-	priv->dist_V = -1; // stays invalid if we bail out half-way; restored at the end
-	PGQ_TRY(priv->dist.reserve(cells * sizeof(DT)));
-	for (int k = 0; k < 2; k++) PGQ_TRY(priv->dirty[k].reserve((size_t)std::max<int64_t>(V, 1) * 8));
-	PGQ_TRY(priv->qbuf[0].reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	PGQ_TRY(priv->qbuf[1].reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	PGQ_TRY(priv->touched.reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	PGQ_TRY(priv->qflag.reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	PGQ_TRY(priv->tflag.reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	// heavy list of a round: entries (vertex, lanes, first chunk) and the chunk -> entry map (<= E/64 + V chunks)
-	PGQ_TRY(priv->hv.reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	PGQ_TRY(priv->hmask.reserve((size_t)std::max<int64_t>(V, 1) * 8));
-	PGQ_TRY(priv->hstart.reserve((size_t)std::max<int64_t>(V, 1) * 4));
-	PGQ_TRY(priv->hmap.reserve((size_t)(c->E / 64 + std::max<int64_t>(V, 1)) * 4));
-	PGQ_TRY(priv->counters.reserve(sizeof(Counters)));
-	static_assert(sizeof(RelaxCounters) <= sizeof(Counters), "counter block too small");
-	RelaxCounters *d_rc = reinterpret_cast<RelaxCounters *>(priv->counters.p);
-	RelaxCounters *h_rc = reinterpret_cast<RelaxCounters *>(priv->h_cnt);
-	if (fresh) {
-		if constexpr (sizeof(DT) == 4) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, priv->dist.as<int32_t>(), (int64_t)cells, (int32_t)inf_label);
-		else hipLaunchKernelGGL(k_fill64, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, priv->dist.as<int64_t>(), (int64_t)cells, inf_bits);
-	}
-	PGQ_HIP_TRY(hipMemsetAsync(priv->dirty[0].p, 0, (size_t)std::max<int64_t>(V, 1) * 8, st));
-	PGQ_HIP_TRY(hipMemsetAsync(priv->dirty[1].p, 0, (size_t)std::max<int64_t>(V, 1) * 8, st));
-	PGQ_HIP_TRY(hipMemsetAsync(priv->qflag.p, 0, (size_t)std::max<int64_t>(V, 1) * 4, st));
-	PGQ_HIP_TRY(hipMemsetAsync(priv->tflag.p, 0, (size_t)std::max<int64_t>(V, 1) * 4, st));
-	u32 epoch = 0, tepoch = 0;
-	// the persistent grid of a round: exactly what is resident at once (each wavefront takes every nwaves-th vertex; a
-	// grid larger than the chip makes the last workgroups start when the first finish: 8192 waves on 7168 slots was 2x)
-	static std::mutex grid_lock;
-	static unsigned grid_cached[3][64] = {}; // per label / weight type and device: a node's devices need not be alike
-	unsigned grid;
-	{
-		std::lock_guard<std::mutex> g(grid_lock);
-		int dev = 0;
-		PGQ_HIP_TRY(hipGetDevice(&dev));
-		unsigned &gc = grid_cached[type_tag - 1][dev & 63];
-		if (!gc) {
-			int per_cu = 0, cus = 0;
-			PGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax<T, DT>, 256, 0));
-			PGQ_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-			gc = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
-		}
-		grid = gc;
-	}
-	for (int b = b0; b < nb; b += bstride) {
-		const int64_t lo = bs[b], hi = bs[b + 1];
-		if (lo == hi) continue;
-		S.batches++;
-		const int64_t base = (int64_t)b * LC;
-		tepoch++;
-		PGQ_HIP_TRY(hipMemsetAsync(d_rc, 0, sizeof(RelaxCounters), st));
-		{
-			KernelTimer kt(st, K_PREP);
-			hipLaunchKernelGGL(k_cheapest_init<DT>, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base,
-			                   priv->dist.as<DT>(), priv->dirty[0].as<u64>(), priv->tflag.as<u32>(), tepoch,
-			                   priv->touched.as<int32_t>(), &d_rc->nq[0], &d_rc->tcount, priv->qbuf[0].as<int32_t>());
-			kt.stop();
-		}
-		int par = 0;
-		u32 nq_now = (u32)std::min<int64_t>(LC, (int64_t)U - base);
-		const u32 small_limit = (u32)std::max(0, options().relax_small_limit);
-		// band width of the ordered rounds: a fraction of the mean weight (0: plain Jacobi rounds, everything at once)
-		T band = T(0);
-		if (options().relax_delta_div > 0) {
-			PGQ_TRY(ensure_weight_mean(c, ws));
-			if constexpr (std::is_same<T, double>::value) band = c->w_mean / options().relax_delta_div;
-			else band = (T)std::max<int64_t>(1, (int64_t)(c->w_mean / options().relax_delta_div));
-		}
-		auto bits_of = [](T x) -> long long {
-			long long r;
-			memcpy(&r, &x, 8);
-			return r;
-		};
-		T thr_val = band;
-		// "light edges first" (relax_light): the rounds run over weight-sorted lists under a cap on the edge weight that
-		// doubles phase by phase — early phases touch a few per cent of the edges and give every lane a tight bound on
-		// its destinations, later phases hardly relax anything (a vertex stops at the first edge whose weight cannot beat
-		// its lanes' bounds) — until the cap reaches the largest bound (heavier edges cannot be on a cheaper path)
-		// (a mean that is not a positive finite number — NaN / inf weights, an int64 sum that wrapped — gives no first cap:
-		// plain rounds then)
-		const bool heavy = options().relax_split != 0;
-		static const bool trace = getenv("PGQ_RELAX_TRACE") != nullptr; // per-round line on stderr (measurement only)
-		auto t_round = std::chrono::steady_clock::now();
-		T wcap = T(0);
-		if (light) {
-			PGQ_TRY(ensure_weight_sorted(c, ws));
-			PGQ_TRY(ensure_weight_mean(c, ws));
-			if constexpr (std::is_same<T, double>::value) wcap = c->w_mean / std::max(1, options().relax_light_div);
-			else wcap = (T)std::max<int64_t>(1, (int64_t)(c->w_mean / std::max(1, options().relax_light_div)));
-		}
-		const int32_t *r_adj = light ? c->wadj : c->adj;
-		const T *r_w = light ? (const T *)c->wsorted : (const T *)c->w;
-		for (;;) {
-			if (!light && sizeof(DT) == 4) return fail(PGQ_ERR_HIP, "internal error: 4-byte labels outside the light-edges-first path");
-			if (!light && nq_now <= small_limit) {
-				// few changed vertices: rounds loop on the device inside one workgroup (8-byte labels only: labels_fit_32)
-				const int max_rounds = 4096;
-				KernelTimer kt(st, K_RELAX);
-				hipLaunchKernelGGL(k_relax_small<T>, dim3(1), dim3(1024), 0, st, c->off, c->adj, (const T *)c->w,
-				                   priv->dist.as<int64_t>(), priv->dirty[0].as<u64>(), priv->dirty[1].as<u64>(),
-				                   priv->qbuf[0].as<int32_t>(), priv->qbuf[1].as<int32_t>(), d_rc, par, small_limit,
-				                   priv->qflag.as<u32>(), epoch + 1, priv->tflag.as<u32>(), tepoch,
-				                   priv->touched.as<int32_t>(), max_rounds);
-				kt.stop();
-				PGQ_HIP_TRY(hipMemcpyAsync(h_rc, d_rc, sizeof(RelaxCounters), hipMemcpyDeviceToHost, st));
-				PGQ_HIP_TRY(hipStreamSynchronize(st));
-				KernelTimer::flush();
-				epoch += h_rc->rounds + 1;
-				S.levels += h_rc->rounds;
-				par ^= (int)(h_rc->rounds & 1u);
-				nq_now = h_rc->nq[par];
-				if (nq_now == 0) break;
-				if (nq_now <= small_limit && h_rc->rounds > 0) continue; // hit max_rounds: go again
-			}
-			epoch++;
-			// one launch instead of five fills per round (2459 rounds per 4096-pair step on the weighted knows graph)
-			hipLaunchKernelGGL(k_round_reset, dim3(1), dim3(64), 0, st, d_rc, par ^ 1);
-			const long long thr_bits = band > T(0) ? bits_of(thr_val) : (long long)0x7FFFFFFFFFFFFFFFll;
-			{
-				KernelTimer kt(st, K_RELAX);
-				hipLaunchKernelGGL(k_lane_bounds<DT>, dim3((unsigned)std::min<int64_t>(blocks_for(hi - lo), 256)), dim3(256), 0, st, lo, hi,
-				                   ws->skey.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, priv->dist.as<DT>(), inf_bits, d_rc->bound);
-				hipLaunchKernelGGL((k_relax<T, DT>), dim3(std::min(grid, std::max(1u, (nq_now + 3) / 4))), dim3(256), 0, st, c->off, r_adj, r_w,
-				                   priv->dist.as<DT>(), priv->dirty[par].as<u64>(), priv->dirty[par ^ 1].as<u64>(),
-				                   priv->qbuf[par].as<int32_t>(), &d_rc->nq[par], priv->qbuf[par ^ 1].as<int32_t>(),
-				                   &d_rc->nq[par ^ 1], priv->tflag.as<u32>(), tepoch,
-				                   priv->touched.as<int32_t>(), &d_rc->tcount, &d_rc->relaxed_edges, thr_bits,
-				                   (const long long *)d_rc->bound, &d_rc->min_deferred, &d_rc->relaxed_vertices, light ? 1 : 0, wcap,
-				                   0, heavy ? &d_rc->heavy : (u64 *)nullptr, priv->hv.as<int32_t>(), priv->hmask.as<u64>(),
-				                   priv->hstart.as<u32>(), priv->hmap.as<u32>(), (const DT *)nullptr, (long long *)nullptr, (u32 *)nullptr,
-				                   (const long long *)nullptr);
-				if (heavy) // the long lists of the round, a chunk per wavefront
-					hipLaunchKernelGGL((k_relax<T, DT>), dim3(grid), dim3(256), 0, st, c->off, r_adj, r_w,
-					                   priv->dist.as<DT>(), priv->dirty[par].as<u64>(), priv->dirty[par ^ 1].as<u64>(),
-					                   priv->qbuf[par].as<int32_t>(), &d_rc->nq[par], priv->qbuf[par ^ 1].as<int32_t>(),
-					                   &d_rc->nq[par ^ 1], priv->tflag.as<u32>(), tepoch,
-					                   priv->touched.as<int32_t>(), &d_rc->tcount, &d_rc->relaxed_edges, thr_bits,
-					                   (const long long *)d_rc->bound, &d_rc->min_deferred, &d_rc->relaxed_vertices, light ? 1 : 0, wcap,
-					                   1, &d_rc->heavy, priv->hv.as<int32_t>(), priv->hmask.as<u64>(), priv->hstart.as<u32>(),
-					                   priv->hmap.as<u32>(), (const DT *)nullptr, (long long *)nullptr, (u32 *)nullptr, (const long long *)nullptr);
-				kt.stop();
-			}
-			PGQ_HIP_TRY(hipMemcpyAsync(h_rc, d_rc, sizeof(RelaxCounters), hipMemcpyDeviceToHost, st));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-			if (trace) {
-				const auto t1 = std::chrono::steady_clock::now();
-				fprintf(stderr, "relax b=%d round=%lld cap=%g nq=%u expanded=%u heavy=%u/%u edges=%llu next=%u us=%.1f\n", b,
-				        (long long)S.levels, (double)wcap, nq_now, h_rc->relaxed_vertices, (u32)(h_rc->heavy >> 32),
-				        (u32)h_rc->heavy, (unsigned long long)h_rc->relaxed_edges, h_rc->nq[par ^ 1],
-				        std::chrono::duration<double, std::micro>(t1 - t_round).count());
-				t_round = t1;
-			}
-			S.levels++;
-			par ^= 1;
-			nq_now = h_rc->nq[par];
-			if (nq_now == 0) {
-				if (!light) break;
-				// the phase has reached its fixpoint.  Done when no heavier edge can matter: the cap has reached the largest
-				// bound of a lane (the bounds of the last round: labels only got smaller since) or the largest weight
-				T max_bound = T(0);
-				bool unbounded = false;
-				for (int l = 0; l < LC; l++) {
-					if (h_rc->bound[l] >= (long long)inf_bits) unbounded = true;
-					T bv;
-					memcpy(&bv, &h_rc->bound[l], 8);
-					if (bv > max_bound) max_bound = bv;
-				}
-				// (negated comparisons: a cap that is NaN or inf ends the search like one that has reached the largest weight)
-				T w_max;
-				memcpy(&w_max, &c->w_max_bits, 8);
-				if (!(wcap < w_max) || (!unbounded && !(wcap < max_bound))) break;
-				if constexpr (std::is_same<T, double>::value) wcap = wcap + wcap;
-				else wcap = wcap > std::numeric_limits<int64_t>::max() / 2 ? std::numeric_limits<int64_t>::max() : wcap + wcap;
-				// every labelled vertex again, over the longer prefix of its list
-				PGQ_HIP_TRY(hipMemsetAsync(&d_rc->nq[par], 0, 4, st));
-				hipLaunchKernelGGL(k_redirty, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, priv->touched.as<int32_t>(), &d_rc->tcount,
-				                   priv->dirty[par].as<u64>(), priv->qbuf[par].as<int32_t>(), &d_rc->nq[par]);
-				PGQ_HIP_TRY(hipMemcpyAsync(h_rc, d_rc, sizeof(RelaxCounters), hipMemcpyDeviceToHost, st));
-				PGQ_HIP_TRY(hipStreamSynchronize(st));
-				nq_now = h_rc->nq[par];
-				if (nq_now == 0) break;
-				continue;
-			}
-			if (band > T(0)) { // next band; an empty one is skipped: straight to the smallest label left
-				thr_val = thr_val + band;
-				if (h_rc->relaxed_vertices == 0 && h_rc->min_deferred != 0x7F7F7F7F7F7F7F7Fll) {
-					T m;
-					memcpy(&m, &h_rc->min_deferred, 8);
-					if (m + band > thr_val) thr_val = m + band;
-				}
-			}
-		}
-		S.edges_scanned += (int64_t)h_rc->relaxed_edges;
-		S.algo_bytes[K_RELAX] += (double)h_rc->relaxed_edges * (4.0 + 8.0 + 2.0 * (double)sizeof(DT) * LC);
-		hipLaunchKernelGGL(k_cheapest_results<DT>, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(),
-		                   ws->sidx.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, priv->dist.as<DT>(), inf_bits,
-		                   d_out, d_ok);
-		hipLaunchKernelGGL(k_reset_touched<DT>, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, priv->touched.as<int32_t>(), &d_rc->tcount,
-		                   priv->dist.as<DT>(), inf_label);
-	}
-	PGQ_HIP_TRY(hipStreamSynchronize(st));
-	KernelTimer::flush();
-	priv->dist_V = V; // every touched row is back at INF
-	priv->dist_lanes = type_tag;
+// ---- what the two relaxation drivers share ------------------------------------------------------------------------------
+// what a label array holds (RelaxSide::dist_tag): INF differs between int64 and double, the cell size between 8 and 4 bytes
+template <typename T, typename DT> constexpr int relax_label_tag() { return sizeof(DT) == 4 ? 3 : (std::is_same<T, double>::value ? 2 : 1); }
+
+// distances start at INF; a full fill only when the array is new, afterwards only touched rows are reset
+template <typename DT> int RelaxSide::prepare(int64_t V, int type_tag, DT inf_label, hipStream_t st) {
+	const size_t Vn = (size_t)std::max<int64_t>(V, 1), cells = Vn * LC;
+	const bool fresh = dist.cap < cells * sizeof(DT) || dist_V != V || dist_tag != type_tag;
+	dist_V = -1; // stays invalid if we bail out half-way; restored by settle()
+	PGQ_TRY(dist.reserve(cells * sizeof(DT)));
+	for (DevBuf &b : dirty) PGQ_TRY(b.reserve(Vn * 8));
+	for (DevBuf *b : { &q[0], &q[1], &touched, &tflag }) PGQ_TRY(b->reserve(Vn * 4));
+	if (fresh && sizeof(DT) == 4) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, dist.as<int32_t>(), (int64_t)cells, (int32_t)inf_label);
+	if (fresh && sizeof(DT) == 8) hipLaunchKernelGGL(k_fill64, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, dist.as<int64_t>(), (int64_t)cells, (int64_t)inf_label);
+	for (DevBuf &b : dirty) PGQ_HIP_TRY(hipMemsetAsync(b.p, 0, Vn * 8, st));
+	PGQ_HIP_TRY(hipMemsetAsync(tflag.p, 0, Vn * 4, st));
 	return PGQ_OK;
 }
 
-// ---- general graphs, about one destination per source: both ends at once (relax_batches_bidir, round 6) ------------------
+// the persistent grid of a round: exactly what is resident at once (each wavefront takes every nwaves-th vertex; a
+// grid larger than the chip makes the last workgroups start when the first finish: 8192 waves on 7168 slots was 2x)
+static std::mutex g_relax_grid_lock;
+template <typename T, typename DT> static int relax_grid(unsigned *grid) {
+	static unsigned cached[64] = {}; // per instantiation and device: a node's devices need not be alike
+	std::lock_guard<std::mutex> g(g_relax_grid_lock);
+	int dev = 0, per_cu = 0, cus = 0;
+	PGQ_HIP_TRY(hipGetDevice(&dev));
+	if (!cached[dev & 63]) {
+		PGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax<T, DT>, 256, 0));
+		PGQ_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+		cached[dev & 63] = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
+	}
+	*grid = cached[dev & 63];
+	return PGQ_OK;
+}
+
+// a fraction of the mean weight as a weight: a band width, a first cap (integers: at least 1)
+template <typename T> static T weight_fraction(double mean, int div) {
+	return std::is_same<T, double>::value ? (T)(mean / div) : (T)std::max<int64_t>(1, (int64_t)(mean / div));
+}
+
+struct BiBlock { // the two-ended search's device block (BidirBatches)
+	RelaxCounters rc[2]; // forward / backward: k_relax's round counters
+	long long mu[64];    // per lane: best src -> dst length so far = both sides' bound; 0 once the lane is finished
+	long long res[64];   // per lane: the answer (INF: no path)
+	u32 alive[2][64];    // per side and lane: a labelled vertex was left unexpanded (over the cap) this round
+	u32 done[64];
+	long long cap, step;
+	u32 active, phases;
+};
+
+// What one k_relax launch works on: everything but the pass, the grid and the queue's fill.
+template <typename T> struct RelaxRound {
+	Workspace *h;       // the worker's: stream, sides and heavy lists (hv, hmask, hstart, hmap)
+	int s, par;         // the side that expands; which of its dirty words / queues are the input, the other parity the output
+	const int64_t *off; // the lists the side walks
+	const int32_t *adj;
+	const T *w;
+	u32 tepoch;
+	RelaxCounters *rc; // the side's counter block
+	long long thr;     // one-sided: only labels below it are expanded this round, no lane beyond rc->bound
+	int sorted;        // the lists ascend by weight, and only the prefix under wcap counts
+	T wcap;
+	bool heavy;            // long lists are set aside for a heavy pass
+	BiBlock *bb = nullptr; // two-ended: the pairs' bounds mu, the side's alive flags, the common cap; the other side's labels close paths
+};
+
+// The one launch of k_relax: pass 0 over the nq changed vertices (a workgroup per four), the heavy pass over the long lists' chunks.
+template <typename T, typename DT> static void launch_relax(const RelaxRound<T> &r, int heavy_pass, unsigned grid, u32 nq) {
+	Workspace *const h = r.h;
+	RelaxSide &s = h->relax[r.s], &o = h->relax[r.s ^ 1];
+	BiBlock *const bb = r.bb;
+	const int p = r.par;
+	if (!heavy_pass) grid = std::min(grid, std::max(1u, (nq + 3) / 4));
+	hipLaunchKernelGGL((k_relax<T, DT>), dim3(grid), dim3(256), 0, h->stream, r.off, r.adj, r.w, s.dist.as<DT>(), s.dirty[p].as<u64>(),
+	                   s.dirty[p ^ 1].as<u64>(), s.q[p].as<int32_t>(), &r.rc->nq[p], s.q[p ^ 1].as<int32_t>(), &r.rc->nq[p ^ 1],
+	                   s.tflag.as<u32>(), r.tepoch, s.touched.as<int32_t>(), &r.rc->tcount, &r.rc->relaxed_edges, r.thr,
+	                   (const long long *)(bb ? bb->mu : r.rc->bound), &r.rc->min_deferred, &r.rc->relaxed_vertices, r.sorted, r.wcap,
+	                   heavy_pass, r.heavy ? &r.rc->heavy : (u64 *)nullptr, h->hv.as<int32_t>(), h->hmask.as<u64>(), h->hstart.as<u32>(),
+	                   h->hmap.as<u32>(), bb ? (const DT *)o.dist.as<DT>() : (const DT *)nullptr, bb ? bb->mu : (long long *)nullptr,
+	                   bb ? bb->alive[r.s] : (u32 *)nullptr, bb ? (const long long *)&bb->cap : (const long long *)nullptr);
+}
+
+// One worker of a call: `ws` holds the sorted rows and the distinct sources (read-only here), `priv` everything a batch
+// writes (labels, dirty words, queues, heavy lists, counters) and the stream.  Batches are independent, so several host
+// threads run side by side on their own workspaces (cheapest_device).
+struct RelaxWorker {
+	pgq_csr *const c;
+	Workspace *const ws, *const priv;
+	const int nb; // the call's batches; this worker runs b0, b0 + bstride, ... < nb
+	int64_t *const d_out;
+	uint8_t *const d_ok;
+	const hipStream_t st = priv->stream;
+	const int64_t V = c->V;
+	const size_t Vn = (size_t)std::max<int64_t>(V, 1);
+	pgq_stats_t &S = tstats().s;
+	unsigned grid = 0; // relax_grid
+	u32 tepoch = 0;    // the batch's first-touch stamp
+	int b = 0;         // the batch
+	const bool trace = getenv("PGQ_RELAX_TRACE") != nullptr; // a line per round on stderr (measurement only)
+	// `sides` sides ready for a batch, a round's heavy lists (entries, and the map of <= E/64 + V chunks to them), the grid
+	template <typename T, typename DT> int prepare(int sides) {
+		for (int s = 0; s < sides; s++) PGQ_TRY(priv->relax[s].prepare<DT>(V, relax_label_tag<T, DT>(), (DT)Lab<DT>::unlabelled(Inf<T>::bits), st));
+		for (DevBuf *b : { &priv->hv, &priv->hstart }) PGQ_TRY(b->reserve(Vn * 4));
+		PGQ_TRY(priv->hmask.reserve(Vn * 8));
+		PGQ_TRY(priv->hmap.reserve(((size_t)(c->E / 64) + Vn) * 4));
+		return relax_grid<T, DT>(&grid);
+	}
+	int read_back(void *host, const void *dev, size_t bytes) { // a round's counters on the host, its timers (if any) resolved
+		PGQ_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		KernelTimer::flush();
+		return PGQ_OK;
+	}
+	// a finished batch: its statistics (adjacency entry, weight, two label rows per relaxed edge), its touched labels back to INF
+	template <typename T, typename DT> void end_batch(u64 edges, int sides, RelaxCounters *rc) {
+		S.edges_scanned += (int64_t)edges;
+		S.algo_bytes[K_RELAX] += (double)edges * (4.0 + 8.0 + 2.0 * (double)sizeof(DT) * LC);
+		for (int s = 0; s < sides; s++)
+			hipLaunchKernelGGL(k_reset_touched<DT>, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, priv->relax[s].touched.as<int32_t>(), &rc[s].tcount,
+			                   priv->relax[s].dist.as<DT>(), (DT)Lab<DT>::unlabelled(Inf<T>::bits));
+	}
+	template <typename T, typename DT> int settle(int sides) { // behind the worker's last batch: every touched row is back at INF
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		KernelTimer::flush();
+		for (int s = 0; s < sides; s++) priv->relax[s].settle(V, relax_label_tag<T, DT>());
+		return PGQ_OK;
+	}
+};
+
+// The lane batches b0, b0 + bstride, ... < nb of a call, one lane per distinct source: plain rounds (every edge of a changed
+// vertex; few changed vertices loop on the device) or light edges first (light_edges_first).
+template <typename T, typename DT> class RelaxBatches : RelaxWorker {
+public:
+	RelaxBatches(const RelaxWorker &w, u32 U, bool light) : RelaxWorker(w), U(U), light(light) {}
+
+	int run(int b0, int bstride) {
+		if (!light && sizeof(DT) == 4) return fail(PGQ_ERR_HIP, "internal error: 4-byte labels outside the light-edges-first path");
+		PGQ_TRY((prepare<T, DT>(1)));
+		PGQ_TRY(priv->qflag.reserve(Vn * 4));
+		PGQ_TRY(priv->counters.reserve(sizeof(Counters)));
+		static_assert(sizeof(RelaxCounters) <= sizeof(Counters), "counter block too small");
+		d_rc = reinterpret_cast<RelaxCounters *>(priv->counters.p);
+		PGQ_HIP_TRY(hipMemsetAsync(priv->qflag.p, 0, Vn * 4, st));
+		for (b = b0; b < nb; b += bstride) {
+			lo = ws->h_bstart[b], hi = ws->h_bstart[b + 1];
+			if (lo == hi) continue;
+			PGQ_TRY(start_batch());
+			for (;;) {
+				if (!light && nq_now <= small_limit) {
+					PGQ_TRY(small_rounds());
+					if (nq_now == 0) break;
+					if (nq_now <= small_limit && h_rc->rounds > 0) continue; // hit max_rounds: go again
+				}
+				PGQ_TRY(round());
+				if (nq_now != 0) next_band();
+				else if (light) PGQ_TRY(next_phase()); // (leaves nq_now at 0 when no heavier edge can matter)
+				if (nq_now == 0) break;
+			}
+			finish_batch();
+		}
+		return settle<T, DT>(1);
+	}
+private:
+	const u32 U;
+	const bool light;
+	RelaxSide &sd = priv->relax[0];
+	RelaxCounters *d_rc = nullptr, *const h_rc = reinterpret_cast<RelaxCounters *>(priv->h_cnt); // priv's counter block, its pinned copy
+	u32 epoch = 0; // queue-flag stamp of the device-side small rounds
+	int par = 0;   // from here on: the batch's (start_batch)
+	int64_t lo = 0, hi = 0, base = 0;
+	u32 nq_now = 0, small_limit = 0;
+	bool heavy = false;
+	T band = T(0), thr_val = T(0), wcap = T(0);
+	std::chrono::steady_clock::time_point t_round;
+
+	int start_batch() {
+		const Options &opt = options();
+		S.batches++;
+		base = (int64_t)b * LC;
+		tepoch++;
+		PGQ_HIP_TRY(hipMemsetAsync(d_rc, 0, sizeof(RelaxCounters), st));
+		KernelTimer kt(st, K_PREP);
+		hipLaunchKernelGGL(k_cheapest_init<DT>, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base, sd.dist.as<DT>(), sd.dirty[0].as<u64>(),
+		                   sd.tflag.as<u32>(), tepoch, sd.touched.as<int32_t>(), &d_rc->nq[0], &d_rc->tcount, sd.q[0].as<int32_t>());
+		kt.stop();
+		par = 0;
+		nq_now = (u32)std::min<int64_t>(LC, (int64_t)U - base);
+		small_limit = (u32)std::max(0, opt.relax_small_limit);
+		// band width of the ordered rounds: a fraction of the mean weight (0: plain Jacobi rounds, everything at once)
+		band = T(0);
+		if (opt.relax_delta_div > 0) {
+			PGQ_TRY(ensure_weight_mean(c, ws));
+			band = weight_fraction<T>(c->w_mean, opt.relax_delta_div);
+		}
+		thr_val = band;
+		// "light edges first" (relax_light): the rounds run over weight-sorted lists under a cap on the edge weight that doubles
+		// phase by phase — early phases touch a few per cent of the edges and give every lane a tight bound on its destinations,
+		// later phases hardly relax anything (a vertex stops at the first edge whose weight cannot beat its lanes' bounds) — until
+		// it reaches the largest bound.  `light`: cheapest_device has left the sorted lists and a positive finite mean on the handle.
+		heavy = opt.relax_split != 0;
+		t_round = std::chrono::steady_clock::now();
+		wcap = light ? weight_fraction<T>(c->w_mean, std::max(1, opt.relax_light_div)) : T(0);
+		return PGQ_OK;
+	}
+	// few changed vertices: rounds loop on the device inside one workgroup (8-byte labels only: labels_fit_32)
+	int small_rounds() {
+		KernelTimer kt(st, K_RELAX);
+		hipLaunchKernelGGL(k_relax_small<T>, dim3(1), dim3(1024), 0, st, c->off, c->adj, (const T *)c->w, sd.dist.as<int64_t>(), sd.dirty[0].as<u64>(),
+		                   sd.dirty[1].as<u64>(), sd.q[0].as<int32_t>(), sd.q[1].as<int32_t>(), d_rc, par, small_limit, priv->qflag.as<u32>(), epoch + 1,
+		                   sd.tflag.as<u32>(), tepoch, sd.touched.as<int32_t>(), 4096); // (at most that many rounds per launch)
+		kt.stop();
+		PGQ_TRY(read_back(h_rc, d_rc, sizeof(RelaxCounters)));
+		epoch += h_rc->rounds + 1;
+		S.levels += h_rc->rounds;
+		par ^= (int)(h_rc->rounds & 1u);
+		nq_now = h_rc->nq[par];
+		return PGQ_OK;
+	}
+	int round() {
+		epoch++;
+		// one launch instead of five fills per round (2459 rounds per 4096-pair step on the weighted knows graph)
+		hipLaunchKernelGGL(k_round_reset, dim3(1), dim3(64), 0, st, d_rc, par ^ 1);
+		const long long thr_bits = band > T(0) ? __builtin_bit_cast(long long, thr_val) : (long long)0x7FFFFFFFFFFFFFFFll;
+		const RelaxRound<T> rr { priv, 0, par, c->off, light ? c->wadj : c->adj, light ? (const T *)c->wsorted : (const T *)c->w, tepoch, d_rc,
+		                         thr_bits, light ? 1 : 0, wcap, heavy };
+		KernelTimer kt(st, K_RELAX);
+		hipLaunchKernelGGL(k_lane_bounds<DT>, dim3((unsigned)std::min<int64_t>(blocks_for(hi - lo), 256)), dim3(256), 0, st, lo, hi,
+		                   ws->skey.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_rc->bound);
+		launch_relax<T, DT>(rr, 0, grid, nq_now);
+		if (heavy) launch_relax<T, DT>(rr, 1, grid, nq_now); // the long lists of the round, a chunk per wavefront
+		kt.stop();
+		PGQ_TRY(read_back(h_rc, d_rc, sizeof(RelaxCounters)));
+		if (trace) {
+			const auto t1 = std::chrono::steady_clock::now();
+			fprintf(stderr, "relax b=%d round=%lld cap=%g nq=%u expanded=%u heavy=%u/%u edges=%llu next=%u us=%.1f\n", b, (long long)S.levels,
+			        (double)wcap, nq_now, h_rc->relaxed_vertices, (u32)(h_rc->heavy >> 32), (u32)h_rc->heavy,
+			        (unsigned long long)h_rc->relaxed_edges, h_rc->nq[par ^ 1], std::chrono::duration<double, std::micro>(t1 - t_round).count());
+			t_round = t1;
+		}
+		S.levels++;
+		par ^= 1;
+		nq_now = h_rc->nq[par];
+		return PGQ_OK;
+	}
+	// The phase has reached its fixpoint.  Done when no heavier edge can matter: the cap has reached the largest bound of a
+	// lane (the bounds of the last round: labels only got smaller since) or the largest weight.  Otherwise the cap doubles.
+	int next_phase() {
+		T max_bound = T(0);
+		bool unbounded = false;
+		for (const long long bits : h_rc->bound) {
+			if (bits >= (long long)Inf<T>::bits) unbounded = true;
+			if (__builtin_bit_cast(T, bits) > max_bound) max_bound = __builtin_bit_cast(T, bits);
+		}
+		// (negated comparisons: a cap that is NaN or inf ends the search like one that has reached the largest weight)
+		if (!(wcap < __builtin_bit_cast(T, c->w_max_bits)) || (!unbounded && !(wcap < max_bound))) return PGQ_OK;
+		if constexpr (std::is_same<T, double>::value) wcap = wcap + wcap;
+		else wcap = wcap > std::numeric_limits<int64_t>::max() / 2 ? std::numeric_limits<int64_t>::max() : wcap + wcap;
+		PGQ_HIP_TRY(hipMemsetAsync(&d_rc->nq[par], 0, 4, st));
+		hipLaunchKernelGGL(k_redirty, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, sd.touched.as<int32_t>(), &d_rc->tcount,
+		                   sd.dirty[par].as<u64>(), sd.q[par].as<int32_t>(), &d_rc->nq[par]);
+		PGQ_TRY(read_back(h_rc, d_rc, sizeof(RelaxCounters)));
+		nq_now = h_rc->nq[par];
+		return PGQ_OK;
+	}
+	void next_band() { // an empty band is skipped: straight to the smallest label left
+		if (!(band > T(0))) return;
+		thr_val = thr_val + band;
+		if (h_rc->relaxed_vertices == 0 && h_rc->min_deferred != 0x7F7F7F7F7F7F7F7Fll)
+			thr_val = std::max(thr_val, __builtin_bit_cast(T, h_rc->min_deferred) + band);
+	}
+	void finish_batch() {
+		hipLaunchKernelGGL(k_cheapest_results<DT>, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(),
+		                   ws->sidx.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_out, d_ok);
+		end_batch<T, DT>(h_rc->relaxed_edges, 1, d_rc);
+	}
+};
+
+// ---- general graphs, about one destination per source: both ends at once (BidirBatches, round 6) ------------------
 // The batched relaxation above gives a lane the distances from its source to EVERY vertex under the lane's bound: on the
 // weighted knows graph (weights 1..999, mean degree 89) that is most of the graph per source, ~14 expansions per vertex and
 // batch — 0.64 s per 4096 pairs, `k_relax` 94 % of it.  A single pair needs the ball of half the distance around each end:
 // balls grow by e^(0.089 r) there, so two of radius D / 2 hold a few hundred settled vertices where one of radius D holds
 // most of V.  Here a lane is one (src, dst) PAIR and a batch runs the same kernel from both ends — forward over the
-// weight-sorted out-lists into `dist`, backward over the weight-sorted in-lists into `dist_b`:
+// weight-sorted out-lists into `dist`, backward over the weight-sorted in-lists into the backward side's labels (Workspace::relax[1]):
 //     mu[l]  = the best src -> dst length seen (the bound BOTH sides prune with; INF at first)
 //     a round = k_relax forward, then k_relax backward, each expanding what is dirty with a label below the common cap C
 //               (the kernel's threshold, read from the device) and below mu[l], labelling what gets under min(mu[l], 2 C) —
@@ -1499,15 +1552,6 @@ static int relax_batches(pgq_csr *c, Workspace *ws, Workspace *priv, int b0, int
 // them a rescan of ~400 K labelled vertices per side.  Both variants move a 64-lane label row per relaxed edge for the
 // one or two lanes that need it; that row traffic, not the number of edges, is what a round costs.  On
 // graphs whose balls stay small (bounded degree, road-like) the two-ended search is the cheaper one; kept, tested, optional.
-struct BiBlock {
-	RelaxCounters rc[2]; // forward / backward: k_relax's round counters
-	long long mu[64];    // per lane: best src -> dst length so far = both sides' bound; 0 once the lane is finished
-	long long res[64];   // per lane: the answer (INF: no path)
-	u32 alive[2][64];    // per side and lane: a labelled vertex was left unexpanded (over the cap) this round
-	u32 done[64];
-	long long cap, step;
-	u32 active, phases;
-};
 
 template <typename DT>
 __global__ __launch_bounds__(64) void k_bidir_init(int64_t lo, int nl, const int32_t *__restrict__ ssrc, const int32_t *__restrict__ sdst,
@@ -1615,154 +1659,101 @@ static int ensure_reverse_sorted(pgq_csr *c, Workspace *ws) {
 }
 
 // The pair batches b0, b0 + bstride, ... < nb of a call: batch b = the sorted rows [64 b, 64 b + 64) of the R rows that need a
-// search (`ws`: sorted rows, read-only; `priv`: everything a batch writes, and the stream — like relax_batches).
-template <typename DT>
-static int relax_batches_bidir(pgq_csr *c, Workspace *ws, Workspace *priv, int b0, int bstride, int nb, int64_t R, int64_t *d_out,
-                               uint8_t *d_ok) {
+// search (`ws`: sorted rows, read-only; `priv`: everything a batch writes, and the stream — like RelaxBatches).
+template <typename DT> class BidirBatches : RelaxWorker {
 	using T = int64_t;
-	hipStream_t st = priv->stream;
-	const int64_t V = std::max<int64_t>(c->V, 1);
-	const int64_t inf_bits = Inf<T>::bits;
-	const DT inf_label = (DT)Lab<DT>::unlabelled(inf_bits);
-	pgq_stats_t &S = tstats().s;
-	const size_t cells = (size_t)V * LC;
-	const int type_tag = sizeof(DT) == 4 ? 3 : 1;
-	DevBuf *dist[2] = { &priv->dist, &priv->dist_b };
-	DevBuf *dirty[2][2] = { { &priv->dirty[0], &priv->dirty[1] }, { &priv->dirty_b[0], &priv->dirty_b[1] } };
-	DevBuf *qbuf[2][2] = { { &priv->qbuf[0], &priv->qbuf[1] }, { &priv->qbuf_b[0], &priv->qbuf_b[1] } };
-	DevBuf *touched[2] = { &priv->touched, &priv->touched_b }, *tflag[2] = { &priv->tflag, &priv->tflag_b };
-	int64_t *dist_V[2] = { &priv->dist_V, &priv->dist_b_V };
-	int *dist_tag[2] = { &priv->dist_lanes, &priv->dist_b_lanes };
-	for (int s = 0; s < 2; s++) {
-		const bool fresh = dist[s]->cap < cells * sizeof(DT) || *dist_V[s] != c->V || *dist_tag[s] != type_tag;
-		*dist_V[s] = -1; // stays invalid if we bail out half-way; restored at the end
-		PGQ_TRY(dist[s]->reserve(cells * sizeof(DT)));
-		for (int k = 0; k < 2; k++) {
-			PGQ_TRY(dirty[s][k]->reserve((size_t)V * 8));
-			PGQ_TRY(qbuf[s][k]->reserve((size_t)V * 4));
+public:
+	BidirBatches(const RelaxWorker &w, int64_t R) : RelaxWorker(w), R(R) {}
+
+	int run(int b0, int bstride) {
+		PGQ_TRY((prepare<T, DT>(2)));
+		PGQ_TRY(priv->bi_block.reserve(sizeof(BiBlock)));
+		if (!priv->h_bi) PGQ_HIP_TRY(hipHostMalloc(&priv->h_bi, sizeof(BiBlock)));
+		bb = priv->bi_block.as<BiBlock>();
+		hb = static_cast<const BiBlock *>(priv->h_bi);
+		for (b = b0; b < nb; b += bstride) {
+			lo = (int64_t)b * LC;
+			nl = (int)std::min<int64_t>(LC, R - lo);
+			if (nl <= 0) continue;
+			PGQ_TRY(start_batch());
+			for (int64_t r = 0;; r++) {
+				if (r > (int64_t)1 << 22) return fail(PGQ_ERR_HIP, "internal error: the bidirectional relaxation does not terminate");
+				PGQ_TRY(round(r));
+				if (hb->active == 0) break;
+				if (hb->phases != phases_seen) redirty_sides();
+			}
+			PGQ_TRY(finish_batch());
 		}
-		PGQ_TRY(touched[s]->reserve((size_t)V * 4));
-		PGQ_TRY(tflag[s]->reserve((size_t)V * 4));
-		if (fresh) {
-			if constexpr (sizeof(DT) == 4) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, dist[s]->template as<int32_t>(), (int64_t)cells, (int32_t)inf_label);
-			else hipLaunchKernelGGL(k_fill64, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, dist[s]->template as<int64_t>(), (int64_t)cells, inf_bits);
-		}
-		for (int k = 0; k < 2; k++) PGQ_HIP_TRY(hipMemsetAsync(dirty[s][k]->p, 0, (size_t)V * 8, st));
-		PGQ_HIP_TRY(hipMemsetAsync(tflag[s]->p, 0, (size_t)V * 4, st));
+		return settle<T, DT>(2);
 	}
-	PGQ_TRY(priv->hv.reserve((size_t)V * 4));
-	PGQ_TRY(priv->hmask.reserve((size_t)V * 8));
-	PGQ_TRY(priv->hstart.reserve((size_t)V * 4));
-	PGQ_TRY(priv->hmap.reserve((size_t)(c->E / 64 + V) * 4));
-	PGQ_TRY(priv->bi_block.reserve(sizeof(BiBlock)));
-	if (!priv->h_bi) PGQ_HIP_TRY(hipHostMalloc(&priv->h_bi, sizeof(BiBlock)));
-	BiBlock *bb = priv->bi_block.as<BiBlock>();
-	const BiBlock *hb = static_cast<const BiBlock *>(priv->h_bi);
-	unsigned grid;
-	{
-		static std::mutex grid_lock;
-		static unsigned grid_cached[2][64] = {};
-		std::lock_guard<std::mutex> g(grid_lock);
-		int dev = 0;
-		PGQ_HIP_TRY(hipGetDevice(&dev));
-		unsigned &gc = grid_cached[sizeof(DT) == 4 ? 0 : 1][dev & 63];
-		if (!gc) {
-			int per_cu = 0, cus = 0;
-			PGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax<T, DT>, 256, 0));
-			PGQ_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-			gc = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
-		}
-		grid = gc;
-	}
-	const Options &opt = options();
+private:
+	const int64_t R;
 	// (the mean of a shortest path's edges is far below the mean weight: the caps are fractions of twice the mean)
-	const long long cap0 = std::max<long long>(1, (long long)(2.0 * c->w_mean / std::max(1, opt.relax_bidir_c0_div)));
-	const long long step = std::max<long long>(1, (long long)(2.0 * c->w_mean / std::max(1, opt.relax_bidir_step_div)));
-	const int64_t *xoff[2] = { c->off, c->roff };
-	const int32_t *xadj[2] = { c->wadj, c->rwadj };
-	const T *xw[2] = { (const T *)c->wsorted, (const T *)c->rwsorted };
-	static const bool trace = getenv("PGQ_RELAX_TRACE") != nullptr;
-	u32 tepoch = 0;
-	for (int b = b0; b < nb; b += bstride) {
-		const int64_t lo = (int64_t)b * LC;
-		const int nl = (int)std::min<int64_t>(LC, R - lo);
-		if (nl <= 0) continue;
+	const long long cap0 = weight_fraction<T>(2.0 * c->w_mean, std::max(1, options().relax_bidir_c0_div));
+	const long long step = weight_fraction<T>(2.0 * c->w_mean, std::max(1, options().relax_bidir_step_div));
+	RelaxSide *const side = priv->relax;
+	BiBlock *bb = nullptr;       // both sides' counters, the pairs' bounds and answers, the cap
+	const BiBlock *hb = nullptr; // ... and its pinned copy of the last round
+	int nl = 0, par[2] = { 0, 0 }; // from here on: the batch's (start_batch)
+	int64_t lo = 0;
+	u32 nq[2] = { 0, 0 }, phases_seen = 0;
+
+	int start_batch() {
 		S.batches++;
 		tepoch++;
 		PGQ_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(BiBlock), st));
-		{
-			KernelTimer kt(st, K_PREP);
-			hipLaunchKernelGGL(k_bidir_init<DT>, dim3(1), dim3(64), 0, st, lo, nl, ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), dist[0]->template as<DT>(),
-			                   dist[1]->template as<DT>(), dirty[0][0]->template as<u64>(), dirty[1][0]->template as<u64>(), tflag[0]->template as<u32>(),
-			                   tflag[1]->template as<u32>(), tepoch, touched[0]->template as<int32_t>(), touched[1]->template as<int32_t>(),
-			                   qbuf[0][0]->template as<int32_t>(), qbuf[1][0]->template as<int32_t>(), bb, cap0, step, (long long)inf_bits);
-			kt.stop();
-		}
-		int par[2] = { 0, 0 };
-		u32 nq[2] = { (u32)nl, (u32)nl }, phases_seen = 0;
-		for (int64_t round = 0;; round++) {
-			if (round > (int64_t)1 << 22) return fail(PGQ_ERR_HIP, "internal error: the bidirectional relaxation does not terminate");
-			hipLaunchKernelGGL(k_bidir_round_reset, dim3(1), dim3(64), 0, st, bb, par[0] ^ 1, par[1] ^ 1);
-			{
-				KernelTimer kt(st, K_RELAX);
-				for (int s = 0; s < 2; s++) {
-					if (nq[s] == 0) continue;
-					RelaxCounters *rc = &bb->rc[s];
-					for (int hp = 0; hp < 2; hp++)
-						hipLaunchKernelGGL((k_relax<T, DT>), dim3(hp ? grid : std::min(grid, std::max(1u, (nq[s] + 3) / 4))), dim3(256), 0, st, xoff[s], xadj[s], xw[s],
-						                   dist[s]->template as<DT>(), dirty[s][par[s]]->template as<u64>(), dirty[s][par[s] ^ 1]->template as<u64>(),
-						                   qbuf[s][par[s]]->template as<int32_t>(), &rc->nq[par[s]], qbuf[s][par[s] ^ 1]->template as<int32_t>(),
-						                   &rc->nq[par[s] ^ 1], tflag[s]->template as<u32>(), tepoch, touched[s]->template as<int32_t>(), &rc->tcount,
-						                   &rc->relaxed_edges, (long long)0, (const long long *)bb->mu, &rc->min_deferred, &rc->relaxed_vertices, 1,
-						                   std::numeric_limits<T>::max(), hp, &rc->heavy, priv->hv.as<int32_t>(), priv->hmask.as<u64>(),
-						                   priv->hstart.as<u32>(), priv->hmap.as<u32>(), (const DT *)dist[s ^ 1]->template as<DT>(), bb->mu, bb->alive[s],
-						                   (const long long *)&bb->cap);
-				}
-				hipLaunchKernelGGL(k_bidir_phase_end, dim3(1), dim3(64), 0, st, bb);
-				kt.stop();
-			}
-			PGQ_HIP_TRY(hipMemcpyAsync(priv->h_bi, bb, sizeof(BiBlock), hipMemcpyDeviceToHost, st));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-			S.levels++;
-			if (trace)
-				fprintf(stderr, "bidir b=%d round=%lld cap=%lld phases=%u nq=%u/%u expanded=%u/%u next=%u/%u active=%u edges=%llu/%llu\n", b, (long long)round,
-				        hb->cap, hb->phases, nq[0], nq[1], hb->rc[0].relaxed_vertices, hb->rc[1].relaxed_vertices, hb->rc[0].nq[par[0] ^ 1],
-				        hb->rc[1].nq[par[1] ^ 1], hb->active, (unsigned long long)hb->rc[0].relaxed_edges, (unsigned long long)hb->rc[1].relaxed_edges);
-			for (int s = 0; s < 2; s++) {
-				if (nq[s] == 0) continue; // (nothing was launched: the side's queues and parity stay as they are)
-				par[s] ^= 1;
-				nq[s] = hb->rc[s].nq[par[s]];
-			}
-			if (hb->active == 0) break;
-			if (hb->phases != phases_seen) { // a higher cap: every labelled vertex again, over the longer prefix of its list
-				phases_seen = hb->phases;
-				for (int s = 0; s < 2; s++) {
-					hipLaunchKernelGGL(k_redirty, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, touched[s]->template as<int32_t>(), &bb->rc[s].tcount,
-					                   dirty[s][par[s]]->template as<u64>(), qbuf[s][par[s]]->template as<int32_t>(), &bb->rc[s].nq[par[s]]);
-					nq[s] = hb->rc[s].tcount;
-				}
-			}
-		}
-		const u64 edges = hb->rc[0].relaxed_edges + hb->rc[1].relaxed_edges;
-		S.edges_scanned += (int64_t)edges;
-		S.algo_bytes[K_RELAX] += (double)edges * (4.0 + 8.0 + 2.0 * (double)sizeof(DT) * LC);
-		hipLaunchKernelGGL(k_bidir_results, dim3(1), dim3(64), 0, st, lo, nl, ws->sidx.as<u32>(), bb, (long long)inf_bits, d_out, d_ok);
-		for (int s = 0; s < 2; s++)
-			hipLaunchKernelGGL(k_reset_touched<DT>, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, touched[s]->template as<int32_t>(), &bb->rc[s].tcount,
-			                   dist[s]->template as<DT>(), inf_label);
-		// what the finished lanes left dirty: the next batch starts from clean words
-		for (int s = 0; s < 2; s++)
-			for (int k = 0; k < 2; k++) PGQ_HIP_TRY(hipMemsetAsync(dirty[s][k]->p, 0, (size_t)V * 8, st));
+		KernelTimer kt(st, K_PREP);
+		hipLaunchKernelGGL(k_bidir_init<DT>, dim3(1), dim3(64), 0, st, lo, nl, ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), side[0].dist.as<DT>(),
+		                   side[1].dist.as<DT>(), side[0].dirty[0].as<u64>(), side[1].dirty[0].as<u64>(), side[0].tflag.as<u32>(), side[1].tflag.as<u32>(), tepoch,
+		                   side[0].touched.as<int32_t>(), side[1].touched.as<int32_t>(), side[0].q[0].as<int32_t>(), side[1].q[0].as<int32_t>(), bb, cap0, step, (long long)Inf<T>::bits);
+		kt.stop();
+		par[0] = par[1] = 0;
+		nq[0] = nq[1] = (u32)nl;
+		phases_seen = 0;
+		return PGQ_OK;
 	}
-	PGQ_HIP_TRY(hipStreamSynchronize(st));
-	KernelTimer::flush();
-	for (int s = 0; s < 2; s++) {
-		*dist_V[s] = c->V; // every touched row is back at INF
-		*dist_tag[s] = type_tag;
+	// k_relax forward, then backward, each with its heavy pass; then the phase's book-keeping on the device
+	int round(int64_t r) {
+		hipLaunchKernelGGL(k_bidir_round_reset, dim3(1), dim3(64), 0, st, bb, par[0] ^ 1, par[1] ^ 1);
+		KernelTimer kt(st, K_RELAX);
+		for (int s = 0; s < 2; s++) {
+			if (nq[s] == 0) continue;
+			// forward over the weight-sorted out-lists, backward over the weight-sorted in-lists
+			const RelaxRound<T> rr { priv, s, par[s], s ? c->roff : c->off, s ? c->rwadj : c->wadj, (const T *)(s ? c->rwsorted : c->wsorted),
+			                         tepoch, &bb->rc[s], 0, 1, std::numeric_limits<T>::max(), true, bb };
+			for (int hp = 0; hp < 2; hp++) launch_relax<T, DT>(rr, hp, grid, nq[s]);
+		}
+		hipLaunchKernelGGL(k_bidir_phase_end, dim3(1), dim3(64), 0, st, bb);
+		kt.stop();
+		PGQ_TRY(read_back(priv->h_bi, bb, sizeof(BiBlock)));
+		S.levels++;
+		if (trace)
+			fprintf(stderr, "bidir b=%d round=%lld cap=%lld phases=%u nq=%u/%u expanded=%u/%u next=%u/%u active=%u edges=%llu/%llu\n", b, (long long)r,
+			        hb->cap, hb->phases, nq[0], nq[1], hb->rc[0].relaxed_vertices, hb->rc[1].relaxed_vertices, hb->rc[0].nq[par[0] ^ 1],
+			        hb->rc[1].nq[par[1] ^ 1], hb->active, (unsigned long long)hb->rc[0].relaxed_edges, (unsigned long long)hb->rc[1].relaxed_edges);
+		for (int s = 0; s < 2; s++) {
+			if (nq[s] == 0) continue; // (nothing was launched: the side's queues and parity stay as they are)
+			par[s] ^= 1;
+			nq[s] = hb->rc[s].nq[par[s]];
+		}
+		return PGQ_OK;
 	}
-	return PGQ_OK;
-}
+	void redirty_sides() { // a higher cap: every labelled vertex again, over the longer prefix of its list
+		phases_seen = hb->phases;
+		for (int s = 0; s < 2; s++) {
+			hipLaunchKernelGGL(k_redirty, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, side[s].touched.as<int32_t>(), &bb->rc[s].tcount,
+			                   side[s].dirty[par[s]].as<u64>(), side[s].q[par[s]].as<int32_t>(), &bb->rc[s].nq[par[s]]);
+			nq[s] = hb->rc[s].tcount;
+		}
+	}
+	int finish_batch() {
+		hipLaunchKernelGGL(k_bidir_results, dim3(1), dim3(64), 0, st, lo, nl, ws->sidx.as<u32>(), bb, (long long)Inf<T>::bits, d_out, d_ok);
+		end_batch<T, DT>(hb->rc[0].relaxed_edges + hb->rc[1].relaxed_edges, 2, bb->rc);
+		for (int s = 0; s < 2; s++) // what the finished lanes left dirty: the next batch starts from clean words
+			for (DevBuf &d : side[s].dirty) PGQ_HIP_TRY(hipMemsetAsync(d.p, 0, Vn * 8, st));
+		return PGQ_OK;
+	}
+};
 
 template <typename T>
 static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
@@ -1794,12 +1785,13 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 		const size_t per_worker = (size_t)std::max<int64_t>(c->V, 1) * (LC * 8 + 64) + (size_t)(c->E / 64) * 4;
 		workers = (int)std::min<size_t>((size_t)workers, 1 + free_b / 2 / per_worker);
 	}
-	// decided once for the whole call, handed to every worker (the weight-sorted copy above has left the mean and the largest
-	// weight on the handle; a mean that is not a positive finite number gives no first cap: plain rounds)
+	// `light` (and with it the label width DT) is decided ONCE, here, and handed to every worker: a concurrent pgq_set_option
+	// between two evaluations used to leave a worker with 4-byte labels outside the light-edges-first path (an "internal error"
+	// return).  The weight-sorted copy above has left the mean on the handle; one that is not positive and finite: plain rounds.
 	const bool light = light_edges_first(c) && c->wadj && c->w_mean > 0 && c->w_mean < 1e300;
 	const bool narrow = light && labels_fit_32<T>(c);
 	// about one destination per source (a list of pairs, not a cross product): every row is a lane of its own, searched from
-	// both ends (relax_batches_bidir); many destinations per source share their source's lane as before
+	// both ends (BidirBatches); many destinations per source share their source's lane as before
 	const int64_t R = bs[nb]; // the rows that need a search (sorted by source; trivial and NULL rows behind them)
 	bool bidir = false;
 	if constexpr (std::is_same<T, int64_t>::value)
@@ -1814,12 +1806,12 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 		}
 	}
 	auto run_relax = [&](Workspace *priv, int b0, int bstride) -> int {
+		const RelaxWorker w { c, ws, priv, nb_run, d_out, d_ok };
 		if constexpr (std::is_same<T, int64_t>::value) {
-			if (bidir) return narrow ? relax_batches_bidir<int32_t>(c, ws, priv, b0, bstride, nb_run, R, d_out, d_ok)
-			                         : relax_batches_bidir<int64_t>(c, ws, priv, b0, bstride, nb_run, R, d_out, d_ok);
-			if (narrow) return relax_batches<T, int32_t>(c, ws, priv, b0, bstride, nb, U, d_out, d_ok, light);
+			if (bidir) return narrow ? BidirBatches<int32_t>(w, R).run(b0, bstride) : BidirBatches<int64_t>(w, R).run(b0, bstride);
+			if (narrow) return RelaxBatches<T, int32_t>(w, U, light).run(b0, bstride);
 		}
-		return relax_batches<T, int64_t>(c, ws, priv, b0, bstride, nb, U, d_out, d_ok, light);
+		return RelaxBatches<T, int64_t>(w, U, light).run(b0, bstride);
 	};
 	int rc = PGQ_OK;
 	if (workers == 1) {

@@ -90,7 +90,7 @@ struct Options {
 	int relax_light_min_degree = 8; // relax_light = 1: only CSRs with at least this many edges per vertex (2: always)
 	int relax_light_div = 4;  // first cap = mean weight / this
 	int relax_bidir = 0;      // int64 weights, light-edges-first graphs, about one destination per source: every lane a (src, dst) pair
-	                          // searched from both ends under a common distance cap (relax_batches_bidir).  Bit-exact in the tests; OFF as
+	                          // searched from both ends under a common distance cap (BidirBatches).  Bit-exact in the tests; OFF as
 	                          // shipped: on the weighted knows graph the two half-distance balls already hold the hubs — 30 M relaxed edges
 	                          // per 64 pairs against 40 M one-sided, but 83 rounds instead of 35: 232 ms per 512 pairs against 89
 	int relax_bidir_rows = 2; // ... when the call has at most this many rows per distinct source

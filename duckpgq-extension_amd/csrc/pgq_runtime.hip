@@ -587,11 +587,11 @@ Workspace::~Workspace() {
 	if (h_bstart) (void)hipHostFree(h_bstart);
 	for (DevBuf *b : { &seen, &qbuf[0], &qbuf[1], &qflag, &counters, &flag, &rank, &usrc, &key, &idx, &skey,
 	                   &sidx, &ssrc, &sdst, &sres, &soff, &sort_tmp, &scan_tmp, &bstart, &levels_tab, &child, &in_src,
-	                   &in_dst, &out_len, &out_off, &dist, &dirty[0], &dirty[1], &touched, &tflag, &out_val, &out_ok, &lane_sums, &ste, &def_src, &def_dst, &def_len,
+	                   &in_dst, &out_len, &out_off, &out_val, &out_ok, &lane_sums, &ste, &def_src, &def_dst, &def_len,
 	                   &def_idx, &def_off, &def_ent, &cbits, &cbbase, &cmeta, &cwords, &lblk, &lrec, &meet_cnt, &meet_rec, &meet_poff, &meet_maps, &meet_trace,
-	                   &wb_scratch, &hv, &hmask, &hstart, &hmap, &route_dec, &ball_segs, &ball_trace, &sort_src, &sort_dst, &sort_out, &dist_b, &dirty_b[0], &dirty_b[1], &qbuf_b[0], &qbuf_b[1],
-	                   &touched_b, &tflag_b, &bi_block, &dpart })
+	                   &wb_scratch, &hv, &hmask, &hstart, &hmap, &route_dec, &ball_segs, &ball_trace, &sort_src, &sort_dst, &sort_out, &bi_block, &dpart })
 		b->release();
+	for (RelaxSide &s : relax) s.release();
 	for (auto *v : { &levels, &pool })
 		for (auto &l : *v) {
 			l->buf.release();

@@ -268,14 +268,26 @@ struct MeetPinned {
 	u32 sample_go;       // the sampled decision's verdict + 1 (k_meet_decide alone, riding in k_meet4d, lane_ranks); 0: none taken
 };
 
+// One direction's search state of the batched relaxation (pgq_cheapest.hip): labels dist[V][64], the lanes of a vertex that
+// improved and the queues of such vertices by round parity, and every vertex a batch labelled (once, by flag).  Between calls
+// the labels are all "unlabelled" — a batch resets what it touched — for ONE (V, label type), or the array is filled whole.
+struct RelaxSide {
+	DevBuf dist, dirty[2], q[2], touched, tflag;
+	int64_t dist_V = -1; // -1: not to be trusted (new, or a call bailed out half-way)
+	int dist_tag = 0;    // relax_label_tag: 1 = int64 labels, 2 = double, 3 = 4-byte labels
+	// before a worker's first batch (pgq_cheapest.hip, by its fill kernels); dist_V stays invalid until settle()
+	template <typename DT> int prepare(int64_t V, int type_tag, DT inf_label, hipStream_t st);
+	void settle(int64_t V, int type_tag) { dist_V = V, dist_tag = type_tag; } // behind the last batch's k_reset_touched, waited for
+	void release() { for (DevBuf *b : { &dist, &dirty[0], &dirty[1], &q[0], &q[1], &touched, &tflag }) b->release(); }
+};
+
 struct Workspace {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev_block = nullptr; // blocking event of wait_stream (created when the process first has many calls in flight)
 	int device = 0; // where its buffers live (workspaces are pooled per device)
 	DevBuf seen, qbuf[2], qflag, counters, flag, rank, usrc, key, idx, skey, sidx, ssrc, sdst, sres, soff,
-	    sort_tmp, scan_tmp, bstart, levels_tab, child, in_src, in_dst, out_len, out_off, dist, dirty[2], touched,
-	    tflag, out_val, out_ok, lane_sums, ste, def_src, def_dst, def_len, def_idx, def_off, def_ent, cbits, cbbase, cmeta, cwords, lblk, lrec, meet_cnt, meet_rec, meet_poff, meet_maps, meet_trace, wb_scratch, hv, hmask, hstart, hmap,
-	    route_dec, ball_segs, ball_trace, sort_src, sort_dst, sort_out, dist_b, dirty_b[2], qbuf_b[2], touched_b, tflag_b, bi_block, dpart; // [kOpenGrid][WD + 1]: every workgroup's open-lane words + open-row count of the level's detection / probe
+	    sort_tmp, scan_tmp, bstart, levels_tab, child, in_src, in_dst, out_len, out_off, out_val, out_ok, lane_sums, ste, def_src, def_dst, def_len, def_idx, def_off, def_ent, cbits, cbbase, cmeta, cwords, lblk, lrec, meet_cnt, meet_rec, meet_poff, meet_maps, meet_trace, wb_scratch, hv, hmask, hstart, hmap,
+	    route_dec, ball_segs, ball_trace, sort_src, sort_dst, sort_out, bi_block, dpart; // [kOpenGrid][WD + 1]: every workgroup's open-lane words + open-row count of the level's detection / probe
 	std::vector<std::unique_ptr<LevelBuf>> levels; // shortestpath: one per level
 	std::vector<std::unique_ptr<LevelBuf>> pool;   // otherwise: [0], [1] sparse pool, [2], [3] dense pool
 	bool pool_trusted = false;                     // the last batch ended normally: the sparse pool's dirty flags are true
@@ -295,14 +307,8 @@ struct Workspace {
 	size_t h_io_cap = 0;
 	int64_t *h_bstart = nullptr;
 	size_t h_bstart_cap = 0;
-	u32 epoch = 0;
-	// cheapest path: which (V, lanes, type) the dist array is currently initialised for
-	int64_t dist_V = -1;
-	int dist_lanes = 0;
-	int64_t dist_b_V = -1; // the same for the backward side's labels (relax_batches_bidir)
-	int dist_b_lanes = 0;
+	RelaxSide relax[2];    // cheapest path: the forward (0) and the backward (1, BidirBatches) search state
 	void *h_bi = nullptr;  // pinned: the bidirectional relaxation's counter block, copied back once per round
-	u32 touch_epoch = 0;
 	~Workspace();
 };
 

@@ -865,7 +865,7 @@ def test_weighted_pair_search_bit_exact(delta_div):
 
 @pytest.mark.parametrize("labels32", [1, 0])
 def test_two_ended_relaxation_bit_exact(labels32):
-    # relax_batches_bidir (pgq_cheapest.hip): every lane a (src, dst) pair, k_relax from both ends under a common distance cap;
+    # BidirBatches (pgq_cheapest.hip): every lane a (src, dst) pair, k_relax from both ends under a common distance cap;
     # int64 weights, lists of pairs.  Caps: shipped, one-unit first cap / steps (a phase per label), one huge cap (a single phase)
     rng = np.random.default_rng(811 + labels32)
     pgq.set_option("relax_bidir", 1)

@@ -937,10 +937,10 @@ def test_source_centric_ball_rule_matches_bfs():
                         assert g == want, (trial, caps, int(ps[a]), int(pd[a + k]), g, want)
 
 
-# ---- the two-ended batched relaxation (relax_batches_bidir, pgq_cheapest.hip), one lane ---------------------------------
+# ---- the two-ended batched relaxation (BidirBatches, pgq_cheapest.hip), one lane ---------------------------------
 
 def two_ended_model(V, off, adj, w, roff, radj, rw, s, t, cap0, step, rng):
-    """One (src, dst) pair under relax_batches_bidir's schedule: a round = one launch forward, then one backward; a launch
+    """One (src, dst) pair under BidirBatches's schedule: a round = one launch forward, then one backward; a launch
     reads the pair's bound mu ONCE (its start), expands what is dirty with a label below min(cap, mu), walks the expanded
     vertex's weight-sorted list while the candidate stays below min(mu, 2 cap) (a candidate the cap cut, not mu, keeps the
     side alive), offers label + other side's label for every vertex it expands; the offers land at the launch's end.  A phase
