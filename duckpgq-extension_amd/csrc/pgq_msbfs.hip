@@ -1596,8 +1596,7 @@ static int lane_ranks(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src
                       const std::function<int()> &pre_wait = nullptr) {
 	hipStream_t st = ws->stream;
 	const int64_t V = c->V;
-	PGQ_TRY(ws->flag.reserve((size_t)(V + 1) * 4));
-	PGQ_TRY(ws->rank.reserve((size_t)(V + 1) * 4));
+	for (DevBuf *b : { &ws->flag, &ws->rank }) PGQ_TRY(b->reserve((size_t)(V + 1) * 4));
 	PGQ_TRY(ws->usrc.reserve((size_t)std::max<int64_t>(V, 1) * 4));
 	for (DevBuf *b : { &ws->skey, &ws->ssrc, &ws->sdst, &ws->sres }) PGQ_TRY(b->reserve((size_t)n * 4));
 	PGQ_TRY(ws->soff.reserve((size_t)n * 8));
@@ -1666,49 +1665,18 @@ int prepare_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, co
 	return lane_rows_sorted(c, ws, n, d_src, d_dst, dst_rule, kTrivial, kNoLane, 32);
 }
 
-int batch_bounds(Workspace *ws, int64_t n, int64_t L, int nb) {
-	hipStream_t st = ws->stream;
-	PGQ_TRY(reserve_bstart(ws, nb));
-	{
-		KernelTimer kt(st, K_PREP);
-		hipLaunchKernelGGL(k_batch_bounds, dim3(blocks_for(nb + 3)), dim3(256), 0, st, ws->skey.as<u32>(), n, (u32)L,
-		                   nb, kTrivial, kNoLane, ws->bstart.as<int64_t>());
-		kt.stop();
-	}
-	PGQ_HIP_TRY(hipMemcpyAsync(ws->h_bstart, ws->bstart.p, (size_t)(nb + 3) * 8, hipMemcpyDeviceToHost, st));
-	PGQ_WAIT(st);
-	return PGQ_OK;
+// Stage 2, rows in place: every row's lane id, endpoints and result word, in the caller's order
+static void pair_rows(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, bool dst_rule) {
+	KernelTimer kt(ws->stream, K_PREP);
+	hipLaunchKernelGGL(k_pair_rows, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, d_src, d_dst, ws->rank.as<u32>(), c->off, c->roff, dst_rule ? 1 : 0, c->V,
+	                   ws->skey.as<u32>(), ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), ws->sres.as<int32_t>());
+	kt.stop();
+	// ids read again + the source's rank and degree (16 + 12 B), four 4-byte arrays written
+	tstats().s.algo_bytes[K_PREP] += (double)n * 44.0;
 }
-
-// The BFS driver's stage 2.  One batch (the distinct sources fit 64 x wd lanes) and nothing downstream that needs the
-// trivial rows as a range (paths): the rows are NOT permuted (k_pair_rows; *identity = true, sidx is not written) and
-// nothing is waited for.  Otherwise: sorted by lane over the bits the keys really have (the sentinels sit right behind
-// the last batch: nb x L and nb x L + 1), bounds computed and fetched (one wait).
-static int lane_rows_bfs(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, bool dst_rule,
-                         int64_t L, int nb, bool may_skip_sort, bool *identity, bool rows_done_ahead = false) {
+// k_batch_bounds under these sentinels, fetched into ws->h_bstart (one wait)
+static int fetch_bounds(Workspace *ws, int64_t n, int64_t L, int nb, u32 key_trivial, u32 key_nolane) {
 	hipStream_t st = ws->stream;
-	PGQ_TRY(reserve_bstart(ws, nb));
-	*identity = may_skip_sort && nb <= 1;
-	if (*identity && rows_done_ahead) { // k_pair_rows ran in front of the lane assignment's wait (search_device)
-		ws->h_bstart[0] = 0;
-		for (int b = 1; b <= nb + 2; b++) ws->h_bstart[b] = n;
-		return PGQ_OK;
-	}
-	if (*identity) {
-		KernelTimer kt(st, K_PREP);
-		hipLaunchKernelGGL(k_pair_rows, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->rank.as<u32>(), c->off, c->roff, dst_rule ? 1 : 0, c->V,
-		                   ws->skey.as<u32>(), ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), ws->sres.as<int32_t>());
-		kt.stop();
-		// stage 2, rows in place: ids read again + the source's rank and degree (16 + 12 B), four 4-byte arrays written
-		tstats().s.algo_bytes[K_PREP] += (double)n * 44.0;
-		ws->h_bstart[0] = 0;
-		for (int b = 1; b <= nb + 2; b++) ws->h_bstart[b] = n; // batch 0 = every row; no trivial / NULL ranges
-		return PGQ_OK;
-	}
-	const u32 key_trivial = (u32)((int64_t)nb * L), key_nolane = key_trivial + 1; // nb x L <= U + L < 2^31 + 2^11
-	int bits = 1;
-	while (bits < 32 && (1ull << bits) <= (u64)key_nolane) bits++;
-	PGQ_TRY(lane_rows_sorted(c, ws, n, d_src, d_dst, dst_rule, key_trivial, key_nolane, bits));
 	{
 		KernelTimer kt(st, K_PREP);
 		hipLaunchKernelGGL(k_batch_bounds, dim3(blocks_for(nb + 3)), dim3(256), 0, st, ws->skey.as<u32>(), n, (u32)L, nb,
@@ -1717,6 +1685,32 @@ static int lane_rows_bfs(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_
 	}
 	PGQ_HIP_TRY(hipMemcpyAsync(ws->h_bstart, ws->bstart.p, (size_t)(nb + 3) * 8, hipMemcpyDeviceToHost, st));
 	PGQ_WAIT(st);
+	return PGQ_OK;
+}
+int batch_bounds(Workspace *ws, int64_t n, int64_t L, int nb) {
+	PGQ_TRY(reserve_bstart(ws, nb));
+	return fetch_bounds(ws, n, L, nb, kTrivial, kNoLane);
+}
+
+// The BFS driver's stage 2.  One batch (the distinct sources fit 64 x wd lanes) and nothing downstream that needs the
+// trivial rows as a range (paths): the rows are NOT permuted (k_pair_rows; *identity = true, sidx is not written) and
+// nothing is waited for.  Otherwise: sorted by lane over the bits the keys really have (the sentinels sit right behind
+// the last batch: nb x L and nb x L + 1), bounds computed and fetched (one wait).
+static int lane_rows_bfs(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, bool dst_rule,
+                         int64_t L, int nb, bool may_skip_sort, bool *identity, bool rows_done_ahead = false) {
+	PGQ_TRY(reserve_bstart(ws, nb));
+	*identity = may_skip_sort && nb <= 1;
+	if (*identity) {
+		if (!rows_done_ahead) pair_rows(c, ws, n, d_src, d_dst, dst_rule); // (else it ran in front of the lane assignment's wait: search_lanes)
+		ws->h_bstart[0] = 0;
+		for (int b = 1; b <= nb + 2; b++) ws->h_bstart[b] = n; // batch 0 = every row; no trivial / NULL ranges
+		return PGQ_OK;
+	}
+	const u32 key_trivial = (u32)((int64_t)nb * L), key_nolane = key_trivial + 1; // nb x L <= U + L < 2^31 + 2^11
+	int bits = 1;
+	while (bits < 32 && (1ull << bits) <= (u64)key_nolane) bits++;
+	PGQ_TRY(lane_rows_sorted(c, ws, n, d_src, d_dst, dst_rule, key_trivial, key_nolane, bits));
+	PGQ_TRY(fetch_bounds(ws, n, L, nb, key_trivial, key_nolane));
 	KernelTimer::flush();
 	return PGQ_OK;
 }
@@ -1803,16 +1797,17 @@ static constexpr int kMaxTeLevels = 1024;
 template <int WD>
 class LaneBatches {
 public:
-	LaneBatches(pgq_csr *c, Workspace *sh, Workspace *ws, int64_t n, int64_t U, bool with_paths, int64_t *d_child_ext,
-	            int64_t child_cap_ext, SearchOutput &outp)
-	    : c(c), sh(sh), ws(ws), outp(outp), n(n), U(U), with_paths(with_paths), d_child_ext(d_child_ext), child_cap_ext(child_cap_ext) {}
+	LaneBatches(pgq_csr *c, Workspace *sh, Workspace *ws, const SearchCall &call, int64_t U, SearchReport &rep)
+	    : c(c), sh(sh), ws(ws), ask(call.ask), rep(rep), n(call.n), U(U), with_paths(call.paths.has_value()),
+	      d_child_ext(with_paths ? call.paths->d_child_ext : nullptr), child_cap_ext(with_paths ? call.paths->child_cap_ext : 0) {}
+	bool deferred = false; // (out) a batch left stragglers marked in sh->sres: the caller's second pass
 
 	int run(int b0, int bstride) {
 		PGQ_TRY(ws->seen.reserve(words * 8));
 		for (DevBuf &q : ws->qbuf) PGQ_TRY(q.reserve((size_t)qcap * 8));
 		PGQ_TRY(ws->counters.reserve(sizeof(Counters)));
 		PGQ_TRY(ws->dpart.reserve((size_t)kOpenRep * WD * 8));
-		if (outp.want_te) {
+		if (ask.want_te) {
 			PGQ_TRY(ws->lane_sums.reserve((size_t)kMaxTeLevels * L * 8));
 			PGQ_TRY(sh->ste.reserve((size_t)n * 8));
 			PGQ_HIP_TRY(hipMemsetAsync(sh->ste.p, 0, (size_t)n * 8, st));
@@ -1839,7 +1834,8 @@ private:
 	// per call
 	pgq_csr *const c;
 	Workspace *const sh, *const ws;
-	SearchOutput &outp;
+	const SearchAsk &ask;
+	SearchReport &rep; // child_used / overflow: written by the one ordered worker of a call with paths
 	const int64_t n, U;
 	const bool with_paths;
 	int64_t *const d_child_ext; // the caller's buffer for the path lists, else sh->child
@@ -1857,14 +1853,14 @@ private:
 	// The destination probe answers a pair one expansion early; it costs one in-neighbour scan per open pair, so it is used
 	// while the batch has few pairs relative to the graph (not for cross products) and never in the traversed-edge
 	// accounting pass (which needs every level of every lane).  Whether a level is probed is decided per level (decide_level).
-	const bool use_probe = opt.probe && !outp.want_te;
+	const bool use_probe = opt.probe && !ask.want_te;
 	const bool lanes_ok = opt.lanes && c->rpk != nullptr;
 	// levels enqueued ahead of the host under the plan of the last batch of this width; paths keep every
 	// level's frontier and the accounting pass its per-level sums: they stay on the round trip per level
-	const bool spec_ok = opt.spec_levels && !with_paths && !outp.want_te;
+	const bool spec_ok = opt.spec_levels && !with_paths && !ask.want_te;
 	// iterativelength_within: level t answers the rows at distance t, so no level beyond the bound is launched — by the host's
 	// loop or from a plan — and what is open then keeps the NULL it started with; such a batch's levels are no plan for others
-	const int max_level = outp.max_hops >= 0 ? (int)std::min<int64_t>(outp.max_hops, 1 << 30) : INT_MAX;
+	const int max_level = ask.max_hops >= 0 ? (int)std::min<int64_t>(ask.max_hops, 1 << 30) : INT_MAX;
 	const int plan_slot = WD == 1 ? 0 : (WD == 2 ? 1 : (WD == 4 ? 2 : (WD == 8 ? 3 : (WD == 16 ? 4 : 5))));
 	const LevelRule rule { (double)E, (double)V, opt.push_div, opt.sparse_below, WD, opt.force_mode, opt.force_pull,
 	                       opt.probe_always, use_probe ? 1 : 0 };
@@ -1932,7 +1928,7 @@ private:
 		if (r < 0) return r;
 		store_plan();
 		ws->pool_trusted = true; // the dirty flags of the sparse pool say what the device did
-		if (outp.want_te)
+		if (ask.want_te)
 			hipLaunchKernelGGL(k_pair_te, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, sh->skey.as<u32>(),
 			                   sh->sres.as<int32_t>(), base_lane, ws->lane_sums.as<u64>(), (int)L, levels_run + 1,
 			                   sh->ste.as<int64_t>());
@@ -1964,14 +1960,14 @@ private:
 		                   act(0), ws->qbuf[0].as<u64>(), qcap, pchunk, (u32)(hi - lo), d_cnt); // act[0]: zeroed with the counter block
 		kt.stop();
 		cur->dirty = true;
-		if (outp.want_te) {
+		if (ask.want_te) {
 			PGQ_HIP_TRY(hipMemsetAsync(ws->lane_sums.p, 0, (size_t)kMaxTeLevels * L * 8, st));
 			hipLaunchKernelGGL(k_lane_degree_sums<WD>, dim3(4 * ncu), dim3(256), 0, st, cur->buf.as<u64>(), c->off, V,
 			                   ws->lane_sums.as<u64>());
 		}
 		stop = use_probe ? 0 : -1;
 		// a narrow batch is scan-bound: re-running its stragglers costs as much as finishing them here
-		if (use_probe && opt.defer && outp.depth < 2 && WD >= 8) stop = (int)std::min<int64_t>(L / opt.defer, (hi - lo) / opt.defer);
+		if (use_probe && opt.defer && ask.depth < 2 && WD >= 8) stop = (int)std::min<int64_t>(L / opt.defer, (hi - lo) / opt.defer);
 		hs = HostState { cur, 0, 0, true, { false, false }, false };
 		last_cw_cap = 0;
 		levels_run = 0;
@@ -2173,7 +2169,7 @@ private:
 		if (probe_now) probe(t);
 		const int stop_lvl = probe_now ? stop : -1; // the expansion returns at once when the probe left <= stop pairs open
 		PGQ_TRY(push ? push_level(nxt, spec, stop_lvl) : pull_level(nxt, bits & kLvSparse, stop_lvl));
-		if (outp.want_te) {
+		if (ask.want_te) {
 			if (t >= kMaxTeLevels) return fail(PGQ_ERR_UNSUPPORTED, "traversed-edge accounting supports at most 1023 levels");
 			hipLaunchKernelGGL(k_lane_degree_sums<WD>, dim3(4 * ncu), dim3(256), 0, st, nxt->buf.as<u64>(), c->off, V,
 			                   ws->lane_sums.as<u64>() + (size_t)t * L);
@@ -2195,7 +2191,7 @@ private:
 		if (probe_now && hc.unresolved <= (u32)stop) { // the expansion kernels returned immediately
 			if (hc.unresolved > 0) {
 				hipLaunchKernelGGL(k_mark_deferred, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, sh->sres.as<int32_t>());
-				outp.deferred = true;
+				deferred = true;
 				S.deferred_pairs += hc.unresolved;
 			}
 			return 1;
@@ -2246,7 +2242,7 @@ private:
 		return plan;
 	}
 	void store_plan() {
-		if (!spec_ok || ran_plan.empty() || outp.max_hops >= 0) return;
+		if (!spec_ok || ran_plan.empty() || ask.max_hops >= 0) return;
 		// (the last batch of a call may hold a handful of lanes: its levels are not what the next FULL batch will run)
 		const bool full = (U - (int64_t)base_lane) * 2 >= L;
 		std::lock_guard<std::mutex> g(c->plan_lock);
@@ -2375,23 +2371,25 @@ private:
 				                   sh->ssrc.as<int32_t>(), child_base, sh->soff.as<int64_t>(), d_child);
 			child_base = need;
 		}
-		outp.child_used = child_base;
+		rep.child_used = child_base;
 		// not an early return: the straggler pass still has to run so that the lengths are complete and child_used
 		// reports everything the caller must provide
-		if (child_overflow) outp.overflow = true;
+		if (child_overflow) rep.overflow = true;
 		return PGQ_OK;
 	}
 };
 
-int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                 bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp,
-                 bool sampled, int ahead_wd, double meet_bytes, double edge_bytes) {
+int search_lanes(pgq_csr *c, Workspace *ws, const SearchCall &call, SearchReport &rep, const LanesPlan &lp) {
+	const int64_t n = call.n, *const d_src = call.d_src, *const d_dst = call.d_dst;
+	const SearchAsk &ask = call.ask;
+	const bool with_paths = call.paths.has_value(), sampled = lp.sampled;
+	int ahead_wd = lp.ahead_wd; // settled below: 0 = nothing goes ahead of the wait
 	hipStream_t st = ws->stream;
 	pgq_stats_t &S = tstats().s;
 	const Options &mopt = options();
 	u32 U = 0;
 	// the accounting pass counts the full BFS of a pair even when dst has no in-edge, so it keeps those lanes
-	SampleArgs sm { meet_bytes, edge_bytes, nullptr, nullptr, n, d_src, c->V };
+	SampleArgs sm { lp.meet_bytes, lp.edge_bytes, nullptr, nullptr, n, d_src, c->V };
 	if (sampled) {
 		PGQ_TRY(ws->route_dec.reserve(sizeof(MeetDecision)));
 		sm.out = ws->route_dec.as<MeetDecision>();
@@ -2403,17 +2401,13 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	// device) and the batch's start (k_batch_reset) — are enqueued BEFORE the host waits for the source count: the GPU used to
 	// idle through that wait and its wake-up (~15 us) and then run them (48 us on the 2.1 M-row cross product).  If the count
 	// says otherwise afterwards (more than one batch, another width) the normal path overwrites / redoes both: same answers.
-	const bool may_stay_in_place = !with_paths && !outp.want_te && mopt.sort_single_batch == 0;
-	const bool bounded = outp.max_hops >= 0; // off the route memo's record, both ways
+	const bool may_stay_in_place = !with_paths && !ask.want_te && mopt.sort_single_batch == 0;
+	const bool bounded = ask.max_hops >= 0; // off the route memo's record, both ways
 	if (!may_stay_in_place || !mopt.stage2_ahead || bounded) ahead_wd = 0;
 	else if (ahead_wd < 0) ahead_wd = memo_lookup(c, n, d_src, d_dst).ahead_wd; // (the route layer did not look)
 	bool rows_ahead = false;
 	auto pre_wait = [&]() -> int {
-		KernelTimer kt(st, K_PREP);
-		hipLaunchKernelGGL(k_pair_rows, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->rank.as<u32>(), c->off, c->roff,
-		                   outp.want_te ? 0 : 1, c->V, ws->skey.as<u32>(), ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), ws->sres.as<int32_t>());
-		kt.stop();
-		S.algo_bytes[K_PREP] += (double)n * 44.0;
+		pair_rows(c, ws, n, d_src, d_dst, !ask.want_te);
 		rows_ahead = true;
 		PGQ_TRY(batch_state_reset(ws, c->V, ahead_wd));
 		ws->prereset_V = c->V;
@@ -2421,7 +2415,7 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 		return PGQ_OK;
 	};
 	ws->prereset_V = -1;
-	PGQ_TRY(lane_ranks(c, ws, n, d_src, d_dst, &U, !outp.want_te, sm, ahead_wd > 0 ? std::function<int()>(pre_wait) : std::function<int()>()));
+	PGQ_TRY(lane_ranks(c, ws, n, d_src, d_dst, &U, !ask.want_te, sm, ahead_wd > 0 ? std::function<int()>(pre_wait) : std::function<int()>()));
 	MemoOutcome memo;
 	// (lane_ranks has waited for the stream) what the sample says about these rows decides the next call's route
 	memo.go_again = sampled && ws->h_meet->sample_go == 2;
@@ -2431,55 +2425,51 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	const int64_t Lb = 64 * (int64_t)wd;
 	const int nb = (int)((U + Lb - 1) / Lb);
 	bool identity = false; // the rows were left in the caller's order (one batch): no permutation to undo
-	PGQ_TRY(lane_rows_bfs(c, ws, n, d_src, d_dst, !outp.want_te, Lb, nb, may_stay_in_place, &identity, rows_ahead));
+	PGQ_TRY(lane_rows_bfs(c, ws, n, d_src, d_dst, !ask.want_te, Lb, nb, may_stay_in_place, &identity, rows_ahead));
 	if (may_stay_in_place) { // what the next call with this row count may do ahead of its wait
 		memo.id_wd = wd;
 		memo.in_place = identity;
 	}
 	if (!bounded) memo_record(c, n, d_src, d_dst, memo);
-	auto run = [&](Workspace *priv, int b0, int bstride, SearchOutput &o) -> int {
+	std::atomic<bool> deferred { false }; // some worker's batch left stragglers
+	auto run = [&](Workspace *priv, int b0, int bstride) -> int {
+		auto worker = [&](auto &&lb) { const int r = lb.run(b0, bstride); if (lb.deferred) deferred = true; return r; };
 		switch (wd) {
-		case 1: return LaneBatches<1>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
-		case 2: return LaneBatches<2>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
-		case 4: return LaneBatches<4>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
-		case 8: return LaneBatches<8>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
-		case 16: return LaneBatches<16>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
-		default: return LaneBatches<32>(c, ws, priv, n, U, with_paths, d_child_ext, child_cap_ext, o).run(b0, bstride);
+		case 1: return worker(LaneBatches<1>(c, ws, priv, call, U, rep));
+		case 2: return worker(LaneBatches<2>(c, ws, priv, call, U, rep));
+		case 4: return worker(LaneBatches<4>(c, ws, priv, call, U, rep));
+		case 8: return worker(LaneBatches<8>(c, ws, priv, call, U, rep));
+		case 16: return worker(LaneBatches<16>(c, ws, priv, call, U, rep));
+		default: return worker(LaneBatches<32>(c, ws, priv, call, U, rep));
 		}
 	};
 	// Independent batches overlap on several streams (one host thread each): hides the per-level host round trip
 	// and fills the GPU during the short levels.  Paths and the accounting pass keep a single ordered worker.
 	int workers = std::max(1, std::min(options().streams, nb));
-	if (with_paths || outp.want_te) workers = 1;
+	if (with_paths || ask.want_te) workers = 1;
 	int rc = PGQ_OK;
 	if (workers == 1) {
-		rc = run(ws, 0, 1, outp);
+		rc = run(ws, 0, 1);
 	} else {
 		std::vector<WorkspaceLease> leases((size_t)workers - 1);
 		for (auto &l : leases) PGQ_TRY(l.acquire());
-		std::vector<SearchOutput> outs((size_t)workers, outp);
-		rc = fan_out(std::vector<int>((size_t)workers, current_device()),
-		             [&](int t) { return run(t == 0 ? ws : leases[(size_t)t - 1].ws, t, workers, outs[(size_t)t]); });
-		for (const SearchOutput &o : outs) outp.deferred = outp.deferred || o.deferred;
+		rc = fan_out(std::vector<int>((size_t)workers, current_device()), [&](int t) { return run(t == 0 ? ws : leases[(size_t)t - 1].ws, t, workers); });
 	}
-	if (rc == PGQ_OK && outp.deferred) {
+	if (rc == PGQ_OK && deferred) {
 		// second, narrow pass over the stragglers
-		PGQ_TRY(ws->def_src.reserve((size_t)n * 8));
-		PGQ_TRY(ws->def_dst.reserve((size_t)n * 8));
-		PGQ_TRY(ws->def_len.reserve((size_t)n * 8));
+		for (DevBuf *b : { &ws->def_src, &ws->def_dst, &ws->def_len }) PGQ_TRY(b->reserve((size_t)n * 8));
 		PGQ_TRY(ws->def_idx.reserve((size_t)n * 4));
 		u32 *d_count = reinterpret_cast<u32 *>(ws->counters.p);
 		PGQ_HIP_TRY(hipMemsetAsync(d_count, 0, 4, st));
-		hipLaunchKernelGGL(k_collect_deferred, dim3(blocks_for(n)), dim3(256), 0, st, n, ws->sres.as<int32_t>(),
-		                   ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(), ws->def_src.as<int64_t>(),
-		                   ws->def_dst.as<int64_t>(), ws->def_idx.as<u32>(), d_count);
+		hipLaunchKernelGGL(k_collect_deferred, dim3(blocks_for(n)), dim3(256), 0, st, n, ws->sres.as<int32_t>(), ws->ssrc.as<int32_t>(), ws->sdst.as<int32_t>(),
+		                   ws->def_src.as<int64_t>(), ws->def_dst.as<int64_t>(), ws->def_idx.as<u32>(), d_count);
 		u32 nd = 0;
 		PGQ_HIP_TRY(hipMemcpyAsync(&nd, d_count, 4, hipMemcpyDeviceToHost, st));
 		PGQ_WAIT(st);
 		if (nd > 0) {
-			const int64_t base = outp.child_used;
-			PGQ_TRY(search_open_rows(c, ws, nd, ws->def_src.as<int64_t>(), ws->def_dst.as<int64_t>(), SearchOutput(), outp, with_paths,
-			                         d_child_ext, child_cap_ext, base, false, [&](bool lists) {
+			const int64_t base = rep.child_used;
+			const OpenRows open { nd, ws->def_src.as<int64_t>(), ws->def_dst.as<int64_t>(), SearchAsk(), base, false };
+			PGQ_TRY(search_open_rows(c, ws, call, rep, open, [&](bool lists) {
 				                         hipLaunchKernelGGL(k_apply_deferred, dim3(blocks_for(nd)), dim3(256), 0, st, (int64_t)nd, ws->def_idx.as<u32>(),
 				                                            ws->def_len.as<int64_t>(), ws->sres.as<int32_t>(), lists ? ws->def_off.as<int64_t>() : nullptr,
 				                                            lists ? ws->soff.as<int64_t>() : nullptr, lists ? base : (int64_t)0);
@@ -2491,12 +2481,11 @@ int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, con
 	KernelTimer kts(st, K_PREP);
 	S.algo_bytes[K_PREP] += (double)n * (identity ? 12.0 : 16.0); // result word (+ permutation) read, 8-byte length written
 	hipLaunchKernelGGL(k_scatter_results, dim3(blocks_for(n)), dim3(256), 0, st, n, identity ? nullptr : ws->sidx.as<u32>(), ws->sres.as<int32_t>(),
-	                   ws->soff.as<int64_t>(), d_out_len, with_paths ? d_out_off : nullptr);
+	                   ws->soff.as<int64_t>(), call.d_out_len, with_paths ? call.paths->d_out_off : nullptr);
 	kts.stop();
 	PGQ_WAIT(st);
 	KernelTimer::flush();
-	if (rc == PGQ_OK && outp.overflow)
-		rc = fail(PGQ_ERR_INVALID_ARG, "child buffer too small: need " + std::to_string(outp.child_used) + " elements");
+	if (rc == PGQ_OK && rep.overflow) rc = fail(PGQ_ERR_INVALID_ARG, "child buffer too small: need " + std::to_string(rep.child_used) + " elements");
 	return rc;
 }
 

@@ -10,7 +10,7 @@
 
 namespace pgq {
 
-// ---- rows sorted by source for the source-centric kernel (search_device: run_sorted_ball) -------------------------------
+// ---- rows sorted by source for the source-centric kernel (Route::run_sorted_ball) -------------------------------
 // NULL and out-of-range sources sort behind every vertex (key V); the gathered rows carry the ORIGINAL ids, so that the
 // kernel answers NULL rows with NULL and reports ids outside [0, V) like every other route.
 __global__ void k_sort_keys(int64_t n, const int64_t *__restrict__ src, int64_t V, u32 *__restrict__ key, u32 *__restrict__ idx) {
@@ -38,7 +38,7 @@ __global__ void k_scatter_te(int64_t n, const u32 *__restrict__ sidx, const int6
 	if (i < n) out[sidx[i]] = ste[i];
 }
 
-// iterativelength_within: whatever a stage reported beyond the bound becomes NULL (SearchOutput::max_hops)
+// iterativelength_within: whatever a stage reported beyond the bound becomes NULL (SearchAsk::max_hops)
 __global__ void k_clamp_hops(int64_t n, int64_t max_hops, int64_t *__restrict__ len) {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n && len[i] > max_hops) len[i] = -1;
@@ -50,10 +50,10 @@ static int64_t search_bound(const pgq_csr *c, int64_t max_hops) { return max_hop
 // Whether the pair-centric pre-pass may run for this call at all, and whether the host-side cost model sends n rows
 // (each taken as a distinct source) to it.  Shared by search_device and the chunk entry point (zero-copy staging).
 constexpr int64_t kMeetDecideRows = 16384; // above: the distinct sources are sampled and the decision is taken on the device
-static bool prepass_may(const pgq_csr *c, const SearchOutput &outp) {
+static bool prepass_may(const pgq_csr *c, const SearchAsk &ask) {
 	// depth 1 = the stragglers a lane batch deferred (a few far pairs of a cross product): the pre-pass answers them from
 	// two-hop scans instead of another round of whole-graph levels
-	return options().meet && !outp.want_te && outp.depth <= 1 && !outp.from_meet && c->E > 0 && c->fdesc != nullptr;
+	return options().meet && !ask.want_te && ask.depth <= 1 && !ask.from_meet && c->E > 0 && c->fdesc != nullptr;
 }
 // Bytes the pre-pass moves per row.  Known once a pre-pass has run on this CSR (measured: its kernels count the entries
 // they walk; calibrate_prepass runs 1024 pseudo-random pairs through it before the first large call is routed).  Before
@@ -84,9 +84,7 @@ static int calibrate_prepass(pgq_csr *c) {
 	WorkspaceLease lease;
 	PGQ_TRY(lease.acquire());
 	Workspace *w = lease.ws;
-	PGQ_TRY(w->in_src.reserve((size_t)n0 * 8));
-	PGQ_TRY(w->in_dst.reserve((size_t)n0 * 8));
-	PGQ_TRY(w->out_len.reserve((size_t)n0 * 8));
+	for (DevBuf *b : { &w->in_src, &w->in_dst, &w->out_len }) PGQ_TRY(b->reserve((size_t)n0 * 8));
 	hipLaunchKernelGGL(k_calibration_pairs, dim3(blocks_for(n0)), dim3(256), 0, w->stream, n0, c->V, w->in_src.as<int64_t>(), w->in_dst.as<int64_t>());
 	pgq_stats_t &S = tstats().s;
 	const pgq_stats_t saved = S; // the caller's statistics are about its own rows
@@ -100,61 +98,11 @@ static int calibrate_prepass(pgq_csr *c) {
 	calibration_store(c); // the next handle over a graph of this shape starts with it
 	return PGQ_OK;
 }
-static bool prepass_takes(const pgq_csr *c, int64_t n, const SearchOutput &outp) {
-	if (!prepass_may(c, outp)) return false;
+static bool prepass_takes(const pgq_csr *c, int64_t n, const SearchAsk &ask) {
+	if (!prepass_may(c, ask)) return false;
 	const double meet_bytes = (double)n * prepass_row_bytes(c);
 	const double edge_bytes = options().meet_bias * (double)c->E;
 	return meet_bytes <= lanes_cost_bytes(edge_bytes, (double)std::min<int64_t>(n, c->V), (double)n, (double)c->V);
-}
-
-static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                              int64_t *d_out_len, bool with_paths, int64_t *d_out_off, int64_t *d_child_ext,
-                              int64_t child_cap_ext, SearchOutput &outp);
-// The byte models that pick a route price kernels at streaming rate; on a graph past the caches the source-centric route is
-// nothing like that (R-MAT-22, 2048 x 1024 rows: global bit maps marked through DRAM atomics, 35,000 far rows searched one
-// by one — 16.7 ms where the model says 0.1) and the lane batches are 4.6 x their model (12 ms).  So large grouped calls are
-// TIMED, per graph shape: the best wall time per row of the source-centric route is kept (the best of at least two calls: a
-// process's first call of a kind pays for allocations, kernel attributes and the calibration); when it is over
-// `route_try_factor` x the lane batches' modelled time the next two such calls go through the lanes, and from then on through
-// whichever measured faster.  Every route is exact, so this only moves time.  (The figures travel with the calibration cache.)
-int search_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                  int64_t *d_out_len, bool with_paths, int64_t *d_out_off, int64_t *d_child_ext,
-                  int64_t child_cap_ext, SearchOutput &outp) {
-	const Options &o = options();
-	if (outp.max_hops >= 0) outp.no_memo = true; // a bounded call: off the record (SearchOutput::max_hops)
-	const bool timed = outp.max_hops < 0 && o.route_timing && o.ball == 1 && outp.depth == 0 && !with_paths && !outp.want_te && !outp.bidir && !outp.no_ball &&
-	                   outp.ball_hint != 0 && n >= (int64_t)std::max(1, o.route_timing_rows);
-	if (!timed) return search_device_impl(c, ws, n, d_src, d_dst, d_out_len, with_paths, d_out_off, d_child_ext, child_cap_ext, outp);
-	const double tb = c->cal.route_ball_ns.load(std::memory_order_relaxed), tl = c->cal.route_lanes_ns.load(std::memory_order_relaxed);
-	const int nb_s = c->cal.route_ball_samples.load(std::memory_order_relaxed), nl_s = c->cal.route_lanes_samples.load(std::memory_order_relaxed);
-	// both figures are the best of at least two calls before they decide anything (a first call pays one-time costs)
-	// ... and they speak for calls of their own size: a lane batch costs the same for 32 rows per source as for 1024, the
-	// source-centric route does not — a call with under half the measured rows is left to the byte models
-	const bool same_size = n * 2 >= c->cal.route_rows.load(std::memory_order_relaxed);
-	const bool trial = same_size && nb_s >= 2 && nl_s < 2 && c->cal.route_try_lanes.load(std::memory_order_relaxed) != 0;
-	outp.prefer_lanes = trial || (same_size && nb_s >= 2 && nl_s >= 2 && tl < tb);
-	// (such a call neither follows nor feeds the route memo: what it would leave there — "these buffers go to the lanes" — must
-	// not outlive the preference, and the decision kernel in front of the lanes is 40 us of a call that takes milliseconds)
-	if (outp.prefer_lanes) outp.no_memo = true;
-	const int64_t levels0 = tstats().s.levels;
-	const auto t0 = std::chrono::steady_clock::now();
-	const int rc = search_device_impl(c, ws, n, d_src, d_dst, d_out_len, with_paths, d_out_off, d_child_ext, child_cap_ext, outp);
-	if (rc != PGQ_OK) return rc;
-	const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count() / (double)n;
-	if (outp.route == 1) {
-		const double best = nb_s > 0 ? std::min(tb, ns) : ns;
-		c->cal.route_ball_ns.store(best, std::memory_order_relaxed);
-		c->cal.route_ball_samples.store(nb_s + 1, std::memory_order_relaxed);
-		if (nb_s == 0 || n > c->cal.route_rows.load(std::memory_order_relaxed)) c->cal.route_rows.store(n, std::memory_order_relaxed);
-		if (nb_s + 1 >= 2 && outp.source_runs > 0) { // the lane batches' modelled time per row, at 8 TB/s
-			const double lanes_ns = lanes_cost_bytes(o.meet_bias * (double)c->E, std::min(outp.source_runs, (double)c->V), (double)n, (double)c->V) / 8000.0 / (double)n;
-			if (best > o.route_try_factor * lanes_ns) c->cal.route_try_lanes.store(1, std::memory_order_relaxed);
-		}
-	} else if (outp.prefer_lanes && tstats().s.levels > levels0) { // (the lane batches did run)
-		c->cal.route_lanes_ns.store(nl_s > 0 ? std::min(tl, ns) : ns, std::memory_order_relaxed);
-		c->cal.route_lanes_samples.store(nl_s + 1, std::memory_order_relaxed);
-	}
-	return PGQ_OK;
 }
 
 // ---- the route memo (pgq_csr::RouteMemo): one look-up and one record per step, each under plan_lock once -------------
@@ -195,34 +143,125 @@ void memo_record(pgq_csr *c, int64_t n, const void *src, const void *dst, const 
 	}
 }
 
-// The route of a call, in order: the per-row bidirectional search (iterativelengthbidirectional); a plan on the host (no
-// launches); the source-centric kernel on the rows sorted by source when the memo says that took these buffers; the
-// pair-centric pre-pass, its chain opened by the source-centric kernels when the rows may be grouped by source; the sort by
-// source when neither took rows of few sources; the lane batches for the rest.  Every route is exact: the choice moves time.
-static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                              int64_t *d_out_len, bool with_paths, int64_t *d_out_off, int64_t *d_child_ext,
-                              int64_t child_cap_ext, SearchOutput &outp) {
-	hipStream_t st = ws->stream;
+// One search_device call.  The route, in order (run): the per-row bidirectional search (iterativelengthbidirectional); a plan on
+// the host (no launches); the source-centric kernel on the rows sorted by source when the memo says that took these buffers; the
+// pair-centric pre-pass, its chain opened by the source-centric kernels when the rows may be grouped by source; the sort by source
+// when neither took rows of few sources; the lane batches for the rest.  Every route is exact: the choice moves time.  The
+// caller's SearchCall is only read; what the call decides for itself (prefer_lanes, no_memo) lives here.
+class Route {
+public:
+	Route(pgq_csr *c, Workspace *ws, const SearchCall &call, SearchReport &rep) : c(c), ws(ws), call(call), rep(rep) {}
+	// The byte models that pick a route price kernels at streaming rate; on a graph past the caches the source-centric route is
+	// nothing like that (R-MAT-22, 2048 x 1024 rows: global bit maps marked through DRAM atomics, 35,000 far rows searched one
+	// by one — 16.7 ms where the model says 0.1) and the lane batches are 4.6 x their model (12 ms).  So large grouped calls are
+	// TIMED, per graph shape: the best wall time per row of the source-centric route is kept (the best of at least two calls: a
+	// process's first call of a kind pays for allocations, kernel attributes and the calibration); when it is over
+	// `route_try_factor` x the lane batches' modelled time the next two such calls go through the lanes, and from then on through
+	// whichever measured faster.  Every route is exact, so this only moves time.  (The figures travel with the calibration cache.)
+	int search() {
+		if (!timed) return run();
+		const int64_t levels0 = S.levels;
+		const auto t0 = std::chrono::steady_clock::now();
+		PGQ_TRY(run());
+		const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count() / (double)n;
+		if (rep.route == 1) {
+			const double best = nb_s > 0 ? std::min(tb, ns) : ns;
+			c->cal.route_ball_ns.store(best, std::memory_order_relaxed);
+			c->cal.route_ball_samples.store(nb_s + 1, std::memory_order_relaxed);
+			if (nb_s == 0 || n > c->cal.route_rows.load(std::memory_order_relaxed)) c->cal.route_rows.store(n, std::memory_order_relaxed);
+			if (nb_s + 1 >= 2 && rep.source_runs > 0) { // the lane batches' modelled time per row, at 8 TB/s
+				const double lanes_ns = lanes_cost_bytes(mopt.meet_bias * (double)c->E, std::min(rep.source_runs, (double)c->V), (double)n, (double)c->V) / 8000.0 / (double)n;
+				if (best > mopt.route_try_factor * lanes_ns) c->cal.route_try_lanes.store(1, std::memory_order_relaxed);
+			}
+		} else if (prefer_lanes && S.levels > levels0) { // (the lane batches did run)
+			c->cal.route_lanes_ns.store(nl_s > 0 ? std::min(tl, ns) : ns, std::memory_order_relaxed);
+			c->cal.route_lanes_samples.store(nl_s + 1, std::memory_order_relaxed);
+		}
+		return PGQ_OK;
+	}
+private:
+	// ---- per call ----
+	pgq_csr *const c;
+	Workspace *const ws;
+	const SearchCall &call;
+	SearchReport &rep;
+	const SearchAsk &ask = call.ask;
+	const int64_t n = call.n, *const d_src = call.d_src, *const d_dst = call.d_dst;
+	int64_t *const d_out_len = call.d_out_len;
+	const bool with_paths = call.paths.has_value();
+	const hipStream_t st = ws->stream;
 	pgq_stats_t &S = tstats().s;
-	S.pairs += n;
-	if (n == 0) return PGQ_OK;
-	if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
-	if (with_paths) PGQ_TRY(ensure_edge_ids(c)); // PGQ_UPLOAD_LAZY_EDGE_IDS: the first shortestpath call brings them over
 	const Options &mopt = options();
-	// a large call is about to be routed on the pre-pass's bytes per row: measured first if this CSR has none yet
-	const bool bounded = outp.max_hops >= 0; // neither reads nor feeds the calibration (before it exists: the pre-pass priced by the graph's two-hop mean)
-	if (prepass_may(c, outp) && n > kMeetDecideRows && mopt.meet_calibrate && !bounded && c->cal.meet_bpr.load(std::memory_order_relaxed) <= 0)
-		PGQ_TRY(calibrate_prepass(c));
-	if (outp.bidir && !with_paths && !outp.want_te && outp.depth == 0 && c->E > 0) {
+	// a bounded call is off the record (SearchAsk::max_hops): it neither reads nor feeds the calibration (before it exists: the
+	// pre-pass priced by the graph's two-hop mean), the route memo or the route timing
+	const bool bounded = ask.max_hops >= 0;
+	const bool timed = !bounded && mopt.route_timing && mopt.ball == 1 && ask.depth == 0 && !with_paths && !ask.want_te && !ask.bidir && !ask.no_ball &&
+	                   ask.ball_hint != 0 && n >= (int64_t)std::max(1, mopt.route_timing_rows);
+	const double tb = c->cal.route_ball_ns.load(std::memory_order_relaxed), tl = c->cal.route_lanes_ns.load(std::memory_order_relaxed);
+	const int nb_s = c->cal.route_ball_samples.load(std::memory_order_relaxed), nl_s = c->cal.route_lanes_samples.load(std::memory_order_relaxed);
+	// both figures are the best of at least two calls before they decide anything (a first call pays one-time costs)
+	// ... and they speak for calls of their own size: a lane batch costs the same for 32 rows per source as for 1024, the
+	// source-centric route does not — a call with under half the measured rows is left to the byte models
+	const bool same_size = n * 2 >= c->cal.route_rows.load(std::memory_order_relaxed);
+	const bool trial = same_size && nb_s >= 2 && nl_s < 2 && c->cal.route_try_lanes.load(std::memory_order_relaxed) != 0;
+	// large grouped call on a graph where the lane batches measured faster than the source-centric route, or their trial
+	const bool prefer_lanes = timed && (trial || (same_size && nb_s >= 2 && nl_s >= 2 && tl < tb));
+	// (such a call neither follows nor feeds the route memo: what it would leave there — "these buffers go to the lanes" — must
+	// not outlive the preference, and the decision kernel in front of the lanes is 40 us of a call that takes milliseconds)
+	const bool no_memo = ask.no_memo || bounded || prefer_lanes;
+	const bool read_memo = mopt.route_memo && !no_memo, write_memo = !no_memo;
+	// few rows: every row is taken as a distinct source (the pessimistic case for the pre-pass); many rows: a sampled
+	// estimate of the distinct sources decides ON THE DEVICE, in the same launch chain (cross products share their lanes)
+	const bool decide = n > kMeetDecideRows;
+	// ---- the plan (plan) ----
+	double meet_bytes = 0, edge_bytes = 0; // the byte rule's two sides
+	BallMode ball = BallMode::Off;
+	bool sort_allowed = false;
+	MemoVerdict memo;
+	DecideMode decide_mode = DecideMode::None;
+
+	int run() {
+		S.pairs += n;
+		if (n == 0) return PGQ_OK;
+		if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
+		if (with_paths) PGQ_TRY(ensure_edge_ids(c)); // PGQ_UPLOAD_LAZY_EDGE_IDS: the first shortestpath call brings them over
+		// a large call is about to be routed on the pre-pass's bytes per row: measured first if this CSR has none yet
+		if (prepass_may(c, ask) && decide && mopt.meet_calibrate && !bounded && c->cal.meet_bpr.load(std::memory_order_relaxed) <= 0) PGQ_TRY(calibrate_prepass(c));
+		if (ask.bidir && !with_paths && !ask.want_te && ask.depth == 0 && c->E > 0) return run_bidirectional();
+		plan();
+		bool sampled = false; // the sampled decision was asked for without the chain: read it after the next wait
+		if (prepass_takes(c, n, ask)) {
+			bool took = false;
+			if (sort_allowed && read_memo && memo.sorted) { // these buffers went through the sort last time: straight there
+				PGQ_TRY(run_sorted_ball(&took));
+				if (took) return PGQ_OK;
+				record_sorted(false);
+			}
+			if (decide && read_memo && memo.go == 0) {
+				sampled = true; // taken inside the lane assignment's first launch (k_mark_sources)
+			} else {
+				PrepassResult r;
+				PGQ_TRY(with_paths ? run_prepass_paths(r) : run_prepass(r));
+				record_prepass(r);
+				if (r.answered) return PGQ_OK;
+				// neither the source-centric kernel (the rows are not grouped) nor the pre-pass (few distinct sources) took the call:
+				// with at least 64 rows per source on average a sort by source makes it the former's
+				if (sort_allowed && r.est_sources > 0 && r.est_sources * 64.0 <= (double)n) {
+					PGQ_TRY(run_sorted_ball(&took));
+					record_sorted(took);
+					if (took) return PGQ_OK;
+				}
+			}
+		}
+		return search_lanes(c, ws, call, rep, LanesPlan { sampled, memo.ahead_wd, meet_bytes, edge_bytes });
+	}
+	int run_bidirectional() {
 		u32 nd = 0;
 		PGQ_TRY(meet_bidirectional(c, ws, n, d_src, d_dst, d_out_len, &nd));
-		SearchOutput child; // over k_bibfs's caps: the lane-batched search
-		child.from_meet = true;
-		return search_open_rows(c, ws, nd, ws->open_src, ws->open_dst, child, outp, false, nullptr, 0, 0, true,
-		                        [&](bool) { return meet_apply(ws, nd, ws->def_len.as<int64_t>(), d_out_len); });
+		OpenRows open { nd, ws->open_src, ws->open_dst }; // over k_bibfs's caps: the lane-batched search
+		open.ask.from_meet = true;
+		return search_open_rows(c, ws, call, rep, open, [&](bool) { return meet_apply(ws, nd, ws->def_len.as<int64_t>(), d_out_len); });
 	}
-
-	// ---- the plan ----
 	// Pair-centric pre-pass: rows at distance <= 3 are answered from two-hop neighbourhood scans (pgq_meet.hip); only what it
 	// leaves open goes through the lane-batched search.  Cost model (bytes at streaming rate, prepass_takes): the pre-pass
 	// walks, per row, the cheaper endpoint's two-hop neighbourhood (~0.6 of E[in-degree x out-degree] entries when it has to
@@ -231,35 +270,30 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 	// the 2048-lane batch of the SF100-shaped graph (0.94 ms ~ 4.3 GB at streaming rate; round 2 priced a batch at 16 B per
 	// edge and sent a 2048 x 32 cross product through the lanes at three times the cost of the pre-pass).  `meet_bias`
 	// scales the lanes' side.
-	const double meet_bytes = (double)n * prepass_row_bytes(c);
-	const double edge_bytes = mopt.meet_bias * (double)c->E; // x (12 + 3 wd) per batch
-	// few rows: every row is taken as a distinct source (the pessimistic case for the pre-pass); many rows: a sampled
-	// estimate of the distinct sources decides ON THE DEVICE, in the same launch chain (cross products share their lanes)
-	const bool decide = n > kMeetDecideRows;
-	const bool read_memo = mopt.route_memo && !outp.no_memo, write_memo = !outp.no_memo;
-	// round 6: the source-centric kernels open the pre-pass's chain and decide on the device (pgq_ball.h); not for paths,
-	// not for the rows that kernel itself left open
-	BallMode ball = BallMode::Off;
-	if (!(with_paths || outp.no_ball || outp.bidir || outp.prefer_lanes || n < 2) && mopt.ball > 0)
-		ball = mopt.ball == 1 ? BallMode::Decide : BallMode::Always;
-	const bool ball_possible = ball != BallMode::Off && (bounded || c->cal.ball_open_frac.load(std::memory_order_relaxed) <= 0.02); // before the memo's say on THESE rows as they lie
-	if (ball == BallMode::Decide && (outp.ball_hint == 0 || !ball_possible)) ball = BallMode::Off;
-	// the caller has counted the source runs on the host and found the rows grouped: the chain is the two kernels alone (if
-	// the device's byte rule declines after all, run_prepass falls back to the stage kernels)
-	if (ball == BallMode::Decide && outp.ball_hint == 1) ball = BallMode::Only;
-	// the memo is read only when a step below uses it (chunk calls and small nested searches take no lock for it)
-	const bool memo_ball = ball == BallMode::Decide && outp.ball_hint < 0; // (a caller that has looked at the rows knows better than the memo)
-	MemoVerdict memo;
-	if (read_memo && (decide || memo_ball)) memo = memo_lookup(c, n, d_src, d_dst);
-	if (memo_ball && memo.ball >= 0) ball = memo.ball ? BallMode::Only : BallMode::Off;
-	// the memo vouches for the pre-pass on these buffers: the sample only observes (it rides in the chain)
-	const DecideMode decide_mode = !decide ? DecideMode::None : (read_memo && memo.go > 0 ? DecideMode::Ride : DecideMode::Gate);
-	const bool sort_allowed = mopt.ball_sort && ball_possible && !outp.want_te && decide;
-
+	void plan() {
+		meet_bytes = (double)n * prepass_row_bytes(c);
+		edge_bytes = mopt.meet_bias * (double)c->E; // x (12 + 3 wd) per batch
+		// round 6: the source-centric kernels open the pre-pass's chain and decide on the device (pgq_ball.h); not for paths,
+		// not for the rows that kernel itself left open
+		if (!(with_paths || ask.no_ball || ask.bidir || prefer_lanes || n < 2) && mopt.ball > 0)
+			ball = mopt.ball == 1 ? BallMode::Decide : BallMode::Always;
+		const bool ball_possible = ball != BallMode::Off && (bounded || c->cal.ball_open_frac.load(std::memory_order_relaxed) <= 0.02); // before the memo's say on THESE rows as they lie
+		if (ball == BallMode::Decide && (ask.ball_hint == 0 || !ball_possible)) ball = BallMode::Off;
+		// the caller has counted the source runs on the host and found the rows grouped: the chain is the two kernels alone (if
+		// the device's byte rule declines after all, run_prepass falls back to the stage kernels)
+		if (ball == BallMode::Decide && ask.ball_hint == 1) ball = BallMode::Only;
+		// the memo is read only when a step below uses it (chunk calls and small nested searches take no lock for it)
+		const bool memo_ball = ball == BallMode::Decide && ask.ball_hint < 0; // (a caller that has looked at the rows knows better than the memo)
+		if (read_memo && (decide || memo_ball)) memo = memo_lookup(c, n, d_src, d_dst);
+		if (memo_ball && memo.ball >= 0) ball = memo.ball ? BallMode::Only : BallMode::Off;
+		// the memo vouches for the pre-pass on these buffers: the sample only observes (it rides in the chain)
+		decide_mode = !decide ? DecideMode::None : (read_memo && memo.go > 0 ? DecideMode::Ride : DecideMode::Gate);
+		sort_allowed = mopt.ball_sort && ball_possible && !ask.want_te && decide;
+	}
 	// the pre-pass chain over the rows as they lie (lengths)
-	auto run_prepass = [&](PrepassResult &r) -> int {
+	int run_prepass(PrepassResult &r) {
 		const double b0 = tstats().route_bytes;
-		PrepassArgs a { n, d_src, d_dst, d_out_len, nullptr, meet_bytes, edge_bytes, decide_mode, ball, outp.max_hops };
+		PrepassArgs a { n, d_src, d_dst, d_out_len, nullptr, meet_bytes, edge_bytes, decide_mode, ball, ask.max_hops };
 		PGQ_TRY(meet_prepass(c, ws, a, &r));
 		if (ball == BallMode::Only && r.ball_attempted && !r.ball_took) { // the kernels-alone chain declined these rows: the stage kernels after all
 			a.ball = BallMode::Off;
@@ -271,8 +305,8 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 				const double now = (double)r.n_open / (double)n, old = c->cal.ball_open_frac.load(std::memory_order_relaxed);
 				c->cal.ball_open_frac.store(0.5 * old + 0.5 * now, std::memory_order_relaxed);
 			}
-			outp.route = 1;
-			outp.source_runs = r.est_sources;
+			rep.route = 1;
+			rep.source_runs = r.est_sources;
 		}
 		if (!r.answered) return PGQ_OK;
 		if (n >= 1024 && !r.ball_took && !bounded) { // what these rows really moved refines the CSR's bytes per row (half the weight to the newest call)
@@ -282,15 +316,14 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 		}
 		// what the source-centric kernel left open (distance >= 5, unreachable, segments over its cap) is the pre-pass's kind
 		// of row (k_meet4d / k_bibfs) before it is the lane batches'
-		SearchOutput child;
-		child.from_meet = !r.ball_took;
-		child.no_ball = true;
-		return search_open_rows(c, ws, r.n_open, ws->open_src, ws->open_dst, child, outp, false, nullptr, 0, 0, true,
-		                        [&](bool) { return meet_apply(ws, r.n_open, ws->def_len.as<int64_t>(), d_out_len); });
-	};
+		OpenRows open { r.n_open, ws->open_src, ws->open_dst };
+		open.ask.from_meet = !r.ball_took;
+		open.ask.no_ball = true;
+		return search_open_rows(c, ws, call, rep, open, [&](bool) { return meet_apply(ws, r.n_open, ws->def_len.as<int64_t>(), d_out_len); });
+	}
 	// shortestpath: the pre-pass also records each answered row's inner vertices (reference tie-break); their lists are
 	// packed first, the lists of the rows left to the lane-batched search are appended behind them
-	auto run_prepass_paths = [&](PrepassResult &r) -> int {
+	int run_prepass_paths(PrepassResult &r) {
 		// the lists of the rows the pre-pass answers have at most 9 elements (distance <= 4): the buffer for them is sized
 		// up front, so that they are written in the same launch chain as the search
 		DecideMode dm = decide_mode;
@@ -298,18 +331,13 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 			bool go = true;
 			PGQ_TRY(meet_decide_alone(c, ws, n, d_src, meet_bytes, edge_bytes, &go));
 			S.host_waits++;
-			if (!go) {
-				r.answered = false;
-				return PGQ_OK;
-			}
+			r.answered = go;
+			if (!go) return PGQ_OK;
 			dm = DecideMode::None;
 		}
-		MeetPathsOut po;
-		po.d_out_off = d_out_off;
-		if (d_child_ext) {
-			po.d_child = d_child_ext;
-			po.child_cap = child_cap_ext;
-		} else {
+		const SearchPaths &p = *call.paths;
+		MeetPathsOut po { p.d_child_ext, p.child_cap_ext, p.d_out_off };
+		if (!p.d_child_ext) {
 			// at most 9 elements per row (distance 4) — up to paths_reserve_mb; a call whose lists need more (over ~15 M rows at
 			// the shipped 1 GB) has them written again into a buffer of the exact size (round-5 advisor finding: 72 bytes per row
 			// reserved up front whatever the call)
@@ -318,31 +346,28 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 			po.d_child = ws->child.as<int64_t>();
 			po.child_cap = (int64_t)(ws->child.cap / 8);
 		}
-		PGQ_HIP_TRY(hipMemsetAsync(d_out_off, 0, (size_t)n * 8, st));
+		PGQ_HIP_TRY(hipMemsetAsync(p.d_out_off, 0, (size_t)n * 8, st));
 		PGQ_TRY(meet_prepass(c, ws, PrepassArgs { n, d_src, d_dst, d_out_len, &po, meet_bytes, edge_bytes, dm, BallMode::Off }, &r));
 		if (!r.answered) return PGQ_OK;
-		if (!d_child_ext && po.total > po.child_cap) { // (the kernel skipped the lists that did not fit)
+		if (!p.d_child_ext && po.total > po.child_cap) { // (the kernel skipped the lists that did not fit)
 			PGQ_TRY(ws->child.reserve((size_t)po.total * 8));
 			po.d_child = ws->child.as<int64_t>();
 			po.child_cap = (int64_t)(ws->child.cap / 8);
 			PGQ_TRY(meet_reemit_paths(c, ws, n, d_src, d_dst, d_out_len, &po));
 		}
-		SearchOutput child;
-		child.from_meet = true;
-		PGQ_TRY(search_open_rows(c, ws, r.n_open, ws->open_src, ws->open_dst, child, outp, true, d_child_ext, child_cap_ext, po.total, true,
-		                         [&](bool) {
-			                         return meet_apply_paths(ws, r.n_open, ws->def_len.as<int64_t>(), ws->def_off.as<int64_t>(), po.total,
-			                                                 d_out_len, d_out_off);
-		                         }));
-		if (outp.overflow)
-			return fail(PGQ_ERR_INVALID_ARG, "child buffer too small: need " + std::to_string(outp.child_used) + " elements");
+		OpenRows open { r.n_open, ws->open_src, ws->open_dst, SearchAsk(), po.total };
+		open.ask.from_meet = true;
+		PGQ_TRY(search_open_rows(c, ws, call, rep, open, [&](bool) {
+			return meet_apply_paths(ws, r.n_open, ws->def_len.as<int64_t>(), ws->def_off.as<int64_t>(), po.total, d_out_len, p.d_out_off);
+		}));
+		if (rep.overflow) return fail(PGQ_ERR_INVALID_ARG, "child buffer too small: need " + std::to_string(rep.child_used) + " elements");
 		return PGQ_OK;
-	};
+	}
 	// Rows of few sources that are NOT grouped (a hash join's output order, a shuffled cross product): sorted by source — one
 	// radix sort of (source, row) over log2 V bits, one gather — they are the source-centric kernel's input after all; its
 	// answers (and those of the rows it leaves open) are scattered back by the sorted row index.  2.1 M rows: ~0.2 ms of
 	// sorting + 0.3 ms of kernel against 2.2 ms through the lane batches.  *took = false: the device's byte rule declined.
-	auto run_sorted_ball = [&](bool *took) -> int {
+	int run_sorted_ball(bool *took) {
 		*took = false;
 		const int64_t V = c->V;
 		for (DevBuf *b : { &ws->key, &ws->idx, &ws->skey, &ws->sidx }) PGQ_TRY(b->reserve((size_t)n * 4));
@@ -363,16 +388,15 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 		}
 		PrepassResult r;
 		PGQ_TRY(meet_prepass(c, ws, PrepassArgs { n, ws->sort_src.as<int64_t>(), ws->sort_dst.as<int64_t>(), ws->sort_out.as<int64_t>(), nullptr,
-		                                          meet_bytes, edge_bytes, DecideMode::None, BallMode::Only, outp.max_hops }, &r));
+		                                          meet_bytes, edge_bytes, DecideMode::None, BallMode::Only, ask.max_hops }, &r));
 		if (!r.ball_took) return PGQ_OK;
-		outp.route = 1;
-		outp.source_runs = r.est_sources;
+		rep.route = 1;
+		rep.source_runs = r.est_sources;
 		// what the kernel left open, in sorted positions: answered like run_prepass's open rows, applied to the sorted output
-		SearchOutput child;
-		child.no_ball = true;
-		child.no_memo = true;
-		PGQ_TRY(search_open_rows(c, ws, r.n_open, ws->open_src, ws->open_dst, child, outp, false, nullptr, 0, 0, false,
-		                         [&](bool) { return meet_apply(ws, r.n_open, ws->def_len.as<int64_t>(), ws->sort_out.as<int64_t>()); }));
+		OpenRows open { r.n_open, ws->open_src, ws->open_dst, SearchAsk(), 0, false };
+		open.ask.no_ball = true;
+		open.ask.no_memo = true;
+		PGQ_TRY(search_open_rows(c, ws, call, rep, open, [&](bool) { return meet_apply(ws, r.n_open, ws->def_len.as<int64_t>(), ws->sort_out.as<int64_t>()); }));
 		{
 			KernelTimer kt(st, K_PREP);
 			hipLaunchKernelGGL(k_sort_scatter, dim3(blocks_for(n)), dim3(256), 0, st, n, ws->sidx.as<u32>(), ws->sort_out.as<int64_t>(), d_out_len);
@@ -383,49 +407,19 @@ static int search_device_impl(pgq_csr *c, Workspace *ws, int64_t n, const int64_
 		KernelTimer::flush();
 		*took = true;
 		return PGQ_OK;
-	};
-
-	// ---- the routes, in order ----
-	bool sampled = false; // the sampled decision was asked for without the chain: read it after the next wait
-	if (prepass_takes(c, n, outp)) {
-		if (sort_allowed && read_memo && memo.sorted) { // these buffers went through the sort last time: straight there
-			bool took = false;
-			PGQ_TRY(run_sorted_ball(&took));
-			if (took) return PGQ_OK;
-			MemoOutcome o;
-			o.sorted = 0;
-			memo_record(c, n, d_src, d_dst, o);
-		}
-		if (decide && read_memo && memo.go == 0) {
-			sampled = true; // taken inside the lane assignment's first launch (k_mark_sources)
-		} else {
-			PrepassResult r;
-			PGQ_TRY(with_paths ? run_prepass_paths(r) : run_prepass(r));
-			if (write_memo) {
-				MemoOutcome o;
-				if ((ball == BallMode::Decide || ball == BallMode::Only) && outp.ball_hint < 0) o.ball = r.ball_took; // what the kernels said about these buffers
-				// these rows look like a cross product now: gated again next time
-				if (decide) o.go = r.answered && !(decide_mode == DecideMode::Ride && r.observed_go == 0 && !r.ball_took);
-				memo_record(c, n, d_src, d_dst, o);
-			}
-			if (r.answered) return PGQ_OK;
-			// neither the source-centric kernel (the rows are not grouped) nor the pre-pass (few distinct sources) took the call:
-			// with at least 64 rows per source on average a sort by source makes it the former's
-			if (sort_allowed && r.est_sources > 0 && r.est_sources * 64.0 <= (double)n) {
-				bool took = false;
-				PGQ_TRY(run_sorted_ball(&took));
-				if (write_memo) {
-					MemoOutcome o;
-					o.sorted = took;
-					memo_record(c, n, d_src, d_dst, o);
-				}
-				if (took) return PGQ_OK;
-			}
-		}
 	}
-	return search_lanes(c, ws, n, d_src, d_dst, d_out_len, with_paths, d_out_off, d_child_ext, child_cap_ext, outp, sampled, memo.ahead_wd,
-	                    meet_bytes, edge_bytes);
-}
+	// ---- the memo record: what the chain said about these buffers; whether the sort by source took them ----
+	void record(const MemoOutcome &o) { if (write_memo) memo_record(c, n, d_src, d_dst, o); }
+	void record_prepass(const PrepassResult &r) {
+		MemoOutcome o;
+		if ((ball == BallMode::Decide || ball == BallMode::Only) && ask.ball_hint < 0) o.ball = r.ball_took; // what the kernels said about these buffers
+		// these rows look like a cross product now: gated again next time
+		if (decide) o.go = r.answered && !(decide_mode == DecideMode::Ride && r.observed_go == 0 && !r.ball_took);
+		record(o);
+	}
+	void record_sorted(bool took) { MemoOutcome o; o.sorted = took; record(o); }
+};
+int search_device(pgq_csr *c, Workspace *ws, const SearchCall &call, SearchReport &rep) { return Route(c, ws, call, rep).search(); }
 
 static int check_csr(pgq_csr_t *csr, int64_t V) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "Constraint Error: Need to initialize CSR before doing shortest path");
@@ -481,8 +475,7 @@ int pgq_release_cached_memory(void) {
 }
 
 // max_hops: null = unbounded
-static int iterativelength_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                                bool bidir, const int64_t *max_hops = nullptr) {
+static int iterativelength_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len, bool bidir, const int64_t *max_hops = nullptr) {
 	const bool arrays = d_src && d_dst && d_out_len;
 	auto check = [&]() -> int {
 		PGQ_TRY(check_arrays(csr, n, arrays, "NULL device array"));
@@ -490,12 +483,13 @@ static int iterativelength_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src,
 		return PGQ_OK;
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		SearchOutput so;
-		so.bidir = bidir;
-		so.max_hops = max_hops ? search_bound(csr, *max_hops) : -1;
-		PGQ_TRY(search_device(csr, ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so));
-		if (so.max_hops >= 0 && n > 0) {
-			hipLaunchKernelGGL(k_clamp_hops, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, so.max_hops, d_out_len);
+		SearchCall call { n, d_src, d_dst, d_out_len };
+		call.ask.bidir = bidir;
+		call.ask.max_hops = max_hops ? search_bound(csr, *max_hops) : -1;
+		SearchReport rep;
+		PGQ_TRY(search_device(csr, ws, call, rep));
+		if (call.ask.max_hops >= 0 && n > 0) {
+			hipLaunchKernelGGL(k_clamp_hops, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, call.ask.max_hops, d_out_len);
 			PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
 		}
 		return PGQ_OK;
@@ -517,26 +511,26 @@ int pgq_traversed_edges_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_
                                     int64_t *d_out_len, int64_t *d_out_te) {
 	const bool arrays = d_src && d_dst && d_out_len && d_out_te;
 	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) -> int {
-		SearchOutput so;
-		so.want_te = true;
-		PGQ_TRY(search_device(csr, ws, n, d_src, d_dst, d_out_len, false, nullptr, nullptr, 0, so));
+		SearchCall call { n, d_src, d_dst, d_out_len };
+		call.ask.want_te = true;
+		SearchReport rep;
+		PGQ_TRY(search_device(csr, ws, call, rep));
 		if (n > 0) {
-			hipLaunchKernelGGL(k_scatter_te, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ws->sidx.as<u32>(),
-			                   ws->ste.as<int64_t>(), d_out_te);
+			hipLaunchKernelGGL(k_scatter_te, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, ws->sidx.as<u32>(), ws->ste.as<int64_t>(), d_out_te);
 			PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
 		}
 		return PGQ_OK;
 	});
 }
 
-int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                                 int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
-                                 int64_t *child_used) {
+int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
+                                 int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
 	const bool arrays = d_src && d_dst && d_out_len && d_out_offset && d_child;
 	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) {
-		SearchOutput so;
-		int rc = search_device(csr, ws, n, d_src, d_dst, d_out_len, true, d_out_offset, d_child, child_cap, so);
-		if (child_used) *child_used = so.child_used;
+		const SearchCall call { n, d_src, d_dst, d_out_len, SearchPaths { d_out_offset, d_child, child_cap } };
+		SearchReport rep;
+		int rc = search_device(csr, ws, call, rep);
+		if (child_used) *child_used = rep.child_used;
 		return rc;
 	});
 }
@@ -554,9 +548,8 @@ int pgq_iterativelength_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, con
 		const size_t bytes = (size_t)(hi - lo) * 8;
 		PGQ_TRY(ws->out_len.reserve(bytes));
 		PGQ_TRY(stage_pairs(ws, hi - lo, src + lo, dst + lo));
-		SearchOutput so;
-		PGQ_TRY(search_device(replica, ws, hi - lo, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(),
-		                      ws->out_len.as<int64_t>(), false, nullptr, nullptr, 0, so));
+		SearchReport rep;
+		PGQ_TRY(search_device(replica, ws, SearchCall { hi - lo, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>() }, rep));
 		return staged_download(out_len + lo, ws->out_len.p, bytes, ws->stream);
 	};
 	return c_entry<false>(csr, check, [&] { return run_shards(csr, n, shard); });
@@ -578,8 +571,7 @@ int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const 
 	auto shard = [&](int k, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
 		const int64_t m = hi - lo;
 		const size_t bytes = (size_t)m * 8;
-		PGQ_TRY(ws->out_len.reserve(bytes));
-		PGQ_TRY(ws->out_off.reserve(bytes));
+		for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve(bytes));
 		PGQ_TRY(stage_pairs(ws, m, src + lo, dst + lo));
 		DevBuf dchild; // not a workspace buffer: search_device uses ws->child for its own staging
 		int64_t cap = std::max<int64_t>(16 * m, 1024), used = 0;
@@ -587,10 +579,10 @@ int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const 
 		for (int attempt = 0; attempt < 2; attempt++) {
 			rc = dchild.reserve((size_t)cap * 8);
 			if (rc != PGQ_OK) break;
-			SearchOutput so;
-			rc = search_device(replica, ws, m, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
-			                   true, ws->out_off.as<int64_t>(), dchild.as<int64_t>(), cap, so);
-			used = so.child_used;
+			const SearchCall call { m, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(), SearchPaths { ws->out_off.as<int64_t>(), dchild.as<int64_t>(), cap } };
+			SearchReport rep;
+			rc = search_device(replica, ws, call, rep);
+			used = rep.child_used;
 			if (rc == PGQ_OK || used <= cap) break;
 			cap = used; // too small: the search reported what it needs
 		}
@@ -685,7 +677,10 @@ static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
 		const int64_t bound = max_hops ? search_bound(csr, *max_hops) : -1;
 		const int64_t top = bound < 0 ? INT64_MAX : bound; // lengths above it are NULL
-		if (!bidir && options().chunk_zero_copy && prepass_takes(csr, n, SearchOutput()) && n <= kMeetDecideRows) {
+		SearchAsk ask; // of either branch: a chunk's staging buffers say nothing to the route memo (SearchAsk::no_memo)
+		ask.no_memo = true;
+		ask.max_hops = bound;
+		if (!bidir && options().chunk_zero_copy && prepass_takes(csr, n, SearchAsk()) && n <= kMeetDecideRows) {
 			// One DuckDB chunk through the pair-centric kernels: they read the rows straight out of a pinned staging block and
 			// write the hop counts straight back into it (2048 rows = 32 KB in, 16 KB out over PCIe, one access per row), so the
 			// call is two or three kernel launches and ONE wait — no copy commands (each is a stream operation of its own:
@@ -694,15 +689,14 @@ static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t
 			PGQ_TRY(io_block(ws, (size_t)n * 24, &hp, &dp));
 			int64_t *h = static_cast<int64_t *>(hp), *d = static_cast<int64_t *>(dp);
 			PGQ_TRY(flatten_pairs_into(V, n, src, dst, h, h + n));
-			SearchOutput so;
-			so.no_memo = true;
-			so.max_hops = bound;
+			SearchCall call { n, d, d + n, d + 2 * n, std::nullopt, ask };
 			{ // the rows are in host memory: whether they are grouped by source costs a pass over 2048 words here, two launches there
 				int64_t runs = 1;
 				for (int64_t i = 1; i < n; i++) runs += h[i] != h[i - 1];
-				so.ball_hint = runs * 8 <= n ? 1 : 0;
+				call.ask.ball_hint = runs * 8 <= n ? 1 : 0;
 			}
-			PGQ_TRY(search_device(csr, ws, n, d, d + n, d + 2 * n, false, nullptr, nullptr, 0, so));
+			SearchReport rep;
+			PGQ_TRY(search_device(csr, ws, call, rep));
 			const int64_t *res = h + 2 * n;
 			for (int64_t w = 0; w < (n + 63) / 64; w++) { // payload of a NULL row stays -1 like iterativelength.cpp:100,137
 				uint64_t m = 0;
@@ -720,12 +714,10 @@ static int iterativelength_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t
 		PGQ_TRY(flatten_pairs(V, n, src, dst, fp, false));
 		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
 		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
-		SearchOutput so;
-		so.bidir = bidir;
-		so.no_memo = true;
-		so.max_hops = bound;
-		PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
-		                      false, nullptr, nullptr, 0, so));
+		SearchCall call { n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(), std::nullopt, ask };
+		call.ask.bidir = bidir;
+		SearchReport rep;
+		PGQ_TRY(search_device(csr, ws, call, rep));
 		PGQ_TRY(staged_download(out_len, ws->out_len.p, (size_t)n * 8, ws->stream));
 		mask_fill_valid(out_valid, n);
 		for (int64_t i = 0; i < n; i++) {
@@ -761,19 +753,17 @@ int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_ve
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
 		FlatPairs fp;
 		PGQ_TRY(flatten_pairs(V, n, src, dst, fp, false));
-		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
-		PGQ_TRY(ws->out_off.reserve((size_t)n * 8));
+		for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve((size_t)n * 8));
 		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
-		SearchOutput so;
-		so.no_memo = true;
-		PGQ_TRY(search_device(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(),
-		                      true, ws->out_off.as<int64_t>(), nullptr, 0, so));
+		SearchCall call { n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(), SearchPaths { ws->out_off.as<int64_t>() } };
+		call.ask.no_memo = true;
+		SearchReport rep;
+		PGQ_TRY(search_device(csr, ws, call, rep));
 		std::vector<int64_t> len(n), off(n);
 		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
 		PGQ_TRY(staged_download(off.data(), ws->out_off.p, (size_t)n * 8, ws->stream));
-		t_child.resize((size_t)so.child_used);
-		if (so.child_used > 0)
-			PGQ_TRY(staged_download(t_child.data(), ws->child.p, (size_t)so.child_used * 8, ws->stream));
+		t_child.resize((size_t)rep.child_used);
+		if (rep.child_used > 0) PGQ_TRY(staged_download(t_child.data(), ws->child.p, (size_t)rep.child_used * 8, ws->stream));
 		mask_fill_valid(out_valid, n);
 		for (int64_t i = 0; i < n; i++) {
 			if (len[i] < 0) {
@@ -786,7 +776,7 @@ int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_ve
 			}
 		}
 		*out_child = t_child.data();
-		*out_child_len = (uint64_t)so.child_used;
+		*out_child_len = (uint64_t)rep.child_used;
 		return PGQ_OK;
 	});
 }

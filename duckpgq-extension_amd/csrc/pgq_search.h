@@ -2,6 +2,7 @@
 #pragma once
 #include <cmath>
 #include <memory>
+#include <optional>
 #include <type_traits>
 
 #include "pgq_internal.h"
@@ -420,14 +421,10 @@ int prepare_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, co
 int batch_bounds(Workspace *ws, int64_t n, int64_t L, int nb);
 
 // ---- the BFS driver (pgq_route.hip picks the route, pgq_msbfs.hip runs the lane batches) ------------------------------
-// What a search_device call is asked for beside the lengths, and what it reports back.  with_paths: [src,e,v,...,dst]
-// lists go into the caller's child buffer (d_child_ext) or ws->child, with per-row offsets.
-struct SearchOutput {
-	int64_t child_used = 0;
+// What a search is asked for beside the lengths.  The caller owns it: no callee writes into it.
+struct SearchAsk {
 	bool want_te = false; // fill ws->ste with per-row traversed-edge counts
 	int depth = 0;        // nesting level of the straggler pass
-	bool deferred = false;
-	bool overflow = false; // the caller's child buffer was too small (lengths are still complete)
 	bool bidir = false;    // iterativelengthbidirectional: every row through the per-row bidirectional search first
 	bool from_meet = false; // these rows are what the pair-centric pre-pass left open: do not run it on them again
 	bool no_ball = false;   // these rows are what the source-centric kernel left open: the pre-pass may take them, that kernel not again
@@ -436,34 +433,46 @@ struct SearchOutput {
 	// remembers about "these buffers" says nothing about THESE rows (round-5 advisor finding: unrelated chunks hit the memo,
 	// and every change of shape was routed one call late) — such calls neither read nor write it
 	bool no_memo = false;
-	bool prefer_lanes = false; // (in) large grouped call on a graph where the lane batches measured faster than the source-centric route, or their trial
 	// iterativelength_within: >= 0 = a row whose distance exceeds it is NULL; negative = unbounded.  Every stage stops where the
 	// bound lets it and the open rows' searches inherit it, but no stage is relied on to: the entry point clamps what comes back
 	// (a lane batch's probes answer rows a level or two ahead, k_meet4d reports 4 for a cut row under a bound of 3).  A bounded
 	// call is off the record of what unbounded calls are routed by (route memo, route timing, ball_open_frac, the refinement of
 	// meet_bpr, meet_far_rows; its lane batches store no level plan): a bounded row costs something else.
 	int64_t max_hops = -1;
-	int route = 0;             // (out) 1: the source-centric kernel took the call (as it lay, or sorted by source)
-	double source_runs = -1;   // (out) ... and counted this many source runs
+};
+// What a search reports back beside the lengths; written by the route that answered and by search_open_rows.
+struct SearchReport {
+	int64_t child_used = 0;  // elements of the path lists (all of them, also when they did not fit)
+	bool overflow = false;   // the caller's child buffer was too small (lengths are still complete)
+	int route = 0;           // 1: the source-centric kernel took the call (as it lay, or sorted by source)
+	double source_runs = -1; // ... and counted this many source runs
+};
+// shortestpath: [src,e,v,...,dst] lists go into the caller's child buffer (d_child_ext) or ws->child, with per-row offsets
+struct SearchPaths { int64_t *d_out_off = nullptr, *d_child_ext = nullptr, child_cap_ext = 0; };
+// The rows of one search (-1 src = NULL row), resident in device memory, and where the answers go
+struct SearchCall {
+	int64_t n = 0;
+	const int64_t *d_src = nullptr, *d_dst = nullptr;
+	int64_t *d_out_len = nullptr;
+	std::optional<SearchPaths> paths; // present: shortestpath
+	SearchAsk ask;
 };
 // every wait of the lane-batched search on its stream is counted (pgq_stats_t::host_waits)
-#define PGQ_WAIT(stream)                                                                                               \
-	do {                                                                                                               \
-		PGQ_TRY(wait_stream(stream, thread_wait_event()));                                                          \
-		tstats().s.host_waits++;                                                                                       \
-	} while (0)
+#define PGQ_WAIT(stream) do { PGQ_TRY(wait_stream(stream, thread_wait_event())); tstats().s.host_waits++; } while (0)
 // A bigger buffer with the first `keep` bytes of the old one (waited for).
 int grow_keeping(DevBuf &buf, size_t bytes, size_t keep, hipStream_t st);
-// Answers n rows resident in device memory (d_src/d_dst, -1 src = NULL row) by whichever route pays: the per-row
-// bidirectional search, the source-centric kernel, the pair-centric pre-pass, the lane batches (pgq_route.hip).
-int search_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                  bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp);
+// Answers the call's rows by whichever route pays: the per-row bidirectional search, the source-centric kernel, the
+// pair-centric pre-pass, the lane batches (pgq_route.hip).
+int search_device(pgq_csr *c, Workspace *ws, const SearchCall &call, SearchReport &rep);
 // The lane-batched MS-BFS (pgq_msbfs.hip): lane assignment, the batches, the straggler pass, results back to row order.
 // sampled: the route memo sent the rows here without the pre-pass (the sample rides in the lane assignment's first launch);
 // ahead_wd: the memo's width for stage 2 ahead of the wait (MemoVerdict; -1: not looked up yet).
-int search_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                 bool with_paths, int64_t *d_out_off, int64_t *d_child_ext, int64_t child_cap_ext, SearchOutput &outp,
-                 bool sampled, int ahead_wd, double meet_bytes, double edge_bytes);
+struct LanesPlan {
+	bool sampled;
+	int ahead_wd;
+	double meet_bytes, edge_bytes; // the byte rule's two sides, for the sample
+};
+int search_lanes(pgq_csr *c, Workspace *ws, const SearchCall &call, SearchReport &rep, const LanesPlan &lp);
 // The route memo (pgq_csr::RouteMemo): what it says about n rows on these buffers, and what a call records there
 // (fields left at -1 / false are not written; an empty outcome takes no lock).
 struct MemoVerdict {
@@ -480,45 +489,56 @@ struct MemoOutcome {
 };
 void memo_record(pgq_csr *c, int64_t n, const void *src, const void *dst, const MemoOutcome &o);
 
-// The rows a route left open (nd at src / dst), searched again one level deeper on a workspace of their own with the
-// caller's flags in `child`; S.pairs counts them once.  Lengths land in ws->def_len; with_paths: offsets in ws->def_off,
-// lists appended behind `base` elements of the caller's child buffer (d_child_ext, else ws->child grown to fit;
-// outp.overflow / outp.child_used as for the caller's own lists).  apply(lists appended) puts the results in place; the
-// stream is waited for before the inner workspace goes back when `wait` says so or lists were appended.
+// The rows a route left open (nd at src / dst), searched again one level deeper on a workspace of their own as `ask` says;
+// S.pairs counts them once.  Lengths land in ws->def_len; a parent with paths: offsets in ws->def_off, lists appended behind
+// `base` elements of the parent's child buffer (d_child_ext, else ws->child grown to fit; rep.overflow / rep.child_used as
+// for the parent's own lists).  apply(lists appended) puts the results in place; the stream is waited for before the inner
+// workspace goes back when `wait` says so or lists were appended.
+struct OpenRows {
+	u32 nd;
+	const int64_t *src, *dst;
+	SearchAsk ask; // depth, max_hops (and with it no_memo) are the parent's say: set below
+	int64_t base = 0;
+	bool wait = true;
+};
 template <typename Apply>
-int search_open_rows(pgq_csr *c, Workspace *ws, u32 nd, const int64_t *src, const int64_t *dst, SearchOutput child, SearchOutput &outp,
-                     bool with_paths, int64_t *d_child_ext, int64_t child_cap_ext, int64_t base, bool wait, Apply &&apply) {
+int search_open_rows(pgq_csr *c, Workspace *ws, const SearchCall &parent, SearchReport &rep, const OpenRows &open, Apply &&apply) {
 	hipStream_t st = ws->stream;
+	const u32 nd = open.nd;
 	WorkspaceLease inner;
+	SearchReport child_rep;
 	if (nd > 0) {
 		PGQ_TRY(ws->def_len.reserve((size_t)nd * 8));
-		if (with_paths) PGQ_TRY(ws->def_off.reserve((size_t)nd * 8));
+		SearchCall child { nd, open.src, open.dst, ws->def_len.as<int64_t>(), std::nullopt, open.ask };
+		if (parent.paths) {
+			PGQ_TRY(ws->def_off.reserve((size_t)nd * 8));
+			child.paths = SearchPaths { ws->def_off.as<int64_t>(), nullptr, 0 };
+		}
 		PGQ_TRY(inner.acquire());
-		child.depth = outp.depth + 1;
-		child.max_hops = outp.max_hops;
-		if (child.max_hops >= 0) child.no_memo = true;
+		child.ask.depth = parent.ask.depth + 1;
+		child.ask.max_hops = parent.ask.max_hops;
+		if (child.ask.max_hops >= 0) child.ask.no_memo = true;
 		tstats().s.pairs -= nd; // counted once
-		PGQ_TRY(search_device(c, inner.ws, nd, src, dst, ws->def_len.as<int64_t>(), with_paths, with_paths ? ws->def_off.as<int64_t>() : nullptr,
-		                      nullptr, 0, child));
+		PGQ_TRY(search_device(c, inner.ws, child, child_rep));
 	}
 	bool lists = false;
-	if (with_paths) { // the open rows' lists land in the inner workspace's child buffer: appended behind the caller's
-		const int64_t need = base + child.child_used;
-		int64_t *d_child = d_child_ext;
-		if (d_child_ext) {
-			if (need > child_cap_ext) outp.overflow = true;
+	if (parent.paths) { // the open rows' lists land in the inner workspace's child buffer: appended behind the parent's
+		const int64_t need = open.base + child_rep.child_used;
+		int64_t *d_child = parent.paths->d_child_ext;
+		if (d_child) {
+			if (need > parent.paths->child_cap_ext) rep.overflow = true;
 		} else {
-			if ((size_t)need * 8 > ws->child.cap) PGQ_TRY(grow_keeping(ws->child, (size_t)need * 8, (size_t)base * 8, st));
+			if ((size_t)need * 8 > ws->child.cap) PGQ_TRY(grow_keeping(ws->child, (size_t)need * 8, (size_t)open.base * 8, st));
 			d_child = ws->child.as<int64_t>();
 		}
-		lists = !outp.overflow; // (lengths are still reported when the lists did not fit)
-		if (lists && child.child_used > 0)
-			PGQ_HIP_TRY(hipMemcpyAsync(d_child + base, inner.ws->child.p, (size_t)child.child_used * 8, hipMemcpyDeviceToDevice, st));
-		outp.child_used = need;
+		lists = !rep.overflow; // (lengths are still reported when the lists did not fit)
+		if (lists && child_rep.child_used > 0)
+			PGQ_HIP_TRY(hipMemcpyAsync(d_child + open.base, inner.ws->child.p, (size_t)child_rep.child_used * 8, hipMemcpyDeviceToDevice, st));
+		rep.child_used = need;
 	}
 	if (nd == 0) return PGQ_OK;
 	PGQ_TRY(apply(lists));
-	if (wait || lists) {
+	if (open.wait || lists) {
 		PGQ_WAIT(st); // the inner workspace goes back to the pool after this
 		KernelTimer::flush();
 	}

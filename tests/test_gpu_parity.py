@@ -500,6 +500,7 @@ def test_source_centric_ball_is_chosen_by_the_source_runs():
             ln, ok = st.iterativelength(0, V, ps, pd)
             assert lens(ln, ok) == [int(v) if k else None for v, k in zip(oln, ook)]
             assert (pgq.get_stats()["ball_calls"] >= 1) == expect_ball, (per, rep, pgq.get_stats())
+            assert pgq.get_stats()["pairs"] == len(ps)  # rows handed on (ball -> open rows -> pre-pass -> open rows -> lanes) count once
     # the same device buffers, first grouped (the kernel takes them: the next chain on these buffers is its two kernels alone),
     # then overwritten in place with scattered pairs: that chain declines and the stage kernels run after all
     import torch
@@ -509,7 +510,9 @@ def test_source_centric_ball_is_chosen_by_the_source_runs():
     t_s, t_d = torch.from_numpy(ps).cuda(), torch.from_numpy(pd).cuda()
     t_o = torch.empty(len(ps), dtype=torch.int64, device="cuda")
     for rep in range(2):
+        pgq.reset_stats()
         dev.iterativelength_bulk_ptr(len(ps), t_s.data_ptr(), t_d.data_ptr(), t_o.data_ptr())
+        assert pgq.get_stats()["pairs"] == len(ps)
     oln, ook = ora.lean_iterativelength(V, ps, pd, nthreads=4)
     assert (t_o.cpu().numpy() == np.where(ook, oln, -1)).all()
     ps2 = rng.integers(0, V, len(ps))
@@ -520,6 +523,7 @@ def test_source_centric_ball_is_chosen_by_the_source_runs():
         dev.iterativelength_bulk_ptr(len(ps), t_s.data_ptr(), t_d.data_ptr(), t_o.data_ptr())
         assert (t_o.cpu().numpy() == np.where(ook, oln, -1)).all()
         assert pgq.get_stats()["ball_calls"] == 0
+        assert pgq.get_stats()["pairs"] == len(ps)
     # 3 sources x every vertex: one narrow lane batch is cheaper than 60 balls + 60,000 in-list scans
     ps = np.repeat(srcs[:3], V)
     pd = np.tile(np.arange(V, dtype=np.int64), 3)
@@ -527,6 +531,7 @@ def test_source_centric_ball_is_chosen_by_the_source_runs():
     pgq.reset_stats()
     ln, ok = st.iterativelength(0, V, ps, pd)
     assert (ok == ook).all() and (ln[ok] == oln[ok]).all()
+    assert pgq.get_stats()["pairs"] == len(ps)
 
 
 def test_large_grouped_calls_keep_the_route_that_measured_faster():
@@ -1192,11 +1197,13 @@ def test_bulk_device_entry_points_match_chunk_api():
         assert got == want
         assert got == dev.shortestpath(ps, pd)
         # too small a child buffer: error status, `used` reports what is needed, lengths are still right
-        small = torch.empty(need // 2, dtype=torch.int64, device="cuda")
-        rc, used = dev.shortestpath_bulk_ptr(n, d_src.data_ptr(), d_dst.data_ptr(), d_len.data_ptr(), d_off.data_ptr(),
-                                             small.data_ptr(), need // 2)
-        assert rc != 0 and used == need
-        assert (d_len.cpu().numpy() == ln).all()
+        # (need - 1: only the last list does not fit — with stragglers or open rows appended, the overflow is the nested search's)
+        for cap in (need // 2, need - 1):
+            small = torch.empty(cap, dtype=torch.int64, device="cuda")
+            rc, used = dev.shortestpath_bulk_ptr(n, d_src.data_ptr(), d_dst.data_ptr(), d_len.data_ptr(), d_off.data_ptr(),
+                                                 small.data_ptr(), cap)
+            assert rc != 0 and used == need, (words, defer, meet, cap, rc, used, need)
+            assert (d_len.cpu().numpy() == ln).all()
     pgq.set_option("words", 0)
     pgq.set_option("defer", 8)
     pgq.set_option("meet", 0)
