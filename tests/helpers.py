@@ -162,7 +162,13 @@ def degree_gadgets(degrees=GADGET_DEGREES, positions=GADGET_POSITIONS, extra_pai
     Tie gadgets (tag tie<n>_...): n = 2, 3 disjoint shortest paths through the first, the last (and a middle) slot of src's
     out-list, whose vertex ids DEscend in slot order, and ascend again on the destination's side for k >= 3.
 
-    Extra rows per gadget: src -> a sink of one of its decoys and a root -> dst (distance 2), dst -> src (unreachable)."""
+    Extra rows per gadget: src -> a sink of one of its decoys and a root -> dst (distance 2), dst -> src (unreachable).
+
+    Two parameter sets are in use.  The defaults sit on the constants of the unweighted search kernels
+    (test_degree_gadgets_cpu.py, test_degree_edges_gpu.py); WEIGHTED_GADGETS sits on those of the cheapest-path relaxation
+    and is given weights by weighted_gadgets (test_weighted_gadgets_cpu.py, test_weighted_gadgets_gpu.py).  A numbered position
+    takes its decoys from pool 0 before it and from pool 1 behind it, so no degree may pass 4097 and no numbered position 320:
+    a longer list would silently come out shorter."""
     enc = lambda region, serial: (np.int64(region) << 32) + np.asarray(serial, dtype=np.int64)
     count = [0] * 7
 
@@ -299,6 +305,73 @@ def degree_gadgets(degrees=GADGET_DEGREES, positions=GADGET_POSITIONS, extra_pai
         g["paths"] = [[int(v) for v in real(p)] for p in g["paths"]]
     return Gadgets(int(base[-1]), real(np.concatenate(es)), real(np.concatenate(ed)), real(rs), real(rd),
                    np.array(dist, dtype=np.int64), np.array(tag), gadgets)
+
+
+# ---- the same gadgets on the constants of the cheapest-path relaxation (pgq_cheapest.hip), with weights by slot ------------
+# k_relax walks eight edges per trip (7, 8, 9 / 15, 16, 17 / 71, 72, 73), sets a list of more than 128 edges aside and walks
+# it in chunks of 64 (63 .. 65, 127 .. 130, 191 .. 193), and fills the chunk map 64 chunks per trip: 4097 edges are 65 chunks
+WEIGHTED_GADGETS = dict(
+    degrees=(1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 71, 72, 73, 127, 128, 129, 130, 191, 192, 193, 4095, 4096, 4097),
+    positions=("first", "last", 7, 8, 63, 64, 127, 128, 191, 192),
+    extra_pairings=((129, 4097),),
+    tie_degrees=(9, 129))
+WEIGHT_SCHEMES = ("ascending", "descending", "witness_heaviest", "zeros")
+WEIGHT_DTYPES = ("int64", "double", "double_inexact")
+
+
+def edge_slots(g):
+    """Per edge-table row of a Gadgets object: its slot in its source's out-list (table order is slot order) and the
+    list's length."""
+    order = np.argsort(g.src, kind="stable")
+    deg = np.bincount(g.src, minlength=g.V)
+    start = np.concatenate([[0], np.cumsum(deg)])
+    slot = np.empty(len(g.src), dtype=np.int64)
+    slot[order] = np.arange(len(g.src), dtype=np.int64) - start[g.src[order]]
+    return slot, deg[g.src].astype(np.int64)
+
+
+def path_edge_rows(g):
+    """The edge-table rows that lie on a gadget's path(s)."""
+    key = g.src * g.V + g.dst
+    on = {u * g.V + v for x in g.gadgets for p in x["paths"] for u, v in zip(p[:-1], p[1:])}
+    return np.isin(key, np.fromiter(on, dtype=np.int64, count=len(on)))
+
+
+def weighted_gadgets(g, scheme, dtype="int64"):
+    """One weight per edge-table row of g, a function of the row's slot i in its source's out-list of length deg alone:
+      ascending         1 + i: the weight-sorted rank is the slot, and 2^j / 2^j + 1 sit at slots 2^j - 1 / 2^j
+      descending        deg - i: sorting reverses every list
+      witness_heaviest  1, but deg + 1 on the edges of the gadgets' paths: such an edge sorts last, behind deg - 1 equal keys
+      zeros             0 (doubles: +0.0 in even slots, -0.0 in odd ones)
+    dtype: int64; double = the int64 weights x 0.125 (every sum exact); double_inexact = x 0.1 (sums round: only the left
+    fold along the path gives the reference's bits).  Weights of g.transposed() go by ITS out-lists, the former in-lists."""
+    slot, deg = edge_slots(g)
+    if scheme == "ascending":
+        w = 1 + slot
+    elif scheme == "descending":
+        w = deg - slot
+    elif scheme == "witness_heaviest":
+        w = np.where(path_edge_rows(g), deg + 1, 1)
+    elif scheme == "zeros":
+        w = np.zeros(len(slot), dtype=np.int64)
+    else:
+        raise ValueError(scheme)
+    if dtype == "int64":
+        return w.astype(np.int64)
+    f = w.astype(np.float64) * {"double": 0.125, "double_inexact": 0.1}[dtype]
+    if scheme == "zeros":
+        f = np.where(slot % 2 == 1, -0.0, 0.0)
+    return f
+
+
+def weight_sort_keys(w):
+    """The keys ensure_weight_sorted sorts a list by: the weight's bit pattern; for doubles without the sign of -0.0 and with
+    NaN counted as +inf (k_weight_keys)."""
+    w = np.ascontiguousarray(w)
+    bits = w.view(np.uint64)
+    if w.dtype.kind == "f":
+        bits = np.minimum(bits & np.uint64(0x7FFFFFFFFFFFFFFF), np.uint64(0x7FF0000000000000))
+    return bits
 
 
 LCC_DEGREES = (2, 64, 65, 511, 512, 513)
