@@ -75,6 +75,9 @@ def load_hip():
         getattr(L, f).argtypes = [C.c_void_p]
     L.pgq_csr_w_type.argtypes = [C.c_void_p]
     L.pgq_csr_pack_k.argtypes = [C.c_void_p]
+    L.pgq_csr_pack_order.argtypes = [C.c_void_p]
+    L.pgq_csr_packed_list.restype = C.c_int64
+    L.pgq_csr_packed_list.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
     L.pgq_debug_live_device_blocks.restype = C.c_int64
     L.pgq_debug_live_device_blocks.argtypes = []
     L.pgq_iterativelength.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
@@ -350,6 +353,19 @@ class DeviceCSR:
     def pack_k(self):
         """Ids per 16-byte group of the lists the pre-pass walks (6 / 5: bit-packed, 4: 32-bit)."""
         return self.L.pgq_csr_pack_k(self.h)
+
+    @property
+    def pack_order(self):
+        """1: the packed lists are in degree order and walked heads first (option meet_pack_order at upload), else 0."""
+        return self.L.pgq_csr_pack_order(self.h)
+
+    def packed_list(self, direction, v):
+        """Vertex v's bit-packed list, decoded, in the order the walks read it (0: forward, 1: reverse)."""
+        n = self.L.pgq_csr_packed_list(self.h, direction, v, None, 0)
+        _check(min(n, 0))
+        out = np.zeros(max(int(n), 1), dtype=np.int32)
+        _check(min(self.L.pgq_csr_packed_list(self.h, direction, v, out.ctypes.data, n), 0))
+        return out[:n]
 
     # -- chunk form (host arrays) ----------------------------------------------
     def _vecs(self, src, dst, src_valid, src_sel, dst_sel, dst_valid, keep):

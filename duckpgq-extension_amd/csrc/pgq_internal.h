@@ -167,6 +167,7 @@ struct Options {
 	int meet_align = 32;    // entries a padded list is aligned and padded to (4 = one 16-byte group; 16 / 32 = whole 64 / 128-byte lines: -4 % / -6 % on the pre-pass)
 	int meet_pack = 1;      // bit-packed copy of the padded lists (pgq_pack.h), walked by k_meet3 / k_meet3w: 1 = for V <= 2^21 (six 21-bit ids per group); 2 = also V <= 2^25 (five 25-bit ids; not measured on R-MAT-22 yet); 0: 32-bit lists only
 	int meet_pack_align = 8; // groups a packed list is aligned and padded to (8 = one 128-byte line)
+	int meet_pack_order = 1; // the packed lists are ordered by non-increasing length bucket of their entries' lists in the other direction and walked heads first (pgq_pack.h); 0: the CSR's order, walked whole.  Read at upload
 	// round 6: source-centric search for rows that arrive grouped by source (pgq_ball.h: k_ball_segments + k_src_ball)
 	int ball = 1;               // 1: the device decides per call from the number of source runs; 2: always when allowed (tests); 0: never
 	int ball_cap = 1 << 20;     // adjacency entries the two-hop ball of one source may hold; a segment over it leaves its far rows open
@@ -288,6 +289,8 @@ struct pgq_csr {
 	int32_t *ppadj = nullptr, *prpadj = nullptr; // 4 words x ppadj_groups / prpadj_groups
 	int64_t ppadj_groups = 0, prpadj_groups = 0;
 	int pack_k = 4;
+	int pack_order = 0; // 1: the packed lists are in degree order (option meet_pack_order at upload) and walked in two parts
+	int pack_align = 1; // groups the packed lists were aligned to at upload (pgq_csr_packed_list finds a list by it)
 	std::unique_ptr<pgq::Options> opt;   // this handle's own options (pgq_csr_set_option); null: the process-wide set
 	std::atomic<int> meet_far_rows { 1 }; // the last pre-pass call left rows for k_bibfs (it is launched only then; pgq_meet.hip)
 	int64_t hub_threshold = 0;

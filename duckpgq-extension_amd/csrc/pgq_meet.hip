@@ -251,6 +251,9 @@ namespace pgq {
 // PATHS: also record the path's inner vertices (MeetPath); the walk then runs from dst over the source-ordered in-lists.
 // BIGV: V > 2^20, the filter folds the higher id bits in.  DEPTH: list requests in flight.  K: ids per list group
 // (pgq_pack.h; K > 4: padj / rpadj are the packed copies).  PATHS walks the 32-bit lists.
+// split (K > 4; the handle's pack_order): the packed lists are in degree order and the walk takes the heads of all the row's
+// lists before their tails (two seg_walk calls).  The cap bounds both parts together; a walk cut among the heads is taken up from
+// its start by the next stage, one cut among the tails in the tails' round; distance >= 4 is known only after both parts.
 // BND (iterativelength_within): rows farther apart than `bound` hops are NULL.  bound <= 2: the one-hop tests decide the row
 // and the two-hop walk is not started; bound == 3: a walk that ran to its END without a witness proves distance >= 4 — NULL
 // here, not queued.  A walk that was CUT proves nothing beyond distance >= 3: that row stays open whatever the bound, and
@@ -265,7 +268,7 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
                                                   const u32 *__restrict__ fwork, const u32 *__restrict__ rwork,
                                                   int64_t *__restrict__ out, MeetPath *__restrict__ rec, int64_t cap,
                                                   const u32 *__restrict__ go, MeetDevBlock *__restrict__ db, MeetQueue q,
-                                                  MeetHostBlock *__restrict__ fin, int bound) {
+                                                  MeetHostBlock *__restrict__ fin, int bound, bool split) {
 	static_assert(!PATHS || !BND, "a bounded search returns hop counts only");
 	static_assert(kMeetWPB == 1, "one wavefront per workgroup: the LDS arrays are addressed statically");
 	static_assert(!PATHS || K == 4, "the path flow walks the 32-bit lists");
@@ -434,24 +437,43 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 		const unsigned long long rt1 = wall_clock64();
 		const unsigned long long ent_before = entries;
 #endif
-		const unsigned long long e3 = seg_walk<DEPTH, PATHS, K>(
-		    exp_desc, exp_n, 0, 1, xp, win, true, d0, (unsigned long long)cap, capped, resume,
-		    [&](const typename SegGroup<K>::type &v, bool ok, u32 ev) {
-			    // a lane past the round's end re-reads real entries of the last list: no mask needed for membership;
-			    // PATHS masks them (their ev is the last list's, so they would even be right, but cost a verification)
-			    const u32 pass = (PATHS && !ok) ? 0u : flt_pass<BIGV>(bm, v);
-			    verify_candidates(R, pass, v, [&](u32 x, int L) {
-				    if constexpr (PATHS) { // backward walk: expanded vertex = second-to-last, entry = the one before it
-					    const u32 y = (u32)__builtin_amdgcn_readlane((int)ev, L);
-					    best = min(best, (u64)y << 32 | x);
-					    return false;
-				    } else {
-					    best = 0;
-					    return true;
-				    }
-			    });
-		    },
-		    [&]() { return best != ~0ull; });
+		auto test = [&](const typename SegGroup<K>::type &v, bool ok, u32 ev) {
+			// a lane past the round's end re-reads real entries of the last list: no mask needed for membership;
+			// PATHS masks them (their ev is the last list's, so they would even be right, but cost a verification)
+			const u32 pass = (PATHS && !ok) ? 0u : flt_pass<BIGV>(bm, v);
+			verify_candidates(R, pass, v, [&](u32 x, int L) {
+				if constexpr (PATHS) { // backward walk: expanded vertex = second-to-last, entry = the one before it
+					const u32 y = (u32)__builtin_amdgcn_readlane((int)ev, L);
+					best = min(best, (u64)y << 32 | x);
+					return false;
+				} else {
+					best = 0;
+					return true;
+				}
+			});
+		};
+		auto done = [&]() { return best != ~0ull; };
+		// K > 4 and `split` (the packed lists are in degree order, pgq_pack.h): the heads of all lists first, then the tails
+		unsigned long long e3 = seg_walk<DEPTH, PATHS, K>(exp_desc, exp_n, 0, 1, xp, win, true, d0, (unsigned long long)cap, capped, resume,
+		                                                  test, done, 0, K > 4 && split);
+		if constexpr (K > 4) {
+			if (split) {
+				// cut among the heads: the tails of the rounds before are unwalked too, the next stage starts over
+				if (capped) resume = 0;
+				if (best == ~0ull && !capped) {
+					// Two calls, not a loop over the parts: d0 would stay live across it (44 B of scratch per lane), so the tails'
+					// descriptors are read again.  The cap bounds both parts together; what is left of it goes into scalar
+					// registers, where `cap` itself sits (in VGPRs it cost 12 B of scratch per lane).  Cut here: every head has been
+					// walked, and the tails before `resume`: the next stage walks whole lists from that round on, a superset of the rest
+					const unsigned long long left = uniform_u64((unsigned long long)cap - min((unsigned long long)cap, e3));
+					entries += e3;
+					walked += e3;
+					e3 = seg_walk<DEPTH, PATHS, K>(exp_desc, exp_n, 0, 1, xp, win, false, make_uint4(0, 0, 0, 0), left, capped, resume,
+					                               test, done, 1, true);
+					vertices += (u32)exp_n; // the descriptors, a second time
+				}
+			}
+		}
 		entries += e3;
 		if (K > 4) walked += e3;
 		const bool found = best != ~0ull;
@@ -501,7 +523,8 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
                                                     const int32_t *__restrict__ padj, const int32_t *__restrict__ rpadj,
                                                     const u32 *__restrict__ fwork, const u32 *__restrict__ rwork,
                                                     int64_t *__restrict__ out, int64_t cap, const u32 *__restrict__ go,
-                                                    MeetDevBlock *__restrict__ db, MeetQueue q, MeetHostBlock *__restrict__ fin, int bound) {
+                                                    MeetDevBlock *__restrict__ db, MeetQueue q, MeetHostBlock *__restrict__ fin, int bound,
+                                                    bool split) {
 	static_assert(kFltWords / 256 <= 4 && (WPB == 2 || WPB == 4), "the filter is cleared in at most four 1-KB parts");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
 	__shared__ __attribute__((aligned(16))) unsigned char win_all[WPB][64];
@@ -638,19 +661,32 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 		// distance 3: the walk's requests dealt out to the WPB wavefronts; every one may request cap / WPB entries
 		bool mine = false, capped = false;
 		int resume = 0;
-		const unsigned long long e3 = seg_walk<PGQ_MEET3_DEPTH_SMALL, false, K>(
-		    exp_desc, exp_n, wib, WPB, xp, win, true, d0, (unsigned long long)cap / WPB, capped, resume,
-		    [&](const typename SegGroup<K>::type &v, bool, u32) {
-			    const u32 pass = flt_pass<BIGV>(bm, v);
-			    verify_candidates(R, pass, v, [&](u32, int) {
-				    mine = true;
-				    return true;
-			    });
-		    },
-		    [&]() {
-			    if (mine) s_found = 1;
-			    return *(volatile u32 *)&s_found != 0u;
-		    });
+		auto test = [&](const typename SegGroup<K>::type &v, bool, u32) {
+			const u32 pass = flt_pass<BIGV>(bm, v);
+			verify_candidates(R, pass, v, [&](u32, int) {
+				mine = true;
+				return true;
+			});
+		};
+		auto done = [&]() {
+			if (mine) s_found = 1;
+			return *(volatile u32 *)&s_found != 0u;
+		};
+		// the heads of all lists, then the tails, as in k_meet3; a wavefront goes on to the tails when ITS share of the heads
+		// is done (no barrier: whoever finds the witness ends the others through s_found)
+		unsigned long long e3 = seg_walk<PGQ_MEET3_DEPTH_SMALL, false, K>(exp_desc, exp_n, wib, WPB, xp, win, true, d0,
+		                                                                  (unsigned long long)cap / WPB, capped, resume, test, done, 0, K > 4 && split);
+		if constexpr (K > 4) {
+			if (split && !capped && !done()) {
+				const unsigned long long mine_cap = (unsigned long long)cap / WPB;
+				const unsigned long long left = uniform_u64(mine_cap - min(mine_cap, e3));
+				entries += e3;
+				walked += e3;
+				e3 = seg_walk<PGQ_MEET3_DEPTH_SMALL, false, K>(exp_desc, exp_n, wib, WPB, xp, win, false, make_uint4(0, 0, 0, 0), left,
+				                                               capped, resume, test, done, 1, true);
+				if (wib == 0) vertices += (u32)exp_n; // the descriptors, a second time
+			}
+		}
 		entries += e3;
 		if (K > 4) walked += e3;
 		if (mine) s_found = 1;
@@ -1987,7 +2023,7 @@ private:
 	} while (0)
 #define PGQ_MEET3KB(P, B, D, K, XF, XR, BN)                                                                              \
 	hipLaunchKernelGGL((k_meet3<P, B, D, K, BN>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, \
-	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound)
+	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound, c->pack_order != 0)
 #define PGQ_MEET3(P, B, D)                                                                                               \
 	do {                                                                                                                 \
 		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \
@@ -2009,7 +2045,7 @@ private:
 	} while (0)
 #define PGQ_MEET3WKB(B, W, K, XF, XR, BN)                                                                                 \
 	hipLaunchKernelGGL((k_meet3w<B, W, K, BN>), dim3((unsigned)n), dim3(64 * W), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
-	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin, bound)
+	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin, bound, c->pack_order != 0)
 #define PGQ_MEET3W(B, W)                                                                                                  \
 	do {                                                                                                                 \
 		if (pk == 6) PGQ_MEET3WK(B, W, 6, c->ppadj, c->prpadj);                                                        \

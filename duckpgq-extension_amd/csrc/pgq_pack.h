@@ -58,4 +58,29 @@ template <int K> PGQ_HD void pack_list_group(const int32_t *adj, int64_t len, ui
 	pack_put<K>(ids, w);
 }
 
+// ---- the order inside a packed list, and the two parts it is walked in -----------------------------------
+// A two-hop walk ends at its first entry that lies in the other endpoint's one-hop list, and an entry is the likelier to
+// be such a member the longer its own list in the OTHER direction is.  The packed copies are private to the hop-count
+// walks, so the upload orders every packed list by non-increasing pack_order_bucket of that length (stable: equal buckets
+// keep the CSR's order), and a row walks the first quarter of the groups of ALL its lists (the heads) before the rest.
+
+// floor(log2(max(len, 1))): 0 .. 31
+PGQ_HD int pack_order_bucket(uint32_t len) { return 31 - __builtin_clz(len | 1u); }
+
+// groups in the head of a list of `ng` groups (ng = ceil(len / K): the groups the walk reads, not the aligned count); the
+// tail is the other ng - pack_head_groups(ng)
+PGQ_HD uint32_t pack_head_groups(uint32_t ng) { return (ng + 3u) >> 2; }
+
+// Part `part` (0: head, 1: tail) of a list of `len` entries: its first group counted from the list's first, its groups and
+// the list entries it holds (the padding of the last group belongs to nobody).  split = false: part 0 is the whole list.
+struct PackPart {
+	uint32_t first, groups, entries;
+};
+PGQ_HD PackPart pack_part(uint32_t len, int K, int part, bool split) {
+	const uint32_t ng = (len + (uint32_t)(K - 1)) / (uint32_t)K;
+	const uint32_t h = split ? pack_head_groups(ng) : ng;
+	const uint32_t he = h * (uint32_t)K < len ? h * (uint32_t)K : len; // entries of the head
+	return part == 0 ? PackPart { 0u, h, he } : PackPart { h, ng - h, len - he };
+}
+
 } // namespace pgq

@@ -340,6 +340,7 @@ static std::vector<OptRef> option_table(Options &o) {
 		{ "meet_align", &o.meet_align, nullptr },
 		{ "meet_pack", &o.meet_pack, nullptr },
 		{ "meet_pack_align", &o.meet_pack_align, nullptr },
+		{ "meet_pack_order", &o.meet_pack_order, nullptr },
 		{ "ball", &o.ball, nullptr },
 		{ "ball_cap", &o.ball_cap, nullptr },
 		{ "ball_test_cap", &o.ball_test_cap, nullptr },
@@ -1292,9 +1293,32 @@ __global__ __launch_bounds__(256) void k_fill_packed(int64_t V, const int64_t *_
 		packed[g] = make_uint4(w[0], w[1], w[2], w[3]);
 	}
 }
+// Sort key of every slot for the degree order of the packed lists (pgq_pack.h): vertex << 5 | (31 - bucket of the entry's list
+// length in the OTHER direction, `ooff`), so that a stable sort keeps the slots of a vertex together, the long-listed
+// entries first and equal buckets in the CSR's order.  One workgroup per 256 consecutive vertices, as k_slot_sources.
+__global__ __launch_bounds__(256) void k_pack_order_keys(int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                         const int64_t *__restrict__ ooff, u32 *__restrict__ key) {
+	__shared__ int64_t s_off[257];
+	const int64_t v0 = (int64_t)blockIdx.x * 256;
+	const int nv = (int)min((int64_t)256, V - v0);
+	for (int t = threadIdx.x; t <= nv; t += 256) s_off[t] = off[v0 + t];
+	__syncthreads();
+	for (int64_t e = s_off[0] + threadIdx.x; e < s_off[nv]; e += 256) {
+		int lo = 0, hi = nv; // largest t with s_off[t] <= e
+		while (hi - lo > 1) {
+			const int mid = (lo + hi) >> 1;
+			if (s_off[mid] <= e) lo = mid;
+			else hi = mid;
+		}
+		const int64_t x = adj[e];
+		key[e] = (u32)(v0 + lo) << 5 | (u32)(31 - pack_order_bucket((u32)(ooff[x + 1] - ooff[x])));
+	}
+}
 // Builds one direction's packed copy and leaves every vertex's first packed group in *d_gb (V + 1 entries, a temporary
 // of the caller's scope `outer`).  Returns PGQ_OK with *packed == nullptr when the group indices would not fit 32 bits.
-static int build_packed_dir(pgq_csr *c, const int64_t *off, const int32_t *adj, int K, int32_t **packed, u32 **d_gb,
+// `ooff` (nullable): the other direction's offsets — the lists are packed in degree order (option meet_pack_order); null:
+// in the CSR's order.
+static int build_packed_dir(pgq_csr *c, const int64_t *off, const int32_t *adj, const int64_t *ooff, int K, int32_t **packed, u32 **d_gb,
                             int64_t *groups_out, DevTemps &outer, hipStream_t st) {
 	const int64_t V = c->V, E = c->E;
 	const u32 align = (u32)std::max(1, options().meet_pack_align);
@@ -1313,6 +1337,20 @@ static int build_packed_dir(pgq_csr *c, const int64_t *off, const int32_t *adj, 
 	*groups_out = (int64_t)total; // (csr_arrays sizes the packed copy from it)
 	PGQ_TRY(csr_alloc(c, *packed));
 	const dim3 grid((unsigned)((V + 255) / 256));
+	if (ooff && E > 0) { // one stable radix sort over the bits in use (V <= 2^25: 30 at most); the vertices stay where they are
+		u32 *d_key = nullptr, *d_skey = nullptr;
+		int32_t *d_ids = nullptr;
+		PGQ_TRY(temps.alloc(&d_key, (size_t)E));
+		PGQ_TRY(temps.alloc(&d_skey, (size_t)E));
+		PGQ_TRY(temps.alloc(&d_ids, (size_t)E));
+		hipLaunchKernelGGL(k_pack_order_keys, grid, dim3(256), 0, st, V, off, adj, ooff, d_key);
+		int end_bit = 6;
+		while ((1LL << (end_bit - 5)) < V) end_bit++;
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) {
+			return hipcub::DeviceRadixSort::SortPairs(tmp, tb, d_key, d_skey, adj, d_ids, (int)E, 0, end_bit, st);
+		}));
+		adj = d_ids; // (freed when `temps` ends, after the stream has drained)
+	}
 	uint4 *dst = reinterpret_cast<uint4 *>(*packed);
 	if (K == 6) hipLaunchKernelGGL(k_fill_packed<6>, grid, dim3(256), 0, st, V, off, adj, *d_gb, dst);
 	else hipLaunchKernelGGL(k_fill_packed<5>, grid, dim3(256), 0, st, V, off, adj, *d_gb, dst);
@@ -1422,11 +1460,17 @@ static int build_meet_layout(pgq_csr *c, hipStream_t st) {
 	u32 *fpg = nullptr, *rpg = nullptr;
 	DevTemps temps(st);
 	c->pack_k = 4;
+	c->pack_order = 0;
+	c->pack_align = 1;
 	if (K > 4) {
-		PGQ_TRY(build_packed_dir(c, c->off, c->adj, K, &c->ppadj, &fpg, &c->ppadj_groups, temps, st));
-		if (c->ppadj) PGQ_TRY(build_packed_dir(c, c->roff, c->radj, K, &c->prpadj, &rpg, &c->prpadj_groups, temps, st));
+		// forward lists by the entries' in-degrees (their walk tests membership in an in-list), reverse lists by out-degrees
+		const bool order = options().meet_pack_order != 0;
+		PGQ_TRY(build_packed_dir(c, c->off, c->adj, order ? c->roff : nullptr, K, &c->ppadj, &fpg, &c->ppadj_groups, temps, st));
+		if (c->ppadj) PGQ_TRY(build_packed_dir(c, c->roff, c->radj, order ? c->off : nullptr, K, &c->prpadj, &rpg, &c->prpadj_groups, temps, st));
 		if (c->ppadj && c->prpadj) {
 			c->pack_k = K;
+			c->pack_order = order ? 1 : 0;
+			c->pack_align = std::max(1, options().meet_pack_align);
 		} else {
 			dev_free(c->ppadj);
 			dev_free(c->prpadj);
@@ -1580,6 +1624,7 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 		c->padj_groups = c->rpadj_groups = 0;
 		c->ppadj_groups = c->prpadj_groups = 0;
 		c->pack_k = 4;
+		c->pack_order = 0;
 	}
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
 	tr.mark("padded adjacency + slot descriptors");
@@ -1597,13 +1642,13 @@ struct CalEntry {
 	double two_hop_mean;
 	pgq_csr::RouteCalibration::Figures figures;
 	std::vector<uint8_t> level_plan[6];
-	int pack_k;
+	int pack_k, pack_order;
 };
 static std::mutex g_cal_lock;
 static std::vector<CalEntry> g_cal; // a handful of graph shapes, the most recent last
 static bool cal_same(const CalEntry &e, const pgq_csr *c) {
 	return e.V == c->V && e.E == c->E && e.max_out == c->max_out_degree && e.max_in == c->max_in_degree && e.two_hop_mean == c->two_hop_mean &&
-	       e.pack_k == c->pack_k; // the route timings differ between the packed and the 32-bit walks
+	       e.pack_k == c->pack_k && e.pack_order == c->pack_order; // the route timings differ between the packed and the 32-bit walks, and with the lists' order
 }
 void calibration_load(pgq_csr *c) {
 	if (!c || !options().calibration_cache) return;
@@ -1618,7 +1663,7 @@ void calibration_load(pgq_csr *c) {
 }
 void calibration_store(pgq_csr *c) {
 	if (!c || c->is_replica || !options().calibration_cache) return;
-	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {}, c->pack_k };
+	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {}, c->pack_k, c->pack_order };
 	bool any = n.figures.meet_bpr > 0 || n.figures.ball_open_frac > 0 || n.figures.route_ball_ns > 0;
 	{
 		std::lock_guard<std::mutex> g2(c->plan_lock);
@@ -1949,6 +1994,8 @@ static int clone_csr(const pgq_csr *c, int dev, pgq_csr **out) {
 	r->ppadj_groups = c->ppadj_groups;
 	r->prpadj_groups = c->prpadj_groups;
 	r->pack_k = c->pack_k;
+	r->pack_order = c->pack_order;
+	r->pack_align = c->pack_align;
 	// every array but the ones built on first use (a replica builds its own), at the size it was allocated with
 	const auto from = csr_arrays(const_cast<pgq_csr *>(c)), to = csr_arrays(r);
 	for (int k = 0; k < kCsrArrays; k++) {
@@ -2017,6 +2064,29 @@ int64_t pgq_debug_live_device_blocks(void) {
 }
 int pgq_csr_has_prepass_layout(const pgq_csr_t *csr) { return csr && csr->fdesc != nullptr ? 1 : 0; }
 int pgq_csr_pack_k(const pgq_csr_t *csr) { return csr ? csr->pack_k : -1; }
+int pgq_csr_pack_order(const pgq_csr_t *csr) { return csr ? csr->pack_order : -1; }
+int64_t pgq_csr_packed_list(pgq_csr_t *c, int dir, int64_t v, int32_t *out, int64_t cap) {
+	if (!c || (dir != 0 && dir != 1) || v < 0 || v >= c->V || cap < 0 || (cap > 0 && !out))
+		return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_packed_list: NULL handle, direction not 0 / 1, vertex out of range or no room");
+	if (c->pack_k <= 4 || !c->ppadj || !c->prpadj) return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_packed_list: this CSR has no packed copy");
+	PGQ_TRY(ensure_init());
+	const int64_t *off = dir == 0 ? c->off : c->roff;
+	const int K = c->pack_k;
+	// a vertex's first packed group is kept in its neighbours' slot descriptors only: count the groups before it again
+	std::vector<int64_t> h_off((size_t)v + 2);
+	PGQ_HIP_TRY(hipMemcpy(h_off.data(), off, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+	uint64_t first = 0;
+	for (int64_t u = 0; u < v; u++) first += pack_list_groups((u32)(h_off[u + 1] - h_off[u]), K, (u32)c->pack_align);
+	const int64_t len = h_off[v + 1] - h_off[v];
+	const uint32_t ng = (uint32_t)((len + K - 1) / K);
+	std::vector<u32> words((size_t)ng * 4);
+	if (ng) PGQ_HIP_TRY(hipMemcpy(words.data(), (dir == 0 ? c->ppadj : c->prpadj) + first * 4, words.size() * sizeof(u32), hipMemcpyDeviceToHost));
+	for (int64_t i = 0; i < len && i < cap; i++) {
+		const u32 *w = &words[(size_t)(i / K) * 4];
+		out[i] = (int32_t)(K == 6 ? pack_get<6>(w, (int)(i % K)) : pack_get<5>(w, (int)(i % K)));
+	}
+	return len;
+}
 
 } // extern "C"
 

@@ -56,6 +56,11 @@ __device__ __forceinline__ u64 wave_min_u64(u64 x) {
 	return x;
 }
 
+// a wave-uniform 64-bit value into scalar registers
+__device__ __forceinline__ u64 uniform_u64(u64 x) {
+	return (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)x) | (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(x >> 32)) << 32;
+}
+
 // ---- packed walk over the padded adjacency (round 3) ---------------------------------------------------------------
 // Device layout (pgq_runtime.hip, build_meet_layout): every vertex's list is copied into a padded adjacency whose lists
 // start on a 16-byte group boundary (aligned to `meet_align` entries) and are filled up to whole groups with copies of
@@ -101,9 +106,16 @@ __device__ __forceinline__ u32 wave_incl_max_u32(u32 x) {
 	r = max(r, PGQ_DPP(0u, r, 0x143, 0xc, 0xf));
 	return r;
 }
-template <int K = 4> __device__ __forceinline__ SegRound seg_round(u32 gbeg, u32 len) {
+// K > 4: the round of one PART of the lists (pgq_pack.h, pack_part): the first group and the count shift to the part's
+template <int K = 4> __device__ __forceinline__ SegRound seg_round(u32 gbeg, u32 len, int part = 0, bool split = false) {
 	SegRound r;
-	r.ng = (len + (u32)(K - 1)) / (u32)K;
+	if constexpr (K > 4) {
+		const PackPart p = pack_part(len, K, part, split);
+		gbeg += p.first;
+		r.ng = p.groups;
+	} else {
+		r.ng = (len + (u32)(K - 1)) / (u32)K;
+	}
 	r.P = wave_incl_scan_u32(r.ng);
 	r.D = gbeg - (r.P - r.ng);
 	r.total = (u32)__builtin_amdgcn_readlane((int)r.P, 63);
@@ -174,11 +186,14 @@ template <int K> __device__ __forceinline__ u32 grp_get(const PGroup<K> &v, int 
 // removed pro rata of the round; wave-uniform).
 // K: ids per group (pgq_pack.h).  K = 4: xp is the 32-bit padded adjacency and a list's first group is the descriptor's
 // 2nd word; K > 4: xp is the packed copy and the first group is its 4th word.  `max_entries` counts K entries per group.
+// K > 4 walks ONE part of every list (pack_part: `part` 0 = the heads, 1 = the tails; split = false: part 0 is the whole
+// list): the caller walks the heads of all rounds, then the tails.  A round whose lists have no groups in the part (short
+// lists have no tail) has total = 0 and is passed through like a round of empty lists.  The entries returned are the part's.
 template <int DEPTH, bool WANT_EV, int K = 4, typename F, typename Stop>
 __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__ list, int list_n, int w, int nw,
                                                        const int32_t *__restrict__ xp, unsigned char *win, bool have_first,
                                                        uint4 first, unsigned long long max_entries, bool &capped, int &resume,
-                                                       F f, Stop stop) {
+                                                       F f, Stop stop, int part = 0, bool split = false) {
 	// Round 4: the DEPTH requests in flight are no longer tied to one round of 64 descriptors.  A request's slot keeps
 	// everything needed to process it (its group, whether the lane holds one, the expanded vertex), so the slot freed by a
 	// processed request is refilled from the NEXT round when the current one has nothing left for this wavefront: the
@@ -201,7 +216,12 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 	// the end of the branch)
 	uint4 dn = zero4;
 	if (64 < list_n) dn = list[min(64 + lane, list_n - 1)];
-	auto round_of = [](const uint4 &dd) { return seg_round<K>(K == 4 ? dd.y : dd.w, dd.z); };
+	auto round_of = [&](const uint4 &dd) { return seg_round<K>(K == 4 ? dd.y : dd.w, dd.z, part, split); };
+	// a list's entries in the part walked (K = 4: the list's)
+	auto part_entries = [&](u32 len) {
+		if constexpr (K > 4) return pack_part(len, K, part, split).entries;
+		else return len;
+	};
 	SegRound r = round_of(d);
 	int nchunk = (int)((r.total + 63u) >> 6);
 	int next = w;   // this wavefront's next request of the round
@@ -239,7 +259,7 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 			if (!have_empty) break;
 			if (next >= nchunk) {
 				if (issued > 0) { // entries of the groups this wavefront requested in the round: pro rata of the round's groups
-					u32 e = d.z;
+					u32 e = part_entries(d.z);
 					for (int o = 32; o > 0; o >>= 1) e += (u32)__shfl_xor((int)e, o);
 					unsigned long long groups = (unsigned long long)issued * 64ull; // 64 per request, except the round's last one
 					if (next - nw == nchunk - 1) groups -= (unsigned long long)nchunk * 64ull - r.total;
@@ -289,7 +309,7 @@ __device__ __forceinline__ unsigned long long seg_walk(const uint4 *__restrict__
 	}
 	if (halt) {
 		if (open && issued > 0) { // the round the walk stopped in
-			u32 e = d.z;
+			u32 e = part_entries(d.z);
 			for (int o = 32; o > 0; o >>= 1) e += (u32)__shfl_xor((int)e, o);
 			unsigned long long groups = (unsigned long long)issued * 64ull;
 			if (next - nw == nchunk - 1) groups -= (unsigned long long)nchunk * 64ull - r.total;

@@ -128,6 +128,16 @@ int pgq_csr_has_prepass_layout(const pgq_csr_t *csr);
  * 5 (25-bit ids, V <= 2^25 with option meet_pack = 2) or 4 (the 32-bit padded lists: meet_pack = 0, larger graphs, no
  * layout); -1 for a NULL handle. */
 int pgq_csr_pack_k(const pgq_csr_t *csr);
+/* 1: the bit-packed lists were built in degree order (option meet_pack_order = 1 at upload, the default): every packed
+ * list holds its entries by non-increasing floor(log2(length of the entry's own list in the OTHER direction)), equal buckets
+ * in the CSR's order, and the hop-count walks read the first quarter of every list's groups before the rest.  0: the CSR's
+ * order (meet_pack_order = 0, or no packed copy); -1 for a NULL handle.  Hop counts are the same either way. */
+int pgq_csr_pack_order(const pgq_csr_t *csr);
+/* Debugging / tests: the bit-packed list of vertex v, decoded, in the order the walks read it.  dir 0: the forward list
+ * (out-neighbours), 1: the reverse list (in-neighbours).  Writes min(length, cap) ids to out (host memory) and returns the
+ * length; PGQ_ERR_UNSUPPORTED for a CSR without a packed copy (pgq_csr_pack_k() == 4).  Not a fast path: it copies the
+ * offsets up to v to the host. */
+int64_t pgq_csr_packed_list(pgq_csr_t *csr, int dir, int64_t v, int32_t *out, int64_t cap);
 /* Debugging / tests: device blocks the library's block cache has handed out and not got back yet (CSR arrays and build
  * temporaries of every live handle; cached free blocks, workspaces and pinned memory are not counted).  The same figure
  * before a handle is created and after it is freed = the handle left nothing behind. */
