@@ -86,6 +86,12 @@ def load_hip():
                                                          C.c_void_p]
     L.pgq_shortestpath.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_shortestpath_within.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_shortestpath_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.pgq_shortestpath_within_multi.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.pgq_cheapest_path_length.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
     L.pgq_iterativelength_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pgq_traversed_edges_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -145,6 +151,8 @@ def load_udf():
                                                  C.c_void_p, C.c_void_p]
     L.pgq_udf_shortestpath.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_udf_shortestpath_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     for f in ("pgq_udf_local_clustering_coefficient", "pgq_udf_pagerank", "pgq_udf_weakly_connected_component"):
         getattr(L, f).argtypes = [C.c_void_p, C.c_int32, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -391,7 +399,7 @@ class DeviceCSR:
         _check(self.L.pgq_iterativelength_within(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
         return out, unpack_validity(ov, n)
 
-    def shortestpath(self, src, dst, src_valid=None, src_sel=None, dst_sel=None, raw=False):
+    def shortestpath(self, src, dst, src_valid=None, src_sel=None, dst_sel=None, raw=False, max_hops=None):
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, None, keep)
         off = np.zeros(n, dtype=np.uint64)
@@ -399,14 +407,23 @@ class DeviceCSR:
         ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
         child = C.c_void_p()
         clen = C.c_uint64()
-        _check(self.L.pgq_shortestpath(self.h, self.V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
-                                       C.byref(clen)))
+        if max_hops is None:
+            _check(self.L.pgq_shortestpath(self.h, self.V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
+                                           C.byref(clen)))
+        else:
+            _check(self.L.pgq_shortestpath_within(self.h, self.V, n, sv, dv, int(max_hops), _p(off), _p(ln), _p(ov),
+                                                  C.byref(child), C.byref(clen)))
         ch = np.zeros(0, dtype=np.int64)
         if clen.value:
             ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
         if raw:  # the LIST vector as DuckDB sees it: list_entry_t{offset,length} per row, validity words, child payload
             return off, ln, ov, ch
         return _lists(off, ln, unpack_validity(ov, n), ch)
+
+    def shortestpath_within(self, src, dst, max_hops, src_valid=None, src_sel=None, dst_sel=None, raw=False):
+        """shortestpath with the pattern's upper bound: rows whose path has more than max_hops hops are NULL and take no room
+        in the child payload."""
+        return self.shortestpath(src, dst, src_valid, src_sel, dst_sel, raw, max_hops=int(max_hops))
 
     def cheapest_path_length(self, src, dst, src_valid=None, dst_valid=None):
         keep = []
@@ -452,7 +469,7 @@ class DeviceCSR:
         _check(self.L.pgq_iterativelength_multi(self.h, len(src), _p(src), _p(dst), _p(out)))
         return out
 
-    def shortestpath_multi(self, src, dst):
+    def shortestpath_multi(self, src, dst, max_hops=None):
         """Paths of host rows by every enabled device; returns (lengths, offsets, child) like the bulk form."""
         src, dst = _i64(src), _i64(dst)
         n = len(src)
@@ -461,12 +478,20 @@ class DeviceCSR:
         cap = max(1024, 16 * n)
         for _ in range(2):
             child = np.zeros(cap, dtype=np.int64)
-            rc = self.L.pgq_shortestpath_multi(self.h, n, _p(src), _p(dst), _p(ln), _p(off), _p(child), cap, C.byref(used))
+            if max_hops is None:
+                rc = self.L.pgq_shortestpath_multi(self.h, n, _p(src), _p(dst), _p(ln), _p(off), _p(child), cap, C.byref(used))
+            else:
+                rc = self.L.pgq_shortestpath_within_multi(self.h, n, _p(src), _p(dst), int(max_hops), _p(ln), _p(off),
+                                                          _p(child), cap, C.byref(used))
             if rc == 0 or used.value <= cap:
                 break
             cap = used.value  # too small: the call reported what it needs
         _check(rc)
         return ln, off, child[:used.value]
+
+    def shortestpath_within_multi(self, src, dst, max_hops):
+        """shortestpath_multi under the pattern's upper bound: only the rows within it have lists."""
+        return self.shortestpath_multi(src, dst, max_hops=int(max_hops))
 
     def cheapest_path_length_multi(self, src, dst):
         src, dst = _i64(src), _i64(dst)
@@ -496,6 +521,13 @@ class DeviceCSR:
         used = C.c_int64(0)
         rc = self.L.pgq_shortestpath_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), C.c_void_p(d_out_len),
                                                  C.c_void_p(d_out_off), C.c_void_p(d_child), child_cap, C.byref(used))
+        return rc, used.value
+
+    def shortestpath_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out_len, d_out_off, d_child, child_cap):
+        used = C.c_int64(0)
+        rc = self.L.pgq_shortestpath_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(max_hops),
+                                                        C.c_void_p(d_out_len), C.c_void_p(d_out_off), C.c_void_p(d_child),
+                                                        child_cap, C.byref(used))
         return rc, used.value
 
     def cheapest_bulk_ptr(self, n, d_src, d_dst, d_out, d_ok):
@@ -599,7 +631,7 @@ class PgqState:
         ok = self._search(self.U.pgq_udf_reachability, csr_id, V, src, dst, src_valid, None, None, None, out)
         return out.astype(bool), ok
 
-    def shortestpath(self, csr_id, V, src, dst, src_valid=None, src_sel=None, dst_sel=None):
+    def shortestpath(self, csr_id, V, src, dst, src_valid=None, src_sel=None, dst_sel=None, max_hops=None):
         keep = []
         sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
         dv = make_vec(_i64(dst), sel=dst_sel, keep=keep)
@@ -609,12 +641,19 @@ class PgqState:
         ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
         child = C.c_void_p()
         clen = C.c_uint64()
-        self._ck(self.U.pgq_udf_shortestpath(self.s, csr_id, V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
-                                             C.byref(clen)))
+        if max_hops is None:
+            self._ck(self.U.pgq_udf_shortestpath(self.s, csr_id, V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
+                                                 C.byref(clen)))
+        else:
+            self._ck(self.U.pgq_udf_shortestpath_within(self.s, csr_id, V, n, sv, dv, int(max_hops), _p(off), _p(ln), _p(ov),
+                                                        C.byref(child), C.byref(clen)))
         ch = np.zeros(0, dtype=np.int64)
         if clen.value:
             ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
         return _lists(off, ln, unpack_validity(ov, n), ch)
+
+    def shortestpath_within(self, csr_id, V, src, dst, max_hops, src_valid=None, src_sel=None, dst_sel=None):
+        return self.shortestpath(csr_id, V, src, dst, src_valid, src_sel, dst_sel, max_hops=int(max_hops))
 
     def bind_cheapest(self, csr_id):
         t = C.c_int(0)

@@ -254,7 +254,7 @@ namespace pgq {
 // split (K > 4; the handle's pack_order): the packed lists are in degree order and the walk takes the heads of all the row's
 // lists before their tails (two seg_walk calls).  The cap bounds both parts together; a walk cut among the heads is taken up from
 // its start by the next stage, one cut among the tails in the tails' round; distance >= 4 is known only after both parts.
-// BND (iterativelength_within): rows farther apart than `bound` hops are NULL.  bound <= 2: the one-hop tests decide the row
+// BND (iterativelength_within, shortestpath_within): rows farther apart than `bound` hops are NULL.  bound <= 2: the one-hop tests decide the row
 // and the two-hop walk is not started; bound == 3: a walk that ran to its END without a witness proves distance >= 4 — NULL
 // here, not queued.  A walk that was CUT proves nothing beyond distance >= 3: that row stays open whatever the bound, and
 // so do the rows whose lists are over the register set (the test that would exclude their distances never ran).
@@ -269,7 +269,6 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
                                                   int64_t *__restrict__ out, MeetPath *__restrict__ rec, int64_t cap,
                                                   const u32 *__restrict__ go, MeetDevBlock *__restrict__ db, MeetQueue q,
                                                   MeetHostBlock *__restrict__ fin, int bound, bool split) {
-	static_assert(!PATHS || !BND, "a bounded search returns hop counts only");
 	static_assert(kMeetWPB == 1, "one wavefront per workgroup: the LDS arrays are addressed statically");
 	static_assert(!PATHS || K == 4, "the path flow walks the 32-bit lists");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
@@ -719,8 +718,13 @@ __global__ __launch_bounds__(64 * WPB) void k_meet3w(int64_t n, const int64_t *_
 // once its lists are past the best second-to-last vertex any wavefront has published.  The 16 wavefronts split a
 // one-hop list round-robin and stream the segments 16 bytes per lane per request.  Rows whose walks exceed `cap`
 // entries stay open.  Distance-only rows take k_meet4d below.
+// BND (shortestpath_within): rows farther apart than `bound` hops are NULL, and the kernel stops at the first phase the bound
+// forbids: bound <= 1 no look at N_in(dst), bound <= 2 no distance-3 walk, bound <= 3 no second marking walk and no distance-4
+// walk.  Every walk here runs to its end (the caps are checked BEFORE a walk starts), so a row whose allowed phases found
+// nothing is farther apart than the bound — closed as NULL, not queued; under bound == 4 the failed distance-4 test proves
+// distance >= 5.  A row over a cap in front of a phase the bound still allows proves nothing: it stays open.
 
-template <bool PATHS, bool GM>
+template <bool PATHS, bool GM, bool BND = false>
 __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                 const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
                                                 const uint4 *__restrict__ fdesc, const uint4 *__restrict__ rdesc,
@@ -728,7 +732,7 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
                                                 int64_t *__restrict__ out_rows,
                                                 MeetPath *__restrict__ rec_rows, int64_t cap, int bm_words,
                                                 MeetDevBlock *__restrict__ db, u32 *__restrict__ gmaps, MeetQueue qout,
-                                                MeetHostBlock *__restrict__ fin) {
+                                                MeetHostBlock *__restrict__ fin, int bound) {
 	extern __shared__ u32 s_map[]; // bm_words: one bit per vertex (GM: the map is this workgroup's slice of `gmaps`)
 	const int64_t n = (int64_t)*qin.count; // rows left open by the kernel before (counted on the device: no host round trip)
 	const int64_t *const src = qin.src, *const dst = qin.dst;
@@ -826,8 +830,14 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 			for (int p = tid; p < degS; p += 1024) mark((u32)adj[so + p]);
 			__syncthreads();
 			if (bit((u32)d)) { // dst in N_out(src)
-				if (tid == 0) out_rows[row] = 1;
+				if (tid == 0) out_rows[row] = (!BND || bound >= 1) ? 1 : -1;
 				continue;
+			}
+			if constexpr (BND) {
+				if (bound < 2) { // (block-uniform) distance >= 2: beyond the bound
+					if (tid == 0) out_rows[row] = -1;
+					continue;
+				}
 			}
 			min_in_neighbour_of_dst();
 			// every wavefront reads s_best between two barriers: the walks below publish into it again, and a wavefront
@@ -841,6 +851,12 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 					if constexpr (PATHS) rec_rows[row].v1 = (int32_t)(u32)best2;
 				}
 				continue;
+			}
+			if constexpr (BND) {
+				if (bound < 3) { // distance >= 3: the backward walk is not started
+					if (tid == 0) out_rows[row] = -1;
+					continue;
+				}
 			}
 			if (work_b > cap) {
 				if (tid == 0) leave_open();
@@ -897,6 +913,12 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 				}
 				continue;
 			}
+			if constexpr (BND) {
+				if (bound < 4) { // the walk ran to its end: distance >= 4, no second marking walk
+					if (tid == 0) out_rows[row] = -1;
+					continue;
+				}
+			}
 			if (work_f > cap) {
 				if (tid == 0) leave_open();
 				continue;
@@ -936,6 +958,7 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 		}
 		if (tid == 0) {
 			if (found4) out_rows[row] = 4;
+			else if (BND && bound <= 4) out_rows[row] = -1; // both walks ran to their ends: distance >= 5
 			else leave_open();
 		}
 	}
@@ -1518,9 +1541,15 @@ __global__ __launch_bounds__(1024) void k_bibfs(MeetQueue qin, u32 max_rows,
 // ---- path emission -------------------------------------------------------------------------------------------------
 // [src, e1, v1, ..., ek, dst] for the rows the pre-pass answered (shortest_path.cpp:149-204): the edge of a hop is the
 // FIRST slot of the parent holding the child (shortest_path.cpp:23-30).  One wavefront per row.
-__global__ void k_path_counts(int64_t n, const int64_t *__restrict__ len, int64_t *__restrict__ cnt) {
+// bound >= 0 (shortestpath_within): a row a stage answered beyond the bound is NULL from here on — before the lists are laid
+// out, so that neither the scan nor the emission nor the total sees it (the bounded kernels answer no such row; this holds
+// whatever they do).
+__global__ void k_path_counts(int64_t n, int64_t *__restrict__ len, int64_t *__restrict__ cnt, int64_t bound) {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) cnt[i] = len[i] >= 0 ? 2 * len[i] + 1 : 0; // open (kMeetOpen, kMeetOpen4) and NULL rows: nothing here
+	if (i >= n) return;
+	int64_t k = len[i];
+	if (bound >= 0 && k > bound) len[i] = k = -1;
+	cnt[i] = k >= 0 ? 2 * k + 1 : 0; // open (kMeetOpen, kMeetOpen4) and NULL rows: nothing here
 }
 __global__ __launch_bounds__(256) void k_emit_paths(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                     const int64_t *__restrict__ len, const MeetPath *__restrict__ rec,
@@ -1677,7 +1706,7 @@ static void meet_attributes() {
 	std::atomic<int> &set = attr_set[current_device() & 63];
 	if (set.load()) return;
 	const void *const map_kernels[] = { (const void *)k_meet4d<false, false>, (const void *)k_meet4d<false, true>, (const void *)k_meet4<true, false>,
-		                                    (const void *)k_bibfs<false>, (const void *)k_meet4d<false, false, true>, (const void *)k_bibfs<false, true> };
+		                                    (const void *)k_bibfs<false>, (const void *)k_meet4d<false, false, true>, (const void *)k_bibfs<false, true>, (const void *)k_meet4<true, false, true> };
 	for (const void *k : map_kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsKB * 1024);
 	(void)hipFuncSetAttribute((const void *)k_src_ball<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
 	(void)hipFuncSetAttribute((const void *)k_src_ball<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBallLdsAttr);
@@ -1809,8 +1838,8 @@ private:
 	// The ride needs k_meet4d (distance-only flow) with its bit map in LDS and large enough to lend: else the gate again
 	const bool may_ride = opt.meet4 && !paths && mp.lds_map && mp.bm_words >= kSampleSlots;
 	const DecideMode decide_mode = a.decide == DecideMode::Ride && !may_ride ? DecideMode::Gate : a.decide;
-	// iterativelength_within: the bounded instantiations of every kernel of the chain (hop counts only)
-	const bool bnd = a.max_hops >= 0 && !paths;
+	// iterativelength_within / shortestpath_within: the bounded instantiations of every kernel of the chain
+	const bool bnd = a.max_hops >= 0;
 	const int bound = bnd ? (int)std::min<int64_t>(a.max_hops, 1 << 30) : -1;
 	const bool decide = decide_mode == DecideMode::Gate;
 	// what is left after k_meet3 (distance >= 4, or over its caps): the bit-map kernels, launched straight behind on a
@@ -2018,7 +2047,7 @@ private:
 		// 32-bit ones.  K = 5 only exists beyond 2^21 vertices: always BIGV
 #define PGQ_MEET3K(P, B, D, K, XF, XR)                                                                                   \
 	do {                                                                                                                 \
-		if (bnd) PGQ_MEET3KB(P, B, D, K, XF, XR, !P);                                                                   \
+		if (bnd) PGQ_MEET3KB(P, B, D, K, XF, XR, true);                                                                 \
 		else PGQ_MEET3KB(P, B, D, K, XF, XR, false);                                                                    \
 	} while (0)
 #define PGQ_MEET3KB(P, B, D, K, XF, XR, BN)                                                                              \
@@ -2080,17 +2109,19 @@ private:
 		KernelTimer kt(st, K_MEET4);
 		if (mp.lds_map) S.lds_map_launches[K_MEET4]++;
 		clear_launch_error();
-#define PGQ_MEET4(G)                                                                                                     \
-	hipLaunchKernelGGL((k_meet4<true, G>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj,     \
-	                   c->fdesc, c->rdesc, c->padj, c->rpadj, a.d_out, rec, cap4, mp.bm_words, db, gmaps, q[1], fin)
+#define PGQ_MEET4(G, BN)                                                                                                 \
+	hipLaunchKernelGGL((k_meet4<true, G, BN>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj, \
+	                   c->fdesc, c->rdesc, c->padj, c->rpadj, a.d_out, rec, cap4, mp.bm_words, db, gmaps, q[1], fin, bound)
 // k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
 // per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
 #define PGQ_MEET4D(G, T) PGQ_MEET4DB(G, T, false)
 #define PGQ_MEET4DB(G, T, BN)                                                                                               \
 	hipLaunchKernelGGL((k_meet4d<G, T, BN>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
 	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride, bound)
-		if (paths && mp.lds_map) PGQ_MEET4(false);
-		else if (paths) PGQ_MEET4(true);
+		if (paths && bnd && mp.lds_map) PGQ_MEET4(false, true);
+		else if (paths && bnd) PGQ_MEET4(true, true);
+		else if (paths && mp.lds_map) PGQ_MEET4(false, false);
+		else if (paths) PGQ_MEET4(true, false);
 		else if (bnd && mp.lds_map) PGQ_MEET4DB(false, false, true);
 		else if (bnd) PGQ_MEET4DB(true, false, true);
 		else if (mp.lds_map && d_trace) PGQ_MEET4D(false, true);
@@ -2121,7 +2152,7 @@ private:
 	// three waits — chain, scan total, emission)
 	int emit_paths() {
 		int64_t *cnt = ws->meet_poff.as<int64_t>() + (n + 1), *poff = ws->meet_poff.as<int64_t>();
-		hipLaunchKernelGGL(k_path_counts, dim3(blocks_for(n)), dim3(256), 0, st, n, a.d_out, cnt);
+		hipLaunchKernelGGL(k_path_counts, dim3(blocks_for(n)), dim3(256), 0, st, n, a.d_out, cnt, (int64_t)bound);
 		PGQ_HIP_TRY(hipMemsetAsync(cnt + n, 0, 8, st));
 		// (scan_tmp is the one buffer sized here: the scan names its own scratch)
 		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, poff, (int)(n + 1), st); }));

@@ -1469,6 +1469,13 @@ __global__ void k_mark_deferred(int64_t lo, int64_t hi, int32_t *__restrict__ sr
 	int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < hi && sres[i] == -1) sres[i] = -3;
 }
+// shortestpath_within: a row of the batch answered beyond the bound (no level beyond it is run, and a probe answers level t
+// from frontier t - 1; this holds whatever they do) is NULL before its list is laid out — k_reconstruct is then never asked
+// for a level whose frontier was not kept
+__global__ void k_clamp_results(int64_t lo, int64_t hi, int32_t max_level, int32_t *__restrict__ sres) {
+	int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < hi && sres[i] > max_level) sres[i] = -1;
+}
 __global__ void k_collect_deferred(int64_t n, const int32_t *__restrict__ sres, const int32_t *__restrict__ ssrc,
                                    const int32_t *__restrict__ sdst, int64_t *__restrict__ dsrc,
                                    int64_t *__restrict__ ddst, u32 *__restrict__ didx, u32 *__restrict__ count) {
@@ -2332,6 +2339,8 @@ private:
 		const int64_t cnt_pairs = hi - lo;
 		h_res.resize(cnt_pairs);
 		h_off.resize(cnt_pairs);
+		if (ask.max_hops >= 0 && cnt_pairs > 0)
+			hipLaunchKernelGGL(k_clamp_results, dim3(blocks_for(cnt_pairs)), dim3(256), 0, st, lo, hi, (int32_t)max_level, sh->sres.as<int32_t>());
 		PGQ_HIP_TRY(hipMemcpyAsync(h_res.data(), sh->sres.as<int32_t>() + lo, (size_t)cnt_pairs * 4, hipMemcpyDeviceToHost, st));
 		PGQ_WAIT(st);
 		int64_t need = child_base;

@@ -43,6 +43,35 @@ __global__ void k_clamp_hops(int64_t n, int64_t max_hops, int64_t *__restrict__ 
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n && len[i] > max_hops) len[i] = -1;
 }
+// shortestpath_within: the entry points' own check behind the search (SearchAsk::max_hops: no stage is relied on).  *beyond (a
+// pinned host word) becomes 1 when a stage reported a row beyond the bound: a plain store, and none in a call that needs none.
+__global__ void k_bound_check(int64_t n, int64_t max_hops, const int64_t *__restrict__ len, u32 *__restrict__ beyond) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n && len[i] > max_hops) *beyond = 1u;
+}
+// When there were such rows: cnt[i] = the elements of row i's list when the row lies within the bound, else 0 ...
+__global__ void k_bound_counts(int64_t n, int64_t max_hops, const int64_t *__restrict__ len, int64_t *__restrict__ cnt) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const int64_t k = len[i];
+	cnt[i] = (k >= 0 && k <= max_hops) ? 2 * k + 1 : 0;
+}
+// ... and, behind their scan: the lists of the others packed in row order (from child to packed, or none when the lists
+// were not written), the rows beyond the bound NULL
+__global__ void k_bound_pack(int64_t n, int64_t max_hops, int64_t *__restrict__ len, int64_t *__restrict__ off, const int64_t *__restrict__ noff,
+                             const int64_t *__restrict__ child, int64_t *__restrict__ packed) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const int64_t k = len[i];
+	if (k > max_hops) {
+		len[i] = -1;
+		off[i] = 0;
+	} else if (k >= 0) {
+		if (packed)
+			for (int64_t j = 0; j < 2 * k + 1; j++) packed[noff[i] + j] = child[off[i] + j];
+		off[i] = noff[i];
+	}
+}
 // The bound a search runs under: V - 1 hops and more reach whatever is reachable — the unbounded search (INT64_MAX is what
 // the binder holds for "no upper bound")
 static int64_t search_bound(const pgq_csr *c, int64_t max_hops) { return max_hops >= c->V - 1 ? -1 : max_hops; }
@@ -347,7 +376,7 @@ private:
 			po.child_cap = (int64_t)(ws->child.cap / 8);
 		}
 		PGQ_HIP_TRY(hipMemsetAsync(p.d_out_off, 0, (size_t)n * 8, st));
-		PGQ_TRY(meet_prepass(c, ws, PrepassArgs { n, d_src, d_dst, d_out_len, &po, meet_bytes, edge_bytes, dm, BallMode::Off }, &r));
+		PGQ_TRY(meet_prepass(c, ws, PrepassArgs { n, d_src, d_dst, d_out_len, &po, meet_bytes, edge_bytes, dm, BallMode::Off, ask.max_hops }, &r));
 		if (!r.answered) return PGQ_OK;
 		if (!p.d_child_ext && po.total > po.child_cap) { // (the kernel skipped the lists that did not fit)
 			PGQ_TRY(ws->child.reserve((size_t)po.total * 8));
@@ -355,7 +384,7 @@ private:
 			po.child_cap = (int64_t)(ws->child.cap / 8);
 			PGQ_TRY(meet_reemit_paths(c, ws, n, d_src, d_dst, d_out_len, &po));
 		}
-		OpenRows open { r.n_open, ws->open_src, ws->open_dst, SearchAsk(), po.total };
+		OpenRows open { r.n_open, ws->open_src, ws->open_dst, SearchAsk(), po.total }; // (search_open_rows hands the bound on)
 		open.ask.from_meet = true;
 		PGQ_TRY(search_open_rows(c, ws, call, rep, open, [&](bool) {
 			return meet_apply_paths(ws, r.n_open, ws->def_len.as<int64_t>(), ws->def_off.as<int64_t>(), po.total, d_out_len, p.d_out_off);
@@ -523,16 +552,81 @@ int pgq_traversed_edges_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_
 	});
 }
 
-int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                                 int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+// shortestpath_within, behind search_device: the stages lay out no list of a row beyond the bound (k_path_counts, batch_paths),
+// and this is where the entry points hold them to it.  path_bound_broken: one launch over the lengths and one wait (the chunk
+// form looks at the lengths it has downloaded anyway).  pack_within_bound, when a stage did report such a row: those rows become
+// NULL, the other rows' lists are packed in row order and rep.child_used counts those alone.  `lists`: the lists were written
+// (at d_child); without them (the caller's buffer was too small) only the lengths, offsets and the count are put right.
+static int path_bound_broken(Workspace *ws, const SearchCall &call, bool *broken) {
+	*broken = false;
+	if (call.ask.max_hops < 0 || call.n == 0) return PGQ_OK;
+	u32 *flag = &ws->h_meet->sample_go; // pinned, device-addressable; no chain is in flight behind a finished search
+	*flag = 0;
+	hipLaunchKernelGGL(k_bound_check, dim3(blocks_for(call.n)), dim3(256), 0, ws->stream, call.n, call.ask.max_hops, call.d_out_len, flag);
+	PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
+	*broken = *flag != 0;
+	*flag = 0;
+	return PGQ_OK;
+}
+static int pack_within_bound(Workspace *ws, const SearchCall &call, SearchReport &rep, int64_t *d_child, bool lists) {
+	const int64_t n = call.n, bound = call.ask.max_hops;
+	hipStream_t st = ws->stream;
+	PGQ_TRY(ws->meet_poff.reserve((size_t)(n + 1) * 8 * 2));
+	int64_t *noff = ws->meet_poff.as<int64_t>(), *cnt = noff + (n + 1), total = 0;
+	PGQ_HIP_TRY(hipMemsetAsync(cnt + n, 0, 8, st));
+	hipLaunchKernelGGL(k_bound_counts, dim3(blocks_for(n)), dim3(256), 0, st, n, bound, call.d_out_len, cnt);
+	PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, noff, (int)(n + 1), st); }));
+	PGQ_HIP_TRY(hipMemcpyAsync(&total, noff + n, 8, hipMemcpyDeviceToHost, st));
+	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	const bool copy = lists && total > 0;
+	DevBuf packed;
+	int rc = copy ? packed.reserve((size_t)total * 8) : PGQ_OK;
+	if (rc == PGQ_OK) {
+		hipLaunchKernelGGL(k_bound_pack, dim3(blocks_for(n)), dim3(256), 0, st, n, bound, call.d_out_len, call.paths->d_out_off, noff, d_child,
+		                   copy ? packed.as<int64_t>() : nullptr);
+		if (copy && hipMemcpyAsync(d_child, packed.p, (size_t)total * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(PGQ_ERR_HIP, "packing the path lists failed");
+		if (hipStreamSynchronize(st) != hipSuccess && rc == PGQ_OK) rc = fail(PGQ_ERR_HIP, "packing the path lists failed");
+	}
+	packed.release();
+	rep.child_used = total;
+	return rc;
+}
+static int enforce_path_bound(Workspace *ws, const SearchCall &call, SearchReport &rep, int64_t *d_child, bool lists) {
+	bool broken = false;
+	PGQ_TRY(path_bound_broken(ws, call, &broken));
+	return broken ? pack_within_bound(ws, call, rep, d_child, lists) : PGQ_OK;
+}
+
+// max_hops: null = unbounded
+static int shortestpath_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len, int64_t *d_out_offset,
+                             int64_t *d_child, int64_t child_cap, int64_t *child_used, const int64_t *max_hops = nullptr) {
 	const bool arrays = d_src && d_dst && d_out_len && d_out_offset && d_child;
-	return c_entry<true>(csr, [&] { return check_arrays(csr, n, arrays, "NULL device array"); }, [&](Workspace *ws) {
-		const SearchCall call { n, d_src, d_dst, d_out_len, SearchPaths { d_out_offset, d_child, child_cap } };
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n, arrays, "NULL device array"));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
+		return PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) {
+		SearchCall call { n, d_src, d_dst, d_out_len, SearchPaths { d_out_offset, d_child, child_cap } };
+		call.ask.max_hops = max_hops ? search_bound(csr, *max_hops) : -1;
 		SearchReport rep;
 		int rc = search_device(csr, ws, call, rep);
+		// (a search that failed for want of room in `d_child` has still written every length: the count is put right for them too)
+		if (rc == PGQ_OK || rep.overflow) {
+			const int rc2 = enforce_path_bound(ws, call, rep, d_child, rc == PGQ_OK);
+			if (rc == PGQ_OK) rc = rc2;
+		}
 		if (child_used) *child_used = rep.child_used;
 		return rc;
 	});
+}
+int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
+                                 int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+	return shortestpath_bulk(csr, n, d_src, d_dst, d_out_len, d_out_offset, d_child, child_cap, child_used);
+}
+int pgq_shortestpath_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                        int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+	return shortestpath_bulk(csr, n, d_src, d_dst, d_out_len, d_out_offset, d_child, child_cap, child_used, &max_hops);
 }
 
 // Multi-GPU inside one process (the single DuckDB process the boundary targets): rows are cut into contiguous shards,
@@ -558,10 +652,12 @@ int pgq_iterativelength_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, con
 // shortestpath on all enabled devices: every shard writes its lists into its own device buffer (grown once if the first
 // guess was too small), the payloads are then concatenated in shard order into `child` and the list offsets shifted by
 // the preceding shards' sizes — the gather of the ragged [v,e,v,...] lists.
-int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t *out_len,
-                           int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used) {
+// max_hops: null = unbounded
+static int shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t *out_len,
+                              int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used, const int64_t *max_hops = nullptr) {
 	auto check = [&] {
 		PGQ_TRY(check_arrays(csr, n, src && dst && out_len && out_offset, "NULL array"));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		if (child_cap < 0 || (child_cap > 0 && !child)) return fail(PGQ_ERR_INVALID_ARG, "NULL array");
 		if (child_used) *child_used = 0;
 		return n == 0 ? kNoRows : PGQ_OK;
@@ -579,9 +675,14 @@ int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const 
 		for (int attempt = 0; attempt < 2; attempt++) {
 			rc = dchild.reserve((size_t)cap * 8);
 			if (rc != PGQ_OK) break;
-			const SearchCall call { m, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(), SearchPaths { ws->out_off.as<int64_t>(), dchild.as<int64_t>(), cap } };
+			SearchCall call { m, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(), SearchPaths { ws->out_off.as<int64_t>(), dchild.as<int64_t>(), cap } };
+			call.ask.max_hops = max_hops ? search_bound(replica, *max_hops) : -1;
 			SearchReport rep;
 			rc = search_device(replica, ws, call, rep);
+			if (rc == PGQ_OK || rep.overflow) {
+				const int rc2 = enforce_path_bound(ws, call, rep, dchild.as<int64_t>(), rc == PGQ_OK);
+				if (rc == PGQ_OK) rc = rc2;
+			}
 			used = rep.child_used;
 			if (rc == PGQ_OK || used <= cap) break;
 			cap = used; // too small: the search reported what it needs
@@ -617,6 +718,15 @@ int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const 
 		}
 		return PGQ_OK;
 	});
+}
+
+int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t *out_len,
+                           int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used) {
+	return shortestpath_multi(csr, n, src, dst, out_len, out_offset, child, child_cap, child_used);
+}
+int pgq_shortestpath_within_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t max_hops, int64_t *out_len,
+                                  int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used) {
+	return shortestpath_multi(csr, n, src, dst, out_len, out_offset, child, child_cap, child_used, &max_hops);
 }
 
 // cheapest_path_length on all enabled devices: out = n values (int64 or double by the CSR's weight type), out_valid = n
@@ -740,10 +850,12 @@ int pgq_iterativelength_bidirectional(pgq_csr_t *csr, int64_t V, int64_t n, pgq_
 	return iterativelength_chunk(csr, V, n, src, dst, out_len, out_valid, true);
 }
 
-int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
-                     uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+// max_hops: null = unbounded
+static int shortestpath_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset, uint64_t *out_length,
+                              uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len, const int64_t *max_hops = nullptr) {
 	auto check = [&] {
 		PGQ_TRY(check_csr(csr, V));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		if (n < 0 || (n > 0 && (!out_offset || !out_length || !out_valid)) || !out_child || !out_child_len)
 			return fail(PGQ_ERR_INVALID_ARG, "NULL output");
 		*out_child = nullptr;
@@ -757,10 +869,16 @@ int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_ve
 		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
 		SearchCall call { n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), ws->out_len.as<int64_t>(), SearchPaths { ws->out_off.as<int64_t>() } };
 		call.ask.no_memo = true;
+		call.ask.max_hops = max_hops ? search_bound(csr, *max_hops) : -1;
 		SearchReport rep;
 		PGQ_TRY(search_device(csr, ws, call, rep));
 		std::vector<int64_t> len(n), off(n);
 		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
+		if (call.ask.max_hops >= 0 && std::any_of(len.begin(), len.end(), [&](int64_t k) { return k > call.ask.max_hops; })) {
+			// (SearchAsk::max_hops: no stage is relied on — a row beyond the bound takes no room in the payload)
+			PGQ_TRY(pack_within_bound(ws, call, rep, ws->child.as<int64_t>(), true));
+			PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
+		}
 		PGQ_TRY(staged_download(off.data(), ws->out_off.p, (size_t)n * 8, ws->stream));
 		t_child.resize((size_t)rep.child_used);
 		if (rep.child_used > 0) PGQ_TRY(staged_download(t_child.data(), ws->child.p, (size_t)rep.child_used * 8, ws->stream));
@@ -779,6 +897,14 @@ int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_ve
 		*out_child_len = (uint64_t)rep.child_used;
 		return PGQ_OK;
 	});
+}
+int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
+                     uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	return shortestpath_chunk(csr, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len);
+}
+int pgq_shortestpath_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, uint64_t *out_offset,
+                            uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	return shortestpath_chunk(csr, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len, &max_hops);
 }
 
 } // extern "C"

@@ -267,6 +267,7 @@ struct MeetPinned {
 	alignas(16) unsigned char report[4096];
 	int64_t paths_total; // shortestpath: elements of the lists the chain wrote (copied behind its scan)
 	u32 sample_go;       // the sampled decision's verdict + 1 (k_meet_decide alone, riding in k_meet4d, lane_ranks); 0: none taken
+	                     // (behind a finished bounded shortestpath search: the flag of the entry point's check for rows beyond the bound)
 };
 
 // One direction's search state of the batched relaxation (pgq_cheapest.hip): labels dist[V][64], the lanes of a vertex that
@@ -392,7 +393,7 @@ struct PrepassArgs {
 	double meet_bytes = 0, edge_bytes = 0; // the byte rule's two sides (decision kernel, source-centric kernel)
 	DecideMode decide = DecideMode::None;
 	BallMode ball = BallMode::Off;
-	int64_t max_hops = -1; // iterativelength_within: >= 0 = rows farther apart are NULL (the kernels' bounded instantiations)
+	int64_t max_hops = -1; // *_within: >= 0 = rows farther apart are NULL (the kernels' bounded instantiations)
 };
 struct PrepassResult {
 	u32 n_open = 0;              // rows left in ws->open_src / open_dst / open_idx
@@ -433,9 +434,11 @@ struct SearchAsk {
 	// remembers about "these buffers" says nothing about THESE rows (round-5 advisor finding: unrelated chunks hit the memo,
 	// and every change of shape was routed one call late) — such calls neither read nor write it
 	bool no_memo = false;
-	// iterativelength_within: >= 0 = a row whose distance exceeds it is NULL; negative = unbounded.  Every stage stops where the
-	// bound lets it and the open rows' searches inherit it, but no stage is relied on to: the entry point clamps what comes back
-	// (a lane batch's probes answer rows a level or two ahead, k_meet4d reports 4 for a cut row under a bound of 3).  A bounded
+	// iterativelength_within / shortestpath_within: >= 0 = a row whose distance exceeds it is NULL; negative = unbounded.  Every
+	// stage stops where the bound lets it and the open rows' searches inherit it, but no stage is relied on to: the entry point
+	// clamps what comes back (a lane batch's probes answer rows a level or two ahead, k_meet4d reports 4 for a cut row under a
+	// bound of 3).  With paths a row beyond the bound must be NULL before its list is laid out (k_path_counts, batch_paths), so
+	// that offsets and child_used count the rows within the bound only; the entry points check that once more.  A bounded
 	// call is off the record of what unbounded calls are routed by (route memo, route timing, ball_open_frac, the refinement of
 	// meet_bpr, meet_far_rows; its lane batches store no level plan): a bounded row costs something else.
 	int64_t max_hops = -1;

@@ -325,6 +325,19 @@ int pgq_udf_shortestpath(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_v
 	return 0;
 }
 
+int pgq_udf_shortestpath_within(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                                uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                                uint64_t *out_child_len) {
+	CsrRef c;
+	pgq_csr_t *d;
+	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
+	if (pgq_shortestpath_within(d, V, n, src, dst, max_hops, out_offset, out_length, out_valid, out_child, out_child_len) != PGQ_OK)
+		return device_fail();
+	std::lock_guard<std::mutex> g(s->csr_lock);
+	s->csr_to_delete.insert(id); // shortest_path.cpp:206
+	return 0;
+}
+
 int pgq_udf_bind_cheapest(pgq_state_t *s, int32_t id, int *ret_type) { // cheapest_path_length_function_data.cpp:7-32
 	if (!s) return fail("Invalid Input Error: NULL state");
 	CsrRef c = find_csr(s, id);

@@ -1,7 +1,7 @@
 // pgq_glue.cpp — the DuckDB side of the drop-in: replacement bodies of the reference's search UDFs that forward to
 // libpgq_hip (include/pgq_hip.h).  Names, argument lists, exception texts and NULL rules are the reference's:
 //   IterativeLengthFunction        src/core/functions/scalar/iterativelength.cpp:34-143   (also registered as iterativelength2)
-//   ShortestPathFunction           src/core/functions/scalar/shortest_path.cpp:43-207
+//   ShortestPathFunction           src/core/functions/scalar/shortest_path.cpp:43-207   (ShortestPathWithinFunction: its five-argument overload)
 //   CheapestPathLengthFunction     src/core/functions/scalar/cheapest_path_length.cpp:138-163
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
@@ -114,7 +114,9 @@ void IterativeLengthWithinFunction(DataChunk &args, ExpressionState &state, Vect
 	in.state->csr_to_delete.insert(in.csr_id);
 }
 
-void ShortestPathFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+namespace {
+// shortestpath with four arguments (upper == nullptr) or five
+void ShortestPath(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper) {
 	SearchInputs in = Prepare(args, state, "shortest path");
 	result.SetVectorType(VectorType::FLAT_VECTOR);
 	auto entries = FlatVector::GetDataMutable<list_entry_t>(result);
@@ -123,9 +125,12 @@ void ShortestPathFunction(DataChunk &args, ExpressionState &state, Vector &resul
 	const int64_t *child = nullptr; // owned by the library until this thread's next pgq_shortestpath
 	uint64_t child_len = 0;
 	vector<uint64_t> offsets(args.size()), lengths(args.size());
-	if (pgq_shortestpath(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src),
-	                     AsVec(in.dst), offsets.data(), lengths.data(), validity.GetData(), &child, &child_len) != PGQ_OK)
-		ThrowDevice();
+	pgq_csr_t *device = DeviceCSR(*in.state, *in.csr, in.v_size);
+	const int rc = upper ? pgq_shortestpath_within(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), *upper, offsets.data(),
+	                                               lengths.data(), validity.GetData(), &child, &child_len)
+	                     : pgq_shortestpath(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), offsets.data(),
+	                                        lengths.data(), validity.GetData(), &child, &child_len);
+	if (rc != PGQ_OK) ThrowDevice();
 	ListVector::Reserve(result, child_len);
 	if (child_len) memcpy(FlatVector::GetDataMutable<int64_t>(ListVector::GetEntry(result)), child, child_len * sizeof(int64_t));
 	ListVector::SetListSize(result, child_len);
@@ -134,6 +139,19 @@ void ShortestPathFunction(DataChunk &args, ExpressionState &state, Vector &resul
 		entries[i].length = lengths[i];
 	}
 	in.state->csr_to_delete.insert(in.csr_id);
+}
+} // namespace
+
+void ShortestPathFunction(DataChunk &args, ExpressionState &state, Vector &result) { ShortestPath(args, state, result, nullptr); }
+
+// shortestpath(csr_id, V, src, dst, upper): the five-argument overload beside iterativelength's.  The binder computes the path
+// over the pairs its `iterativelength(...) BETWEEN lower AND upper` filter keeps (match.cpp:467-495, 658-671), so a row beyond
+// `upper` is NULL to the query anyway: here it is NULL, takes no room in the list's child vector, and its search stops at the bound.
+void ShortestPathWithinFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	UnifiedVectorFormat upper_fmt; // a constant of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	ShortestPath(args, state, result, &upper);
 }
 
 void CheapestPathLengthFunction(DataChunk &args, ExpressionState &state, Vector &result) {
@@ -203,7 +221,9 @@ void PageRankFunction(DataChunk &args, ExpressionState &state, Vector &result) {
 // Whole-relation entry point: every (src, dst) row of a relation resident in host memory, any
 // row count, answered by ONE search that yields the hop count AND the path — the list of a reachable pair holds
 // 2 * hops + 1 elements, so `lengths` needs no second BFS (the binder evaluates iterativelength as a filter and then
-// shortestpath on the same pairs: match.cpp:473-474,477).  Rows with hops outside [lower, upper] get valid = false.
+// shortestpath on the same pairs: match.cpp:473-474,477).  The search runs under `upper` (pgq_shortestpath_within*): rows
+// farther apart come back NULL without a list and without their far levels having been searched.  Rows with hops outside
+// [lower, upper] get valid = false (`lower` needs nothing from the search: the filter below stays).
 struct PathFindingResult {
 	vector<int64_t> hops;        // -1 for NULL / unreachable
 	vector<list_entry_t> lists;  // into `child`
@@ -224,6 +244,7 @@ PathFindingResult PathFindingRelation(DuckPGQState &state, int32_t csr_id, const
 	r.lists.assign(n, list_entry_t { 0, 0 });
 	r.valid.assign(n, false);
 	pgq_csr_t *device = DeviceCSR(state, csr, v_size);
+	const int64_t bound = upper < 0 ? 0 : upper; // (no row is valid under a negative upper bound; the search takes none)
 	if (pgq_num_enabled_devices() > 1 && n >= 4096) {
 		// several GPUs behind this process (pgq_init_devices at extension load): contiguous shards of the relation, one
 		// replica of the CSR per device, the ragged lists gathered behind each other
@@ -232,17 +253,17 @@ PathFindingResult PathFindingRelation(DuckPGQState &state, int32_t csr_id, const
 		// first guess: a list of h hops holds 2h + 1 elements, 16 per row covers paths of up to 7 hops on average (social
 		// graphs: 3-4); a call that needs more says how much in `used` and is repeated once
 		r.child.resize(16 * n);
-		int rc = pgq_shortestpath_multi(device, (int64_t)n, src.data(), dst.data(), len.data(), off.data(), r.child.data(),
-		                                (int64_t)r.child.size(), &used);
+		int rc = pgq_shortestpath_within_multi(device, (int64_t)n, src.data(), dst.data(), bound, len.data(), off.data(), r.child.data(),
+		                                       (int64_t)r.child.size(), &used);
 		if (rc != PGQ_OK && used > (int64_t)r.child.size()) { // the first guess was too small: the call said what it needs
 			r.child.resize((size_t)used);
-			rc = pgq_shortestpath_multi(device, (int64_t)n, src.data(), dst.data(), len.data(), off.data(), r.child.data(),
-			                            (int64_t)r.child.size(), &used);
+			rc = pgq_shortestpath_within_multi(device, (int64_t)n, src.data(), dst.data(), bound, len.data(), off.data(), r.child.data(),
+			                                   (int64_t)r.child.size(), &used);
 		}
 		if (rc != PGQ_OK) ThrowDevice();
 		r.child.resize((size_t)used);
 		for (idx_t i = 0; i < n; i++) {
-			if (len[i] < 0) continue; // NULL source or unreachable
+			if (len[i] < 0) continue; // NULL source, unreachable or beyond `upper`
 			r.hops[i] = len[i];
 			r.lists[i] = list_entry_t { (uint64_t)off[i], (uint64_t)(2 * len[i] + 1) };
 			r.valid[i] = len[i] >= lower && len[i] <= upper;
@@ -254,8 +275,8 @@ PathFindingResult PathFindingRelation(DuckPGQState &state, int32_t csr_id, const
 	pgq_vec_t s { src.data(), nullptr, nullptr }, d { dst.data(), nullptr, nullptr };
 	const int64_t *child = nullptr;
 	uint64_t child_len = 0;
-	if (pgq_shortestpath(device, v_size, (int64_t)n, s, d, offsets.data(), lengths.data(), mask.data(), &child, &child_len) !=
-	    PGQ_OK)
+	if (pgq_shortestpath_within(device, v_size, (int64_t)n, s, d, bound, offsets.data(), lengths.data(), mask.data(), &child,
+	                            &child_len) != PGQ_OK)
 		ThrowDevice();
 	r.child.assign(child, child + child_len);
 	for (idx_t i = 0; i < n; i++) {

@@ -176,6 +176,17 @@ int pgq_iterativelength_bidirectional(pgq_csr_t *csr, int64_t V, int64_t n, pgq_
 int pgq_shortestpath(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
                      uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len);
 
+/* shortestpath(csr_id, V, src, dst, upper) -> LIST(BIGINT): pgq_shortestpath, except that a row whose path has more than
+ * max_hops hops is NULL — validity bit clear, entry {0,0}, and NO elements in the child payload: *out_child_len counts the
+ * lists of the rows within the bound only.  The binder computes shortestpath over the very pairs it filters with
+ * `iterativelength(...) BETWEEN lower AND upper` (match.cpp:467-495, 658-671), so a row beyond `upper` is NULL to the query
+ * anyway; here its search stops at the bound and no level frontier is kept for a list nobody reads.  src == dst -> [src]
+ * for every max_hops >= 0; max_hops >= V - 1 (INT64_MAX: the binder's "no upper bound") is the unbounded search, same lists,
+ * lengths and payload as pgq_shortestpath; max_hops < 0 -> PGQ_ERR_INVALID_ARG. */
+int pgq_shortestpath_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                            uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                            uint64_t *out_child_len);
+
 /* cheapest_path_length(csr_id, V, src, dst) -> BIGINT | DOUBLE (by the CSR's weight type; out is int64_t* or
  * double*).  NULL src, NULL dst or unreachable -> NULL. */
 int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
@@ -207,6 +218,10 @@ int pgq_iterativelength_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, con
  * PGQ_ERR_INVALID_ARG when child_cap is too small (out_len is complete, the payload is not usable). */
 int pgq_shortestpath_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t *out_len,
                            int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used);
+/* pgq_shortestpath_multi under the pattern's upper bound (pgq_shortestpath_within_bulk_device per shard): rows farther apart
+ * than max_hops have out_len -1 and no list; *child_used and the gathered payload count the rows within the bound only. */
+int pgq_shortestpath_within_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t max_hops,
+                                  int64_t *out_len, int64_t *out_offset, int64_t *child, int64_t child_cap, int64_t *child_used);
 /* cheapest_path_length (CheapestPathLengthFunction, cheapest_path_length.cpp:138-163) by all enabled devices:
  * out = n int64 or double (by weight type), out_valid = n bytes. */
 int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, void *out,
@@ -222,6 +237,12 @@ int pgq_traversed_edges_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_
 int pgq_shortestpath_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                  int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
                                  int64_t *child_used);
+/* pgq_shortestpath_within without the chunk ceiling: as pgq_shortestpath_bulk_device, except that a row farther apart than
+ * max_hops has d_out_len[i] = -1, no offset and no elements in d_child — *child_used (and what child_cap must hold) counts the
+ * lists of the rows within the bound only. */
+int pgq_shortestpath_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                        int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
+                                        int64_t *child_used);
 /* out: int64 or double per weight type; NULL -> validity payload -1 (int64) / NaN is never used: d_out_valid
  * (n bytes, 1 = valid) carries validity. */
 int pgq_cheapest_path_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,

@@ -14,6 +14,7 @@
  *   pgq_udf_iterativelength2        IterativeLength2Function     src/core/functions/scalar/iterativelength2.cpp:33-130 (same results)
  *   pgq_udf_iterativelengthbidirectional  IterativeLengthBidirectionalFunction  src/core/functions/scalar/iterativelength_bidirectional.cpp:43-153 (intended semantics)
  *   pgq_udf_shortestpath            ShortestPathFunction         src/core/functions/scalar/shortest_path.cpp:43-207
+ *   pgq_udf_shortestpath_within     ShortestPathFunction with the pattern's upper bound as fifth argument (match.cpp:467-495, 658-671)
  *   pgq_udf_bind_cheapest           CheapestPathLengthBind       src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_delete_csr              DeleteCsrFunction            src/core/functions/scalar/csr_deletion.cpp:10-20
@@ -66,6 +67,11 @@ int pgq_udf_iterativelengthbidirectional(pgq_state_t *, int32_t id, int64_t V, i
 int pgq_udf_shortestpath(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                          uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                          uint64_t *out_child_len);
+/* shortestpath(id, V, src, dst, upper): rows whose path has more than max_hops hops are NULL and take no room in the child
+ * payload (pgq_shortestpath_within); errors as for pgq_udf_shortestpath, max_hops < 0 is the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_shortestpath_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                                uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                                uint64_t *out_child_len);
 /* *ret_type: PGQ_W_INT64 -> BIGINT result, PGQ_W_DOUBLE -> DOUBLE result */
 int pgq_udf_bind_cheapest(pgq_state_t *, int32_t id, int *ret_type);
 int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
