@@ -93,6 +93,11 @@ def load_hip():
     L.pgq_shortestpath_within_multi.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.pgq_cheapest_path_length.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
+    L.pgq_cheapest_path_length_within.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pgq_cheapest_path_length_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                              C.c_void_p, C.c_void_p]
+    L.pgq_cheapest_path_length_within_multi.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                        C.c_void_p]
     L.pgq_iterativelength_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pgq_traversed_edges_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pgq_shortestpath_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -154,6 +159,8 @@ def load_udf():
     L.pgq_udf_shortestpath_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+    L.pgq_udf_cheapest_path_length_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64,
+                                                      C.c_void_p, C.c_void_p]
     for f in ("pgq_udf_local_clustering_coefficient", "pgq_udf_pagerank", "pgq_udf_weakly_connected_component"):
         getattr(L, f).argtypes = [C.c_void_p, C.c_int32, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_udf_delete_csr.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
@@ -433,6 +440,16 @@ class DeviceCSR:
         _check(self.L.pgq_cheapest_path_length(self.h, self.V, n, sv, dv, _p(out), _p(ov)))
         return out, unpack_validity(ov, n)
 
+    def cheapest_path_length_within(self, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        """The cost of the cheapest walk of at most max_hops edges per row: another number than cheapest_path_length's, not
+        that one with far rows NULL (include/pgq_hip.h)."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        out = np.zeros(n, dtype=np.int64 if self.w_type == 1 else np.float64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_cheapest_path_length_within(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
     # -- bulk form (device pointers; torch tensors supply them) ------------------
     def iterativelength_bulk_ptr(self, n, d_src, d_dst, d_out):
         _check(self.L.pgq_iterativelength_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
@@ -501,6 +518,15 @@ class DeviceCSR:
         _check(self.L.pgq_cheapest_path_length_multi(self.h, n, _p(src), _p(dst), _p(out), _p(ok)))
         return out, ok.astype(bool)
 
+    def cheapest_path_length_within_multi(self, src, dst, max_hops):
+        """cheapest_path_length_within of host rows by every enabled device."""
+        src, dst = _i64(src), _i64(dst)
+        n = len(src)
+        out = np.zeros(n, dtype=np.int64 if self.w_type == 1 else np.float64)
+        ok = np.zeros(n, dtype=np.uint8)
+        _check(self.L.pgq_cheapest_path_length_within_multi(self.h, n, _p(src), _p(dst), int(max_hops), _p(out), _p(ok)))
+        return out, ok.astype(bool)
+
     def replicate(self):
         _check(self.L.pgq_csr_replicate(self.h))
 
@@ -533,6 +559,10 @@ class DeviceCSR:
     def cheapest_bulk_ptr(self, n, d_src, d_dst, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                            C.c_void_p(d_out), C.c_void_p(d_ok)))
+
+    def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
+        _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
+                                                                  int(max_hops), C.c_void_p(d_out), C.c_void_p(d_ok)))
 
 
 class PgqState:
@@ -665,6 +695,19 @@ class PgqState:
         out = np.zeros(len(src), dtype=np.int64 if rt == 1 else np.float64)
         ok = self._search(self.U.pgq_udf_cheapest_path_length, csr_id, V, src, dst, src_valid, None, None, dst_valid,
                           out)
+        return out, ok
+
+    def cheapest_path_length_within(self, csr_id, V, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None,
+                                    dst_sel=None):
+        rt = self.bind_cheapest(csr_id)
+        n = len(src_sel) if src_sel is not None else len(src)
+        out = np.zeros(n, dtype=np.int64 if rt == 1 else np.float64)
+        hops = int(max_hops)
+
+        def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            return self.U.pgq_udf_cheapest_path_length_within(s, csr_id, V, n, sv, dv, hops, out_p, ov_p)
+
+        ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
         return out, ok
 
     def _analytics(self, fn, csr_id, src, dtype):

@@ -17,6 +17,10 @@
 // dirty[parity][V] = 64-bit mask of lanes of v that improved in the previous round.  A lane is one distinct
 // source.  Rounds are kernel launches: improvements made in round r are consumed in round r+1, so no
 // intra-kernel visibility between XCDs is needed.
+//
+// pgq_cheapest_path_length_within (the cheapest walk of at most K edges: another number, not this one clamped) cannot use these
+// rounds, in which a label travels several edges per launch; its round of exactly one edge is k_hop_snapshot + k_relax_hops
+// under HopBatches, further down.
 #include <hipcub/hipcub.hpp>
 
 #include <cstddef>
@@ -456,7 +460,7 @@ struct RelaxCounters {
 	u64 relaxed_edges;
 	long long min_deferred; // smallest label (bit pattern) a round left for later (k_relax's threshold)
 	u32 relaxed_vertices;   // vertices a round expanded
-	u32 pad;
+	u32 snap_rows;          // label rows k_hop_snapshot copied (hop-bounded rounds; runs on over a batch, like `rounds` there)
 	u64 heavy;              // (entries << 32) | chunks of the round's heavy list (k_relax)
 	long long bound[64];    // per lane: the largest tentative label among its destinations (nothing beyond it matters)
 };
@@ -1149,7 +1153,7 @@ static int weighted_pairs_prepass(pgq_csr *c, Workspace *ws, u32 nd, int64_t *d_
 
 template <typename T>
 static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                           int64_t *d_out, uint8_t *d_ok, bool chain);
+                           int64_t *d_out, uint8_t *d_ok, bool chain, int64_t max_hops = -1);
 
 template <typename T>
 static int cheapest_with_chains(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
@@ -1263,18 +1267,21 @@ template <typename DT> int RelaxSide::prepare(int64_t V, int type_tag, DT inf_la
 // the persistent grid of a round: exactly what is resident at once (each wavefront takes every nwaves-th vertex; a
 // grid larger than the chip makes the last workgroups start when the first finish: 8192 waves on 7168 slots was 2x)
 static std::mutex g_relax_grid_lock;
-template <typename T, typename DT> static int relax_grid(unsigned *grid) {
-	static unsigned cached[64] = {}; // per instantiation and device: a node's devices need not be alike
+template <typename Kernel> static int resident_grid(Kernel kernel, unsigned (&cached)[64], unsigned *grid) {
 	std::lock_guard<std::mutex> g(g_relax_grid_lock);
 	int dev = 0, per_cu = 0, cus = 0;
 	PGQ_HIP_TRY(hipGetDevice(&dev));
 	if (!cached[dev & 63]) {
-		PGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax<T, DT>, 256, 0));
+		PGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
 		PGQ_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
 		cached[dev & 63] = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
 	}
 	*grid = cached[dev & 63];
 	return PGQ_OK;
+}
+template <typename T, typename DT> static int relax_grid(unsigned *grid) {
+	static unsigned cached[64] = {}; // per instantiation and device: a node's devices need not be alike
+	return resident_grid(k_relax<T, DT>, cached, grid);
 }
 
 // a fraction of the mean weight as a weight: a band width, a first cap (integers: at least 1)
@@ -1519,6 +1526,246 @@ private:
 	}
 };
 
+// ---- hop-bounded rounds: the cheapest walk of at most K edges (HopBatches) -----------------------------------------------
+// pgq_cheapest_path_length_within answers, per row (src, dst), D_K[dst] of
+//     D_0[src] = 0, D_0[v] = INF otherwise;   D_k[n] = min(D_{k-1}[n], min over edges (u, n) of D_{k-1}[u] + w(u, n))
+// where the sum is the reference's `dist[v] + w` (cheapest_path_length.cpp:29-36) and counts only where it is < D_{k-1}[n]
+// (so a sum that does not get under INF = max / 2 never labels a vertex); NULL when D_K[dst] == INF.  The reference has NO
+// counterpart: its Bellman-Ford sweeps in place, so its rounds are not hops, and neither are k_relax's or k_relax_small's —
+// a vertex expanded late in a launch may carry a label an earlier wavefront of the same launch improved, labels travel
+// several edges per round (the order-independence the file's header relies on).  The result is NOT "the unbounded answer with
+// far rows set to NULL" either: the cheapest walk of at most K edges is in general another walk than the cheapest one, and
+// costs more.  A bound needs a round that moves every label by exactly ONE edge: two launches.
+//   k_hop_snapshot  one wavefront per queue entry i: takes the dirty word of the queue's vertex v with an exchange and copies
+//                   v's 512-byte label row into snap[i][0..63], the word into snapmask[i].  Behind this launch `snap` holds
+//                   D_{k-1} of every vertex that changed in round k-1, frozen.
+//   k_relax_hops    a persistent grid; wavefronts stride over the queue, lane l = search l.  A wavefront reads v, snapmask[i]
+//                   and its lane's snap[i][l] — never dist[v] — and walks v's whole out-list eight edges per dependent trip
+//                   (k_relax's plain, unsorted path): lanes whose mask bit is set atomicMin snap + w into dist[n][l].
+// Exact per round: the sources of a relaxation come only from `snap` (D_{k-1}), the targets are only `dist`, so no label
+// written in round k is read in round k; a lane whose label at v did not change in round k-1 made its offers the round after
+// it last changed and has nothing new, so only dirty lanes relax.  The plain pre-check load of dist[n][l] may be stale-high
+// within a launch (another wavefront's atomic): that costs an atomic and never an answer, the atomicMin decides.  All
+// freshness comes from kernel boundaries: no fence, no agent-scope load, no round loop inside a kernel.
+// Exact per walk (what makes the result the reference's arithmetic, bit for bit, for int64 and for double):
+//   claim      D_k[n] = the minimum, over the walks src -> n of at most k edges, of the left-to-right fold of their weights.
+//   k = 0      the empty walk at src folds to 0; no other vertex has a walk.
+//   k-1 -> k   a walk of <= k edges into n is a walk P of <= k-1 edges into some u plus an edge (u, n), fold(P) + w.  For a
+//              fixed non-negative w, x -> x + w is monotone (IEEE round-to-nearest as well as int64), so the minimum over P of
+//              fold(P) + w is (min over P of fold(P)) + w = D_{k-1}[u] + w: the recurrence above.
+// NaN and +inf weights never relax an edge, -0.0 is accepted: as in k_relax.  K >= V - 1 is the unbounded search (a cheapest
+// walk needs no repeated vertex under non-negative weights) and takes the unbounded drivers.
+// Known limits: lists over 128 edges are walked by the wavefront that finds them (correct, only slow: no heavy-list split
+// here yet), and there is no destination-bound pruning — a lane relaxes everything within K edges of its source.
+template <typename DT>
+__global__ __launch_bounds__(256) void k_hop_snapshot(const int32_t *__restrict__ qcur, const u32 *__restrict__ nq_ptr,
+                                                      u64 *__restrict__ dirty_cur, const DT *__restrict__ dist,
+                                                      DT *__restrict__ snap, u64 *__restrict__ snapmask, u32 *__restrict__ snap_rows) {
+	const int lane = threadIdx.x & 63;
+	const u32 wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+	const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
+	const u32 nq = *nq_ptr;
+	for (u32 i = wave; i < nq; i += nwaves) {
+		const int v = qcur[i];
+		snap[(size_t)i * LC + lane] = dist[(size_t)v * LC + lane];
+		if (lane == 0) snapmask[i] = atomicExch(&dirty_cur[v], 0ull); // consumed: the word is clean for the round after next
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0) *snap_rows += nq; // (statistics; the batch's launches never overlap)
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, PGQ_RELAX_WAVES) void k_relax_hops(const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                    const T *__restrict__ w, int64_t *__restrict__ dist,
+                                                    const int64_t *__restrict__ snap, const u64 *__restrict__ snapmask,
+                                                    u64 *__restrict__ dirty_nxt, const int32_t *__restrict__ qcur,
+                                                    const u32 *__restrict__ nq_ptr, int32_t *__restrict__ qnxt, u32 *__restrict__ nq_nxt,
+                                                    u32 *__restrict__ tflag, u32 tepoch, int32_t *__restrict__ touched,
+                                                    u32 *__restrict__ tcount, u64 *__restrict__ relaxed_edges, u32 *__restrict__ rounds) {
+	constexpr int UNR = kRelaxUnroll;
+	__shared__ int s_pq[4][kPendCap];
+	__shared__ int s_pt[4][kPendCap];
+	__shared__ u64 s_edges; // the workgroup's counters go through LDS first, like k_relax's
+	__shared__ int s_pend[2][4];
+	__shared__ u32 s_base[2];
+	if (threadIdx.x == 0) s_edges = 0;
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const int wib = threadIdx.x >> 6;
+	const u32 wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+	const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
+	const u32 nq = *nq_ptr;
+	u64 edges = 0;
+	int pend_q = 0, pend_t = 0; // wave-uniform
+	int *const pq = s_pq[wib];
+	int *const pt = s_pt[wib];
+	for (u32 i = wave; i < nq; i += nwaves) {
+		const int v = qcur[i];
+		const bool mine = (snapmask[i] >> lane) & 1ull; // the lane's label at v changed in the previous round (so it is below INF)
+		const u64 dvb = (u64)snap[(size_t)i * LC + lane];
+		const int64_t b = off[v], e = off[v + 1];
+		edges += (u64)(e - b);
+		for (int64_t k0 = b; k0 < e; k0 += UNR) {
+			int nn[UNR];
+			T ww[UNR];
+			u64 cand[UNR], curv[UNR];
+#pragma unroll
+			for (int u = 0; u < UNR; u++) {
+				const bool in = k0 + u < e;
+				nn[u] = in ? adj[k0 + u] : v;
+				ww[u] = in ? w[k0 + u] : T(0);
+				// labels are compared as bit patterns; a NaN weight never relaxes an edge in the reference, +inf behaves the same here
+				if constexpr (std::is_same<T, double>::value) ww[u] = ww[u] == ww[u] ? ww[u] : __longlong_as_double(0x7FF0000000000000ll);
+			}
+#pragma unroll
+			for (int u = 0; u < UNR; u++) {
+				// labels and weights are non-negative: the int64 sum cannot wrap as an unsigned one, a double's bits order like its value
+				if constexpr (std::is_same<T, double>::value) cand[u] = (u64)__double_as_longlong(__longlong_as_double((long long)dvb) + ww[u]);
+				else cand[u] = dvb + (u64)ww[u];
+				curv[u] = (u64)dist[(size_t)nn[u] * LC + lane]; // all eight rows in flight together; <= INF, possibly stale-high
+			}
+#pragma unroll
+			for (int u = 0; u < UNR; u++) {
+				const bool go = k0 + u < e && mine && cand[u] < curv[u]; // (then cand < INF: it fits the signed atomic)
+				curv[u] = cand[u]; // "not improved" unless the atomic says otherwise
+				if (go) curv[u] = (u64)atomicMin((long long *)&dist[(size_t)nn[u] * LC + lane], (long long)cand[u]);
+			}
+			u64 my_im = 0;
+			int my_n = 0;
+#pragma unroll
+			for (int u = 0; u < UNR; u++) {
+				const u64 im = __ballot(cand[u] < curv[u]);
+				if (lane == u) {
+					my_im = im;
+					my_n = nn[u];
+				}
+			}
+			if (!__any(my_im != 0)) continue;
+			bool fresh_q = false, fresh_t = false;
+			if (my_im) { // lanes 0..7, one improved neighbour each: dirty in the NEXT parity's word, queued on its 0 -> non-zero transition
+				fresh_q = atomicOr(&dirty_nxt[my_n], my_im) == 0ull;
+				fresh_t = tflag[my_n] != tepoch && atomicExch(&tflag[my_n], tepoch) != tepoch;
+			}
+			relax_append(pq, pend_q, fresh_q, my_n, qnxt, nq_nxt, lane);
+			relax_append(pt, pend_t, fresh_t, my_n, touched, tcount, lane);
+		}
+	}
+	if (lane == 0) {
+		if (edges) atomicAdd(&s_edges, edges);
+		s_pend[0][wib] = pend_q;
+		s_pend[1][wib] = pend_t;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		const u32 tq = (u32)(s_pend[0][0] + s_pend[0][1] + s_pend[0][2] + s_pend[0][3]);
+		const u32 tt = (u32)(s_pend[1][0] + s_pend[1][1] + s_pend[1][2] + s_pend[1][3]);
+		s_base[0] = tq ? atomicAdd(nq_nxt, tq) : 0u;
+		s_base[1] = tt ? atomicAdd(tcount, tt) : 0u;
+		if (s_edges) atomicAdd(relaxed_edges, s_edges);
+		if (blockIdx.x == 0 && nq) *rounds += 1; // a round enqueued behind an empty queue is none
+	}
+	__syncthreads();
+	u32 oq = s_base[0], ot = s_base[1];
+	for (int k = 0; k < wib; k++) {
+		oq += (u32)s_pend[0][k];
+		ot += (u32)s_pend[1][k];
+	}
+	if (lane < pend_q) qnxt[oq + lane] = pq[lane];
+	if (lane < pend_t) touched[ot + lane] = pt[lane];
+}
+
+template <typename T> static int hop_grid(unsigned *grid) { // relax_grid for k_relax_hops
+	static unsigned cached[64] = {};
+	return resident_grid(k_relax_hops<T>, cached, grid);
+}
+
+// The lane batches b0, b0 + bstride, ... < nb of a bounded call, one lane per distinct source like RelaxBatches: each batch
+// runs min(K, rounds until its queue is empty) rounds of the two launches above.  Rounds are enqueued in groups of up to
+// kHopGroup without a host wait — the kernels read the queue's fill on the device, k_round_reset clears the next one, a
+// round behind an empty queue does nothing — and the counter block comes back once per group.  `snap` and `snapmask`
+// live in the worker's second RelaxSide (labels, first dirty array), whose labels a later two-ended call must not trust.
+template <typename T> class HopBatches : RelaxWorker {
+	using DT = int64_t; // 8-byte labels only
+	static constexpr int kHopGroup = 8;
+public:
+	HopBatches(const RelaxWorker &w, u32 U, int64_t K) : RelaxWorker(w), U(U), K(K) {}
+
+	int run(int b0, int bstride) {
+		PGQ_TRY(sd.prepare<DT>(V, relax_label_tag<T, DT>(), (DT)Inf<T>::bits, st));
+		sn.dist_V = -1; // (stays so: what is left here is no label array)
+		PGQ_TRY(sn.dist.reserve(Vn * LC * sizeof(DT)));
+		PGQ_TRY(sn.dirty[0].reserve(Vn * 8));
+		PGQ_TRY(hop_grid<T>(&grid));
+		PGQ_TRY(priv->counters.reserve(sizeof(Counters)));
+		d_rc = reinterpret_cast<RelaxCounters *>(priv->counters.p);
+		for (b = b0; b < nb; b += bstride) {
+			lo = ws->h_bstart[b], hi = ws->h_bstart[b + 1];
+			if (lo == hi) continue;
+			PGQ_TRY(start_batch());
+			for (int64_t done = 0; done < K && nq_now != 0; done += kHopGroup) PGQ_TRY(round_group((int)std::min<int64_t>(kHopGroup, K - done)));
+			PGQ_TRY(finish_batch());
+		}
+		return settle<T, DT>(1);
+	}
+private:
+	const u32 U;
+	const int64_t K;
+	RelaxSide &sd = priv->relax[0], &sn = priv->relax[1];
+	RelaxCounters *d_rc = nullptr, *const h_rc = reinterpret_cast<RelaxCounters *>(priv->h_cnt);
+	int par = 0; // from here on: the batch's (start_batch)
+	int64_t lo = 0, hi = 0, base = 0;
+	u32 nq_now = 0, rounds_seen = 0, snap_seen = 0;
+	u64 edges = 0;
+
+	int start_batch() {
+		S.batches++;
+		base = (int64_t)b * LC;
+		tepoch++;
+		PGQ_HIP_TRY(hipMemsetAsync(d_rc, 0, sizeof(RelaxCounters), st));
+		KernelTimer kt(st, K_PREP);
+		hipLaunchKernelGGL(k_cheapest_init<DT>, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base, sd.dist.as<DT>(), sd.dirty[0].as<u64>(),
+		                   sd.tflag.as<u32>(), tepoch, sd.touched.as<int32_t>(), &d_rc->nq[0], &d_rc->tcount, sd.q[0].as<int32_t>());
+		kt.stop();
+		par = 0;
+		nq_now = (u32)std::min<int64_t>(LC, (int64_t)U - base);
+		rounds_seen = snap_seen = 0;
+		edges = 0;
+		return PGQ_OK;
+	}
+	int round_group(int rounds) {
+		for (int r = 0; r < rounds; r++, par ^= 1) {
+			hipLaunchKernelGGL(k_round_reset, dim3(1), dim3(64), 0, st, d_rc, par ^ 1);
+			// the group's first round knows its queue's fill; the others size their grids for a full one
+			const unsigned g = r == 0 ? std::min(grid, std::max(1u, (nq_now + 3) / 4)) : grid;
+			KernelTimer kt(st, K_RELAX);
+			hipLaunchKernelGGL(k_hop_snapshot<DT>, dim3(g), dim3(256), 0, st, sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.dirty[par].as<u64>(), sd.dist.as<DT>(),
+			                   sn.dist.as<DT>(), sn.dirty[0].as<u64>(), &d_rc->snap_rows);
+			hipLaunchKernelGGL(k_relax_hops<T>, dim3(g), dim3(256), 0, st, c->off, c->adj, (const T *)c->w, sd.dist.as<DT>(), sn.dist.as<DT>(),
+			                   sn.dirty[0].as<u64>(), sd.dirty[par ^ 1].as<u64>(), sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.q[par ^ 1].as<int32_t>(),
+			                   &d_rc->nq[par ^ 1], sd.tflag.as<u32>(), tepoch, sd.touched.as<int32_t>(), &d_rc->tcount, &d_rc->relaxed_edges, &d_rc->rounds);
+			kt.stop();
+		}
+		PGQ_TRY(read_back(h_rc, d_rc, sizeof(RelaxCounters)));
+		if (trace)
+			fprintf(stderr, "hops b=%d rounds=%u edges=%llu next=%u\n", b, h_rc->rounds, (unsigned long long)h_rc->relaxed_edges, h_rc->nq[par]);
+		// the block's counters run on over the batch: what this group added
+		S.levels += h_rc->rounds - rounds_seen;
+		S.algo_bytes[K_RELAX] += (double)(h_rc->snap_rows - snap_seen) * (2.0 * sizeof(DT) * LC + 16.0); // a row read and written, the dirty word exchanged, the mask written
+		rounds_seen = h_rc->rounds;
+		snap_seen = h_rc->snap_rows;
+		edges = h_rc->relaxed_edges;
+		nq_now = h_rc->nq[par];
+		return PGQ_OK;
+	}
+	int finish_batch() {
+		hipLaunchKernelGGL(k_cheapest_results<DT>, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(),
+		                   ws->sidx.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_out, d_ok);
+		end_batch<T, DT>(edges, 1, d_rc);
+		// stopped at the bound with vertices still queued: their dirty words go back to zero for the next batch
+		if (nq_now != 0) PGQ_HIP_TRY(hipMemsetAsync(sd.dirty[par].p, 0, Vn * 8, st));
+		return PGQ_OK;
+	}
+};
+
 // ---- general graphs, about one destination per source: both ends at once (BidirBatches, round 6) ------------------
 // The batched relaxation above gives a lane the distances from its source to EVERY vertex under the lane's bound: on the
 // weighted knows graph (weights 1..999, mean degree 89) that is most of the graph per source, ~14 expansions per vertex and
@@ -1755,10 +2002,14 @@ private:
 	}
 };
 
+// max_hops: negative = unbounded.  A bound of V - 1 or more IS the unbounded search (a cheapest walk repeats no vertex under
+// non-negative weights) and takes its drivers; a smaller one takes HopBatches alone — no chain pre-pass, no k_wbibfs, no
+// light-edges-first lists, no two-ended batches, no 4-byte labels: none of them knows hops.
 template <typename T>
 static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                           int64_t *d_out, uint8_t *d_ok, bool chain) {
-	if (chain && options().chain && n > 0 && n < (1LL << 31)) return cheapest_with_chains<T>(c, ws, n, d_src, d_dst, d_out, d_ok);
+                           int64_t *d_out, uint8_t *d_ok, bool chain, int64_t max_hops) {
+	const bool bounded = max_hops >= 0 && max_hops < c->V - 1;
+	if (!bounded && chain && options().chain && n > 0 && n < (1LL << 31)) return cheapest_with_chains<T>(c, ws, n, d_src, d_dst, d_out, d_ok);
 	hipStream_t st = ws->stream;
 	pgq_stats_t &S = tstats().s;
 	S.pairs += n;
@@ -1770,10 +2021,10 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	const int nb = (int)(((int64_t)U + LC - 1) / LC);
 	PGQ_TRY(batch_bounds(ws, n, LC, nb));
 	const int64_t *bs = ws->h_bstart;
-	if (light_edges_first(c)) { // once per CSR, before the workers need them
+	if (!bounded && light_edges_first(c)) { // once per CSR, before the workers need them (hop-bounded rounds: plain lists, no mean)
 		PGQ_TRY(ensure_weight_sorted(c, ws));
 		PGQ_TRY(ensure_weight_mean(c, ws));
-	} else if (options().relax_delta_div > 0) {
+	} else if (!bounded && options().relax_delta_div > 0) {
 		PGQ_TRY(ensure_weight_mean(c, ws));
 	}
 	// Independent batches overlap on several streams (one host thread each, like the lane batches of the unweighted
@@ -1782,13 +2033,14 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	if (workers > 1) { // every extra worker holds its own label array (V x 64 x 8 bytes): only while half the free memory covers them
 		size_t free_b = 0, total_b = 0;
 		PGQ_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-		const size_t per_worker = (size_t)std::max<int64_t>(c->V, 1) * (LC * 8 + 64) + (size_t)(c->E / 64) * 4;
+		// (a bounded worker: the snapshot rows and their masks besides)
+		const size_t per_worker = (size_t)std::max<int64_t>(c->V, 1) * (LC * 8 + 64 + (bounded ? LC * 8 + 8 : 0)) + (size_t)(c->E / 64) * 4;
 		workers = (int)std::min<size_t>((size_t)workers, 1 + free_b / 2 / per_worker);
 	}
 	// `light` (and with it the label width DT) is decided ONCE, here, and handed to every worker: a concurrent pgq_set_option
 	// between two evaluations used to leave a worker with 4-byte labels outside the light-edges-first path (an "internal error"
 	// return).  The weight-sorted copy above has left the mean on the handle; one that is not positive and finite: plain rounds.
-	const bool light = light_edges_first(c) && c->wadj && c->w_mean > 0 && c->w_mean < 1e300;
+	const bool light = !bounded && light_edges_first(c) && c->wadj && c->w_mean > 0 && c->w_mean < 1e300;
 	const bool narrow = light && labels_fit_32<T>(c);
 	// about one destination per source (a list of pairs, not a cross product): every row is a lane of its own, searched from
 	// both ends (BidirBatches); many destinations per source share their source's lane as before
@@ -1807,6 +2059,7 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	}
 	auto run_relax = [&](Workspace *priv, int b0, int bstride) -> int {
 		const RelaxWorker w { c, ws, priv, nb_run, d_out, d_ok };
+		if (bounded) return HopBatches<T>(w, U, max_hops).run(b0, bstride);
 		if constexpr (std::is_same<T, int64_t>::value) {
 			if (bidir) return narrow ? BidirBatches<int32_t>(w, R).run(b0, bstride) : BidirBatches<int64_t>(w, R).run(b0, bstride);
 			if (narrow) return RelaxBatches<T, int32_t>(w, U, light).run(b0, bstride);
@@ -1847,26 +2100,33 @@ using namespace pgq;
 
 extern "C" {
 
-int pgq_cheapest_path_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                                         void *d_out, uint8_t *d_out_valid) {
+// max_hops: null = unbounded (iterativelength_bulk's convention).  The bounded forms answer a NULL handle before anything else.
+static int cheapest_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, void *d_out, uint8_t *d_out_valid,
+                         const int64_t *max_hops) {
+	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	const bool arrays = d_src && d_dst && d_out && d_out_valid;
-	auto check = [&] {
+	auto check = [&]() -> int {
 		PGQ_TRY(check_weighted(csr));
-		return check_arrays(csr, n, arrays, "NULL device array");
+		PGQ_TRY(check_arrays(csr, n, arrays, "NULL device array"));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
+		return PGQ_OK;
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) {
+		const int64_t bound = max_hops ? *max_hops : -1;
 		if (csr->w_type == PGQ_W_INT64)
-			return cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true);
-		return cheapest_device<double>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true);
+			return cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true, bound);
+		return cheapest_device<double>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true, bound);
 	});
 }
 
-int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
-                             uint64_t *out_valid) {
-	auto check = [&] {
+static int cheapest_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out, uint64_t *out_valid,
+                          const int64_t *max_hops) {
+	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
 		PGQ_TRY(check_weighted(csr));
 		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
 		if (n < 0 || (n > 0 && (!out || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		return n == 0 ? kNoRows : PGQ_OK;
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
@@ -1878,11 +2138,30 @@ int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 		PGQ_TRY(ws->out_ok.reserve((size_t)n));
 		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
 		const int64_t *d_src = ws->in_src.as<int64_t>(), *d_dst = ws->in_dst.as<int64_t>();
+		const int64_t bound = max_hops ? *max_hops : -1;
 		PGQ_TRY(csr->w_type == PGQ_W_INT64
-		            ? cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true)
-		            : cheapest_device<double>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true));
+		            ? cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true, bound)
+		            : cheapest_device<double>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true, bound));
 		return download_valid(ws, n, out, out_valid);
 	});
+}
+
+int pgq_cheapest_path_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
+                                         void *d_out, uint8_t *d_out_valid) {
+	return cheapest_bulk(csr, n, d_src, d_dst, d_out, d_out_valid, nullptr);
+}
+int pgq_cheapest_path_length_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                                void *d_out, uint8_t *d_out_valid) {
+	return cheapest_bulk(csr, n, d_src, d_dst, d_out, d_out_valid, &max_hops);
+}
+
+int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
+                             uint64_t *out_valid) {
+	return cheapest_chunk(csr, V, n, src, dst, out, out_valid, nullptr);
+}
+int pgq_cheapest_path_length_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, void *out,
+                                    uint64_t *out_valid) {
+	return cheapest_chunk(csr, V, n, src, dst, out, out_valid, &max_hops);
 }
 
 } // extern "C"

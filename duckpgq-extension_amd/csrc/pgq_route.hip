@@ -731,10 +731,13 @@ int pgq_shortestpath_within_multi(pgq_csr_t *csr, int64_t n, const int64_t *src,
 
 // cheapest_path_length on all enabled devices: out = n values (int64 or double by the CSR's weight type), out_valid = n
 // bytes (1 = a path exists)
-int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, void *out,
-                                   uint8_t *out_valid) {
-	auto check = [&] {
+// (max_hops: null = unbounded; the bounded form answers a NULL handle before anything else, like its single-device forms)
+static int cheapest_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, void *out, uint8_t *out_valid,
+                          const int64_t *max_hops = nullptr) {
+	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
 		PGQ_TRY(check_arrays(csr, n, src && dst && out && out_valid, "NULL array"));
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		return n == 0 ? kNoRows : PGQ_OK;
 	};
 	auto shard = [&](int, int64_t lo, int64_t hi, pgq_csr_t *replica, Workspace *ws) -> int {
@@ -750,14 +753,23 @@ int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src
 		                     hipStreamSynchronize(ws->stream) != hipSuccess))
 			rc = fail(PGQ_ERR_HIP, "copying a shard's rows to its device failed");
 		if (rc == PGQ_OK)
-			rc = pgq_cheapest_path_length_bulk_device(replica, m, d_src.as<int64_t>(), d_dst.as<int64_t>(), d_val.p,
-			                                          d_ok.as<uint8_t>());
+			rc = max_hops ? pgq_cheapest_path_length_within_bulk_device(replica, m, d_src.as<int64_t>(), d_dst.as<int64_t>(), *max_hops, d_val.p,
+			                                                            d_ok.as<uint8_t>())
+			              : pgq_cheapest_path_length_bulk_device(replica, m, d_src.as<int64_t>(), d_dst.as<int64_t>(), d_val.p, d_ok.as<uint8_t>());
 		if (rc == PGQ_OK) rc = staged_download(static_cast<char *>(out) + (size_t)lo * 8, d_val.p, bytes, ws->stream);
 		if (rc == PGQ_OK) rc = staged_download(out_valid + lo, d_ok.p, (size_t)m, ws->stream);
 		for (DevBuf *b : { &d_src, &d_dst, &d_val, &d_ok }) b->release();
 		return rc;
 	};
 	return c_entry<false>(csr, check, [&] { return run_shards(csr, n, shard); });
+}
+int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, void *out,
+                                   uint8_t *out_valid) {
+	return cheapest_multi(csr, n, src, dst, out, out_valid);
+}
+int pgq_cheapest_path_length_within_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t max_hops, void *out,
+                                          uint8_t *out_valid) {
+	return cheapest_multi(csr, n, src, dst, out, out_valid, &max_hops);
 }
 
 // pinned, device-addressable staging block of a workspace (grown on demand)

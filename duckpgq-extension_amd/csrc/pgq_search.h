@@ -309,7 +309,8 @@ struct Workspace {
 	size_t h_io_cap = 0;
 	int64_t *h_bstart = nullptr;
 	size_t h_bstart_cap = 0;
-	RelaxSide relax[2];    // cheapest path: the forward (0) and the backward (1, BidirBatches) search state
+	RelaxSide relax[2];    // cheapest path: the forward (0) and the backward (1, BidirBatches) search state; the hop-bounded rounds
+	                       // (HopBatches) keep their snapshot rows and masks in [1]'s label and first dirty array and leave its dist_V at -1
 	void *h_bi = nullptr;  // pinned: the bidirectional relaxation's counter block, copied back once per round
 	~Workspace();
 };

@@ -352,8 +352,9 @@ int pgq_udf_bind_cheapest(pgq_state_t *s, int32_t id, int *ret_type) { // cheape
 	return 0;
 }
 
-int pgq_udf_cheapest_path_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
-                                 void *out, uint64_t *out_valid) {
+// max_hops: null = unbounded
+static int cheapest_path_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
+                                uint64_t *out_valid, const int64_t *max_hops) {
 	if (!s) return fail("Invalid Input Error: NULL state");
 	CsrRef c = find_csr(s, id);
 	if (!c) return fail("Constraint Error: CSR not found with ID " + std::to_string(id));
@@ -362,10 +363,22 @@ int pgq_udf_cheapest_path_length(pgq_state_t *s, int32_t id, int64_t V, int64_t 
 	if ((int64_t)c->vsize != V + 2) return fail("Invalid Input Error: vertex count does not match the CSR");
 	pgq_csr_t *d = device_csr(s, c, V);
 	if (!d) return device_fail();
-	if (pgq_cheapest_path_length(d, V, n, src, dst, out, out_valid) != PGQ_OK) return device_fail();
+	const int rc = max_hops ? pgq_cheapest_path_length_within(d, V, n, src, dst, *max_hops, out, out_valid)
+	                        : pgq_cheapest_path_length(d, V, n, src, dst, out, out_valid);
+	if (rc != PGQ_OK) return device_fail();
 	std::lock_guard<std::mutex> g(s->csr_lock);
 	s->csr_to_delete.insert(id); // cheapest_path_length.cpp:162
 	return 0;
+}
+
+int pgq_udf_cheapest_path_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
+                                 void *out, uint64_t *out_valid) {
+	return cheapest_path_length(s, id, V, n, src, dst, out, out_valid, nullptr);
+}
+
+int pgq_udf_cheapest_path_length_within(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                                        void *out, uint64_t *out_valid) {
+	return cheapest_path_length(s, id, V, n, src, dst, out, out_valid, &max_hops);
 }
 
 int pgq_udf_reachability(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint8_t *out,

@@ -2,7 +2,7 @@
 // libpgq_hip (include/pgq_hip.h).  Names, argument lists, exception texts and NULL rules are the reference's:
 //   IterativeLengthFunction        src/core/functions/scalar/iterativelength.cpp:34-143   (also registered as iterativelength2)
 //   ShortestPathFunction           src/core/functions/scalar/shortest_path.cpp:43-207   (ShortestPathWithinFunction: its five-argument overload)
-//   CheapestPathLengthFunction     src/core/functions/scalar/cheapest_path_length.cpp:138-163
+//   CheapestPathLengthFunction     src/core/functions/scalar/cheapest_path_length.cpp:138-163   (CheapestPathLengthWithinFunction: its five-argument overload)
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
 // plus PathFindingRelation, the whole-relation entry point SURVEY.md §8f rank 2 asks for (length and path of every
@@ -154,7 +154,9 @@ void ShortestPathWithinFunction(DataChunk &args, ExpressionState &state, Vector 
 	ShortestPath(args, state, result, &upper);
 }
 
-void CheapestPathLengthFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+namespace {
+// cheapest_path_length with four arguments (upper == nullptr) or five
+void CheapestPathLength(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper) {
 	auto &info = state.expr.Cast<BoundFunctionExpression>().BindInfo()->Cast<CheapestPathLengthFunctionData>();
 	auto duckpgq_state = GetDuckPGQState(info.context);
 	auto entry = duckpgq_state->csr_list.find(info.csr_id);
@@ -173,10 +175,25 @@ void CheapestPathLengthFunction(DataChunk &args, ExpressionState &state, Vector 
 	// BIGINT result for int64 weights, DOUBLE otherwise: the bind fixed the type (cheapest_path_length_function_data.cpp:25-29)
 	void *out = csr.w.empty() ? static_cast<void *>(FlatVector::GetDataMutable<double>(result))
 	                          : static_cast<void *>(FlatVector::GetDataMutable<int64_t>(result));
-	if (pgq_cheapest_path_length(DeviceCSR(*duckpgq_state, csr, v_size), v_size, (int64_t)args.size(), AsVec(src), AsVec(dst),
-	                             out, validity.GetData()) != PGQ_OK)
-		ThrowDevice();
+	pgq_csr_t *device = DeviceCSR(*duckpgq_state, csr, v_size);
+	const int rc = upper ? pgq_cheapest_path_length_within(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *upper, out, validity.GetData())
+	                     : pgq_cheapest_path_length(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), out, validity.GetData());
+	if (rc != PGQ_OK) ThrowDevice();
 	duckpgq_state->csr_to_delete.insert(info.csr_id);
+}
+} // namespace
+
+void CheapestPathLengthFunction(DataChunk &args, ExpressionState &state, Vector &result) { CheapestPathLength(args, state, result, nullptr); }
+
+// cheapest_path_length(csr_id, V, src, dst, upper): the five-argument overload for a quantified edge pattern with an upper bound
+// (match.cpp:658-671 passes subpath->upper to the search functions).  Unlike the hop counts' overloads this one changes the VALUE:
+// the cheapest walk of at most `upper` edges is in general another walk than the unbounded cheapest one, which the pattern does not
+// admit — no filter around the four-argument call can produce this number.
+void CheapestPathLengthWithinFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	UnifiedVectorFormat upper_fmt; // a constant of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	CheapestPathLength(args, state, result, &upper);
 }
 
 void LocalClusteringCoefficientFunction(DataChunk &args, ExpressionState &state, Vector &result) {

@@ -192,6 +192,22 @@ int pgq_shortestpath_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src,
 int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
                              uint64_t *out_valid);
 
+/* cheapest_path_length(csr_id, V, src, dst, upper) -> BIGINT | DOUBLE: the cost of the cheapest walk src -> dst of AT MOST
+ * max_hops edges, for a quantified edge pattern with an upper bound (match.cpp:658-671).  With INF = numeric_limits<T>::max() / 2
+ * (cheapest_path_length.cpp:15) the result is D_K[dst], K = max_hops, of
+ *     D_0[src] = 0, D_0[v] = INF otherwise;   D_k[n] = min(D_{k-1}[n], min over edges (u, n) of D_{k-1}[u] + w(u, n))
+ * — the sum is the reference's `dist[v] + w` (cheapest_path_length.cpp:29-36) and counts only where it is < D_{k-1}[n] — and NULL
+ * when D_K[dst] == INF.  For non-negative weights that is the minimum, over the walks of at most K edges, of the left-to-right
+ * fold of their weights, bit for bit, for int64 and for double.  NaN and +inf weights never relax an edge, -0.0 is accepted.
+ * WARNING: this is NOT pgq_cheapest_path_length with far rows set to NULL.  The cheapest walk of at most K edges is in general a
+ * different walk from the unbounded cheapest one and costs more; no filter around the unbounded call can produce it.  The
+ * reference has no counterpart either: its Bellman-Ford sweeps in place, so its rounds are not hops.
+ * NULL src or NULL dst -> NULL; src == dst -> 0 (+0.0) for every max_hops >= 0; max_hops >= V - 1 (INT64_MAX: the binder's "no
+ * upper bound") is the unbounded search, the same bits as pgq_cheapest_path_length; max_hops < 0 -> PGQ_ERR_INVALID_ARG.  An
+ * unweighted CSR, negative weights and ids out of range fail as in pgq_cheapest_path_length. */
+int pgq_cheapest_path_length_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, void *out,
+                                    uint64_t *out_valid);
+
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
  * freed CSR / upload blocks kept for the next upload (PGQ_ALLOC_CACHE_MB). */
@@ -226,6 +242,10 @@ int pgq_shortestpath_within_multi(pgq_csr_t *csr, int64_t n, const int64_t *src,
  * out = n int64 or double (by weight type), out_valid = n bytes. */
 int pgq_cheapest_path_length_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, void *out,
                                    uint8_t *out_valid);
+/* pgq_cheapest_path_length_multi under the pattern's upper bound (pgq_cheapest_path_length_within_bulk_device per shard): the
+ * cheapest walk of at most max_hops edges per row — another number than the unbounded one, see pgq_cheapest_path_length_within. */
+int pgq_cheapest_path_length_within_multi(pgq_csr_t *csr, int64_t n, const int64_t *src, const int64_t *dst, int64_t max_hops, void *out,
+                                          uint8_t *out_valid);
 /* Measurement helper: same search, additionally d_out_te[i] = edges traversed by pair i's own level-synchronous BFS
  * up to the level that reaches dst (all levels if unreachable) — the numerator of bench.py's MTEPS. */
 int pgq_traversed_edges_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
@@ -247,6 +267,10 @@ int pgq_shortestpath_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t
  * (n bytes, 1 = valid) carries validity. */
 int pgq_cheapest_path_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst,
                                          void *d_out, uint8_t *d_out_valid);
+/* pgq_cheapest_path_length_within without the chunk ceiling: as pgq_cheapest_path_length_bulk_device, each row the cost of its
+ * cheapest walk of at most max_hops edges (NOT the unbounded cost with far rows NULL: see pgq_cheapest_path_length_within). */
+int pgq_cheapest_path_length_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                                void *d_out, uint8_t *d_out_valid);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

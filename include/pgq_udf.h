@@ -17,6 +17,7 @@
  *   pgq_udf_shortestpath_within     ShortestPathFunction with the pattern's upper bound as fifth argument (match.cpp:467-495, 658-671)
  *   pgq_udf_bind_cheapest           CheapestPathLengthBind       src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
+ *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
  *   pgq_udf_delete_csr              DeleteCsrFunction            src/core/functions/scalar/csr_deletion.cpp:10-20
  *   pgq_udf_csr_get_w_type          GetCsrWTypeFunction          src/core/functions/scalar/csr_get_w_type.cpp:16-36
  *   pgq_udf_reachability            ReachabilityFunction         src/core/functions/scalar/reachability.cpp:165-254 (intended semantics)
@@ -76,6 +77,11 @@ int pgq_udf_shortestpath_within(pgq_state_t *, int32_t id, int64_t V, int64_t n,
 int pgq_udf_bind_cheapest(pgq_state_t *, int32_t id, int *ret_type);
 int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                                  void *out, uint64_t *out_valid);
+/* cheapest_path_length(id, V, src, dst, upper): the cheapest walk of at most max_hops edges (pgq_cheapest_path_length_within: not
+ * the unbounded cost with far rows NULL); errors as for pgq_udf_cheapest_path_length, max_hops < 0 is the device library's
+ * PGQ_ERR_INVALID_ARG */
+int pgq_udf_cheapest_path_length_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                                        void *out, uint64_t *out_valid);
 /* reachability(id, is_variant, V, src, dst) -> BOOL; the reference's BOOL argument only selects one of its three
  * internal BFS modes (reachability.cpp:154-163) and does not change the result, so it is not part of this call.
  * Boolean reachability with the semantics the reference intends (reachability.cpp:165-254 indexes its inputs
