@@ -100,6 +100,18 @@ LDS_LIMITS = {
 }
 
 
+# The limits of the lane batches' destination probes (pgq_msbfs.hip: k_probe, k_probe2; pgq_internal.h: the options' defaults).
+# helpers.probe_gadgets and test_probe_limits_gpu.py stand on them; test_probe_gadgets_cpu.py reads them back from the sources.
+PROBE_LIMITS = {
+    "kQueue": 1024,         # k_probe: open rows a workgroup pools in LDS before it probes a chunk's rows where it finds them
+    "kHubQueue": 256,       # k_probe: rows of hub destinations a workgroup sets aside for all its 16 wavefronts
+    "kOpenGrid": 512,       # workgroups of 1024 threads k_probe / k_detect run at most: 8192 wavefronts
+    "hub_step": 4 * 1024,   # k_probe: in-neighbours of a hub destination per step of the whole workgroup
+    "probe_max_in": 4096,   # option: a destination with MORE in-neighbours is a hub destination
+    "probe2_cap": 1 << 16,  # option: a pair whose two-hop walk holds MORE in-edges is left open by k_probe2
+}
+
+
 # ---- gadgets whose adjacency-list lengths sit on the kernels' own constants ----------------------------------------------
 
 GADGET_DEGREES = (1, 2, 63, 64, 65, 319, 320, 321, 511, 512, 513, 4095, 4096, 4097)
@@ -408,3 +420,149 @@ def spread_ids(rng, n, V):
     ids = np.unique(np.concatenate([fixed, rng.choice(top, n, replace=False)]))
     drop = rng.choice(np.flatnonzero(~np.isin(ids, fixed)), len(ids) - n, replace=False)
     return np.delete(ids, drop).astype(np.int64)
+
+
+# ---- gadgets on the limits of the lane batches' destination probes (k_probe, k_probe2) -------------------------------------
+PROBE_DEGREES = (1, 2, 63, 64, 65, 1023, 1024, 1025, 4095, 4096, 4097, 8191, 8192, 8193)
+PROBE_POSITIONS = (0, 63, 64, 1023, 1024, 4095, 4096, "last")
+PROBE2_FANS = (1, 15, 16, 17, 32, 33)       # in-degree of a two-hop gadget's destination
+PROBE2_FAN_POSITIONS = (0, 15, 16, "last")  # where among them the one in-neighbour sits that leads on
+PROBE2_LISTS = (65, 129)                    # length of that in-neighbour's own in-list ...
+PROBE2_LIST_POSITIONS = (0, 63, 64, "last")  # ... and the witness's position in it
+PROBE2_CAP = 4096                           # the probe2_cap the two-hop gadgets' walk sizes sit on
+_PROBE_POOL = 8192
+
+
+class ProbeGadgets:
+    """V, the edge table (src, dst), the rows (rs, rd; dist with -1 = unreachable; tag; kind: one / two / indeg0 / self /
+    decoys; b = in-degree of the destination, p = position of the one in-neighbour on the path in its in-list, both -1 where
+    the row has none; walk = in-degree sum over N_in(dst) for two-hop rows, else -1) and one record per gadget."""
+
+    def __init__(self, V, src, dst, rows, gadgets):
+        self.V, self.src, self.dst, self.gadgets = V, src, dst, gadgets
+        self.rs = np.array([r[0] for r in rows], dtype=np.int64)
+        self.rd = np.array([r[1] for r in rows], dtype=np.int64)
+        self.dist = np.array([r[2] for r in rows], dtype=np.int64)
+        self.tag = np.array([r[3] for r in rows])
+        self.kind = np.array([r[4] for r in rows])
+        self.b = np.array([r[5] for r in rows], dtype=np.int64)
+        self.p = np.array([r[6] for r in rows], dtype=np.int64)
+        self.walk = np.array([r[7] for r in rows], dtype=np.int64)
+
+    def rows_where(self, pick):
+        return np.array([g["row"] for g in self.gadgets if pick(g)], dtype=np.int64)
+
+
+def probe_gadgets(cap=PROBE2_CAP):
+    """One graph of gadgets for the destination probes.  The reverse CSR orders an in-list by (source id, slot), so a vertex's
+    position in N_in(dst) is its id's rank among the in-neighbours: a LOW pool of decoys holds the smallest ids, a HIGH pool
+    the largest, sources, chains and destinations lie between.  A decoy has in-degree 0: it is in no frontier.  A list of n
+    entries with its one live entry at position p takes p decoys from the low pool and n - 1 - p from the high pool.
+
+    One-hop gadgets (kind one, tag one_k<k>_b<b>_p<p>): a chain source = c0 -> .. -> c(k-1) -> dst, k = 1, 2, 3, so dst is
+    exactly k hops away by one path and c(k-1), the witness k_probe looks for at level k, sits at position p of the b entries
+    of N_in(dst); b in PROBE_DEGREES, p in PROBE_POSITIONS where below b.
+
+    Two-hop gadgets (kind two, tag two_k<k>_f<b1>_q<q>_n<n>_v<pv>_w<walk - cap>): dst has b1 in-neighbours u_0 .. u_(b1-1), in
+    id order; only u_q has a live in-neighbour, the witness v, at position pv of u_q's n in-neighbours; v is k - 2 hops from
+    the source (k = 2: the source itself).  The others' in-lists are decoys, sized so that the in-degree sum over N_in(dst) —
+    k_probe2's walk — is cap - 1, cap or cap + 1 (b1 = 1: the walk is n).  Every (b1, q) has every (n, pv) at the cap and two of
+    them at cap - 1 and cap + 1 for k = 2, one at each walk for k = 3.
+
+    Other rows: indeg0 (a decoy as destination: nothing points at it), self (src == dst), decoys (a destination whose whole
+    in-list of b entries is decoys: unreachable after a full scan, asked from the source of a k = 3 gadget)."""
+    low = np.arange(_PROBE_POOL, dtype=np.int64)
+    high = -1 - np.arange(_PROBE_POOL, dtype=np.int64)  # placed behind the last id between the pools at the end
+    count = [_PROBE_POOL]
+    es, ed, rows, gadgets = [], [], [], []
+
+    def new(n=None):
+        at = count[0]
+        count[0] += 1 if n is None else n
+        return at if n is None else np.arange(at, at + n, dtype=np.int64)
+
+    def edges(s, d):
+        s, d = np.broadcast_arrays(np.asarray(s, dtype=np.int64), np.asarray(d, dtype=np.int64))
+        es.append(s.ravel())
+        ed.append(d.ravel())
+
+    def in_list(live, n, p):
+        assert 0 <= p < n and p <= _PROBE_POOL and n - 1 - p <= _PROBE_POOL
+        return np.concatenate([low[:p], [live], high[:n - 1 - p]]).astype(np.int64)
+
+    def chain(k):  # k edges: k + 1 vertices
+        c = [new() for _ in range(k + 1)]
+        if k:
+            edges(c[:-1], c[1:])
+        return c
+
+    def row(s, d, dist, tag, kind, b=-1, p=-1, walk=-1):
+        rows.append((s, d, dist, tag, kind, b, p, walk))
+        return len(rows) - 1
+
+    def index(pos, n):
+        idx = n - 1 if pos == "last" else pos
+        return idx if idx < n else None
+
+    # one-hop
+    for k in (1, 2, 3):
+        for b in PROBE_DEGREES:
+            for p in sorted({index(pos, b) for pos in PROBE_POSITIONS} - {None}):
+                c = chain(k - 1)
+                d = new()
+                edges(in_list(c[-1], b, p), d)
+                t = "one_k%d_b%d_p%d" % (k, b, p)
+                r = row(c[0], d, k, t, "one", b, p)
+                gadgets.append(dict(tag=t, kind="one", k=k, b=b, p=p, src=c[0], dst=d, path=c + [d], row=r))
+                if len(gadgets) % 7 == 0:
+                    row(c[0], int(low[(p + 11 * len(gadgets)) % _PROBE_POOL]), -1, t + "_indeg0", "indeg0", 0)
+                if len(gadgets) % 5 == 0:
+                    row(c[0], c[0], 0, t + "_self_src", "self")
+                    row(d, d, 0, t + "_self_dst", "self")
+    far = [g for g in gadgets if g["k"] == 3]
+    for i, b in enumerate((1, 64, 65, 1024, 4096, 4097, 8193)):
+        d = new()
+        edges(np.concatenate([low[:b // 2], high[:b - b // 2]]), d)
+        for g in far[i::7][:3]:
+            row(g["src"], d, -1, "decoys_b%d_from_%s" % (b, g["tag"]), "decoys", b)
+
+    # two-hop
+    def two_hop(k, b1, q, n, pv, walk):
+        c = chain(k - 2)
+        us = new(b1)
+        d = new()
+        edges(us, d)
+        edges(in_list(c[-1], n, pv), us[q])
+        if b1 == 1:
+            walk = n
+        else:
+            rest, others = walk - n, np.delete(us, q)
+            assert rest >= 0
+            for i, u in enumerate(others):
+                m = rest // len(others) + (1 if i < rest % len(others) else 0)
+                edges(low[(7 * i + np.arange(m)) % _PROBE_POOL], u)
+        t = "two_k%d_f%d_q%d_n%d_v%d_w%+d" % (k, b1, q, n, pv, walk - cap)
+        r = row(c[0], d, k, t, "two", b1, q, walk)
+        gadgets.append(dict(tag=t, kind="two", k=k, b=b1, p=q, n=n, pv=pv, walk=walk, src=c[0], dst=d,
+                            path=c + [int(us[q]), d], row=r))
+
+    cells = sorted({(n, index(pos, n)) for n in PROBE2_LISTS for pos in PROBE2_LIST_POSITIONS})
+    turn = 0
+    for b1 in PROBE2_FANS:
+        for q in sorted({index(pos, b1) for pos in PROBE2_FAN_POSITIONS} - {None}):
+            for n, pv in cells:
+                two_hop(2, b1, q, n, pv, cap)
+            if b1 == 1:
+                continue
+            for walk in (cap - 1, cap + 1):
+                for _ in range(2):
+                    two_hop(2, b1, q, *cells[turn % len(cells)], walk)
+                    turn += 1
+            for walk in (cap - 1, cap, cap + 1):
+                two_hop(3, b1, q, *cells[turn % len(cells)], walk)
+                turn += 1
+
+    hi_base = count[0]
+    V = hi_base + _PROBE_POOL
+    real = lambda v: np.where(np.asarray(v, dtype=np.int64) < 0, hi_base - 1 - np.asarray(v, dtype=np.int64), v).astype(np.int64)
+    return ProbeGadgets(V, real(np.concatenate(es)), real(np.concatenate(ed)), rows, gadgets)
