@@ -104,6 +104,10 @@ def load_hip():
                                                C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.pgq_cheapest_path_length_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+    L.pgq_cheapest_path.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_cheapest_path_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -159,6 +163,8 @@ def load_udf():
     L.pgq_udf_shortestpath_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+    L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_cheapest_path_length_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64,
                                                       C.c_void_p, C.c_void_p]
     for f in ("pgq_udf_local_clustering_coefficient", "pgq_udf_pagerank", "pgq_udf_weakly_connected_component"):
@@ -450,6 +456,24 @@ class DeviceCSR:
         _check(self.L.pgq_cheapest_path_length_within(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
         return out, unpack_validity(ov, n)
 
+    def cheapest_path(self, src, dst, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, raw=False):
+        """The cheapest path itself as a list [src, e1, v1, ..., ek, dst] per row (None for NULL rows): hop-minimal among the
+        cheapest paths, shortestpath's tie-breaks (include/pgq_hip.h).  raw=True: offsets, lengths, validity words, child."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        off = np.zeros(n, dtype=np.uint64)
+        ln = np.zeros(n, dtype=np.uint64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        child = C.c_void_p()
+        clen = C.c_uint64()
+        _check(self.L.pgq_cheapest_path(self.h, self.V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child), C.byref(clen)))
+        ch = np.zeros(0, dtype=np.int64)
+        if clen.value:
+            ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
+        if raw:
+            return off, ln, ov, ch
+        return _lists(off, ln, unpack_validity(ov, n), ch)
+
     # -- bulk form (device pointers; torch tensors supply them) ------------------
     def iterativelength_bulk_ptr(self, n, d_src, d_dst, d_out):
         _check(self.L.pgq_iterativelength_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
@@ -559,6 +583,13 @@ class DeviceCSR:
     def cheapest_bulk_ptr(self, n, d_src, d_dst, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                            C.c_void_p(d_out), C.c_void_p(d_ok)))
+
+    def cheapest_path_bulk_ptr(self, n, d_src, d_dst, d_out_len, d_out_off, d_child, child_cap):
+        """(status, elements needed): as shortestpath_bulk_ptr, the lists of the cheapest paths."""
+        used = C.c_int64(0)
+        rc = self.L.pgq_cheapest_path_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), C.c_void_p(d_out_len),
+                                                  C.c_void_p(d_out_off), C.c_void_p(d_child), child_cap, C.byref(used))
+        return rc, used.value
 
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
@@ -709,6 +740,24 @@ class PgqState:
 
         ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
         return out, ok
+
+    def cheapest_path(self, csr_id, V, src, dst, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        self.bind_cheapest(csr_id)
+        keep = []
+        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
+        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
+        n = len(src_sel) if src_sel is not None else len(src)
+        off = np.zeros(n, dtype=np.uint64)
+        ln = np.zeros(n, dtype=np.uint64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        child = C.c_void_p()
+        clen = C.c_uint64()
+        self._ck(self.U.pgq_udf_cheapest_path(self.s, csr_id, V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
+                                              C.byref(clen)))
+        ch = np.zeros(0, dtype=np.int64)
+        if clen.value:
+            ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
+        return _lists(off, ln, unpack_validity(ov, n), ch)
 
     def _analytics(self, fn, csr_id, src, dtype):
         keep = []

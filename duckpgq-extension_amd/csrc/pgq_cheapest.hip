@@ -991,32 +991,42 @@ __global__ __launch_bounds__(1024) void k_wbibfs(int64_t n, const int64_t *__res
 
 static std::mutex g_rw_lock;
 // in-edge weights in reverse-CSR order + the mean weight, built on first use (a stable sort of the forward slots by
-// destination: the permutation the upload used for radj)
-static int ensure_reverse_weights(pgq_csr *c, Workspace *ws) {
+// destination: the permutation the upload used for radj).  with_mean = false: the weights alone, w_mean stays what it is (the
+// sum below adds the weights as int64: cheapest_path reads the in-edge weights of double CSRs too)
+static int ensure_reverse_weights(pgq_csr *c, Workspace *ws, bool with_mean = true) {
 	std::lock_guard<std::mutex> g(g_rw_lock);
-	if (c->rw || c->E == 0) return PGQ_OK;
+	if (c->E == 0) return PGQ_OK;
+	// (a copy that cheapest_path built came without the mean: a caller that wants one gets it here, unless the handle has it)
+	const bool build = !c->rw, mean = with_mean && (build || !(c->w_mean > 0));
+	if (!build && !mean) return PGQ_OK;
 	hipStream_t st = ws->stream;
 	const int64_t E = c->E;
 	DevTemps temps(st);
 	u32 *iota = nullptr, *sslot = nullptr, *skey = nullptr;
 	int64_t *sum = nullptr;
 	void *rw = nullptr;
-	for (u32 **b : { &iota, &sslot, &skey }) PGQ_TRY(temps.alloc(b, (size_t)E));
-	PGQ_TRY(temps.alloc(&sum, 8));
-	hipLaunchKernelGGL(k_iota32, dim3(blocks_for(E)), dim3(256), 0, st, E, iota);
-	int end_bit = 1;
-	while ((1LL << end_bit) < c->V) end_bit++;
-	const u32 *keys = reinterpret_cast<const u32 *>(c->adj);
-	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, skey, iota, sslot, (int)E, 0, end_bit, st); }));
-	PGQ_TRY(temps.alloc_bytes(&rw, csr_bytes(c, c->rw)));
-	hipLaunchKernelGGL(k_gather_weights, dim3(blocks_for(E)), dim3(256), 0, st, E, sslot, (const int64_t *)c->w, (int64_t *)rw);
-	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceReduce::Sum(tmp, tb, (const int64_t *)c->w, sum, (int)E, st); }));
+	if (build) {
+		for (u32 **b : { &iota, &sslot, &skey }) PGQ_TRY(temps.alloc(b, (size_t)E));
+		hipLaunchKernelGGL(k_iota32, dim3(blocks_for(E)), dim3(256), 0, st, E, iota);
+		int end_bit = 1;
+		while ((1LL << end_bit) < c->V) end_bit++;
+		const u32 *keys = reinterpret_cast<const u32 *>(c->adj);
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, skey, iota, sslot, (int)E, 0, end_bit, st); }));
+		PGQ_TRY(temps.alloc_bytes(&rw, csr_bytes(c, c->rw)));
+		hipLaunchKernelGGL(k_gather_weights, dim3(blocks_for(E)), dim3(256), 0, st, E, sslot, (const int64_t *)c->w, (int64_t *)rw);
+	}
 	int64_t total = 0;
-	PGQ_HIP_TRY(hipMemcpyAsync(&total, sum, 8, hipMemcpyDeviceToHost, st));
+	if (mean) {
+		PGQ_TRY(temps.alloc(&sum, 8));
+		PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceReduce::Sum(tmp, tb, (const int64_t *)c->w, sum, (int)E, st); }));
+		PGQ_HIP_TRY(hipMemcpyAsync(&total, sum, 8, hipMemcpyDeviceToHost, st));
+	}
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
-	c->w_mean = (double)total / (double)E;
-	temps.keep(rw);
-	c->rw = rw;
+	if (mean) c->w_mean = (double)total / (double)E;
+	if (build) {
+		temps.keep(rw);
+		c->rw = rw;
+	}
 	return PGQ_OK;
 }
 
@@ -1378,11 +1388,24 @@ struct RelaxWorker {
 	}
 };
 
+// What cheapest_path asks of the lane batches (pgq_cheapest_path.hip) instead of the rows' costs: the labels of EVERY vertex a
+// lane reaches settled (no lane stops at its destinations' bound: see k_lane_unbound), and a call per settled batch — rows
+// [lo, hi) of the sorted arrays, lane 0 = distinct source `base` — while the batch's labels are still in place.
+struct SettledBatch {
+	std::function<int(int64_t lo, int64_t hi, int64_t base)> then;
+};
+
+// The lanes' bounds of a round for a driver that needs every label final, not only the destinations': k_lane_bounds prunes a
+// lane at the largest tentative label B among its destinations, which leaves the vertices with a final label of exactly B
+// unexpanded — and what lies behind them over zero-weight edges (final label B as well) unlabelled or too high.  A tight edge
+// into a destination may come from just there.  Without a bound the rounds run to the fixpoint of everything reachable.
+__global__ void k_lane_unbound(long long *__restrict__ bound) { bound[threadIdx.x] = 0x7FFFFFFFFFFFFFFFll; }
+
 // The lane batches b0, b0 + bstride, ... < nb of a call, one lane per distinct source: plain rounds (every edge of a changed
 // vertex; few changed vertices loop on the device) or light edges first (light_edges_first).
 template <typename T, typename DT> class RelaxBatches : RelaxWorker {
 public:
-	RelaxBatches(const RelaxWorker &w, u32 U, bool light) : RelaxWorker(w), U(U), light(light) {}
+	RelaxBatches(const RelaxWorker &w, u32 U, bool light, const SettledBatch *settled = nullptr) : RelaxWorker(w), U(U), light(light), settled(settled) {}
 
 	int run(int b0, int bstride) {
 		if (!light && sizeof(DT) == 4) return fail(PGQ_ERR_HIP, "internal error: 4-byte labels outside the light-edges-first path");
@@ -1407,13 +1430,14 @@ public:
 				else if (light) PGQ_TRY(next_phase()); // (leaves nq_now at 0 when no heavier edge can matter)
 				if (nq_now == 0) break;
 			}
-			finish_batch();
+			PGQ_TRY(finish_batch());
 		}
 		return settle<T, DT>(1);
 	}
 private:
 	const u32 U;
 	const bool light;
+	const SettledBatch *const settled; // null: the rows' costs (k_cheapest_results)
 	RelaxSide &sd = priv->relax[0];
 	RelaxCounters *d_rc = nullptr, *const h_rc = reinterpret_cast<RelaxCounters *>(priv->h_cnt); // priv's counter block, its pinned copy
 	u32 epoch = 0; // queue-flag stamp of the device-side small rounds
@@ -1475,8 +1499,9 @@ private:
 		const RelaxRound<T> rr { priv, 0, par, c->off, light ? c->wadj : c->adj, light ? (const T *)c->wsorted : (const T *)c->w, tepoch, d_rc,
 		                         thr_bits, light ? 1 : 0, wcap, heavy };
 		KernelTimer kt(st, K_RELAX);
-		hipLaunchKernelGGL(k_lane_bounds<DT>, dim3((unsigned)std::min<int64_t>(blocks_for(hi - lo), 256)), dim3(256), 0, st, lo, hi,
-		                   ws->skey.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_rc->bound);
+		if (settled) hipLaunchKernelGGL(k_lane_unbound, dim3(1), dim3(64), 0, st, d_rc->bound);
+		else hipLaunchKernelGGL(k_lane_bounds<DT>, dim3((unsigned)std::min<int64_t>(blocks_for(hi - lo), 256)), dim3(256), 0, st, lo, hi,
+		                        ws->skey.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_rc->bound);
 		launch_relax<T, DT>(rr, 0, grid, nq_now);
 		if (heavy) launch_relax<T, DT>(rr, 1, grid, nq_now); // the long lists of the round, a chunk per wavefront
 		kt.stop();
@@ -1519,10 +1544,12 @@ private:
 		if (h_rc->relaxed_vertices == 0 && h_rc->min_deferred != 0x7F7F7F7F7F7F7F7Fll)
 			thr_val = std::max(thr_val, __builtin_bit_cast(T, h_rc->min_deferred) + band);
 	}
-	void finish_batch() {
-		hipLaunchKernelGGL(k_cheapest_results<DT>, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(),
-		                   ws->sidx.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_out, d_ok);
+	int finish_batch() {
+		if (settled) PGQ_TRY(settled->then(lo, hi, base));
+		else hipLaunchKernelGGL(k_cheapest_results<DT>, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(),
+		                        ws->sidx.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_out, d_ok);
 		end_batch<T, DT>(h_rc->relaxed_edges, 1, d_rc);
+		return PGQ_OK;
 	}
 };
 
@@ -2095,6 +2122,8 @@ static int check_weighted(pgq_csr_t *csr) {
 }
 
 } // namespace pgq
+
+#include "pgq_cheapest_path.hip" // cheapest_path: the list next to the cost, on this file's relaxation state and k_relax launches
 
 using namespace pgq;
 

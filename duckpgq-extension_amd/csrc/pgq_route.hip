@@ -462,6 +462,9 @@ using namespace pgq;
 
 // per-thread arena for list payloads returned by the chunk API
 static thread_local std::vector<int64_t> t_child;
+namespace pgq {
+std::vector<int64_t> &thread_child_arena() { return t_child; }
+} // namespace pgq
 
 // body(k, lo, hi, replica, ws): shard k = rows [lo, hi) on device k's replica, called on a thread bound to that device
 template <typename Body>

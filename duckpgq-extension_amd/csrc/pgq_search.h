@@ -312,6 +312,11 @@ struct Workspace {
 	RelaxSide relax[2];    // cheapest path: the forward (0) and the backward (1, BidirBatches) search state; the hop-bounded rounds
 	                       // (HopBatches) keep their snapshot rows and masks in [1]'s label and first dirty array and leave its dist_V at -1
 	void *h_bi = nullptr;  // pinned: the bidirectional relaxation's counter block, copied back once per round
+	// cheapest_path (pgq_cheapest_path.hip): tight hop counts H[V][64] (-1 = none; a batch resets what it set, tight_V says for
+	// which V that holds), the frontier of a tight-level round (lane masks and vertex queues by round parity), its counters, the
+	// lists of the finished batches in batch order
+	DevBuf tight_h, tight_mask[2], tight_q[2], tight_cnt, tight_stage;
+	int64_t tight_V = -1;
 	~Workspace();
 };
 
@@ -463,6 +468,8 @@ struct SearchCall {
 };
 // every wait of the lane-batched search on its stream is counted (pgq_stats_t::host_waits)
 #define PGQ_WAIT(stream) do { PGQ_TRY(wait_stream(stream, thread_wait_event())); tstats().s.host_waits++; } while (0)
+// This host thread's arena for the list payloads the chunk entry points hand out (pgq_route.hip; pgq_thread_release drops it).
+std::vector<int64_t> &thread_child_arena();
 // A bigger buffer with the first `keep` bytes of the old one (waited for).
 int grow_keeping(DevBuf &buf, size_t bytes, size_t keep, hipStream_t st);
 // Answers the call's rows by whichever route pays: the per-row bidirectional search, the source-centric kernel, the

@@ -196,6 +196,43 @@ void CheapestPathLengthWithinFunction(DataChunk &args, ExpressionState &state, V
 	CheapestPathLength(args, state, result, &upper);
 }
 
+// cheapest_path(csr_id, V, src, dst) -> LIST(BIGINT): the cheapest path itself, [src, e1, v1, ..., ek, dst], bound like
+// cheapest_path_length (CheapestPathLengthFunctionData; registered beside it with a LIST(BIGINT) return type).  The reference has no
+// such function: a MATCH over a weighted edge table gets vertices(p) / edges(p) of its cheapest path from this list the way it gets
+// them from shortestpath's.  There is no five-argument overload (the cheapest walk of at most `upper` edges needs per-round parents).
+void CheapestPathFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	auto &info = state.expr.Cast<BoundFunctionExpression>().BindInfo()->Cast<CheapestPathLengthFunctionData>();
+	auto duckpgq_state = GetDuckPGQState(info.context);
+	auto entry = duckpgq_state->csr_list.find(info.csr_id);
+	if (entry == duckpgq_state->csr_list.end()) throw ConstraintException("CSR not found with ID " + std::to_string(info.csr_id));
+	CSR &csr = *entry->second;
+	if (!(csr.initialized_v && csr.initialized_e && csr.initialized_w))
+		throw ConstraintException("Need to initialize CSR before doing cheapest path");
+	UnifiedVectorFormat vsize_fmt, src, dst;
+	args.data[1].ToUnifiedFormat(args.size(), vsize_fmt);
+	const int64_t v_size = reinterpret_cast<const int64_t *>(vsize_fmt.data)[0];
+	args.data[2].ToUnifiedFormat(args.size(), src);
+	args.data[3].ToUnifiedFormat(args.size(), dst);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto entries = FlatVector::GetDataMutable<list_entry_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	const int64_t *child = nullptr; // owned by the library until this thread's next list-returning call
+	uint64_t child_len = 0;
+	vector<uint64_t> offsets(args.size()), lengths(args.size());
+	if (pgq_cheapest_path(DeviceCSR(*duckpgq_state, csr, v_size), v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), offsets.data(),
+	                      lengths.data(), validity.GetData(), &child, &child_len) != PGQ_OK)
+		ThrowDevice();
+	ListVector::Reserve(result, child_len);
+	if (child_len) memcpy(FlatVector::GetDataMutable<int64_t>(ListVector::GetEntry(result)), child, child_len * sizeof(int64_t));
+	ListVector::SetListSize(result, child_len);
+	for (idx_t i = 0; i < args.size(); i++) { // NULL rows keep {0, 0}
+		entries[i].offset = offsets[i];
+		entries[i].length = lengths[i];
+	}
+	duckpgq_state->csr_to_delete.insert(info.csr_id);
+}
+
 void LocalClusteringCoefficientFunction(DataChunk &args, ExpressionState &state, Vector &result) {
 	auto &info = state.expr.Cast<BoundFunctionExpression>().BindInfo()->Cast<LocalClusteringCoefficientFunctionData>();
 	auto duckpgq_state = GetDuckPGQState(info.context);

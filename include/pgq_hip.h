@@ -208,6 +208,26 @@ int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 int pgq_cheapest_path_length_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, void *out,
                                     uint64_t *out_valid);
 
+/* cheapest_path(csr_id, V, src, dst) -> LIST(BIGINT) [src, e1, v1, ..., ek, dst]: the cheapest path itself, next to the cost
+ * pgq_cheapest_path_length returns (the reference has no counterpart: its Bellman-Ford keeps no parents).  With D[v] the labels
+ * pgq_cheapest_path_length defines (the least fixpoint of dist[n] = min(dist[n], dist[v] + w) from dist[src] = 0, INF = max(T) / 2,
+ * the reference's arithmetic for int64 and for double):
+ *   - a slot s of u's out-list with adj[s] = x is TIGHT when D[u] < INF and D[u] + w[s] == D[x], computed as the relaxation
+ *     computes it; NaN and +inf weights are never tight;
+ *   - H[src] = 0 and H[x] = 1 + min H[u] over the tight slots (u, x): the BFS levels of the tight subgraph;
+ *   - for a row with D[dst] < INF and k = H[dst]: x_k = dst, and for i = k .. 1, x_{i-1} = the smallest u with H[u] = i - 1 that
+ *     has a tight slot into x_i (shortestpath's min-parent rule), e_i = edge_ids[the first tight slot of that u into x_i]
+ *     (shortestpath's first-slot rule among the tight slots); the list is [x_0, e_1, x_1, ..., e_k, x_k].
+ * The path is hop-minimal among the cheapest ones, so zero-weight cycles and absorbed double edges (2^53 + 1.0 == 2^53) cannot
+ * make it loop.  The left-to-right fold of the weights of e_1 .. e_k is pgq_cheapest_path_length's result, bit for bit; when every
+ * weight is the same positive int64 the list is pgq_shortestpath's.  src == dst -> [src]; NULL src, NULL dst or unreachable ->
+ * NULL (validity clear, entry {0,0}, no payload).  Signature and thread-local child arena as pgq_shortestpath (the arena is the
+ * same one: valid until the next list-returning call on the thread).  An unweighted CSR, negative weights and ids out of range fail
+ * as in pgq_cheapest_path_length.  There is no hop-bounded form (that needs per-round parents), no _multi form, and the two-ended
+ * search is not used. */
+int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
+                      uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len);
+
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
  * freed CSR / upload blocks kept for the next upload (PGQ_ALLOC_CACHE_MB). */
@@ -271,6 +291,12 @@ int pgq_cheapest_path_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_
  * cheapest walk of at most max_hops edges (NOT the unbounded cost with far rows NULL: see pgq_cheapest_path_length_within). */
 int pgq_cheapest_path_length_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
                                                 void *d_out, uint8_t *d_out_valid);
+/* pgq_cheapest_path without the chunk ceiling: d_out_len[i] = hops of the cheapest path (its tight hop count H[dst]), 0 for
+ * src == dst, -1 for NULL rows (d_src[i] < 0) and unreachable rows; lists and child-capacity protocol as
+ * pgq_shortestpath_bulk_device: entry i at d_out_offset[i] with 2 * len + 1 elements, *child_used = the elements needed,
+ * PGQ_ERR_INVALID_ARG when child_cap is too small (d_out_len is complete, the payload is not usable). */
+int pgq_cheapest_path_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
+                                  int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

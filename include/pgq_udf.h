@@ -18,6 +18,7 @@
  *   pgq_udf_bind_cheapest           CheapestPathLengthBind       src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
+ *   pgq_udf_cheapest_path           (no counterpart) the cheapest path as a list; bound like cheapest_path_length
  *   pgq_udf_delete_csr              DeleteCsrFunction            src/core/functions/scalar/csr_deletion.cpp:10-20
  *   pgq_udf_csr_get_w_type          GetCsrWTypeFunction          src/core/functions/scalar/csr_get_w_type.cpp:16-36
  *   pgq_udf_reachability            ReachabilityFunction         src/core/functions/scalar/reachability.cpp:165-254 (intended semantics)
@@ -82,6 +83,11 @@ int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n
  * PGQ_ERR_INVALID_ARG */
 int pgq_udf_cheapest_path_length_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
                                         void *out, uint64_t *out_valid);
+/* cheapest_path(id, V, src, dst) -> LIST(BIGINT): the cheapest path itself, [src, e1, v1, ..., ek, dst] (pgq_cheapest_path: the
+ * hop-minimal cheapest path under shortestpath's tie-breaks); bound through pgq_udf_bind_cheapest, outputs as
+ * pgq_udf_shortestpath, errors as for pgq_udf_cheapest_path_length.  The reference has no such function. */
+int pgq_udf_cheapest_path(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
+                          uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len);
 /* reachability(id, is_variant, V, src, dst) -> BOOL; the reference's BOOL argument only selects one of its three
  * internal BFS modes (reachability.cpp:154-163) and does not change the result, so it is not part of this call.
  * Boolean reachability with the semantics the reference intends (reachability.cpp:165-254 indexes its inputs
