@@ -160,8 +160,11 @@ struct Options {
 	int lanes = 1;          // sparse bottom-up levels use the lane-list kernel (k_pull_lanes); 0: k_pull_sparse
 	int lanes_unroll = 2;   // 64-entry chunks in flight per wave in k_pull_lanes (1, 2 or 4)
 	int meet_trace = 0;      // debugging: per-workgroup timestamps of k_meet4d, summarised on stderr
-	int meet4_grid_mult = 1; // k_meet4d grid = this many 1024-thread workgroups per CU (2 fit beside their LDS bit maps; rows are handed out
-	                         // dynamically).  Round 5, after stage A / the probe shortened a row: one per CU 42.6 us, two 51.2, three 62.8 per 65,536 rows
+	int meet4_grid_mult = 1; // k_meet4d grid = this many 1024-thread workgroups per CU (rows are handed out dynamically).  Round 5, after stage A /
+	                         // the probe shortened a row: one per CU 42.6 us, two 51.2, three 62.8 per 65,536 rows.  Since round 13 the kernel is
+	                         // compiled for one workgroup per CU (PGQ_MEET4_BLOCKS): the others of a larger grid wait for a free CU
+	int meet4_batch = 1;     // k_meet4d: the rows proven to be at distance >= 4 are taken in batches, one row per wavefront, when more than two
+	                         // of them are queued per workgroup (2: always — tests; 0: one after the other by the whole workgroup, as before round 13)
 	int meet_grid_mult = 8; // k_meet3 grid = this many times the 8192 one-wavefront workgroups the chip holds (rows per workgroup = n / grid)
 	int meet_layout = 1;    // build the padded adjacency + slot descriptors at upload (the pre-pass needs them)
 	int meet_align = 32;    // entries a padded list is aligned and padded to (4 = one 16-byte group; 16 / 32 = whole 64 / 128-byte lines: -4 % / -6 % on the pre-pass)
@@ -188,6 +191,9 @@ struct Options {
 	double ball_bias = 1.0;     // the ball runs while ball_bias x its estimated bytes <= the cheaper of the pre-pass and the lane batches
 };
 Options &options();
+// rows k_meet4d's batch pass has answered in this process (every handle and thread); read-only entry meet4_batch_settled of the
+// option table: only that pass advances it, so a test can tell that it ran
+extern std::atomic<long long> g_meet4_batch_settled;
 // per-handle options (pgq_csr_set_option): the override a host thread works under, and a scope that installs a
 // handle's for the duration of a C-ABI call
 // Host worker threads that outlive a call (one idle list per device: a worker keeps its HIP events and its device

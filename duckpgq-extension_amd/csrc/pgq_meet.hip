@@ -14,7 +14,8 @@
 //     behind a 4-KB two-bit filter in LDS; the other side's one-hop list arrives as slot descriptors and its lists are
 //     walked as one virtual sequence of 16-byte groups (seg_walk, pgq_walk.h), ended by the first pass with a witness;
 //   * k_meet4d / k_meet4 (paths), one 1024-thread workgroup per row k_meet3 leaves open, an exact vertex bit map as the
-//     set: distance <= 4;
+//     set: distance <= 4 (k_meet4d first takes the rows k_meet3 proved to be at distance >= 4 in batches, one row per
+//     wavefront with k_meet3's kind of set: a witness settles 4, no witness sends the row to the whole workgroup);
 //   * k_bibfs, one bidirectional BFS per row for a handful of leftovers;
 //   * every kernel appends the rows it cannot answer to the next one's queue, the last workgroup of the last kernel
 //     reports into pinned host memory: the host launches 2-4 kernels and waits once.
@@ -58,7 +59,11 @@ constexpr int kMeetWPB = 1;         // wavefronts per k_meet3 workgroup: one, so
 #endif
 constexpr int kM4Threads = 64 * PGQ_MEET4_WAVES;
 #ifndef PGQ_MEET4_BLOCKS
-#define PGQ_MEET4_BLOCKS 8 // wavefronts per SIMD k_meet4d is compiled for: 8 = two 1024-thread workgroups per CU (64 VGPRs); at 84 VGPRs only one fits
+#define PGQ_MEET4_BLOCKS 4 // wavefronts per SIMD k_meet4d is compiled for: 4 = ONE 1024-thread workgroup per CU (up to 128 VGPRs), which is what
+                           // every shipped launch runs (meet4_grid_mult = 1, small calls, the global-map grids).  At 8 (64 VGPRs, two per CU) every
+                           // instantiation spilled (24-48 B of scratch per lane, on the path every row takes) for an occupancy no launch used;
+                           // with meet4_grid_mult > 1 the extra workgroups wait for a free CU instead of sharing one (rows are handed out
+                           // dynamically and no workgroup waits for another: only the timing changes)
 #endif
 #ifndef PGQ_MEET4_MARK_DEPTH
 #define PGQ_MEET4_MARK_DEPTH 2 // the marking walk of k_meet4d never stops early: deeper costs nothing but registers
@@ -69,8 +74,16 @@ constexpr int kM4Threads = 64 * PGQ_MEET4_WAVES;
 // (a k_meet4d variant with 8 requests in flight per wavefront for small calls — one workgroup per CU has the registers —
 // measured no better on R-MAT-22's long rows, which wait for L2 atomics, not for loads, and worse on the SF100 graph)
 #ifndef PGQ_MEET4_DEPTH
-#define PGQ_MEET4_DEPTH 2 // the same for each of the 16 wavefronts of a k_meet4d row (more only adds overshoot past the first hit)
+#define PGQ_MEET4_DEPTH 2 // the same for each of the 16 wavefronts of a k_meet4d row (more only adds overshoot past the first hit; round 13,
+                          // with the registers of one workgroup per CU: at 4 the longest row is 7.5-7.9 us against 6.4-7.0, the step the same)
 #endif
+#ifndef PGQ_MEET4_BATCH_DEPTH
+#define PGQ_MEET4_BATCH_DEPTH 2 // list requests in flight per wavefront of k_meet4d's batch pass (one row each).  4: 127 VGPRs and no gain
+                                // (SF100-shaped graph: longest batch 17.5 us against 16.5, step 0.1727 ms against 0.1721)
+#endif
+constexpr int kBatchTestCap = 4096; // k_meet4d's batch pass: entries a wavefront may request of the tested side's two-hop lists before its row goes the long way
+constexpr int kMeet4BatchAlways = 0x100; // ... flag beside the batch size in the kernel's `batch` argument: also when few rows are queued
+constexpr int kMeet4TraceWords = 8; // option meet_trace: 64-bit words per workgroup of k_meet4d
 constexpr u32 kMeetKnown4Bit = 0x80000000u; // in the queued row indices: the row is known to be at distance >= 4
 constexpr int kMeetStatSlots = 256; // statistics are spread over slots: 10^4 atomics on one address take longer than the walks
 struct MeetCounters {
@@ -122,7 +135,8 @@ struct MeetDevBlock { // device side; all zero between calls
 	u32 count[4]; // rows open after stage 1, 2, 3; [3]: stage 1's rows appended from the back of its queue
 	u32 ticket;   // workgroups of the chain's last kernel that are done
 	u32 next_job; // k_meet4d: the next queue position to hand out
-	u32 pad[2];
+	u32 next_batch;    // ... its batch pass: the next back row to hand out (claimed several at a time)
+	u32 batch_settled; // ... and the rows that pass answered
 	MeetDecision dec;
 	BallDev ball;
 };
@@ -134,6 +148,7 @@ struct MeetHostBlock { // pinned host memory, written by the last workgroup of t
 	u32 done, count_back;
 	unsigned long long ball_entries, ball_descs;
 	u32 ball_go, ball_nseg, ball_nrun, ball_open;
+	u32 batch_settled, pad; // rows k_meet4d's batch pass answered (read-only option meet4_batch_settled)
 };
 static_assert(sizeof(MeetHostBlock) <= sizeof(MeetPinned::report), "pinned statistics block too small");
 __device__ __forceinline__ void queue_push(const MeetQueue &q, u32 row, const MeetEntry &e) { // one lane
@@ -219,6 +234,9 @@ __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *f
 		db->count[3] = 0;
 		db->ticket = 0;
 		db->next_job = 0;
+		fin->batch_settled = __hip_atomic_load(&db->batch_settled, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		db->next_batch = 0;
+		db->batch_settled = 0;
 		db->dec.go = 0;
 		__threadfence_system();
 		fin->done = 1;
@@ -995,7 +1013,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
                                                  const int32_t *__restrict__ padj, const int32_t *__restrict__ rpadj,
                                                  int64_t *__restrict__ out_rows, int64_t cap, int64_t test_cap, int bm_words,
                                                  MeetDevBlock *__restrict__ db, u32 *__restrict__ gmaps, MeetQueue qout,
-                                                 MeetHostBlock *__restrict__ fin, unsigned long long *__restrict__ trace, SampleArgs sm, int bound) {
+                                                 MeetHostBlock *__restrict__ fin, unsigned long long *__restrict__ trace, SampleArgs sm, int bound, int batch) {
 	extern __shared__ __attribute__((aligned(16))) u32 s_map[]; // bm_words: one bit per vertex (GM: the map is this workgroup's slice of `gmaps`)
 	// rows the stage before left open (counted on the device: no host round trip): nf from the front of its queue (the
 	// long ones), the rest from the back
@@ -1085,12 +1103,124 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 	// takes the sample in the bit map's LDS before its first row clears it
 	if (!GM && sm.h_go && blockIdx.x == gridDim.x - 1 && bm_words >= kSampleSlots && !db->ball.go)
 		sample_distinct_sources(sm.n, sm.src, sm.V, sm.meet_bytes, sm.edge_bytes, sm.out, sm.h_go, s_map);
-	u32 job = blockIdx.x;
+	//
+	// Round 13, the batch pass (option meet4_batch): the rows at the BACK of the queue — distance >= 4 proven, ~95 % of what
+	// arrives — are taken `bs` at a time, one row per WAVEFRONT, all of them in flight at once, instead of one after the
+	// other with 16 wavefronts each running the whole round bookkeeping for one request.  A wavefront keeps the first <= 512
+	// entries of the cheaper endpoint's two-hop walk as k_meet3 keeps its set (RegSet behind the 4-KB two-bit filter,
+	// pgq_walk.h; the filters lie in the bit map's LDS, which is idle during a batch) and walks up to kBatchTestCap entries
+	// of the other endpoint's two-hop lists against it.  A verified witness lies in both two-hop neighbourhoods: with
+	// distance >= 4 proven the row is 4.  No witness proves nothing: the row goes into s_miss and through the whole-workgroup
+	// procedure below, unchanged, in the same launch.  The front rows (cut walks, long lists) keep that procedure too: the
+	// row loop draws them first (jobs < n_whole), then batches (claimed from db->next_batch), then each batch's misses.
+	// When it pays: a row alone in a wavefront takes ~16 us (SF100-shaped graph, longest batch of the trace), the whole workgroup
+	// ~7 us per row, so a workgroup with one or two back rows to its name is faster the old way — chunk-sized calls, whose
+	// handful of open rows find a workgroup each (24 rows on 64 workgroups: 9 us per launch, 13 with a wavefront per row).  The
+	// pass runs when the queue holds more than two back rows per workgroup; kMeet4BatchAlways (option meet4_batch = 2): always.
+	const u32 batch_fit = (!GM && (!BND || bound >= 4)) ? (u32)min(batch & 0xFF, PGQ_MEET4_WAVES) : 0u; // the host: min(16, map bytes / 4096), 0 = off
+	const u32 n_back = n - nf;
+	const u32 batch_max = ((batch & kMeet4BatchAlways) || n_back > 2u * gridDim.x) ? batch_fit : 0u; // every workgroup computes the same
+	const u32 nb = batch_max ? n_back : 0u, n_whole = batch_max ? nf : n; // back rows for the batches; jobs of the row loop
+	const u32 bs = max(1u, min(batch_max, (nb + gridDim.x - 1u) / gridDim.x)); // every workgroup computes the same: the free ones share the back rows
+	__shared__ u32 s_miss[PGQ_MEET4_WAVES];
+	__shared__ u32 s_nmiss;
+	unsigned long long n_batch_rows = 0, n_batch_miss = 0, t_batch_max = 0; // workgroup-uniform
+	// one wavefront, one proven-far row (queue job `bjob`); true: settled (distance 4 written)
+	auto batch_row = [&](u32 bjob) {
+		const uint4 *ep = reinterpret_cast<const uint4 *>(qin.ent + queue_pos(qin, bjob, nf));
+		const uint4 e0 = ep[0], e1 = ep[1], e2w = ep[2];
+		const u32 workS = (u32)__builtin_amdgcn_readfirstlane((int)e2w.x), workD = (u32)__builtin_amdgcn_readfirstlane((int)e2w.y);
+		const u32 row = (u32)__builtin_amdgcn_readfirstlane((int)e0.x), flags = (u32)__builtin_amdgcn_readfirstlane((int)e0.y);
+		const int so = __builtin_amdgcn_readfirstlane((int)e1.x), degS = __builtin_amdgcn_readfirstlane((int)e1.y);
+		const int di = __builtin_amdgcn_readfirstlane((int)e1.z), degD = __builtin_amdgcn_readfirstlane((int)e1.w);
+		if (!(flags & kEntKnown4) || degS <= 0 || degD <= 0) return false; // (only proven rows are queued from the back; an empty list: the full procedure says what that means)
+		const bool fwd = workS <= workD; // the set side: the endpoint with the smaller two-hop walk, as below
+		const uint4 *set_list = fwd ? fdesc + so : rdesc + di, *test_list = fwd ? rdesc + di : fdesc + so;
+		const int set_n = fwd ? degS : degD, test_n = fwd ? degD : degS;
+		uint4 d_set = make_uint4(0, 0, 0, 0), d_test = make_uint4(0, 0, 0, 0); // both endpoints' first descriptors in one round trip
+		if (lane < set_n) d_set = set_list[lane];
+		if (lane < test_n) d_test = test_list[lane];
+		u32 *flt = s_map + (size_t)wib * kFltWords;
+#pragma unroll
+		for (int k = 0; k < kFltWords / 256; k++) reinterpret_cast<uint4_alias *>(flt)[k * 64 + lane] = make_uint4(0, 0, 0, 0);
+		// the set: what this lane held in the first two requests (selects, not an indexed array: that would live in scratch)
+		const int4 none = make_int4((int)kMeetEmpty, (int)kMeetEmpty, (int)kMeetEmpty, (int)kMeetEmpty);
+		int4 set0 = none, set1 = none;
+		int got = 0; // requests collected (wave-uniform)
+		bool capped = false;
+		int resume = 0;
+		unsigned long long e2 = seg_walk<2, false>(
+		    set_list, set_n, 0, 1, fwd ? padj : rpadj, win, true, d_set, (unsigned long long)kSetRegMax - 1ull, capped, resume,
+		    [&](const int4 &v, bool ok, u32) {
+			    const bool k0 = ok && got == 0, k1 = ok && got == 1;
+			    set0 = make_int4(k0 ? v.x : set0.x, k0 ? v.y : set0.y, k0 ? v.z : set0.z, k0 ? v.w : set0.w);
+			    set1 = make_int4(k1 ? v.x : set1.x, k1 ? v.y : set1.y, k1 ? v.z : set1.z, k1 ? v.w : set1.w);
+			    got++;
+		    },
+		    [&]() { return got >= kSetRegs / 4; });
+		// descriptors: a walk that stopped had entered the rounds up to `resume`'s and requested one ahead
+		u32 descs = (u32)((got >= kSetRegs / 4 || capped) ? min(set_n, resume + 128) : set_n);
+		RegSet R; // (regset_has asks every lane and register: which lane holds which entry does not matter)
+		R.r[0] = (u32)set0.x, R.r[1] = (u32)set0.y, R.r[2] = (u32)set0.z, R.r[3] = (u32)set0.w;
+		R.r[4] = (u32)set1.x, R.r[5] = (u32)set1.y, R.r[6] = (u32)set1.z, R.r[7] = (u32)set1.w;
+		R.rounds = kSetRegs;
+		__builtin_amdgcn_wave_barrier();
+#pragma unroll
+		for (int k = 0; k < kSetRegs; k++)
+			if (R.r[k] != kMeetEmpty) atomicOr(&flt[flt_word(R.r[k])], flt_mask<true>(R.r[k]));
+		__builtin_amdgcn_wave_barrier();
+		bool found = false; // wave-uniform
+		capped = false;
+		resume = 0;
+		e2 += seg_walk<PGQ_MEET4_BATCH_DEPTH, false>(
+		    test_list, test_n, 0, 1, fwd ? rpadj : padj, win, true, d_test, (unsigned long long)kBatchTestCap, capped, resume,
+		    [&](const int4 &v, bool, u32) {
+			    // (a lane past the round's end re-reads real entries of the last list: no mask needed for membership)
+			    verify_candidates(R, flt_pass<true>(flt, v), v, [&](u32, int) {
+				    found = true;
+				    return true;
+			    });
+		    },
+		    [&]() { return found; });
+		descs += (u32)((found || capped) ? min(test_n, resume + 128) : test_n);
+		entries += e2;
+		vertices += descs;
+		if (found && lane == 0) out_rows[row] = 4;
+		return found;
+	};
+	u32 job = blockIdx.x, miss_k = 0, miss_n = 0;
+	bool front = true; // jobs of the row loop may be left
 	for (;;) {
 		__syncthreads(); // the previous row's flags, map and s_job are no longer read
-		if (job >= n) break;
+		const bool from_miss = miss_k < miss_n;
+		if (!from_miss && !(front && job < n_whole)) {
+			front = false;
+			if (nb == 0) break;
+			// ---- one batch: every wavefront reaches both barriers, with or without a row ----
+			const unsigned long long t_b = TRACE ? wall_clock64() : 0ull;
+			if (tid == 0) {
+				s_job = atomicAdd(&db->next_batch, bs);
+				s_nmiss = 0;
+			}
+			__syncthreads(); // before the batch: the map's LDS becomes the wavefronts' filters
+			const u32 b0 = s_job;
+			if (b0 >= nb) break;
+			const u32 cnt = min(bs, nb - b0);
+			if ((u32)wib < cnt) {
+				const u32 bjob = nf + b0 + (u32)wib;
+				if (!batch_row(bjob) && lane == 0) s_miss[atomicAdd(&s_nmiss, 1u)] = bjob;
+			}
+			__syncthreads(); // after the batch: the LDS is the workgroup's map again, s_miss is complete
+			miss_k = 0;
+			miss_n = s_nmiss;
+			n_batch_rows += cnt;
+			n_batch_miss += miss_n;
+			if constexpr (TRACE) t_batch_max = max(t_batch_max, wall_clock64() - t_b);
+			continue;
+		}
 		u32 next_job = 0;
-		if (tid == 0) next_job = gridDim.x + atomicAdd(&db->next_job, 1u);
+		if (from_miss) job = s_miss[miss_k++];
+		else if (tid == 0) next_job = gridDim.x + atomicAdd(&db->next_job, 1u);
 		const unsigned long long t_row = TRACE ? wall_clock64() : 0ull;
 		// the row's queue entry: everything the stage before knew about it, in three 16-byte loads (the queue is a few
 		// tens of KB written moments ago), wave-uniform -> scalar registers
@@ -1281,29 +1411,36 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 				const MeetEntry e = { row, 0u, es, ed, (u32)so, (u32)degS, (u32)di, (u32)degD, workS, workD, 0u, 0u };
 				queue_push(qout, row, e);
 			}
-			s_job = next_job;
+			if (!from_miss) s_job = next_job;
 		}
 		if constexpr (TRACE) {
 			t_row_max = max(t_row_max, wall_clock64() - t_row);
 			n_rows_done++;
 		}
+		if (from_miss) continue; // (the barrier at the top of the loop)
 		__syncthreads();
 		job = s_job;
 	}
 	if (TRACE && tid == 0) {
-		trace[4 * blockIdx.x] = t_begin;
-		trace[4 * blockIdx.x + 1] = wall_clock64();
-		trace[4 * blockIdx.x + 2] = n_rows_done;
-		trace[4 * blockIdx.x + 3] = t_row_max;
+		trace[kMeet4TraceWords * blockIdx.x] = t_begin;
+		trace[kMeet4TraceWords * blockIdx.x + 1] = wall_clock64();
+		trace[kMeet4TraceWords * blockIdx.x + 2] = n_rows_done;
+		trace[kMeet4TraceWords * blockIdx.x + 3] = t_row_max;
+		trace[kMeet4TraceWords * blockIdx.x + 4] = n_batch_rows;
+		trace[kMeet4TraceWords * blockIdx.x + 5] = n_batch_miss;
+		trace[kMeet4TraceWords * blockIdx.x + 6] = t_batch_max;
 	}
 	__shared__ unsigned long long s_stat[2];
 	__syncthreads();
 	if (tid < 2) s_stat[tid] = 0;
 	__syncthreads();
 	if (lane == 0 && entries) atomicAdd(&s_stat[0], entries);
-	if (tid == 0 && vertices) atomicAdd(&s_stat[1], (unsigned long long)vertices);
+	if (lane == 0 && vertices) atomicAdd(&s_stat[1], (unsigned long long)vertices); // (whole-workgroup rows: wavefront 0 counted)
 	__syncthreads();
-	if (tid == 0) meet_add_stats(&db->m, 1, s_stat[0], s_stat[1]);
+	if (tid == 0) {
+		meet_add_stats(&db->m, 1, s_stat[0], s_stat[1]);
+		if (n_batch_rows > n_batch_miss) atomicAdd(&db->batch_settled, (u32)(n_batch_rows - n_batch_miss));
+	}
 	meet_finalize(db, fin);
 }
 
@@ -1740,24 +1877,31 @@ static int print_ball_trace(const unsigned long long *b_trace, u32 nseg, u32 ope
 }
 
 // debugging aid (option meet_trace): where k_meet4d's time goes
-static int print_meet4d_trace(const unsigned long long *d_trace, u32 grid4, u32 long_first) {
-	std::vector<unsigned long long> t((size_t)grid4 * 4);
+static int print_meet4d_trace(const unsigned long long *d_trace, u32 grid4, u32 long_first, u32 back) {
+	constexpr int W = kMeet4TraceWords;
+	std::vector<unsigned long long> t((size_t)grid4 * W);
 	PGQ_HIP_TRY(hipMemcpy(t.data(), d_trace, t.size() * 8, hipMemcpyDeviceToHost));
 	unsigned long long t0 = ~0ull, t1 = 0, rows = 0, longest = 0, first_end = ~0ull, last_start = 0, most = 0;
+	unsigned long long b_rows = 0, b_miss = 0, b_most = 0, b_longest = 0;
 	for (u32 b = 0; b < grid4; b++) {
-		if (!t[4 * b + 1]) continue;
-		t0 = std::min(t0, t[4 * b]);
-		t1 = std::max(t1, t[4 * b + 1]);
-		first_end = std::min(first_end, t[4 * b + 1]);
-		last_start = std::max(last_start, t[4 * b]);
-		rows += t[4 * b + 2];
-		most = std::max(most, t[4 * b + 2]);
-		longest = std::max(longest, t[4 * b + 3]);
+		if (!t[W * b + 1]) continue;
+		t0 = std::min(t0, t[W * b]);
+		t1 = std::max(t1, t[W * b + 1]);
+		first_end = std::min(first_end, t[W * b + 1]);
+		last_start = std::max(last_start, t[W * b]);
+		rows += t[W * b + 2];
+		most = std::max(most, t[W * b + 2]);
+		longest = std::max(longest, t[W * b + 3]);
+		b_rows += t[W * b + 4];
+		b_miss += t[W * b + 5];
+		b_most = std::max(b_most, t[W * b + 4]);
+		b_longest = std::max(b_longest, t[W * b + 6]);
 	}
-	fprintf(stderr, "[pgq] k_meet4d trace: %u workgroups, %llu rows (%u long first), at most %llu per workgroup, span %.1f us, last start +%.1f us, "
-	        "first end +%.1f us, longest row %.1f us\n",
-	        grid4, rows, long_first, most, (double)(t1 - t0) * 0.01, (double)(last_start - t0) * 0.01, (double)(first_end - t0) * 0.01,
-	        (double)longest * 0.01);
+	// rows: taken by a whole workgroup (the front rows, the batch pass's misses, every row when that pass is off)
+	fprintf(stderr, "[pgq] k_meet4d trace: %u workgroups, queue %u front + %u back, %llu whole-workgroup rows, at most %llu per workgroup, span %.1f us, "
+	        "last start +%.1f us, first end +%.1f us, longest row %.1f us; batch pass: %llu rows (%llu missed), at most %llu per workgroup, longest batch %.1f us\n",
+	        grid4, long_first, back, rows, most, (double)(t1 - t0) * 0.01, (double)(last_start - t0) * 0.01, (double)(first_end - t0) * 0.01,
+	        (double)longest * 0.01, b_rows, b_miss, b_most, (double)b_longest * 0.01);
 	return PGQ_OK;
 }
 
@@ -1853,10 +1997,11 @@ private:
 	const int last_stage = run_bi ? 2 : (run4 ? 1 : 0);
 	const int bibfs_rows = opt.bibfs_rows <= 0 ? 0 : std::max(opt.bibfs_rows, (int)std::min<int64_t>(opt.bibfs_rows_max, c->E / 4096));
 	const int qcap = std::max(1024, opt.bibfs_queue);
-	// k_meet4d hands rows out dynamically: a grid of exactly the workgroups the chip holds (meet4_grid_mult = 2 per CU).
-	// A row alone on its CU is through in ~15 us, beside a second one in ~20 (the phases of a row are short bursts of
-	// instructions from 16 wavefronts, and two workgroups share the CU's issue slots): small calls, whose ~2 % of open rows
-	// do not fill 256 CUs anyway, get one workgroup per CU (8192 rows: 0.086 -> 0.076 ms, 2048 rows: 0.062 -> 0.053 ms)
+	// k_meet4d hands rows out dynamically: a grid of meet4_grid_mult workgroups per CU (shipped: 1; until round 5: 2, when a row
+	// alone on its CU was through in ~15 us and beside a second one in ~20).  Since round 13 the kernel is compiled for ONE
+	// workgroup per CU (PGQ_MEET4_BLOCKS = 4: no launch that ships used the second slot, and at its 64 VGPRs every
+	// instantiation spilled): the workgroups of a larger grid take a CU as one frees up.  Small calls, whose ~2 % of open rows
+	// do not fill 256 CUs anyway, get at most one workgroup per CU whatever the option says
 	const bool small_call = !paths && n <= (int64_t)opt.meet_small_rows;
 
 	// settled by plan()
@@ -1948,9 +2093,9 @@ private:
 		meet_attributes();
 		if (run4 && !paths) q[0].count_back = &db->count[3]; // k_meet3 -> k_meet4d: long rows from the front, the others from the back
 		if (opt.meet_trace && run4 && !paths && !bnd) { // (the bounded kernels carry no trace)
-			PGQ_TRY(ws->meet_trace.reserve((size_t)grid4 * 32));
+			PGQ_TRY(ws->meet_trace.reserve((size_t)grid4 * kMeet4TraceWords * 8));
 			d_trace = ws->meet_trace.as<unsigned long long>();
-			PGQ_HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)grid4 * 32, st));
+			PGQ_HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)grid4 * kMeet4TraceWords * 8, st));
 		}
 		// shortestpath on a large input: if the decision kernel calls the pre-pass off, nothing writes a.d_out — the list layout
 		// (emit_paths) must then see "no list" everywhere (-1 in every row), not what the buffer happened to hold
@@ -2106,6 +2251,9 @@ private:
 		const size_t lds = mp.lds_map ? mp.map_bytes() : 0;
 		const int64_t cap4 = (int64_t)std::max(1, opt.meet4_cap);
 		MeetHostBlock *fin = last_stage == 1 ? hb : nullptr;
+		// k_meet4d's batch pass: one 4-KB filter per wavefront inside the LDS map (a map under 4 KB, or in global memory: no pass)
+		const int batch_fit = (mp.lds_map && opt.meet4_batch > 0) ? (int)std::min<size_t>(PGQ_MEET4_WAVES, mp.map_bytes() / (kFltWords * 4)) : 0;
+		const int batch = batch_fit | ((batch_fit && opt.meet4_batch >= 2) ? kMeet4BatchAlways : 0);
 		KernelTimer kt(st, K_MEET4);
 		if (mp.lds_map) S.lds_map_launches[K_MEET4]++;
 		clear_launch_error();
@@ -2117,7 +2265,7 @@ private:
 #define PGQ_MEET4D(G, T) PGQ_MEET4DB(G, T, false)
 #define PGQ_MEET4DB(G, T, BN)                                                                                               \
 	hipLaunchKernelGGL((k_meet4d<G, T, BN>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
-	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride, bound)
+	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride, bound, batch)
 		if (paths && bnd && mp.lds_map) PGQ_MEET4(false, true);
 		else if (paths && bnd) PGQ_MEET4(true, true);
 		else if (paths && mp.lds_map) PGQ_MEET4(false, false);
@@ -2168,7 +2316,8 @@ private:
 		if (decide_mode == DecideMode::Ride && ws->h_meet->sample_go) r->observed_go = (int)ws->h_meet->sample_go - 1;
 		if (paths) a.po->total = ws->h_meet->paths_total;
 		const MeetHostBlock &h = *hb;
-		if (d_trace) PGQ_TRY(print_meet4d_trace(d_trace, grid4, h.count[0]));
+		if (d_trace) PGQ_TRY(print_meet4d_trace(d_trace, grid4, h.count[0], h.count_back));
+		if (h.batch_settled) g_meet4_batch_settled.fetch_add((long long)h.batch_settled, std::memory_order_relaxed);
 		if (ball_mode && h.ball_go) return ball_took(h);
 		if (ball_mode) // it looked at the rows (8 B per row, twice) and declined
 			S.algo_bytes[K_BALL] += 16.0 * (double)n;

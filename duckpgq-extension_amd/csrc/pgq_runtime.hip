@@ -250,7 +250,9 @@ struct OptRef {
 	const char *name;
 	int *i;
 	double *d;
+	const std::atomic<long long> *counter = nullptr; // a counter the library keeps: pgq_get_option reads it, nothing sets it
 };
+std::atomic<long long> g_meet4_batch_settled { 0 };
 static std::vector<OptRef> option_table(Options &o) {
 	return {
 		{ "words", &o.words, nullptr },
@@ -335,6 +337,8 @@ static std::vector<OptRef> option_table(Options &o) {
 		{ "upload_narrow_host", &o.upload_narrow_host, nullptr },
 		{ "meet_grid_mult", &o.meet_grid_mult, nullptr },
 		{ "meet4_grid_mult", &o.meet4_grid_mult, nullptr },
+		{ "meet4_batch", &o.meet4_batch, nullptr },
+		{ "meet4_batch_settled", nullptr, nullptr, &g_meet4_batch_settled },
 		{ "meet_trace", &o.meet_trace, nullptr },
 		{ "meet_layout", &o.meet_layout, nullptr },
 		{ "meet_align", &o.meet_align, nullptr },
@@ -389,6 +393,7 @@ static int do_init(int device) {
 	if (g_devices.empty()) g_devices.push_back(device);
 	// every option of the table can be preset from the environment: PGQ_<NAME IN CAPITALS>
 	for (const OptRef &r : option_table(g_opt)) {
+		if (r.counter) continue;
 		std::string name = "PGQ_";
 		for (const char *q = r.name; *q; q++) name += (char)toupper((unsigned char)*q);
 		if (r.i) env_int(name.c_str(), *r.i);
@@ -2098,6 +2103,7 @@ static int set_option_in(Options &o, const char *key, const char *value) {
 	if (!key || !value) return fail(PGQ_ERR_INVALID_ARG, "NULL option");
 	for (const OptRef &r : option_table(o)) {
 		if (strcmp(r.name, key) != 0) continue;
+		if (r.counter) return fail(PGQ_ERR_INVALID_ARG, std::string("read-only option: ") + key);
 		if (r.i) *r.i = atoi(value);
 		else *r.d = atof(value);
 		return PGQ_OK;
@@ -2108,7 +2114,7 @@ static int get_option_in(Options &o, const char *key, double *value) {
 	if (!key || !value) return fail(PGQ_ERR_INVALID_ARG, "NULL option");
 	for (const OptRef &r : option_table(o)) {
 		if (strcmp(r.name, key) != 0) continue;
-		*value = r.i ? (double)*r.i : *r.d;
+		*value = r.counter ? (double)r.counter->load() : (r.i ? (double)*r.i : *r.d);
 		return PGQ_OK;
 	}
 	return fail(PGQ_ERR_INVALID_ARG, std::string("unknown option: ") + key);
