@@ -166,6 +166,9 @@ struct Options {
 	int meet4_batch = 1;     // k_meet4d: the rows proven to be at distance >= 4 are taken in batches, one row per wavefront, when more than two
 	                         // of them are queued per workgroup (2: always — tests; 0: one after the other by the whole workgroup, as before round 13)
 	int meet_grid_mult = 8; // k_meet3 grid = this many times the 8192 one-wavefront workgroups the chip holds (rows per workgroup = n / grid)
+	int meet_rows_per_wave = 4; // k_meet3, hop counts of calls over meet_small_rows: consecutive rows a wavefront takes at once, their headers fetched
+	                            // together (1, 2, 4 or 8; 1: one row per wavefront, the schedule before round 14)
+	int meet_tail_rows = 0;     // ... the last rows of such a call that stay one per wavefront; 0: twice the wavefronts the kernel has resident
 	int meet_layout = 1;    // build the padded adjacency + slot descriptors at upload (the pre-pass needs them)
 	int meet_align = 32;    // entries a padded list is aligned and padded to (4 = one 16-byte group; 16 / 32 = whole 64 / 128-byte lines: -4 % / -6 % on the pre-pass)
 	int meet_pack = 1;      // bit-packed copy of the padded lists (pgq_pack.h), walked by k_meet3 / k_meet3w: 1 = for V <= 2^21 (six 21-bit ids per group); 2 = also V <= 2^25 (five 25-bit ids; not measured on R-MAT-22 yet); 0: 32-bit lists only

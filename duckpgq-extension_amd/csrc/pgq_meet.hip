@@ -51,6 +51,31 @@ constexpr int kMeetWPB = 1;         // wavefronts per k_meet3 workgroup: one, so
 #ifndef PGQ_MEET3_DEPTH
 #define PGQ_MEET3_DEPTH 2 // list requests in flight per wavefront
 #endif
+// wavefronts per SIMD a k_meet3 instantiation is compiled for (its __launch_bounds__, and the host's count of resident wavefronts)
+constexpr int meet3_waves(bool paths, int depth, int k, bool bnd) {
+	return paths ? 6 : (depth > 4 ? 4 : (depth > 2 ? 5 : ((k > 4 || bnd) ? PGQ_MEET3_WAVES_PACKED : PGQ_MEET3_WAVES)));
+}
+constexpr int kMeet3RowsMax = 8; // most rows a k_meet3 wavefront takes at once (option meet_rows_per_wave: 1, 2, 4 or 8)
+// k_meet3's static schedule, a pure function of (n, R = 1 << shift, T = tail): the first max(0, n - T) rows, rounded down to
+// a multiple of R, go R consecutive rows to a group; every row behind them is a group of its own, in row order behind the
+// head's groups.  A one-wavefront workgroup takes group blockIdx.x (and, on a capped grid, further groups at the grid's stride).
+// The host sizes the grid and the kernel finds its rows with this one struct.  (The hardware starts workgroups in blockIdx
+// order in practice, so the single rows run last and the launch does not end on a wavefront with R rows still to go;
+// nothing but the timing depends on that.)
+// (32-bit: a call has fewer than 2^31 rows, pgq_route.hip, and the scalar unit compares no 64-bit numbers for order — as
+// 64-bit values the loop's bounds sat in vector registers and spilled)
+struct Meet3Schedule {
+	int head_groups; // groups of R rows
+	int groups;      // ... plus the single rows
+	int shift;
+	__host__ __device__ Meet3Schedule(int n, int shift_, int tail) : shift(shift_) {
+		const int head = n > tail ? n - tail : 0;
+		head_groups = head >> shift;
+		groups = head_groups + (n - (head_groups << shift));
+	}
+	__host__ __device__ int first(int g) const { return g < head_groups ? g << shift : (head_groups << shift) + (g - head_groups); }
+	__host__ __device__ int rows(int g) const { return g < head_groups ? 1 << shift : 1; }
+};
 #ifndef PGQ_MEET3_DEPTH_SMALL
 #define PGQ_MEET3_DEPTH_SMALL 4 // ... in the variant for calls too small to fill the chip (latency, not bandwidth, is what counts)
 #endif
@@ -277,8 +302,10 @@ namespace pgq {
 // here, not queued.  A walk that was CUT proves nothing beyond distance >= 3: that row stays open whatever the bound, and
 // so do the rows whose lists are over the register set (the test that would exclude their distances never ran).
 // (Compiled for PGQ_MEET3_WAVES_PACKED wavefronts per SIMD over the 32-bit lists too: at 64 VGPRs the bound's tests spilled two.)
+// rows_shift, tail_rows: the launch's Meet3Schedule.  A wavefront takes a group of 1 << rows_shift consecutive rows (one row in the
+// launch's tail): their headers are fetched by the group's first lanes, one row each, and the rows then run one after the other.
 template <bool PATHS, bool BIGV, int DEPTH, int K, bool BND = false>
-__global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH > 2 ? 5 : ((K > 4 || BND) ? PGQ_MEET3_WAVES_PACKED : PGQ_MEET3_WAVES)))) void k_meet3(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
+__global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) void k_meet3(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                   int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                   const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
                                                   const uint4 *__restrict__ fdesc, const uint4 *__restrict__ rdesc,
@@ -286,11 +313,13 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
                                                   const u32 *__restrict__ fwork, const u32 *__restrict__ rwork,
                                                   int64_t *__restrict__ out, MeetPath *__restrict__ rec, int64_t cap,
                                                   const u32 *__restrict__ go, MeetDevBlock *__restrict__ db, MeetQueue q,
-                                                  MeetHostBlock *__restrict__ fin, int bound, bool split) {
+                                                  MeetHostBlock *__restrict__ fin, int bound, bool split, int rows_shift,
+                                                  int tail_rows) {
 	static_assert(kMeetWPB == 1, "one wavefront per workgroup: the LDS arrays are addressed statically");
 	static_assert(!PATHS || K == 4, "the path flow walks the 32-bit lists");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
 	__shared__ __attribute__((aligned(16))) unsigned char win[64];
+	__shared__ __attribute__((aligned(16))) uint4 hdr[kMeet3RowsMax][2]; // per row of the group: s, d, so, degS | di, degD, workS, workD
 	MeetCounters *const mc = &db->m;
 	if ((go && *go == 0) || db->ball.go) { // (a scalar load: one word read by every wavefront through the vector path is a hot spot on one L2
 		meet_finalize(db, fin); // channel — polling it per row while the decision kernel ran beside this one made k_meet3
@@ -298,226 +327,249 @@ __global__ __launch_bounds__(64 * kMeetWPB, PATHS ? 6 : (DEPTH > 4 ? 4 : (DEPTH 
 	}
 	const int lane = threadIdx.x & 63;
 	win[lane] = 0;
+	// a row's answer where it is a constant: built at the store from a scalar (as 64-bit constants the compiler kept every one of them
+	// in a register pair from the kernel's start across every walk: 20 B of scratch per lane under the second loop)
+	auto answer = [&](int64_t i, int v) {
+		asm volatile("" : "+s"(v));
+		out[i] = (int64_t)v;
+	};
 	unsigned long long entries = 0, walked = 0; // wave-uniform
 	u32 vertices = 0;
-	const int64_t wave0 = (int64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-	const int64_t nwaves = (int64_t)((gridDim.x * blockDim.x) >> 6);
-	for (int64_t i = wave0; i < n; i += nwaves) {
-#ifdef PGQ_MEET3_ROWTRACE
-		const unsigned long long rt0 = wall_clock64();
-#endif
-		const int64_t s = src[i], d = dst[i];
-		{
+	const int wave0 = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+	const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+	const Meet3Schedule sched((int)n, rows_shift, tail_rows);
+	for (int g = wave0; g < sched.groups; g += nwaves) {
+		const int i0 = sched.first(g);
+		const int nrows = sched.rows(g);
+		// The headers of the group's rows in two vector round trips instead of three scalar ones per row: lane r loads row r's ids,
+		// settles the row if it is trivial (the tests of a single row, in their order), loads its offsets and walk sizes and leaves
+		// them in LDS.  Nothing of it stays in a register across a row's walk.  degS == 0 marks a row that is settled.
+		if (lane < nrows) {
+			// (an opaque copy of the lane, and 32-bit offsets from the group's scalar addresses: what the compiler can compute before the
+			// loops from the lane alone — hdr[lane]'s address, the zero above a 64-bit lane — stayed in registers across the walks and spilled)
+			u32 slot = (u32)lane;
+			asm volatile("" : "+v"(slot));
+			const int64_t s = *(const int64_t *)((const char *)(src + i0) + slot * 8u), d = *(const int64_t *)((const char *)(dst + i0) + slot * 8u);
+			uint4 h0 = make_uint4((u32)s, (u32)d, 0u, 0u), h1 = make_uint4(0u, 0u, 0u, 0u);
+			int64_t settled = -1; // what a trivial row is answered with
 			if (s < 0) { // NULL row (iterativelength.cpp:99-101)
-				if (lane == 0) out[i] = -1;
-				continue;
-			}
-			if (s >= V || d < 0 || d >= V) {
-				if (lane == 0) {
-					mc->bad = 1;
-					out[i] = -1;
+			} else if (s >= V || d < 0 || d >= V) {
+				mc->bad = 1;
+			} else if (s == d) { // iterativelength.cpp:102-103
+				settled = 0;
+			} else {
+				const int so = (int)off[s], se = (int)off[s + 1], di = (int)roff[d], de = (int)roff[d + 1];
+				const u32 workS = fwork[s], workD = rwork[d];
+				const int degS = se - so, degD = de - di;
+				if (degS != 0 && degD != 0) { // (else no path can exist: NULL like an exhausted search, iterativelength.cpp:133-139)
+					h0.z = (u32)so, h0.w = (u32)degS;
+					h1 = make_uint4((u32)di, (u32)degD, workS, workD);
 				}
-				continue;
 			}
-			if (s == d) { // iterativelength.cpp:102-103
-				if (lane == 0) out[i] = 0;
-				continue;
-			}
+			if (h0.w == 0) *(int64_t *)((char *)(out + i0) + slot * 8u) = settled;
+			hdr[slot][0] = h0;
+			hdr[slot][1] = h1;
 		}
-		const int so = (int)off[s], se = (int)off[s + 1], di = (int)roff[d], de = (int)roff[d + 1];
-		const u32 workS = fwork[s], workD = rwork[d];
-		const int degS = se - so, degD = de - di;
-		{
-			if (degS == 0 || degD == 0) { // no path can exist: NULL like an exhausted search (iterativelength.cpp:133-139)
-				if (lane == 0) out[i] = -1;
-				continue;
+		__builtin_amdgcn_wave_barrier();
+		for (int r = 0; r < nrows; r++) {
+			const int64_t i = (int64_t)(i0 + r);
+#ifdef PGQ_MEET3_ROWTRACE
+			const unsigned long long rt0 = wall_clock64();
+#endif
+			const uint4 h0 = hdr[r][0], h1 = hdr[r][1];
+			const int degS = __builtin_amdgcn_readfirstlane((int)h0.w);
+			if (degS == 0) continue; // settled by its lane above
+			const u32 s = (u32)__builtin_amdgcn_readfirstlane((int)h0.x), d = (u32)__builtin_amdgcn_readfirstlane((int)h0.y);
+			const int so = __builtin_amdgcn_readfirstlane((int)h0.z);
+			const int di = __builtin_amdgcn_readfirstlane((int)h1.x), degD = __builtin_amdgcn_readfirstlane((int)h1.y);
+			const u32 workS = (u32)__builtin_amdgcn_readfirstlane((int)h1.z), workD = (u32)__builtin_amdgcn_readfirstlane((int)h1.w);
+			MeetEntry ent = { (u32)i, 0u, (u32)s, (u32)d, (u32)so, (u32)degS, (u32)di, (u32)degD, workS, workD, 0u, 0u };
+			// expand from the endpoint whose two-hop walk is the shorter one (round 4: the sums of the neighbours' list lengths
+			// are kept per vertex; the shorter one-hop LIST picked the longer walk for every row that ran into the cap, and the
+			// walks are 4 % shorter on average); the other endpoint's list is the set.  fwd: walk N_out(N_out(s)) against the
+			// set N_in(d).  PATHS always expands from dst against the set N_out(src): the in-lists are ordered by source (built
+			// so at upload), so the walk meets the witnesses in the order of the reference's tie-break (smallest second-to-last
+			// vertex first, then the smallest vertex before it) and may stop at the first one
+			bool fwd = PATHS ? false : workS <= workD;
+			// (handing a row on whenever the preferred set does not fit the registers, instead of walking from the other endpoint,
+			// sent 1740 instead of 34 such rows of the 65,536 to the bit-map kernel: 0.244 -> 0.264 ms)
+			if (!PATHS && (fwd ? degD : degS) > kSetRegMax) fwd = !fwd;
+			const int set_n = fwd ? degD : degS;
+			const int exp_n = fwd ? degS : degD;
+			{
+				// both lists too long for the registers — or the expanded side's own list is a hub's: its distance-2 test alone is one
+				// wavefront reading exp_n descriptors 256 per round trip (R-MAT-22: a 100,000-neighbour endpoint among 1024 random pairs
+				// held the kernel for 70 us); the bit-map kernel reads it with 16 wavefronts
+				if (set_n > kSetRegMax || (!PATHS && exp_n > kMeet3ExpMax)) {
+					if (lane == 0) {
+						answer(i, (int)kMeetOpen);
+						queue_push(q, (u32)i, ent);
+					}
+					continue;
+				}
 			}
-		}
-		MeetEntry ent = { (u32)i, 0u, (u32)s, (u32)d, (u32)so, (u32)degS, (u32)di, (u32)degD, workS, workD, 0u, 0u };
-		// expand from the endpoint whose two-hop walk is the shorter one (round 4: the sums of the neighbours' list lengths
-		// are kept per vertex; the shorter one-hop LIST picked the longer walk for every row that ran into the cap, and the
-		// walks are 4 % shorter on average); the other endpoint's list is the set.  fwd: walk N_out(N_out(s)) against the
-		// set N_in(d).  PATHS always expands from dst against the set N_out(src): the in-lists are ordered by source (built
-		// so at upload), so the walk meets the witnesses in the order of the reference's tie-break (smallest second-to-last
-		// vertex first, then the smallest vertex before it) and may stop at the first one
-		bool fwd = PATHS ? false : workS <= workD;
-		// (handing a row on whenever the preferred set does not fit the registers, instead of walking from the other endpoint,
-		// sent 1740 instead of 34 such rows of the 65,536 to the bit-map kernel: 0.244 -> 0.264 ms)
-		if (!PATHS && (fwd ? degD : degS) > kSetRegMax) fwd = !fwd;
-		const int set_n = fwd ? degD : degS;
-		const int exp_n = fwd ? degS : degD;
-		{
-			// both lists too long for the registers — or the expanded side's own list is a hub's: its distance-2 test alone is one
-			// wavefront reading exp_n descriptors 256 per round trip (R-MAT-22: a 100,000-neighbour endpoint among 1024 random pairs
-			// held the kernel for 70 us); the bit-map kernel reads it with 16 wavefronts
-			if (set_n > kSetRegMax || (!PATHS && exp_n > kMeet3ExpMax)) {
-				if (lane == 0) {
-					out[i] = kMeetOpen;
+			const int32_t *set_adj = fwd ? radj + di : adj + so;      // the set side's one-hop list (ids)
+			const uint4 *exp_desc = fwd ? fdesc + so : rdesc + di;    // the expanded side's one-hop list (slot descriptors)
+			const int32_t *xp = fwd ? padj : rpadj;                   // padded adjacency of the expanded side's direction
+			const u32 other = (u32)(fwd ? s : d);                     // distance 1: the set list contains the other endpoint
+			// both one-hop lists are requested together: the set's ids into registers, the expanded side's first descriptors
+			RegSet R;
+			R.rounds = (set_n + 63) >> 6;
+#pragma unroll
+			for (int k = 0; k < kSetRegs; k++) {
+				R.r[k] = kMeetEmpty;
+				if (k < R.rounds) { // wave-uniform
+					const int p = k * 64 + lane;
+					const u32 x = (u32)set_adj[min(p, set_n - 1)];
+					R.r[k] = p < set_n ? x : kMeetEmpty;
+				}
+			}
+			uint4 d0 = make_uint4(0, 0, 0, 0);
+			if (lane < exp_n) d0 = exp_desc[lane];
+#pragma unroll
+			for (int k = 0; k < kFltWords / 256; k++) reinterpret_cast<uint4_alias *>(bm)[k * 64 + lane] = make_uint4(0, 0, 0, 0);
+			__builtin_amdgcn_wave_barrier();
+			bool hit = false;
+#pragma unroll
+			for (int k = 0; k < kSetRegs; k++) {
+				if (k < R.rounds) {
+					const u32 x = R.r[k];
+					if (x != kMeetEmpty) {
+						hit |= x == other;
+						atomicOr(&bm[flt_word(x)], flt_mask<BIGV>(x));
+					}
+				}
+			}
+			entries += (unsigned long long)set_n;
+			vertices += (u32)exp_n; // one 16-byte descriptor per expanded vertex
+			__builtin_amdgcn_wave_barrier();
+			{
+				if (__any(hit)) {
+					if (lane == 0) answer(i, (!BND || bound >= 1) ? 1 : -1);
+					continue;
+				}
+				if (BND && bound < 2) { // distance >= 2 and at most `bound` hops wanted
+					if (lane == 0) answer(i, -1);
+					continue;
+				}
+				// distance 2: the middle vertex is the smallest common one
+				u32 mid = kMeetEmpty; // wave-uniform
+				{
+					const u32 v = lane < exp_n ? d0.x : kMeetEmpty;
+					const u32 pass = v != kMeetEmpty ? (flt_test<BIGV>(bm[flt_word(v)], v) & 1u) : 0u;
+					verify_candidates(R, pass, make_int4((int)v, 0, 0, 0), [&](u32 x, int) {
+						mid = min(mid, x);
+						return !PATHS; // a hop count needs any common neighbour, a path the smallest
+					});
+				}
+				// the rest of a long one-hop list, 256 ids per round trip (a hub's 5000 neighbours were 78 dependent trips of 64)
+				for (int pb = 64; pb < exp_n; pb += 256) {
+					u32 v[4];
+#pragma unroll
+					for (int u = 0; u < 4; u++) {
+						const int p = pb + 64 * u + lane;
+						v[u] = exp_desc[min(p, exp_n - 1)].x;
+						if (p >= exp_n) v[u] = kMeetEmpty;
+					}
+					u32 pass = 0;
+#pragma unroll
+					for (int u = 0; u < 4; u++)
+						if (v[u] != kMeetEmpty) pass |= (flt_test<BIGV>(bm[flt_word(v[u])], v[u]) & 1u) << u;
+					verify_candidates(R, pass, make_int4((int)v[0], (int)v[1], (int)v[2], (int)v[3]), [&](u32 x, int) {
+						mid = min(mid, x);
+						return !PATHS;
+					});
+					if (!PATHS && mid != kMeetEmpty) break;
+				}
+				if (mid != kMeetEmpty) {
+					if (lane == 0) {
+						if constexpr (PATHS) rec[i].v1 = (int32_t)mid;
+						answer(i, 2);
+					}
+					continue;
+				}
+				if (BND && bound < 3) { // distance >= 3: the two-hop walk is not started
+					if (lane == 0) answer(i, -1);
+					continue;
+				}
+			}
+			// distance 3: the padded lists of the expanded side's vertices, one filter probe per entry (the exact test only for
+			// what the filter lets through), ended by the first pass with a hit.  PATHS: requests are processed in walk order
+			// and the lists ascend, so every later witness has a larger (second vertex, first vertex) key than the smallest one
+			// of the pass that found the first
+			u64 best = ~0ull; // wave-uniform: smallest (outer vertex << 32 | inner vertex) over the witnesses (PATHS), or 0 = found
+			bool capped = false;
+			int resume = 0;
+#ifdef PGQ_MEET3_ROWTRACE
+			const unsigned long long rt1 = wall_clock64();
+			const unsigned long long ent_before = entries;
+#endif
+			auto test = [&](const typename SegGroup<K>::type &v, bool ok, u32 ev) {
+				// a lane past the round's end re-reads real entries of the last list: no mask needed for membership;
+				// PATHS masks them (their ev is the last list's, so they would even be right, but cost a verification)
+				const u32 pass = (PATHS && !ok) ? 0u : flt_pass<BIGV>(bm, v);
+				verify_candidates(R, pass, v, [&](u32 x, int L) {
+					if constexpr (PATHS) { // backward walk: expanded vertex = second-to-last, entry = the one before it
+						const u32 y = (u32)__builtin_amdgcn_readlane((int)ev, L);
+						best = min(best, (u64)y << 32 | x);
+						return false;
+					} else {
+						best = 0;
+						return true;
+					}
+				});
+			};
+			auto done = [&]() { return best != ~0ull; };
+			// K > 4 and `split` (the packed lists are in degree order, pgq_pack.h): the heads of all lists first, then the tails
+			unsigned long long e3 = seg_walk<DEPTH, PATHS, K>(exp_desc, exp_n, 0, 1, xp, win, true, d0, (unsigned long long)cap, capped, resume,
+			                                                  test, done, 0, K > 4 && split);
+			if constexpr (K > 4) {
+				if (split) {
+					// cut among the heads: the tails of the rounds before are unwalked too, the next stage starts over
+					if (capped) resume = 0;
+					if (best == ~0ull && !capped) {
+						// Two calls, not a loop over the parts: d0 would stay live across it (44 B of scratch per lane), so the tails'
+						// descriptors are read again.  The cap bounds both parts together; what is left of it goes into scalar
+						// registers, where `cap` itself sits (in VGPRs it cost 12 B of scratch per lane).  Cut here: every head has been
+						// walked, and the tails before `resume`: the next stage walks whole lists from that round on, a superset of the rest
+						const unsigned long long left = uniform_u64((unsigned long long)cap - min((unsigned long long)cap, e3));
+						entries += e3;
+						walked += e3;
+						e3 = seg_walk<DEPTH, PATHS, K>(exp_desc, exp_n, 0, 1, xp, win, false, make_uint4(0, 0, 0, 0), left, capped, resume,
+						                               test, done, 1, true);
+						vertices += (u32)exp_n; // the descriptors, a second time
+					}
+				}
+			}
+			entries += e3;
+			if (K > 4) walked += e3;
+			const bool found = best != ~0ull;
+#ifdef PGQ_MEET3_ROWTRACE
+			{
+				const unsigned long long rt2 = wall_clock64();
+				if (lane == 0 && rt2 - rt0 > 2000) // > 20 us
+					printf("meet3 row %lld: start +%.1f us, head %.1f us, walk %.1f us, degS %d degD %d workS %u workD %u set %d exp %d walked %llu found %d capped %d\n", (long long)i,
+					       0.0, (rt1 - rt0) * 0.01, (rt2 - rt1) * 0.01, degS, degD, workS, workD, set_n, exp_n, entries - ent_before, (int)found, (int)capped);
+			}
+#endif
+			if (lane == 0) {
+				if constexpr (PATHS) {
+					if (found) {
+						rec[i].v2 = (int32_t)(best >> 32);
+						rec[i].v1 = (int32_t)(u32)best;
+					}
+				}
+				// the walk ran to its end without a witness: the distance is at least 4; it was cut short: distances 1 and 2
+				// are excluded and the next stage takes the walk up where it stopped
+				const bool beyond = BND && bound < 4 && !found && !capped; // distance >= 4 proven under a bound of 3
+				out[i] = found ? 3 : (beyond ? -1 : (capped ? kMeetOpen : kMeetOpen4));
+				if (!found && !beyond) {
+					ent.flags = capped ? (kEntKnown3 | (fwd ? kEntFwd : 0u) | ((u32)resume << kEntResumeShift)) : kEntKnown4;
 					queue_push(q, (u32)i, ent);
 				}
-				continue;
 			}
 		}
-		const int32_t *set_adj = fwd ? radj + di : adj + so;      // the set side's one-hop list (ids)
-		const uint4 *exp_desc = fwd ? fdesc + so : rdesc + di;    // the expanded side's one-hop list (slot descriptors)
-		const int32_t *xp = fwd ? padj : rpadj;                   // padded adjacency of the expanded side's direction
-		const u32 other = (u32)(fwd ? s : d);                     // distance 1: the set list contains the other endpoint
-		// both one-hop lists are requested together: the set's ids into registers, the expanded side's first descriptors
-		RegSet R;
-		R.rounds = (set_n + 63) >> 6;
-#pragma unroll
-		for (int k = 0; k < kSetRegs; k++) {
-			R.r[k] = kMeetEmpty;
-			if (k < R.rounds) { // wave-uniform
-				const int p = k * 64 + lane;
-				const u32 x = (u32)set_adj[min(p, set_n - 1)];
-				R.r[k] = p < set_n ? x : kMeetEmpty;
-			}
-		}
-		uint4 d0 = make_uint4(0, 0, 0, 0);
-		if (lane < exp_n) d0 = exp_desc[lane];
-#pragma unroll
-		for (int k = 0; k < kFltWords / 256; k++) reinterpret_cast<uint4_alias *>(bm)[k * 64 + lane] = make_uint4(0, 0, 0, 0);
-		__builtin_amdgcn_wave_barrier();
-		bool hit = false;
-#pragma unroll
-		for (int k = 0; k < kSetRegs; k++) {
-			if (k < R.rounds) {
-				const u32 x = R.r[k];
-				if (x != kMeetEmpty) {
-					hit |= x == other;
-					atomicOr(&bm[flt_word(x)], flt_mask<BIGV>(x));
-				}
-			}
-		}
-		entries += (unsigned long long)set_n;
-		vertices += (u32)exp_n; // one 16-byte descriptor per expanded vertex
-		__builtin_amdgcn_wave_barrier();
-		{
-			if (__any(hit)) {
-				if (lane == 0) out[i] = (!BND || bound >= 1) ? 1 : -1;
-				continue;
-			}
-			if (BND && bound < 2) { // distance >= 2 and at most `bound` hops wanted
-				if (lane == 0) out[i] = -1;
-				continue;
-			}
-			// distance 2: the middle vertex is the smallest common one
-			u32 mid = kMeetEmpty; // wave-uniform
-			{
-				const u32 v = lane < exp_n ? d0.x : kMeetEmpty;
-				const u32 pass = v != kMeetEmpty ? (flt_test<BIGV>(bm[flt_word(v)], v) & 1u) : 0u;
-				verify_candidates(R, pass, make_int4((int)v, 0, 0, 0), [&](u32 x, int) {
-					mid = min(mid, x);
-					return !PATHS; // a hop count needs any common neighbour, a path the smallest
-				});
-			}
-			// the rest of a long one-hop list, 256 ids per round trip (a hub's 5000 neighbours were 78 dependent trips of 64)
-			for (int pb = 64; pb < exp_n; pb += 256) {
-				u32 v[4];
-#pragma unroll
-				for (int u = 0; u < 4; u++) {
-					const int p = pb + 64 * u + lane;
-					v[u] = exp_desc[min(p, exp_n - 1)].x;
-					if (p >= exp_n) v[u] = kMeetEmpty;
-				}
-				u32 pass = 0;
-#pragma unroll
-				for (int u = 0; u < 4; u++)
-					if (v[u] != kMeetEmpty) pass |= (flt_test<BIGV>(bm[flt_word(v[u])], v[u]) & 1u) << u;
-				verify_candidates(R, pass, make_int4((int)v[0], (int)v[1], (int)v[2], (int)v[3]), [&](u32 x, int) {
-					mid = min(mid, x);
-					return !PATHS;
-				});
-				if (!PATHS && mid != kMeetEmpty) break;
-			}
-			if (mid != kMeetEmpty) {
-				if (lane == 0) {
-					if constexpr (PATHS) rec[i].v1 = (int32_t)mid;
-					out[i] = 2;
-				}
-				continue;
-			}
-			if (BND && bound < 3) { // distance >= 3: the two-hop walk is not started
-				if (lane == 0) out[i] = -1;
-				continue;
-			}
-		}
-		// distance 3: the padded lists of the expanded side's vertices, one filter probe per entry (the exact test only for
-		// what the filter lets through), ended by the first pass with a hit.  PATHS: requests are processed in walk order
-		// and the lists ascend, so every later witness has a larger (second vertex, first vertex) key than the smallest one
-		// of the pass that found the first
-		u64 best = ~0ull; // wave-uniform: smallest (outer vertex << 32 | inner vertex) over the witnesses (PATHS), or 0 = found
-		bool capped = false;
-		int resume = 0;
-#ifdef PGQ_MEET3_ROWTRACE
-		const unsigned long long rt1 = wall_clock64();
-		const unsigned long long ent_before = entries;
-#endif
-		auto test = [&](const typename SegGroup<K>::type &v, bool ok, u32 ev) {
-			// a lane past the round's end re-reads real entries of the last list: no mask needed for membership;
-			// PATHS masks them (their ev is the last list's, so they would even be right, but cost a verification)
-			const u32 pass = (PATHS && !ok) ? 0u : flt_pass<BIGV>(bm, v);
-			verify_candidates(R, pass, v, [&](u32 x, int L) {
-				if constexpr (PATHS) { // backward walk: expanded vertex = second-to-last, entry = the one before it
-					const u32 y = (u32)__builtin_amdgcn_readlane((int)ev, L);
-					best = min(best, (u64)y << 32 | x);
-					return false;
-				} else {
-					best = 0;
-					return true;
-				}
-			});
-		};
-		auto done = [&]() { return best != ~0ull; };
-		// K > 4 and `split` (the packed lists are in degree order, pgq_pack.h): the heads of all lists first, then the tails
-		unsigned long long e3 = seg_walk<DEPTH, PATHS, K>(exp_desc, exp_n, 0, 1, xp, win, true, d0, (unsigned long long)cap, capped, resume,
-		                                                  test, done, 0, K > 4 && split);
-		if constexpr (K > 4) {
-			if (split) {
-				// cut among the heads: the tails of the rounds before are unwalked too, the next stage starts over
-				if (capped) resume = 0;
-				if (best == ~0ull && !capped) {
-					// Two calls, not a loop over the parts: d0 would stay live across it (44 B of scratch per lane), so the tails'
-					// descriptors are read again.  The cap bounds both parts together; what is left of it goes into scalar
-					// registers, where `cap` itself sits (in VGPRs it cost 12 B of scratch per lane).  Cut here: every head has been
-					// walked, and the tails before `resume`: the next stage walks whole lists from that round on, a superset of the rest
-					const unsigned long long left = uniform_u64((unsigned long long)cap - min((unsigned long long)cap, e3));
-					entries += e3;
-					walked += e3;
-					e3 = seg_walk<DEPTH, PATHS, K>(exp_desc, exp_n, 0, 1, xp, win, false, make_uint4(0, 0, 0, 0), left, capped, resume,
-					                               test, done, 1, true);
-					vertices += (u32)exp_n; // the descriptors, a second time
-				}
-			}
-		}
-		entries += e3;
-		if (K > 4) walked += e3;
-		const bool found = best != ~0ull;
-#ifdef PGQ_MEET3_ROWTRACE
-		{
-			const unsigned long long rt2 = wall_clock64();
-			if (lane == 0 && rt2 - rt0 > 2000) // > 20 us
-				printf("meet3 row %lld: start +%.1f us, head %.1f us, walk %.1f us, degS %d degD %d workS %u workD %u set %d exp %d walked %llu found %d capped %d\n", (long long)i,
-				       0.0, (rt1 - rt0) * 0.01, (rt2 - rt1) * 0.01, degS, degD, workS, workD, set_n, exp_n, entries - ent_before, (int)found, (int)capped);
-		}
-#endif
-		if (lane == 0) {
-			if constexpr (PATHS) {
-				if (found) {
-					rec[i].v2 = (int32_t)(best >> 32);
-					rec[i].v1 = (int32_t)(u32)best;
-				}
-			}
-			// the walk ran to its end without a witness: the distance is at least 4; it was cut short: distances 1 and 2
-			// are excluded and the next stage takes the walk up where it stopped
-			const bool beyond = BND && bound < 4 && !found && !capped; // distance >= 4 proven under a bound of 3
-			out[i] = found ? 3 : (beyond ? -1 : (capped ? kMeetOpen : kMeetOpen4));
-			if (!found && !beyond) {
-				ent.flags = capped ? (kEntKnown3 | (fwd ? kEntFwd : 0u) | ((u32)resume << kEntResumeShift)) : kEntKnown4;
-				queue_push(q, (u32)i, ent);
-			}
-		}
+		__builtin_amdgcn_wave_barrier(); // (a capped grid: the next group's headers overwrite these)
 	}
 	if (lane == 0) meet_add_stats(mc, 0, entries, (unsigned long long)vertices, walked);
 	meet_finalize(db, fin);
@@ -2185,7 +2237,20 @@ private:
 		const int pk = c->pack_k;
 		KernelTimer kt(st, K_MEET);
 		const unsigned resident = (unsigned)ncu * 32 / kMeetWPB; // more workgroups than the chip holds at once: up to 8 rounds
-		const dim3 grid((unsigned)std::min<int64_t>((n + kMeetWPB - 1) / kMeetWPB, (int64_t)std::max(1, opt.meet_grid_mult) * resident));
+		// Several rows per wavefront (Meet3Schedule) for the hop counts of calls that fill the chip: a row's header is two or
+		// three dependent round trips that use nothing of the wavefront slot they hold, and R rows fetch them together.  The
+		// last meet_tail_rows rows stay one per wavefront: the launch ends on its long rows (2.4 % walk their whole two-hop
+		// neighbourhood), and a wavefront that starts late with R rows ends later still (R = 8 with a tail of one times the
+		// resident wavefronts: 0.180 ms per 65,536 rows against 0.160).  Small calls and the path flow are bound by their longest
+		// row: one row per wavefront, as before.  The bounded flow is on the schedule: 65,536 rows under max_hops 2 / 3 / 4
+		// 0.148 / 0.213 / 0.222 ms with R = 1, 0.120 / 0.197 / 0.207 with R = 4
+		const bool taper = !paths && !small_call;
+		const int rpw = opt.meet_rows_per_wave;
+		const int rows_shift = !taper ? 0 : (rpw == 8 ? 3 : (rpw == 4 ? 2 : (rpw == 2 ? 1 : 0)));
+		const int tail_rows = opt.meet_tail_rows > 0 ? opt.meet_tail_rows // 0: twice the wavefronts the instantiation has resident
+		                                             : 2 * ncu * 4 * meet3_waves(false, PGQ_MEET3_DEPTH, pk, bnd);
+		const Meet3Schedule sched((int)n, rows_shift, tail_rows);
+		const dim3 grid((unsigned)std::min<int64_t>((int64_t)sched.groups, (int64_t)std::max(1, opt.meet_grid_mult) * resident));
 		MeetHostBlock *fin = last_stage == 0 ? hb : nullptr;
 		const u32 *d_go = decide ? &db->dec.go : nullptr; // the gate's verdict on the device
 		// the hop-count walks read the packed lists (pack_k ids per group) when the upload built them; the path flow the
@@ -2197,7 +2262,8 @@ private:
 	} while (0)
 #define PGQ_MEET3KB(P, B, D, K, XF, XR, BN)                                                                              \
 	hipLaunchKernelGGL((k_meet3<P, B, D, K, BN>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, \
-	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound, c->pack_order != 0)
+	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound, c->pack_order != 0, \
+	                   rows_shift, tail_rows)
 #define PGQ_MEET3(P, B, D)                                                                                               \
 	do {                                                                                                                 \
 		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \

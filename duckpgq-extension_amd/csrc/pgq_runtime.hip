@@ -336,6 +336,8 @@ static std::vector<OptRef> option_table(Options &o) {
 		{ "upload_threads", &o.upload_threads, nullptr },
 		{ "upload_narrow_host", &o.upload_narrow_host, nullptr },
 		{ "meet_grid_mult", &o.meet_grid_mult, nullptr },
+		{ "meet_rows_per_wave", &o.meet_rows_per_wave, nullptr },
+		{ "meet_tail_rows", &o.meet_tail_rows, nullptr },
 		{ "meet4_grid_mult", &o.meet4_grid_mult, nullptr },
 		{ "meet4_batch", &o.meet4_batch, nullptr },
 		{ "meet4_batch_settled", nullptr, nullptr, &g_meet4_batch_settled },
@@ -2104,6 +2106,11 @@ static int set_option_in(Options &o, const char *key, const char *value) {
 	for (const OptRef &r : option_table(o)) {
 		if (strcmp(r.name, key) != 0) continue;
 		if (r.counter) return fail(PGQ_ERR_INVALID_ARG, std::string("read-only option: ") + key);
+		if (r.i == &o.meet_rows_per_wave || r.i == &o.meet_tail_rows) {
+			const int v = atoi(value);
+			if (r.i == &o.meet_rows_per_wave ? (v != 1 && v != 2 && v != 4 && v != 8) : v < 0)
+				return fail(PGQ_ERR_INVALID_ARG, std::string(key) + (r.i == &o.meet_tail_rows ? ": not below 0" : ": 1, 2, 4 or 8"));
+		}
 		if (r.i) *r.i = atoi(value);
 		else *r.d = atof(value);
 		return PGQ_OK;
