@@ -171,20 +171,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 	unsigned char *win = s_win[wib];
 	win[lane] = 0;
 	if (tid < 2) s_stat[tid] = 0;
-	u32 *const gmap = GM ? gmaps + (size_t)blockIdx.x * bm_words : nullptr;
-	auto bit = [&](u32 x) {
-		const u32 w = GM ? __hip_atomic_load(&gmap[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s_map[x >> 5];
-		return (w >> (x & 31)) & 1u;
-	};
-	auto bits4 = [&](const int4 &v) { return bit((u32)v.x) | bit((u32)v.y) | bit((u32)v.z) | bit((u32)v.w); };
-	auto mark = [&](u32 x) {
-		if constexpr (GM) { // look first: most entries of a two-hop walk on a skewed graph are the same few hubs (pgq_meet.hip, k_meet4d)
-			const u32 w = __hip_atomic_load(&gmap[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			if (!((w >> (x & 31)) & 1u)) atomicOr(&gmap[x >> 5], 1u << (x & 31));
-		} else {
-			atomicOr(&s_map[x >> 5], 1u << (x & 31));
-		}
-	};
+	const VertexMap<GM> map { GM ? gmaps + (size_t)blockIdx.x * bm_words : s_map, bm_words };
 	// option meet_trace: time per phase (10-ns ticks of the constant clock, thread 0 of every workgroup), summed over the grid
 	unsigned long long t_last = TRACE ? wall_clock64() : 0ull, t_ph[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, t_pmax[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, t_seg_max = 0, t_seg0 = 0;
 	auto tick = [&](int k) {
@@ -220,13 +207,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 		{
 			const int64_t ic = min((int64_t)start + tid, n - 1);
 			const int64_t si = src[ic], di = dst[ic];
-			if constexpr (GM) {
-				uint4 *m4 = reinterpret_cast<uint4 *>(gmap);
-				for (int k = tid; k < bm_words / 4; k += kBallRows) m4[k] = make_uint4(0, 0, 0, 0);
-			} else {
-				uint4_alias *m4 = reinterpret_cast<uint4_alias *>(s_map);
-				for (int k = tid; k < bm_words / 4; k += kBallRows) m4[k] = make_uint4(0, 0, 0, 0);
-			}
+			map.template clear<kBallRows>(tid);
 			__syncthreads();
 			if (start + (u32)tid >= wend || si != s) atomicMin(&s_len, (u32)tid);
 			di32 = (di < 0 || di >= V) ? 0xFFFFFFFFu : (u32)di; // out of range: no vertex id (V < 2^31 - 1)
@@ -267,12 +248,12 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 		const bool need_ball = sval && degS > 0; // workgroup-uniform
 		if (need_ball) {
 			// S1 = N_out(s)
-			for (int k = tid; k < degS; k += kBallRows) mark(fdesc[so + k].x);
+			for (int k = tid; k < degS; k += kBallRows) map.mark(fdesc[so + k].x);
 			if (tid == 0) atomicAdd(&s_stat[1], 2ull * (unsigned long long)degS); // once as ids, once as the walk's descriptors
 			__syncthreads();
 			tick(1);
 			if (s_res[tid] == kBallOpenI) {
-				if (bit(di32)) s_res[tid] = (!BND || bound >= 1) ? 1 : -1;
+				if (map.test(di32)) s_res[tid] = (!BND || bound >= 1) ? 1 : -1;
 				else if (BND && bound < 2) s_res[tid] = -1; // S1 is complete: distance >= 2
 			}
 			__syncthreads(); // every test against S1 is done before S2's marks land
@@ -288,12 +269,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 				const unsigned long long e1 = seg_walk<2, false>(
 				    fdesc + so, degS, wib, kBallRows / 64, padj, win, false, make_uint4(0, 0, 0, 0),
 				    (unsigned long long)cap / (kBallRows / 64), capped, resume,
-				    [&](const int4 &v, bool, u32) {
-					    mark((u32)v.x);
-					    mark((u32)v.y);
-					    mark((u32)v.z);
-					    mark((u32)v.w);
-				    },
+				    [&](const int4 &v, bool, u32) { map.mark4(v); },
 				    []() { return false; });
 				if (lane == 0 && e1) atomicAdd(&s_stat[0], e1);
 				if (capped) s_capped = 1;
@@ -304,7 +280,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 				// S2 incomplete (over the cap): a set bit still proves distance 2 (S1 is complete), nothing else holds
 				bool scan = false;
 				if (s_res[tid] == kBallOpenI) {
-					if (bit(di32)) s_res[tid] = 2;
+					if (map.test(di32)) s_res[tid] = 2;
 					else if (BND && bound < 3 && s_capped == 0) s_res[tid] = -1; // S2 is complete: distance >= 3
 					else scan = s_capped == 0;
 				}
@@ -355,7 +331,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 								// the in-degree: word 31 = the first line's last word (pass 1 kept it in s_in)
 								const u32 cnt = pass == 0 ? (u32)__shfl((int)x0[u].w, sub8 * 8 + 7) : (have ? s_in[t[u]].y : 0u);
 								bool hit = false;
-								if (have && cnt > 0) hit = (bit(x0[u].x) | bit(x0[u].y) | bit(x0[u].z) | ((pass == 1 || j8 < 7) ? bit(x0[u].w) : 0u)) != 0;
+								if (have && cnt > 0) hit = (map.test(x0[u].x) | map.test(x0[u].y) | map.test(x0[u].z) | ((pass == 1 || j8 < 7) ? map.test(x0[u].w) : 0u)) != 0;
 								const u64 m = __ballot(hit);
 								const bool found = ((m >> (8 * sub8)) & 0xFFull) != 0;
 								if (have && j8 == 0) {
@@ -396,7 +372,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 #pragma unroll
 					for (int u = 0; u < UQ; u++) {
 						const bool have = t[u] != 0xFFFFFFFFu;
-						const bool hit = (u32)j < ng[u] && bits4(x0[u]);
+						const bool hit = (u32)j < ng[u] && map.any4(x0[u]);
 						const u64 m = __ballot(hit);
 						const bool found = ((m >> (16 * sub)) & 0xFFFFull) != 0;
 						if (have && j == 0) {
@@ -425,7 +401,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 						const bool a0 = act && ga < ng, a1 = act && gb < ng;
 						const int4 y0 = load_group_nt(rpadj, sg.x + (a0 ? ga : 0u));
 						const int4 y1 = load_group_nt(rpadj, sg.x + (a1 ? gb : 0u));
-						const bool h2 = (a0 && bits4(y0)) || (a1 && bits4(y1));
+						const bool h2 = (a0 && map.any4(y0)) || (a1 && map.any4(y1));
 						const u64 m = __ballot(h2);
 						if ((m >> (16 * sub)) & 0xFFFFull) found = true;
 						if (act && j == 0) ent += min(sg.y - g0 * 4u, 128u);
@@ -461,7 +437,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 					int resume = 0;
 					const unsigned long long e2 = seg_walk<1, false>(
 					    dl, min(degD, 64), 0, kOneShot, rpadj, win, true, d0, 0ull, capped, resume,
-					    [&](const int4 &v, bool, u32) { f |= bits4(v) != 0; }, []() { return true; });
+					    [&](const int4 &v, bool, u32) { f |= map.any4(v) != 0; }, []() { return true; });
 					const bool any_f = __any(f) != 0;
 					if (lane == 0) {
 						atomicAdd(&s_stat[0], e2);
@@ -489,7 +465,7 @@ __global__ __launch_bounds__(kBallRows, PGQ_BALL_WAVES) void k_src_ball(int64_t 
 					const unsigned long long e3 = seg_walk<2, false>(
 					    dl, degD, wib, kBallRows / 64, rpadj, win, false, make_uint4(0, 0, 0, 0),
 					    (unsigned long long)test_cap / (kBallRows / 64), capped, resume,
-					    [&](const int4 &v, bool, u32) { f |= bits4(v) != 0; },
+					    [&](const int4 &v, bool, u32) { f |= map.any4(v) != 0; },
 					    [&]() {
 						    if (__any(f)) s_flag = 1;
 						    return *(volatile int *)&s_flag != 0;

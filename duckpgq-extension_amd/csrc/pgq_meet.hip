@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <type_traits>
 
 #include "pgq_search.h"
 #include "pgq_walk.h"
@@ -55,6 +56,9 @@ constexpr int kMeetWPB = 1;         // wavefronts per k_meet3 workgroup: one, so
 constexpr int meet3_waves(bool paths, int depth, int k, bool bnd) {
 	return paths ? 6 : (depth > 4 ? 4 : (depth > 2 ? 5 : ((k > 4 || bnd) ? PGQ_MEET3_WAVES_PACKED : PGQ_MEET3_WAVES)));
 }
+// which k_meet3 / k_meet3w instantiations are built (the launch dispatch excludes the others): the path flow walks the 32-bit
+// lists at the standard depth alone, and K = 5 only exists beyond 2^21 vertices, where the filter folds the high id bits in
+constexpr bool meet3_built(bool paths, bool bigv, int depth, int k) { return paths ? (k == 4 && depth == PGQ_MEET3_DEPTH) : (k != 5 || bigv); }
 constexpr int kMeet3RowsMax = 8; // most rows a k_meet3 wavefront takes at once (option meet_rows_per_wave: 1, 2, 4 or 8)
 // k_meet3's static schedule, a pure function of (n, R = 1 << shift, T = tail): the first max(0, n - T) rows, rounded down to
 // a multiple of R, go R consecutive rows to a group; every row behind them is a group of its own, in row order behind the
@@ -190,6 +194,30 @@ __device__ __forceinline__ void queue_push(const MeetQueue &q, u32 row, const Me
 }
 // position of job j of a (possibly two-ended) queue with nf rows at the front
 __device__ __forceinline__ u32 queue_pos(const MeetQueue &q, u32 j, u32 nf) { return j < nf ? j : q.cap - 1u - (j - nf); }
+// A queue entry as the kernel that takes the row up holds it: wave-uniform, in scalar registers.
+struct MeetRow {
+	u32 row, flags, s, d;
+	int so, degS, di, degD;
+	u32 workS, workD;
+	// the entry that hands the row on to the next stage
+	__device__ __forceinline__ MeetEntry entry(u32 new_flags) const {
+		return { row, new_flags, s, d, (u32)so, (u32)degS, (u32)di, (u32)degD, workS, workD, 0u, 0u };
+	}
+};
+// everything the stage before knew about the row at queue position `pos`, in three 16-byte loads (the queue is a few tens
+// of KB written moments ago)
+__device__ __forceinline__ MeetRow load_row(const MeetQueue &q, u32 pos) {
+	const uint4 *ep = reinterpret_cast<const uint4 *>(q.ent + pos);
+	const uint4 e0 = ep[0], e1 = ep[1], e2 = ep[2];
+	auto uni = [](u32 x) { return __builtin_amdgcn_readfirstlane((int)x); };
+	MeetRow r;
+	r.workS = (u32)uni(e2.x), r.workD = (u32)uni(e2.y);
+	r.row = (u32)uni(e0.x), r.flags = (u32)uni(e0.y);
+	r.s = (u32)uni(e0.z), r.d = (u32)uni(e0.w);
+	r.so = uni(e1.x), r.degS = uni(e1.y);
+	r.di = uni(e1.z), r.degD = uni(e1.w);
+	return r;
+}
 // Every workgroup of a stage kernel ends here (all its threads).  fin == nullptr: not the chain's last kernel.  The last
 // workgroup to arrive sums the statistic slots, writes the host block (coherent pinned memory: visible to the host once
 // the stream has drained) and leaves the device block zeroed.
@@ -276,6 +304,21 @@ __device__ __forceinline__ void meet_add_stats(MeetCounters *mc, int stage, unsi
 	if (entries) atomicAdd(&mc->entries[base + blockIdx.x % cnt], entries);
 	if (vertices) atomicAdd(&mc->vertices[base + blockIdx.x % cnt], vertices);
 	if (walked) atomicAdd(&mc->walked[base + blockIdx.x % cnt], walked);
+}
+// How a multi-wavefront stage kernel (stage 1: the bit-map kernels, 2: k_bibfs) ends, all its threads: the wavefronts' counts
+// are folded in LDS into the workgroup's one pair of atomics, then meet_finalize.  entries, vertices: wave-uniform, what this
+// wavefront counted (a count that one thread keeps is zero in the other wavefronts).
+__device__ __forceinline__ void meet_stage_end(MeetDevBlock *db, MeetHostBlock *fin, int stage, unsigned long long entries, u32 vertices) {
+	__shared__ unsigned long long s_stat[2];
+	const int tid = threadIdx.x, lane = tid & 63;
+	__syncthreads();
+	if (tid < 2) s_stat[tid] = 0;
+	__syncthreads();
+	if (lane == 0 && entries) atomicAdd(&s_stat[0], entries);
+	if (lane == 0 && vertices) atomicAdd(&s_stat[1], (unsigned long long)vertices);
+	__syncthreads();
+	if (tid == 0) meet_add_stats(&db->m, stage, s_stat[0], s_stat[1]);
+	meet_finalize(db, fin);
 }
 
 } // namespace pgq
@@ -803,12 +846,12 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
                                                 MeetPath *__restrict__ rec_rows, int64_t cap, int bm_words,
                                                 MeetDevBlock *__restrict__ db, u32 *__restrict__ gmaps, MeetQueue qout,
                                                 MeetHostBlock *__restrict__ fin, int bound) {
-	extern __shared__ u32 s_map[]; // bm_words: one bit per vertex (GM: the map is this workgroup's slice of `gmaps`)
+	static_assert(PATHS, "distance-only rows take k_meet4d");
+	extern __shared__ __attribute__((aligned(16))) u32 s_map[]; // bm_words: one bit per vertex (GM: the map is this workgroup's slice of `gmaps`)
 	const int64_t n = (int64_t)*qin.count; // rows left open by the kernel before (counted on the device: no host round trip)
 	const int64_t *const src = qin.src, *const dst = qin.dst;
 	const u32 *const didx = qin.idx;
-	MeetCounters *const mc = &db->m;
-	u32 *const gmap = GM ? gmaps + (size_t)blockIdx.x * bm_words : nullptr;
+	const VertexMap<GM> map { GM ? gmaps + (size_t)blockIdx.x * bm_words : s_map, bm_words };
 	__shared__ unsigned long long s_best;
 	__shared__ __attribute__((aligned(16))) unsigned char s_win[16][64];
 	const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
@@ -816,29 +859,6 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 	win[lane] = 0;
 	unsigned long long entries = 0;
 	u32 vertices = 0;
-	// GM: bits are set by L2 atomics, so they are read with device-scope atomic loads (a plain load may hit a stale L1 line)
-	auto bit = [&](u32 x) {
-		const u32 w = GM ? __hip_atomic_load(&gmap[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s_map[x >> 5];
-		return (w >> (x & 31)) & 1u;
-	};
-	auto mark = [&](u32 x) {
-		if constexpr (GM) {
-			// look first: on a skewed graph most entries of a two-hop walk are the same few hubs, and read-modify-writes of
-			// one word serialise in the L2 (R-MAT-22: a 200,000-entry marking walk took 270 us) — a set bit needs no atomic
-			const u32 w = __hip_atomic_load(&gmap[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			if (!((w >> (x & 31)) & 1u)) atomicOr(&gmap[x >> 5], 1u << (x & 31));
-		} else {
-			atomicOr(&s_map[x >> 5], 1u << (x & 31));
-		}
-	};
-	auto clear_map = [&]() {
-		if constexpr (GM) {
-			uint4 *m4 = reinterpret_cast<uint4 *>(gmap); // bm_words is a multiple of 4, slices are 16-byte aligned
-			for (int k = tid; k < bm_words / 4; k += 1024) m4[k] = make_uint4(0, 0, 0, 0);
-		} else {
-			for (int k = tid; k < bm_words; k += 1024) s_map[k] = 0;
-		}
-	};
 	for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
 		__syncthreads(); // the previous row's flags and map are no longer read
 		const int64_t s = src[i], d = dst[i]; // rows left open by k_meet3: ids in range, src != dst, both have edges
@@ -858,7 +878,7 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 			const MeetEntry e = { row, 0u, (u32)s, (u32)d, (u32)so, (u32)degS, (u32)di, (u32)degD, (u32)work_f, (u32)work_b, 0u, 0u };
 			queue_push(qout, row, e);
 		};
-		clear_map();
+		map.template clear<1024>(tid);
 		if (tid == 0) s_best = ~0ull;
 		__syncthreads();
 		// the smallest vertex of N_in(dst) whose bit is set (distance 2: the middle vertex; distance 3: the second one)
@@ -866,26 +886,26 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 			u32 m = kMeetEmpty;
 			for (int p = tid; p < degD; p += 1024) {
 				const u32 u = (u32)radj[di + p];
-				if (bit(u)) m = min(m, u);
+				if (map.test(u)) m = min(m, u);
 			}
 			if (m != kMeetEmpty) atomicMin(&s_best, (unsigned long long)m);
 		};
 		// PATHS: first inner vertex = smallest in-neighbour of `v` that src points at.  The map is rebuilt as N_out(src).
 		auto first_inner_vertex = [&](u32 v) -> u32 {
 			__syncthreads();
-			clear_map();
+			map.template clear<1024>(tid);
 			if (tid == 0) s_best = ~0ull;
 			__syncthreads();
 			for (int p = tid; p < degS; p += 1024) {
 				const u32 x = (u32)adj[so + p];
-				mark(x);
+				map.mark(x);
 			}
 			__syncthreads();
 			u32 m = kMeetEmpty;
 			const int vb = (int)roff[v], ve = (int)roff[v + 1];
 			for (int p = vb + tid; p < ve; p += 1024) {
 				const u32 y = (u32)radj[p];
-				if (bit(y)) m = min(m, y);
+				if (map.test(y)) m = min(m, y);
 			}
 			if (m != kMeetEmpty) atomicMin(&s_best, (unsigned long long)m);
 			__syncthreads();
@@ -897,9 +917,9 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 		}
 		if (!known4) {
 			// B = N_out(src)
-			for (int p = tid; p < degS; p += 1024) mark((u32)adj[so + p]);
+			for (int p = tid; p < degS; p += 1024) map.mark((u32)adj[so + p]);
 			__syncthreads();
-			if (bit((u32)d)) { // dst in N_out(src)
+			if (map.test((u32)d)) { // dst in N_out(src)
 				if (tid == 0) out_rows[row] = (!BND || bound >= 1) ? 1 : -1;
 				continue;
 			}
@@ -950,10 +970,10 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 			    [&](const int4 &v, bool ok, u32 ev) {
 				    last = ev; // lanes past the round's end carry the last list's vertex: not smaller than any real one
 				    if (ok) {
-					    if (bit((u32)v.x)) best = min(best, (unsigned long long)ev << 32 | (u32)v.x);
-					    if (bit((u32)v.y)) best = min(best, (unsigned long long)ev << 32 | (u32)v.y);
-					    if (bit((u32)v.z)) best = min(best, (unsigned long long)ev << 32 | (u32)v.z);
-					    if (bit((u32)v.w)) best = min(best, (unsigned long long)ev << 32 | (u32)v.w);
+					    if (map.test((u32)v.x)) best = min(best, (unsigned long long)ev << 32 | (u32)v.x);
+					    if (map.test((u32)v.y)) best = min(best, (unsigned long long)ev << 32 | (u32)v.y);
+					    if (map.test((u32)v.z)) best = min(best, (unsigned long long)ev << 32 | (u32)v.z);
+					    if (map.test((u32)v.w)) best = min(best, (unsigned long long)ev << 32 | (u32)v.w);
 				    }
 			    },
 			    [&]() {
@@ -1000,12 +1020,7 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 			int resume = 0;
 			const unsigned long long e2 = seg_walk<2, false>(
 			    fdesc + so, degS, wib, 16, padj, win, false, make_uint4(0, 0, 0, 0), ~0ull, capped, resume,
-			    [&](const int4 &v, bool, u32) { // padding and re-read groups repeat real entries: a mark does not mind
-				    mark((u32)v.x);
-				    mark((u32)v.y);
-				    mark((u32)v.z);
-				    mark((u32)v.w);
-			    },
+			    [&](const int4 &v, bool, u32) { map.mark4(v); },
 			    []() { return false; });
 			if (lane == 0) entries += e2;
 		}
@@ -1032,16 +1047,8 @@ __global__ __launch_bounds__(1024) void k_meet4(MeetQueue qin, int64_t V, const 
 			else leave_open();
 		}
 	}
-	__shared__ unsigned long long s_stat[2];
-	__syncthreads();
-	if (tid < 2) s_stat[tid] = 0;
-	__syncthreads();
 	for (int o = 32; o > 0; o >>= 1) entries += __shfl_xor(entries, o);
-	if (lane == 0 && entries) atomicAdd(&s_stat[0], entries);
-	if (tid == 0 && vertices) atomicAdd(&s_stat[1], (unsigned long long)vertices);
-	__syncthreads();
-	if (tid == 0) meet_add_stats(mc, 1, s_stat[0], s_stat[1]);
-	meet_finalize(db, fin);
+	meet_stage_end(db, fin, 1, entries, vertices);
 }
 
 // ---- distance only: k_meet4d -------------------------------------------------------------------------------------------
@@ -1070,7 +1077,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 	// rows the stage before left open (counted on the device: no host round trip): nf from the front of its queue (the
 	// long ones), the rest from the back
 	const u32 nf = *qin.count, n = nf + (qin.count_back ? *qin.count_back : 0u);
-	u32 *const gmap = GM ? gmaps + (size_t)blockIdx.x * bm_words : nullptr;
+	const VertexMap<GM> map { GM ? gmaps + (size_t)blockIdx.x * bm_words : s_map, bm_words };
 	__shared__ int s_flag;
 	__shared__ int s_capped;
 	__shared__ u32 s_job;
@@ -1080,29 +1087,6 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 	win[lane] = 0;
 	unsigned long long entries = 0; // wave-uniform: this wavefront's share
 	u32 vertices = 0;               // wave-uniform (wavefront 0 counts)
-	auto bit = [&](u32 x) {
-		const u32 w = GM ? __hip_atomic_load(&gmap[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s_map[x >> 5];
-		return (w >> (x & 31)) & 1u;
-	};
-	auto mark = [&](u32 x) {
-		if constexpr (GM) {
-			// look first: on a skewed graph most entries of a two-hop walk are the same few hubs, and read-modify-writes of
-			// one word serialise in the L2 (R-MAT-22: a 200,000-entry marking walk took 270 us) — a set bit needs no atomic
-			const u32 w = __hip_atomic_load(&gmap[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			if (!((w >> (x & 31)) & 1u)) atomicOr(&gmap[x >> 5], 1u << (x & 31));
-		} else {
-			atomicOr(&s_map[x >> 5], 1u << (x & 31));
-		}
-	};
-	auto clear_map = [&]() {
-		if constexpr (GM) {
-			uint4 *m4 = reinterpret_cast<uint4 *>(gmap);
-			for (int k = tid; k < bm_words / 4; k += kM4Threads) m4[k] = make_uint4(0, 0, 0, 0);
-		} else {
-			uint4_alias *m4 = reinterpret_cast<uint4_alias *>(s_map);
-			for (int k = tid; k < bm_words / 4; k += kM4Threads) m4[k] = make_uint4(0, 0, 0, 0);
-		}
-	};
 	auto flag_set = [&]() { return *(volatile int *)&s_flag != 0; };
 	// every wavefront reads the flag between two barriers, so that none of them can still be reading it when a later
 	// phase sets it again (a wavefront delayed between the barrier and its read would otherwise take another branch)
@@ -1119,7 +1103,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 		int resume = 0;
 		const unsigned long long e2 = seg_walk<PGQ_MEET4_DEPTH, false>(
 		    list, list_n, wib, PGQ_MEET4_WAVES, xp, win, have_first, first, (unsigned long long)limit / PGQ_MEET4_WAVES, capped, resume,
-		    [&](const int4 &v, bool, u32) { f |= (bit((u32)v.x) | bit((u32)v.y) | bit((u32)v.z) | bit((u32)v.w)) != 0; },
+		    [&](const int4 &v, bool, u32) { f |= map.any4(v) != 0; },
 		    [&]() {
 			    if (__any(f)) s_flag = 1;
 			    return flag_set();
@@ -1133,12 +1117,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 		int resume = 0;
 		const unsigned long long e2 = seg_walk<PGQ_MEET4_MARK_DEPTH, false>(
 		    list, list_n, wib, PGQ_MEET4_WAVES, xp, win, true, first, (unsigned long long)cap / PGQ_MEET4_WAVES, capped, resume,
-		    [&](const int4 &v, bool, u32) {
-			    mark((u32)v.x);
-			    mark((u32)v.y);
-			    mark((u32)v.z);
-			    mark((u32)v.w);
-		    },
+		    [&](const int4 &v, bool, u32) { map.mark4(v); },
 		    []() { return false; });
 		entries += e2;
 		if (capped) s_capped = 1;
@@ -1179,16 +1158,11 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 	unsigned long long n_batch_rows = 0, n_batch_miss = 0, t_batch_max = 0; // workgroup-uniform
 	// one wavefront, one proven-far row (queue job `bjob`); true: settled (distance 4 written)
 	auto batch_row = [&](u32 bjob) {
-		const uint4 *ep = reinterpret_cast<const uint4 *>(qin.ent + queue_pos(qin, bjob, nf));
-		const uint4 e0 = ep[0], e1 = ep[1], e2w = ep[2];
-		const u32 workS = (u32)__builtin_amdgcn_readfirstlane((int)e2w.x), workD = (u32)__builtin_amdgcn_readfirstlane((int)e2w.y);
-		const u32 row = (u32)__builtin_amdgcn_readfirstlane((int)e0.x), flags = (u32)__builtin_amdgcn_readfirstlane((int)e0.y);
-		const int so = __builtin_amdgcn_readfirstlane((int)e1.x), degS = __builtin_amdgcn_readfirstlane((int)e1.y);
-		const int di = __builtin_amdgcn_readfirstlane((int)e1.z), degD = __builtin_amdgcn_readfirstlane((int)e1.w);
-		if (!(flags & kEntKnown4) || degS <= 0 || degD <= 0) return false; // (only proven rows are queued from the back; an empty list: the full procedure says what that means)
-		const bool fwd = workS <= workD; // the set side: the endpoint with the smaller two-hop walk, as below
-		const uint4 *set_list = fwd ? fdesc + so : rdesc + di, *test_list = fwd ? rdesc + di : fdesc + so;
-		const int set_n = fwd ? degS : degD, test_n = fwd ? degD : degS;
+		const MeetRow r = load_row(qin, queue_pos(qin, bjob, nf));
+		if (!(r.flags & kEntKnown4) || r.degS <= 0 || r.degD <= 0) return false; // (only proven rows are queued from the back; an empty list: the full procedure says what that means)
+		const bool fwd = r.workS <= r.workD; // the set side: the endpoint with the smaller two-hop walk, as below
+		const uint4 *set_list = fwd ? fdesc + r.so : rdesc + r.di, *test_list = fwd ? rdesc + r.di : fdesc + r.so;
+		const int set_n = fwd ? r.degS : r.degD, test_n = fwd ? r.degD : r.degS;
 		uint4 d_set = make_uint4(0, 0, 0, 0), d_test = make_uint4(0, 0, 0, 0); // both endpoints' first descriptors in one round trip
 		if (lane < set_n) d_set = set_list[lane];
 		if (lane < test_n) d_test = test_list[lane];
@@ -1237,7 +1211,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 		descs += (u32)((found || capped) ? min(test_n, resume + 128) : test_n);
 		entries += e2;
 		vertices += descs;
-		if (found && lane == 0) out_rows[row] = 4;
+		if (found && lane == 0) out_rows[r.row] = 4;
 		return found;
 	};
 	u32 job = blockIdx.x, miss_k = 0, miss_n = 0;
@@ -1274,24 +1248,16 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 		if (from_miss) job = s_miss[miss_k++];
 		else if (tid == 0) next_job = gridDim.x + atomicAdd(&db->next_job, 1u);
 		const unsigned long long t_row = TRACE ? wall_clock64() : 0ull;
-		// the row's queue entry: everything the stage before knew about it, in three 16-byte loads (the queue is a few
-		// tens of KB written moments ago), wave-uniform -> scalar registers
-		const uint4 *ep = reinterpret_cast<const uint4 *>(qin.ent + queue_pos(qin, job, nf));
-		const uint4 e0 = ep[0], e1 = ep[1], e2w = ep[2];
-		const u32 workS = (u32)__builtin_amdgcn_readfirstlane((int)e2w.x), workD = (u32)__builtin_amdgcn_readfirstlane((int)e2w.y);
-		const u32 row = (u32)__builtin_amdgcn_readfirstlane((int)e0.x), flags = (u32)__builtin_amdgcn_readfirstlane((int)e0.y);
-		const u32 es = (u32)__builtin_amdgcn_readfirstlane((int)e0.z), ed = (u32)__builtin_amdgcn_readfirstlane((int)e0.w);
-		const int so = __builtin_amdgcn_readfirstlane((int)e1.x), degS = __builtin_amdgcn_readfirstlane((int)e1.y);
-		const int di = __builtin_amdgcn_readfirstlane((int)e1.z), degD = __builtin_amdgcn_readfirstlane((int)e1.w);
-		const bool known4 = (flags & kEntKnown4) != 0, known3 = (flags & kEntKnown3) != 0;
-		clear_map();
+		const MeetRow r = load_row(qin, queue_pos(qin, job, nf)); // wave-uniform -> scalar registers
+		const bool known4 = (r.flags & kEntKnown4) != 0, known3 = (r.flags & kEntKnown3) != 0;
+		map.template clear<kM4Threads>(tid);
 		if (tid == 0) {
 			s_flag = 0;
 			s_capped = 0;
 		}
 		__syncthreads();
-		if (wib == 0) vertices += (u32)(degS + degD); // both one-hop lists as descriptors
-		bool walk_fwd = workS <= workD; // which endpoint's two-hop neighbourhood is walked / marked: the smaller one
+		if (wib == 0) vertices += (u32)(r.degS + r.degD); // both one-hop lists as descriptors
+		bool walk_fwd = r.workS <= r.workD; // which endpoint's two-hop neighbourhood is walked / marked: the smaller one
 		int64_t result = kMeetOpen;   // wave-uniform
 		int resume3 = 0;
 		bool do3 = false, do4 = true;
@@ -1302,22 +1268,22 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 			// register set (512 ids); the bit map takes any list, so the side is chosen again by the walks' sizes — R-MAT-22:
 			// a row that had followed k_meet3 into a hub's two-hop neighbourhood walked its full million-entry allowance,
 			// 270 us for one row — and the walk is taken up where k_meet3 stopped only if the side is the same
-			walk_fwd = workS <= workD;
-			resume3 = walk_fwd == ((flags & kEntFwd) != 0) ? (int)(flags >> kEntResumeShift) : 0;
+			walk_fwd = r.workS <= r.workD;
+			resume3 = walk_fwd == ((r.flags & kEntFwd) != 0) ? (int)(r.flags >> kEntResumeShift) : 0;
 			if (BND && bound < 3) { // (k_meet3 starts no walk under such a bound: no row arrives cut)
 				result = -1;
 				do4 = false;
 			} else {
-				const int32_t *set_list = walk_fwd ? radj + di : adj + so;
-				const int set_n = walk_fwd ? degD : degS;
-				for (int p = tid; p < set_n; p += kM4Threads) mark((u32)set_list[p]);
+				const int32_t *set_list = walk_fwd ? radj + r.di : adj + r.so;
+				const int set_n = walk_fwd ? r.degD : r.degS;
+				for (int p = tid; p < set_n; p += kM4Threads) map.mark((u32)set_list[p]);
 				if (wib == 0) entries += (unsigned long long)set_n;
 				__syncthreads();
 				do3 = true;
 			}
 		} else if (!known4) {
 			bool hit = false;
-			for (int p = tid; p < degS; p += kM4Threads) hit |= (u32)adj[so + p] == ed;
+			for (int p = tid; p < r.degS; p += kM4Threads) hit |= (u32)adj[r.so + p] == r.d;
 			if (__any(hit) && lane == 0) s_flag = 1;
 			if (flag_snapshot()) { // dst in N_out(src)
 				result = (!BND || bound >= 1) ? 1 : -1;
@@ -1326,20 +1292,20 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 				result = -1;
 				do4 = false;
 			} else {
-				const int64_t work_f = (int64_t)workS, work_b = (int64_t)workD; // the two-hop walks' sizes came with the row
+				const int64_t work_f = (int64_t)r.workS, work_b = (int64_t)r.workD; // the two-hop walks' sizes came with the row
 				walk_fwd = work_f <= work_b;
 				{ // the set: one-hop list of the endpoint that is not walked
-					const int32_t *set_list = walk_fwd ? radj + di : adj + so;
-					const int set_n = walk_fwd ? degD : degS;
-					for (int p = tid; p < set_n; p += kM4Threads) mark((u32)set_list[p]);
+					const int32_t *set_list = walk_fwd ? radj + r.di : adj + r.so;
+					const int set_n = walk_fwd ? r.degD : r.degS;
+					for (int p = tid; p < set_n; p += kM4Threads) map.mark((u32)set_list[p]);
 				}
 				__syncthreads();
-				const int32_t *wl = walk_fwd ? adj + so : radj + di;
-				const int wn = walk_fwd ? degS : degD;
-				if (wib == 0) entries += (unsigned long long)(degS + degD);
+				const int32_t *wl = walk_fwd ? adj + r.so : radj + r.di;
+				const int wn = walk_fwd ? r.degS : r.degD;
+				if (wib == 0) entries += (unsigned long long)(r.degS + r.degD);
 				{ // distance 2: a common neighbour
 					bool f = false;
-					for (int p = tid; p < wn; p += kM4Threads) f |= bit((u32)wl[p]) != 0;
+					for (int p = tid; p < wn; p += kM4Threads) f |= map.test((u32)wl[p]) != 0;
 					if (__any(f) && lane == 0) s_flag = 1;
 				}
 				if (flag_snapshot()) {
@@ -1358,8 +1324,8 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 		}
 		if (do3) {
 			// distance 3: the cheaper two-hop walk against the other endpoint's one-hop set
-			const uint4 *wl = (walk_fwd ? fdesc + so : rdesc + di) + resume3;
-			const int wn = (walk_fwd ? degS : degD) - resume3;
+			const uint4 *wl = (walk_fwd ? fdesc + r.so : rdesc + r.di) + resume3;
+			const int wn = (walk_fwd ? r.degS : r.degD) - resume3;
 			walk_test(wl, wn, walk_fwd ? padj : rpadj, false, make_uint4(0, 0, 0, 0), cap);
 			if (flag_snapshot()) {
 				result = 3;
@@ -1371,15 +1337,15 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 					result = -1;
 					do4 = false;
 				}
-				if (do4) clear_map(); // every wavefront is past its reads of the map (barriers above)
+				if (do4) map.template clear<kM4Threads>(tid); // every wavefront is past its reads of the map (barriers above)
 				__syncthreads();
 			}
 		}
 		if (do4) {
 			// distance 4: two-hop set of the walked endpoint, two-hop walk of the other one.  Both walks' first
 			// descriptors are requested together (one round trip instead of two)
-			const uint4 *mark_list = walk_fwd ? fdesc + so : rdesc + di, *test_list = walk_fwd ? rdesc + di : fdesc + so;
-			const int mark_n = walk_fwd ? degS : degD, test_n = walk_fwd ? degD : degS;
+			const uint4 *mark_list = walk_fwd ? fdesc + r.so : rdesc + r.di, *test_list = walk_fwd ? rdesc + r.di : fdesc + r.so;
+			const int mark_n = walk_fwd ? r.degS : r.degD, test_n = walk_fwd ? r.degD : r.degS;
 			uint4 d_mark = make_uint4(0, 0, 0, 0), d_test = make_uint4(0, 0, 0, 0);
 			if (lane < mark_n) d_mark = mark_list[lane]; // every wavefront holds the round's 64 descriptors (it takes every 16th request)
 			if (lane < test_n) d_test = test_list[lane];
@@ -1402,12 +1368,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 				if (wib < H) {
 					const unsigned long long e2 = seg_walk<1, false>(
 					    mark_list, min(mark_n, 64), wib, kOneShot, walk_fwd ? padj : rpadj, win, true, d_mark, 0ull, capped, resume,
-					    [&](const int4 &v, bool, u32) {
-						    mark((u32)v.x);
-						    mark((u32)v.y);
-						    mark((u32)v.z);
-						    mark((u32)v.w);
-					    },
+					    [&](const int4 &v, bool, u32) { map.mark4(v); },
 					    []() { return true; });
 					entries += e2;
 				} else {
@@ -1421,7 +1382,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 					entries += e2;
 				}
 				__syncthreads();
-				if (have && (bit((u32)held.x) | bit((u32)held.y) | bit((u32)held.z) | bit((u32)held.w))) s_flag = 1;
+				if (have && map.any4(held)) s_flag = 1;
 				f4 = flag_snapshot();
 			}
 			if (!f4) {
@@ -1439,7 +1400,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 					int resume = 0;
 					const unsigned long long e2 = seg_walk<1, false>(
 					    test_list, min(test_n, 64), H + wib, kOneShot, walk_fwd ? rpadj : padj, win, true, d_test, 0ull, capped, resume,
-					    [&](const int4 &v, bool, u32) { f |= (bit((u32)v.x) | bit((u32)v.y) | bit((u32)v.z) | bit((u32)v.w)) != 0; },
+					    [&](const int4 &v, bool, u32) { f |= map.any4(v) != 0; },
 					    []() { return true; });
 					entries += e2;
 					if (__any(f)) s_flag = 1;
@@ -1458,10 +1419,9 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 			else if (BND && bound <= 4 && !s_capped) result = -1; // both walks ran to their ends: distance >= 5
 		}
 		if (tid == 0) {
-			out_rows[row] = result;
+			out_rows[r.row] = result;
 			if (result == kMeetOpen) {
-				const MeetEntry e = { row, 0u, es, ed, (u32)so, (u32)degS, (u32)di, (u32)degD, workS, workD, 0u, 0u };
-				queue_push(qout, row, e);
+				queue_push(qout, r.row, r.entry(0u));
 			}
 			if (!from_miss) s_job = next_job;
 		}
@@ -1482,6 +1442,7 @@ __global__ __launch_bounds__(64 * PGQ_MEET4_WAVES, PGQ_MEET4_BLOCKS) void k_meet
 		trace[kMeet4TraceWords * blockIdx.x + 5] = n_batch_miss;
 		trace[kMeet4TraceWords * blockIdx.x + 6] = t_batch_max;
 	}
+	// (meet_stage_end's fold, with the batch pass's count in its last step: the add must stand in front of meet_finalize)
 	__shared__ unsigned long long s_stat[2];
 	__syncthreads();
 	if (tid < 2) s_stat[tid] = 0;
@@ -1523,7 +1484,6 @@ __global__ __launch_bounds__(1024) void k_bibfs(MeetQueue qin, u32 max_rows,
                                                 MeetHostBlock *__restrict__ fin, int bound) {
 	const int64_t *const src = qin.src, *const dst = qin.dst;
 	const u32 *const didx = qin.idx;
-	MeetCounters *const mc = &db->m;
 	extern __shared__ u32 s_map[]; // !GM: both maps, (bm_words + 4) words each; the spare words take the masked lanes' bits
 	// rows still open, counted on the device (no host round trip before this launch); more than a handful: not this
 	// kernel's job, the lane-batched search takes them
@@ -1715,16 +1675,8 @@ __global__ __launch_bounds__(1024) void k_bibfs(MeetQueue qin, u32 max_rows,
 			}
 		}
 	}
-	__shared__ unsigned long long s_stat[2];
-	__syncthreads();
-	if (tid < 2) s_stat[tid] = 0;
-	__syncthreads();
 	for (int o = 32; o > 0; o >>= 1) entries += __shfl_xor(entries, o);
-	if (lane == 0 && entries) atomicAdd(&s_stat[0], entries);
-	if (tid == 0 && vertices) atomicAdd(&s_stat[1], (unsigned long long)vertices);
-	__syncthreads();
-	if (tid == 0) meet_add_stats(mc, 2, s_stat[0], s_stat[1]);
-	meet_finalize(db, fin);
+	meet_stage_end(db, fin, 2, entries, vertices);
 }
 
 // ---- path emission -------------------------------------------------------------------------------------------------
@@ -1914,6 +1866,20 @@ static int check_launch(hipStream_t st, const char *kernel, size_t lds_bytes) {
 	(void)hipStreamSynchronize(st); // what the chain launched before it finishes before the workspace is reused
 	return fail(PGQ_ERR_HIP, std::string(kernel) + " launch with " + std::to_string(lds_bytes) + " B of dynamic LDS failed: " + hipGetErrorString(e));
 }
+// Runtime flags into template arguments: with_flags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), and
+// with_int<4, 5, 6>(k, f) calls f(std::integral_constant<int, k>{}) for the first listed value that equals k.  A launcher
+// holds its launch once, in a generic lambda; the combinations its kernel is not built for are excluded there with
+// `if constexpr`; a launcher that launched nothing (such a combination, or a value with_int does not list) returns no_kernel():
+// a missing kernel is an error, never another kernel.
+template <typename F> static void with_flags(F &&f) { f(); }
+template <typename F, typename... Bools> static void with_flags(F &&f, bool b, Bools... rest) {
+	if (b) with_flags([&](auto... cs) { f(std::true_type {}, cs...); }, rest...);
+	else with_flags([&](auto... cs) { f(std::false_type {}, cs...); }, rest...);
+}
+template <int... Vs, typename F> static bool with_int(int v, F &&f) { // false: v is none of Vs, f was not called
+	return ((v == Vs && (f(std::integral_constant<int, Vs> {}), true)) || ...);
+}
+static int no_kernel(const char *kernel) { return fail(PGQ_ERR_HIP, std::string(kernel) + " is not built for this combination of flags"); }
 
 // debugging aid (option meet_trace): where k_src_ball's time goes
 static int print_ball_trace(const unsigned long long *b_trace, u32 nseg, u32 open) {
@@ -1974,14 +1940,12 @@ static int launch_bibfs(pgq_csr *c, Workspace *ws, const MapPlan &mp, u32 grid, 
 	KernelTimer kt(st, K_BIBFS);
 	if (mp.bi_lds) tstats().s.lds_map_launches[K_BIBFS]++;
 	clear_launch_error();
-#define PGQ_BIBFS(G, B)                                                                                                      \
-	hipLaunchKernelGGL((k_bibfs<G, B>), dim3(grid), dim3(1024), lds, st, qi, rows, c->off, c->adj, c->roff, c->radj, d_out, capb,   \
-	                   mp.bm_words, qcap, db, maps, queues, qo, hb, bound)
-	if (mp.bi_lds && bound >= 0) PGQ_BIBFS(false, true);
-	else if (mp.bi_lds) PGQ_BIBFS(false, false);
-	else if (bound >= 0) PGQ_BIBFS(true, true);
-	else PGQ_BIBFS(true, false);
-#undef PGQ_BIBFS
+	with_flags(
+	    [&](auto gm, auto bnd) {
+		    hipLaunchKernelGGL((k_bibfs<decltype(gm)::value, decltype(bnd)::value>), dim3(grid), dim3(1024), lds, st, qi, rows, c->off, c->adj, c->roff,
+		                       c->radj, d_out, capb, mp.bm_words, qcap, db, maps, queues, qo, hb, bound);
+	    },
+	    !mp.bi_lds, bound >= 0);
 	PGQ_TRY(check_launch(st, "k_bibfs", lds));
 	kt.stop();
 	return PGQ_OK;
@@ -2000,7 +1964,7 @@ public:
 		// record / wait pair costs what the 12 us kernel does, and the polled word must be spread over many lines)
 		if (decide)
 			hipLaunchKernelGGL(k_meet_decide, dim3(1), dim3(1024), 0, st, n, a.d_src, c->V, a.meet_bytes, a.edge_bytes, &db->dec, (u32 *)nullptr, (const u32 *)&db->ball.go);
-		launch_meet3();
+		PGQ_TRY(launch_meet3());
 		if (run4) PGQ_TRY(launch_bitmap());
 		if (run_bi) PGQ_TRY(launch_bibfs_stage());
 		else set_open(ws, q[open_stage]);
@@ -2182,17 +2146,19 @@ private:
 		                   ws->ball_segs.as<u32>(), db, seg_rows);
 		const int64_t capb = std::max(1, opt.ball_cap), tcap = std::max(1, opt.ball_test_cap);
 		if (b_trace) PGQ_HIP_TRY(hipMemsetAsync(b_trace, 0, 256, st));
-#define PGQ_BALL(G, T, ...)                                                                                                  \
-	hipLaunchKernelGGL((k_src_ball<G, T, ##__VA_ARGS__>), dim3(grid_b), dim3(kBallRows), lds, st, n, a.d_src, a.d_dst, c->V, c->off, c->roff, c->fdesc, \
-	                   c->rdesc, c->padj, c->rpadj, c->rseg, opt.ball_head_mb > 0 ? c->rhead : (const uint4 *)nullptr, ws->ball_segs.as<u32>(), a.d_out, capb, tcap, \
-	                   mp.bm_words, db, gmaps, q[0], rule, b_trace, seg_rows, bound)
-		if (bnd && mp.ball_lds) PGQ_BALL(false, false, true);
-		else if (bnd) PGQ_BALL(true, false, true);
-		else if (mp.ball_lds && b_trace) PGQ_BALL(false, true);
-		else if (mp.ball_lds) PGQ_BALL(false, false);
-		else if (b_trace) PGQ_BALL(true, true);
-		else PGQ_BALL(true, false);
-#undef PGQ_BALL
+		bool launched = false;
+		with_flags(
+		    [&](auto gm, auto tr, auto bn) {
+			    constexpr bool GM = decltype(gm)::value, TRACE = decltype(tr)::value, BND = decltype(bn)::value;
+			    if constexpr (!(TRACE && BND)) { // the bounded kernels carry no trace (reserve() hands out no trace buffer under a bound)
+				    hipLaunchKernelGGL((k_src_ball<GM, TRACE, BND>), dim3(grid_b), dim3(kBallRows), lds, st, n, a.d_src, a.d_dst, c->V, c->off, c->roff,
+				                       c->fdesc, c->rdesc, c->padj, c->rpadj, c->rseg, opt.ball_head_mb > 0 ? c->rhead : (const uint4 *)nullptr,
+				                       ws->ball_segs.as<u32>(), a.d_out, capb, tcap, mp.bm_words, db, gmaps, q[0], rule, b_trace, seg_rows, bound);
+				    launched = true;
+			    }
+		    },
+		    !mp.ball_lds, b_trace != nullptr, bnd);
+		if (!launched) return no_kernel("k_src_ball");
 		PGQ_TRY(check_launch(st, "k_src_ball", lds));
 		kt.stop();
 		return PGQ_OK;
@@ -2228,7 +2194,7 @@ private:
 		r->n_open = h.ball_open;
 		return PGQ_OK;
 	}
-	void launch_meet3() {
+	int launch_meet3() {
 		// calls too small to fill the chip are bound by the longest row, not by bandwidth: more requests in flight shorten
 		// every row (meet_cap_small is a cap of their own; 4096 .. 16384 measured within 3 % of each other: it ships equal
 		// to meet_cap)
@@ -2255,62 +2221,52 @@ private:
 		const u32 *d_go = decide ? &db->dec.go : nullptr; // the gate's verdict on the device
 		// the hop-count walks read the packed lists (pack_k ids per group) when the upload built them; the path flow the
 		// 32-bit ones.  K = 5 only exists beyond 2^21 vertices: always BIGV
-#define PGQ_MEET3K(P, B, D, K, XF, XR)                                                                                   \
-	do {                                                                                                                 \
-		if (bnd) PGQ_MEET3KB(P, B, D, K, XF, XR, true);                                                                 \
-		else PGQ_MEET3KB(P, B, D, K, XF, XR, false);                                                                    \
-	} while (0)
-#define PGQ_MEET3KB(P, B, D, K, XF, XR, BN)                                                                              \
-	hipLaunchKernelGGL((k_meet3<P, B, D, K, BN>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, \
-	                   c->radj, c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound, c->pack_order != 0, \
-	                   rows_shift, tail_rows)
-#define PGQ_MEET3(P, B, D)                                                                                               \
-	do {                                                                                                                 \
-		if (!P && pk == 6) PGQ_MEET3K(false, B, D, 6, c->ppadj, c->prpadj);                                            \
-		else if (!P && pk == 5) PGQ_MEET3K(false, true, D, 5, c->ppadj, c->prpadj);                                    \
-		else PGQ_MEET3K(P, B, D, 4, c->padj, c->rpadj);                                                                 \
-	} while (0)
-		if (paths) {
-			if (bigv) PGQ_MEET3K(true, true, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
-			else PGQ_MEET3K(true, false, PGQ_MEET3_DEPTH, 4, c->padj, c->rpadj);
-		} else if (small_call && n <= (int64_t)opt.meet_wide_rows && (opt.meet_wide_rows_always || (double)c->E * 4.0 > 256e6)) {
+		const int k_ids = paths ? 4 : (pk == 6 ? 6 : (pk == 5 ? 5 : 4));
+		const bool big = bigv || k_ids == 5;
+		const int32_t *xf = k_ids > 4 ? c->ppadj : c->padj, *xr = k_ids > 4 ? c->prpadj : c->rpadj;
+		const bool split = c->pack_order != 0;
+		bool launched = false;
+		// (small_call is defined above as !paths && ...: no path call gets here as a small or wide one)
+		if (small_call && n <= (int64_t)opt.meet_wide_rows && (opt.meet_wide_rows_always || (double)c->E * 4.0 > 256e6)) {
 			// chunk-sized calls on a graph whose adjacency does not fit the Infinity Cache (a list request is a DRAM round trip,
 			// ~3.5 us under load): several wavefronts per row (k_meet3w: 97 VGPRs, four wavefronts per SIMD = 4096 on the chip) —
 			// four while all rows are resident at once, else two.  Measured: R-MAT-22 x 1024 pairs 49 -> 41 us; the SF100-shaped
 			// graph (160 MB of padded lists, cache resident) 24.1 -> 25.5 us at 1024 rows, 29.1 -> 29.7 at 2048: not taken there
-#define PGQ_MEET3WK(B, W, K, XF, XR)                                                                                      \
-	do {                                                                                                                 \
-		if (bnd) PGQ_MEET3WKB(B, W, K, XF, XR, true);                                                                   \
-		else PGQ_MEET3WKB(B, W, K, XF, XR, false);                                                                      \
-	} while (0)
-#define PGQ_MEET3WKB(B, W, K, XF, XR, BN)                                                                                 \
-	hipLaunchKernelGGL((k_meet3w<B, W, K, BN>), dim3((unsigned)n), dim3(64 * W), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj, c->roff, c->radj, \
-	                   c->fdesc, c->rdesc, XF, XR, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin, bound, c->pack_order != 0)
-#define PGQ_MEET3W(B, W)                                                                                                  \
-	do {                                                                                                                 \
-		if (pk == 6) PGQ_MEET3WK(B, W, 6, c->ppadj, c->prpadj);                                                        \
-		else if (pk == 5) PGQ_MEET3WK(true, W, 5, c->ppadj, c->prpadj);                                                \
-		else PGQ_MEET3WK(B, W, 4, c->padj, c->rpadj);                                                                   \
-	} while (0)
 			const bool four = n * 4 <= (int64_t)ncu * 16;
-			if (bigv && four) PGQ_MEET3W(true, 4);
-			else if (bigv) PGQ_MEET3W(true, 2);
-			else if (four) PGQ_MEET3W(false, 4);
-			else PGQ_MEET3W(false, 2);
-#undef PGQ_MEET3W
-#undef PGQ_MEET3WK
-#undef PGQ_MEET3WKB
-		} else if (small_call) {
-			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH_SMALL);
-			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH_SMALL);
+			auto launch = [&](auto w, auto k, auto b, auto bn) {
+				constexpr int W = decltype(w)::value, K = decltype(k)::value;
+				constexpr bool BIGV = decltype(b)::value, BND = decltype(bn)::value;
+				if constexpr (meet3_built(false, BIGV, PGQ_MEET3_DEPTH_SMALL, K)) {
+					hipLaunchKernelGGL((k_meet3w<BIGV, W, K, BND>), dim3((unsigned)n), dim3(64 * W), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj,
+					                   c->roff, c->radj, c->fdesc, c->rdesc, xf, xr, c->fwork, c->rwork, a.d_out, cap, d_go, db, q[0], fin, bound, split);
+					launched = true;
+				}
+			};
+			with_int<2, 4>(four ? 4 : 2, [&](auto w) {
+				with_int<4, 5, 6>(k_ids, [&](auto k) {
+					with_flags([&](auto b, auto bn) { launch(w, k, b, bn); }, big, bnd);
+				});
+			});
 		} else {
-			if (bigv) PGQ_MEET3(false, true, PGQ_MEET3_DEPTH);
-			else PGQ_MEET3(false, false, PGQ_MEET3_DEPTH);
+			const int depth = small_call ? PGQ_MEET3_DEPTH_SMALL : PGQ_MEET3_DEPTH;
+			auto launch = [&](auto d, auto k, auto p, auto b, auto bn) {
+				constexpr int DEPTH = decltype(d)::value, K = decltype(k)::value;
+				constexpr bool PATHS = decltype(p)::value, BIGV = decltype(b)::value, BND = decltype(bn)::value;
+				if constexpr (meet3_built(PATHS, BIGV, DEPTH, K)) {
+					hipLaunchKernelGGL((k_meet3<PATHS, BIGV, DEPTH, K, BND>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj,
+					                   c->roff, c->radj, c->fdesc, c->rdesc, xf, xr, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound, split,
+					                   rows_shift, tail_rows);
+					launched = true;
+				}
+			};
+			with_int<PGQ_MEET3_DEPTH, PGQ_MEET3_DEPTH_SMALL>(depth, [&](auto d) {
+				with_int<4, 5, 6>(k_ids, [&](auto k) {
+					with_flags([&](auto p, auto b, auto bn) { launch(d, k, p, b, bn); }, paths, big, bnd);
+				});
+			});
 		}
-#undef PGQ_MEET3
-#undef PGQ_MEET3K
-#undef PGQ_MEET3KB
 		kt.stop();
+		return launched ? PGQ_OK : no_kernel("k_meet3");
 	}
 	// k_meet4d (hop counts) or k_meet4<paths> over what k_meet3 queued
 	int launch_bitmap() {
@@ -2323,28 +2279,31 @@ private:
 		KernelTimer kt(st, K_MEET4);
 		if (mp.lds_map) S.lds_map_launches[K_MEET4]++;
 		clear_launch_error();
-#define PGQ_MEET4(G, BN)                                                                                                 \
-	hipLaunchKernelGGL((k_meet4<true, G, BN>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj, c->roff, c->radj, \
-	                   c->fdesc, c->rdesc, c->padj, c->rpadj, a.d_out, rec, cap4, mp.bm_words, db, gmaps, q[1], fin, bound)
-// k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
-// per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
-#define PGQ_MEET4D(G, T) PGQ_MEET4DB(G, T, false)
-#define PGQ_MEET4DB(G, T, BN)                                                                                               \
-	hipLaunchKernelGGL((k_meet4d<G, T, BN>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj, \
-	                   c->rpadj, a.d_out, cap4, (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride, bound, batch)
-		if (paths && bnd && mp.lds_map) PGQ_MEET4(false, true);
-		else if (paths && bnd) PGQ_MEET4(true, true);
-		else if (paths && mp.lds_map) PGQ_MEET4(false, false);
-		else if (paths) PGQ_MEET4(true, false);
-		else if (bnd && mp.lds_map) PGQ_MEET4DB(false, false, true);
-		else if (bnd) PGQ_MEET4DB(true, false, true);
-		else if (mp.lds_map && d_trace) PGQ_MEET4D(false, true);
-		else if (mp.lds_map) PGQ_MEET4D(false, false);
-		else if (d_trace) PGQ_MEET4D(true, true);
-		else PGQ_MEET4D(true, false);
-#undef PGQ_MEET4DB
-#undef PGQ_MEET4D
-#undef PGQ_MEET4
+		bool launched = false;
+		if (paths) {
+			with_flags(
+			    [&](auto gm, auto bn) {
+				    hipLaunchKernelGGL((k_meet4<true, decltype(gm)::value, decltype(bn)::value>), dim3(grid4), dim3(1024), lds, st, q[0], c->V, c->off, c->adj,
+				                       c->roff, c->radj, c->fdesc, c->rdesc, c->padj, c->rpadj, a.d_out, rec, cap4, mp.bm_words, db, gmaps, q[1], fin, bound);
+				    launched = true;
+			    },
+			    !mp.lds_map, bnd);
+		} else {
+			// k_meet4d stays on the 32-bit lists: a variant over the packed ones (K = 6) spilled 21 registers at its 64 and took 61 us
+			// per launch instead of 43 on the SF100-shaped graph (its rows are latency-bound walks; a larger request only overshoots)
+			with_flags(
+			    [&](auto gm, auto tr, auto bn) {
+				    constexpr bool GM = decltype(gm)::value, TRACE = decltype(tr)::value, BND = decltype(bn)::value;
+				    if constexpr (!(TRACE && BND)) { // the bounded kernels carry no trace (reserve() hands out no trace buffer under a bound)
+					    hipLaunchKernelGGL((k_meet4d<GM, TRACE, BND>), dim3(grid4), dim3(kM4Threads), lds, st, q[0], c->adj, c->radj, c->fdesc, c->rdesc, c->padj,
+					                       c->rpadj, a.d_out, cap4,
+					                       (int64_t)std::max(1, opt.meet4_test_cap), mp.bm_words, db, gmaps, q[1], fin, d_trace, ride, bound, batch);
+					    launched = true;
+				    }
+			    },
+			    !mp.lds_map, d_trace != nullptr, bnd);
+		}
+		if (!launched) return no_kernel(paths ? "k_meet4" : "k_meet4d");
 		PGQ_TRY(check_launch(st, paths ? "k_meet4" : "k_meet4d", lds));
 		kt.stop();
 		open_stage = 1;

@@ -389,6 +389,41 @@ template <typename G, typename H> __device__ __forceinline__ void verify_candida
 	}
 }
 
+// ---- the exact set: one bit per vertex ----------------------------------------------------------------------------------
+// The map of a whole workgroup (k_meet4, k_meet4d, k_src_ball): `words` words in LDS, or (GM: V too large for LDS) the
+// workgroup's slice of a global buffer.  words is a multiple of 4 and a slice is 16-byte aligned (MapPlan, pgq_meet.hip).
+template <bool GM> struct VertexMap {
+	u32 *w;
+	int words;
+	// GM: bits are set by L2 atomics, so they are read with device-scope atomic loads (a plain load may hit a stale L1 line)
+	__device__ __forceinline__ u32 word_of(u32 x) const {
+		return GM ? __hip_atomic_load(&w[x >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : w[x >> 5];
+	}
+	__device__ __forceinline__ u32 test(u32 x) const { return (word_of(x) >> (x & 31)) & 1u; }
+	__device__ __forceinline__ u32 any4(const int4 &v) const { return test((u32)v.x) | test((u32)v.y) | test((u32)v.z) | test((u32)v.w); }
+	__device__ __forceinline__ void mark(u32 x) const {
+		if constexpr (GM) {
+			// look first: on a skewed graph most entries of a two-hop walk are the same few hubs, and read-modify-writes of
+			// one word serialise in the L2 (R-MAT-22: a 200,000-entry marking walk took 270 us) — a set bit needs no atomic
+			if (!test(x)) atomicOr(&w[x >> 5], 1u << (x & 31));
+		} else {
+			atomicOr(&w[x >> 5], 1u << (x & 31));
+		}
+	}
+	// (padding and re-read groups of a walk repeat real entries: a mark does not mind)
+	__device__ __forceinline__ void mark4(const int4 &v) const {
+		mark((u32)v.x);
+		mark((u32)v.y);
+		mark((u32)v.z);
+		mark((u32)v.w);
+	}
+	// all THREADS threads of the workgroup, 16 bytes per lane
+	template <int THREADS> __device__ __forceinline__ void clear(int tid) const {
+		uint4_alias *m4 = reinterpret_cast<uint4_alias *>(w);
+		for (int k = tid; k < words / 4; k += THREADS) m4[k] = make_uint4(0, 0, 0, 0);
+	}
+};
+
 // Streams the adjacency segments of list[w], list[w + stride], ... (positions < list_n) and calls f(entry) for every
 // entry until stop() (wave-uniform) says so.  Returns the number of entries requested.
 template <typename F, typename Stop>
