@@ -108,6 +108,10 @@ def load_hip():
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_cheapest_path_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.pgq_cheapest_path_within.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_cheapest_path_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -165,6 +169,8 @@ def load_udf():
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_udf_cheapest_path_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_cheapest_path_length_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64,
                                                       C.c_void_p, C.c_void_p]
     for f in ("pgq_udf_local_clustering_coefficient", "pgq_udf_pagerank", "pgq_udf_weakly_connected_component"):
@@ -456,9 +462,10 @@ class DeviceCSR:
         _check(self.L.pgq_cheapest_path_length_within(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
         return out, unpack_validity(ov, n)
 
-    def cheapest_path(self, src, dst, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, raw=False):
+    def cheapest_path(self, src, dst, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, raw=False, max_hops=None):
         """The cheapest path itself as a list [src, e1, v1, ..., ek, dst] per row (None for NULL rows): hop-minimal among the
-        cheapest paths, shortestpath's tie-breaks (include/pgq_hip.h).  raw=True: offsets, lengths, validity words, child."""
+        cheapest paths, shortestpath's tie-breaks (include/pgq_hip.h).  raw=True: offsets, lengths, validity words, child.
+        max_hops: the cheapest walk of at most that many edges instead (cheapest_path_within)."""
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
         off = np.zeros(n, dtype=np.uint64)
@@ -466,13 +473,22 @@ class DeviceCSR:
         ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
         child = C.c_void_p()
         clen = C.c_uint64()
-        _check(self.L.pgq_cheapest_path(self.h, self.V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child), C.byref(clen)))
+        if max_hops is None:
+            _check(self.L.pgq_cheapest_path(self.h, self.V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child), C.byref(clen)))
+        else:
+            _check(self.L.pgq_cheapest_path_within(self.h, self.V, n, sv, dv, int(max_hops), _p(off), _p(ln), _p(ov),
+                                                   C.byref(child), C.byref(clen)))
         ch = np.zeros(0, dtype=np.int64)
         if clen.value:
             ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
         if raw:
             return off, ln, ov, ch
         return _lists(off, ln, unpack_validity(ov, n), ch)
+
+    def cheapest_path_within(self, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, raw=False):
+        """The cheapest walk of at most max_hops edges per row, as cheapest_path's list: the walk whose cost
+        cheapest_path_length_within returns, not cheapest_path's list with long rows None (include/pgq_hip.h)."""
+        return self.cheapest_path(src, dst, src_valid, dst_valid, src_sel, dst_sel, raw, max_hops=int(max_hops))
 
     # -- bulk form (device pointers; torch tensors supply them) ------------------
     def iterativelength_bulk_ptr(self, n, d_src, d_dst, d_out):
@@ -589,6 +605,14 @@ class DeviceCSR:
         used = C.c_int64(0)
         rc = self.L.pgq_cheapest_path_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), C.c_void_p(d_out_len),
                                                   C.c_void_p(d_out_off), C.c_void_p(d_child), child_cap, C.byref(used))
+        return rc, used.value
+
+    def cheapest_path_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out_len, d_out_off, d_child, child_cap):
+        """(status, elements needed): as cheapest_path_bulk_ptr, the cheapest walks of at most max_hops edges."""
+        used = C.c_int64(0)
+        rc = self.L.pgq_cheapest_path_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(max_hops),
+                                                         C.c_void_p(d_out_len), C.c_void_p(d_out_off), C.c_void_p(d_child),
+                                                         child_cap, C.byref(used))
         return rc, used.value
 
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
@@ -741,7 +765,7 @@ class PgqState:
         ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
         return out, ok
 
-    def cheapest_path(self, csr_id, V, src, dst, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+    def cheapest_path(self, csr_id, V, src, dst, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, max_hops=None):
         self.bind_cheapest(csr_id)
         keep = []
         sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
@@ -752,12 +776,19 @@ class PgqState:
         ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
         child = C.c_void_p()
         clen = C.c_uint64()
-        self._ck(self.U.pgq_udf_cheapest_path(self.s, csr_id, V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
-                                              C.byref(clen)))
+        if max_hops is None:
+            self._ck(self.U.pgq_udf_cheapest_path(self.s, csr_id, V, n, sv, dv, _p(off), _p(ln), _p(ov), C.byref(child),
+                                                  C.byref(clen)))
+        else:
+            self._ck(self.U.pgq_udf_cheapest_path_within(self.s, csr_id, V, n, sv, dv, int(max_hops), _p(off), _p(ln), _p(ov),
+                                                         C.byref(child), C.byref(clen)))
         ch = np.zeros(0, dtype=np.int64)
         if clen.value:
             ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
         return _lists(off, ln, unpack_validity(ov, n), ch)
+
+    def cheapest_path_within(self, csr_id, V, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        return self.cheapest_path(csr_id, V, src, dst, src_valid, dst_valid, src_sel, dst_sel, max_hops=int(max_hops))
 
     def _analytics(self, fn, csr_id, src, dtype):
         keep = []

@@ -1710,17 +1710,32 @@ template <typename T> static int hop_grid(unsigned *grid) { // relax_grid for k_
 // kHopGroup without a host wait — the kernels read the queue's fill on the device, k_round_reset clears the next one, a
 // round behind an empty queue does nothing — and the counter block comes back once per group.  `snap` and `snapmask`
 // live in the worker's second RelaxSide (labels, first dirty array), whose labels a later two-ended call must not trust.
+//
+// What cheapest_path_within asks of these rounds (pgq_cheapest_path_within.hip) instead of the rows' costs: the snapshot rows
+// of every round KEPT, in a log that grows round by round, and a call per finished batch while the log is in place.
+struct HopLog {
+	// In k_hop_snapshot's place: logs the `nq` vertices of the queue of parity `par` with their label rows as they stand after
+	// `round` rounds, takes their dirty words, and says where these entries' rows and masks lie — what the next k_relax_hops
+	// reads.  The host knows nq: a logged batch waits after every round, so the log has its room before a launch appends to it.
+	std::function<int(int par, u32 nq, int64_t round, const int64_t **snap, const u64 **snapmask)> append;
+	// behind the batch's last round and the log pass of the vertices it changed: rows [lo, hi) of the sorted arrays, lane 0 =
+	// distinct source `base`
+	std::function<int(int64_t lo, int64_t hi, int64_t base)> then;
+};
+
 template <typename T> class HopBatches : RelaxWorker {
 	using DT = int64_t; // 8-byte labels only
 	static constexpr int kHopGroup = 8;
 public:
-	HopBatches(const RelaxWorker &w, u32 U, int64_t K) : RelaxWorker(w), U(U), K(K) {}
+	HopBatches(const RelaxWorker &w, u32 U, int64_t K, const HopLog *log = nullptr) : RelaxWorker(w), U(U), K(K), log(log) {}
 
 	int run(int b0, int bstride) {
 		PGQ_TRY(sd.prepare<DT>(V, relax_label_tag<T, DT>(), (DT)Inf<T>::bits, st));
 		sn.dist_V = -1; // (stays so: what is left here is no label array)
-		PGQ_TRY(sn.dist.reserve(Vn * LC * sizeof(DT)));
-		PGQ_TRY(sn.dirty[0].reserve(Vn * 8));
+		if (!log) {
+			PGQ_TRY(sn.dist.reserve(Vn * LC * sizeof(DT)));
+			PGQ_TRY(sn.dirty[0].reserve(Vn * 8));
+		}
 		PGQ_TRY(hop_grid<T>(&grid));
 		PGQ_TRY(priv->counters.reserve(sizeof(Counters)));
 		d_rc = reinterpret_cast<RelaxCounters *>(priv->counters.p);
@@ -1728,7 +1743,8 @@ public:
 			lo = ws->h_bstart[b], hi = ws->h_bstart[b + 1];
 			if (lo == hi) continue;
 			PGQ_TRY(start_batch());
-			for (int64_t done = 0; done < K && nq_now != 0; done += kHopGroup) PGQ_TRY(round_group((int)std::min<int64_t>(kHopGroup, K - done)));
+			const int group = log ? 1 : kHopGroup;
+			for (int64_t done = 0; done < K && nq_now != 0; done += group) PGQ_TRY(round_group((int)std::min<int64_t>(group, K - done)));
 			PGQ_TRY(finish_batch());
 		}
 		return settle<T, DT>(1);
@@ -1736,10 +1752,11 @@ public:
 private:
 	const u32 U;
 	const int64_t K;
+	const HopLog *const log; // null: the rows' costs (k_cheapest_results)
 	RelaxSide &sd = priv->relax[0], &sn = priv->relax[1];
 	RelaxCounters *d_rc = nullptr, *const h_rc = reinterpret_cast<RelaxCounters *>(priv->h_cnt);
 	int par = 0; // from here on: the batch's (start_batch)
-	int64_t lo = 0, hi = 0, base = 0;
+	int64_t lo = 0, hi = 0, base = 0, hop = 0; // hop: the rounds enqueued so far
 	u32 nq_now = 0, rounds_seen = 0, snap_seen = 0;
 	u64 edges = 0;
 
@@ -1756,18 +1773,23 @@ private:
 		nq_now = (u32)std::min<int64_t>(LC, (int64_t)U - base);
 		rounds_seen = snap_seen = 0;
 		edges = 0;
+		hop = 0;
 		return PGQ_OK;
 	}
 	int round_group(int rounds) {
-		for (int r = 0; r < rounds; r++, par ^= 1) {
+		for (int r = 0; r < rounds; r++, par ^= 1, hop++) {
 			hipLaunchKernelGGL(k_round_reset, dim3(1), dim3(64), 0, st, d_rc, par ^ 1);
 			// the group's first round knows its queue's fill; the others size their grids for a full one
 			const unsigned g = r == 0 ? std::min(grid, std::max(1u, (nq_now + 3) / 4)) : grid;
+			const int64_t *snap = sn.dist.as<DT>();
+			const u64 *snapmask = sn.dirty[0].as<u64>();
+			if (log) PGQ_TRY(log->append(par, nq_now, hop, &snap, &snapmask)); // (a group of one round: nq_now is this round's)
 			KernelTimer kt(st, K_RELAX);
-			hipLaunchKernelGGL(k_hop_snapshot<DT>, dim3(g), dim3(256), 0, st, sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.dirty[par].as<u64>(), sd.dist.as<DT>(),
-			                   sn.dist.as<DT>(), sn.dirty[0].as<u64>(), &d_rc->snap_rows);
-			hipLaunchKernelGGL(k_relax_hops<T>, dim3(g), dim3(256), 0, st, c->off, c->adj, (const T *)c->w, sd.dist.as<DT>(), sn.dist.as<DT>(),
-			                   sn.dirty[0].as<u64>(), sd.dirty[par ^ 1].as<u64>(), sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.q[par ^ 1].as<int32_t>(),
+			if (!log)
+				hipLaunchKernelGGL(k_hop_snapshot<DT>, dim3(g), dim3(256), 0, st, sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.dirty[par].as<u64>(), sd.dist.as<DT>(),
+				                   sn.dist.as<DT>(), sn.dirty[0].as<u64>(), &d_rc->snap_rows);
+			hipLaunchKernelGGL(k_relax_hops<T>, dim3(g), dim3(256), 0, st, c->off, c->adj, (const T *)c->w, sd.dist.as<DT>(), snap,
+			                   snapmask, sd.dirty[par ^ 1].as<u64>(), sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.q[par ^ 1].as<int32_t>(),
 			                   &d_rc->nq[par ^ 1], sd.tflag.as<u32>(), tepoch, sd.touched.as<int32_t>(), &d_rc->tcount, &d_rc->relaxed_edges, &d_rc->rounds);
 			kt.stop();
 		}
@@ -1784,6 +1806,14 @@ private:
 		return PGQ_OK;
 	}
 	int finish_batch() {
+		if (log) { // the vertices the last round changed are logged too, which takes their dirty words: nothing is left queued
+			const int64_t *snap = nullptr;
+			const u64 *snapmask = nullptr;
+			if (nq_now != 0) PGQ_TRY(log->append(par, nq_now, hop, &snap, &snapmask));
+			PGQ_TRY(log->then(lo, hi, base));
+			end_batch<T, DT>(edges, 1, d_rc);
+			return PGQ_OK;
+		}
 		hipLaunchKernelGGL(k_cheapest_results<DT>, dim3(blocks_for(hi - lo)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(),
 		                   ws->sidx.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, sd.dist.as<DT>(), Inf<T>::bits, d_out, d_ok);
 		end_batch<T, DT>(edges, 1, d_rc);

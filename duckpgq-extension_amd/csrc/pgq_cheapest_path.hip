@@ -39,8 +39,10 @@
 //      the lists gathered into the caller's child buffer (shortestpath's layout: lengths 2 H + 1, exclusive scan, fill).
 // Kernel-class time: the settling is K_RELAX as ever, the level rounds are booked as K_PUSH (they are top-down frontier
 // expansions), lengths / walk-back / gather as K_RECON, the staging as K_PREP.
-// Not built: the hop-bounded form (a cheapest_path_within needs per-round parents: HopBatches' D_k, not D), _multi, the
-// two-ended search, and any speed-up of the level rounds (a long list is walked by the one wavefront that finds it).
+// The hop-bounded form, pgq_cheapest_path_within, needs per-round parents — HopBatches' D_k, not D — and lives in
+// pgq_cheapest_path_within.hip, on this file's staging, layout and entry points (PathBatches, path_call).
+// Not built: _multi, the two-ended search, and any speed-up of the level rounds (a long list is walked by the one wavefront
+// that finds it).
 
 namespace pgq {
 
@@ -244,26 +246,56 @@ __global__ void k_list_gather(int64_t lo_trivial, int64_t lo_null, const u32 *__
 }
 
 // The tight levels, the walk-back and the staging of one settled batch; the layout of the whole call behind the last one.
+// levels = false: the staging and the layout alone, for a driver with a walk-back of its own (cheapest_path_within).
 template <typename T> class PathBatches {
 public:
-	PathBatches(pgq_csr *c, Workspace *ws, u32 U, int64_t *d_out_len) : c(c), ws(ws), U(U), d_out_len(d_out_len) {}
+	PathBatches(pgq_csr *c, Workspace *ws, u32 U, int64_t *d_out_len, bool levels = true) : c(c), ws(ws), U(U), d_out_len(d_out_len), levels(levels) {}
 
 	int prepare() {
-		for (DevBuf &b : ws->tight_mask) PGQ_TRY(b.reserve(Vn * 8));
-		for (DevBuf &b : ws->tight_q) PGQ_TRY(b.reserve(Vn * 4));
 		PGQ_TRY(ws->tight_cnt.reserve(sizeof(TightCounters)));
 		tc = ws->tight_cnt.as<TightCounters>();
+		PGQ_TRY(ensure_reverse_weights(c, ws, false));
+		PGQ_TRY(ensure_edge_ids(c));
+		if (!levels) return PGQ_OK;
+		for (DevBuf &b : ws->tight_mask) PGQ_TRY(b.reserve(Vn * 8));
+		for (DevBuf &b : ws->tight_q) PGQ_TRY(b.reserve(Vn * 4));
 		const size_t cells = Vn * LC;
 		const bool fresh = ws->tight_h.cap < cells * 4 || ws->tight_V != c->V;
 		ws->tight_V = -1; // stays invalid if the call bails out half-way
 		PGQ_TRY(ws->tight_h.reserve(cells * 4));
 		if (fresh) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, ws->tight_h.as<int32_t>(), (int64_t)cells, -1);
 		for (DevBuf &b : ws->tight_mask) PGQ_HIP_TRY(hipMemsetAsync(b.p, 0, Vn * 8, st));
-		PGQ_TRY(ensure_reverse_weights(c, ws, false));
-		PGQ_TRY(ensure_edge_ids(c));
 		return PGQ_OK;
 	}
-	void settle() { ws->tight_V = c->V; } // behind the last batch's reset, waited for
+	void settle() { // behind the last batch's reset, waited for
+		if (levels) ws->tight_V = c->V;
+	}
+	TightCounters *counters() const { return tc; }
+
+	// The places of a batch's m lists: `lengths(cnt)` enqueues the kernel that writes every row's element count, their
+	// exclusive scan is *loc; *total (their sum) is on the host once the stream has been waited for.
+	template <typename Lengths> int place_rows(int64_t m, Lengths &&lengths, int64_t **loc, int64_t *total) {
+		PGQ_TRY(ws->def_len.reserve((size_t)(m + 1) * 8));
+		PGQ_TRY(ws->def_ent.reserve((size_t)(m + 1) * 8));
+		int64_t *cnt = ws->def_len.as<int64_t>();
+		*loc = ws->def_ent.as<int64_t>();
+		KernelTimer kt(st, K_RECON);
+		PGQ_HIP_TRY(hipMemsetAsync(cnt + m, 0, 8, st));
+		lengths(cnt);
+		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, *loc, (int)(m + 1), st); }));
+		kt.stop();
+		PGQ_HIP_TRY(hipMemcpyAsync(total, *loc + m, 8, hipMemcpyDeviceToHost, st));
+		return PGQ_OK;
+	}
+	// room for `total` more elements in the staging buffer, behind the finished batches' lists: *at = where they start
+	int stage_reserve(int64_t total, int64_t *at) {
+		const size_t need = (size_t)(staged + total) * 8;
+		if (need > ws->tight_stage.cap) PGQ_TRY(grow_keeping(ws->tight_stage, std::max(need, 2 * ws->tight_stage.cap), (size_t)staged * 8, st));
+		*at = staged;
+		staged += total;
+		S.algo_bytes[K_RECON] += (double)total * 8.0;
+		return PGQ_OK;
+	}
 
 	// rows [lo, hi) of the sorted arrays, lane 0 = distinct source `base`; the batch's labels are final and in place
 	int batch(int64_t lo, int64_t hi, int64_t base) {
@@ -300,31 +332,21 @@ public:
 		}
 		// lengths, their scan, the batch's total
 		const int64_t m = hi - lo;
-		PGQ_TRY(ws->def_len.reserve((size_t)(m + 1) * 8));
-		PGQ_TRY(ws->def_ent.reserve((size_t)(m + 1) * 8));
-		int64_t *cnt = ws->def_len.as<int64_t>(), *loc = ws->def_ent.as<int64_t>(), total = 0;
-		{
-			KernelTimer kt(st, K_RECON);
-			PGQ_HIP_TRY(hipMemsetAsync(cnt + m, 0, 8, st));
+		int64_t *loc = nullptr, total = 0, at = 0;
+		PGQ_TRY(place_rows(m, [&](int64_t *cnt) {
 			hipLaunchKernelGGL(k_tight_lengths, dim3(row_blocks), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(), ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
 			                   (u32)base, dist, H, Inf<T>::bits, d_out_len, cnt, tc);
-			PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, loc, (int)(m + 1), st); }));
-			kt.stop();
-		}
-		PGQ_HIP_TRY(hipMemcpyAsync(&total, loc + m, 8, hipMemcpyDeviceToHost, st));
+		}, &loc, &total));
 		PGQ_TRY(read_back(&h, tc, sizeof(h)));
 		if (h.error) return fail(PGQ_ERR_HIP, "cheapest_path: internal error: a destination with a label has no tight hop count");
-		const size_t need = (size_t)(staged + total) * 8;
-		if (need > ws->tight_stage.cap) PGQ_TRY(grow_keeping(ws->tight_stage, std::max(need, 2 * ws->tight_stage.cap), (size_t)staged * 8, st));
+		PGQ_TRY(stage_reserve(total, &at));
 		{
 			KernelTimer kt(st, K_RECON);
 			hipLaunchKernelGGL(k_cheapest_walkback<T>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, hi, ws->skey.as<u32>(),
 			                   ws->sdst.as<int32_t>(), (u32)base, c->off, c->adj, (const T *)c->w, c->edge_ids, c->roff, c->radj, (const T *)c->rw, dist, H, loc,
-			                   staged, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+			                   at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
 			kt.stop();
 		}
-		staged += total;
-		S.algo_bytes[K_RECON] += (double)total * 8.0;
 		// H back to "none"; a frontier the early end left behind is dropped
 		hipLaunchKernelGGL(k_tight_reset_touched, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, ws->relax[0].touched.as<int32_t>(),
 		                   &reinterpret_cast<RelaxCounters *>(ws->counters.p)->tcount, H);
@@ -373,6 +395,7 @@ private:
 	Workspace *const ws;
 	const u32 U;
 	int64_t *const d_out_len;
+	const bool levels;
 	const hipStream_t st = ws->stream;
 	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
 	pgq_stats_t &S = tstats().s;
@@ -388,14 +411,18 @@ private:
 };
 
 // The rows of one call (device memory, src < 0 = NULL row): lengths, offsets and lists.  One worker: the batches share the
-// staging buffer and the hop counts.
-template <typename T>
-static int cheapest_path_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                                int64_t *d_out_off, int64_t *d_child, int64_t child_cap, int64_t *child_used, bool *overflow) {
+// staging buffer and the hop counts.  run(paths, worker, U) settles the lane batches and stages their lists through `paths`;
+// levels: PathBatches' own tight levels and walk-back are part of it.
+struct PathOut {
+	int64_t *d_len, *d_off, *d_child, child_cap, *child_used;
+	bool *overflow;
+};
+template <typename T, typename Run>
+static int path_call(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out, bool levels, Run &&run) {
 	pgq_stats_t &S = tstats().s;
 	S.pairs += n;
-	*child_used = 0;
-	*overflow = false;
+	*out.child_used = 0;
+	*out.overflow = false;
 	if (n == 0) return PGQ_OK;
 	if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
 	u32 U = 0;
@@ -404,52 +431,65 @@ static int cheapest_path_device(pgq_csr *c, Workspace *ws, int64_t n, const int6
 	const int nb = PathBatches<T>::nb_of(U);
 	PGQ_TRY(batch_bounds(ws, n, LC, nb));
 	if (options().relax_delta_div > 0) PGQ_TRY(ensure_weight_mean(c, ws));
-	PathBatches<T> paths(c, ws, U, d_out_len);
+	PathBatches<T> paths(c, ws, U, out.d_len, levels);
 	if (nb > 0) {
 		PGQ_TRY(paths.prepare());
-		const SettledBatch settled { [&](int64_t lo, int64_t hi, int64_t base) { return paths.batch(lo, hi, base); } };
 		const RelaxWorker w { c, ws, ws, nb, nullptr, nullptr };
-		PGQ_TRY((RelaxBatches<T, int64_t>(w, U, false, &settled).run(0, 1)));
+		PGQ_TRY(run(paths, w, U));
 		paths.settle();
 	}
-	return paths.layout(n, d_out_off, d_child, child_cap, child_used, overflow);
+	return paths.layout(n, out.d_off, out.d_child, out.child_cap, out.child_used, out.overflow);
+}
+
+template <typename T> static int cheapest_path_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out) {
+	return path_call<T>(c, ws, n, d_src, d_dst, out, true, [&](PathBatches<T> &paths, const RelaxWorker &w, u32 U) {
+		const SettledBatch settled { [&](int64_t lo, int64_t hi, int64_t base) { return paths.batch(lo, hi, base); } };
+		return RelaxBatches<T, int64_t>(w, U, false, &settled).run(0, 1);
+	});
 }
 
 } // namespace pgq
+
+#include "pgq_cheapest_path_within.hip" // the hop-bounded form: HopBatches' rounds with a round log, on PathBatches' staging and layout
 
 using namespace pgq;
 
 extern "C" {
 
-int pgq_cheapest_path_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
-                                  int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+// max_hops: null = unbounded (cheapest_bulk's convention).  The bounded forms answer a NULL handle before anything else.
+static int cheapest_path_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, const int64_t *max_hops, int64_t *d_out_len,
+                              int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+	if (child_used) *child_used = 0;
+	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	const bool arrays = d_src && d_dst && d_out_len && d_out_offset && d_child;
 	auto check = [&]() -> int {
 		PGQ_TRY(check_weighted(csr));
 		PGQ_TRY(check_arrays(csr, n, arrays, "NULL device array"));
 		if (child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative child_cap");
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		return PGQ_OK;
 	};
-	if (child_used) *child_used = 0;
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
 		int64_t used = 0;
 		bool overflow = false;
-		const int rc = csr->w_type == PGQ_W_INT64
-		                   ? cheapest_path_device<int64_t>(csr, ws, n, d_src, d_dst, d_out_len, d_out_offset, d_child, child_cap, &used, &overflow)
-		                   : cheapest_path_device<double>(csr, ws, n, d_src, d_dst, d_out_len, d_out_offset, d_child, child_cap, &used, &overflow);
+		const PathOut out { d_out_len, d_out_offset, d_child, child_cap, &used, &overflow };
+		const int rc = csr->w_type == PGQ_W_INT64 ? cheapest_path_rows<int64_t>(csr, ws, n, d_src, d_dst, out, max_hops)
+		                                          : cheapest_path_rows<double>(csr, ws, n, d_src, d_dst, out, max_hops);
 		if (child_used) *child_used = used;
 		if (rc == PGQ_OK && overflow) return fail(PGQ_ERR_INVALID_ARG, "child buffer too small for the path lists (see *child_used)");
 		return rc;
 	});
 }
 
-int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset, uint64_t *out_length,
-                      uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+static int cheapest_path_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, const int64_t *max_hops, uint64_t *out_offset,
+                               uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	auto check = [&]() -> int {
 		PGQ_TRY(check_weighted(csr));
 		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
 		if (n < 0 || (n > 0 && (!out_offset || !out_length || !out_valid)) || !out_child || !out_child_len)
 			return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		if (max_hops && *max_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be negative");
 		*out_child = nullptr;
 		*out_child_len = 0;
 		return n == 0 ? kNoRows : PGQ_OK;
@@ -464,9 +504,9 @@ int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_v
 		const int64_t *d_src = ws->in_src.as<int64_t>(), *d_dst = ws->in_dst.as<int64_t>();
 		int64_t used = 0;
 		bool overflow = false;
-		PGQ_TRY(csr->w_type == PGQ_W_INT64
-		            ? cheapest_path_device<int64_t>(csr, ws, n, d_src, d_dst, ws->out_len.as<int64_t>(), ws->out_off.as<int64_t>(), nullptr, 0, &used, &overflow)
-		            : cheapest_path_device<double>(csr, ws, n, d_src, d_dst, ws->out_len.as<int64_t>(), ws->out_off.as<int64_t>(), nullptr, 0, &used, &overflow));
+		const PathOut out { ws->out_len.as<int64_t>(), ws->out_off.as<int64_t>(), nullptr, 0, &used, &overflow };
+		PGQ_TRY(csr->w_type == PGQ_W_INT64 ? cheapest_path_rows<int64_t>(csr, ws, n, d_src, d_dst, out, max_hops)
+		                                   : cheapest_path_rows<double>(csr, ws, n, d_src, d_dst, out, max_hops));
 		std::vector<int64_t> len(n), off(n);
 		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
 		PGQ_TRY(staged_download(off.data(), ws->out_off.p, (size_t)n * 8, ws->stream));
@@ -488,6 +528,23 @@ int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_v
 		*out_child_len = (uint64_t)used;
 		return PGQ_OK;
 	});
+}
+
+int pgq_cheapest_path_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
+                                  int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+	return cheapest_path_bulk(csr, n, d_src, d_dst, nullptr, d_out_len, d_out_offset, d_child, child_cap, child_used);
+}
+int pgq_cheapest_path_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                         int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+	return cheapest_path_bulk(csr, n, d_src, d_dst, &max_hops, d_out_len, d_out_offset, d_child, child_cap, child_used);
+}
+int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset, uint64_t *out_length,
+                      uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	return cheapest_path_chunk(csr, V, n, src, dst, nullptr, out_offset, out_length, out_valid, out_child, out_child_len);
+}
+int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, uint64_t *out_offset,
+                             uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	return cheapest_path_chunk(csr, V, n, src, dst, &max_hops, out_offset, out_length, out_valid, out_child, out_child_len);
 }
 
 } // extern "C"

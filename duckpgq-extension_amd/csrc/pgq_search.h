@@ -317,6 +317,11 @@ struct Workspace {
 	// lists of the finished batches in batch order
 	DevBuf tight_h, tight_mask[2], tight_q[2], tight_cnt, tight_stage;
 	int64_t tight_V = -1;
+	// cheapest_path_within (pgq_cheapest_path_within.hip): the round log of one lane batch — per entry the 512-byte label row,
+	// the lanes that changed and {round, the vertex's previous entry} — and per vertex its latest entry (-1 = none; a batch
+	// resets what it set, hop_last_V says for which V that holds)
+	DevBuf hop_row, hop_mask, hop_ent, hop_last;
+	int64_t hop_last_V = -1;
 	~Workspace();
 };
 

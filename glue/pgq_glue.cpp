@@ -3,6 +3,7 @@
 //   IterativeLengthFunction        src/core/functions/scalar/iterativelength.cpp:34-143   (also registered as iterativelength2)
 //   ShortestPathFunction           src/core/functions/scalar/shortest_path.cpp:43-207   (ShortestPathWithinFunction: its five-argument overload)
 //   CheapestPathLengthFunction     src/core/functions/scalar/cheapest_path_length.cpp:138-163   (CheapestPathLengthWithinFunction: its five-argument overload)
+//   CheapestPathFunction           (no counterpart) the cheapest path as a list   (CheapestPathWithinFunction: its five-argument overload)
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
 // plus PathFindingRelation, the whole-relation entry point SURVEY.md §8f rank 2 asks for (length and path of every
@@ -199,8 +200,10 @@ void CheapestPathLengthWithinFunction(DataChunk &args, ExpressionState &state, V
 // cheapest_path(csr_id, V, src, dst) -> LIST(BIGINT): the cheapest path itself, [src, e1, v1, ..., ek, dst], bound like
 // cheapest_path_length (CheapestPathLengthFunctionData; registered beside it with a LIST(BIGINT) return type).  The reference has no
 // such function: a MATCH over a weighted edge table gets vertices(p) / edges(p) of its cheapest path from this list the way it gets
-// them from shortestpath's.  There is no five-argument overload (the cheapest walk of at most `upper` edges needs per-round parents).
-void CheapestPathFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+// them from shortestpath's.
+namespace {
+// cheapest_path with four arguments (upper == nullptr) or five
+void CheapestPath(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper) {
 	auto &info = state.expr.Cast<BoundFunctionExpression>().BindInfo()->Cast<CheapestPathLengthFunctionData>();
 	auto duckpgq_state = GetDuckPGQState(info.context);
 	auto entry = duckpgq_state->csr_list.find(info.csr_id);
@@ -220,9 +223,12 @@ void CheapestPathFunction(DataChunk &args, ExpressionState &state, Vector &resul
 	const int64_t *child = nullptr; // owned by the library until this thread's next list-returning call
 	uint64_t child_len = 0;
 	vector<uint64_t> offsets(args.size()), lengths(args.size());
-	if (pgq_cheapest_path(DeviceCSR(*duckpgq_state, csr, v_size), v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), offsets.data(),
-	                      lengths.data(), validity.GetData(), &child, &child_len) != PGQ_OK)
-		ThrowDevice();
+	pgq_csr_t *device = DeviceCSR(*duckpgq_state, csr, v_size);
+	const int rc = upper ? pgq_cheapest_path_within(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *upper, offsets.data(),
+	                                                lengths.data(), validity.GetData(), &child, &child_len)
+	                     : pgq_cheapest_path(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), offsets.data(), lengths.data(),
+	                                         validity.GetData(), &child, &child_len);
+	if (rc != PGQ_OK) ThrowDevice();
 	ListVector::Reserve(result, child_len);
 	if (child_len) memcpy(FlatVector::GetDataMutable<int64_t>(ListVector::GetEntry(result)), child, child_len * sizeof(int64_t));
 	ListVector::SetListSize(result, child_len);
@@ -231,6 +237,19 @@ void CheapestPathFunction(DataChunk &args, ExpressionState &state, Vector &resul
 		entries[i].length = lengths[i];
 	}
 	duckpgq_state->csr_to_delete.insert(info.csr_id);
+}
+} // namespace
+
+void CheapestPathFunction(DataChunk &args, ExpressionState &state, Vector &result) { CheapestPath(args, state, result, nullptr); }
+
+// cheapest_path(csr_id, V, src, dst, upper): the five-argument overload beside cheapest_path_length's, registered beside
+// cheapest_path.  Like that one it changes the VALUE: the list is the cheapest walk of at most `upper` edges — the walk whose cost
+// CheapestPathLengthWithinFunction returns — not the four-argument list with long rows NULL (pgq_cheapest_path_within).
+void CheapestPathWithinFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	UnifiedVectorFormat upper_fmt; // a constant of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	CheapestPath(args, state, result, &upper);
 }
 
 void LocalClusteringCoefficientFunction(DataChunk &args, ExpressionState &state, Vector &result) {

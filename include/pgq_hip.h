@@ -223,10 +223,33 @@ int pgq_cheapest_path_length_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_ve
  * weight is the same positive int64 the list is pgq_shortestpath's.  src == dst -> [src]; NULL src, NULL dst or unreachable ->
  * NULL (validity clear, entry {0,0}, no payload).  Signature and thread-local child arena as pgq_shortestpath (the arena is the
  * same one: valid until the next list-returning call on the thread).  An unweighted CSR, negative weights and ids out of range fail
- * as in pgq_cheapest_path_length.  There is no hop-bounded form (that needs per-round parents), no _multi form, and the two-ended
+ * as in pgq_cheapest_path_length.  The hop-bounded form is pgq_cheapest_path_within; there is no _multi form, and the two-ended
  * search is not used. */
 int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
                       uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len);
+
+/* cheapest_path(csr_id, V, src, dst, upper) -> LIST(BIGINT) [src, e1, v1, ..., eh, dst]: the cheapest walk of AT MOST max_hops
+ * edges itself, next to the cost pgq_cheapest_path_length_within returns (the reference has no counterpart).  With D_0 .. D_K the
+ * labels that call defines for the row's source and K = max_hops, every sum computed as the relaxation computes it:
+ *   - NULL when D_K[dst] == INF, or src or dst is NULL; src == dst -> [src] for every K >= 0;
+ *   - h = the smallest k with D_k[dst] == D_K[dst] as bit patterns: the fewest edges among the cheapest walks of at most K edges;
+ *   - x_h = dst, and for i = h .. 1, x_{i-1} = the smallest u with D_{i-1}[u] < INF and a slot (u, x_i) whose
+ *     D_{i-1}[u] + w[s] == D_i[x_i], e_i = edge_ids[the first such slot of u's out-list into x_i] (shortestpath's min-parent and
+ *     first-slot rules); NaN and +inf weights are never tight; the list is [x_0, e_1, x_1, ..., e_h, x_h] with x_0 = src.
+ * WARNING: this is NOT pgq_cheapest_path's list with rows of more than max_hops edges set to NULL: the cheapest walk of at most K
+ * edges is in general another walk than the cheapest one.  The left-to-right fold of the weights of e_1 .. e_h is
+ * pgq_cheapest_path_length_within's result, bit for bit, and h <= max_hops; when every weight is the same positive int64 the list
+ * is pgq_shortestpath_within's.  max_hops >= V - 1 changes nothing any more (D_k stands still from V - 1 on): for int64 weights
+ * the list is then pgq_cheapest_path's; for DOUBLE weights the two CAN DIFFER, where a label absorbs a difference — with edges
+ * 0->2 (1.0), 0->1 (0.25), 1->2 (0.25), 2->3 (2^53) this call answers the two-hop walk 0, 2, 3 for every max_hops >= 2
+ * (1.0 + 2^53 == 0.5 + 2^53: the third round improves nothing), pgq_cheapest_path the three-hop path through vertex 1; both fold
+ * to 2^53.  max_hops < 0 -> PGQ_ERR_INVALID_ARG.  Signature, arena and NULL conventions as pgq_cheapest_path; an unweighted CSR,
+ * negative weights and ids out of range fail as in pgq_cheapest_path_length.  The search keeps a log of every round's changed
+ * label rows (rounds x changed vertices x 528 bytes per 64 sources): PGQ_ERR_OOM when it cannot be allocated, PGQ_ERR_UNSUPPORTED
+ * beyond 2^31 entries, no list written in either case.  No _multi form. */
+int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                             uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                             uint64_t *out_child_len);
 
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
@@ -297,6 +320,12 @@ int pgq_cheapest_path_length_within_bulk_device(pgq_csr_t *csr, int64_t n, const
  * PGQ_ERR_INVALID_ARG when child_cap is too small (d_out_len is complete, the payload is not usable). */
 int pgq_cheapest_path_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t *d_out_len,
                                   int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used);
+/* pgq_cheapest_path_within without the chunk ceiling: d_out_len[i] = h, the edges of the cheapest walk of at most max_hops edges
+ * (NOT pgq_cheapest_path_bulk_device's lengths with long rows at -1: see pgq_cheapest_path_within), 0 for src == dst, -1 for
+ * NULL rows and rows without such a walk; lists and child-capacity protocol as pgq_cheapest_path_bulk_device. */
+int pgq_cheapest_path_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                         int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
+                                         int64_t *child_used);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

@@ -19,6 +19,7 @@
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
  *   pgq_udf_cheapest_path           (no counterpart) the cheapest path as a list; bound like cheapest_path_length
+ *   pgq_udf_cheapest_path_within    (no counterpart) ... of at most the pattern's upper bound of edges, fifth argument
  *   pgq_udf_delete_csr              DeleteCsrFunction            src/core/functions/scalar/csr_deletion.cpp:10-20
  *   pgq_udf_csr_get_w_type          GetCsrWTypeFunction          src/core/functions/scalar/csr_get_w_type.cpp:16-36
  *   pgq_udf_reachability            ReachabilityFunction         src/core/functions/scalar/reachability.cpp:165-254 (intended semantics)
@@ -88,6 +89,12 @@ int pgq_udf_cheapest_path_length_within(pgq_state_t *, int32_t id, int64_t V, in
  * pgq_udf_shortestpath, errors as for pgq_udf_cheapest_path_length.  The reference has no such function. */
 int pgq_udf_cheapest_path(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
                           uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len);
+/* cheapest_path(id, V, src, dst, upper) -> LIST(BIGINT): the cheapest walk of at most max_hops edges itself
+ * (pgq_cheapest_path_within: the list whose cost pgq_udf_cheapest_path_length_within returns, not pgq_udf_cheapest_path's list
+ * with long rows NULL); errors as for pgq_udf_cheapest_path, max_hops < 0 is the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_cheapest_path_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                                 uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                                 uint64_t *out_child_len);
 /* reachability(id, is_variant, V, src, dst) -> BOOL; the reference's BOOL argument only selects one of its three
  * internal BFS modes (reachability.cpp:154-163) and does not change the result, so it is not part of this call.
  * Boolean reachability with the semantics the reference intends (reachability.cpp:165-254 indexes its inputs
