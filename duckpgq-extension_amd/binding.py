@@ -112,6 +112,14 @@ def load_hip():
                                            C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_cheapest_path_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.pgq_shortestpath_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pgq_shortestpath_count_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.pgq_all_shortestpaths.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_all_shortestpaths_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                    C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -166,6 +174,11 @@ def load_udf():
                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_shortestpath_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_udf_shortestpath_count.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p,
+                                             C.c_void_p]
+    L.pgq_udf_all_shortestpaths.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -284,6 +297,31 @@ def copy_bandwidth_gbps(nbytes=1 << 30, iters=10):
 
 def _lists(off, ln, valid, child):
     return [child[int(o):int(o) + int(l)].tolist() if ok else None for o, l, ok in zip(off, ln, valid)]
+
+
+def _u64_copy(ptr, count):
+    if not count:
+        return np.zeros(0, dtype=np.uint64)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(count,)).copy()
+
+
+def _all_shortestpaths(call, n, raw):
+    """Runs call(first, npaths, validity words, &path_offset, &path_length, &path_total, &child, &child_len) and unpacks the
+    LIST(LIST(BIGINT)) it fills: per row a list of paths (None for NULL rows).  raw=True: the vectors as DuckDB sees them —
+    outer entries (first, npaths), validity words, inner entries (offset, length), child payload."""
+    first = np.zeros(n, dtype=np.uint64)
+    npaths = np.zeros(n, dtype=np.uint64)
+    ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+    poff, plen, child = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    ptotal, clen = C.c_uint64(), C.c_uint64()
+    call(_p(first), _p(npaths), _p(ov), C.byref(poff), C.byref(plen), C.byref(ptotal), C.byref(child), C.byref(clen))
+    po, pl = _u64_copy(poff, ptotal.value), _u64_copy(plen, ptotal.value)
+    ch = _u64_copy(child, clen.value).view(np.int64)
+    if raw:
+        return first, npaths, ov, po, pl, ch
+    valid = unpack_validity(ov, n)
+    return [[ch[int(po[k]):int(po[k]) + int(pl[k])].tolist() for k in range(int(f), int(f) + int(c))] if ok else None
+            for f, c, ok in zip(first, npaths, valid)]
 
 
 class DeviceCSR:
@@ -443,6 +481,28 @@ class DeviceCSR:
         """shortestpath with the pattern's upper bound: rows whose path has more than max_hops hops are NULL and take no room
         in the child payload."""
         return self.shortestpath(src, dst, src_valid, src_sel, dst_sel, raw, max_hops=int(max_hops))
+
+    def shortestpath_count(self, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        """The number of shortest paths of at most max_hops hops per row (saturated at 2^63 - 1): 1 for src == dst, 0 for
+        unreachable or farther rows, NULL for a NULL endpoint (include/pgq_hip.h)."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        out = np.zeros(n, dtype=np.int64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_shortestpath_count(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
+    def all_shortestpaths(self, src, dst, max_hops, max_paths, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None,
+                          raw=False):
+        """Per row the list of its first max_paths shortest paths of at most max_hops hops, each [src, e1, v1, ..., dst], in the
+        contract's order (path 0 is shortestpath's); None for NULL rows.  raw=True: see _all_shortestpaths."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+
+        def call(*outs):
+            _check(self.L.pgq_all_shortestpaths(self.h, self.V, n, sv, dv, int(max_hops), int(max_paths), *outs))
+
+        return _all_shortestpaths(call, n, raw)
 
     def cheapest_path_length(self, src, dst, src_valid=None, dst_valid=None):
         keep = []
@@ -615,6 +675,21 @@ class DeviceCSR:
                                                          child_cap, C.byref(used))
         return rc, used.value
 
+    def shortestpath_count_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out_count):
+        _check(self.L.pgq_shortestpath_count_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(max_hops),
+                                                         C.c_void_p(d_out_count)))
+
+    def all_shortestpaths_bulk_ptr(self, n, d_src, d_dst, max_hops, max_paths, d_out_len, d_out_count, d_out_first, d_out_npaths,
+                                   d_path_offset, path_cap, d_child, child_cap):
+        """(status, paths needed, elements needed): the capacity protocol of shortestpath_bulk_ptr for both buffers."""
+        paths, used = C.c_int64(0), C.c_int64(0)
+        rc = self.L.pgq_all_shortestpaths_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(max_hops),
+                                                      int(max_paths), C.c_void_p(d_out_len), C.c_void_p(d_out_count),
+                                                      C.c_void_p(d_out_first), C.c_void_p(d_out_npaths),
+                                                      C.c_void_p(d_path_offset), path_cap, C.c_void_p(d_child), child_cap,
+                                                      C.byref(paths), C.byref(used))
+        return rc, paths.value, used.value
+
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                                   int(max_hops), C.c_void_p(d_out), C.c_void_p(d_ok)))
@@ -739,6 +814,29 @@ class PgqState:
 
     def shortestpath_within(self, csr_id, V, src, dst, max_hops, src_valid=None, src_sel=None, dst_sel=None):
         return self.shortestpath(csr_id, V, src, dst, src_valid, src_sel, dst_sel, max_hops=int(max_hops))
+
+    def shortestpath_count(self, csr_id, V, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        n = len(src_sel) if src_sel is not None else len(src)
+        out = np.zeros(n, dtype=np.int64)
+        hops = int(max_hops)
+
+        def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            return self.U.pgq_udf_shortestpath_count(s, csr_id, V, n, sv, dv, hops, out_p, ov_p)
+
+        ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
+        return out, ok
+
+    def all_shortestpaths(self, csr_id, V, src, dst, max_hops, max_paths, src_valid=None, dst_valid=None, src_sel=None,
+                          dst_sel=None, raw=False):
+        keep = []
+        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
+        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
+        n = len(src_sel) if src_sel is not None else len(src)
+
+        def call(*outs):
+            self._ck(self.U.pgq_udf_all_shortestpaths(self.s, csr_id, V, n, sv, dv, int(max_hops), int(max_paths), *outs))
+
+        return _all_shortestpaths(call, n, raw)
 
     def bind_cheapest(self, csr_id):
         t = C.c_int(0)

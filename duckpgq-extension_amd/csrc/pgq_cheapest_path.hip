@@ -43,6 +43,7 @@
 // pgq_cheapest_path_within.hip, on this file's staging, layout and entry points (PathBatches, path_call).
 // Not built: _multi, the two-ended search, and any speed-up of the level rounds (a long list is walked by the one wavefront
 // that finds it).
+// pgq_all_shortest.hip (shortestpath_count, all_shortestpaths) is included at this file's end: it keeps its BFS levels in H.
 
 namespace pgq {
 
@@ -548,3 +549,5 @@ int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 }
 
 } // extern "C"
+
+#include "pgq_all_shortest.hip" // shortestpath_count / all_shortestpaths: level rounds on this file's H table, masks and queues

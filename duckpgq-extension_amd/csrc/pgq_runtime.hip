@@ -600,7 +600,8 @@ Workspace::~Workspace() {
 	                   &wb_scratch, &hv, &hmask, &hstart, &hmap, &route_dec, &ball_segs, &ball_trace, &sort_src, &sort_dst, &sort_out, &bi_block, &dpart })
 		b->release();
 	for (RelaxSide &s : relax) s.release();
-	for (DevBuf *b : { &tight_h, &tight_mask[0], &tight_mask[1], &tight_q[0], &tight_q[1], &tight_cnt, &tight_stage, &hop_row, &hop_mask, &hop_ent, &hop_last })
+	for (DevBuf *b : { &tight_h, &tight_mask[0], &tight_mask[1], &tight_q[0], &tight_q[1], &tight_cnt, &tight_stage, &hop_row, &hop_mask, &hop_ent, &hop_last,
+	                   &asp_rows, &asp_paths })
 		b->release();
 	for (auto *v : { &levels, &pool })
 		for (auto &l : *v) {

@@ -322,6 +322,10 @@ struct Workspace {
 	// resets what it set, hop_last_V says for which V that holds)
 	DevBuf hop_row, hop_mask, hop_ent, hop_last;
 	int64_t hop_last_V = -1;
+	// shortestpath_count / all_shortestpaths (pgq_all_shortest.hip): the rows' results in row order until the call has succeeded,
+	// and the chunk form's inner list entries.  The levels live in tight_h and the tight_* frontier buffers (same invariants),
+	// the staged lists in tight_stage; sigma is block-cache memory of the call
+	DevBuf asp_rows, asp_paths;
 	~Workspace();
 };
 

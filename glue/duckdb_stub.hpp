@@ -79,6 +79,8 @@ struct FlatVector {
 	template <class T> static T *GetDataMutable(Vector &v);
 	static ValidityMask &ValidityMutable(Vector &v);
 };
+// A LIST(LIST(BIGINT)) result (all_shortestpaths) nests them: GetEntry of the result is itself a list vector, with
+// list_entry_t data of its own, a size, and the BIGINT payload as ITS entry.
 struct ListVector {
 	static void Reserve(Vector &v, idx_t capacity);
 	static Vector &GetEntry(Vector &v);

@@ -4,6 +4,8 @@
 //   ShortestPathFunction           src/core/functions/scalar/shortest_path.cpp:43-207   (ShortestPathWithinFunction: its five-argument overload)
 //   CheapestPathLengthFunction     src/core/functions/scalar/cheapest_path_length.cpp:138-163   (CheapestPathLengthWithinFunction: its five-argument overload)
 //   CheapestPathFunction           (no counterpart) the cheapest path as a list   (CheapestPathWithinFunction: its five-argument overload)
+//   ShortestPathCountFunction      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
+//   AllShortestPathsFunction       (no counterpart) ... the first max_paths of them, LIST(LIST(BIGINT)); bound and max_paths trail the arguments
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
 // plus PathFindingRelation, the whole-relation entry point SURVEY.md §8f rank 2 asks for (length and path of every
@@ -153,6 +155,64 @@ void ShortestPathWithinFunction(DataChunk &args, ExpressionState &state, Vector 
 	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
 	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
 	ShortestPath(args, state, result, &upper);
+}
+
+// shortestpath_count(csr_id, V, src, dst, upper) -> BIGINT: the number of shortest paths of at most `upper` hops, what a
+// MATCH ALL SHORTEST needs to size its result (the reference's binder rejects the form, match.cpp:82; bound like shortestpath,
+// registered beside it).  0 for unreachable or farther rows, NULL for a NULL endpoint; saturates at 2^63 - 1.
+void ShortestPathCountFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	UnifiedVectorFormat upper_fmt; // a constant of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto result_data = FlatVector::GetDataMutable<int64_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	if (pgq_shortestpath_count(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), upper,
+	                           result_data, validity.GetData()) != PGQ_OK)
+		ThrowDevice();
+	in.state->csr_to_delete.insert(in.csr_id);
+}
+
+// all_shortestpaths(csr_id, V, src, dst, upper, max_paths) -> LIST(LIST(BIGINT)): the first `max_paths` shortest paths of every
+// row, each [src, e1, v1, ..., dst], path 0 being shortestpath's.  The result vector's child is a LIST(BIGINT) vector: its
+// entries are the inner lists, its own child the payload.  NULL rows keep the outer entry {0, 0}.
+void AllShortestPathsFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	UnifiedVectorFormat upper_fmt, paths_fmt; // constants of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
+	args.data[5].ToUnifiedFormat(args.size(), paths_fmt);
+	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	const int64_t max_paths = reinterpret_cast<const int64_t *>(paths_fmt.data)[0];
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto outer = FlatVector::GetDataMutable<list_entry_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	const uint64_t *path_offset = nullptr, *path_length = nullptr; // owned by the library until this thread's next list-returning call
+	const int64_t *child = nullptr;
+	uint64_t path_total = 0, child_len = 0;
+	vector<uint64_t> first(args.size()), npaths(args.size());
+	if (pgq_all_shortestpaths(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), upper, max_paths,
+	                          first.data(), npaths.data(), validity.GetData(), &path_offset, &path_length, &path_total, &child, &child_len) != PGQ_OK)
+		ThrowDevice();
+	ListVector::Reserve(result, path_total);
+	Vector &inner = ListVector::GetEntry(result);
+	inner.SetVectorType(VectorType::FLAT_VECTOR);
+	auto inner_entries = FlatVector::GetDataMutable<list_entry_t>(inner);
+	for (idx_t k = 0; k < path_total; k++) {
+		inner_entries[k].offset = path_offset[k];
+		inner_entries[k].length = path_length[k];
+	}
+	ListVector::SetListSize(result, path_total);
+	ListVector::Reserve(inner, child_len);
+	if (child_len) memcpy(FlatVector::GetDataMutable<int64_t>(ListVector::GetEntry(inner)), child, child_len * sizeof(int64_t));
+	ListVector::SetListSize(inner, child_len);
+	for (idx_t i = 0; i < args.size(); i++) {
+		outer[i].offset = first[i];
+		outer[i].length = npaths[i];
+	}
+	in.state->csr_to_delete.insert(in.csr_id);
 }
 
 namespace {

@@ -251,6 +251,40 @@ int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
                              uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                              uint64_t *out_child_len);
 
+/* shortestpath_count(csr_id, V, src, dst, upper) -> BIGINT and all_shortestpaths(csr_id, V, src, dst, upper, max_paths) ->
+ * LIST(LIST(BIGINT)): what SQL/PGQ's ALL SHORTEST needs (the reference's binder rejects the form: "ALL SHORTEST has not been
+ * implemented yet", match.cpp:82).  Both are hop-bounded: max_hops = INT64_MAX or >= V - 1 means no bound, max_hops < 0 ->
+ * PGQ_ERR_INVALID_ARG.  Both work on any CSR and ignore weights.  For a row (src, dst), with L[v] the BFS level of v from src and
+ * d = L[dst]:
+ *     sigma[src] = 1;   sigma[x] = min(INT64_MAX, sum of sigma[u] over the in-slots (u, x) with L[u] = L[x] - 1)
+ * Parallel edges are separate slots and count separately (a path is a sequence of edges, as in shortestpath's list); the sum
+ * saturates at 2^63 - 1 and never wraps.
+ *   - pgq_shortestpath_count: sigma[dst]; 1 for src == dst; 0 when dst is unreachable or d > max_hops; NULL (payload -1) for a
+ *     NULL src or a NULL dst.
+ *   - pgq_all_shortestpaths: a row's list holds its first min(sigma[dst], max_paths) shortest paths, each in shortestpath's
+ *     layout [src, e1, v1, ..., ed, dst].  Order: compare two paths from the destination end, first by (x_{d-1}, forward slot of
+ *     e_d), then by (x_{d-2}, slot of e_{d-1}), and so on — the lexicographic order of in-list positions (an in-list is ordered by
+ *     parent id, then forward slot).  Path number r is found by unranking: start at x_d = dst with rank r; scan the in-list of x_t in
+ *     its stored order, and for every in-slot (u, x_t) with L[u] = t - 1: if r < sigma[u] take that slot, otherwise r -= sigma[u].
+ *     The taken in-slot is the m-th in-slot from u into x_t; its edge is the m-th slot of u's out-list whose target is x_t.
+ *     Path 0 is therefore pgq_shortestpath's list; with max_paths = 1 the call returns pgq_shortestpath_within's lists, validity
+ *     and payload, wrapped one level deeper.  src == dst -> [[src]].  NULL src, NULL dst, unreachable dst or d > max_hops -> NULL:
+ *     no inner list, no payload.  max_paths < 1 -> PGQ_ERR_INVALID_ARG.  A call that would emit more than 2^31 - 1 paths returns
+ *     PGQ_ERR_UNSUPPORTED and writes nothing.  A saturated sigma stays valid for unranking: every emitted rank is below 2^31.
+ * Outer entry i = {out_first[i], out_npaths[i]} into the inner entries {(*out_path_offset)[k], (*out_path_length)[k]},
+ * k < *out_path_total, which index *out_child.  The inner entries and the child live in the thread's result arena: valid until
+ * the next list-returning call on that thread.  NULL rows keep the outer entry {0, 0}.
+ * Workspace: about 768 bytes per vertex (hop counts and sigma of one batch of 64 sources); PGQ_ERR_OOM with nothing written when
+ * it cannot be had.  A NULL handle is answered with PGQ_ERR_INVALID_ARG ("NULL csr") before any device is asked for.
+ * NOT BUILT: _multi forms; splitting long in-lists over several wavefronts (a list is walked by one wavefront); sharing prefixes
+ * between the paths of one row; any change to how shortestpath or iterativelength are routed. */
+int pgq_shortestpath_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, int64_t *out_count,
+                           uint64_t *out_valid);
+int pgq_all_shortestpaths(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, int64_t max_paths,
+                          uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset,
+                          const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
+                          uint64_t *out_child_len);
+
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
  * freed CSR / upload blocks kept for the next upload (PGQ_ALLOC_CACHE_MB). */
@@ -326,6 +360,21 @@ int pgq_cheapest_path_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_sr
 int pgq_cheapest_path_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
                                          int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
                                          int64_t *child_used);
+/* pgq_shortestpath_count without the chunk ceiling: d_out_count[i] = sigma[dst] (saturated), 1 for src == dst, 0 for an
+ * unreachable row or one farther apart than max_hops, -1 for a NULL row (d_src[i] < 0). */
+int pgq_shortestpath_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                       int64_t *d_out_count);
+/* pgq_all_shortestpaths without the chunk ceiling.  Per row: d_out_len[i] = hops (0 for src == dst, -1 for NULL rows, unreachable
+ * rows and rows beyond max_hops), d_out_count[i] = sigma as pgq_shortestpath_count_bulk_device reports it (whatever max_paths),
+ * d_out_npaths[i] = the paths emitted, min(sigma, max_paths), d_out_first[i] = the index of its first path.  Path k starts at
+ * d_path_offset[k] in d_child and has 2 * len + 1 elements; paths and payload are packed in row order.  *paths_used / *child_used =
+ * the paths and elements needed; PGQ_ERR_INVALID_ARG when path_cap or child_cap is too small: d_out_len, d_out_count and
+ * d_out_npaths are complete then and both *_used values say what to provide, the payload is not usable.  A NULL handle:
+ * PGQ_ERR_INVALID_ARG, both *_used values 0. */
+int pgq_all_shortestpaths_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
+                                      int64_t max_paths, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first,
+                                      int64_t *d_out_npaths, int64_t *d_path_offset, int64_t path_cap, int64_t *d_child,
+                                      int64_t child_cap, int64_t *paths_used, int64_t *child_used);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

@@ -15,7 +15,9 @@
  *   pgq_udf_iterativelengthbidirectional  IterativeLengthBidirectionalFunction  src/core/functions/scalar/iterativelength_bidirectional.cpp:43-153 (intended semantics)
  *   pgq_udf_shortestpath            ShortestPathFunction         src/core/functions/scalar/shortest_path.cpp:43-207
  *   pgq_udf_shortestpath_within     ShortestPathFunction with the pattern's upper bound as fifth argument (match.cpp:467-495, 658-671)
- *   pgq_udf_bind_cheapest           CheapestPathLengthBind       src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
+ *   pgq_udf_shortestpath_count      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
+ *   pgq_udf_all_shortestpaths       (no counterpart) ... and the first max_paths of them as a list of lists; both bound like shortestpath
+ *   pgq_udf_bind_cheapest           CheapestPathLengthBind      src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
  *   pgq_udf_cheapest_path           (no counterpart) the cheapest path as a list; bound like cheapest_path_length
@@ -75,6 +77,19 @@ int pgq_udf_shortestpath(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_ve
 int pgq_udf_shortestpath_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
                                 uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                                 uint64_t *out_child_len);
+/* shortestpath_count(id, V, src, dst, upper) -> BIGINT: the number of shortest paths of at most max_hops hops, saturated at
+ * 2^63 - 1 (pgq_shortestpath_count: 1 for src == dst, 0 for unreachable or farther rows, NULL for a NULL endpoint); bound through
+ * pgq_udf_bind_search, errors as for pgq_udf_shortestpath, max_hops < 0 is the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_shortestpath_count(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                               int64_t *out, uint64_t *out_valid);
+/* all_shortestpaths(id, V, src, dst, upper, max_paths) -> LIST(LIST(BIGINT)): the first max_paths shortest paths of every row in
+ * the contract's order (pgq_all_shortestpaths; path 0 is shortestpath's list); outputs as that call's: outer entries per row,
+ * inner entries and child payload in the thread's result arena.  Bound through pgq_udf_bind_search, errors as for
+ * pgq_udf_shortestpath; max_hops < 0 and max_paths < 1 are the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_all_shortestpaths(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
+                              int64_t max_paths, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
+                              const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
+                              const int64_t **out_child, uint64_t *out_child_len);
 /* *ret_type: PGQ_W_INT64 -> BIGINT result, PGQ_W_DOUBLE -> DOUBLE result */
 int pgq_udf_bind_cheapest(pgq_state_t *, int32_t id, int *ret_type);
 int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
