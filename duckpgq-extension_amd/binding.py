@@ -120,6 +120,14 @@ def load_hip():
     L.pgq_all_shortestpaths_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                     C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.pgq_walk_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pgq_walk_count_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    L.pgq_k_shortest_walks.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_k_shortest_walks_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -179,6 +187,11 @@ def load_udf():
     L.pgq_udf_all_shortestpaths.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_udf_walk_count.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_void_p]
+    L.pgq_udf_k_shortest_walks.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -504,6 +517,28 @@ class DeviceCSR:
 
         return _all_shortestpaths(call, n, raw)
 
+    def walk_count(self, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        """The number of walks of min_hops..max_hops edges per row (saturated at 2^63 - 1): src == dst counts the empty walk when
+        min_hops == 0 and every closed walk; 0 when there is none, NULL for a NULL endpoint (include/pgq_hip.h)."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        out = np.zeros(n, dtype=np.int64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_walk_count(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
+    def k_shortest_walks(self, src, dst, min_hops, max_hops, k, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None,
+                         raw=False):
+        """Per row the list of its first k walks of min_hops..max_hops edges, shorter walks first, each [x_0, e_1, x_1, ..., x_t],
+        in the contract's order; None for rows without a walk and NULL rows.  raw=True: see _all_shortestpaths."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+
+        def call(*outs):
+            _check(self.L.pgq_k_shortest_walks(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), int(k), *outs))
+
+        return _all_shortestpaths(call, n, raw)
+
     def cheapest_path_length(self, src, dst, src_valid=None, dst_valid=None):
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, None, None, dst_valid, keep)
@@ -690,6 +725,21 @@ class DeviceCSR:
                                                       C.byref(paths), C.byref(used))
         return rc, paths.value, used.value
 
+    def walk_count_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, d_out_count):
+        _check(self.L.pgq_walk_count_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                 C.c_void_p(d_out_count)))
+
+    def k_shortest_walks_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, k, d_out_len, d_out_count, d_out_first, d_out_npaths,
+                                  d_path_offset, d_path_hops, path_cap, d_child, child_cap):
+        """(status, walks needed, elements needed): the capacity protocol of all_shortestpaths_bulk_ptr."""
+        paths, used = C.c_int64(0), C.c_int64(0)
+        rc = self.L.pgq_k_shortest_walks_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                     int(k), C.c_void_p(d_out_len), C.c_void_p(d_out_count),
+                                                     C.c_void_p(d_out_first), C.c_void_p(d_out_npaths), C.c_void_p(d_path_offset),
+                                                     C.c_void_p(d_path_hops), path_cap, C.c_void_p(d_child), child_cap,
+                                                     C.byref(paths), C.byref(used))
+        return rc, paths.value, used.value
+
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                                   int(max_hops), C.c_void_p(d_out), C.c_void_p(d_ok)))
@@ -835,6 +885,29 @@ class PgqState:
 
         def call(*outs):
             self._ck(self.U.pgq_udf_all_shortestpaths(self.s, csr_id, V, n, sv, dv, int(max_hops), int(max_paths), *outs))
+
+        return _all_shortestpaths(call, n, raw)
+
+    def walk_count(self, csr_id, V, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        n = len(src_sel) if src_sel is not None else len(src)
+        out = np.zeros(n, dtype=np.int64)
+        lo, hi = int(min_hops), int(max_hops)
+
+        def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            return self.U.pgq_udf_walk_count(s, csr_id, V, n, sv, dv, lo, hi, out_p, ov_p)
+
+        ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
+        return out, ok
+
+    def k_shortest_walks(self, csr_id, V, src, dst, min_hops, max_hops, k, src_valid=None, dst_valid=None, src_sel=None,
+                         dst_sel=None, raw=False):
+        keep = []
+        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
+        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
+        n = len(src_sel) if src_sel is not None else len(src)
+
+        def call(*outs):
+            self._ck(self.U.pgq_udf_k_shortest_walks(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), int(k), *outs))
 
         return _all_shortestpaths(call, n, raw)
 

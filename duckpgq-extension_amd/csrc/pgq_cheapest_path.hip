@@ -44,6 +44,7 @@
 // Not built: _multi, the two-ended search, and any speed-up of the level rounds (a long list is walked by the one wavefront
 // that finds it).
 // pgq_all_shortest.hip (shortestpath_count, all_shortestpaths) is included at this file's end: it keeps its BFS levels in H.
+// pgq_k_walks.hip (walk_count, k_shortest_walks) comes behind it: tables of its own, all_shortestpaths' saturating add and row staging.
 
 namespace pgq {
 
@@ -551,3 +552,4 @@ int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 } // extern "C"
 
 #include "pgq_all_shortest.hip" // shortestpath_count / all_shortestpaths: level rounds on this file's H table, masks and queues
+#include "pgq_k_walks.hip"      // walk_count / k_shortest_walks: rounds over all walks of lower..upper edges, tables of their own

@@ -1,0 +1,745 @@
+// pgq_k_walks.hip — walk_count and k_shortest_walks on MI355X: how many walks of lower..upper edges a row has, and the first k of
+// them as lists, shortest first, for SQL/PGQ's quantified pattern -[e]->{lower,upper} in WALK mode and its SHORTEST k.  The reference
+// has no counterpart: its binder rejects TopK (match.cpp:82-98) and filters a quantified pattern with iterativelength BETWEEN lower
+// AND upper (match.cpp:658-671), which drops a pair at distance 1 that also has a walk of 2 edges from {2,3} and never finds a cycle
+// (src == dst is 0 hops there).  Every list follows shortestpath's layout (shortest_path.cpp:43-207).
+//
+// Part of pgq_cheapest.hip's translation unit (included at the end of pgq_cheapest_path.hip behind pgq_all_shortest.hip, not compiled
+// on its own): LC, asp_sat_add and the staging helpers are defined there.  Weights are never read: the calls work on any CSR.
+//
+// The contract, for a row (src, dst), lo = min_hops, K = max_hops, over the forward CSR's slots (parallel edges are separate slots):
+//   W_0[v] = 1 if v == src else 0
+//   W_t[x] = min(INT64_MAX, sum of W_{t-1}[u] over ALL in-slots (u, x))      t = 1 .. K
+//   count  = min(INT64_MAX, sum of W_t[dst] for t = lo .. K)
+// The sums saturate at 2^63 - 1 and never wrap.  src == dst is not special: it counts the empty walk when lo == 0 and every closed
+// walk of lo..K edges.  NULL src or dst: NULL (bulk form: -1).
+//   the walks    the first min(count, k) walks, each [x_0, e_1, x_1, ..., e_t, x_t] (the empty walk is [src]).  Shorter walks come
+//                first; walks of equal length t are ordered by in-list positions read from the destination end — all_shortestpaths'
+//                order with "W_{i-1}[u] > 0" in place of "L[u] = i - 1" and W_{i-1}[u] in place of sigma[u].  Walk number r:
+//                1. the smallest t >= lo with r < W_t[dst], after subtracting W_t[dst] of the shorter lengths from r;
+//                2. x_t = dst; for i = t .. 1 scan x_i's in-list in stored order; for each in-slot (u, x_i): r < W_{i-1}[u] takes it,
+//                   otherwise r -= W_{i-1}[u];
+//                3. the taken in-slot is the m-th from u into x_i, its edge the m-th slot of u's out-list whose target is x_i.
+//                A saturated W stays valid for unranking: every emitted rank is below 2^31.
+//                For src != dst, d = dist(src, dst) and lo <= d <= K the walks of length d come first and are all_shortestpaths'
+//                lists in its order: walk 0 is shortestpath's list.
+//   no walk      count 0 (or a NULL endpoint): the row's list is NULL, no inner list, no payload.
+//   the list form's count   the rounds of a lane batch stop once none of its rows is short of k walks, and a row stops adding once it
+//                has k: d_out_count is the number of walks of lo..T edges, T the length of the row's last emitted walk.  That is
+//                `count` whenever count <= k; otherwise it is at least k and at most count (walk_count gives count itself).
+//
+// Per lane batch (at most 64 distinct sources, lane l = source l); per round t one table W_t of V x 64 int64 and one mask word per
+// vertex, M_t[v] = the lanes with W_t[v] > 0.  W_t[v][l] is only read where M_t[v] has bit l: the tables need no reset, the masks do.
+// walk_count keeps two rounds (ping-pong, 1040 B x V); k_shortest_walks keeps rounds 0..R (R <= K the last round run) for the
+// unranking: 520 B x V per round and batch, block-cache memory of the call, PGQ_ERR_OOM with nothing written if it cannot be had.
+//   0. k_walk_init: W_0[src][l] = 1, M_0, the first queue.
+//   1. k_walk_activate, round t: a wavefront per vertex v of round t-1's queue walks v's out-list 64 targets per load, ONE lane per
+//      edge does atomicOr(&M_t[n], M_{t-1}[v]) (skipped where a plain read shows nothing to add); who sees the old value 0 queues n.
+//   2. k_walk_pull, behind it: a wavefront per queued n reads n's in-list 64 entries and 64 mask words at a time, ballots the
+//      neighbours with a non-empty M_{t-1}; lane l in M_t[n] saturating-adds W_{t-1}[u][l] where M_{t-1}[u] has bit l.  One plain
+//      store per (vertex, lane), no atomics on W: the same on every run.
+//   3. k_walk_after: for t >= lo a thread per row adds W_t[dst][lane] (0 where the mask bit is clear) to the row's count, notes the
+//      first length, counts the rows still short of k; walk_count: M_{t-1} back to zero over round t-1's queue.
+//   Rounds stop after round K, with an empty queue, and (lists) when no row of the batch is short of k: k = 1 on a pair d apart
+//   costs d rounds.  walk_count has no such stop.  The host waits once per round for the counters.
+//   4. k_walk_plan, a thread per row: walks and elements per row from W_t[dst], t = lo..R; two exclusive scans place them.
+//   5. k_walk_unrank, a wavefront per emitted walk: its t by the same small loop, then all_shortestpaths' saturating prefix sum over
+//      64 in-list positions per step.  A step that finds no parent or no slot, or a walk that does not end on the lane's source,
+//      raises the error flag: PGQ_ERR_HIP.
+//   6. Behind the last batch: trivial rows (src == dst without a lane: [[src]] when lo == 0, nothing otherwise), NULL rows, scans in
+//      ROW order, k_walk_gather.  Results go to the caller only then: a call that fails has written nothing.
+// The call owns its tables, masks and queues (block cache); it does not touch ws->tight_h / tight_mask / tight_q / tight_V, so
+// PathBatches and AspCall find them as they left them.  Lists are staged in ws->tight_stage, rows in ws->asp_rows.
+// Kernel-class time: the rounds are K_PUSH, plan / unranking / gather K_RECON.
+// Not built: _multi forms, path modes TRAIL / ACYCLIC / SIMPLE, SHORTEST k GROUP, splitting long in-lists over several wavefronts (a
+// list is walked by the one wavefront that meets it), any change to how the binder's iterativelength filter is emitted.
+
+namespace pgq {
+
+struct WalkCounters {
+	u32 nq[2];   // queued vertices by round parity
+	u32 pending; // rows of the batch short of k walks
+	u32 error;   // unranking: no length / parent (2), no slot (4), not at the source (8)
+	u64 edges;   // adjacency entries the rounds walked
+};
+struct WalkRound {
+	const int64_t *W;
+	const u64 *M;
+};
+
+__device__ __forceinline__ int64_t walk_w(const WalkRound &rd, int x, u32 l) { return (rd.M[x] >> l) & 1ull ? rd.W[(size_t)x * LC + l] : 0; }
+
+__global__ void k_walk_init(const int32_t *__restrict__ usrc, int64_t U, int64_t base, int64_t *__restrict__ W0, u64 *__restrict__ M0,
+                            int32_t *__restrict__ q, WalkCounters *__restrict__ tc) {
+	const int l = threadIdx.x;
+	const int64_t g = base + l;
+	if (l == 0) {
+		tc->nq[0] = (u32)min((int64_t)LC, U - base);
+		tc->nq[1] = 0;
+		tc->pending = 0;
+		tc->error = 0;
+		tc->edges = 0;
+	}
+	if (l >= LC || g >= U) return;
+	const int v = usrc[g];
+	W0[(size_t)v * LC + l] = 1;
+	M0[v] = 1ull << l; // (distinct sources: distinct vertices)
+	q[l] = v;
+}
+__global__ void k_walk_rows(int64_t lo, int64_t hi, const u32 *__restrict__ sidx, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count) {
+	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= hi) return;
+	r_len[sidx[i]] = -1;
+	r_count[sidx[i]] = 0;
+}
+__global__ void k_walk_round_reset(WalkCounters *__restrict__ tc, int next_par) {
+	tc->nq[next_par] = 0;
+	tc->pending = 0;
+}
+
+// Round t, activation: a wavefront per vertex v of the last round's queue, a LANE per out-slot.
+__global__ __launch_bounds__(256) void k_walk_activate(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, const u64 *__restrict__ m_prev,
+                                                       u64 *__restrict__ m_cur, const int32_t *__restrict__ qprev, int32_t *__restrict__ qcur,
+                                                       WalkCounters *__restrict__ tc, int par) {
+	const int lane = threadIdx.x & 63;
+	const u32 wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+	const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
+	const u32 nq = tc->nq[par];
+	for (u32 i = wave; i < nq; i += nwaves) {
+		const int v = qprev[i];
+		const u64 mv = m_prev[v];
+		const int64_t b = off[v], e = off[v + 1];
+		for (int64_t k0 = b; k0 < e; k0 += 64) {
+			int n = -1;
+			bool fresh = false;
+			if (k0 + lane < e) {
+				n = adj[k0 + lane];
+				// (a stale read only costs the atomic it would have spared: bits are never taken away during the launch)
+				if ((__atomic_load_n(&m_cur[n], __ATOMIC_RELAXED) & mv) != mv) fresh = atomicOr(&m_cur[n], mv) == 0ull;
+			}
+			const u64 fm = __ballot(fresh); // each vertex sees the old value 0 once per round: <= V queue entries
+			if (fm) {
+				u32 at = 0;
+				if (lane == 0) at = atomicAdd(&tc->nq[par ^ 1], (u32)__popcll(fm));
+				at = __shfl(at, 0);
+				if (fresh) qcur[at + (u32)__popcll(fm & ((1ull << lane) - 1ull))] = n;
+			}
+		}
+		if (lane == 0 && e > b) atomicAdd(&tc->edges, (u64)(e - b));
+	}
+}
+
+// Round t, the sums: a wavefront per vertex n the round queued (once), lane l = source l.
+__global__ __launch_bounds__(256) void k_walk_pull(const int64_t *__restrict__ roff, const int32_t *__restrict__ radj, const int64_t *__restrict__ w_prev,
+                                                   const u64 *__restrict__ m_prev, int64_t *__restrict__ w_cur, const u64 *__restrict__ m_cur,
+                                                   const int32_t *__restrict__ qcur, WalkCounters *__restrict__ tc, int par_cur) {
+	const int lane = threadIdx.x & 63;
+	const u32 wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+	const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
+	const u32 nq = tc->nq[par_cur];
+	for (u32 i = wave; i < nq; i += nwaves) {
+		const int n = qcur[i];
+		const bool want = (m_cur[n] >> lane) & 1ull;
+		int64_t acc = 0;
+		const int64_t rb = roff[n], re = roff[n + 1];
+		for (int64_t j0 = rb; j0 < re; j0 += 64) { // 64 in-neighbours and their mask words per trip; only the active ones are visited
+			const int cand = j0 + lane < re ? radj[j0 + lane] : -1;
+			const u64 cm = cand >= 0 ? m_prev[cand] : 0ull;
+			u64 live = __ballot(cm != 0ull);
+			while (live) {
+				const int bpos = __ffsll((long long)live) - 1;
+				live &= live - 1;
+				const int u = __shfl(cand, bpos);
+				const u64 mu = __shfl(cm, bpos);
+				if (want && ((mu >> lane) & 1ull)) acc = asp_sat_add(acc, w_prev[(size_t)u * LC + lane]);
+			}
+		}
+		if (want) w_cur[(size_t)n * LC + lane] = acc; // (> 0: some in-neighbour gave the lane its mask bit)
+		if (lane == 0 && re > rb) atomicAdd(&tc->edges, (u64)(re - rb));
+	}
+}
+
+// Round t is over: the rows' counts (a row that has k_stop walks adds no more), the rows still short of k_stop; m_zero != null
+// (walk_count's ping-pong): round t-1's mask words back to zero over its queue.
+__global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx,
+                             const int32_t *__restrict__ sdst, u32 base_lane, WalkRound cur, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count,
+                             const int32_t *__restrict__ qprev, u64 *__restrict__ m_zero, int par_prev, WalkCounters *__restrict__ tc) {
+	const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (m_zero && tid < (int64_t)tc->nq[par_prev]) m_zero[qprev[tid]] = 0;
+	const int64_t i = lo + tid;
+	bool open = false;
+	if (i < hi) {
+		const u32 row = sidx[i];
+		int64_t cnt = r_count[row];
+		if (t >= min_hops && cnt < k_stop) {
+			const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
+			if (w > 0) {
+				if (r_len[row] < 0) r_len[row] = t;
+				cnt = asp_sat_add(cnt, w);
+				r_count[row] = cnt;
+			}
+		}
+		open = cnt < k_stop;
+	}
+	const u64 om = __ballot(open);
+	if (om && (threadIdx.x & 63) == 0) atomicAdd(&tc->pending, (u32)__popcll(om));
+}
+
+// per row of the batch: the walks it emits and their elements; staged per row as [hops of each walk][the walks' elements]
+__global__ void k_walk_plan(int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst,
+                            u32 base_lane, const WalkRound *__restrict__ tabs, int64_t min_hops, int rounds, int64_t k, int64_t *__restrict__ r_np,
+                            int64_t *__restrict__ r_el, int64_t *__restrict__ cntp, int64_t *__restrict__ cnte) {
+	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= hi) return;
+	const int x = sdst[i];
+	const u32 l = skey[i] - base_lane;
+	int64_t rem = k, np = 0, el = 0;
+	for (int64_t t = min_hops; t <= rounds && rem > 0; t++) {
+		const int64_t take = min(walk_w(tabs[t], x, l), rem);
+		np += take;
+		el += take * (2 * t + 1); // take <= 2^31, 2 t + 1 <= 129
+		rem -= take;
+	}
+	const u32 row = sidx[i];
+	r_np[row] = np;
+	r_el[row] = el;
+	cntp[i - lo] = np;
+	cnte[i - lo] = np > 0 ? np + el : 0;
+}
+
+// One wavefront per emitted walk (row, rank): its length, then the list, written back to front into the row's staged block.
+__global__ __launch_bounds__(64) void k_walk_unrank(int64_t lo, int64_t m, int64_t nwalks, const u32 *__restrict__ skey, const int32_t *__restrict__ sdst,
+                                                   u32 base_lane, const int32_t *__restrict__ usrc, const int64_t *__restrict__ off,
+                                                   const int32_t *__restrict__ adj, const int64_t *__restrict__ edge_ids,
+                                                   const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
+                                                   const WalkRound *__restrict__ tabs, int64_t min_hops, int rounds,
+                                                   const int64_t *__restrict__ ploc, const int64_t *__restrict__ eloc, int64_t stage_base,
+                                                   int64_t *__restrict__ stage, int64_t *__restrict__ soff, WalkCounters *__restrict__ tc) {
+	const int lane = threadIdx.x;
+	for (int64_t p = blockIdx.x; p < nwalks; p += gridDim.x) {
+		// the row: the last j in [0, m) with ploc[j] <= p (rows without walks share their successor's start and are passed over)
+		int64_t a = 0, b = m;
+		while (b - a > 1) {
+			const int64_t mid = (a + b) >> 1;
+			if (ploc[mid] <= p) a = mid;
+			else b = mid;
+		}
+		const int64_t i = lo + a;
+		const int64_t rank = p - ploc[a], np = ploc[a + 1] - ploc[a];
+		int64_t r = rank;
+		const u32 l = skey[i] - base_lane;
+		int x = sdst[i];
+		// the walk's length: the shorter lengths' walks come first
+		int64_t eoff = 0;
+		int t = -1;
+		for (int64_t tt = min_hops; tt <= rounds; tt++) {
+			const int64_t w = walk_w(tabs[tt], x, l);
+			if (r < w) {
+				t = (int)tt;
+				break;
+			}
+			r -= w; // (w <= r < 2^31)
+			eoff += w * (2 * tt + 1);
+		}
+		if (t < 0) { // (k_walk_plan gave the row no such walk)
+			if (lane == 0) atomicOr(&tc->error, 2u);
+			continue;
+		}
+		const int64_t rowbase = stage_base + eloc[a];
+		int64_t *out = stage + rowbase + np + eoff + r * (2 * (int64_t)t + 1);
+		if (lane == 0) {
+			if (rank == 0) soff[i] = rowbase;
+			stage[rowbase + rank] = t;
+			out[2 * t] = x;
+		}
+		bool lost = false;
+		for (int s = t; s >= 1 && !lost; s--) {
+			const WalkRound pr = tabs[s - 1];
+			const int64_t rb = roff[x], re = roff[x + 1];
+			int64_t jsel = -1;
+			int u = -1;
+			for (int64_t j0 = rb; j0 < re; j0 += 64) {
+				const int64_t j = j0 + lane;
+				const int cand = j < re ? radj[j] : -1;
+				const int64_t sg = cand >= 0 ? walk_w(pr, cand, l) : 0;
+				int64_t inc = sg; // saturating inclusive prefix sum over the wavefront
+				for (int o = 1; o < 64; o <<= 1) {
+					const int64_t y = __shfl_up(inc, o);
+					if (lane >= o) inc = asp_sat_add(inc, y);
+				}
+				int64_t exc = __shfl_up(inc, 1);
+				if (lane == 0) exc = 0;
+				const u64 hit = __ballot(r < inc); // inc never falls along the lanes: the first lane past r holds the slot
+				if (hit) {
+					const int pos = __ffsll((long long)hit) - 1;
+					r -= __shfl(exc, pos);
+					u = __shfl(cand, pos);
+					jsel = j0 + pos;
+					break;
+				}
+				r -= __shfl(inc, 63); // (<= r, so it is a true sum)
+			}
+			if (jsel < 0) {
+				if (lane == 0) atomicOr(&tc->error, 2u);
+				lost = true;
+				break;
+			}
+			// the taken in-slot is the mth from u into x (they are consecutive: the in-list is ordered by parent, then forward slot)
+			int mth = 0;
+			for (int64_t j = rb + lane; j < jsel; j += 64) mth += radj[j] == u ? 1 : 0;
+			for (int o = 32; o > 0; o >>= 1) mth += __shfl_xor(mth, o);
+			// ... its edge the mth slot of u's out-list into x
+			int64_t slot = -1;
+			const int64_t fb = off[u], fe = off[u + 1];
+			for (int64_t e0 = fb; e0 < fe && slot < 0; e0 += 64) {
+				const int64_t e = e0 + lane;
+				u64 hm = __ballot(e < fe && adj[e] == x);
+				const int c = __popcll(hm);
+				if (mth < c) {
+					for (int k = 0; k < mth; k++) hm &= hm - 1;
+					slot = e0 + __ffsll((long long)hm) - 1;
+				} else {
+					mth -= c;
+				}
+			}
+			if (slot < 0) {
+				if (lane == 0) atomicOr(&tc->error, 4u);
+				lost = true;
+				break;
+			}
+			if (lane == 0) {
+				out[2 * s - 1] = edge_ids ? edge_ids[slot] : slot;
+				out[2 * s - 2] = u;
+			}
+			x = u;
+		}
+		if (!lost && lane == 0 && x != usrc[base_lane + l]) atomicOr(&tc->error, 8u);
+	}
+}
+
+// rows without a lane.  Trivial: src == dst with no out-edge or no in-edge — the empty walk when min_hops == 0, nothing otherwise;
+// the others: a NULL endpoint (count -1) or a row that cannot have a walk (0)
+__global__ void k_walk_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, int64_t min_hops, const u32 *__restrict__ sidx, const int64_t *__restrict__ src,
+                             const int64_t *__restrict__ dst, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np,
+                             int64_t *__restrict__ r_el) {
+	const int64_t i = lo_trivial + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const u32 row = sidx[i];
+	const bool empty_walk = i < lo_null && min_hops == 0;
+	r_len[row] = empty_walk ? 0 : -1;
+	r_count[row] = empty_walk ? 1 : (i >= lo_null && (src[row] < 0 || dst[row] < 0) ? -1 : 0);
+	if (r_np) r_np[row] = r_el[row] = empty_walk ? 1 : 0;
+}
+
+// Row order: a wavefront per sorted position below lo_null copies the row's staged walks to its place in the child payload and
+// writes its inner entries (offsets from a running prefix sum over the walks' lengths); trivial rows write their [src].
+__global__ __launch_bounds__(64) void k_walk_gather(int64_t lo_trivial, int64_t lo_null, const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst,
+                                                   const int64_t *__restrict__ r_np, const int64_t *__restrict__ r_el, const int64_t *__restrict__ r_first,
+                                                   const int64_t *__restrict__ r_eoff, const int64_t *__restrict__ soff, const int64_t *__restrict__ stage,
+                                                   int64_t *__restrict__ path_off, int64_t *__restrict__ path_hops, int64_t *__restrict__ path_len,
+                                                   int64_t *__restrict__ child) {
+	const int lane = threadIdx.x;
+	for (int64_t i = blockIdx.x; i < lo_null; i += gridDim.x) {
+		const u32 row = sidx[i];
+		const int64_t np = r_np[row];
+		if (np <= 0) continue;
+		const int64_t f = r_first[row], eo = r_eoff[row];
+		if (i >= lo_trivial) {
+			if (lane == 0) {
+				child[eo] = sdst[i];
+				path_off[f] = eo;
+				if (path_hops) path_hops[f] = 0;
+				if (path_len) path_len[f] = 1;
+			}
+			continue;
+		}
+		const int64_t *hp = stage + soff[i], *in = hp + np;
+		const int64_t el = r_el[row];
+		for (int64_t k = lane; k < el; k += 64) child[eo + k] = in[k];
+		int64_t run = 0;
+		for (int64_t k0 = 0; k0 < np; k0 += 64) {
+			const int64_t k = k0 + lane;
+			const int64_t h = k < np ? hp[k] : 0, w = k < np ? 2 * h + 1 : 0;
+			int64_t inc = w;
+			for (int o = 1; o < 64; o <<= 1) {
+				const int64_t y = __shfl_up(inc, o);
+				if (lane >= o) inc += y;
+			}
+			if (k < np) {
+				path_off[f + k] = eo + run + inc - w;
+				if (path_hops) path_hops[f + k] = h;
+				if (path_len) path_len[f + k] = w;
+			}
+			run += __shfl(inc, 63);
+		}
+	}
+}
+
+// Where one call's results go.  lists = false: the counts alone (d_count).  External buffers (bulk form) with their capacities,
+// or none (chunk form): then the inner entries and the payload land in ws->asp_paths / ws->child, grown to fit.
+struct WalkOut {
+	bool lists = false;
+	int64_t k = 1;
+	int64_t *d_len = nullptr, *d_count = nullptr, *d_first = nullptr, *d_np = nullptr;
+	int64_t *d_path_off = nullptr, *d_path_hops = nullptr, path_cap = 0, *d_child = nullptr, child_cap = 0;
+	bool external = false;
+	int64_t paths_used = 0, child_used = 0;
+	bool overflow = false;
+};
+
+class WalkCall {
+public:
+	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, WalkOut &out)
+	    : c(c), ws(ws), n(n), d_src(d_src), d_dst(d_dst), min_hops(min_hops), max_hops(max_hops), out(out), temps(ws->stream) {}
+
+	int run() {
+		S.pairs += n;
+		if (n == 0) return PGQ_OK;
+		if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
+		u32 U = 0;
+		PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U, true, true));
+		S.unique_sources += U;
+		const int nb = (int)(((int64_t)U + LC - 1) / LC);
+		PGQ_TRY(batch_bounds(ws, n, LC, nb));
+		// the rows' results, in row order: first length, count, walks, elements, first walk, first element (n + 1 entries each)
+		PGQ_TRY(ws->asp_rows.reserve((size_t)(n + 1) * 8 * 6));
+		int64_t *rows = ws->asp_rows.as<int64_t>();
+		r_len = rows, r_count = rows + (n + 1), r_np = rows + 2 * (n + 1), r_el = rows + 3 * (n + 1), r_first = rows + 4 * (n + 1), r_eoff = rows + 5 * (n + 1);
+		if (nb > 0) {
+			PGQ_TRY(prepare());
+			const int64_t *bs = ws->h_bstart;
+			for (int b = 0; b < nb; b++) PGQ_TRY(batch(bs[b], bs[b + 1], (int64_t)b * LC, U));
+			PGQ_HIP_TRY(hipStreamSynchronize(st));
+			KernelTimer::flush();
+		}
+		return layout(nb);
+	}
+
+private:
+	pgq_csr *const c;
+	Workspace *const ws;
+	const int64_t n;
+	const int64_t *const d_src, *const d_dst;
+	const int64_t min_hops, max_hops;
+	WalkOut &out;
+	DevTemps temps; // the rounds' tables, masks and queues: block-cache memory for the call
+	const hipStream_t st = ws->stream;
+	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
+	pgq_stats_t &S = tstats().s;
+	WalkCounters *tc = nullptr;
+	std::vector<int64_t *> W; // lists: one per round; counts: two
+	std::vector<u64 *> M;
+	std::vector<WalkRound> h_tabs;
+	WalkRound *d_tabs = nullptr;
+	int32_t *q[2] = { nullptr, nullptr };
+	int64_t *r_len = nullptr, *r_count = nullptr, *r_np = nullptr, *r_el = nullptr, *r_first = nullptr, *r_eoff = nullptr;
+	int64_t staged = 0, walks_so_far = 0;
+
+	int read_back(void *host, const void *dev, size_t bytes) {
+		PGQ_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		KernelTimer::flush();
+		return PGQ_OK;
+	}
+	size_t slot_of(int64_t t) const { return out.lists ? (size_t)t : (size_t)(t & 1); }
+	// round t's table and (zeroed) mask
+	int ensure_round(int64_t t) {
+		while (W.size() <= slot_of(t)) {
+			int64_t *w = nullptr;
+			u64 *m = nullptr;
+			PGQ_TRY(temps.alloc(&w, Vn * LC));
+			PGQ_TRY(temps.alloc(&m, Vn));
+			PGQ_HIP_TRY(hipMemsetAsync(m, 0, Vn * 8, st));
+			W.push_back(w), M.push_back(m);
+		}
+		return PGQ_OK;
+	}
+	WalkRound round_of(int64_t t) const { return WalkRound { W[slot_of(t)], M[slot_of(t)] }; }
+
+	int prepare() {
+		PGQ_TRY(ws->tight_cnt.reserve(std::max(sizeof(WalkCounters), sizeof(TightCounters))));
+		tc = ws->tight_cnt.as<WalkCounters>();
+		if (out.lists) {
+			PGQ_TRY(ensure_edge_ids(c));
+			PGQ_TRY(temps.alloc(&d_tabs, (size_t)PGQ_WALK_MAX_HOPS + 1));
+		}
+		for (int32_t *&b : q) PGQ_TRY(temps.alloc(&b, Vn));
+		return PGQ_OK;
+	}
+
+	// rows [lo, hi) of the sorted arrays, lane 0 = distinct source `base`
+	int batch(int64_t lo, int64_t hi, int64_t base, u32 U) {
+		const int64_t m = hi - lo;
+		const unsigned cus = (unsigned)device_cus();
+		const int64_t k_stop = out.lists ? out.k : kAspMax;
+		const u32 *skey = ws->skey.as<u32>(), *sidx = ws->sidx.as<u32>();
+		const int32_t *sdst = ws->sdst.as<int32_t>();
+		WalkCounters h {};
+		S.batches++;
+		for (u64 *mk : M) PGQ_HIP_TRY(hipMemsetAsync(mk, 0, Vn * 8, st)); // what the batch before left
+		PGQ_TRY(ensure_round(0));
+		u32 nq = (u32)std::min<int64_t>(LC, (int64_t)U - base);
+		{
+			KernelTimer kt(st, K_PUSH);
+			hipLaunchKernelGGL(k_walk_init, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base, W[0], M[0], q[0], tc);
+			if (m > 0) hipLaunchKernelGGL(k_walk_rows, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, sidx, r_len, r_count);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, min_hops, k_stop, lo, hi, skey, sidx, sdst, (u32)base,
+			                   round_of(0), r_len, r_count, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
+			kt.stop();
+		}
+		PGQ_TRY(read_back(&h, tc, sizeof(h)));
+		int par = 0;
+		int rounds = 0;
+		for (int64_t t = 1; t <= max_hops && nq > 0 && m > 0 && !(out.lists && h.pending == 0); t++) {
+			PGQ_TRY(ensure_round(t));
+			KernelTimer kt(st, K_PUSH);
+			const WalkRound prev = round_of(t - 1), cur = round_of(t);
+			hipLaunchKernelGGL(k_walk_round_reset, dim3(1), dim3(1), 0, st, tc, par ^ 1);
+			hipLaunchKernelGGL(k_walk_activate, dim3(std::min(cus * 8, std::max(1u, (nq + 3) / 4))), dim3(256), 0, st, c->off, c->adj, prev.M, M[slot_of(t)], q[par],
+			                   q[par ^ 1], tc, par);
+			// (the new queue's fill is not known here: the grid is sized for a queue of any size, its wavefronts stride)
+			hipLaunchKernelGGL(k_walk_pull, dim3(cus * 8), dim3(256), 0, st, c->roff, c->radj, prev.W, prev.M, W[slot_of(t)], cur.M, q[par ^ 1], tc, par ^ 1);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, lo, hi, skey, sidx, sdst, (u32)base,
+			                   cur, r_len, r_count, (const int32_t *)q[par], out.lists ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
+			kt.stop();
+			PGQ_TRY(read_back(&h, tc, sizeof(h)));
+			S.levels++;
+			rounds = (int)t;
+			par ^= 1;
+			nq = h.nq[par];
+		}
+		S.edges_scanned += (int64_t)h.edges;
+		S.algo_bytes[K_PUSH] += (double)h.edges * (4.0 + 8.0 + 512.0);
+		if (!out.lists) return PGQ_OK;
+		// walks and elements per row; where the batch's walks and staged blocks go
+		PGQ_TRY(ws->def_len.reserve((size_t)(m + 1) * 8 * 2));
+		PGQ_TRY(ws->def_ent.reserve((size_t)(m + 1) * 8 * 2));
+		int64_t *cntp = ws->def_len.as<int64_t>(), *cnte = cntp + (m + 1);
+		int64_t *ploc = ws->def_ent.as<int64_t>(), *eloc = ploc + (m + 1);
+		int64_t totals[2] = { 0, 0 };
+		h_tabs.assign((size_t)PGQ_WALK_MAX_HOPS + 1, WalkRound { nullptr, nullptr });
+		for (int t = 0; t <= rounds; t++) h_tabs[t] = round_of(t);
+		PGQ_HIP_TRY(hipMemcpyAsync(d_tabs, h_tabs.data(), h_tabs.size() * sizeof(WalkRound), hipMemcpyHostToDevice, st));
+		{
+			KernelTimer kt(st, K_RECON);
+			PGQ_HIP_TRY(hipMemsetAsync(cntp, 0, (size_t)(m + 1) * 8 * 2, st));
+			if (m > 0)
+				hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, min_hops, rounds, out.k, r_np, r_el,
+				                   cntp, cnte);
+			PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cntp, ploc, (int)(m + 1), st); }));
+			PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnte, eloc, (int)(m + 1), st); }));
+			kt.stop();
+		}
+		PGQ_HIP_TRY(hipMemcpyAsync(&totals[0], ploc + m, 8, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipMemcpyAsync(&totals[1], eloc + m, 8, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		KernelTimer::flush();
+		walks_so_far += totals[0];
+		if (walks_so_far > 0x7FFFFFFFll) return fail(PGQ_ERR_UNSUPPORTED, "k_shortest_walks: the call would emit more than 2^31-1 walks");
+		const size_t need = (size_t)(staged + totals[1]) * 8;
+		if (need > ws->tight_stage.cap) PGQ_TRY(grow_keeping(ws->tight_stage, std::max(need, 2 * ws->tight_stage.cap), (size_t)staged * 8, st));
+		const int64_t at = staged;
+		staged += totals[1];
+		S.algo_bytes[K_RECON] += (double)totals[1] * 8.0;
+		if (totals[0] > 0) {
+			KernelTimer kt(st, K_RECON);
+			hipLaunchKernelGGL(k_walk_unrank, dim3((unsigned)std::min<int64_t>(totals[0], 1 << 20)), dim3(64), 0, st, lo, m, totals[0], skey, sdst, (u32)base,
+			                   ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, min_hops, rounds, ploc, eloc, at,
+			                   ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+			kt.stop();
+		}
+		PGQ_TRY(read_back(&h, tc, sizeof(h))); // (also: the next batch's memsets and table upload come behind this batch's kernels)
+		if (h.error) return fail(PGQ_ERR_HIP, "k_shortest_walks: internal error: the unranking lost its way (no parent, no slot, or not at the source)");
+		return PGQ_OK;
+	}
+
+	// behind the last batch: the trivial and NULL rows, the scans in row order, capacities, the gather, the caller's arrays
+	int layout(int nb) {
+		const int64_t *bs = ws->h_bstart;
+		const int64_t lo_t = bs[nb + 1], lo_n = bs[nb + 2];
+		int64_t totals[2] = { 0, 0 };
+		KernelTimer kt(st, K_RECON);
+		if (n > lo_t)
+			hipLaunchKernelGGL(k_walk_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, lo_n, n, min_hops, ws->sidx.as<u32>(), d_src, d_dst, r_len, r_count,
+			                   out.lists ? r_np : nullptr, r_el);
+		if (!out.lists) {
+			PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+			kt.stop();
+			PGQ_HIP_TRY(hipStreamSynchronize(st));
+			KernelTimer::flush();
+			return PGQ_OK;
+		}
+		PGQ_HIP_TRY(hipMemsetAsync(r_np + n, 0, 8, st));
+		PGQ_HIP_TRY(hipMemsetAsync(r_el + n, 0, 8, st));
+		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, r_np, r_first, (int)(n + 1), st); }));
+		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, r_el, r_eoff, (int)(n + 1), st); }));
+		PGQ_HIP_TRY(hipMemcpyAsync(&totals[0], r_first + n, 8, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipMemcpyAsync(&totals[1], r_eoff + n, 8, hipMemcpyDeviceToHost, st));
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		if (totals[0] > 0x7FFFFFFFll) return fail(PGQ_ERR_UNSUPPORTED, "k_shortest_walks: the call would emit more than 2^31-1 walks");
+		out.paths_used = totals[0];
+		out.child_used = totals[1];
+		int64_t *path_off = out.d_path_off, *path_hops = out.d_path_hops, *path_len = nullptr, *child = out.d_child;
+		if (!out.external) {
+			PGQ_TRY(ws->asp_paths.reserve((size_t)std::max<int64_t>(totals[0], 1) * 8 * 2));
+			PGQ_TRY(ws->child.reserve((size_t)std::max<int64_t>(totals[1], 1) * 8));
+			path_off = ws->asp_paths.as<int64_t>();
+			path_len = path_off + std::max<int64_t>(totals[0], 1);
+			child = ws->child.as<int64_t>();
+		} else if (totals[0] > out.path_cap || totals[1] > out.child_cap) {
+			out.overflow = true;
+		}
+		if (!out.overflow && lo_n > 0)
+			hipLaunchKernelGGL(k_walk_gather, dim3((unsigned)std::min<int64_t>(lo_n, 1 << 20)), dim3(64), 0, st, lo_t, lo_n, ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
+			                   r_np, r_el, r_first, r_eoff, ws->soff.as<int64_t>(), ws->tight_stage.as<int64_t>(), path_off, path_hops, path_len, child);
+		PGQ_HIP_TRY(hipMemcpyAsync(out.d_len, r_len, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+		PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+		PGQ_HIP_TRY(hipMemcpyAsync(out.d_np, r_np, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+		if (!out.overflow) PGQ_HIP_TRY(hipMemcpyAsync(out.d_first, r_first, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+		kt.stop();
+		PGQ_HIP_TRY(hipStreamSynchronize(st));
+		KernelTimer::flush();
+		S.algo_bytes[K_RECON] += (double)totals[1] * 16.0 + (double)totals[0] * 24.0 + (double)n * 64.0;
+		return PGQ_OK;
+	}
+};
+
+} // namespace pgq
+
+using namespace pgq;
+
+extern "C" {
+
+static int walk_check_bounds(int64_t min_hops, int64_t max_hops, const int64_t *k) {
+	if (min_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "min_hops must not be negative");
+	if (max_hops < min_hops) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be below min_hops");
+	if (k && *k < 1) return fail(PGQ_ERR_INVALID_ARG, "k must be at least 1");
+	if (max_hops > PGQ_WALK_MAX_HOPS)
+		return fail(PGQ_ERR_UNSUPPORTED, "walks need an upper bound of at most " + std::to_string(PGQ_WALK_MAX_HOPS) +
+		                                     " edges: in a cyclic graph the number of walks is unbounded");
+	return PGQ_OK;
+}
+
+int pgq_walk_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops,
+                               int64_t *d_out_count) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_count, "NULL device array"));
+		return walk_check_bounds(min_hops, max_hops, nullptr);
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		WalkOut out;
+		out.d_count = d_out_count;
+		return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, out).run();
+	});
+}
+
+int pgq_k_shortest_walks_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t k,
+                                     int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths, int64_t *d_path_offset,
+                                     int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used, int64_t *child_used) {
+	if (paths_used) *paths_used = 0;
+	if (child_used) *child_used = 0;
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_len && d_out_count && d_out_first && d_out_npaths && d_path_offset && d_path_hops && d_child,
+		                     "NULL device array"));
+		if (path_cap < 0 || child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
+		return walk_check_bounds(min_hops, max_hops, &k);
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		WalkOut out;
+		out.lists = true, out.external = true;
+		out.k = std::min<int64_t>(k, 1LL << 31);
+		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths;
+		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
+		const int rc = WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, out).run();
+		if (rc == PGQ_OK) {
+			if (paths_used) *paths_used = out.paths_used;
+			if (child_used) *child_used = out.child_used;
+			if (out.overflow) return fail(PGQ_ERR_INVALID_ARG, "path or child buffer too small for the lists (see *paths_used, *child_used)");
+		}
+		return rc;
+	});
+}
+
+int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t *out_count,
+                   uint64_t *out_valid) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
+		if (n < 0 || (n > 0 && (!out_count || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		PGQ_TRY(walk_check_bounds(min_hops, max_hops, nullptr));
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		PGQ_TRY(asp_stage_rows(ws, V, n, src, dst));
+		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
+		WalkOut out;
+		out.d_count = ws->out_len.as<int64_t>();
+		PGQ_TRY(WalkCall(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), min_hops, max_hops, out).run());
+		std::vector<int64_t> cnt((size_t)n);
+		PGQ_TRY(staged_download(cnt.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
+		mask_fill_valid(out_valid, n);
+		for (int64_t i = 0; i < n; i++) {
+			out_count[i] = cnt[i];
+			if (cnt[i] < 0) mask_set_invalid(out_valid, i);
+		}
+		return PGQ_OK;
+	});
+}
+
+int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t k,
+                         uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
+                         uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
+		if (n < 0 || (n > 0 && (!out_first || !out_npaths || !out_valid)) || !out_path_offset || !out_path_length || !out_path_total || !out_child || !out_child_len)
+			return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+		PGQ_TRY(walk_check_bounds(min_hops, max_hops, &k));
+		*out_path_offset = *out_path_length = nullptr;
+		*out_child = nullptr;
+		*out_path_total = *out_child_len = 0;
+		return n == 0 ? kNoRows : PGQ_OK;
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		PGQ_TRY(asp_stage_rows(ws, V, n, src, dst));
+		for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve((size_t)n * 8 * 2));
+		WalkOut out;
+		out.lists = true;
+		out.k = std::min<int64_t>(k, 1LL << 31);
+		out.d_len = ws->out_len.as<int64_t>(), out.d_count = out.d_len + n, out.d_first = ws->out_off.as<int64_t>(), out.d_np = out.d_first + n;
+		PGQ_TRY(WalkCall(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), min_hops, max_hops, out).run());
+		std::vector<int64_t> len(n), first_np((size_t)2 * n);
+		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
+		PGQ_TRY(staged_download(first_np.data(), ws->out_off.p, (size_t)n * 8 * 2, ws->stream));
+		// one arena block, filled whole before the caller's arrays are touched: the child payload, then the inner entries' offsets and lengths
+		const size_t P = (size_t)out.paths_used, C = (size_t)out.child_used;
+		std::vector<int64_t> &arena = thread_child_arena();
+		arena.resize(C + 2 * P);
+		if (C > 0) PGQ_TRY(staged_download(arena.data(), ws->child.p, C * 8, ws->stream));
+		if (P > 0) {
+			PGQ_TRY(staged_download(arena.data() + C, ws->asp_paths.p, P * 8, ws->stream));
+			PGQ_TRY(staged_download(arena.data() + C + P, ws->asp_paths.as<int64_t>() + P, P * 8, ws->stream));
+		}
+		mask_fill_valid(out_valid, n);
+		for (int64_t i = 0; i < n; i++) {
+			if (len[i] < 0) {
+				mask_set_invalid(out_valid, i);
+				out_first[i] = 0;
+				out_npaths[i] = 0;
+			} else {
+				out_first[i] = (uint64_t)first_np[i];
+				out_npaths[i] = (uint64_t)first_np[(size_t)n + i];
+			}
+		}
+		*out_child = arena.data();
+		*out_child_len = (uint64_t)C;
+		*out_path_offset = reinterpret_cast<const uint64_t *>(arena.data() + C);
+		*out_path_length = reinterpret_cast<const uint64_t *>(arena.data() + C + P);
+		*out_path_total = (uint64_t)P;
+		return PGQ_OK;
+	});
+}
+
+} // extern "C"

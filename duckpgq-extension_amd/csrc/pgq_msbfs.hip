@@ -90,19 +90,20 @@ __device__ __forceinline__ bool pair_needs_search(int64_t s, int64_t d, const in
 	return off[s + 1] > off[s] && (!dst_rule || roff[d + 1] > roff[d]);
 }
 
+// closed_rows (the walk calls, pgq_k_walks.hip): a src == dst row takes a lane like any other, its closed walks count.
 // sm.h_go != null: workgroup 0 also takes the pre-pass's sample of the distinct sources (a call the route memo sent
 // straight to the lane batches keeps asking whether its rows still look like a cross product; the verdict lands in pinned
 // memory and is read after the lane assignment's wait).  It rides in this launch: the other workgroups take as long anyway.
 __global__ __launch_bounds__(256) void k_mark_sources(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                       u32 *__restrict__ flag, int64_t V, const int64_t *__restrict__ off,
                                                       const int64_t *__restrict__ roff, int dst_rule, int *__restrict__ bad,
-                                                      SampleArgs sm) {
+                                                      SampleArgs sm, int closed_rows) {
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) {
 		int64_t s = src[i], d = dst[i];
 		if (s >= 0) { // not a NULL row
 			if (s >= V || d < 0 || d >= V) *bad = 1;
-			else if (s != d && pair_needs_search(s, d, off, roff, dst_rule)) flag[s] = 1;
+			else if ((s != d || closed_rows) && pair_needs_search(s, d, off, roff, dst_rule)) flag[s] = 1;
 		}
 	}
 	__shared__ u32 s_set[kSampleSlots];
@@ -130,13 +131,14 @@ __global__ void k_prep_zero(u32 *__restrict__ flag, int64_t n_flag, u32 *__restr
 __global__ void k_pair_keys(int64_t n, const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                             const u32 *__restrict__ rank, const int64_t *__restrict__ off,
                             const int64_t *__restrict__ roff, int dst_rule, int64_t V, u32 key_trivial, u32 key_nolane,
-                            u32 *__restrict__ key, u32 *__restrict__ idx) {
+                            u32 *__restrict__ key, u32 *__restrict__ idx, int closed_rows) {
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	int64_t s = src[i], d = dst[i];
 	u32 k = key_nolane;
 	if (s >= 0 && s < V && d >= 0 && d < V) {
-		if (s == d) k = key_trivial;
+		// closed_rows: only a src == dst row that cannot have a closed walk (no out-edge, or no in-edge) stays trivial
+		if (s == d && !(closed_rows && pair_needs_search(s, d, off, roff, dst_rule))) k = key_trivial;
 		else if (pair_needs_search(s, d, off, roff, dst_rule)) k = rank[s];
 	}
 	key[i] = k;
@@ -1600,7 +1602,7 @@ __global__ void k_trivial_paths(int64_t lo, int64_t hi, const int32_t *__restric
 // of distinct sources and the range check come back with ONE wait.
 static int lane_ranks(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, u32 *U_out,
                       bool dst_rule, const SampleArgs &sm = SampleArgs { 0.0, 0.0, nullptr, nullptr, 0, nullptr, 0 },
-                      const std::function<int()> &pre_wait = nullptr) {
+                      const std::function<int()> &pre_wait = nullptr, bool closed_rows = false) {
 	hipStream_t st = ws->stream;
 	const int64_t V = c->V;
 	for (DevBuf *b : { &ws->flag, &ws->rank }) PGQ_TRY(b->reserve((size_t)(V + 1) * 4));
@@ -1611,7 +1613,8 @@ static int lane_ranks(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src
 	int *d_bad = reinterpret_cast<int *>(ws->counters.p); // reused before the batch loop resets it
 	KernelTimer kt(st, K_PREP);
 	hipLaunchKernelGGL(k_prep_zero, dim3(blocks_for(V + 1)), dim3(256), 0, st, ws->flag.as<u32>(), V + 1, ws->counters.as<u32>(), (int)(sizeof(Counters) / 4));
-	hipLaunchKernelGGL(k_mark_sources, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->flag.as<u32>(), V, c->off, c->roff, dst_rule ? 1 : 0, d_bad, sm);
+	hipLaunchKernelGGL(k_mark_sources, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->flag.as<u32>(), V, c->off, c->roff, dst_rule ? 1 : 0, d_bad, sm,
+	                   closed_rows ? 1 : 0);
 	PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) {
 		return hipcub::DeviceScan::ExclusiveSum(tmp, tb, ws->flag.as<u32>(), ws->rank.as<u32>(), (int)(V + 1), st);
 	}));
@@ -1646,12 +1649,12 @@ static int reserve_bstart(Workspace *ws, int nb) {
 // Stage 2, rows grouped by lane: keys -> stable radix sort over `bits` key bits -> sorted copies.  The two sentinels
 // (trivial rows, rows without a lane) sort behind every lane.
 static int lane_rows_sorted(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, bool dst_rule,
-                            u32 key_trivial, u32 key_nolane, int bits) {
+                            u32 key_trivial, u32 key_nolane, int bits, bool closed_rows = false) {
 	hipStream_t st = ws->stream;
 	for (DevBuf *b : { &ws->key, &ws->idx, &ws->sidx }) PGQ_TRY(b->reserve((size_t)n * 4));
 	KernelTimer kt(st, K_PREP);
 	hipLaunchKernelGGL(k_pair_keys, dim3(blocks_for(n)), dim3(256), 0, st, n, d_src, d_dst, ws->rank.as<u32>(), c->off, c->roff, dst_rule ? 1 : 0, c->V,
-	                   key_trivial, key_nolane, ws->key.as<u32>(), ws->idx.as<u32>());
+	                   key_trivial, key_nolane, ws->key.as<u32>(), ws->idx.as<u32>(), closed_rows ? 1 : 0);
 	PGQ_TRY(cub_run(ws->sort_tmp, [&](void *tmp, size_t &tb) {
 		return hipcub::DeviceRadixSort::SortPairs(tmp, tb, ws->key.as<u32>(), ws->skey.as<u32>(), ws->idx.as<u32>(), ws->sidx.as<u32>(), (int)n, 0, bits, st);
 	}));
@@ -1665,11 +1668,11 @@ static int lane_rows_sorted(pgq_csr *c, Workspace *ws, int64_t n, const int64_t 
 }
 
 // The cheapest-path driver's entry: lanes ranked, rows sorted by lane under the classic sentinels (its own batch width
-// goes to batch_bounds afterwards).
+// goes to batch_bounds afterwards).  closed_rows: src == dst rows take a lane too (see k_mark_sources).
 int prepare_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, u32 *U_out,
-                  bool dst_rule) {
-	PGQ_TRY(lane_ranks(c, ws, n, d_src, d_dst, U_out, dst_rule));
-	return lane_rows_sorted(c, ws, n, d_src, d_dst, dst_rule, kTrivial, kNoLane, 32);
+                  bool dst_rule, bool closed_rows) {
+	PGQ_TRY(lane_ranks(c, ws, n, d_src, d_dst, U_out, dst_rule, SampleArgs { 0.0, 0.0, nullptr, nullptr, 0, nullptr, 0 }, nullptr, closed_rows));
+	return lane_rows_sorted(c, ws, n, d_src, d_dst, dst_rule, kTrivial, kNoLane, 32, closed_rows);
 }
 
 // Stage 2, rows in place: every row's lane id, endpoints and result word, in the caller's order

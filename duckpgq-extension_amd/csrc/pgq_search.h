@@ -325,6 +325,7 @@ struct Workspace {
 	// shortestpath_count / all_shortestpaths (pgq_all_shortest.hip): the rows' results in row order until the call has succeeded,
 	// and the chunk form's inner list entries.  The levels live in tight_h and the tight_* frontier buffers (same invariants),
 	// the staged lists in tight_stage; sigma is block-cache memory of the call
+	// (walk_count / k_shortest_walks, pgq_k_walks.hip, use asp_rows, asp_paths, tight_stage and tight_cnt, and nothing else of the tight_* state)
 	DevBuf asp_rows, asp_paths;
 	~Workspace();
 };
@@ -430,9 +431,11 @@ int meet_apply_paths(Workspace *ws, int64_t nd, const int64_t *d_len, const int6
                      int64_t *d_out_len, int64_t *d_out_off);
 int meet_apply(Workspace *ws, int64_t nd, const int64_t *d_len, int64_t *d_out);
 // Assigns one lane per distinct source: fills ws->usrc (lane -> vertex), the row arrays sorted by lane
-// (skey/sidx/ssrc/sdst/sres) and returns the number of distinct sources in *U.
+// (skey/sidx/ssrc/sdst/sres) and returns the number of distinct sources in *U.  src == dst rows are "trivial" and take no
+// lane; closed_rows (walk_count / k_shortest_walks): they take one like any other row, and only those without an out-edge
+// or an in-edge stay trivial.
 int prepare_lanes(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, u32 *U,
-                  bool dst_rule = true);
+                  bool dst_rule = true, bool closed_rows = false);
 // bstart (pinned host) <- sorted-row boundaries of nb batches of L lanes (+ trivial / NULL tails)
 int batch_bounds(Workspace *ws, int64_t n, int64_t L, int nb);
 

@@ -6,6 +6,8 @@
 //   CheapestPathFunction           (no counterpart) the cheapest path as a list   (CheapestPathWithinFunction: its five-argument overload)
 //   ShortestPathCountFunction      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
 //   AllShortestPathsFunction       (no counterpart) ... the first max_paths of them, LIST(LIST(BIGINT)); bound and max_paths trail the arguments
+//   WalkCountFunction              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
+//   KShortestWalksFunction         (no counterpart: TopK, match.cpp:82-98) ... the first k of them, shortest first, LIST(LIST(BIGINT))
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
 // plus PathFindingRelation, the whole-relation entry point SURVEY.md §8f rank 2 asks for (length and path of every
@@ -203,6 +205,68 @@ void AllShortestPathsFunction(DataChunk &args, ExpressionState &state, Vector &r
 	for (idx_t k = 0; k < path_total; k++) {
 		inner_entries[k].offset = path_offset[k];
 		inner_entries[k].length = path_length[k];
+	}
+	ListVector::SetListSize(result, path_total);
+	ListVector::Reserve(inner, child_len);
+	if (child_len) memcpy(FlatVector::GetDataMutable<int64_t>(ListVector::GetEntry(inner)), child, child_len * sizeof(int64_t));
+	ListVector::SetListSize(inner, child_len);
+	for (idx_t i = 0; i < args.size(); i++) {
+		outer[i].offset = first[i];
+		outer[i].length = npaths[i];
+	}
+	in.state->csr_to_delete.insert(in.csr_id);
+}
+
+namespace {
+// the BIGINT constant of the pattern in argument `col`
+int64_t ConstantArg(DataChunk &args, idx_t col) {
+	UnifiedVectorFormat fmt;
+	args.data[col].ToUnifiedFormat(args.size(), fmt);
+	return reinterpret_cast<const int64_t *>(fmt.data)[0];
+}
+} // namespace
+
+// walk_count(csr_id, V, src, dst, lower, upper) -> BIGINT: the number of walks of lower..upper edges, the row count of a
+// MATCH ALL over -[e]->{lower,upper} in WALK mode (bound like shortestpath, registered beside it).  Unlike the binder's
+// iterativelength BETWEEN lower AND upper filter (match.cpp:658-671) it counts a pair at distance 1 that also has a walk of 2
+// edges under {2,3}, and closed walks for src == dst.  0 when there is no such walk, NULL for a NULL endpoint; saturates at 2^63 - 1.
+void WalkCountFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	const int64_t lower = ConstantArg(args, 4), upper = ConstantArg(args, 5);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto result_data = FlatVector::GetDataMutable<int64_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	if (pgq_walk_count(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper,
+	                   result_data, validity.GetData()) != PGQ_OK)
+		ThrowDevice();
+	in.state->csr_to_delete.insert(in.csr_id);
+}
+
+// k_shortest_walks(csr_id, V, src, dst, lower, upper, k) -> LIST(LIST(BIGINT)): SHORTEST k — the first `k` walks of lower..upper
+// edges of every row, shorter walks first, each [x_0, e_1, x_1, ..., x_t].  Nested like all_shortestpaths' result; the inner lists
+// of one row differ in length.  Rows without a walk are NULL and keep the outer entry {0, 0}.
+void KShortestWalksFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	const int64_t lower = ConstantArg(args, 4), upper = ConstantArg(args, 5), k = ConstantArg(args, 6);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto outer = FlatVector::GetDataMutable<list_entry_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	const uint64_t *path_offset = nullptr, *path_length = nullptr; // owned by the library until this thread's next list-returning call
+	const int64_t *child = nullptr;
+	uint64_t path_total = 0, child_len = 0;
+	vector<uint64_t> first(args.size()), npaths(args.size());
+	if (pgq_k_shortest_walks(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k,
+	                         first.data(), npaths.data(), validity.GetData(), &path_offset, &path_length, &path_total, &child, &child_len) != PGQ_OK)
+		ThrowDevice();
+	ListVector::Reserve(result, path_total);
+	Vector &inner = ListVector::GetEntry(result);
+	inner.SetVectorType(VectorType::FLAT_VECTOR);
+	auto inner_entries = FlatVector::GetDataMutable<list_entry_t>(inner);
+	for (idx_t j = 0; j < path_total; j++) {
+		inner_entries[j].offset = path_offset[j];
+		inner_entries[j].length = path_length[j];
 	}
 	ListVector::SetListSize(result, path_total);
 	ListVector::Reserve(inner, child_len);

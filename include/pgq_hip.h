@@ -285,6 +285,49 @@ int pgq_all_shortestpaths(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, p
                           const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
                           uint64_t *out_child_len);
 
+/* walk_count(csr_id, V, src, dst, lower, upper) -> BIGINT and k_shortest_walks(csr_id, V, src, dst, lower, upper, k) ->
+ * LIST(LIST(BIGINT)): the walks a quantified pattern -[e]->{lower,upper} matches in WALK mode, and SQL/PGQ's SHORTEST k over them
+ * (the reference's binder rejects TopK, match.cpp:82-98, and filters {lower,upper} with iterativelength BETWEEN lower AND upper,
+ * match.cpp:658-671, which drops a pair at distance 1 that also has a walk of 2 edges from {2,3} and never finds a cycle).  Both
+ * work on any CSR and ignore weights.  For a row (src, dst), lo = min_hops, K = max_hops, over the forward CSR's slots (parallel
+ * edges are separate slots):
+ *     W_0[v] = 1 if v == src else 0
+ *     W_t[x] = min(INT64_MAX, sum of W_{t-1}[u] over ALL in-slots (u, x))      t = 1 .. K
+ *     count  = min(INT64_MAX, sum of W_t[dst] for t = lo .. K)
+ * The sums saturate at 2^63 - 1 and never wrap.
+ *   - pgq_walk_count: count, 0 when there is no such walk.  src == dst is not special: it counts the empty walk when lo == 0 and
+ *     every closed walk of lo..K edges.  NULL (payload -1) for a NULL src or a NULL dst.
+ *   - pgq_k_shortest_walks: a row's list holds its first min(count, k) walks, each in shortestpath's layout
+ *     [x_0, e_1, x_1, ..., e_t, x_t]; the empty walk is [src].  Shorter walks come first; walks of equal length t are ordered by
+ *     in-list positions read from the destination end: pgq_all_shortestpaths' order with "W_{i-1}[u] > 0" in place of
+ *     "L[u] = i - 1" and W_{i-1}[u] in place of sigma[u].  Walk number r of a row:
+ *       1. take the smallest t >= lo with r < W_t[dst], after subtracting W_t[dst] of the shorter lengths from r;
+ *       2. start at x_t = dst; for i = t .. 1 scan x_i's in-list in stored order; for each in-slot (u, x_i): if r < W_{i-1}[u] take
+ *          it, otherwise r -= W_{i-1}[u];
+ *       3. the taken in-slot is the m-th from u into x_i; its edge is the m-th slot of u's out-list whose target is x_i.
+ *     A saturated W stays valid for unranking: every emitted rank is below 2^31.  Consequence: for src != dst, d = dist(src, dst)
+ *     and lo <= d <= K the walks of length d come first and are exactly pgq_all_shortestpaths' lists in its order, so walk 0 is
+ *     pgq_shortestpath's list.  A row with count 0, or with a NULL endpoint, is NULL: outer entry {0, 0}, no inner list, no payload.
+ * min_hops < 0, max_hops < min_hops or k < 1 -> PGQ_ERR_INVALID_ARG.  max_hops > PGQ_WALK_MAX_HOPS -> PGQ_ERR_UNSUPPORTED (this
+ * includes INT64_MAX, the binder's "no upper bound"): walks need an upper bound, in a cyclic graph their number is unbounded (what
+ * match.cpp:100-104 says about ALL with WALK).  More than 2^31 - 1 emitted walks in one call -> PGQ_ERR_UNSUPPORTED, nothing
+ * written.  A NULL handle is answered with PGQ_ERR_INVALID_ARG ("NULL csr") before any device is asked for.
+ * Outputs as pgq_all_shortestpaths (the walks of one row differ in length: (*out_path_length)[k] says how many elements walk k
+ * has); the inner entries and the child live in the thread's result arena.  A failed call has written nothing to the caller.
+ * The rounds of the list form stop once no row of a batch of 64 sources is short of k walks (k = 1 on a pair d apart costs d
+ * rounds, not K); pgq_walk_count runs every round up to K or to the round that activates no vertex.
+ * Workspace per batch of 64 sources: pgq_walk_count two rounds (1040 bytes per vertex); pgq_k_shortest_walks every round it runs,
+ * 0..K at most, for the unranking: 520 bytes per vertex and round; PGQ_ERR_OOM with nothing written when it cannot be had.
+ * NOT BUILT: _multi forms; path modes TRAIL / ACYCLIC / SIMPLE; SHORTEST k GROUP; splitting long in-lists over several wavefronts
+ * (a list is walked by one wavefront); any change to how the binder's iterativelength filter is emitted. */
+#define PGQ_WALK_MAX_HOPS 64
+int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                   int64_t *out_count, uint64_t *out_valid);
+int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                         int64_t k, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset,
+                         const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
+                         uint64_t *out_child_len);
+
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
  * freed CSR / upload blocks kept for the next upload (PGQ_ALLOC_CACHE_MB). */
@@ -375,6 +418,22 @@ int pgq_all_shortestpaths_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *
                                       int64_t max_paths, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first,
                                       int64_t *d_out_npaths, int64_t *d_path_offset, int64_t path_cap, int64_t *d_child,
                                       int64_t child_cap, int64_t *paths_used, int64_t *child_used);
+/* pgq_walk_count without the chunk ceiling: d_out_count[i] = count (saturated), 0 when there is no such walk, -1 for a NULL row
+ * (d_src[i] < 0). */
+int pgq_walk_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                               int64_t max_hops, int64_t *d_out_count);
+/* pgq_k_shortest_walks without the chunk ceiling; outputs as pgq_all_shortestpaths_bulk_device with these differences.  The walks
+ * of one row differ in length: walk j starts at d_path_offset[j] in d_child and has 2 * d_path_hops[j] + 1 elements (both arrays
+ * path_cap entries).  d_out_len[i] = the hops of the row's first walk, -1 if it has none.  d_out_npaths[i] = min(count, k).
+ * d_out_count[i] = the walks of lo..T edges, T the length of the row's last emitted walk (the rounds stop there, and a row that
+ * has its k walks adds no more): this is count whenever count <= k, otherwise at least k and at most count —
+ * pgq_walk_count_bulk_device gives count itself; -1 for a NULL row.  Capacity protocol: *paths_used / *child_used = the walks and
+ * elements needed; PGQ_ERR_INVALID_ARG when path_cap or child_cap is too small: d_out_len, d_out_count and d_out_npaths are
+ * complete then, the payload is not usable.  A NULL handle: PGQ_ERR_INVALID_ARG, both *_used values 0. */
+int pgq_k_shortest_walks_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                     int64_t max_hops, int64_t k, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first,
+                                     int64_t *d_out_npaths, int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap,
+                                     int64_t *d_child, int64_t child_cap, int64_t *paths_used, int64_t *child_used);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

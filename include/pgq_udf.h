@@ -17,6 +17,8 @@
  *   pgq_udf_shortestpath_within     ShortestPathFunction with the pattern's upper bound as fifth argument (match.cpp:467-495, 658-671)
  *   pgq_udf_shortestpath_count      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
  *   pgq_udf_all_shortestpaths       (no counterpart) ... and the first max_paths of them as a list of lists; both bound like shortestpath
+ *   pgq_udf_walk_count              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
+ *   pgq_udf_k_shortest_walks        (no counterpart: TopK, match.cpp:82-98) ... and the first k of them, shortest first; both bound like shortestpath
  *   pgq_udf_bind_cheapest           CheapestPathLengthBind      src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
@@ -90,6 +92,20 @@ int pgq_udf_all_shortestpaths(pgq_state_t *, int32_t id, int64_t V, int64_t n, p
                               int64_t max_paths, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
                               const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
                               const int64_t **out_child, uint64_t *out_child_len);
+/* walk_count(id, V, src, dst, lower, upper) -> BIGINT: the number of walks of lower..upper edges, saturated at 2^63 - 1
+ * (pgq_walk_count: src == dst counts the empty walk when lower == 0 and every closed walk; 0 when there is none, NULL for a NULL
+ * endpoint); bound through pgq_udf_bind_search, errors as for pgq_udf_shortestpath; bounds out of range are the device library's
+ * PGQ_ERR_INVALID_ARG / PGQ_ERR_UNSUPPORTED (upper > PGQ_WALK_MAX_HOPS: walks need an upper bound) */
+int pgq_udf_walk_count(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                       int64_t *out, uint64_t *out_valid);
+/* k_shortest_walks(id, V, src, dst, lower, upper, k) -> LIST(LIST(BIGINT)): the first k walks of lower..upper edges of every row,
+ * shorter walks first, in the contract's order (pgq_k_shortest_walks; for src != dst and lower <= dist <= upper walk 0 is
+ * shortestpath's list); outputs as pgq_udf_all_shortestpaths.  Bound through pgq_udf_bind_search, errors as for
+ * pgq_udf_walk_count; k < 1 is the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_k_shortest_walks(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops,
+                             int64_t max_hops, int64_t k, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
+                             const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
+                             const int64_t **out_child, uint64_t *out_child_len);
 /* *ret_type: PGQ_W_INT64 -> BIGINT result, PGQ_W_DOUBLE -> DOUBLE result */
 int pgq_udf_bind_cheapest(pgq_state_t *, int32_t id, int *ret_type);
 int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
