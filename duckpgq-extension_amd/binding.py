@@ -78,6 +78,10 @@ def load_hip():
     L.pgq_csr_pack_order.argtypes = [C.c_void_p]
     L.pgq_csr_packed_list.restype = C.c_int64
     L.pgq_csr_packed_list.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
+    L.pgq_csr_pull_layout_sizes.restype = C.c_int
+    L.pgq_csr_pull_layout_sizes.argtypes = [C.c_void_p, C.c_void_p]
+    L.pgq_csr_pull_layout.restype = C.c_int
+    L.pgq_csr_pull_layout.argtypes = [C.c_void_p] + [C.c_void_p] * 5
     L.pgq_debug_live_device_blocks.restype = C.c_int64
     L.pgq_debug_live_device_blocks.argtypes = []
     L.pgq_iterativelength.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
@@ -444,6 +448,22 @@ class DeviceCSR:
         out = np.zeros(max(int(n), 1), dtype=np.int32)
         _check(min(self.L.pgq_csr_packed_list(self.h, direction, v, out.ctypes.data, n), 0))
         return out[:n]
+
+    def pull_layout(self):
+        """The bottom-up work partition built at upload, as a dict of numpy arrays: parts [n, 2] (begin, end), hub_items
+        [n, 3] (vertex, begin, end), hub_vertices, rown (one byte per in-slot) and rpk (one word per in-slot, or None where
+        the upload did not build them)."""
+        sizes = np.zeros(5, dtype=np.int64)
+        _check(self.L.pgq_csr_pull_layout_sizes(self.h, _p(sizes)))
+        n_parts, n_items, n_hubs, E, has_rpk = (int(x) for x in sizes)
+        parts = np.zeros((max(n_parts, 1), 2), dtype=np.int32)
+        items = np.zeros((max(n_items, 1), 3), dtype=np.int64)
+        hubs = np.zeros(max(n_hubs, 1), dtype=np.int32)
+        rown = np.zeros(max(E, 1), dtype=np.uint8)
+        rpk = np.zeros(max(E, 1), dtype=np.uint32) if has_rpk else None
+        _check(self.L.pgq_csr_pull_layout(self.h, _p(parts), _p(items), _p(hubs), _p(rown), _p(rpk)))
+        return dict(parts=parts[:n_parts], hub_items=items[:n_items], hub_vertices=hubs[:n_hubs], rown=rown[:E],
+                    rpk=None if rpk is None else rpk[:E])
 
     # -- chunk form (host arrays) ----------------------------------------------
     def _vecs(self, src, dst, src_valid, src_sel, dst_sel, dst_valid, keep):

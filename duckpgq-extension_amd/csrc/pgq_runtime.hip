@@ -2097,6 +2097,37 @@ int64_t pgq_csr_packed_list(pgq_csr_t *c, int dir, int64_t v, int32_t *out, int6
 	}
 	return len;
 }
+int pgq_csr_pull_layout_sizes(const pgq_csr_t *c, int64_t *sizes) {
+	if (!c || !sizes) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_pull_layout_sizes: NULL handle or no room");
+	sizes[0] = c->n_pull_parts;
+	sizes[1] = c->n_pull_hub_items;
+	sizes[2] = c->n_pull_hub_vertices;
+	sizes[3] = c->E;
+	sizes[4] = c->rpk ? 1 : 0;
+	return PGQ_OK;
+}
+int pgq_csr_pull_layout(const pgq_csr_t *c, int32_t *parts, int64_t *hub_items, int32_t *hub_vertices, uint8_t *rown,
+                        uint32_t *rpk) {
+	PGQ_TRY(ensure_init());
+	if (!c) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_pull_layout: NULL handle");
+	if (rpk && !c->rpk) return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_pull_layout: this CSR has no packed in-slot words (V >= 2^28)");
+	hipStream_t st = nullptr; // the null stream, as pgq_csr_download
+	if (parts && c->n_pull_parts > 0) PGQ_TRY(staged_download(parts, c->pull_parts, (size_t)c->n_pull_parts * 8, st));
+	if (hub_items && c->n_pull_hub_items > 0) {
+		std::vector<HubItem> items((size_t)c->n_pull_hub_items);
+		PGQ_TRY(staged_download(items.data(), c->pull_hubs, items.size() * sizeof(HubItem), st));
+		for (size_t i = 0; i < items.size(); i++) {
+			hub_items[3 * i] = items[i].vertex;
+			hub_items[3 * i + 1] = items[i].begin;
+			hub_items[3 * i + 2] = items[i].end;
+		}
+	}
+	if (hub_vertices && c->n_pull_hub_vertices > 0)
+		PGQ_TRY(staged_download(hub_vertices, c->pull_hub_vertices, (size_t)c->n_pull_hub_vertices * 4, st));
+	if (rown && c->E > 0) PGQ_TRY(staged_download(rown, c->rown, (size_t)c->E, st));
+	if (rpk && c->E > 0) PGQ_TRY(staged_download(rpk, c->rpk, (size_t)c->E * 4, st));
+	return PGQ_OK;
+}
 
 } // extern "C"
 

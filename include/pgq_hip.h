@@ -138,6 +138,17 @@ int pgq_csr_pack_order(const pgq_csr_t *csr);
  * length; PGQ_ERR_UNSUPPORTED for a CSR without a packed copy (pgq_csr_pack_k() == 4).  Not a fast path: it copies the
  * offsets up to v to the host. */
 int64_t pgq_csr_packed_list(pgq_csr_t *csr, int dir, int64_t v, int32_t *out, int64_t cap);
+/* Debugging / tests: the work partition the upload built for the bottom-up kernels of the lane batches, copied to host
+ * memory.  pgq_csr_pull_layout_sizes writes sizes[0 .. 4] = {parts, hub slices, hub vertices, in-slots (= edges), 1 if the
+ * packed in-slot words exist else 0}.  pgq_csr_pull_layout fills whichever buffers are not NULL: parts = (begin, end)
+ * vertex pairs; hub_items = (vertex, begin, end) triples, the slices of the hubs' in-lists in vertex order; hub_vertices;
+ * rown = one byte per in-slot, its owner vertex as an index inside its part (0 for a hub's slots); rpk = one word per
+ * in-slot of a part, in-neighbour | owner index << 28, and 0 for a hub's slots, which are never read through it
+ * (PGQ_ERR_UNSUPPORTED where V >= 2^28 and the words were not built).  Read-only: no
+ * search path and no layout depends on these calls. */
+int pgq_csr_pull_layout_sizes(const pgq_csr_t *csr, int64_t *sizes);
+int pgq_csr_pull_layout(const pgq_csr_t *csr, int32_t *parts, int64_t *hub_items, int32_t *hub_vertices, uint8_t *rown,
+                        uint32_t *rpk);
 /* Debugging / tests: device blocks the library's block cache has handed out and not got back yet (CSR arrays and build
  * temporaries of every live handle; cached free blocks, workspaces and pinned memory are not counted).  The same figure
  * before a handle is created and after it is freed = the handle left nothing behind. */

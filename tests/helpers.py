@@ -566,3 +566,419 @@ def probe_gadgets(cap=PROBE2_CAP):
     V = hi_base + _PROBE_POOL
     real = lambda v: np.where(np.asarray(v, dtype=np.int64) < 0, hi_base - 1 - np.asarray(v, dtype=np.int64), v).astype(np.int64)
     return ProbeGadgets(V, real(np.concatenate(es)), real(np.concatenate(ed)), rows, gadgets)
+
+
+# ---- gadgets on the partition limits of the lane batches' expansion kernels ---------------------------------------------
+# Every constant the gadgets sit on, and where it was read (test_pull_gadgets_cpu.py reads them back from the sources):
+PULL_LIMITS = dict(
+    kPartRun=256,         # pgq_runtime.hip, `constexpr int kPartRun = 256;`: k_make_parts packs one run per thread
+    part_vertices=16,     # k_make_parts, `v - begin >= 16`; `constexpr int NV = 16;` in k_pull_sparse and k_pull_lanes
+    vertex_weight=8,      # k_make_parts, `const int64_t wv = d + 8;`
+    part_weight=1024,     # pgq_internal.h, `int part_weight = 1024;`
+    hub_chunk=4096,       # pgq_internal.h, `int hub_chunk = 4096;`
+    push_chunk=256,       # pgq_internal.h, `int push_chunk = 256;`
+    min_option=64,        # finish_upload / the batch worker: std::max(64, hub_chunk | part_weight | push_chunk)
+    hub_slice_div=4,      # finish_upload, `slice = std::max<int64_t>(64, chunk / 4)`
+    lanes_qcap=64,        # k_pull_lanes, `constexpr int QCAP = 64;`: queued records with more than two lane ids
+    sparse_qcap=128,      # k_pull_sparse, `constexpr int QCAP = 128;`: spilled words per trip
+    kInlineWords=3,       # pgq_msbfs.hip: words of a frontier record that need no second fetch
+    kLaneFields=10,       # pgq_lanes.hip: lane ids a record holds; one more and the dense row is read
+    rpk_pad=2048)         # pgq_internal.h, csr_arrays: `(En + 2048) * 4` bytes of rpk
+PULL_UNROLLS = (1, 2, 4)  # lanes_unroll / sparse_unroll: a trip is 64 x UN in-slots
+PULL_DEGREES = (1, 2, 3, 5, 16, 17, 32, 33, 48, 49, 63, 64, 65, 127, 128, 129)  # k_pull: 64 per trip, GRP breaks at r0 * NS
+PUSH_DEGREES = (1, 63, 64, 65, 127, 128, 129, 192, 193)
+_Z = 32  # symbolic ids: zone << 32 | index; zones in id order: targets, low pools, middle, high pools, top, tail
+
+
+def pull_parts_model(roff, part_weight, hub_chunk, max_vertices=16):
+    """k_make_parts's contract in plain Python: per run of 256 consecutive vertices a greedy pass, hubs (in-degree above the
+    chunk) in no part, a part closed before the vertex that would be its 17th or would take its in-degree + 8 per vertex above
+    the weight, unless the part is empty.  Returns (parts as [n, 2], hub vertices)."""
+    W, C, run = max(64, part_weight), max(64, hub_chunk), PULL_LIMITS["kPartRun"]
+    V = len(roff) - 1
+    deg = np.diff(roff).tolist()
+    parts, hubs = [], []
+    for v0 in range(0, V, run):
+        v1 = min(V, v0 + run)
+        begin, acc = v0, 0
+        for v in range(v0, v1):
+            d = deg[v]
+            if d > C:
+                hubs.append(v)
+                if v > begin:
+                    parts.append((begin, v))
+                begin, acc = v + 1, 0
+                continue
+            if v > begin and (acc + d + 8 > W or v - begin >= max_vertices):
+                parts.append((begin, v))
+                begin, acc = v, 0
+            acc += d + 8
+        if v1 > begin:
+            parts.append((begin, v1))
+    return np.array(parts, dtype=np.int64).reshape(-1, 2), np.array(hubs, dtype=np.int64)
+
+
+def hub_slices_model(roff, hubs, hub_chunk):
+    """finish_upload's hub items: every hub's in-list cut into slices of max(64, chunk / 4) entries, in vertex order."""
+    S = max(64, max(64, hub_chunk) // PULL_LIMITS["hub_slice_div"])
+    return np.array([(v, b, min(b + S, roff[v + 1])) for v in hubs for b in range(roff[v], roff[v + 1], S)],
+                    dtype=np.int64).reshape(-1, 3)
+
+
+class PullGadgets:
+    """V, the edge table (src, dst), the rows (rs, rd, dist with -1 = unreachable, tag) and one record per gadget:
+      tag, family, k (hops), rows (row indices; the first is (src, dst)), cut (per row, the edge without which the row's answer
+      changes; None for a negative row), src, dst, path, b (in-degree of dst), p (in-slot of
+      the witness path[-2] in N_in(dst)), live (decoys are frontier vertices) and, where the family fixes them, expect = a dict
+      of v0 / own (part start, owner row) / closes (dst is its part's last vertex) / alone / hub / prel (part-relative
+      in-slot) / mod4 (roff[v0] % 4) / slice, last_slice / out_deg, out_slot (of the witness edge in path[-2]'s out-list) /
+      lanes (distinct sources the witness carries) / words (distinct 64-lane words of those sources in the spread call).
+    fixed = rows that belong in every call (the decoy sources: they make the pools live), pairs = rows to call on their own
+    (two lanes: the early exit), spread = rows of the call in which the spread witnesses' sources lie in different lane-words,
+    negative = rows that a scan without the first trip's mask answers, stale = two calls to make one after the other (first, second):
+    the second asks for a hub the first reached, from a source that does not reach it."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def rows_where(self, pick):
+        return np.array([r for g in self.gadgets if pick(g) for r in g["rows"]], dtype=np.int64)
+
+    def calls(self, words):
+        """Row sets of at most 64 x words distinct sources (one batch), each holding the fixed rows; a gadget's rows stay
+        together."""
+        fixed = set(self.rs[self.fixed].tolist())
+        room = 64 * words - len(fixed)
+        out, cur, srcs = [], [], set()
+        for g in self.gadgets:
+            if g["family"] in ("spread", "spill"):
+                continue
+            s = set(self.rs[g["rows"]].tolist()) - fixed
+            if len(srcs | s) > room:
+                out.append(cur)
+                cur, srcs = [], set()
+            cur += g["rows"]
+            srcs |= s
+        out.append(cur)
+        return [np.array(list(self.fixed) + c, dtype=np.int64) for c in out if c]
+
+
+def pull_gadgets(part_weight=64, hub_chunk=64):
+    """One graph of gadgets for the expansion kernels of the lane batches (k_push, k_pull, k_pull_sparse, k_pull_lanes,
+    k_pull_hub) and the work partition of finish_upload, for a handle uploaded under `part_weight` and `hub_chunk`.
+
+    A gadget is a row (s, t) whose only shortest path enters t through one in-edge, from the witness; s = c0 -> .. -> c(k-1)
+    = witness -> t, k = 1, 2, 3 (5 in the push family).  In-lists are ordered by source id: the target zone has the smallest
+    ids (so roff of a target is the sum of the target zone's in-degrees before it), then the LOW pools, the sources, chains and
+    witnesses, the HIGH pools; a witness at in-slot p of b entries has p in-neighbours out of a LOW pool and b - 1 - p out of a
+    HIGH pool.  Decoys are LIVE: pool k is in the frontier of level k - 1 with other lanes' bits (pool 1: eight + eight sources
+    of rows of their own; pool 2: every vertex an out-neighbour of three sources D2 — three lane ids, a queued record in
+    k_pull_lanes — and of the four spread sources; pool 3: two hops from a source D3; the D sources keep a row five hops long,
+    so their lanes stay wanted).  A list longer than its pool, and the `cold` family, takes vertices nothing reaches.  Kind
+    `detour`: a second path two hops longer enters t just before the witness, else a lost witness leaves the row unreachable.
+
+    The target zone is cut into segments that begin at a multiple of 256 (a run of k_make_parts: a part begins there); the
+    last vertex of the run before, the aligner, takes 0 .. 3 cold in-edges (or a part's weight of them: the heavy aligner of the
+    `align` family, alone in its part) so that roff of the segment's first vertex has the wanted remainder mod 4."""
+    L = PULL_LIMITS
+    W, C, RUN, NV = max(L["min_option"], part_weight), max(L["min_option"], hub_chunk), L["kPartRun"], L["part_vertices"]
+    S = max(64, C // L["hub_slice_div"])
+    PC = L["min_option"]  # the push_chunk the push family stands on
+    T, LOW, MID, HIGH, TOP, TAIL = (z << _Z for z in range(6))
+    n1, NP, N3 = 8, max(1100, C + S + 8), 320
+    count = {z: 0 for z in (LOW, MID, HIGH, TOP, TAIL)}
+    tdeg = []  # in-degrees of the target zone, by id
+    es, ed, rows, gadgets = [], [], [], []
+    fixed, pairs, negative, tags = [], [], [], set()
+
+    def new(zone=MID, n=None):
+        at = zone + count[zone]
+        count[zone] += 1 if n is None else n
+        return at if n is None else at + np.arange(n, dtype=np.int64)
+
+    def edges(s, d):
+        s, d = np.broadcast_arrays(np.asarray(s, dtype=np.int64), np.asarray(d, dtype=np.int64))
+        es.append(s.ravel().copy())
+        ed.append(d.ravel().copy())
+
+    def row(s, d, dist, tag):
+        rows.append((int(s), int(d), dist, tag))
+        return len(rows) - 1
+
+    def chain(k, first=None):  # k edges from `first` (a new vertex if None): the k + 1 vertices
+        c = [new() if first is None else first] + [new() for _ in range(k)]
+        if k:
+            edges(c[:-1], c[1:])
+        return c
+
+    # the pools
+    pool = {}
+    for zone, side in ((LOW, "low"), (HIGH, "high")):
+        pool[side, 1] = new(zone, n1)
+        pool[side, 2] = new(zone, NP)
+        pool[side, 3] = new(zone, N3)
+        pool[side, 0] = new(zone, NP)  # cold: nothing points at them
+    d2, d3 = new(LOW, 3), new(LOW)
+    spread = [None] * 4  # sources 64 ranks apart (below): their lanes lie in four lane-words
+
+    def far_row(s, tag):  # keeps a decoy source's lane wanted for five levels
+        row(s, chain(5, s)[-1], 5, tag)
+        fixed.append(len(rows) - 1)
+
+    sink1 = new()
+    for side in ("low", "high"):
+        for i, v in enumerate(pool[side, 1]):
+            edges(v, sink1)
+            fixed.append(row(v, sink1, 1, "pool1_%s%d" % (side, i)))
+    for j, s in enumerate(d2):
+        for side in ("low", "high"):
+            edges(s, pool[side, 2])
+        far_row(s, "d2_%d" % j)
+    m3 = new()
+    edges(d3, m3)
+    for side in ("low", "high"):
+        edges(m3, pool[side, 3])
+    far_row(d3, "d3")
+    # ballast: 63 rows one hop long between two spread sources
+    ballast = []
+    for i in range(4):
+        spread[i] = new()
+        if i < 3:
+            for j in range(63):
+                s, d = new(), new()
+                edges(s, d)
+                ballast.append(row(s, d, 1, "ballast%d_%d" % (i, j)))
+    for s in spread:
+        for side in ("low", "high"):
+            edges(s, pool[side, 2])
+
+    def in_list(k, b, p, live, before=()):
+        """The in-neighbours of a list of b entries around a witness at in-slot p: low side, then `before`, [witness], high."""
+        n_low, n_high = p - len(before), b - 1 - p
+        assert n_low >= 0 and n_high >= 0, (b, p)
+        out = []
+        for side, n in (("low", n_low), ("high", n_high)):
+            a = min(n, len(pool[side, k])) if live else 0
+            assert n - a <= NP, (b, p)
+            out.append(np.concatenate([pool[side, k][:a], pool[side, 0][:n - a]]).astype(np.int64))
+        return out[0], out[1]
+
+    # -- the target zone
+    def tv(b):
+        tdeg.append(b)
+        return T + len(tdeg) - 1
+
+    def segment(mod4=None, heavy=False):
+        """Pads to the next multiple of 256; the last pad vertex is the aligner.  Returns it where it is heavy."""
+        pad = RUN - len(tdeg) % RUN
+        tdeg.extend([0] * (pad - 1))
+        a = 0
+        if heavy:
+            a = W - L["vertex_weight"] + 1  # alone in its part: a + 8 > W whatever precedes it
+        if mod4 is not None:
+            a += (mod4 - sum(tdeg) - a) % 4
+        assert a <= C
+        v = tv(a)
+        if a and not heavy:
+            edges(pool["low", 0][:a], v)
+        return v, a
+
+    def gadget(family, k, b, p, live=True, detour=False, t=None, tag=None, expect=None, n_src=1, srcs=None):
+        """s = c0 -> .. -> witness -> t.  n_src > 1: so many sources, each with an edge to c1 (k = 2: the witness), a row each."""
+        t = tv(b) if t is None else t
+        ss = [new() for _ in range(n_src)] if srcs is None else srcs
+        before = []
+        if detour:  # a path of k + 2 hops whose last vertex sits in the slot before the witness (the witness gets the next id)
+            assert p >= 1
+            before = [chain(k + 1, ss[0])[-1]]
+        c = chain(k - 1, ss[0])
+        for s in ss[1:]:
+            assert k >= 2
+            edges(s, c[1])
+        lo, hi = in_list(min(k, 3), b, p, live, before)
+        edges(np.concatenate([lo, before, [c[-1]], hi]).astype(np.int64), t)
+        tag = tag or "%s_k%d_b%d_p%d%s%s" % (family, k, b, p, "" if live else "_cold", "_detour" if detour else "")
+        if tag in tags:
+            tag += "_n%d" % len(gadgets)
+        tags.add(tag)
+        rs_ = [row(s, t, k, tag if i == 0 else "%s_src%d" % (tag, i)) for i, s in enumerate(ss)]
+        g = dict(tag=tag, family=family, k=k, b=b, p=p, live=live, detour=detour, src=ss[0], dst=t, path=c + [t], rows=rs_,
+                 expect=dict(expect or {}))
+        if n_src > 1:
+            g["expect"]["lanes"] = n_src
+        gadgets.append(g)
+        return g
+
+    last = lambda b: b - 1
+    # run 0: nothing points at it; ids 62 .. 65 are sources of the push family (k_queue_from_dense takes 64 vertices per trip)
+    tdeg.extend([0] * 66)
+    # a. degrees: every kernel's 64-entry trip, k_pull's GRP loop (r0 * NS | + 1 entries in the last chunk, NS = 64 / words);
+    #    above the chunk the same lists are hubs
+    segment()
+    for k in (1, 2, 3):
+        for b in PULL_DEGREES:
+            for p in sorted({0, last(b)} | ({63, 64} & set(range(b)))):
+                gadget("deg", k, b, p, detour=(k == 2 and p == last(b) and b in (5, 64, 129)),
+                       expect=dict(hub=b > C))
+    for b in (5, 64, 65, 129):
+        gadget("cold", 2, b, last(b), live=False, expect=dict(hub=b > C))
+        gadget("cold", 3, b, 0, live=False, expect=dict(hub=b > C))
+    for b in sorted({64 + x for x in (16, 17, 32, 33, 48, 49)}):
+        gadget("deg", 2, b, last(b), expect=dict(hub=b > C))
+    # b. part shapes
+    n_fit = min(NV, W // (3 + L["vertex_weight"]))  # vertices of in-degree 3 a part takes: 16 under the defaults, 5 at weight 64
+    v0 = segment()[0] + 1
+    for j in range(n_fit + 1):  # the vertex after the full part opens the next one
+        p = 0 if j in (0, n_fit) else 2
+        gadget("full_part", 2, 3, p, expect=dict(v0=v0 + (n_fit if j == n_fit else 0), own=j % n_fit, closes=j == n_fit - 1,
+                                                  full=n_fit == NV and j < n_fit, opens_next=j == n_fit))
+    half = (W - 2 * L["vertex_weight"]) // 2  # two vertices of `half` in-edges weigh exactly W
+    for over in (0, 1):
+        v0 = segment()[0] + 1
+        gadget("weight", 2, half, last(half), expect=dict(v0=v0, own=0, closes=bool(over)), tag="weight_first_over%d" % over)
+        gadget("weight", 2, half + over, last(half + over), expect=dict(v0=v0 + over, own=1 - over), tag="weight_second_over%d" % over)
+    v0 = segment()[0] + 1
+    gadget("heavy", 2, 2, 1, expect=dict(v0=v0, own=0, closes=True))
+    big = min(C, W + 36)  # heavier than a part on its own, and no hub
+    gadget("heavy", 2, big, last(big), expect=dict(v0=v0 + 1, own=0, alone=True))
+    gadget("heavy", 2, 2, 0, expect=dict(v0=v0 + 2, own=0))
+    # the end of a run cuts a part: targets at ids 255 | 256 of a two-run segment
+    v0 = segment()[0] + 1
+    tdeg.extend([0] * (RUN - 1))
+    gadget("run_end", 2, 3, 2, expect=dict(closes=True, run_last=True))
+    gadget("run_end", 2, 3, 0, expect=dict(v0=v0 + RUN, own=0))
+    # hubs inside a run: at its first vertex, two adjacent ones, at its last vertex; in-degree 0 inside a part
+    v0 = segment()[0] + 1
+    hb = C + 1
+    gadget("hub_in_run", 2, hb, last(hb), expect=dict(hub=True), tag="hub_first_of_run")
+    gadget("hub_in_run", 2, 2, 1, expect=dict(v0=v0 + 1, own=0))
+    tv(0), tv(0)
+    gadget("hub_in_run", 2, 2, 1, expect=dict(v0=v0 + 1, own=3, closes=True), tag="zero_degrees_inside")
+    gadget("hub_in_run", 2, hb, 0, expect=dict(hub=True), tag="hub_adjacent_a")
+    gadget("hub_in_run", 2, hb + 1, last(hb + 1), expect=dict(hub=True), tag="hub_adjacent_b")
+    gadget("hub_in_run", 2, 2, 0, expect=dict(v0=v0 + 7, own=0), tag="after_two_hubs")
+    tdeg.extend([0] * (RUN - 10))
+    gadget("hub_in_run", 2, 2, 1, expect=dict(closes=True), tag="before_hub_last_of_run")
+    gadget("hub_in_run", 2, hb, S, expect=dict(hub=True, run_last=True), tag="hub_last_of_run")
+    # c. trip position: roff[v0] mod 4 with the witness in in-slot e0; the aligner before it is heavy and ends in a live
+    #    witness of another lane, which a first trip that starts at e0 & ~3 without a mask credits to this part's owner row 0
+    for r in range(4):
+        av, a = segment(mod4=r, heavy=True)
+        lo, _ = in_list(2, a, a - 1, False)
+        sa, wa = new(), new()
+        edges(sa, wa)
+        edges(np.concatenate([lo, [wa]]), av)
+        ra = row(sa, av, 2, "align_mod%d_aligner" % r)
+        g = gadget("align", 2, 5, 0, expect=dict(v0=av + 1, own=0, mod4=r, prel=0))
+        negative.append(row(sa, g["dst"], -1, "align_mod%d_negative" % r))
+        gadgets.append(dict(tag="align_mod%d_aligner" % r, family="aligner", k=2, b=a, p=a - 1, live=False, detour=False, src=sa,
+                            dst=av, path=[sa, wa, av], rows=[ra, negative[-1]], expect=dict(v0=av, own=0, alone=True)))
+    # part-relative in-slots on the ends of the trips of 64 x UN entries (k_pull_lanes: two prologue trips, then the pipeline)
+    slots = sorted({m * 64 * un - 1 for un in PULL_UNROLLS for m in (1, 2)} | {m * 64 * un for un in PULL_UNROLLS for m in (1, 2, 3)})
+    longest = W - L["vertex_weight"]  # the longest list that is not alone in its part by weight
+    for q in slots:
+        if q < longest:
+            v0 = segment(mod4=q % 3 + 1)[0] + 1
+            gadget("trip", 2, longest, q, expect=dict(v0=v0, own=0, prel=q))
+        elif q < C:  # (weight 64: a part's in-slots end before 64 unless one vertex holds them all) heavier than a part, no hub
+            v0 = segment(mod4=q % 3 + 1)[0] + 1
+            gadget("trip", 2, q + 1, q, expect=dict(v0=v0, own=0, prel=q, alone=True))
+    # d. hubs: in-degrees around the chunk, last slices of 1, 63, 64 (a whole slice) and 65 = 64 + 1 entries, the witness in
+    #    the first and last slot of the first, a middle and the last slice
+    segment()
+    gadget("hub", 2, C, last(C), expect=dict(hub=False), tag="hub_not_yet_last")
+    gadget("hub", 2, C, 0, expect=dict(hub=False), tag="hub_not_yet_first")
+    hub_degrees = [C + 1, C + 63, C + 64, C + 65, C + S] if C > 64 else [C + 1, 2 * S - 1, 2 * S, 2 * S + 1, 3 * S - 1, 3 * S, 3 * S + 1, 4 * S + 63]
+    for b in hub_degrees:
+        n_sl = (b + S - 1) // S
+        for sl in sorted({0, n_sl // 2, n_sl - 1}):
+            for p in sorted({sl * S, min(b, (sl + 1) * S) - 1}):
+                gadget("hub", 2, b, p, expect=dict(hub=True, slice=sl, last_slice=sl == n_sl - 1, tail=b - (n_sl - 1) * S))
+    gadget("hub", 3, hub_degrees[1], last(hub_degrees[1]), expect=dict(hub=True, last_slice=True))
+    gadget("hub", 1, hub_degrees[1], last(hub_degrees[1]), expect=dict(hub=True, last_slice=True))
+    gadget("hub", 2, hub_degrees[-1], last(hub_degrees[-1]), live=False, expect=dict(hub=True, last_slice=True), tag="hub_cold_last")
+    # a hub reached in one call and asked for, from a source that does not reach it, in the next: the two calls' only sources
+    # share lane 0, and the bottom-up levels' frontier buffers are never cleared between calls, so a k_pull_hub_zero that left the
+    # hub's row of `next` alone would hand the second call the first call's bit (its other row, three hops long, keeps it running)
+    gz = gadget("stale", 2, hub_degrees[0], last(hub_degrees[0]), live=False, expect=dict(hub=True, last_slice=True))
+    sz = new()
+    stale = dict(first=list(gz["rows"]), second=[row(sz, gz["dst"], -1, "stale_negative"), row(sz, chain(3, sz)[-1], 3, "stale_far")])
+    # e. two lanes want one target: A is supplied in the first 64 in-slots, B only by the last one (the early exit of k_pull and
+    #    k_pull_hub must wait for B).  Cold decoys; B's witness lies above the high pools.  `levels`: A arrives a level before B
+    #    (k_pull_hub: `have`, `want` and the fold of a hub one lane has seen already)
+    def pair(b, ka, tag):
+        t = tv(b)
+        ca, cb, wb = chain(ka - 1), [new()], new(TOP)
+        edges(cb[0], wb)
+        lo, hi = in_list(2, b - 1, 3, False)
+        edges(np.concatenate([lo, [ca[-1]], hi, [wb]]).astype(np.int64), t)
+        r = [row(cb[0], t, 2, tag + "_B"), row(ca[0], t, ka, tag + "_A")]
+        gadgets.append(dict(tag=tag, family="pair", k=2, b=b, p=b - 1, live=False, detour=False, src=cb[0], dst=t, path=[cb[0], wb, t],
+                            rows=r, expect=dict(hub=b > C, first=3), cut=[(wb, t), (ca[-1], t)]))
+        pairs.append(r)
+
+    for b in (65, 129, 4 * S + 1):
+        pair(b, 2, "pair_b%d" % b)
+        pair(b, 1, "pair_levels_b%d" % b)
+    # f. frontier records: a witness that carries 1, 2, 3, 9, 10, 11 lanes (k_pull_lanes: two ids inline, the tail queue from
+    #    the third, the dense row from the eleventh)
+    segment()
+    for m in (1, 2, 3, 9, 10, 11):
+        gadget("lanes", 2, 3, 1, n_src=m, tag="lanes_%d" % m)
+    # sources in 3 and in 4 lane-words (k_compact_frontier: three words inline, the fourth out of cw), and lists whose live
+    # entries each spill a fourth word: under and over k_pull_sparse's queue (their decoys carry the four spread lanes)
+    gadget("spread", 2, 3, 1, live=False, srcs=spread[:3], tag="spread_3words")
+    gadget("spread", 2, 3, 1, live=False, srcs=spread, tag="spread_4words")
+    for b in (100, 200):
+        if b <= C and b + L["vertex_weight"] <= W:
+            v0 = segment()[0] + 1
+            gadget("spill", 2, b, last(b), expect=dict(v0=v0, own=0, prel=b - 1))
+    # g. top-down: the witness edge in the last slot of the first, a middle and the last item of `push_chunk` out-edges
+    sinks = new(MID, 256)
+    push_src = [T + 62, T + 63, T + 64, T + 65]
+    n_push = [0]
+
+    def push(k, d, q, src=None):
+        c = chain(k - 1, src)
+        t = new()
+        junk = sinks[(37 * n_push[0] + np.arange(d - 1)) % len(sinks)]
+        n_push[0] += 1
+        edges(c[-1], np.concatenate([junk[:q], [t], junk[q:]]).astype(np.int64))
+        tag = "push_k%d_d%d_q%d" % (k, d, q)
+        if tag in tags:
+            tag += "_n%d" % len(gadgets)
+        tags.add(tag)
+        gadgets.append(dict(tag=tag, family="push", k=k, b=1, p=0, live=False, detour=False, src=c[0], dst=t, path=c + [t],
+                            rows=[row(c[0], t, k, tag)], expect=dict(out_deg=d, out_slot=q, item=q // PC)))
+        return gadgets[-1]
+
+    for d in PUSH_DEGREES:
+        items = (d + PC - 1) // PC
+        for q in sorted({min(d, (i + 1) * PC) - 1 for i in (0, items // 2, items - 1)} | {0}):
+            for k in (1, 2):
+                push(k, d, q, src=push_src.pop() if push_src and k == 1 and q == d - 1 else None)
+    for d, q in ((65, 64), (129, 128), (64, 63)):
+        push(5, d, q)  # the fifth level's frontier is a handful of vertices: top-down after bottom-up levels
+    # the tail: the last part ends at V, its in-slots are the last of the graph (rpk and rown are padded behind them), and
+    # the last vertex is a source
+    t_last = new(TAIL)
+    gadget("tail", 2, 6, 5, t=t_last, expect=dict(closes=False, ends_at_V=True))
+    push(1, 65, 64, src=new(TAIL))["expect"]["last_vertex"] = True
+
+    base = np.concatenate([[0], np.cumsum([len(tdeg)] + [count[z] for z in (LOW, MID, HIGH, TOP, TAIL)])])
+    real = lambda v: base[np.asarray(v, dtype=np.int64) >> _Z] + (np.asarray(v, dtype=np.int64) & 0xFFFFFFFF)
+    for g in gadgets:
+        # per row, the edge whose removal must change the row's answer (None: a negative row)
+        cut = g.pop("cut", None) or [(g["path"][-2], g["path"][-1])] * len(g["rows"])
+        g["cut"] = [None if r in negative else (int(real(u)), int(real(v))) for r, (u, v) in zip(g["rows"], cut)]
+        g["src"], g["dst"] = int(real(g["src"])), int(real(g["dst"]))
+        g["path"] = [int(v) for v in real(g["path"])]
+        if "v0" in g["expect"]:
+            g["expect"]["v0"] = int(real(g["expect"]["v0"]))
+    src, dst = real(np.concatenate(es)), real(np.concatenate(ed))
+    assert (np.bincount(dst, minlength=len(tdeg))[:len(tdeg)] == np.array(tdeg)).all(), "the target zone's in-degrees are the declared ones"
+    spread_rows = fixed + ballast + [r for g in gadgets if g["family"] in ("spread", "spill") for r in g["rows"]]
+    return PullGadgets(V=int(base[-1]), src=src, dst=dst, rs=real([r[0] for r in rows]), rd=real([r[1] for r in rows]),
+                       dist=np.array([r[2] for r in rows], dtype=np.int64), tag=np.array([r[3] for r in rows]), gadgets=gadgets,
+                       fixed=fixed, pairs=pairs, stale=stale, spread=np.array(spread_rows, dtype=np.int64), negative=negative,
+                       part_weight=part_weight, hub_chunk=hub_chunk, n_targets=len(tdeg), spread_sources=[int(real(s)) for s in spread])
