@@ -4,7 +4,10 @@
 //
 // Part of pgq_cheapest.hip's translation unit (included at the end of pgq_cheapest_path.hip, not compiled on its own): the hop
 // counts live in that file's H table (ws->tight_h, 64 lanes per vertex, "-1 everywhere between calls"), the frontier masks and
-// queues are k_tight_levels', LC and k_fill32 are defined there.  Weights are never read: the calls work on any CSR.
+// queues are k_tight_levels', LC and k_fill32 are defined there.  What this call shares with k_shortest_walks (pgq_k_walks.hip) —
+// the saturating add and scan, the pull's inner loop, one step of the unranking, the tails kernel, the list staging, the call
+// skeleton ListCall with its layout, the C entry points' prologues and epilogues — is in pgq_path_lists.h, described there once.
+// Weights are never read: the calls work on any CSR.
 //
 // The contract, for a row (src, dst).  L[v] = the BFS level of v from src, d = L[dst];
 //   sigma[src] = 1,  sigma[x] = min(INT64_MAX, sum of sigma[u] over the in-slots (u, x) with L[u] = L[x] - 1)
@@ -34,15 +37,14 @@
 //   3. k_asp_after clears the consumed mask words and counts the destinations still without H.  The rounds end with the
 //      frontier, when every destination has its H (its sigma was completed in the same round), or after max_hops rounds.
 //   4. k_asp_plan, a thread per row: hops, sigma, the paths the row emits and their elements; two exclusive scans place them.
-//   5. k_asp_unrank, a wavefront per emitted path: step t reads x_t's in-list 64 positions at a time, a saturating inclusive
-//      prefix sum over the wavefront, a ballot and a find-first-set pick the position, the rank loses the exclusive prefix; then
-//      u's out-list gives the m-th slot into x_t.  Loops are bounded by d and the lists' lengths; a step that finds nothing, or
-//      a walk that does not end on the lane's source, raises the batch's error flag and the call fails with PGQ_ERR_HIP.
+//   5. k_asp_unrank, a wavefront per emitted path: step t is unrank_step (pgq_path_lists.h) with the weight sigma[u][l] where
+//      H[u][l] == t - 1.  Loops are bounded by d and the lists' lengths; a step that finds nothing, or a walk that does not end
+//      on the lane's source, raises the batch's error flag and the call fails with PGQ_ERR_HIP.
 //   6. H and the masks go back to "none" over the touched list.  sigma needs no reset: it is only read where H says it was
 //      written in this batch.  On an error return ws->tight_V stays invalid and the next call fills H whole (PathBatches' rule).
-//   7. Behind the last batch: the src == dst and NULL rows, scans in ROW order, and the gather of outer entries {first path,
-//      paths}, inner entries {offset, 2 d + 1} and the child payload.  Results go to the caller only then: a call that fails
-//      has written nothing.
+//   7. Behind the last batch (ListCall::layout): the src == dst and NULL rows, scans in ROW order, and the gather of outer
+//      entries {first path, paths}, inner entries {offset, 2 d + 1} and the child payload.  Results go to the caller only then: a
+//      call that fails has written nothing.
 // Kernel-class time: the rounds are K_PUSH, plan / unranking / gather K_RECON.  768 bytes per vertex per batch: H (shared with
 // cheapest_path) and sigma (from the block cache for the call).
 // Not built: _multi forms, splitting long in-lists over several wavefronts (a list is walked by the one wavefront that meets
@@ -58,12 +60,6 @@ struct AspCounters {
 	u32 pad;
 	u64 edges;   // adjacency entries the rounds walked
 };
-
-constexpr int64_t kAspMax = 0x7FFFFFFFFFFFFFFFll;
-__device__ __forceinline__ int64_t asp_sat_add(int64_t a, int64_t b) { // a, b >= 0
-	const u64 s = (u64)a + (u64)b;
-	return s > (u64)kAspMax ? kAspMax : (int64_t)s;
-}
 
 // the batch's sources: H = 0, sigma = 1, in the first frontier and on the touched list (distinct sources: distinct vertices)
 __global__ void k_asp_init(const int32_t *__restrict__ usrc, int64_t U, int64_t base, int32_t *__restrict__ H, int64_t *__restrict__ sigma,
@@ -139,20 +135,9 @@ __global__ __launch_bounds__(256) void k_asp_sigma(const int64_t *__restrict__ r
 		const int h = H[(size_t)n * LC + lane];
 		const bool want = h == round;
 		const bool first = !__any(h >= 0 && h < round); // no lane had reached n before this round
-		int64_t acc = 0;
+		// (mask_prev[u] IS "H[u][l] == round - 1": only the neighbours of the last frontier are visited)
+		const int64_t acc = pull_masked_sum(n, lane, want, roff, radj, mask_prev, sigma);
 		const int64_t rb = roff[n], re = roff[n + 1];
-		for (int64_t j0 = rb; j0 < re; j0 += 64) { // 64 in-neighbours and their mask words per trip; only those of the last frontier are visited
-			const int cand = j0 + lane < re ? radj[j0 + lane] : -1;
-			const u64 cm = cand >= 0 ? mask_prev[cand] : 0ull; // the lanes with H[cand] == round - 1
-			u64 live = __ballot(cm != 0ull);
-			while (live) { // (in in-list order; a saturating sum of non-negative terms does not depend on it anyway)
-				const int bpos = __ffsll((long long)live) - 1;
-				live &= live - 1;
-				const int u = __shfl(cand, bpos);
-				const u64 mu = __shfl(cm, bpos);
-				if (want && ((mu >> lane) & 1ull)) acc = asp_sat_add(acc, sigma[(size_t)u * LC + lane]);
-			}
-		}
 		if (want) sigma[(size_t)n * LC + lane] = acc;
 		if (lane == 0) {
 			if (first) touched[atomicAdd(&tc->nt, 1u)] = n; // a vertex is queued once per round and is `first` in one round only: <= V entries
@@ -176,7 +161,7 @@ __global__ void k_asp_after(const int32_t *__restrict__ qcur, u64 *__restrict__ 
 // per row of the batch: hops (-1: none within the bound), sigma, the paths it emits, their elements
 __global__ void k_asp_plan(int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst,
                            u32 base_lane, const int32_t *__restrict__ H, const int64_t *__restrict__ sigma, int64_t max_paths,
-                           int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np,
+                           int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np, int64_t *__restrict__ r_el,
                            int64_t *__restrict__ cntp, int64_t *__restrict__ cnte) {
 	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= hi) return;
@@ -190,7 +175,7 @@ __global__ void k_asp_plan(int64_t lo, int64_t hi, const u32 *__restrict__ skey,
 	const int64_t np = min(count, max_paths);
 	r_np[row] = np;
 	cntp[i - lo] = np;
-	cnte[i - lo] = np * (2 * d + 1); // np <= 2^31, 2 d + 1 < 2^32
+	r_el[row] = cnte[i - lo] = np * (2 * d + 1); // np <= 2^31, 2 d + 1 < 2^32 (np = 0 where d < 0)
 }
 
 // One wavefront per emitted path (row, rank): the list, written back to front into the row's slice of the staging buffer.
@@ -203,13 +188,7 @@ __global__ __launch_bounds__(64) void k_asp_unrank(int64_t lo, int64_t m, int64_
                                                   int64_t *__restrict__ stage, int64_t *__restrict__ soff, AspCounters *__restrict__ tc) {
 	const int lane = threadIdx.x;
 	for (int64_t p = blockIdx.x; p < npaths; p += gridDim.x) {
-		// the row: the last j in [0, m) with ploc[j] <= p (rows without paths share their successor's start and are passed over)
-		int64_t a = 0, b = m;
-		while (b - a > 1) {
-			const int64_t mid = (a + b) >> 1;
-			if (ploc[mid] <= p) a = mid;
-			else b = mid;
-		}
+		const int64_t a = rank_row(ploc, m, p);
 		const int64_t i = lo + a;
 		int64_t r = p - ploc[a];
 		const u32 l = skey[i] - base_lane;
@@ -226,63 +205,19 @@ __global__ __launch_bounds__(64) void k_asp_unrank(int64_t lo, int64_t m, int64_
 		}
 		bool lost = false;
 		for (int t = d; t >= 1 && !lost; t--) {
-			const int64_t rb = roff[x], re = roff[x + 1];
-			int64_t jsel = -1;
-			int u = -1;
-			for (int64_t j0 = rb; j0 < re; j0 += 64) {
-				const int64_t j = j0 + lane;
-				const int cand = j < re ? radj[j] : -1;
-				const int64_t s = cand >= 0 && H[(size_t)cand * LC + l] == t - 1 ? sigma[(size_t)cand * LC + l] : 0;
-				int64_t inc = s; // saturating inclusive prefix sum over the wavefront
-				for (int o = 1; o < 64; o <<= 1) {
-					const int64_t y = __shfl_up(inc, o);
-					if (lane >= o) inc = asp_sat_add(inc, y);
-				}
-				int64_t exc = __shfl_up(inc, 1);
-				if (lane == 0) exc = 0;
-				const u64 hit = __ballot(r < inc); // inc never falls along the lanes: the first lane past r holds the slot
-				if (hit) {
-					const int pos = __ffsll((long long)hit) - 1;
-					r -= __shfl(exc, pos);
-					u = __shfl(cand, pos);
-					jsel = j0 + pos;
-					break;
-				}
-				r -= __shfl(inc, 63); // (<= r, so it is a true sum)
-			}
-			if (jsel < 0) {
-				if (lane == 0) atomicOr(&tc->error, 2u);
-				lost = true;
-				break;
-			}
-			// the taken in-slot is the mth from u into x (they are consecutive: the in-list is ordered by parent, then forward slot)
-			int mth = 0;
-			for (int64_t j = rb + lane; j < jsel; j += 64) mth += radj[j] == u ? 1 : 0;
-			for (int o = 32; o > 0; o >>= 1) mth += __shfl_xor(mth, o);
-			// ... its edge the mth slot of u's out-list into x
-			int64_t slot = -1;
-			const int64_t fb = off[u], fe = off[u + 1];
-			for (int64_t e0 = fb; e0 < fe && slot < 0; e0 += 64) {
-				const int64_t e = e0 + lane;
-				u64 hm = __ballot(e < fe && adj[e] == x);
-				const int c = __popcll(hm);
-				if (mth < c) {
-					for (int k = 0; k < mth; k++) hm &= hm - 1;
-					slot = e0 + __ffsll((long long)hm) - 1;
-				} else {
-					mth -= c;
-				}
-			}
-			if (slot < 0) {
-				if (lane == 0) atomicOr(&tc->error, 4u);
+			const UnrankStep step = unrank_step(x, r, lane, roff, radj, off, adj, [&](int cand) -> int64_t {
+				return H[(size_t)cand * LC + l] == t - 1 ? sigma[(size_t)cand * LC + l] : 0;
+			});
+			if (step.error) {
+				if (lane == 0) atomicOr(&tc->error, step.error);
 				lost = true;
 				break;
 			}
 			if (lane == 0) {
-				out[2 * t - 1] = edge_ids ? edge_ids[slot] : slot;
-				out[2 * t - 2] = u;
+				out[2 * t - 1] = edge_ids ? edge_ids[step.slot] : step.slot;
+				out[2 * t - 2] = step.u;
 			}
-			x = u;
+			x = step.u;
 		}
 		if (!lost && lane == 0 && x != usrc[base_lane + l]) atomicOr(&tc->error, 8u);
 	}
@@ -301,21 +236,6 @@ __global__ void k_asp_reset(const int32_t *__restrict__ touched, const AspCounte
 	}
 }
 
-// src == dst rows: no hops, one path; rows without a lane: a NULL endpoint (count -1) or an endpoint no edge leaves / enters (0)
-__global__ void k_asp_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, const u32 *__restrict__ sidx, const int64_t *__restrict__ src,
-                            const int64_t *__restrict__ dst, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np) {
-	const int64_t i = lo_trivial + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const u32 row = sidx[i];
-	const bool trivial = i < lo_null;
-	r_len[row] = trivial ? 0 : -1;
-	r_count[row] = trivial ? 1 : (src[row] < 0 || dst[row] < 0 ? -1 : 0);
-	if (r_np) r_np[row] = trivial ? 1 : 0;
-}
-__global__ void k_asp_elements(int64_t n, const int64_t *__restrict__ r_len, const int64_t *__restrict__ r_np, int64_t *__restrict__ r_el) {
-	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) r_el[i] = r_np[i] > 0 ? r_np[i] * (2 * r_len[i] + 1) : 0;
-}
 // Row order: a wavefront per sorted position below lo_null copies the row's staged lists (they lie behind each other by rank)
 // to its place in the child payload and writes its inner entries; src == dst rows write their one-element list.
 __global__ __launch_bounds__(64) void k_asp_gather(int64_t lo_trivial, int64_t lo_null, const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst,
@@ -346,70 +266,30 @@ __global__ __launch_bounds__(64) void k_asp_gather(int64_t lo_trivial, int64_t l
 	}
 }
 
-// Where one call's results go.  lists = false: the counts alone (d_count).  External buffers (bulk form) with their capacities,
-// or none (chunk form): then the inner entries and the payload land in ws->asp_paths / ws->child, grown to fit.
-struct AspOut {
-	bool lists = false;
-	int64_t max_paths = 1;
-	int64_t *d_len = nullptr, *d_count = nullptr, *d_first = nullptr, *d_np = nullptr;
-	int64_t *d_path_off = nullptr, path_cap = 0, *d_child = nullptr, child_cap = 0;
-	bool external = false;
-	int64_t paths_used = 0, child_used = 0;
-	bool overflow = false;
-};
-
-class AspCall {
+// The level and sigma rounds of the lane batches on ListCall's skeleton (pgq_path_lists.h): its run, emit and layout.
+class AspCall : ListCall {
 public:
-	AspCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops, AspOut &out)
-	    : c(c), ws(ws), n(n), d_src(d_src), d_dst(d_dst), max_hops(max_hops), out(out), temps(ws->stream) {}
+	AspCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops, ListOut &out)
+	    : ListCall(c, ws, n, d_src, d_dst, out, "all_shortestpaths", "paths"), max_hops(max_hops), temps(ws->stream) {}
 
 	int run() {
-		S.pairs += n;
-		if (n == 0) return PGQ_OK;
-		if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
-		u32 U = 0;
-		PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U));
-		S.unique_sources += U;
-		const int nb = (int)(((int64_t)U + LC - 1) / LC);
-		PGQ_TRY(batch_bounds(ws, n, LC, nb));
-		// the rows' results, in row order: hops, sigma, paths, elements, first path, first element (n + 1 entries each)
-		PGQ_TRY(ws->asp_rows.reserve((size_t)(n + 1) * 8 * 6));
-		int64_t *rows = ws->asp_rows.as<int64_t>();
-		r_len = rows, r_count = rows + (n + 1), r_np = rows + 2 * (n + 1), r_el = rows + 3 * (n + 1), r_first = rows + 4 * (n + 1), r_eoff = rows + 5 * (n + 1);
-		if (nb > 0) {
-			PGQ_TRY(prepare());
-			const int64_t *bs = ws->h_bstart;
-			for (int b = 0; b < nb; b++) PGQ_TRY(batch(bs[b], bs[b + 1], (int64_t)b * LC, U));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-			ws->tight_V = c->V; // behind the last batch's reset, waited for
-		}
-		return layout(nb);
+		return ListCall::run(
+		    false, [&] { return prepare(); }, [&](int64_t lo, int64_t hi, int64_t base, u32 U) { return batch(lo, hi, base, U); },
+		    [&](int nb) {
+			    if (nb > 0) ws->tight_V = c->V; // behind the last batch's reset, waited for
+			    return layout(nb, 0, [&](int64_t lo_t, int64_t lo_n, int64_t *path_off, int64_t *path_len, int64_t *child) {
+				    hipLaunchKernelGGL(k_asp_gather, dim3((unsigned)std::min<int64_t>(lo_n, 1 << 20)), dim3(64), 0, st, lo_t, lo_n, ws->sidx.as<u32>(),
+				                       ws->sdst.as<int32_t>(), r_len, r_np, r_first, r_eoff, ws->soff.as<int64_t>(), ws->tight_stage.as<int64_t>(), path_off, path_len, child);
+			    }, 16.0);
+		    });
 	}
 
 private:
-	pgq_csr *const c;
-	Workspace *const ws;
-	const int64_t n;
-	const int64_t *const d_src, *const d_dst;
 	const int64_t max_hops;
-	AspOut &out;
 	DevTemps temps; // sigma and the touched list: block-cache memory for the call
-	const hipStream_t st = ws->stream;
-	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
-	pgq_stats_t &S = tstats().s;
 	AspCounters *tc = nullptr;
 	int64_t *sigma = nullptr;
 	int32_t *touched = nullptr;
-	int64_t *r_len = nullptr, *r_count = nullptr, *r_np = nullptr, *r_el = nullptr, *r_first = nullptr, *r_eoff = nullptr;
-	int64_t staged = 0, paths_so_far = 0;
-
-	int read_back(void *host, const void *dev, size_t bytes) {
-		PGQ_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		return PGQ_OK;
-	}
 
 	// H as PathBatches::prepare keeps it (shared with cheapest_path: tight_V says for which V "-1 everywhere" holds)
 	int prepare() {
@@ -434,6 +314,8 @@ private:
 		int32_t *H = ws->tight_h.as<int32_t>();
 		const int64_t m = hi - lo;
 		const unsigned cus = (unsigned)device_cus();
+		const u32 *skey = ws->skey.as<u32>(), *sidx = ws->sidx.as<u32>();
+		const int32_t *sdst = ws->sdst.as<int32_t>();
 		AspCounters h {};
 		S.batches++;
 		{
@@ -453,10 +335,9 @@ private:
 			                   par, (int)round);
 			// (the new queue's fill is not known here: the grid is sized for a frontier of any size, its wavefronts stride)
 			hipLaunchKernelGGL(k_asp_sigma, dim3(cus * 8), dim3(256), 0, st, c->roff, c->radj, H, sigma, mcur, qnxt, touched, tc, par ^ 1, (int)round);
-			hipLaunchKernelGGL(k_asp_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, qcur, mcur, par, lo, hi, ws->skey.as<u32>(),
-			                   ws->sdst.as<int32_t>(), (u32)base, H, tc);
+			hipLaunchKernelGGL(k_asp_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, qcur, mcur, par, lo, hi, skey, sdst, (u32)base, H, tc);
 			kt.stop();
-			PGQ_TRY(read_back(&h, tc, sizeof(h)));
+			PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 			S.levels++;
 			par ^= 1;
 			nq = h.nq[par];
@@ -464,101 +345,27 @@ private:
 		}
 		S.edges_scanned += (int64_t)h.edges;
 		S.algo_bytes[K_PUSH] += (double)h.edges * (4.0 + 256.0 + 512.0);
-		// hops, sigma, paths and elements per row; where the batch's paths and elements go
-		PGQ_TRY(ws->def_len.reserve((size_t)(m + 1) * 8 * 2));
-		PGQ_TRY(ws->def_ent.reserve((size_t)(m + 1) * 8 * 2));
-		int64_t *cntp = ws->def_len.as<int64_t>(), *cnte = cntp + (m + 1);
-		int64_t *ploc = ws->def_ent.as<int64_t>(), *eloc = ploc + (m + 1);
-		int64_t totals[2] = { 0, 0 }, at = 0;
-		{
+		// hops, sigma, paths and elements per row (the count alone: no places, nothing staged)
+		auto plan = [&](int64_t *cntp, int64_t *cnte) {
+			hipLaunchKernelGGL(k_asp_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, H, sigma, out.limit, r_len, r_count,
+			                   out.lists ? r_np : nullptr, r_el, cntp, cnte);
+		};
+		if (out.lists) {
+			PGQ_TRY(emit(m, plan, [&](int64_t npaths, const int64_t *ploc, const int64_t *eloc, int64_t at) {
+				hipLaunchKernelGGL(k_asp_unrank, dim3((unsigned)std::min<int64_t>(npaths, 1 << 20)), dim3(64), 0, st, lo, m, npaths, skey, sdst, (u32)base,
+				                   ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, H, sigma, ploc, eloc, at, ws->tight_stage.as<int64_t>(),
+				                   ws->soff.as<int64_t>(), tc);
+			}));
+		} else {
 			KernelTimer kt(st, K_RECON);
-			if (out.lists) PGQ_HIP_TRY(hipMemsetAsync(cntp, 0, (size_t)(m + 1) * 8 * 2, st));
-			if (m > 0)
-				hipLaunchKernelGGL(k_asp_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(), ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
-				                   (u32)base, H, sigma, out.max_paths, r_len, r_count, out.lists ? r_np : nullptr, cntp, cnte);
-			if (out.lists) {
-				PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cntp, ploc, (int)(m + 1), st); }));
-				PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnte, eloc, (int)(m + 1), st); }));
-			}
+			if (m > 0) plan(nullptr, nullptr);
 			kt.stop();
 		}
-		if (out.lists) {
-			PGQ_HIP_TRY(hipMemcpyAsync(&totals[0], ploc + m, 8, hipMemcpyDeviceToHost, st));
-			PGQ_HIP_TRY(hipMemcpyAsync(&totals[1], eloc + m, 8, hipMemcpyDeviceToHost, st));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-			paths_so_far += totals[0];
-			if (paths_so_far > 0x7FFFFFFFll) return fail(PGQ_ERR_UNSUPPORTED, "all_shortestpaths: the call would emit more than 2^31-1 paths");
-			const size_t need = (size_t)(staged + totals[1]) * 8;
-			if (need > ws->tight_stage.cap) PGQ_TRY(grow_keeping(ws->tight_stage, std::max(need, 2 * ws->tight_stage.cap), (size_t)staged * 8, st));
-			at = staged;
-			staged += totals[1];
-			S.algo_bytes[K_RECON] += (double)totals[1] * 8.0;
-			if (totals[0] > 0) {
-				KernelTimer kt(st, K_RECON);
-				hipLaunchKernelGGL(k_asp_unrank, dim3((unsigned)std::min<int64_t>(totals[0], 1 << 20)), dim3(64), 0, st, lo, m, totals[0], ws->skey.as<u32>(),
-				                   ws->sdst.as<int32_t>(), (u32)base, ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, H, sigma, ploc, eloc,
-				                   at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
-				kt.stop();
-			}
-		}
+		// (between the unranking launch and the wait for its error flag)
 		hipLaunchKernelGGL(k_asp_reset, dim3(cus * 4), dim3(256), 0, st, touched, tc, H, ws->tight_mask[0].as<u64>(), ws->tight_mask[1].as<u64>());
-		if (out.lists) {
-			PGQ_TRY(read_back(&h, tc, sizeof(h)));
-			if (h.error) return fail(PGQ_ERR_HIP, "all_shortestpaths: internal error: the unranking lost its way (no parent, no slot, or not at the source)");
-		}
-		return PGQ_OK;
-	}
-
-	// behind the last batch: the trivial and NULL rows, the scans in row order, capacities, the gather, the caller's arrays
-	int layout(int nb) {
-		const int64_t *bs = ws->h_bstart;
-		const int64_t lo_t = bs[nb + 1], lo_n = bs[nb + 2];
-		int64_t totals[2] = { 0, 0 };
-		KernelTimer kt(st, K_RECON);
-		if (n > lo_t)
-			hipLaunchKernelGGL(k_asp_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, lo_n, n, ws->sidx.as<u32>(), d_src, d_dst, r_len, r_count,
-			                   out.lists ? r_np : nullptr);
-		if (!out.lists) {
-			PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-			kt.stop();
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-			return PGQ_OK;
-		}
-		PGQ_HIP_TRY(hipMemsetAsync(r_np + n, 0, 8, st));
-		PGQ_HIP_TRY(hipMemsetAsync(r_el + n, 0, 8, st));
-		hipLaunchKernelGGL(k_asp_elements, dim3(blocks_for(n)), dim3(256), 0, st, n, r_len, r_np, r_el);
-		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, r_np, r_first, (int)(n + 1), st); }));
-		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, r_el, r_eoff, (int)(n + 1), st); }));
-		PGQ_HIP_TRY(hipMemcpyAsync(&totals[0], r_first + n, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(&totals[1], r_eoff + n, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		if (totals[0] > 0x7FFFFFFFll) return fail(PGQ_ERR_UNSUPPORTED, "all_shortestpaths: the call would emit more than 2^31-1 paths");
-		out.paths_used = totals[0];
-		out.child_used = totals[1];
-		int64_t *path_off = out.d_path_off, *path_len = nullptr, *child = out.d_child;
-		if (!out.external) {
-			PGQ_TRY(ws->asp_paths.reserve((size_t)std::max<int64_t>(totals[0], 1) * 8 * 2));
-			PGQ_TRY(ws->child.reserve((size_t)std::max<int64_t>(totals[1], 1) * 8));
-			path_off = ws->asp_paths.as<int64_t>();
-			path_len = path_off + std::max<int64_t>(totals[0], 1);
-			child = ws->child.as<int64_t>();
-		} else if (totals[0] > out.path_cap || totals[1] > out.child_cap) {
-			out.overflow = true;
-		}
-		if (!out.overflow && lo_n > 0)
-			hipLaunchKernelGGL(k_asp_gather, dim3((unsigned)std::min<int64_t>(lo_n, 1 << 20)), dim3(64), 0, st, lo_t, lo_n, ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
-			                   r_len, r_np, r_first, r_eoff, ws->soff.as<int64_t>(), ws->tight_stage.as<int64_t>(), path_off, path_len, child);
-		PGQ_HIP_TRY(hipMemcpyAsync(out.d_len, r_len, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(out.d_np, r_np, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		if (!out.overflow) PGQ_HIP_TRY(hipMemcpyAsync(out.d_first, r_first, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		kt.stop();
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		S.algo_bytes[K_RECON] += (double)totals[1] * 16.0 + (double)totals[0] * 16.0 + (double)n * 64.0;
-		return PGQ_OK;
+		if (!out.lists) return PGQ_OK;
+		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
+		return unrank_status(h.error);
 	}
 };
 
@@ -581,7 +388,7 @@ int pgq_shortestpath_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t 
 		return asp_check_bounds(max_hops, nullptr);
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		AspOut out;
+		ListOut out;
 		out.d_count = d_out_count;
 		return AspCall(csr, ws, n, d_src, d_dst, max_hops, out).run();
 	});
@@ -599,47 +406,19 @@ int pgq_all_shortestpaths_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *
 		return asp_check_bounds(max_hops, &max_paths);
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		AspOut out;
-		out.lists = true, out.external = true;
-		out.max_paths = std::min<int64_t>(max_paths, 1LL << 31);
+		ListOut out;
 		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths;
 		out.d_path_off = d_path_offset, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
-		const int rc = AspCall(csr, ws, n, d_src, d_dst, max_hops, out).run();
-		if (paths_used) *paths_used = out.paths_used;
-		if (child_used) *child_used = out.child_used;
-		if (rc == PGQ_OK && out.overflow) return fail(PGQ_ERR_INVALID_ARG, "path or child buffer too small for the lists (see *paths_used, *child_used)");
-		return rc;
+		return list_bulk_body(out, max_paths, [&](ListOut &o) { return AspCall(csr, ws, n, d_src, d_dst, max_hops, o).run(); }, paths_used, child_used);
 	});
-}
-
-// the chunk forms' rows on the device: NULL src or NULL dst -> -1
-static int asp_stage_rows(Workspace *ws, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst) {
-	FlatPairs fp;
-	PGQ_TRY(flatten_pairs(V, n, src, dst, fp, true));
-	for (int64_t i = 0; i < n; i++)
-		if (!fp.dst_valid[i]) fp.src[i] = -1;
-	return stage_pairs(ws, n, fp.src.data(), fp.dst.data());
 }
 
 int pgq_shortestpath_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, int64_t *out_count, uint64_t *out_valid) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-		if (n < 0 || (n > 0 && (!out_count || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-		PGQ_TRY(asp_check_bounds(max_hops, nullptr));
-		return n == 0 ? kNoRows : PGQ_OK;
-	};
+	auto check = [&] { return count_chunk_check(csr, V, n, out_count, out_valid, [&] { return asp_check_bounds(max_hops, nullptr); }); };
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		PGQ_TRY(asp_stage_rows(ws, V, n, src, dst));
-		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
-		AspOut out;
-		out.d_count = ws->out_len.as<int64_t>();
-		PGQ_TRY(AspCall(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), max_hops, out).run());
-		PGQ_TRY(staged_download(out_count, ws->out_len.p, (size_t)n * 8, ws->stream));
-		mask_fill_valid(out_valid, n);
-		for (int64_t i = 0; i < n; i++)
-			if (out_count[i] < 0) mask_set_invalid(out_valid, i);
-		return PGQ_OK;
+		auto run = [&](ListOut &o, const int64_t *d_src, const int64_t *d_dst) { return AspCall(csr, ws, n, d_src, d_dst, max_hops, o).run(); };
+		return count_chunk_body(ws, V, n, src, dst, run, out_count, out_valid);
 	});
 }
 
@@ -647,53 +426,11 @@ int pgq_all_shortestpaths(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, p
                           uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
                           uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-		if (n < 0 || (n > 0 && (!out_first || !out_npaths || !out_valid)) || !out_path_offset || !out_path_length || !out_path_total || !out_child || !out_child_len)
-			return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-		PGQ_TRY(asp_check_bounds(max_hops, &max_paths));
-		*out_path_offset = *out_path_length = nullptr;
-		*out_child = nullptr;
-		*out_path_total = *out_child_len = 0;
-		return n == 0 ? kNoRows : PGQ_OK;
-	};
+	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len };
+	auto check = [&] { return list_chunk_check(csr, V, n, o, [&] { return asp_check_bounds(max_hops, &max_paths); }); };
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		PGQ_TRY(asp_stage_rows(ws, V, n, src, dst));
-		for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve((size_t)n * 8 * 2));
-		AspOut out;
-		out.lists = true;
-		out.max_paths = std::min<int64_t>(max_paths, 1LL << 31);
-		out.d_len = ws->out_len.as<int64_t>(), out.d_count = out.d_len + n, out.d_first = ws->out_off.as<int64_t>(), out.d_np = out.d_first + n;
-		PGQ_TRY(AspCall(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), max_hops, out).run());
-		std::vector<int64_t> len(n), first_np((size_t)2 * n);
-		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
-		PGQ_TRY(staged_download(first_np.data(), ws->out_off.p, (size_t)n * 8 * 2, ws->stream));
-		// one arena block: the child payload, then the inner entries' offsets and lengths
-		const size_t P = (size_t)out.paths_used, C = (size_t)out.child_used;
-		std::vector<int64_t> &arena = thread_child_arena();
-		arena.resize(C + 2 * P);
-		if (C > 0) PGQ_TRY(staged_download(arena.data(), ws->child.p, C * 8, ws->stream));
-		if (P > 0) {
-			PGQ_TRY(staged_download(arena.data() + C, ws->asp_paths.p, P * 8, ws->stream));
-			PGQ_TRY(staged_download(arena.data() + C + P, ws->asp_paths.as<int64_t>() + P, P * 8, ws->stream));
-		}
-		mask_fill_valid(out_valid, n);
-		for (int64_t i = 0; i < n; i++) {
-			if (len[i] < 0) {
-				mask_set_invalid(out_valid, i);
-				out_first[i] = 0;
-				out_npaths[i] = 0;
-			} else {
-				out_first[i] = (uint64_t)first_np[i];
-				out_npaths[i] = (uint64_t)first_np[(size_t)n + i];
-			}
-		}
-		*out_child = arena.data();
-		*out_child_len = (uint64_t)C;
-		*out_path_offset = reinterpret_cast<const uint64_t *>(arena.data() + C);
-		*out_path_length = reinterpret_cast<const uint64_t *>(arena.data() + C + P);
-		*out_path_total = (uint64_t)P;
-		return PGQ_OK;
+		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return AspCall(csr, ws, n, d_src, d_dst, max_hops, lo).run(); };
+		return list_chunk_body(ws, V, n, src, dst, max_paths, run, o);
 	});
 }
 

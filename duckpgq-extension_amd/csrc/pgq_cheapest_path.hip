@@ -43,8 +43,11 @@
 // pgq_cheapest_path_within.hip, on this file's staging, layout and entry points (PathBatches, path_call).
 // Not built: _multi, the two-ended search, and any speed-up of the level rounds (a long list is walked by the one wavefront
 // that finds it).
-// pgq_all_shortest.hip (shortestpath_count, all_shortestpaths) is included at this file's end: it keeps its BFS levels in H.
-// pgq_k_walks.hip (walk_count, k_shortest_walks) comes behind it: tables of its own, all_shortestpaths' saturating add and row staging.
+// pgq_path_lists.h is included at this file's head: the staging of a batch's lists (ListStage) that every driver here uses, and
+// what the nested-list calls share.  pgq_all_shortest.hip (shortestpath_count, all_shortestpaths) is included at this file's end:
+// it keeps its BFS levels in H.  pgq_k_walks.hip (walk_count, k_shortest_walks) comes behind it, with tables of its own.
+
+#include "pgq_path_lists.h"
 
 namespace pgq {
 
@@ -251,7 +254,9 @@ __global__ void k_list_gather(int64_t lo_trivial, int64_t lo_null, const u32 *__
 // levels = false: the staging and the layout alone, for a driver with a walk-back of its own (cheapest_path_within).
 template <typename T> class PathBatches {
 public:
-	PathBatches(pgq_csr *c, Workspace *ws, u32 U, int64_t *d_out_len, bool levels = true) : c(c), ws(ws), U(U), d_out_len(d_out_len), levels(levels) {}
+	PathBatches(pgq_csr *c, Workspace *ws, u32 U, int64_t *d_out_len, bool levels = true) : stage(ws), c(c), ws(ws), U(U), d_out_len(d_out_len), levels(levels) {}
+
+	ListStage stage; // the places of a batch's lists and the room for them: also for a driver with a walk-back of its own
 
 	int prepare() {
 		PGQ_TRY(ws->tight_cnt.reserve(sizeof(TightCounters)));
@@ -273,31 +278,6 @@ public:
 		if (levels) ws->tight_V = c->V;
 	}
 	TightCounters *counters() const { return tc; }
-
-	// The places of a batch's m lists: `lengths(cnt)` enqueues the kernel that writes every row's element count, their
-	// exclusive scan is *loc; *total (their sum) is on the host once the stream has been waited for.
-	template <typename Lengths> int place_rows(int64_t m, Lengths &&lengths, int64_t **loc, int64_t *total) {
-		PGQ_TRY(ws->def_len.reserve((size_t)(m + 1) * 8));
-		PGQ_TRY(ws->def_ent.reserve((size_t)(m + 1) * 8));
-		int64_t *cnt = ws->def_len.as<int64_t>();
-		*loc = ws->def_ent.as<int64_t>();
-		KernelTimer kt(st, K_RECON);
-		PGQ_HIP_TRY(hipMemsetAsync(cnt + m, 0, 8, st));
-		lengths(cnt);
-		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, *loc, (int)(m + 1), st); }));
-		kt.stop();
-		PGQ_HIP_TRY(hipMemcpyAsync(total, *loc + m, 8, hipMemcpyDeviceToHost, st));
-		return PGQ_OK;
-	}
-	// room for `total` more elements in the staging buffer, behind the finished batches' lists: *at = where they start
-	int stage_reserve(int64_t total, int64_t *at) {
-		const size_t need = (size_t)(staged + total) * 8;
-		if (need > ws->tight_stage.cap) PGQ_TRY(grow_keeping(ws->tight_stage, std::max(need, 2 * ws->tight_stage.cap), (size_t)staged * 8, st));
-		*at = staged;
-		staged += total;
-		S.algo_bytes[K_RECON] += (double)total * 8.0;
-		return PGQ_OK;
-	}
 
 	// rows [lo, hi) of the sorted arrays, lane 0 = distinct source `base`; the batch's labels are final and in place
 	int batch(int64_t lo, int64_t hi, int64_t base) {
@@ -323,7 +303,7 @@ public:
 			hipLaunchKernelGGL(k_tight_pending, dim3(row_blocks), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(), ws->sdst.as<int32_t>(), (u32)base, dist, H,
 			                   Inf<T>::bits, tc);
 			kt.stop();
-			PGQ_TRY(read_back(&h, tc, sizeof(h)));
+			PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 			S.levels++;
 			par ^= 1;
 			nq = h.nq[par];
@@ -335,13 +315,13 @@ public:
 		// lengths, their scan, the batch's total
 		const int64_t m = hi - lo;
 		int64_t *loc = nullptr, total = 0, at = 0;
-		PGQ_TRY(place_rows(m, [&](int64_t *cnt) {
+		PGQ_TRY(stage.place(m, [&](int64_t *const *cnt) {
 			hipLaunchKernelGGL(k_tight_lengths, dim3(row_blocks), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(), ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
-			                   (u32)base, dist, H, Inf<T>::bits, d_out_len, cnt, tc);
-		}, &loc, &total));
-		PGQ_TRY(read_back(&h, tc, sizeof(h)));
+			                   (u32)base, dist, H, Inf<T>::bits, d_out_len, cnt[0], tc);
+		}, 1, &loc, &total));
+		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 		if (h.error) return fail(PGQ_ERR_HIP, "cheapest_path: internal error: a destination with a label has no tight hop count");
-		PGQ_TRY(stage_reserve(total, &at));
+		PGQ_TRY(stage.stage_reserve(total, &at));
 		{
 			KernelTimer kt(st, K_RECON);
 			hipLaunchKernelGGL(k_cheapest_walkback<T>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, hi, ws->skey.as<u32>(),
@@ -353,7 +333,7 @@ public:
 		hipLaunchKernelGGL(k_tight_reset_touched, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, ws->relax[0].touched.as<int32_t>(),
 		                   &reinterpret_cast<RelaxCounters *>(ws->counters.p)->tcount, H);
 		if (early) PGQ_HIP_TRY(hipMemsetAsync(ws->tight_mask[par].p, 0, Vn * 8, st));
-		PGQ_TRY(read_back(&h, tc, sizeof(h)));
+		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 		if (h.error) return fail(PGQ_ERR_HIP, "cheapest_path: internal error: the walk back found no tight parent at some step");
 		return PGQ_OK;
 	}
@@ -402,14 +382,6 @@ private:
 	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
 	pgq_stats_t &S = tstats().s;
 	TightCounters *tc = nullptr;
-	int64_t staged = 0; // elements of the finished batches' lists
-
-	int read_back(void *host, const void *dev, size_t bytes) {
-		PGQ_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		return PGQ_OK;
-	}
 };
 
 // The rows of one call (device memory, src < 0 = NULL row): lengths, offsets and lists.  One worker: the batches share the
@@ -497,12 +469,8 @@ static int cheapest_path_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t s
 		return n == 0 ? kNoRows : PGQ_OK;
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		FlatPairs fp;
-		PGQ_TRY(flatten_pairs(V, n, src, dst, fp, true));
-		for (int64_t i = 0; i < n; i++)
-			if (!fp.dst_valid[i]) fp.src[i] = -1; // NULL dst -> NULL, as in pgq_cheapest_path_length
+		PGQ_TRY(stage_rows_null_as_minus_one(ws, V, n, src, dst)); // NULL dst -> NULL, as in pgq_cheapest_path_length
 		for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve((size_t)n * 8));
-		PGQ_TRY(stage_pairs(ws, n, fp.src.data(), fp.dst.data()));
 		const int64_t *d_src = ws->in_src.as<int64_t>(), *d_dst = ws->in_dst.as<int64_t>();
 		int64_t used = 0;
 		bool overflow = false;
@@ -551,5 +519,5 @@ int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 
 } // extern "C"
 
-#include "pgq_all_shortest.hip" // shortestpath_count / all_shortestpaths: level rounds on this file's H table, masks and queues
-#include "pgq_k_walks.hip"      // walk_count / k_shortest_walks: rounds over all walks of lower..upper edges, tables of their own
+#include "pgq_all_shortest.hip" // shortestpath_count / all_shortestpaths: level rounds on this file's H table, masks and queues; ListCall's skeleton
+#include "pgq_k_walks.hip"      // walk_count / k_shortest_walks: rounds over all walks of lower..upper edges, tables of their own; ListCall's skeleton

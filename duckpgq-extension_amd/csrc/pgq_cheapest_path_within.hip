@@ -255,13 +255,12 @@ private:
 		const HopEntry *ent = ws->hop_ent.as<HopEntry>();
 		int64_t *loc = nullptr, total = 0, at = 0;
 		PGQ_HIP_TRY(hipMemsetAsync(tc, 0, sizeof(TightCounters), st));
-		PGQ_TRY(paths.place_rows(m, [&](int64_t *cnt) {
+		PGQ_TRY(paths.stage.place(m, [&](int64_t *const *cnt) {
 			hipLaunchKernelGGL(k_hop_lengths, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(), ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
-			                   (u32)base, last, mask, ent, d_out_len, cnt);
-		}, &loc, &total));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		PGQ_TRY(paths.stage_reserve(total, &at));
+			                   (u32)base, last, mask, ent, d_out_len, cnt[0]);
+		}, 1, &loc, &total));
+		PGQ_TRY(paths.stage.wait());
+		PGQ_TRY(paths.stage.stage_reserve(total, &at));
 		{
 			KernelTimer kt(st, K_RECON);
 			hipLaunchKernelGGL(k_hop_walkback<T>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, hi, ws->skey.as<u32>(),
@@ -273,9 +272,7 @@ private:
 		                   &reinterpret_cast<RelaxCounters *>(ws->counters.p)->tcount, ws->hop_last.as<int32_t>());
 		count = 0;
 		TightCounters h {};
-		PGQ_HIP_TRY(hipMemcpyAsync(&h, tc, sizeof(h), hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
+		PGQ_TRY(paths.stage.read_back(&h, tc, sizeof(h)));
 		if (h.error) return fail(PGQ_ERR_HIP, "cheapest_path_within: internal error: the walk back lost its way (no tight parent, no tight slot, or not at the source)");
 		return PGQ_OK;
 	}

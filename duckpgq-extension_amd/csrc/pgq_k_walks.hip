@@ -5,7 +5,9 @@
 // (src == dst is 0 hops there).  Every list follows shortestpath's layout (shortest_path.cpp:43-207).
 //
 // Part of pgq_cheapest.hip's translation unit (included at the end of pgq_cheapest_path.hip behind pgq_all_shortest.hip, not compiled
-// on its own): LC, asp_sat_add and the staging helpers are defined there.  Weights are never read: the calls work on any CSR.
+// on its own): LC is defined there.  The saturating add, the pull's inner loop, one step of the unranking, the tails kernel, the
+// list staging and the call skeleton ListCall with its layout are all_shortestpaths' too: pgq_path_lists.h, described there once.
+// Weights are never read: the calls work on any CSR.
 //
 // The contract, for a row (src, dst), lo = min_hops, K = max_hops, over the forward CSR's slots (parallel edges are separate slots):
 //   W_0[v] = 1 if v == src else 0
@@ -43,11 +45,11 @@
 //   Rounds stop after round K, with an empty queue, and (lists) when no row of the batch is short of k: k = 1 on a pair d apart
 //   costs d rounds.  walk_count has no such stop.  The host waits once per round for the counters.
 //   4. k_walk_plan, a thread per row: walks and elements per row from W_t[dst], t = lo..R; two exclusive scans place them.
-//   5. k_walk_unrank, a wavefront per emitted walk: its t by the same small loop, then all_shortestpaths' saturating prefix sum over
-//      64 in-list positions per step.  A step that finds no parent or no slot, or a walk that does not end on the lane's source,
-//      raises the error flag: PGQ_ERR_HIP.
+//   5. k_walk_unrank, a wavefront per emitted walk: its t by the same small loop, then unrank_step (pgq_path_lists.h) per step, with
+//      the weight W_{i-1}[u][l].  A step that finds no parent or no slot, or a walk that does not end on the lane's source, raises
+//      the error flag: PGQ_ERR_HIP.
 //   6. Behind the last batch: trivial rows (src == dst without a lane: [[src]] when lo == 0, nothing otherwise), NULL rows, scans in
-//      ROW order, k_walk_gather.  Results go to the caller only then: a call that fails has written nothing.
+//      ROW order, k_walk_gather (ListCall::layout).  Results go to the caller only then: a call that fails has written nothing.
 // The call owns its tables, masks and queues (block cache); it does not touch ws->tight_h / tight_mask / tight_q / tight_V, so
 // PathBatches and AspCall find them as they left them.  Lists are staged in ws->tight_stage, rows in ws->asp_rows.
 // Kernel-class time: the rounds are K_PUSH, plan / unranking / gather K_RECON.
@@ -140,20 +142,8 @@ __global__ __launch_bounds__(256) void k_walk_pull(const int64_t *__restrict__ r
 	for (u32 i = wave; i < nq; i += nwaves) {
 		const int n = qcur[i];
 		const bool want = (m_cur[n] >> lane) & 1ull;
-		int64_t acc = 0;
+		const int64_t acc = pull_masked_sum(n, lane, want, roff, radj, m_prev, w_prev); // (only the active in-neighbours are visited)
 		const int64_t rb = roff[n], re = roff[n + 1];
-		for (int64_t j0 = rb; j0 < re; j0 += 64) { // 64 in-neighbours and their mask words per trip; only the active ones are visited
-			const int cand = j0 + lane < re ? radj[j0 + lane] : -1;
-			const u64 cm = cand >= 0 ? m_prev[cand] : 0ull;
-			u64 live = __ballot(cm != 0ull);
-			while (live) {
-				const int bpos = __ffsll((long long)live) - 1;
-				live &= live - 1;
-				const int u = __shfl(cand, bpos);
-				const u64 mu = __shfl(cm, bpos);
-				if (want && ((mu >> lane) & 1ull)) acc = asp_sat_add(acc, w_prev[(size_t)u * LC + lane]);
-			}
-		}
 		if (want) w_cur[(size_t)n * LC + lane] = acc; // (> 0: some in-neighbour gave the lane its mask bit)
 		if (lane == 0 && re > rb) atomicAdd(&tc->edges, (u64)(re - rb));
 	}
@@ -217,13 +207,7 @@ __global__ __launch_bounds__(64) void k_walk_unrank(int64_t lo, int64_t m, int64
                                                    int64_t *__restrict__ stage, int64_t *__restrict__ soff, WalkCounters *__restrict__ tc) {
 	const int lane = threadIdx.x;
 	for (int64_t p = blockIdx.x; p < nwalks; p += gridDim.x) {
-		// the row: the last j in [0, m) with ploc[j] <= p (rows without walks share their successor's start and are passed over)
-		int64_t a = 0, b = m;
-		while (b - a > 1) {
-			const int64_t mid = (a + b) >> 1;
-			if (ploc[mid] <= p) a = mid;
-			else b = mid;
-		}
+		const int64_t a = rank_row(ploc, m, p);
 		const int64_t i = lo + a;
 		const int64_t rank = p - ploc[a], np = ploc[a + 1] - ploc[a];
 		int64_t r = rank;
@@ -255,80 +239,20 @@ __global__ __launch_bounds__(64) void k_walk_unrank(int64_t lo, int64_t m, int64
 		bool lost = false;
 		for (int s = t; s >= 1 && !lost; s--) {
 			const WalkRound pr = tabs[s - 1];
-			const int64_t rb = roff[x], re = roff[x + 1];
-			int64_t jsel = -1;
-			int u = -1;
-			for (int64_t j0 = rb; j0 < re; j0 += 64) {
-				const int64_t j = j0 + lane;
-				const int cand = j < re ? radj[j] : -1;
-				const int64_t sg = cand >= 0 ? walk_w(pr, cand, l) : 0;
-				int64_t inc = sg; // saturating inclusive prefix sum over the wavefront
-				for (int o = 1; o < 64; o <<= 1) {
-					const int64_t y = __shfl_up(inc, o);
-					if (lane >= o) inc = asp_sat_add(inc, y);
-				}
-				int64_t exc = __shfl_up(inc, 1);
-				if (lane == 0) exc = 0;
-				const u64 hit = __ballot(r < inc); // inc never falls along the lanes: the first lane past r holds the slot
-				if (hit) {
-					const int pos = __ffsll((long long)hit) - 1;
-					r -= __shfl(exc, pos);
-					u = __shfl(cand, pos);
-					jsel = j0 + pos;
-					break;
-				}
-				r -= __shfl(inc, 63); // (<= r, so it is a true sum)
-			}
-			if (jsel < 0) {
-				if (lane == 0) atomicOr(&tc->error, 2u);
-				lost = true;
-				break;
-			}
-			// the taken in-slot is the mth from u into x (they are consecutive: the in-list is ordered by parent, then forward slot)
-			int mth = 0;
-			for (int64_t j = rb + lane; j < jsel; j += 64) mth += radj[j] == u ? 1 : 0;
-			for (int o = 32; o > 0; o >>= 1) mth += __shfl_xor(mth, o);
-			// ... its edge the mth slot of u's out-list into x
-			int64_t slot = -1;
-			const int64_t fb = off[u], fe = off[u + 1];
-			for (int64_t e0 = fb; e0 < fe && slot < 0; e0 += 64) {
-				const int64_t e = e0 + lane;
-				u64 hm = __ballot(e < fe && adj[e] == x);
-				const int c = __popcll(hm);
-				if (mth < c) {
-					for (int k = 0; k < mth; k++) hm &= hm - 1;
-					slot = e0 + __ffsll((long long)hm) - 1;
-				} else {
-					mth -= c;
-				}
-			}
-			if (slot < 0) {
-				if (lane == 0) atomicOr(&tc->error, 4u);
+			const UnrankStep step = unrank_step(x, r, lane, roff, radj, off, adj, [&](int cand) -> int64_t { return walk_w(pr, cand, l); });
+			if (step.error) {
+				if (lane == 0) atomicOr(&tc->error, step.error);
 				lost = true;
 				break;
 			}
 			if (lane == 0) {
-				out[2 * s - 1] = edge_ids ? edge_ids[slot] : slot;
-				out[2 * s - 2] = u;
+				out[2 * s - 1] = edge_ids ? edge_ids[step.slot] : step.slot;
+				out[2 * s - 2] = step.u;
 			}
-			x = u;
+			x = step.u;
 		}
 		if (!lost && lane == 0 && x != usrc[base_lane + l]) atomicOr(&tc->error, 8u);
 	}
-}
-
-// rows without a lane.  Trivial: src == dst with no out-edge or no in-edge — the empty walk when min_hops == 0, nothing otherwise;
-// the others: a NULL endpoint (count -1) or a row that cannot have a walk (0)
-__global__ void k_walk_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, int64_t min_hops, const u32 *__restrict__ sidx, const int64_t *__restrict__ src,
-                             const int64_t *__restrict__ dst, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np,
-                             int64_t *__restrict__ r_el) {
-	const int64_t i = lo_trivial + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const u32 row = sidx[i];
-	const bool empty_walk = i < lo_null && min_hops == 0;
-	r_len[row] = empty_walk ? 0 : -1;
-	r_count[row] = empty_walk ? 1 : (i >= lo_null && (src[row] < 0 || dst[row] < 0) ? -1 : 0);
-	if (r_np) r_np[row] = r_el[row] = empty_walk ? 1 : 0;
 }
 
 // Row order: a wavefront per sorted position below lo_null copies the row's staged walks to its place in the child payload and
@@ -375,72 +299,34 @@ __global__ __launch_bounds__(64) void k_walk_gather(int64_t lo_trivial, int64_t 
 	}
 }
 
-// Where one call's results go.  lists = false: the counts alone (d_count).  External buffers (bulk form) with their capacities,
-// or none (chunk form): then the inner entries and the payload land in ws->asp_paths / ws->child, grown to fit.
-struct WalkOut {
-	bool lists = false;
-	int64_t k = 1;
-	int64_t *d_len = nullptr, *d_count = nullptr, *d_first = nullptr, *d_np = nullptr;
-	int64_t *d_path_off = nullptr, *d_path_hops = nullptr, path_cap = 0, *d_child = nullptr, child_cap = 0;
-	bool external = false;
-	int64_t paths_used = 0, child_used = 0;
-	bool overflow = false;
-};
-
-class WalkCall {
+// The walk rounds of the lane batches on ListCall's skeleton (pgq_path_lists.h): its run, emit and layout.
+class WalkCall : ListCall {
 public:
-	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, WalkOut &out)
-	    : c(c), ws(ws), n(n), d_src(d_src), d_dst(d_dst), min_hops(min_hops), max_hops(max_hops), out(out), temps(ws->stream) {}
+	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, ListOut &out)
+	    : ListCall(c, ws, n, d_src, d_dst, out, "k_shortest_walks", "walks"), min_hops(min_hops), max_hops(max_hops), temps(ws->stream) {}
 
 	int run() {
-		S.pairs += n;
-		if (n == 0) return PGQ_OK;
-		if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
-		u32 U = 0;
-		PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U, true, true));
-		S.unique_sources += U;
-		const int nb = (int)(((int64_t)U + LC - 1) / LC);
-		PGQ_TRY(batch_bounds(ws, n, LC, nb));
-		// the rows' results, in row order: first length, count, walks, elements, first walk, first element (n + 1 entries each)
-		PGQ_TRY(ws->asp_rows.reserve((size_t)(n + 1) * 8 * 6));
-		int64_t *rows = ws->asp_rows.as<int64_t>();
-		r_len = rows, r_count = rows + (n + 1), r_np = rows + 2 * (n + 1), r_el = rows + 3 * (n + 1), r_first = rows + 4 * (n + 1), r_eoff = rows + 5 * (n + 1);
-		if (nb > 0) {
-			PGQ_TRY(prepare());
-			const int64_t *bs = ws->h_bstart;
-			for (int b = 0; b < nb; b++) PGQ_TRY(batch(bs[b], bs[b + 1], (int64_t)b * LC, U));
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-		}
-		return layout(nb);
+		return ListCall::run(
+		    true, [&] { return prepare(); }, [&](int64_t lo, int64_t hi, int64_t base, u32 U) { return batch(lo, hi, base, U); },
+		    [&](int nb) {
+			    return layout(nb, min_hops, [&](int64_t lo_t, int64_t lo_n, int64_t *path_off, int64_t *path_len, int64_t *child) {
+				    hipLaunchKernelGGL(k_walk_gather, dim3((unsigned)std::min<int64_t>(lo_n, 1 << 20)), dim3(64), 0, st, lo_t, lo_n, ws->sidx.as<u32>(),
+				                       ws->sdst.as<int32_t>(), r_np, r_el, r_first, r_eoff, ws->soff.as<int64_t>(), ws->tight_stage.as<int64_t>(), path_off,
+				                       out.d_path_hops, path_len, child);
+			    }, 24.0);
+		    });
 	}
 
 private:
-	pgq_csr *const c;
-	Workspace *const ws;
-	const int64_t n;
-	const int64_t *const d_src, *const d_dst;
 	const int64_t min_hops, max_hops;
-	WalkOut &out;
 	DevTemps temps; // the rounds' tables, masks and queues: block-cache memory for the call
-	const hipStream_t st = ws->stream;
-	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
-	pgq_stats_t &S = tstats().s;
 	WalkCounters *tc = nullptr;
 	std::vector<int64_t *> W; // lists: one per round; counts: two
 	std::vector<u64 *> M;
 	std::vector<WalkRound> h_tabs;
 	WalkRound *d_tabs = nullptr;
 	int32_t *q[2] = { nullptr, nullptr };
-	int64_t *r_len = nullptr, *r_count = nullptr, *r_np = nullptr, *r_el = nullptr, *r_first = nullptr, *r_eoff = nullptr;
-	int64_t staged = 0, walks_so_far = 0;
 
-	int read_back(void *host, const void *dev, size_t bytes) {
-		PGQ_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		return PGQ_OK;
-	}
 	size_t slot_of(int64_t t) const { return out.lists ? (size_t)t : (size_t)(t & 1); }
 	// round t's table and (zeroed) mask
 	int ensure_round(int64_t t) {
@@ -471,7 +357,7 @@ private:
 	int batch(int64_t lo, int64_t hi, int64_t base, u32 U) {
 		const int64_t m = hi - lo;
 		const unsigned cus = (unsigned)device_cus();
-		const int64_t k_stop = out.lists ? out.k : kAspMax;
+		const int64_t k_stop = out.lists ? out.limit : kAspMax;
 		const u32 *skey = ws->skey.as<u32>(), *sidx = ws->sidx.as<u32>();
 		const int32_t *sdst = ws->sdst.as<int32_t>();
 		WalkCounters h {};
@@ -487,7 +373,7 @@ private:
 			                   round_of(0), r_len, r_count, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
 			kt.stop();
 		}
-		PGQ_TRY(read_back(&h, tc, sizeof(h)));
+		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 		int par = 0;
 		int rounds = 0;
 		for (int64_t t = 1; t <= max_hops && nq > 0 && m > 0 && !(out.lists && h.pending == 0); t++) {
@@ -502,7 +388,7 @@ private:
 			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, lo, hi, skey, sidx, sdst, (u32)base,
 			                   cur, r_len, r_count, (const int32_t *)q[par], out.lists ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
 			kt.stop();
-			PGQ_TRY(read_back(&h, tc, sizeof(h)));
+			PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 			S.levels++;
 			rounds = (int)t;
 			par ^= 1;
@@ -510,97 +396,24 @@ private:
 		}
 		S.edges_scanned += (int64_t)h.edges;
 		S.algo_bytes[K_PUSH] += (double)h.edges * (4.0 + 8.0 + 512.0);
-		if (!out.lists) return PGQ_OK;
+		if (!out.lists) return PGQ_OK; // (before any staging)
 		// walks and elements per row; where the batch's walks and staged blocks go
-		PGQ_TRY(ws->def_len.reserve((size_t)(m + 1) * 8 * 2));
-		PGQ_TRY(ws->def_ent.reserve((size_t)(m + 1) * 8 * 2));
-		int64_t *cntp = ws->def_len.as<int64_t>(), *cnte = cntp + (m + 1);
-		int64_t *ploc = ws->def_ent.as<int64_t>(), *eloc = ploc + (m + 1);
-		int64_t totals[2] = { 0, 0 };
 		h_tabs.assign((size_t)PGQ_WALK_MAX_HOPS + 1, WalkRound { nullptr, nullptr });
 		for (int t = 0; t <= rounds; t++) h_tabs[t] = round_of(t);
 		PGQ_HIP_TRY(hipMemcpyAsync(d_tabs, h_tabs.data(), h_tabs.size() * sizeof(WalkRound), hipMemcpyHostToDevice, st));
-		{
-			KernelTimer kt(st, K_RECON);
-			PGQ_HIP_TRY(hipMemsetAsync(cntp, 0, (size_t)(m + 1) * 8 * 2, st));
-			if (m > 0)
-				hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, min_hops, rounds, out.k, r_np, r_el,
-				                   cntp, cnte);
-			PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cntp, ploc, (int)(m + 1), st); }));
-			PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnte, eloc, (int)(m + 1), st); }));
-			kt.stop();
-		}
-		PGQ_HIP_TRY(hipMemcpyAsync(&totals[0], ploc + m, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(&totals[1], eloc + m, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		walks_so_far += totals[0];
-		if (walks_so_far > 0x7FFFFFFFll) return fail(PGQ_ERR_UNSUPPORTED, "k_shortest_walks: the call would emit more than 2^31-1 walks");
-		const size_t need = (size_t)(staged + totals[1]) * 8;
-		if (need > ws->tight_stage.cap) PGQ_TRY(grow_keeping(ws->tight_stage, std::max(need, 2 * ws->tight_stage.cap), (size_t)staged * 8, st));
-		const int64_t at = staged;
-		staged += totals[1];
-		S.algo_bytes[K_RECON] += (double)totals[1] * 8.0;
-		if (totals[0] > 0) {
-			KernelTimer kt(st, K_RECON);
-			hipLaunchKernelGGL(k_walk_unrank, dim3((unsigned)std::min<int64_t>(totals[0], 1 << 20)), dim3(64), 0, st, lo, m, totals[0], skey, sdst, (u32)base,
-			                   ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, min_hops, rounds, ploc, eloc, at,
-			                   ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
-			kt.stop();
-		}
-		PGQ_TRY(read_back(&h, tc, sizeof(h))); // (also: the next batch's memsets and table upload come behind this batch's kernels)
-		if (h.error) return fail(PGQ_ERR_HIP, "k_shortest_walks: internal error: the unranking lost its way (no parent, no slot, or not at the source)");
-		return PGQ_OK;
-	}
-
-	// behind the last batch: the trivial and NULL rows, the scans in row order, capacities, the gather, the caller's arrays
-	int layout(int nb) {
-		const int64_t *bs = ws->h_bstart;
-		const int64_t lo_t = bs[nb + 1], lo_n = bs[nb + 2];
-		int64_t totals[2] = { 0, 0 };
-		KernelTimer kt(st, K_RECON);
-		if (n > lo_t)
-			hipLaunchKernelGGL(k_walk_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, lo_n, n, min_hops, ws->sidx.as<u32>(), d_src, d_dst, r_len, r_count,
-			                   out.lists ? r_np : nullptr, r_el);
-		if (!out.lists) {
-			PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-			kt.stop();
-			PGQ_HIP_TRY(hipStreamSynchronize(st));
-			KernelTimer::flush();
-			return PGQ_OK;
-		}
-		PGQ_HIP_TRY(hipMemsetAsync(r_np + n, 0, 8, st));
-		PGQ_HIP_TRY(hipMemsetAsync(r_el + n, 0, 8, st));
-		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, r_np, r_first, (int)(n + 1), st); }));
-		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, r_el, r_eoff, (int)(n + 1), st); }));
-		PGQ_HIP_TRY(hipMemcpyAsync(&totals[0], r_first + n, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(&totals[1], r_eoff + n, 8, hipMemcpyDeviceToHost, st));
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		if (totals[0] > 0x7FFFFFFFll) return fail(PGQ_ERR_UNSUPPORTED, "k_shortest_walks: the call would emit more than 2^31-1 walks");
-		out.paths_used = totals[0];
-		out.child_used = totals[1];
-		int64_t *path_off = out.d_path_off, *path_hops = out.d_path_hops, *path_len = nullptr, *child = out.d_child;
-		if (!out.external) {
-			PGQ_TRY(ws->asp_paths.reserve((size_t)std::max<int64_t>(totals[0], 1) * 8 * 2));
-			PGQ_TRY(ws->child.reserve((size_t)std::max<int64_t>(totals[1], 1) * 8));
-			path_off = ws->asp_paths.as<int64_t>();
-			path_len = path_off + std::max<int64_t>(totals[0], 1);
-			child = ws->child.as<int64_t>();
-		} else if (totals[0] > out.path_cap || totals[1] > out.child_cap) {
-			out.overflow = true;
-		}
-		if (!out.overflow && lo_n > 0)
-			hipLaunchKernelGGL(k_walk_gather, dim3((unsigned)std::min<int64_t>(lo_n, 1 << 20)), dim3(64), 0, st, lo_t, lo_n, ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
-			                   r_np, r_el, r_first, r_eoff, ws->soff.as<int64_t>(), ws->tight_stage.as<int64_t>(), path_off, path_hops, path_len, child);
-		PGQ_HIP_TRY(hipMemcpyAsync(out.d_len, r_len, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		PGQ_HIP_TRY(hipMemcpyAsync(out.d_np, r_np, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		if (!out.overflow) PGQ_HIP_TRY(hipMemcpyAsync(out.d_first, r_first, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-		kt.stop();
-		PGQ_HIP_TRY(hipStreamSynchronize(st));
-		KernelTimer::flush();
-		S.algo_bytes[K_RECON] += (double)totals[1] * 16.0 + (double)totals[0] * 24.0 + (double)n * 64.0;
-		return PGQ_OK;
+		PGQ_TRY(emit(
+		    m,
+		    [&](int64_t *cntp, int64_t *cnte) {
+			    hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, min_hops, rounds, out.limit, r_np,
+			                       r_el, cntp, cnte);
+		    },
+		    [&](int64_t nwalks, const int64_t *ploc, const int64_t *eloc, int64_t at) {
+			    hipLaunchKernelGGL(k_walk_unrank, dim3((unsigned)std::min<int64_t>(nwalks, 1 << 20)), dim3(64), 0, st, lo, m, nwalks, skey, sdst, (u32)base,
+			                       ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, min_hops, rounds, ploc, eloc, at,
+			                       ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+		    }));
+		PGQ_TRY(stage.read_back(&h, tc, sizeof(h))); // (also: the next batch's memsets and table upload come behind this batch's kernels)
+		return unrank_status(h.error);
 	}
 };
 
@@ -628,7 +441,7 @@ int pgq_walk_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, 
 		return walk_check_bounds(min_hops, max_hops, nullptr);
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		WalkOut out;
+		ListOut out;
 		out.d_count = d_out_count;
 		return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, out).run();
 	});
@@ -647,44 +460,20 @@ int pgq_k_shortest_walks_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d
 		return walk_check_bounds(min_hops, max_hops, &k);
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		WalkOut out;
-		out.lists = true, out.external = true;
-		out.k = std::min<int64_t>(k, 1LL << 31);
+		ListOut out;
 		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths;
 		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
-		const int rc = WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, out).run();
-		if (rc == PGQ_OK) {
-			if (paths_used) *paths_used = out.paths_used;
-			if (child_used) *child_used = out.child_used;
-			if (out.overflow) return fail(PGQ_ERR_INVALID_ARG, "path or child buffer too small for the lists (see *paths_used, *child_used)");
-		}
-		return rc;
+		return list_bulk_body(out, k, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o).run(); }, paths_used, child_used);
 	});
 }
 
 int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t *out_count,
                    uint64_t *out_valid) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-		if (n < 0 || (n > 0 && (!out_count || !out_valid))) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-		PGQ_TRY(walk_check_bounds(min_hops, max_hops, nullptr));
-		return n == 0 ? kNoRows : PGQ_OK;
-	};
+	auto check = [&] { return count_chunk_check(csr, V, n, out_count, out_valid, [&] { return walk_check_bounds(min_hops, max_hops, nullptr); }); };
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		PGQ_TRY(asp_stage_rows(ws, V, n, src, dst));
-		PGQ_TRY(ws->out_len.reserve((size_t)n * 8));
-		WalkOut out;
-		out.d_count = ws->out_len.as<int64_t>();
-		PGQ_TRY(WalkCall(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), min_hops, max_hops, out).run());
-		std::vector<int64_t> cnt((size_t)n);
-		PGQ_TRY(staged_download(cnt.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
-		mask_fill_valid(out_valid, n);
-		for (int64_t i = 0; i < n; i++) {
-			out_count[i] = cnt[i];
-			if (cnt[i] < 0) mask_set_invalid(out_valid, i);
-		}
-		return PGQ_OK;
+		auto run = [&](ListOut &o, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o).run(); };
+		return count_chunk_body(ws, V, n, src, dst, run, out_count, out_valid);
 	});
 }
 
@@ -692,53 +481,11 @@ int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pg
                          uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
                          uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
-		if (n < 0 || (n > 0 && (!out_first || !out_npaths || !out_valid)) || !out_path_offset || !out_path_length || !out_path_total || !out_child || !out_child_len)
-			return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-		PGQ_TRY(walk_check_bounds(min_hops, max_hops, &k));
-		*out_path_offset = *out_path_length = nullptr;
-		*out_child = nullptr;
-		*out_path_total = *out_child_len = 0;
-		return n == 0 ? kNoRows : PGQ_OK;
-	};
+	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len };
+	auto check = [&] { return list_chunk_check(csr, V, n, o, [&] { return walk_check_bounds(min_hops, max_hops, &k); }); };
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		PGQ_TRY(asp_stage_rows(ws, V, n, src, dst));
-		for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve((size_t)n * 8 * 2));
-		WalkOut out;
-		out.lists = true;
-		out.k = std::min<int64_t>(k, 1LL << 31);
-		out.d_len = ws->out_len.as<int64_t>(), out.d_count = out.d_len + n, out.d_first = ws->out_off.as<int64_t>(), out.d_np = out.d_first + n;
-		PGQ_TRY(WalkCall(csr, ws, n, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>(), min_hops, max_hops, out).run());
-		std::vector<int64_t> len(n), first_np((size_t)2 * n);
-		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
-		PGQ_TRY(staged_download(first_np.data(), ws->out_off.p, (size_t)n * 8 * 2, ws->stream));
-		// one arena block, filled whole before the caller's arrays are touched: the child payload, then the inner entries' offsets and lengths
-		const size_t P = (size_t)out.paths_used, C = (size_t)out.child_used;
-		std::vector<int64_t> &arena = thread_child_arena();
-		arena.resize(C + 2 * P);
-		if (C > 0) PGQ_TRY(staged_download(arena.data(), ws->child.p, C * 8, ws->stream));
-		if (P > 0) {
-			PGQ_TRY(staged_download(arena.data() + C, ws->asp_paths.p, P * 8, ws->stream));
-			PGQ_TRY(staged_download(arena.data() + C + P, ws->asp_paths.as<int64_t>() + P, P * 8, ws->stream));
-		}
-		mask_fill_valid(out_valid, n);
-		for (int64_t i = 0; i < n; i++) {
-			if (len[i] < 0) {
-				mask_set_invalid(out_valid, i);
-				out_first[i] = 0;
-				out_npaths[i] = 0;
-			} else {
-				out_first[i] = (uint64_t)first_np[i];
-				out_npaths[i] = (uint64_t)first_np[(size_t)n + i];
-			}
-		}
-		*out_child = arena.data();
-		*out_child_len = (uint64_t)C;
-		*out_path_offset = reinterpret_cast<const uint64_t *>(arena.data() + C);
-		*out_path_length = reinterpret_cast<const uint64_t *>(arena.data() + C + P);
-		*out_path_total = (uint64_t)P;
-		return PGQ_OK;
+		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo).run(); };
+		return list_chunk_body(ws, V, n, src, dst, k, run, o);
 	});
 }
 

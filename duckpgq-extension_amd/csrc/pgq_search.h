@@ -322,10 +322,10 @@ struct Workspace {
 	// resets what it set, hop_last_V says for which V that holds)
 	DevBuf hop_row, hop_mask, hop_ent, hop_last;
 	int64_t hop_last_V = -1;
-	// shortestpath_count / all_shortestpaths (pgq_all_shortest.hip): the rows' results in row order until the call has succeeded,
-	// and the chunk form's inner list entries.  The levels live in tight_h and the tight_* frontier buffers (same invariants),
-	// the staged lists in tight_stage; sigma is block-cache memory of the call
-	// (walk_count / k_shortest_walks, pgq_k_walks.hip, use asp_rows, asp_paths, tight_stage and tight_cnt, and nothing else of the tight_* state)
+	// The nested-list calls (ListCall, pgq_path_lists.h): the rows' results in row order until the call has succeeded, and the chunk
+	// form's inner list entries; the staged lists lie in tight_stage.  shortestpath_count / all_shortestpaths (pgq_all_shortest.hip)
+	// keep their levels in tight_h and the tight_* frontier buffers (same invariants), sigma is block-cache memory of the call;
+	// walk_count / k_shortest_walks (pgq_k_walks.hip) use tight_cnt and nothing else of the tight_* state
 	DevBuf asp_rows, asp_paths;
 	~Workspace();
 };

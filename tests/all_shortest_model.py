@@ -26,7 +26,9 @@ MAX_PATHS_ALL = (1 << 31) - 1
 # first_slot    the edge of the taken in-slot is the parent's FIRST slot into x_t, not its m-th
 # no_bound      max_hops ignored
 # paths_plus_1  one path more than max_paths
-MUTANTS = ("wrap", "any_level", "slot_order", "collapse", "first_slot", "no_bound", "paths_plus_1")
+# m_mod_64      which of the parent's slots into x_t the taken in-slot is, counted modulo 64
+# slot_first_64 the parent's m-th slot into x_t searched in the first 64 entries of its out-list only
+MUTANTS = ("wrap", "any_level", "slot_order", "collapse", "first_slot", "no_bound", "paths_plus_1", "m_mod_64", "slot_first_64")
 
 
 def graph(V, es, ed, eid_base=1000):
@@ -100,6 +102,15 @@ def sigmas(V, rin, L, src, mutant=None):
     return sigma
 
 
+def mth_slot(off, adj, u, x, m, mutant=None):
+    """The m-th slot of u's out-list into x, as an implementation finds it that walks the out-list; None when it finds none."""
+    if mutant == "m_mod_64":
+        m %= 64
+    end = min(off[u + 1], off[u] + 64) if mutant == "slot_first_64" else off[u + 1]
+    into = [s for s in range(off[u], end) if adj[s] == x]
+    return into[m] if m < len(into) else None
+
+
 def unrank(V, off, adj, eid, rin, L, sigma, src, dst, r, mutant=None):
     """Path number r of the row, or ("lost",) when a (mutant) walk finds no slot or does not come home."""
     x = dst
@@ -110,14 +121,18 @@ def unrank(V, off, adj, eid, rin, L, sigma, src, dst, r, mutant=None):
         taken = None
         for u, slot, m in _parents(rin, L, x, mutant):
             if r < sigma[u]:
-                taken = (u, slot)
+                taken = (u, slot, m)
                 break
             r -= sigma[u]
         if taken is None:
             return ("lost",)
-        u, slot = taken
+        u, slot, m = taken
         if mutant == "first_slot":
             slot = next(s for s in range(off[u], off[u + 1]) if adj[s] == x)
+        if mutant in ("m_mod_64", "slot_first_64"):
+            slot = mth_slot(off, adj, u, x, m, mutant)
+            if slot is None:
+                return ("lost",)
         rev += [int(eid[slot]), int(u)]
         x = u
     return rev[::-1] if x == src else ("lost",)
@@ -254,6 +269,18 @@ def parallel_edges():
     return _fx(4, es, ed, [(0, 3), (0, 2), (1, 3), (3, 0)])
 
 
+def parallel_run(P):
+    """s = 0, middle vertices u0 = 1 < u = 2, destination x = 3, decoy y = 4.  One slot u0 -> x; P parallel slots u -> x, each behind a
+    decoy slot u -> y in u's out-list: the k-th slot into x stands at out-position 2 k + 1 and at in-position 1 + k of x's in-list,
+    behind u0's.  Rows (s, x): 1 + P paths, and (u, x): P.  For P >= 64 the run of u's in-slots crosses position 64 of the in-list;
+    from P = 33 on the m-th slot into x lies behind the out-list's first 64 entries, from P = 65 on m itself reaches 64."""
+    es, ed = [0, 0, 1], [1, 2, 3]
+    for _ in range(P):
+        es += [2, 2]
+        ed += [4, 3]
+    return _fx(5, es, ed, [(0, 3), (2, 3)])
+
+
 def many_sources(k, V=150, seed=9):
     """k distinct sources with two destinations each over one graph: the lane batches of 64 walk vertices earlier ones touched."""
     rng = np.random.default_rng(seed)
@@ -283,4 +310,6 @@ def gpu_fixtures():
         fx["diamonds_%d" % k] = (diamond_chain(k), (2 * k - 1, INT64_MAX), (3,))
     for k in (63, 64, 65, 129):
         fx["sources_%d" % k] = (many_sources(k), (3, INT64_MAX), (2,))
+    for P in (63, 64, 65, 129):
+        fx["parallel_run_%d" % P] = (parallel_run(P), (2, INT64_MAX), (1, MAX_PATHS_ALL))
     return fx

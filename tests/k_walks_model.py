@@ -33,7 +33,10 @@ MAX_HOPS = 64  # PGQ_WALK_MAX_HOPS
 # collapse            parallel edges counted once
 # slot_order          candidates ordered by (which of the parent's parallel slots, parent) instead of (parent, slot)
 # k_plus_1            one walk more than k
-MUTANTS = ("wrap", "bfs_only", "lower_ignored", "empty_walk_always", "trivial_src_eq_dst", "length_order", "collapse", "slot_order", "k_plus_1")
+# m_mod_64            which of the parent's slots into x_i the taken in-slot is, counted modulo 64
+# slot_first_64       the parent's m-th slot into x_i searched in the first 64 entries of its out-list only
+MUTANTS = ("wrap", "bfs_only", "lower_ignored", "empty_walk_always", "trivial_src_eq_dst", "length_order", "collapse", "slot_order", "k_plus_1",
+           "m_mod_64", "slot_first_64")
 
 
 def _add(a, b, mutant):
@@ -87,15 +90,19 @@ def unrank(off, adj, eid, rin, Ws, src, dst, t, r, mutant=None):
     rev = [int(x)]
     for i in range(t, 0, -1):
         taken = None
-        for u, slot, _ in _in_slots(rin, x, mutant):
+        for u, slot, m in _in_slots(rin, x, mutant):
             w = Ws[i - 1].get(u, 0)
             if r < w:
-                taken = (u, slot)
+                taken = (u, slot, m)
                 break
             r -= max(w, 0)
         if taken is None:
             return ("lost",)
-        u, slot = taken
+        u, slot, m = taken
+        if mutant in ("m_mod_64", "slot_first_64"):
+            slot = A.mth_slot(off, adj, u, x, m, mutant)
+            if slot is None:
+                return ("lost",)
         rev += [int(eid[slot]), int(u)]
         x = u
     return rev[::-1] if x == src else ("lost",)
@@ -226,4 +233,6 @@ def gpu_fixtures():
         fx["in_list_%d" % deg] = (in_list_gadget(deg), ((0, 3, (1, K_ALL)), (3, 7, (1, 200)), (4, 4, (K_ALL,))))
     for n in (63, 64, 65, 128, 129):
         fx["sources_%d" % n] = (A.many_sources(n), ((1, 3, (2,)),))
+    for P in (63, 64, 65, 129):
+        fx["parallel_run_%d" % P] = (A.parallel_run(P), ((2, 2, (1, K_ALL)), (1, 2, (1, K_ALL))))
     return fx

@@ -33,6 +33,18 @@ def test_model_against_brute_force():
     assert graphs == 300 and multi > 1000 and deep > 1000, (graphs, rows, multi, deep)
 
 
+def test_model_against_brute_force_on_a_run_of_parallel_slots():
+    """parallel_run(65): the m-th of 65 parallel slots, m up to 64, at in-position 1 + m and out-position 2 m + 1."""
+    V, off, adj, eid, rs, rd = M.parallel_run(65)
+    counts, hops, lists = M.solve(V, off, adj, eid, rs, rd, INT64_MAX, M.MAX_PATHS_ALL)
+    assert counts == [66, 65] and hops == [2, 1]
+    for i, (s, d) in enumerate(zip(rs.tolist(), rd.tolist())):
+        assert lists[i] == M.brute_force(V, off, adj, eid, s, d), (s, d)
+    rin = M.in_lists(V, off, adj)
+    assert [u for u, _ in rin[3]] == [1] + [2] * 65 and [slot - off[2] for _, slot in rin[3][1:]] == [2 * k + 1 for k in range(65)]
+    assert len({p[-2] for p in lists[0]}) == 66  # distinct edge ids: every slot is told from the others
+
+
 @pytest.fixture(scope="module")
 def random_rows():
     V, off, adj, eid, rs, rd = fx = M.random_fixture()
@@ -126,6 +138,10 @@ def test_the_gpu_fixtures_catch_the_mutants(mutant, expected):
         assert "random" in names
     if mutant == "paths_plus_1":
         assert ("parallel", INT64_MAX, 9) in caught and ("parallel", INT64_MAX, 10) not in caught
+    if mutant in ("m_mod_64", "slot_first_64"):  # three parallel slots do not show them, a run of 65 does
+        assert "parallel" not in names and "parallel_run_65" in names
+    if mutant == "m_mod_64":
+        assert all(name.startswith("parallel_run") for name in names)
 
 
 def test_every_layer_names_the_functions():

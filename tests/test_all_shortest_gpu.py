@@ -175,6 +175,16 @@ def test_parallel_edges_and_per_row_limits():
     assert len({tuple(q) for q in nine}) == 9 and len({e for q in nine for e in (q[1], q[3])}) == 6
 
 
+@pytest.mark.parametrize("P", [63, 64, 65, 129])
+def test_a_run_of_parallel_slots(P):
+    """The m-th of P parallel slots, m up to P - 1: the run crosses position 64 of the in-list, its edges lie at other positions
+    of the parent's out-list, past its first 64 entries."""
+    name = "parallel_run_%d" % P
+    check_all_forms(name)
+    counts, hops, lists = want_of(name, INT64_MAX, ALL)
+    assert counts == [1 + P, P] and hops == [2, 1] and len({q[-2] for q in lists[0]}) == 1 + P
+
+
 # ---- 4. batch boundaries: later batches walk what earlier ones touched; the next call sees a clean workspace ------------------
 @pytest.mark.parametrize("k", [63, 64, 65, 129])
 def test_batch_boundaries(k):

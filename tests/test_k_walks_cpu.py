@@ -41,6 +41,18 @@ def test_model_against_brute_force():
     assert graphs == 300 and multi > 1000 and mixed > 1000 and closed > 300, (graphs, multi, mixed, closed)
 
 
+def test_model_against_brute_force_on_a_run_of_parallel_slots():
+    """parallel_run(65): the m-th of 65 parallel slots, m up to 64, at in-position 1 + m and out-position 2 m + 1."""
+    V, off, adj, eid, rs, rd = A.parallel_run(65)
+    brute = {s: M.brute_force(V, off, adj, eid, s, 2) for s in set(rs.tolist())}
+    for lo, K in ((2, 2), (1, 2)):
+        counts, hops, lists, counts_k = M.solve(V, off, adj, eid, rs, rd, lo, K, M.K_ALL)
+        for i, (s, d) in enumerate(zip(rs.tolist(), rd.tolist())):
+            want = [p for p in brute[s][d] if len(p) // 2 >= lo]
+            assert counts[i] == counts_k[i] == len(want) and lists[i] == (want or None), (lo, K, s, d)
+    assert counts == [66, 65] and hops == [2, 1]
+
+
 def test_k_cuts_the_list_and_the_list_forms_count():
     V, off, adj, eid, rs, rd = A.tiny_multigraph(3)
     full = M.solve(V, off, adj, eid, rs, rd, 1, 4, M.K_ALL)
@@ -168,6 +180,10 @@ def test_the_gpu_fixtures_catch_the_mutants(mutant, expected):
         assert "random" in names
     if mutant == "k_plus_1":
         assert ("parallel", 0, 3, 9) in caught and ("parallel", 0, 3, 10) not in caught
+    if mutant in ("m_mod_64", "slot_first_64"):  # three parallel slots do not show them, a run of 65 does
+        assert "parallel" not in names and "parallel_run_65" in names
+    if mutant == "m_mod_64":
+        assert all(name.startswith("parallel_run") for name in names)
 
 
 def test_every_layer_names_the_functions():

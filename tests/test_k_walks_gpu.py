@@ -166,6 +166,17 @@ def test_parallel_edges_and_per_row_limits():
     assert len({tuple(q) for q in nine}) == 9 and len({e for q in nine for e in (q[1], q[3])}) == 6
 
 
+@pytest.mark.parametrize("P", [63, 64, 65, 129])
+def test_a_run_of_parallel_slots(P):
+    """The m-th of P parallel slots, m up to P - 1: the run crosses position 64 of the in-list, its edges lie at other positions
+    of the parent's out-list, past its first 64 entries."""
+    name = "parallel_run_%d" % P
+    check_all_forms(name)
+    counts, hops, lists, _ = want_of(name, 2, 2, ALL)
+    assert counts == [1 + P, 0] and hops == [2, -1] and len({q[-2] for q in lists[0]}) == 1 + P
+    assert want_of(name, 1, 2, ALL)[0] == [1 + P, P]
+
+
 # ---- 5. cycles: a ring of 5, a self-loop; rows without a lane ---------------------------------------------------------------------------
 def test_ring_and_self_loop():
     check_all_forms("ring5")
