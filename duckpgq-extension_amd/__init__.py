@@ -9,4 +9,4 @@ every search call fails loudly if the HIP library or a GPU is missing.
 """
 from .binding import (DeviceCSR, PgqError, PgqState, build_native, copy_bandwidth_gbps, get_stats, kclass_names,  # noqa: F401
                       lib_paths, load_hip, load_udf, reset_stats, set_option, get_option, get_default_option, init_devices,
-                      live_device_blocks)
+                      live_device_blocks, mode_steps, MODE_NONE, MODE_WALK, MODE_SIMPLE, MODE_TRAIL, MODE_ACYCLIC)

@@ -132,6 +132,17 @@ def load_hip():
     L.pgq_k_shortest_walks_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.pgq_walk_count_mode.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_void_p]
+    L.pgq_walk_count_mode_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                                  C.c_void_p]
+    L.pgq_k_shortest_walks_mode.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_k_shortest_walks_mode_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.pgq_debug_mode_steps.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -196,6 +207,11 @@ def load_udf():
     L.pgq_udf_k_shortest_walks.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_udf_walk_count_mode.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                          C.c_void_p, C.c_void_p]
+    L.pgq_udf_k_shortest_walks_mode.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -304,6 +320,18 @@ def reset_stats():
 def live_device_blocks():
     """Device blocks handed out by the library's block cache and not freed yet (pgq_debug_live_device_blocks)."""
     return load_hip().pgq_debug_live_device_blocks()
+
+
+# the path modes of k_shortest_walks / walk_count, numbered as the reference's PGQPathMode (include/pgq_hip.h: PGQ_MODE_*)
+MODE_NONE, MODE_WALK, MODE_SIMPLE, MODE_TRAIL, MODE_ACYCLIC = range(5)
+
+
+def mode_steps():
+    """(total, row_max): the steps this thread's last path-mode call took over all rows and both passes, and the most one row took
+    in one pass (pgq_debug_mode_steps); a step is one 64-entry in-list chunk examined or one descent."""
+    total, row_max = C.c_int64(0), C.c_int64(0)
+    _check(load_hip().pgq_debug_mode_steps(C.byref(total), C.byref(row_max)))
+    return total.value, row_max.value
 
 
 def copy_bandwidth_gbps(nbytes=1 << 30, iters=10):
@@ -537,24 +565,36 @@ class DeviceCSR:
 
         return _all_shortestpaths(call, n, raw)
 
-    def walk_count(self, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+    def walk_count(self, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, limit=None,
+                   path_mode=None):
         """The number of walks of min_hops..max_hops edges per row (saturated at 2^63 - 1): src == dst counts the empty walk when
-        min_hops == 0 and every closed walk; 0 when there is none, NULL for a NULL endpoint (include/pgq_hip.h)."""
+        min_hops == 0 and every closed walk; 0 when there is none, NULL for a NULL endpoint (include/pgq_hip.h).
+        With limit and path_mode (MODE_*): min(the walks the mode admits, limit) — pgq_walk_count_mode; both or neither."""
+        if (limit is None) != (path_mode is None):
+            raise PgqError("walk_count: limit and path_mode go together")
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
         out = np.zeros(n, dtype=np.int64)
         ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
-        _check(self.L.pgq_walk_count(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), _p(out), _p(ov)))
+        if path_mode is None:
+            _check(self.L.pgq_walk_count(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), _p(out), _p(ov)))
+        else:
+            _check(self.L.pgq_walk_count_mode(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), int(limit), int(path_mode), _p(out),
+                                              _p(ov)))
         return out, unpack_validity(ov, n)
 
     def k_shortest_walks(self, src, dst, min_hops, max_hops, k, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None,
-                         raw=False):
+                         raw=False, path_mode=None):
         """Per row the list of its first k walks of min_hops..max_hops edges, shorter walks first, each [x_0, e_1, x_1, ..., x_t],
-        in the contract's order; None for rows without a walk and NULL rows.  raw=True: see _all_shortestpaths."""
+        in the contract's order; None for rows without a walk and NULL rows.  raw=True: see _all_shortestpaths.
+        path_mode (MODE_*): the first k walks the mode admits — pgq_k_shortest_walks_mode."""
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
 
         def call(*outs):
+            if path_mode is not None:
+                return _check(self.L.pgq_k_shortest_walks_mode(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), int(k), int(path_mode),
+                                                               *outs))
             _check(self.L.pgq_k_shortest_walks(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), int(k), *outs))
 
         return _all_shortestpaths(call, n, raw)
@@ -760,6 +800,21 @@ class DeviceCSR:
                                                      C.byref(paths), C.byref(used))
         return rc, paths.value, used.value
 
+    def walk_count_mode_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, limit, path_mode, d_out_count):
+        _check(self.L.pgq_walk_count_mode_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                      int(limit), int(path_mode), C.c_void_p(d_out_count)))
+
+    def k_shortest_walks_mode_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, k, path_mode, d_out_len, d_out_count, d_out_first,
+                                       d_out_npaths, d_path_offset, d_path_hops, path_cap, d_child, child_cap):
+        """(status, walks needed, elements needed): k_shortest_walks_bulk_ptr under a path mode."""
+        paths, used = C.c_int64(0), C.c_int64(0)
+        rc = self.L.pgq_k_shortest_walks_mode_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                          int(k), int(path_mode), C.c_void_p(d_out_len), C.c_void_p(d_out_count),
+                                                          C.c_void_p(d_out_first), C.c_void_p(d_out_npaths),
+                                                          C.c_void_p(d_path_offset), C.c_void_p(d_path_hops), path_cap,
+                                                          C.c_void_p(d_child), child_cap, C.byref(paths), C.byref(used))
+        return rc, paths.value, used.value
+
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                                   int(max_hops), C.c_void_p(d_out), C.c_void_p(d_ok)))
@@ -908,25 +963,33 @@ class PgqState:
 
         return _all_shortestpaths(call, n, raw)
 
-    def walk_count(self, csr_id, V, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+    def walk_count(self, csr_id, V, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None,
+                   limit=None, path_mode=None):
+        if (limit is None) != (path_mode is None):
+            raise PgqError("walk_count: limit and path_mode go together")
         n = len(src_sel) if src_sel is not None else len(src)
         out = np.zeros(n, dtype=np.int64)
         lo, hi = int(min_hops), int(max_hops)
 
         def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            if path_mode is not None:
+                return self.U.pgq_udf_walk_count_mode(s, csr_id, V, n, sv, dv, lo, hi, int(limit), int(path_mode), out_p, ov_p)
             return self.U.pgq_udf_walk_count(s, csr_id, V, n, sv, dv, lo, hi, out_p, ov_p)
 
         ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
         return out, ok
 
     def k_shortest_walks(self, csr_id, V, src, dst, min_hops, max_hops, k, src_valid=None, dst_valid=None, src_sel=None,
-                         dst_sel=None, raw=False):
+                         dst_sel=None, raw=False, path_mode=None):
         keep = []
         sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
         dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
         n = len(src_sel) if src_sel is not None else len(src)
 
         def call(*outs):
+            if path_mode is not None:
+                return self._ck(self.U.pgq_udf_k_shortest_walks_mode(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), int(k),
+                                                                     int(path_mode), *outs))
             self._ck(self.U.pgq_udf_k_shortest_walks(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), int(k), *outs))
 
         return _all_shortestpaths(call, n, raw)

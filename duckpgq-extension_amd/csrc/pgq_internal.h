@@ -191,6 +191,8 @@ struct Options {
 	int route_timing_rows = 65536; // ... calls of at least this many rows
 	double route_try_factor = 4.0; // ... the lane batches are tried once when the source-centric route took this many times their modelled time
 	int ball_sort = 1;          // rows with repeated sources that are NOT grouped are sorted by source first (0: such calls take the older routes)
+	int mode_step_cap = 1 << 24; // k_shortest_walks_mode / walk_count_mode: steps (64-entry in-list trips and descents) one row's search may take per
+	                             // pass before the call fails with PGQ_ERR_UNSUPPORTED.  A safety limit, not a tuned number
 	double ball_bias = 1.0;     // the ball runs while ball_bias x its estimated bytes <= the cheaper of the pre-pass and the lane batches
 };
 Options &options();

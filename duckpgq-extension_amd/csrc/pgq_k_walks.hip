@@ -53,8 +53,11 @@
 // The call owns its tables, masks and queues (block cache); it does not touch ws->tight_h / tight_mask / tight_q / tight_V, so
 // PathBatches and AspCall find them as they left them.  Lists are staged in ws->tight_stage, rows in ws->asp_rows.
 // Kernel-class time: the rounds are K_PUSH, plan / unranking / gather K_RECON.
-// Not built: _multi forms, path modes TRAIL / ACYCLIC / SIMPLE, SHORTEST k GROUP, splitting long in-lists over several wavefronts (a
-// list is walked by the one wavefront that meets it), any change to how the binder's iterativelength filter is emitted.
+// The path modes TRAIL / ACYCLIC / SIMPLE (pgq_k_shortest_walks_mode, pgq_walk_count_mode) run these rounds with every table kept
+// and k_walk_after's stop by distance, then search each row over the tables: pgq_path_modes.h, included below, has the contract.
+// Not built: _multi forms, SHORTEST k GROUP, splitting long in-lists over several wavefronts (a list is walked by the one wavefront
+// that meets it), any change to how the binder's iterativelength filter is emitted; under a mode: an unbounded upper, an unlimited
+// count, a smarter prune than W, several wavefronts per row.
 
 namespace pgq {
 
@@ -63,6 +66,8 @@ struct WalkCounters {
 	u32 pending; // rows of the batch short of k walks
 	u32 error;   // unranking: no length / parent (2), no slot (4), not at the source (8)
 	u64 edges;   // adjacency entries the rounds walked
+	u64 steps;   // path modes: the steps of the batch's searches, both passes ...
+	u64 row_max; // ... and the most a row took in one pass
 };
 struct WalkRound {
 	const int64_t *W;
@@ -81,6 +86,8 @@ __global__ void k_walk_init(const int32_t *__restrict__ usrc, int64_t U, int64_t
 		tc->pending = 0;
 		tc->error = 0;
 		tc->edges = 0;
+		tc->steps = 0;
+		tc->row_max = 0;
 	}
 	if (l >= LC || g >= U) return;
 	const int v = usrc[g];
@@ -151,7 +158,10 @@ __global__ __launch_bounds__(256) void k_walk_pull(const int64_t *__restrict__ r
 
 // Round t is over: the rows' counts (a row that has k_stop walks adds no more), the rows still short of k_stop; m_zero != null
 // (walk_count's ping-pong): round t-1's mask words back to zero over its queue.
-__global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx,
+// by_distance (the path modes): a mode may reject any walk longer than d = dist(src, dst), the first t >= 0 with W_t[dst] > 0, and
+// rejects none of length d.  r_len notes d; a row is closed (r_count = k_stop) when min_hops <= d and W_d[dst] >= k_stop, and every
+// other row stays open to the last round.  The search's counting pass overwrites both arrays.
+__global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, bool by_distance, int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx,
                              const int32_t *__restrict__ sdst, u32 base_lane, WalkRound cur, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count,
                              const int32_t *__restrict__ qprev, u64 *__restrict__ m_zero, int par_prev, WalkCounters *__restrict__ tc) {
 	const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,7 +171,15 @@ __global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, int64_t lo
 	if (i < hi) {
 		const u32 row = sidx[i];
 		int64_t cnt = r_count[row];
-		if (t >= min_hops && cnt < k_stop) {
+		if (by_distance) {
+			if (r_len[row] < 0) {
+				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
+				if (w > 0) {
+					r_len[row] = t;
+					if (t >= min_hops && w >= k_stop) r_count[row] = cnt = k_stop;
+				}
+			}
+		} else if (t >= min_hops && cnt < k_stop) {
 			const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
 			if (w > 0) {
 				if (r_len[row] < 0) r_len[row] = t;
@@ -299,11 +317,29 @@ __global__ __launch_bounds__(64) void k_walk_gather(int64_t lo_trivial, int64_t 
 	}
 }
 
+} // namespace pgq
+
+#include "pgq_path_modes.h" // k_mode_search: the depth-first search of TRAIL / ACYCLIC / SIMPLE over the rounds' tables
+
+namespace pgq {
+
+// the steps of this thread's last path-mode call (pgq_debug_mode_steps)
+struct ModeSteps {
+	int64_t total = 0, row_max = 0;
+};
+static ModeSteps &mode_steps() {
+	static thread_local ModeSteps s;
+	return s;
+}
+
 // The walk rounds of the lane batches on ListCall's skeleton (pgq_path_lists.h): its run, emit and layout.
 class WalkCall : ListCall {
 public:
-	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, ListOut &out)
-	    : ListCall(c, ws, n, d_src, d_dst, out, "k_shortest_walks", "walks"), min_hops(min_hops), max_hops(max_hops), temps(ws->stream) {}
+	// mode: 0 for the walks themselves, or PGQ_MODE_SIMPLE / _TRAIL / _ACYCLIC: then out.limit is k (lists) or the count's limit,
+	// every round's table is kept, the rounds stop by distance and the rows are searched (pgq_path_modes.h)
+	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, ListOut &out, int mode = 0)
+	    : ListCall(c, ws, n, d_src, d_dst, out, mode ? "k_shortest_walks_mode" : "k_shortest_walks", "walks"), min_hops(min_hops), max_hops(max_hops), mode(mode),
+	      keep_rounds(out.lists || mode != 0), step_cap(std::max(options().mode_step_cap, 0)), temps(ws->stream) {}
 
 	int run() {
 		return ListCall::run(
@@ -319,6 +355,10 @@ public:
 
 private:
 	const int64_t min_hops, max_hops;
+	const int mode;
+	const bool keep_rounds; // a table per round (the unranking, the search) instead of walk_count's two
+	const int64_t step_cap; // path modes: steps a row's search may take per pass
+	uint64_t steps_seen = 0; // ... the batch's steps already booked
 	DevTemps temps; // the rounds' tables, masks and queues: block-cache memory for the call
 	WalkCounters *tc = nullptr;
 	std::vector<int64_t *> W; // lists: one per round; counts: two
@@ -327,7 +367,7 @@ private:
 	WalkRound *d_tabs = nullptr;
 	int32_t *q[2] = { nullptr, nullptr };
 
-	size_t slot_of(int64_t t) const { return out.lists ? (size_t)t : (size_t)(t & 1); }
+	size_t slot_of(int64_t t) const { return keep_rounds ? (size_t)t : (size_t)(t & 1); }
 	// round t's table and (zeroed) mask
 	int ensure_round(int64_t t) {
 		while (W.size() <= slot_of(t)) {
@@ -345,10 +385,8 @@ private:
 	int prepare() {
 		PGQ_TRY(ws->tight_cnt.reserve(std::max(sizeof(WalkCounters), sizeof(TightCounters))));
 		tc = ws->tight_cnt.as<WalkCounters>();
-		if (out.lists) {
-			PGQ_TRY(ensure_edge_ids(c));
-			PGQ_TRY(temps.alloc(&d_tabs, (size_t)PGQ_WALK_MAX_HOPS + 1));
-		}
+		if (out.lists || mode == PGQ_MODE_TRAIL) PGQ_TRY(ensure_edge_ids(c));
+		if (keep_rounds) PGQ_TRY(temps.alloc(&d_tabs, (size_t)PGQ_WALK_MAX_HOPS + 1));
 		for (int32_t *&b : q) PGQ_TRY(temps.alloc(&b, Vn));
 		return PGQ_OK;
 	}
@@ -357,7 +395,7 @@ private:
 	int batch(int64_t lo, int64_t hi, int64_t base, u32 U) {
 		const int64_t m = hi - lo;
 		const unsigned cus = (unsigned)device_cus();
-		const int64_t k_stop = out.lists ? out.limit : kAspMax;
+		const int64_t k_stop = keep_rounds ? out.limit : kAspMax;
 		const u32 *skey = ws->skey.as<u32>(), *sidx = ws->sidx.as<u32>();
 		const int32_t *sdst = ws->sdst.as<int32_t>();
 		WalkCounters h {};
@@ -369,14 +407,14 @@ private:
 			KernelTimer kt(st, K_PUSH);
 			hipLaunchKernelGGL(k_walk_init, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base, W[0], M[0], q[0], tc);
 			if (m > 0) hipLaunchKernelGGL(k_walk_rows, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, sidx, r_len, r_count);
-			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, min_hops, k_stop, lo, hi, skey, sidx, sdst, (u32)base,
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, min_hops, k_stop, mode != 0, lo, hi, skey, sidx, sdst, (u32)base,
 			                   round_of(0), r_len, r_count, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
 			kt.stop();
 		}
 		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 		int par = 0;
 		int rounds = 0;
-		for (int64_t t = 1; t <= max_hops && nq > 0 && m > 0 && !(out.lists && h.pending == 0); t++) {
+		for (int64_t t = 1; t <= max_hops && nq > 0 && m > 0 && !(keep_rounds && h.pending == 0); t++) {
 			PGQ_TRY(ensure_round(t));
 			KernelTimer kt(st, K_PUSH);
 			const WalkRound prev = round_of(t - 1), cur = round_of(t);
@@ -385,8 +423,8 @@ private:
 			                   q[par ^ 1], tc, par);
 			// (the new queue's fill is not known here: the grid is sized for a queue of any size, its wavefronts stride)
 			hipLaunchKernelGGL(k_walk_pull, dim3(cus * 8), dim3(256), 0, st, c->roff, c->radj, prev.W, prev.M, W[slot_of(t)], cur.M, q[par ^ 1], tc, par ^ 1);
-			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, lo, hi, skey, sidx, sdst, (u32)base,
-			                   cur, r_len, r_count, (const int32_t *)q[par], out.lists ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, mode != 0, lo, hi, skey, sidx, sdst, (u32)base,
+			                   cur, r_len, r_count, (const int32_t *)q[par], keep_rounds ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
 			kt.stop();
 			PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 			S.levels++;
@@ -396,11 +434,12 @@ private:
 		}
 		S.edges_scanned += (int64_t)h.edges;
 		S.algo_bytes[K_PUSH] += (double)h.edges * (4.0 + 8.0 + 512.0);
-		if (!out.lists) return PGQ_OK; // (before any staging)
+		if (!keep_rounds) return PGQ_OK; // (before any staging)
 		// walks and elements per row; where the batch's walks and staged blocks go
 		h_tabs.assign((size_t)PGQ_WALK_MAX_HOPS + 1, WalkRound { nullptr, nullptr });
 		for (int t = 0; t <= rounds; t++) h_tabs[t] = round_of(t);
 		PGQ_HIP_TRY(hipMemcpyAsync(d_tabs, h_tabs.data(), h_tabs.size() * sizeof(WalkRound), hipMemcpyHostToDevice, st));
+		if (mode) return search(lo, m, (u32)base, rounds);
 		PGQ_TRY(emit(
 		    m,
 		    [&](int64_t *cntp, int64_t *cnte) {
@@ -415,6 +454,42 @@ private:
 		PGQ_TRY(stage.read_back(&h, tc, sizeof(h))); // (also: the next batch's memsets and table upload come behind this batch's kernels)
 		return unrank_status(h.error);
 	}
+
+	// Path modes: the batch's rows searched over the tables of rounds 0..rounds, a wavefront per row.  The counting pass is emit's
+	// plan step; the count form ends behind it.
+	template <bool EMIT> void launch_search(int64_t lo, int64_t m, u32 base, int rounds, int64_t *cntp, int64_t *cnte, const int64_t *ploc, const int64_t *eloc, int64_t at) {
+		hipLaunchKernelGGL(k_mode_search<EMIT>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, m, ws->skey.as<u32>(), ws->sidx.as<u32>(),
+		                   ws->sdst.as<int32_t>(), base, ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, mode, min_hops, rounds, out.limit,
+		                   step_cap, r_len, r_count, r_np, r_el, cntp, cnte, ploc, eloc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+	}
+	// what a pass left in the batch's counters: its steps booked, the step cap and the search's own errors reported
+	int search_status() {
+		WalkCounters h {};
+		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
+		ModeSteps &ms = mode_steps();
+		ms.total += (int64_t)(h.steps - steps_seen);
+		ms.row_max = std::max(ms.row_max, (int64_t)h.row_max);
+		steps_seen = h.steps;
+		if (h.error & kModeOverCap)
+			return fail(PGQ_ERR_UNSUPPORTED, name + ": a row's search took more than mode_step_cap = " + std::to_string(step_cap) +
+			                                     " steps in one pass (finding a simple path of an exact length is NP-hard; raise the option or lower the bounds)");
+		return unrank_status(h.error);
+	}
+	int search(int64_t lo, int64_t m, u32 base, int rounds) {
+		steps_seen = 0; // (k_walk_init zeroed the batch's counters)
+		if (m == 0) return PGQ_OK;
+		if (!out.lists) {
+			KernelTimer kt(st, K_RECON);
+			launch_search<false>(lo, m, base, rounds, nullptr, nullptr, nullptr, nullptr, 0);
+			kt.stop();
+			return search_status();
+		}
+		PGQ_TRY(emit(
+		    m, [&](int64_t *cntp, int64_t *cnte) { launch_search<false>(lo, m, base, rounds, cntp, cnte, nullptr, nullptr, 0); },
+		    [&](int64_t, const int64_t *ploc, const int64_t *eloc, int64_t at) { launch_search<true>(lo, m, base, rounds, nullptr, nullptr, ploc, eloc, at); },
+		    [&] { return search_status(); }));
+		return search_status();
+	}
 };
 
 } // namespace pgq
@@ -423,10 +498,10 @@ using namespace pgq;
 
 extern "C" {
 
-static int walk_check_bounds(int64_t min_hops, int64_t max_hops, const int64_t *k) {
+static int walk_check_bounds(int64_t min_hops, int64_t max_hops, const int64_t *k, const char *k_name = "k") {
 	if (min_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "min_hops must not be negative");
 	if (max_hops < min_hops) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be below min_hops");
-	if (k && *k < 1) return fail(PGQ_ERR_INVALID_ARG, "k must be at least 1");
+	if (k && *k < 1) return fail(PGQ_ERR_INVALID_ARG, std::string(k_name) + " must be at least 1");
 	if (max_hops > PGQ_WALK_MAX_HOPS)
 		return fail(PGQ_ERR_UNSUPPORTED, "walks need an upper bound of at most " + std::to_string(PGQ_WALK_MAX_HOPS) +
 		                                     " edges: in a cyclic graph the number of walks is unbounded");
@@ -487,6 +562,107 @@ int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pg
 		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo).run(); };
 		return list_chunk_body(ws, V, n, src, dst, k, run, o);
 	});
+}
+
+// ---- the path modes ------------------------------------------------------------------------------------------------------------
+
+// min(count, limit) over n counts, -1 (NULL) kept: pgq_walk_count_mode under NONE / WALK
+__global__ void k_walk_clamp(int64_t n, int64_t limit, int64_t *__restrict__ count) {
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n && count[i] > limit) count[i] = limit;
+}
+
+static bool mode_is_walk(int path_mode) { return path_mode == PGQ_MODE_NONE || path_mode == PGQ_MODE_WALK; }
+// a NULL handle, the mode's number, then the bounds; an unbounded upper is not built under a mode either
+static int mode_check(const pgq_csr *csr, int path_mode, int64_t min_hops, int64_t max_hops, const int64_t *k, const char *k_name) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	if (path_mode < PGQ_MODE_NONE || path_mode > PGQ_MODE_ACYCLIC)
+		return fail(PGQ_ERR_INVALID_ARG, "path_mode must be PGQ_MODE_NONE, _WALK, _SIMPLE, _TRAIL or _ACYCLIC (0 .. 4)");
+	return walk_check_bounds(min_hops, max_hops, k, k_name);
+}
+// the count form's run: the search's counting pass, or the walks' count cut at the limit
+static int count_mode_run(pgq_csr *csr, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t limit,
+                          int path_mode, ListOut &o) {
+	if (!mode_is_walk(path_mode)) {
+		o.limit = limit;
+		return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o, path_mode).run();
+	}
+	PGQ_TRY(WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o).run());
+	if (n > 0) hipLaunchKernelGGL(k_walk_clamp, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, limit, o.d_count);
+	PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
+	return PGQ_OK;
+}
+
+int pgq_walk_count_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t limit,
+                                    int path_mode, int64_t *d_out_count) {
+	mode_steps() = ModeSteps {};
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_count, "NULL device array"));
+		return mode_check(csr, path_mode, min_hops, max_hops, &limit, "limit");
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		ListOut out;
+		out.d_count = d_out_count;
+		return count_mode_run(csr, ws, n, d_src, d_dst, min_hops, max_hops, limit, path_mode, out);
+	});
+}
+
+int pgq_k_shortest_walks_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t k,
+                                          int path_mode, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths,
+                                          int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used,
+                                          int64_t *child_used) {
+	mode_steps() = ModeSteps {};
+	if (paths_used) *paths_used = 0;
+	if (child_used) *child_used = 0;
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_len && d_out_count && d_out_first && d_out_npaths && d_path_offset && d_path_hops && d_child,
+		                     "NULL device array"));
+		if (path_cap < 0 || child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
+		return mode_check(csr, path_mode, min_hops, max_hops, &k, "k");
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		ListOut out;
+		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths;
+		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
+		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
+		return list_bulk_body(out, k, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o, mode).run(); }, paths_used, child_used);
+	});
+}
+
+int pgq_walk_count_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t limit, int path_mode,
+                        int64_t *out_count, uint64_t *out_valid) {
+	mode_steps() = ModeSteps {};
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&] { return count_chunk_check(csr, V, n, out_count, out_valid, [&] { return mode_check(csr, path_mode, min_hops, max_hops, &limit, "limit"); }); };
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		auto run = [&](ListOut &o, const int64_t *d_src, const int64_t *d_dst) {
+			return count_mode_run(csr, ws, n, d_src, d_dst, min_hops, max_hops, limit, path_mode, o);
+		};
+		return count_chunk_body(ws, V, n, src, dst, run, out_count, out_valid);
+	});
+}
+
+int pgq_k_shortest_walks_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t k, int path_mode,
+                              uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
+                              uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
+	mode_steps() = ModeSteps {};
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len };
+	auto check = [&] { return list_chunk_check(csr, V, n, o, [&] { return mode_check(csr, path_mode, min_hops, max_hops, &k, "k"); }); };
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
+		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo, mode).run(); };
+		return list_chunk_body(ws, V, n, src, dst, k, run, o);
+	});
+}
+
+int pgq_debug_mode_steps(int64_t *total, int64_t *row_max) {
+	if (!total || !row_max) return fail(PGQ_ERR_INVALID_ARG, "pgq_debug_mode_steps: NULL output");
+	*total = mode_steps().total;
+	*row_max = mode_steps().row_max;
+	return PGQ_OK;
 }
 
 } // extern "C"

@@ -7,6 +7,7 @@
 //   pull_masked_sum              a vertex's in-list, 64 entries and 64 mask words per trip: the saturating sum, per lane, of the
 //                                table rows of the in-neighbours whose mask word has the lane's bit
 //   rank_row                     the row of a batch that a global path number belongs to
+//   unrank_slot                  the forward slot of an in-slot (the m-th-slot rule below), callable alone
 //   unrank_step                  one step of the unranking: the in-slot of x that rank r falls into, by a caller-given weight per
 //                                candidate, and the forward slot it stands for — the m-th in-slot from u into x is the m-th slot of
 //                                u's out-list into x, because the reverse CSR is the forward slot list stably sorted by target
@@ -76,6 +77,32 @@ struct UnrankStep {
 	int64_t slot; // the forward slot of the edge (u, x)
 	u32 error;    // 0; 2: rank r lies behind x's in-list; 4: u's out-list has no such slot
 };
+// The forward slot that the in-slot at position jsel of x's in-list (radj[jsel] = u, the list starts at rb) stands for, for a whole
+// wavefront; -1 when u's out-list has no such slot.  On its own for the path modes' search (pgq_path_modes.h), which needs a
+// candidate's edge before it takes it.
+__device__ __forceinline__ int64_t unrank_slot(int x, int u, int64_t jsel, int lane, int64_t rb, const int32_t *__restrict__ radj,
+                                               const int64_t *__restrict__ off, const int32_t *__restrict__ adj) {
+	// the taken in-slot is the mth from u into x (they are consecutive: the in-list is ordered by parent, then forward slot)
+	int mth = 0;
+	for (int64_t j = rb + lane; j < jsel; j += 64) mth += radj[j] == u ? 1 : 0;
+	for (int o = 32; o > 0; o >>= 1) mth += __shfl_xor(mth, o);
+	// ... its edge the mth slot of u's out-list into x
+	int64_t slot = -1;
+	const int64_t fb = off[u], fe = off[u + 1];
+	for (int64_t e0 = fb; e0 < fe && slot < 0; e0 += 64) {
+		const int64_t e = e0 + lane;
+		u64 hm = __ballot(e < fe && adj[e] == x);
+		const int c = __popcll(hm);
+		if (mth < c) {
+			for (int k = 0; k < mth; k++) hm &= hm - 1;
+			slot = e0 + __ffsll((long long)hm) - 1;
+		} else {
+			mth -= c;
+		}
+	}
+	return slot;
+}
+
 // One step of the unranking, a wavefront at x with rank r (uniform over the lanes): x's in-list in its stored order, 64 positions
 // at a time; weight(cand) = the paths that reach x through candidate cand (0: not a parent).  The first position whose inclusive
 // prefix sum passes r is taken and r loses the exclusive prefix.
@@ -102,24 +129,7 @@ __device__ __forceinline__ UnrankStep unrank_step(int x, int64_t &r, int lane, c
 		r -= __shfl(upto, 63); // (<= r, so it is a true sum)
 	}
 	if (jsel < 0) return UnrankStep { -1, -1, 2u };
-	// the taken in-slot is the mth from u into x (they are consecutive: the in-list is ordered by parent, then forward slot)
-	int mth = 0;
-	for (int64_t j = rb + lane; j < jsel; j += 64) mth += radj[j] == u ? 1 : 0;
-	for (int o = 32; o > 0; o >>= 1) mth += __shfl_xor(mth, o);
-	// ... its edge the mth slot of u's out-list into x
-	int64_t slot = -1;
-	const int64_t fb = off[u], fe = off[u + 1];
-	for (int64_t e0 = fb; e0 < fe && slot < 0; e0 += 64) {
-		const int64_t e = e0 + lane;
-		u64 hm = __ballot(e < fe && adj[e] == x);
-		const int c = __popcll(hm);
-		if (mth < c) {
-			for (int k = 0; k < mth; k++) hm &= hm - 1;
-			slot = e0 + __ffsll((long long)hm) - 1;
-		} else {
-			mth -= c;
-		}
-	}
+	const int64_t slot = unrank_slot(x, u, jsel, lane, rb, radj, off, adj);
 	return UnrankStep { u, slot, slot < 0 ? 4u : 0u };
 }
 
@@ -250,11 +260,16 @@ protected:
 
 	// A batch's lists, from the end of its rounds to the unranking launch.  plan(cntp, cnte) enqueues the kernel that writes the
 	// lists and the staged elements of each of the batch's m rows; unrank(lists, ploc, eloc, at) the one that writes them, `at`
-	// being where the batch's block of tight_stage starts.  The caller reads the error flag back.
+	// being where the batch's block of tight_stage starts.  The caller reads the error flag back.  planned(), if given, runs once
+	// the plan kernel has been waited for: what it returns other than PGQ_OK ends the batch before anything is staged.
 	template <typename Plan, typename Unrank> int emit(int64_t m, Plan &&plan, Unrank &&unrank) {
+		return emit(m, plan, unrank, [] { return PGQ_OK; });
+	}
+	template <typename Plan, typename Unrank, typename Planned> int emit(int64_t m, Plan &&plan, Unrank &&unrank, Planned &&planned) {
 		int64_t *loc[2], totals[2] = { 0, 0 }, at = 0;
 		PGQ_TRY(stage.place(m, [&](int64_t *const *cnt) { if (m > 0) plan(cnt[0], cnt[1]); }, 2, loc, totals));
 		PGQ_TRY(stage.wait());
+		PGQ_TRY(planned());
 		emitted += totals[0];
 		if (emitted > 0x7FFFFFFFll) return too_many();
 		PGQ_TRY(stage.stage_reserve(totals[1], &at));

@@ -8,6 +8,8 @@
 //   AllShortestPathsFunction       (no counterpart) ... the first max_paths of them, LIST(LIST(BIGINT)); bound and max_paths trail the arguments
 //   WalkCountFunction              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
 //   KShortestWalksFunction         (no counterpart: TopK, match.cpp:82-98) ... the first k of them, shortest first, LIST(LIST(BIGINT))
+//   WalkCountModeFunction          (no counterpart: path modes, match.cpp:80-108) the walks TRAIL / ACYCLIC / SIMPLE admit, up to a limit
+//   KShortestWalksModeFunction     (no counterpart) ... the first k of them, shortest first, LIST(LIST(BIGINT))
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
 // plus PathFindingRelation, the whole-relation entry point SURVEY.md §8f rank 2 asks for (length and path of every
@@ -243,10 +245,41 @@ void WalkCountFunction(DataChunk &args, ExpressionState &state, Vector &result) 
 	in.state->csr_to_delete.insert(in.csr_id);
 }
 
+// walk_count(csr_id, V, src, dst, lower, upper, limit, path_mode) -> BIGINT: min(the walks of lower..upper edges that the path mode
+// admits, limit); path_mode is the binder's PGQPathMode (subpath_element.hpp:9) as a BIGINT constant.  There is no unlimited count
+// under a mode (counting simple paths is #P-hard): `count >= n` and `EXISTS` are what a query can ask.  NULL for a NULL endpoint.
+void WalkCountModeFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	const int64_t lower = ConstantArg(args, 4), upper = ConstantArg(args, 5), limit = ConstantArg(args, 6), path_mode = ConstantArg(args, 7);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto result_data = FlatVector::GetDataMutable<int64_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	if (pgq_walk_count_mode(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, limit,
+	                        (int)path_mode, result_data, validity.GetData()) != PGQ_OK)
+		ThrowDevice();
+	in.state->csr_to_delete.insert(in.csr_id);
+}
+
 // k_shortest_walks(csr_id, V, src, dst, lower, upper, k) -> LIST(LIST(BIGINT)): SHORTEST k — the first `k` walks of lower..upper
 // edges of every row, shorter walks first, each [x_0, e_1, x_1, ..., x_t].  Nested like all_shortestpaths' result; the inner lists
 // of one row differ in length.  Rows without a walk are NULL and keep the outer entry {0, 0}.
-void KShortestWalksFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+namespace {
+void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *path_mode);
+}
+void KShortestWalksFunction(DataChunk &args, ExpressionState &state, Vector &result) { KShortestWalks(args, state, result, nullptr); }
+
+// k_shortest_walks(csr_id, V, src, dst, lower, upper, k, path_mode) -> LIST(LIST(BIGINT)): SHORTEST k under TRAIL / ACYCLIC / SIMPLE —
+// the first `k` walks that the mode admits, in k_shortest_walks' order; path_mode is the binder's PGQPathMode as a BIGINT constant
+// (NONE and WALK give the seven-argument call's lists).  Rows without an admitted walk are NULL.
+void KShortestWalksModeFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	const int64_t path_mode = ConstantArg(args, 7);
+	KShortestWalks(args, state, result, &path_mode);
+}
+
+namespace {
+// k_shortest_walks with seven arguments (path_mode == nullptr) or eight
+void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *path_mode) {
 	SearchInputs in = Prepare(args, state, "shortest path");
 	const int64_t lower = ConstantArg(args, 4), upper = ConstantArg(args, 5), k = ConstantArg(args, 6);
 	result.SetVectorType(VectorType::FLAT_VECTOR);
@@ -257,9 +290,13 @@ void KShortestWalksFunction(DataChunk &args, ExpressionState &state, Vector &res
 	const int64_t *child = nullptr;
 	uint64_t path_total = 0, child_len = 0;
 	vector<uint64_t> first(args.size()), npaths(args.size());
-	if (pgq_k_shortest_walks(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k,
-	                         first.data(), npaths.data(), validity.GetData(), &path_offset, &path_length, &path_total, &child, &child_len) != PGQ_OK)
-		ThrowDevice();
+	pgq_csr_t *device = DeviceCSR(*in.state, *in.csr, in.v_size);
+	const int rc = path_mode ? pgq_k_shortest_walks_mode(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k, (int)*path_mode,
+	                                                     first.data(), npaths.data(), validity.GetData(), &path_offset, &path_length, &path_total, &child,
+	                                                     &child_len)
+	                         : pgq_k_shortest_walks(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k, first.data(),
+	                                                npaths.data(), validity.GetData(), &path_offset, &path_length, &path_total, &child, &child_len);
+	if (rc != PGQ_OK) ThrowDevice();
 	ListVector::Reserve(result, path_total);
 	Vector &inner = ListVector::GetEntry(result);
 	inner.SetVectorType(VectorType::FLAT_VECTOR);
@@ -278,6 +315,7 @@ void KShortestWalksFunction(DataChunk &args, ExpressionState &state, Vector &res
 	}
 	in.state->csr_to_delete.insert(in.csr_id);
 }
+} // namespace
 
 namespace {
 // cheapest_path_length with four arguments (upper == nullptr) or five

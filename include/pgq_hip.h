@@ -329,8 +329,8 @@ int pgq_all_shortestpaths(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, p
  * rounds, not K); pgq_walk_count runs every round up to K or to the round that activates no vertex.
  * Workspace per batch of 64 sources: pgq_walk_count two rounds (1040 bytes per vertex); pgq_k_shortest_walks every round it runs,
  * 0..K at most, for the unranking: 520 bytes per vertex and round; PGQ_ERR_OOM with nothing written when it cannot be had.
- * NOT BUILT: _multi forms; path modes TRAIL / ACYCLIC / SIMPLE; SHORTEST k GROUP; splitting long in-lists over several wavefronts
- * (a list is walked by one wavefront); any change to how the binder's iterativelength filter is emitted. */
+ * NOT BUILT: _multi forms; SHORTEST k GROUP; splitting long in-lists over several wavefronts (a list is walked by one wavefront);
+ * any change to how the binder's iterativelength filter is emitted.  The path modes are the _mode calls below. */
 #define PGQ_WALK_MAX_HOPS 64
 int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                    int64_t *out_count, uint64_t *out_valid);
@@ -338,6 +338,56 @@ int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pg
                          int64_t k, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset,
                          const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
                          uint64_t *out_child_len);
+
+/* k_shortest_walks_mode / walk_count_mode: SHORTEST k and a limited count under SQL/PGQ's path modes (the reference's binder rejects
+ * every mode but WALK, match.cpp:80-108, and tells its users to pick one when ALL explodes on a cyclic graph, match.cpp:100-104).
+ * The modes are numbered as the reference's PGQPathMode (subpath_element.hpp:9); any other value is PGQ_ERR_INVALID_ARG.
+ * For a row (src, dst), lo = min_hops, K = max_hops, let S be the whole sequence pgq_k_shortest_walks would list with unlimited k:
+ * every walk of lo..K edges, shortest first, equal lengths ordered by in-list positions from the destination end.  A walk
+ * [x_0, e_1, x_1, ..., e_t, x_t] is ADMITTED by a mode when, judged on the list itself:
+ *   PGQ_MODE_ACYCLIC  no two of x_0 .. x_t are equal.  For src == dst only the empty walk is admitted.
+ *   PGQ_MODE_SIMPLE   no two of x_0 .. x_t are equal, except that x_0 == x_t is allowed: a self-loop [a, e, a] and a ring back to its
+ *                     start are simple.
+ *   PGQ_MODE_TRAIL    no two of e_1 .. e_t are equal, compared as the list's elements (edge_ids[slot], or the slot when the CSR has
+ *                     no edge ids).  Parallel slots with different ids are different edges; the two slots the binder's undirected CTE
+ *                     gives one edge share an id, so a trail cannot go back over it (GQL's meaning).  Ids are taken to be shared by
+ *                     an edge's two directions at most: then every walk of dist(src, dst) edges is a trail.
+ *   PGQ_MODE_NONE / PGQ_MODE_WALK  every walk.
+ *   - pgq_k_shortest_walks_mode: a row's list is the first min(a, k) admitted walks of S, in S's order, a being the number of
+ *     admitted walks — NOT the admitted ones among the first k of S.  Outputs, arena and NULL conventions as pgq_k_shortest_walks.
+ *     A row with no admitted walk, or with a NULL endpoint, is NULL: outer entry {0, 0}, no inner list, no payload.
+ *   - pgq_walk_count_mode: min(a, limit); NULL (payload -1) for a NULL endpoint.  The same search with nothing emitted.  There is
+ *     no unlimited count: counting simple paths is #P-hard, so the count is only ever taken up to a limit.
+ * With path_mode NONE or WALK both calls go to the existing code and return exactly what pgq_k_shortest_walks and
+ * min(pgq_walk_count, limit) return.
+ * min_hops < 0, max_hops < min_hops, k < 1 or limit < 1 -> PGQ_ERR_INVALID_ARG.  max_hops > PGQ_WALK_MAX_HOPS (INT64_MAX included) ->
+ * PGQ_ERR_UNSUPPORTED: an unbounded upper under a mode, finite though the answer would be, is NOT BUILT.  A NULL handle ->
+ * PGQ_ERR_INVALID_ARG before any device is asked for.  More than 2^31 - 1 emitted walks -> PGQ_ERR_UNSUPPORTED.  A failed call has
+ * written nothing to the caller.
+ * How: the rounds of pgq_k_shortest_walks with every round's table kept, then a depth-first search per row from the destination over
+ * the stored in-list order, pruned by the tables (a parent must still reach the source in exactly the edges left) and by the mode's
+ * test on the partial walk; a counting pass, then an emitting pass.  The walks of d = dist(src, dst) edges are admitted by every mode,
+ * so a row with lo <= d is settled once W_d[dst] >= k and the rounds of a batch stop when all its rows are (k = 1 on a pair d >= lo
+ * apart costs d rounds); every other row keeps them going to round K.
+ * WORK LIMIT: finding a simple path of an exact length is NP-hard, a row's search can take exponentially long.  Option
+ * "mode_step_cap" (pgq_set_option / pgq_csr_set_option; shipped 2^24, a safety limit, not a tuned number) bounds the steps of one row
+ * in one pass, a step being one 64-entry in-list chunk examined or one descent; a row beyond it ends the call with
+ * PGQ_ERR_UNSUPPORTED, pgq_last_error() names the cap, nothing is written.  pgq_debug_mode_steps gives the steps the calling thread's
+ * last mode call took: their sum over rows and passes, and the most one row took in one pass (both 0 under NONE / WALK).
+ * NOT BUILT: _multi forms; an unbounded upper; an unlimited count; a smarter prune than the walk tables (they admit a parent that
+ * reaches the source only through the stack); several wavefronts per row. */
+#define PGQ_MODE_NONE 0
+#define PGQ_MODE_WALK 1
+#define PGQ_MODE_SIMPLE 2
+#define PGQ_MODE_TRAIL 3
+#define PGQ_MODE_ACYCLIC 4
+int pgq_walk_count_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                        int64_t limit, int path_mode, int64_t *out_count, uint64_t *out_valid);
+int pgq_k_shortest_walks_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                              int64_t k, int path_mode, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
+                              const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
+                              const int64_t **out_child, uint64_t *out_child_len);
+int pgq_debug_mode_steps(int64_t *total, int64_t *row_max);
 
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
@@ -445,6 +495,17 @@ int pgq_k_shortest_walks_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d
                                      int64_t max_hops, int64_t k, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first,
                                      int64_t *d_out_npaths, int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap,
                                      int64_t *d_child, int64_t child_cap, int64_t *paths_used, int64_t *child_used);
+/* pgq_walk_count_mode without the chunk ceiling: d_out_count[i] = min(a, limit), -1 for a NULL row (d_src[i] < 0). */
+int pgq_walk_count_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                    int64_t max_hops, int64_t limit, int path_mode, int64_t *d_out_count);
+/* pgq_k_shortest_walks_mode without the chunk ceiling: pgq_k_shortest_walks_bulk_device with path_mode behind k, the same outputs and
+ * the same two-buffer capacity protocol.  Under a mode d_out_len[i] = the hops of the row's first admitted walk (-1: none) and
+ * d_out_npaths[i] = d_out_count[i] = min(a, k) (-1 / 0 for a NULL row as there); under NONE / WALK all of them are that call's. */
+int pgq_k_shortest_walks_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                          int64_t max_hops, int64_t k, int path_mode, int64_t *d_out_len, int64_t *d_out_count,
+                                          int64_t *d_out_first, int64_t *d_out_npaths, int64_t *d_path_offset, int64_t *d_path_hops,
+                                          int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used,
+                                          int64_t *child_used);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

@@ -19,6 +19,8 @@
  *   pgq_udf_all_shortestpaths       (no counterpart) ... and the first max_paths of them as a list of lists; both bound like shortestpath
  *   pgq_udf_walk_count              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
  *   pgq_udf_k_shortest_walks        (no counterpart: TopK, match.cpp:82-98) ... and the first k of them, shortest first; both bound like shortestpath
+ *   pgq_udf_walk_count_mode         (no counterpart: path modes, match.cpp:80-108) the admitted walks under TRAIL / ACYCLIC / SIMPLE, up to a limit
+ *   pgq_udf_k_shortest_walks_mode   (no counterpart) ... and the first k of them, shortest first; both bound like shortestpath
  *   pgq_udf_bind_cheapest           CheapestPathLengthBind      src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
@@ -106,6 +108,19 @@ int pgq_udf_k_shortest_walks(pgq_state_t *, int32_t id, int64_t V, int64_t n, pg
                              int64_t max_hops, int64_t k, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
                              const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
                              const int64_t **out_child, uint64_t *out_child_len);
+/* walk_count(id, V, src, dst, lower, upper, limit, path_mode) -> BIGINT: min(admitted walks, limit) under path_mode (PGQ_MODE_*,
+ * pgq_walk_count_mode; NONE / WALK: min(walk_count, limit)); NULL for a NULL endpoint.  Bound through pgq_udf_bind_search, errors as
+ * for pgq_udf_walk_count; limit < 1 and an unknown mode are the device library's PGQ_ERR_INVALID_ARG, a row's search beyond option
+ * mode_step_cap its PGQ_ERR_UNSUPPORTED */
+int pgq_udf_walk_count_mode(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops,
+                            int64_t max_hops, int64_t limit, int path_mode, int64_t *out, uint64_t *out_valid);
+/* k_shortest_walks(id, V, src, dst, lower, upper, k, path_mode) -> LIST(LIST(BIGINT)): the first k walks of lower..upper edges that
+ * path_mode admits, in k_shortest_walks' order (pgq_k_shortest_walks_mode; NONE / WALK: that call's lists); outputs and errors as
+ * pgq_udf_k_shortest_walks, plus those of pgq_udf_walk_count_mode */
+int pgq_udf_k_shortest_walks_mode(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops,
+                                  int64_t max_hops, int64_t k, int path_mode, uint64_t *out_first, uint64_t *out_npaths,
+                                  uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
+                                  uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len);
 /* *ret_type: PGQ_W_INT64 -> BIGINT result, PGQ_W_DOUBLE -> DOUBLE result */
 int pgq_udf_bind_cheapest(pgq_state_t *, int32_t id, int *ret_type);
 int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
