@@ -143,6 +143,13 @@ def load_hip():
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pgq_debug_mode_steps.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.pgq_k_shortest_groups.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_k_shortest_groups_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                                    C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -212,6 +219,9 @@ def load_udf():
     L.pgq_udf_k_shortest_walks_mode.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_udf_k_shortest_groups.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -367,6 +377,12 @@ def _all_shortestpaths(call, n, raw):
     valid = unpack_validity(ov, n)
     return [[ch[int(po[k]):int(po[k]) + int(pl[k])].tolist() for k in range(int(f), int(f) + int(c))] if ok else None
             for f, c, ok in zip(first, npaths, valid)]
+
+
+def _grouped_shortestpaths(call, n, raw):
+    """_all_shortestpaths for k_shortest_groups, whose call takes the groups per row behind npaths: (its result, ngroups)."""
+    ngroups = np.zeros(n, dtype=np.uint64)
+    return _all_shortestpaths(lambda first, npaths, *rest: call(first, npaths, _p(ngroups), *rest), n, raw), ngroups
 
 
 class DeviceCSR:
@@ -599,6 +615,20 @@ class DeviceCSR:
 
         return _all_shortestpaths(call, n, raw)
 
+    def k_shortest_groups(self, src, dst, min_hops, max_hops, groups, max_paths, path_mode=0, src_valid=None, dst_valid=None,
+                          src_sel=None, dst_sel=None, raw=False):
+        """SHORTEST k GROUP: per row every walk of its `groups` smallest distinct lengths in min_hops..max_hops that have a walk
+        path_mode (MODE_*) admits, in k_shortest_walks' order, cut at max_paths walks; None for rows without one and NULL rows.
+        Returns (lists, groups per row) — pgq_k_shortest_groups.  raw=True: see _all_shortestpaths."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+
+        def call(*outs):
+            _check(self.L.pgq_k_shortest_groups(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), int(groups), int(max_paths),
+                                                int(path_mode), *outs))
+
+        return _grouped_shortestpaths(call, n, raw)
+
     def cheapest_path_length(self, src, dst, src_valid=None, dst_valid=None):
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, None, None, dst_valid, keep)
@@ -815,6 +845,18 @@ class DeviceCSR:
                                                           C.c_void_p(d_child), child_cap, C.byref(paths), C.byref(used))
         return rc, paths.value, used.value
 
+    def k_shortest_groups_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, groups, max_paths, path_mode, d_out_len, d_out_count,
+                                   d_out_first, d_out_npaths, d_out_ngroups, d_path_offset, d_path_hops, path_cap, d_child, child_cap):
+        """(status, walks needed, elements needed): k_shortest_walks_mode_bulk_ptr with groups and max_paths in k's place and the
+        groups per row behind d_out_npaths."""
+        paths, used = C.c_int64(0), C.c_int64(0)
+        rc = self.L.pgq_k_shortest_groups_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                      int(groups), int(max_paths), int(path_mode), C.c_void_p(d_out_len),
+                                                      C.c_void_p(d_out_count), C.c_void_p(d_out_first), C.c_void_p(d_out_npaths),
+                                                      C.c_void_p(d_out_ngroups), C.c_void_p(d_path_offset), C.c_void_p(d_path_hops),
+                                                      path_cap, C.c_void_p(d_child), child_cap, C.byref(paths), C.byref(used))
+        return rc, paths.value, used.value
+
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                                   int(max_hops), C.c_void_p(d_out), C.c_void_p(d_ok)))
@@ -993,6 +1035,19 @@ class PgqState:
             self._ck(self.U.pgq_udf_k_shortest_walks(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), int(k), *outs))
 
         return _all_shortestpaths(call, n, raw)
+
+    def k_shortest_groups(self, csr_id, V, src, dst, min_hops, max_hops, groups, max_paths, path_mode=0, src_valid=None,
+                          dst_valid=None, src_sel=None, dst_sel=None, raw=False):
+        keep = []
+        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
+        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
+        n = len(src_sel) if src_sel is not None else len(src)
+
+        def call(*outs):
+            self._ck(self.U.pgq_udf_k_shortest_groups(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), int(groups),
+                                                      int(max_paths), int(path_mode), *outs))
+
+        return _grouped_shortestpaths(call, n, raw)
 
     def bind_cheapest(self, csr_id):
         t = C.c_int(0)

@@ -55,9 +55,15 @@
 // Kernel-class time: the rounds are K_PUSH, plan / unranking / gather K_RECON.
 // The path modes TRAIL / ACYCLIC / SIMPLE (pgq_k_shortest_walks_mode, pgq_walk_count_mode) run these rounds with every table kept
 // and k_walk_after's stop by distance, then search each row over the tables: pgq_path_modes.h, included below, has the contract.
-// Not built: _multi forms, SHORTEST k GROUP, splitting long in-lists over several wavefronts (a list is walked by the one wavefront
-// that meets it), any change to how the binder's iterativelength filter is emitted; under a mode: an unbounded upper, an unlimited
-// count, a smarter prune than W, several wavefronts per row.
+// SHORTEST k GROUP (pgq_k_shortest_groups: every walk of a row's g smallest non-empty lengths, capped at P = max_paths) runs the same
+// rounds with k_walk_after's group rule — per row the groups seen and the saturating sum `cum` of their W_t[dst]; a row is open while
+// groups seen < g and cum <= P — and k_walk_plan's: min(W_t[dst], P - taken) from each non-empty length, a stop behind the g-th,
+// ngroups = the lengths emitted from, count = min(cum, P + 1).  A is a prefix of S, so a rank means the same walk: k_walk_unrank, the
+// staging and k_walk_gather serve as they are.  ngroups has a seventh row array (ListCall::r_ng), reserved for this call alone.
+// Under a mode the rows close by distance (g == 1 or W_d[dst] > P) and k_mode_search carries the group rule.
+// Not built: _multi forms, splitting long in-lists over several wavefronts (a list is walked by the one wavefront that meets it), any
+// change to how the binder's iterativelength filter is emitted; under a mode: an unbounded upper, an unlimited count, a smarter
+// prune than W, several wavefronts per row; for the groups: a count-only form.
 
 namespace pgq {
 
@@ -95,11 +101,13 @@ __global__ void k_walk_init(const int32_t *__restrict__ usrc, int64_t U, int64_t
 	M0[v] = 1ull << l; // (distinct sources: distinct vertices)
 	q[l] = v;
 }
-__global__ void k_walk_rows(int64_t lo, int64_t hi, const u32 *__restrict__ sidx, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count) {
+__global__ void k_walk_rows(int64_t lo, int64_t hi, const u32 *__restrict__ sidx, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count,
+                            int64_t *__restrict__ r_ng) {
 	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= hi) return;
 	r_len[sidx[i]] = -1;
 	r_count[sidx[i]] = 0;
+	if (r_ng) r_ng[sidx[i]] = 0;
 }
 __global__ void k_walk_round_reset(WalkCounters *__restrict__ tc, int next_par) {
 	tc->nq[next_par] = 0;
@@ -161,9 +169,14 @@ __global__ __launch_bounds__(256) void k_walk_pull(const int64_t *__restrict__ r
 // by_distance (the path modes): a mode may reject any walk longer than d = dist(src, dst), the first t >= 0 with W_t[dst] > 0, and
 // rejects none of length d.  r_len notes d; a row is closed (r_count = k_stop) when min_hops <= d and W_d[dst] >= k_stop, and every
 // other row stays open to the last round.  The search's counting pass overwrites both arrays.
-__global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, bool by_distance, int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx,
-                             const int32_t *__restrict__ sdst, u32 base_lane, WalkRound cur, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count,
-                             const int32_t *__restrict__ qprev, u64 *__restrict__ m_zero, int par_prev, WalkCounters *__restrict__ tc) {
+// groups > 0 (k_shortest_groups; k_stop is its max_paths P, r_ng the groups seen): a non-empty length t >= min_hops is a group and
+// adds to r_count, the saturating sum `cum`; a row is open while it has seen fewer than `groups` of them and cum <= P — not cum < P:
+// with cum == P on a boundary a later non-empty length still makes the row's count P + 1.  by_distance: the row is closed (r_count =
+// P + 1) at its distance d when min_hops <= d and either groups == 1 or W_d[dst] > P.  k_walk_plan / the search overwrite the arrays.
+__global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, bool by_distance, int64_t groups, int64_t lo, int64_t hi, const u32 *__restrict__ skey,
+                             const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst, u32 base_lane, WalkRound cur, int64_t *__restrict__ r_len,
+                             int64_t *__restrict__ r_count, int64_t *__restrict__ r_ng, const int32_t *__restrict__ qprev, u64 *__restrict__ m_zero, int par_prev,
+                             WalkCounters *__restrict__ tc) {
 	const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (m_zero && tid < (int64_t)tc->nq[par_prev]) m_zero[qprev[tid]] = 0;
 	const int64_t i = lo + tid;
@@ -176,18 +189,37 @@ __global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, bool by_di
 				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
 				if (w > 0) {
 					r_len[row] = t;
-					if (t >= min_hops && w >= k_stop) r_count[row] = cnt = k_stop;
+					if (groups > 0) {
+						if (t >= min_hops && (groups == 1 || w > k_stop)) r_count[row] = cnt = k_stop + 1; // (P <= 2^31)
+					} else if (t >= min_hops && w >= k_stop) {
+						r_count[row] = cnt = k_stop;
+					}
 				}
 			}
-		} else if (t >= min_hops && cnt < k_stop) {
-			const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
-			if (w > 0) {
-				if (r_len[row] < 0) r_len[row] = t;
-				cnt = asp_sat_add(cnt, w);
-				r_count[row] = cnt;
+			open = groups > 0 ? cnt <= k_stop : cnt < k_stop;
+		} else if (groups > 0) {
+			int64_t ng = r_ng[row];
+			if (t >= min_hops && ng < groups && cnt <= k_stop) {
+				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
+				if (w > 0) {
+					if (r_len[row] < 0) r_len[row] = t;
+					cnt = asp_sat_add(cnt, w);
+					r_count[row] = cnt;
+					r_ng[row] = ++ng;
+				}
 			}
+			open = ng < groups && cnt <= k_stop;
+		} else {
+			if (t >= min_hops && cnt < k_stop) {
+				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
+				if (w > 0) {
+					if (r_len[row] < 0) r_len[row] = t;
+					cnt = asp_sat_add(cnt, w);
+					r_count[row] = cnt;
+				}
+			}
+			open = cnt < k_stop;
 		}
-		open = cnt < k_stop;
 	}
 	const u64 om = __ballot(open);
 	if (om && (threadIdx.x & 63) == 0) atomicAdd(&tc->pending, (u32)__popcll(om));
@@ -195,20 +227,40 @@ __global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, bool by_di
 
 // per row of the batch: the walks it emits and their elements; staged per row as [hops of each walk][the walks' elements]
 __global__ void k_walk_plan(int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst,
-                            u32 base_lane, const WalkRound *__restrict__ tabs, int64_t min_hops, int rounds, int64_t k, int64_t *__restrict__ r_np,
-                            int64_t *__restrict__ r_el, int64_t *__restrict__ cntp, int64_t *__restrict__ cnte) {
+                            u32 base_lane, const WalkRound *__restrict__ tabs, int64_t min_hops, int rounds, int64_t k, int64_t groups,
+                            int64_t *__restrict__ r_np, int64_t *__restrict__ r_el, int64_t *__restrict__ r_count, int64_t *__restrict__ r_ng,
+                            int64_t *__restrict__ cntp, int64_t *__restrict__ cnte) {
 	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= hi) return;
 	const int x = sdst[i];
 	const u32 l = skey[i] - base_lane;
-	int64_t rem = k, np = 0, el = 0;
-	for (int64_t t = min_hops; t <= rounds && rem > 0; t++) {
-		const int64_t take = min(walk_w(tabs[t], x, l), rem);
-		np += take;
-		el += take * (2 * t + 1); // take <= 2^31, 2 t + 1 <= 129
-		rem -= take;
-	}
 	const u32 row = sidx[i];
+	int64_t rem = k, np = 0, el = 0;
+	if (groups > 0) {
+		// k_shortest_groups, k = max_paths: the first `groups` non-empty lengths, cut at k walks (inside a group too).  The row's
+		// groups are the lengths it emits from; its count the walks of the planned lengths, capped at k + 1.
+		int64_t planned = 0, emitted = 0, cum = 0;
+		for (int64_t t = min_hops; t <= rounds && planned < groups; t++) {
+			const int64_t w = walk_w(tabs[t], x, l);
+			if (w <= 0) continue;
+			planned++;
+			cum = asp_sat_add(cum, w);
+			const int64_t take = min(w, rem);
+			if (take > 0) emitted++;
+			np += take;
+			el += take * (2 * t + 1);
+			rem -= take;
+		}
+		r_count[row] = min(cum, k + 1); // (k <= 2^31)
+		r_ng[row] = emitted;
+	} else {
+		for (int64_t t = min_hops; t <= rounds && rem > 0; t++) {
+			const int64_t take = min(walk_w(tabs[t], x, l), rem);
+			np += take;
+			el += take * (2 * t + 1); // take <= 2^31, 2 t + 1 <= 129
+			rem -= take;
+		}
+	}
 	r_np[row] = np;
 	r_el[row] = el;
 	cntp[i - lo] = np;
@@ -337,9 +389,11 @@ class WalkCall : ListCall {
 public:
 	// mode: 0 for the walks themselves, or PGQ_MODE_SIMPLE / _TRAIL / _ACYCLIC: then out.limit is k (lists) or the count's limit,
 	// every round's table is kept, the rounds stop by distance and the rows are searched (pgq_path_modes.h)
-	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, ListOut &out, int mode = 0)
-	    : ListCall(c, ws, n, d_src, d_dst, out, mode ? "k_shortest_walks_mode" : "k_shortest_walks", "walks"), min_hops(min_hops), max_hops(max_hops), mode(mode),
-	      keep_rounds(out.lists || mode != 0), step_cap(std::max(options().mode_step_cap, 0)), temps(ws->stream) {}
+	// groups > 0: k_shortest_groups — out.limit is max_paths, out.d_ng is set, the rounds and the search stop by groups
+	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, ListOut &out, int mode = 0,
+	         int64_t groups = 0)
+	    : ListCall(c, ws, n, d_src, d_dst, out, groups ? "k_shortest_groups" : mode ? "k_shortest_walks_mode" : "k_shortest_walks", "walks"), min_hops(min_hops),
+	      max_hops(max_hops), mode(mode), groups(groups), keep_rounds(out.lists || mode != 0), step_cap(std::max(options().mode_step_cap, 0)), temps(ws->stream) {}
 
 	int run() {
 		return ListCall::run(
@@ -356,6 +410,7 @@ public:
 private:
 	const int64_t min_hops, max_hops;
 	const int mode;
+	const int64_t groups; // 0, or SHORTEST k GROUP's k
 	const bool keep_rounds; // a table per round (the unranking, the search) instead of walk_count's two
 	const int64_t step_cap; // path modes: steps a row's search may take per pass
 	uint64_t steps_seen = 0; // ... the batch's steps already booked
@@ -406,9 +461,9 @@ private:
 		{
 			KernelTimer kt(st, K_PUSH);
 			hipLaunchKernelGGL(k_walk_init, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base, W[0], M[0], q[0], tc);
-			if (m > 0) hipLaunchKernelGGL(k_walk_rows, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, sidx, r_len, r_count);
-			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, min_hops, k_stop, mode != 0, lo, hi, skey, sidx, sdst, (u32)base,
-			                   round_of(0), r_len, r_count, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
+			if (m > 0) hipLaunchKernelGGL(k_walk_rows, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, sidx, r_len, r_count, r_ng);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, min_hops, k_stop, mode != 0, groups, lo, hi, skey, sidx, sdst,
+			                   (u32)base, round_of(0), r_len, r_count, r_ng, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
 			kt.stop();
 		}
 		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
@@ -423,8 +478,8 @@ private:
 			                   q[par ^ 1], tc, par);
 			// (the new queue's fill is not known here: the grid is sized for a queue of any size, its wavefronts stride)
 			hipLaunchKernelGGL(k_walk_pull, dim3(cus * 8), dim3(256), 0, st, c->roff, c->radj, prev.W, prev.M, W[slot_of(t)], cur.M, q[par ^ 1], tc, par ^ 1);
-			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, mode != 0, lo, hi, skey, sidx, sdst, (u32)base,
-			                   cur, r_len, r_count, (const int32_t *)q[par], keep_rounds ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, mode != 0, groups, lo, hi, skey, sidx, sdst,
+			                   (u32)base, cur, r_len, r_count, r_ng, (const int32_t *)q[par], keep_rounds ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
 			kt.stop();
 			PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 			S.levels++;
@@ -443,8 +498,8 @@ private:
 		PGQ_TRY(emit(
 		    m,
 		    [&](int64_t *cntp, int64_t *cnte) {
-			    hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, min_hops, rounds, out.limit, r_np,
-			                       r_el, cntp, cnte);
+			    hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, min_hops, rounds, out.limit, groups,
+			                       r_np, r_el, r_count, r_ng, cntp, cnte);
 		    },
 		    [&](int64_t nwalks, const int64_t *ploc, const int64_t *eloc, int64_t at) {
 			    hipLaunchKernelGGL(k_walk_unrank, dim3((unsigned)std::min<int64_t>(nwalks, 1 << 20)), dim3(64), 0, st, lo, m, nwalks, skey, sdst, (u32)base,
@@ -460,7 +515,7 @@ private:
 	template <bool EMIT> void launch_search(int64_t lo, int64_t m, u32 base, int rounds, int64_t *cntp, int64_t *cnte, const int64_t *ploc, const int64_t *eloc, int64_t at) {
 		hipLaunchKernelGGL(k_mode_search<EMIT>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, m, ws->skey.as<u32>(), ws->sidx.as<u32>(),
 		                   ws->sdst.as<int32_t>(), base, ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, mode, min_hops, rounds, out.limit,
-		                   step_cap, r_len, r_count, r_np, r_el, cntp, cnte, ploc, eloc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+		                   groups, step_cap, r_len, r_count, r_np, r_el, r_ng, cntp, cnte, ploc, eloc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
 	}
 	// what a pass left in the batch's counters: its steps booked, the step cap and the search's own errors reported
 	int search_status() {
@@ -655,6 +710,62 @@ int pgq_k_shortest_walks_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t sr
 		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
 		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo, mode).run(); };
 		return list_chunk_body(ws, V, n, src, dst, k, run, o);
+	});
+}
+
+// ---- SHORTEST k GROUP ----------------------------------------------------------------------------------------------------------
+
+// the path modes' checks with max_paths in k's place, and the groups
+static int groups_check(const pgq_csr *csr, int path_mode, int64_t min_hops, int64_t max_hops, int64_t groups, int64_t max_paths) {
+	PGQ_TRY(mode_check(csr, path_mode, min_hops, max_hops, &max_paths, "max_paths"));
+	if (groups < 1) return fail(PGQ_ERR_INVALID_ARG, "groups must be at least 1");
+	return PGQ_OK;
+}
+
+int pgq_k_shortest_groups_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t groups,
+                                      int64_t max_paths, int path_mode, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths,
+                                      int64_t *d_out_ngroups, int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap,
+                                      int64_t *paths_used, int64_t *child_used) {
+	mode_steps() = ModeSteps {};
+	if (paths_used) *paths_used = 0;
+	if (child_used) *child_used = 0;
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		PGQ_TRY(check_arrays(csr, n,
+		                     d_src && d_dst && d_out_len && d_out_count && d_out_first && d_out_npaths && d_out_ngroups && d_path_offset && d_path_hops && d_child,
+		                     "NULL device array"));
+		if (path_cap < 0 || child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
+		return groups_check(csr, path_mode, min_hops, max_hops, groups, max_paths);
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		ListOut out;
+		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths, out.d_ng = d_out_ngroups;
+		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
+		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
+		return list_bulk_body(out, max_paths, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o, mode, groups).run(); }, paths_used,
+		                      child_used);
+	});
+}
+
+int pgq_k_shortest_groups(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t groups, int64_t max_paths,
+                          int path_mode, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_ngroups, uint64_t *out_valid, const uint64_t **out_path_offset,
+                          const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
+	mode_steps() = ModeSteps {};
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	uint64_t no_rows = 0; // (n == 0: nothing is written through it)
+	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len, out_ngroups ? out_ngroups : &no_rows };
+	auto check = [&] {
+		return list_chunk_check(csr, V, n, o, [&]() -> int {
+			if (n > 0 && !out_ngroups) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+			return groups_check(csr, path_mode, min_hops, max_hops, groups, max_paths);
+		});
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
+		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) {
+			return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo, mode, groups).run();
+		};
+		return list_chunk_body(ws, V, n, src, dst, max_paths, run, o);
 	});
 }
 

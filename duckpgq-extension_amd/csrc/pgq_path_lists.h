@@ -135,9 +135,10 @@ __device__ __forceinline__ UnrankStep unrank_step(int x, int64_t &r, int lane, c
 
 // Rows without a lane.  Trivial ([lo_trivial, lo_null)): src == dst — one list, [src], of no hops when min_hops == 0, nothing
 // otherwise; the others: a NULL endpoint (count -1) or a row that cannot have a path (0).  r_np == null: the counts alone.
+// r_ng != null (k_shortest_groups): the row's groups, 1 with the list and 0 without.
 __global__ void k_asp_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, int64_t min_hops, const u32 *__restrict__ sidx, const int64_t *__restrict__ src,
                             const int64_t *__restrict__ dst, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np,
-                            int64_t *__restrict__ r_el) {
+                            int64_t *__restrict__ r_el, int64_t *__restrict__ r_ng) {
 	const int64_t i = lo_trivial + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const u32 row = sidx[i];
@@ -145,6 +146,7 @@ __global__ void k_asp_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, int6
 	r_len[row] = one ? 0 : -1;
 	r_count[row] = one ? 1 : (i >= lo_null && (src[row] < 0 || dst[row] < 0) ? -1 : 0);
 	if (r_np) r_np[row] = r_el[row] = one ? 1 : 0;
+	if (r_ng) r_ng[row] = one ? 1 : 0;
 }
 
 // The lists of a call's finished batches lie behind each other in ws->tight_stage; a batch's rows get their places there from
@@ -203,6 +205,7 @@ struct ListOut {
 	bool lists = false;
 	int64_t limit = 1; // max_paths / k
 	int64_t *d_len = nullptr, *d_count = nullptr, *d_first = nullptr, *d_np = nullptr;
+	int64_t *d_ng = nullptr; // k_shortest_groups only: the groups among a row's lists
 	int64_t *d_path_off = nullptr, *d_path_hops = nullptr, path_cap = 0, *d_child = nullptr, child_cap = 0; // d_path_hops: k_shortest_walks only
 	bool external = false;
 	int64_t paths_used = 0, child_used = 0;
@@ -228,6 +231,7 @@ protected:
 	pgq_stats_t &S = tstats().s;
 	// the rows' results, in row order: hops (of the first list), count, lists, elements, first list, first element (n + 1 entries each)
 	int64_t *r_len = nullptr, *r_count = nullptr, *r_np = nullptr, *r_el = nullptr, *r_first = nullptr, *r_eoff = nullptr;
+	int64_t *r_ng = nullptr; // a seventh, for the call that has out.d_ng: the groups (k_shortest_groups; during its rounds the groups seen)
 
 	int too_many() const { return fail(PGQ_ERR_UNSUPPORTED, name + ": the call would emit more than 2^31-1 " + noun); }
 	// what the unranking kernel left in its batch's error flag
@@ -246,9 +250,10 @@ protected:
 		S.unique_sources += U;
 		const int nb = (int)(((int64_t)U + LC - 1) / LC);
 		PGQ_TRY(batch_bounds(ws, n, LC, nb));
-		PGQ_TRY(ws->asp_rows.reserve((size_t)(n + 1) * 8 * 6));
+		PGQ_TRY(ws->asp_rows.reserve((size_t)(n + 1) * 8 * (out.d_ng ? 7 : 6)));
 		int64_t *rows = ws->asp_rows.as<int64_t>();
 		r_len = rows, r_count = rows + (n + 1), r_np = rows + 2 * (n + 1), r_el = rows + 3 * (n + 1), r_first = rows + 4 * (n + 1), r_eoff = rows + 5 * (n + 1);
+		if (out.d_ng) r_ng = rows + 6 * (n + 1);
 		if (nb > 0) {
 			PGQ_TRY(prepare());
 			const int64_t *bs = ws->h_bstart;
@@ -291,7 +296,7 @@ protected:
 		KernelTimer kt(st, K_RECON);
 		if (n > lo_t)
 			hipLaunchKernelGGL(k_asp_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, lo_n, n, min_hops, ws->sidx.as<u32>(), d_src, d_dst, r_len, r_count,
-			                   out.lists ? r_np : nullptr, r_el);
+			                   out.lists ? r_np : nullptr, r_el, out.lists ? r_ng : nullptr);
 		if (!out.lists) {
 			PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
 			kt.stop();
@@ -321,6 +326,7 @@ protected:
 		PGQ_HIP_TRY(hipMemcpyAsync(out.d_len, r_len, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
 		PGQ_HIP_TRY(hipMemcpyAsync(out.d_count, r_count, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
 		PGQ_HIP_TRY(hipMemcpyAsync(out.d_np, r_np, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+		if (out.d_ng) PGQ_HIP_TRY(hipMemcpyAsync(out.d_ng, r_ng, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
 		if (!out.overflow) PGQ_HIP_TRY(hipMemcpyAsync(out.d_first, r_first, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
 		kt.stop();
 		PGQ_TRY(stage.wait());
@@ -371,6 +377,7 @@ struct ListChunkOut {
 	uint64_t *path_total;
 	const int64_t **child;
 	uint64_t *child_len;
+	uint64_t *ngroups = nullptr; // k_shortest_groups only
 };
 template <typename Bounds> static int list_chunk_check(const pgq_csr *csr, int64_t V, int64_t n, const ListChunkOut &o, Bounds &&bounds) {
 	if (V != csr->V) return fail(PGQ_ERR_INVALID_ARG, "V does not match the uploaded CSR");
@@ -386,14 +393,17 @@ template <typename Bounds> static int list_chunk_check(const pgq_csr *csr, int64
 // are touched: the child payload, then the inner entries' offsets and lengths
 template <typename Run> static int list_chunk_body(Workspace *ws, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t limit, Run &&run, const ListChunkOut &o) {
 	PGQ_TRY(stage_rows_null_as_minus_one(ws, V, n, src, dst));
-	for (DevBuf *b : { &ws->out_len, &ws->out_off }) PGQ_TRY(b->reserve((size_t)n * 8 * 2));
+	PGQ_TRY(ws->out_len.reserve((size_t)n * 8 * (o.ngroups ? 3 : 2)));
+	PGQ_TRY(ws->out_off.reserve((size_t)n * 8 * 2));
 	ListOut out;
 	out.lists = true;
 	out.limit = std::min<int64_t>(limit, 1LL << 31);
 	out.d_len = ws->out_len.as<int64_t>(), out.d_count = out.d_len + n, out.d_first = ws->out_off.as<int64_t>(), out.d_np = out.d_first + n;
+	if (o.ngroups) out.d_ng = out.d_len + 2 * n;
 	PGQ_TRY(run(out, ws->in_src.as<int64_t>(), ws->in_dst.as<int64_t>()));
-	std::vector<int64_t> len(n), first_np((size_t)2 * n);
+	std::vector<int64_t> len(n), first_np((size_t)2 * n), ng(o.ngroups ? (size_t)n : 0);
 	PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
+	if (o.ngroups) PGQ_TRY(staged_download(ng.data(), out.d_ng, (size_t)n * 8, ws->stream));
 	PGQ_TRY(staged_download(first_np.data(), ws->out_off.p, (size_t)n * 8 * 2, ws->stream));
 	const size_t P = (size_t)out.paths_used, C = (size_t)out.child_used;
 	std::vector<int64_t> &arena = thread_child_arena();
@@ -413,6 +423,7 @@ template <typename Run> static int list_chunk_body(Workspace *ws, int64_t V, int
 			o.first[i] = (uint64_t)first_np[i];
 			o.npaths[i] = (uint64_t)first_np[(size_t)n + i];
 		}
+		if (o.ngroups) o.ngroups[i] = (uint64_t)ng[i];
 	}
 	*o.child = arena.data();
 	*o.child_len = (uint64_t)C;

@@ -27,6 +27,10 @@
 // Two passes over one device function: EMIT = false counts (r_np / r_el / r_len / r_count and the count arrays of ListCall::emit's
 // plan step, stopping a row at k), EMIT = true repeats the search and writes each admitted walk into the row's staged block in
 // k_walk_unrank's layout, [hops of each walk][elements], for k_walk_gather.  pgq_walk_count_mode runs the first pass only.
+// The group rule (pgq_k_shortest_groups, groups > 0, k = max_paths P): a length counts as a group once it yields an admitted walk, and
+// the row's search ends behind the length that completed group `groups`, or at `want`.  The counting pass runs with want = P + 1, so
+// that r_count = min(|A|, P + 1), and keeps the first min(found, P) walks for the emitting pass (r_np, r_el, the count arrays);
+// r_ng = the lengths among the kept walks.  With groups == 0 — every other caller — the search takes the steps it always took.
 // Not built: a smarter prune than W (a vertex that W admits may only be reachable through the stack), several wavefronts per row.
 
 namespace pgq {
@@ -41,8 +45,9 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
                                                    const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                    const int64_t *__restrict__ edge_ids, const int64_t *__restrict__ roff,
                                                    const int32_t *__restrict__ radj, const WalkRound *__restrict__ tabs, int mode, int64_t min_hops,
-                                                   int rounds, int64_t k, int64_t step_cap, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count,
-                                                   int64_t *__restrict__ r_np, int64_t *__restrict__ r_el, int64_t *__restrict__ cntp,
+                                                   int rounds, int64_t k, int64_t groups, int64_t step_cap, int64_t *__restrict__ r_len,
+                                                   int64_t *__restrict__ r_count, int64_t *__restrict__ r_np, int64_t *__restrict__ r_el,
+                                                   int64_t *__restrict__ r_ng, int64_t *__restrict__ cntp,
                                                    int64_t *__restrict__ cnte, const int64_t *__restrict__ ploc, const int64_t *__restrict__ eloc,
                                                    int64_t stage_base, int64_t *__restrict__ stage, int64_t *__restrict__ soff,
                                                    WalkCounters *__restrict__ tc) {
@@ -55,14 +60,17 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
 		const int64_t row_i = lo + a;
 		const u32 l = skey[row_i] - base_lane;
 		const int dst = sdst[row_i], src = usrc[base_lane + l];
-		const int64_t want = EMIT ? ploc[a + 1] - ploc[a] : k;                      // walks to find
+		const int64_t want = EMIT ? ploc[a + 1] - ploc[a] : (groups > 0 ? k + 1 : k); // walks to find (groups: one past the cap, k <= 2^31)
+		const int64_t keep = EMIT || groups <= 0 ? want : k;                        // ... of which the first `keep` are the row's list
 		const int64_t rowbase = EMIT ? stage_base + eloc[a] : 0;                    // the row's staged block ...
 		const int64_t room = EMIT ? eloc[a + 1] - eloc[a] - want : 0;               // ... and the elements it holds behind the hops
 		int64_t found = 0, el = 0, steps = 0, first = -1;
+		int64_t seen = 0, kept = 0; // the lengths that yielded an admitted walk (the group rule), and those among the first `keep` walks
 		u32 error = 0;
-		for (int64_t t64 = min_hops; t64 <= rounds && found < want && !error; t64++) {
+		for (int64_t t64 = min_hops; t64 <= rounds && found < want && !error && (groups <= 0 || seen < groups); t64++) {
 			const int t = (int)t64;
 			if (walk_w(tabs[t], dst, l) <= 0) continue;
+			bool fresh = true; // the length has yielded no admitted walk yet
 			int i = t;
 			sx[t] = dst;
 			scur[t] = 0;
@@ -86,8 +94,13 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
 						}
 					}
 					if (first < 0) first = t;
+					if (fresh) {
+						fresh = false;
+						seen++;
+						if (found < keep) kept++;
+					}
+					if (found < keep) el += 2 * t + 1;
 					found++;
-					el += 2 * t + 1;
 					i = 1; // (t == 0: past the loop)
 					continue;
 				}
@@ -152,12 +165,14 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
 			if (!EMIT) {
 				const u32 row = sidx[row_i];
 				r_len[row] = first;
+				const int64_t np = min(found, keep);
 				r_count[row] = found;
-				r_np[row] = found;
+				r_np[row] = np;
 				r_el[row] = el;
+				if (r_ng) r_ng[row] = kept;
 				if (cntp) {
-					cntp[a] = found;
-					cnte[a] = found > 0 ? found + el : 0;
+					cntp[a] = np;
+					cnte[a] = np > 0 ? np + el : 0;
 				}
 			} else if (found > 0) {
 				soff[row_i] = rowbase;

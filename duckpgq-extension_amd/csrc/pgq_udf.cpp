@@ -418,6 +418,22 @@ int pgq_udf_k_shortest_walks_mode(pgq_state_t *s, int32_t id, int64_t V, int64_t
 	return 0;
 }
 
+// SHORTEST k GROUP (no counterpart: the parser's PathPattern::group, path_pattern.hpp:22, is rejected with TopK): bound through pgq_udf_bind_search
+int pgq_udf_k_shortest_groups(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                              int64_t groups, int64_t max_paths, int path_mode, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_ngroups,
+                              uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
+                              const int64_t **out_child, uint64_t *out_child_len) {
+	CsrRef c;
+	pgq_csr_t *d;
+	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
+	if (pgq_k_shortest_groups(d, V, n, src, dst, min_hops, max_hops, groups, max_paths, path_mode, out_first, out_npaths, out_ngroups, out_valid,
+	                          out_path_offset, out_path_length, out_path_total, out_child, out_child_len) != PGQ_OK)
+		return device_fail();
+	std::lock_guard<std::mutex> g(s->csr_lock);
+	s->csr_to_delete.insert(id);
+	return 0;
+}
+
 int pgq_udf_bind_cheapest(pgq_state_t *s, int32_t id, int *ret_type) { // cheapest_path_length_function_data.cpp:7-32
 	if (!s) return fail("Invalid Input Error: NULL state");
 	CsrRef c = find_csr(s, id);

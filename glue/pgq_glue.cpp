@@ -10,6 +10,7 @@
 //   KShortestWalksFunction         (no counterpart: TopK, match.cpp:82-98) ... the first k of them, shortest first, LIST(LIST(BIGINT))
 //   WalkCountModeFunction          (no counterpart: path modes, match.cpp:80-108) the walks TRAIL / ACYCLIC / SIMPLE admit, up to a limit
 //   KShortestWalksModeFunction     (no counterpart) ... the first k of them, shortest first, LIST(LIST(BIGINT))
+//   KShortestGroupsFunction        (no counterpart: SHORTEST k GROUP, path_pattern.hpp:22) every walk of the k smallest lengths, LIST(LIST(BIGINT))
 //   LocalClusteringCoefficientFunction  src/core/functions/scalar/local_clustering_coefficient.cpp:11-72
 //   PageRankFunction               src/core/functions/scalar/pagerank.cpp:11-111
 // plus PathFindingRelation, the whole-relation entry point SURVEY.md §8f rank 2 asks for (length and path of every
@@ -265,7 +266,7 @@ void WalkCountModeFunction(DataChunk &args, ExpressionState &state, Vector &resu
 // edges of every row, shorter walks first, each [x_0, e_1, x_1, ..., x_t].  Nested like all_shortestpaths' result; the inner lists
 // of one row differ in length.  Rows without a walk are NULL and keep the outer entry {0, 0}.
 namespace {
-void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *path_mode);
+void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *path_mode, bool grouped = false);
 }
 void KShortestWalksFunction(DataChunk &args, ExpressionState &state, Vector &result) { KShortestWalks(args, state, result, nullptr); }
 
@@ -277,11 +278,22 @@ void KShortestWalksModeFunction(DataChunk &args, ExpressionState &state, Vector 
 	KShortestWalks(args, state, result, &path_mode);
 }
 
+// k_shortest_groups(csr_id, V, src, dst, lower, upper, groups, max_paths, path_mode) -> LIST(LIST(BIGINT)): SHORTEST k GROUP — every
+// walk of the `groups` smallest distinct lengths in lower..upper that have a walk the mode admits, in k_shortest_walks' order, cut at
+// `max_paths` walks per row (the cap may cut inside a group).  path_mode is the binder's PGQPathMode as a BIGINT constant.  Rows
+// without an admitted walk are NULL.
+void KShortestGroupsFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	const int64_t path_mode = ConstantArg(args, 8);
+	KShortestWalks(args, state, result, &path_mode, true);
+}
+
 namespace {
-// k_shortest_walks with seven arguments (path_mode == nullptr) or eight
-void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *path_mode) {
+// k_shortest_walks with seven arguments (path_mode == nullptr) or eight; grouped: k_shortest_groups' nine (groups and max_paths in
+// k's place, the groups per row are not part of the SQL result)
+void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *path_mode, bool grouped) {
 	SearchInputs in = Prepare(args, state, "shortest path");
 	const int64_t lower = ConstantArg(args, 4), upper = ConstantArg(args, 5), k = ConstantArg(args, 6);
+	const int64_t max_paths = grouped ? ConstantArg(args, 7) : 0;
 	result.SetVectorType(VectorType::FLAT_VECTOR);
 	auto outer = FlatVector::GetDataMutable<list_entry_t>(result);
 	ValidityMask &validity = FlatVector::ValidityMutable(result);
@@ -289,9 +301,12 @@ void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, con
 	const uint64_t *path_offset = nullptr, *path_length = nullptr; // owned by the library until this thread's next list-returning call
 	const int64_t *child = nullptr;
 	uint64_t path_total = 0, child_len = 0;
-	vector<uint64_t> first(args.size()), npaths(args.size());
+	vector<uint64_t> first(args.size()), npaths(args.size()), ngroups(grouped ? args.size() : 0);
 	pgq_csr_t *device = DeviceCSR(*in.state, *in.csr, in.v_size);
-	const int rc = path_mode ? pgq_k_shortest_walks_mode(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k, (int)*path_mode,
+	const int rc = grouped   ? pgq_k_shortest_groups(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k, max_paths,
+	                                                 (int)*path_mode, first.data(), npaths.data(), ngroups.data(), validity.GetData(), &path_offset,
+	                                                 &path_length, &path_total, &child, &child_len)
+	         : path_mode ? pgq_k_shortest_walks_mode(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k, (int)*path_mode,
 	                                                     first.data(), npaths.data(), validity.GetData(), &path_offset, &path_length, &path_total, &child,
 	                                                     &child_len)
 	                         : pgq_k_shortest_walks(device, in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper, k, first.data(),

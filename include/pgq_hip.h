@@ -329,8 +329,9 @@ int pgq_all_shortestpaths(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, p
  * rounds, not K); pgq_walk_count runs every round up to K or to the round that activates no vertex.
  * Workspace per batch of 64 sources: pgq_walk_count two rounds (1040 bytes per vertex); pgq_k_shortest_walks every round it runs,
  * 0..K at most, for the unranking: 520 bytes per vertex and round; PGQ_ERR_OOM with nothing written when it cannot be had.
- * NOT BUILT: _multi forms; SHORTEST k GROUP; splitting long in-lists over several wavefronts (a list is walked by one wavefront);
- * any change to how the binder's iterativelength filter is emitted.  The path modes are the _mode calls below. */
+ * NOT BUILT: _multi forms; splitting long in-lists over several wavefronts (a list is walked by one wavefront); any change to how
+ * the binder's iterativelength filter is emitted.  The path modes are the _mode calls below, SHORTEST k GROUP is
+ * pgq_k_shortest_groups. */
 #define PGQ_WALK_MAX_HOPS 64
 int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                    int64_t *out_count, uint64_t *out_valid);
@@ -388,6 +389,44 @@ int pgq_k_shortest_walks_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t sr
                               const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
                               const int64_t **out_child, uint64_t *out_child_len);
 int pgq_debug_mode_steps(int64_t *total, int64_t *row_max);
+
+/* k_shortest_groups(csr_id, V, src, dst, lower, upper, groups, max_paths, path_mode) -> LIST(LIST(BIGINT)): SQL/PGQ's SHORTEST k
+ * GROUP — every path of the k smallest distinct lengths a row has (the reference's parser carries the selector next to topk,
+ * PathPattern::group, path_pattern.hpp:22; its binder rejects it with TopK, match.cpp:80-108).  pgq_k_shortest_walks(k) cuts in the
+ * middle of a length and pgq_all_shortestpaths knows one length only.  For a row (src, dst), lo = min_hops, K = max_hops,
+ * g = groups, P = max_paths and a path_mode numbered as PGQ_MODE_*:
+ *   S            the sequence pgq_k_shortest_walks_mode defines for that mode with unlimited k: every admitted walk of lo..K edges,
+ *                shortest first, equal lengths ordered by in-list positions read from the destination end.  NONE and WALK admit
+ *                every walk.
+ *   the lengths  t_1 < t_2 < ...: the lengths in [lo, K] that have at least one admitted walk.  A length whose W_t[dst] is 0 is no
+ *                group; under a mode a length all of whose walks the mode refuses is no group; lengths below lo are no groups.
+ *   A            the admitted walks of lengths t_1 .. t_min(g, number of lengths): a prefix of S that ends on a group boundary.
+ *   the list     the first min(|A|, P) walks of A, each in shortestpath's layout.  P is a cap, as max_paths is in
+ *                pgq_all_shortestpaths; when it cuts it may cut inside a group, which is emitted as far as P goes.
+ * Per row: npaths = min(|A|, P); ngroups = the distinct lengths among the emitted walks (a cut-off group counts);
+ * count = min(|A|, P + 1), computed without overflow, so count > npaths exactly when the cap cut the row's answer; len = the hops
+ * of the first walk, -1 when there is none.  A row with no admitted walk, or with a NULL endpoint, is NULL: outer entry {0, 0}, no
+ * inner list, no payload, ngroups 0, count 0 (no walk) or -1 (NULL endpoint).  src == dst is not special, as in
+ * pgq_k_shortest_walks: with lo == 0 the empty walk [src] is group 1, and under ACYCLIC the only group.
+ * Consequences: g = 1 under NONE / WALK with src != dst and lo <= dist <= K gives pgq_all_shortestpaths(max_hops = K, max_paths = P)'s
+ * lists in its order; g >= K - lo + 1 gives pgq_k_shortest_walks_mode(k = P)'s lists under every mode; P = 1 with lo <= dist gives
+ * pgq_shortestpath's list as walk 0.
+ * Errors as pgq_k_shortest_walks_mode for the arguments it shares; groups < 1 or max_paths < 1 -> PGQ_ERR_INVALID_ARG; max_hops >
+ * PGQ_WALK_MAX_HOPS -> PGQ_ERR_UNSUPPORTED; more than 2^31 - 1 emitted walks -> PGQ_ERR_UNSUPPORTED; "mode_step_cap" bounds a row's
+ * steps per pass as there (the counting pass looks for P + 1 walks) and pgq_debug_mode_steps reports this call's steps too.  A NULL
+ * handle fails before any device is asked for.  A failed call has written nothing.
+ * How: NONE / WALK — pgq_k_shortest_walks' rounds; a row is open while it has seen fewer than g non-empty lengths and their walks'
+ * saturating sum is <= P (not < P: on a boundary a later non-empty length still makes count P + 1), a batch's rounds stop when no
+ * row is open; A is a prefix of S, so a rank means the same walk and the unranking serves as it is.  Under a mode — the search of
+ * pgq_k_shortest_walks_mode; a length is a group once it yields an admitted walk and a row's search ends behind the length that
+ * completed group g, or at P + 1 walks; a row is settled at its distance d when lo <= d and g == 1 or W_d[dst] > P, every other
+ * row keeps its batch going to round K.  Outputs as pgq_k_shortest_walks_mode plus out_ngroups (n entries).
+ * NOT BUILT: _multi forms; a count-only form; an unbounded upper; several wavefronts per row; a split of long in-lists. */
+int pgq_k_shortest_groups(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                          int64_t groups, int64_t max_paths, int path_mode, uint64_t *out_first, uint64_t *out_npaths,
+                          uint64_t *out_ngroups, uint64_t *out_valid, const uint64_t **out_path_offset,
+                          const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
+                          uint64_t *out_child_len);
 
 void pgq_thread_release(void); /* drop this thread's result arena */
 /* Frees the pooled per-call workspaces (search state sized by V x lanes is kept between calls for reuse) and the
@@ -506,6 +545,16 @@ int pgq_k_shortest_walks_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64
                                           int64_t *d_out_first, int64_t *d_out_npaths, int64_t *d_path_offset, int64_t *d_path_hops,
                                           int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used,
                                           int64_t *child_used);
+/* pgq_k_shortest_groups without the chunk ceiling: pgq_k_shortest_walks_mode_bulk_device with groups and max_paths in k's place and
+ * d_out_ngroups (n entries) behind d_out_npaths; the same two-buffer capacity protocol and arena rules.  d_out_len[i] = the hops of
+ * the row's first walk (-1: none), d_out_npaths[i] = min(|A|, P), d_out_ngroups[i] = the distinct lengths among the emitted walks,
+ * d_out_count[i] = min(|A|, P + 1), -1 for a NULL row.  When path_cap or child_cap is too small (PGQ_ERR_INVALID_ARG) d_out_len,
+ * d_out_count, d_out_npaths and d_out_ngroups are complete, the payload is not usable. */
+int pgq_k_shortest_groups_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                      int64_t max_hops, int64_t groups, int64_t max_paths, int path_mode, int64_t *d_out_len,
+                                      int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths, int64_t *d_out_ngroups,
+                                      int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap, int64_t *d_child,
+                                      int64_t child_cap, int64_t *paths_used, int64_t *child_used);
 
 /* ---- the other CSR consumers ------------------------------------------------------------- */
 

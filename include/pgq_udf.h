@@ -21,6 +21,7 @@
  *   pgq_udf_k_shortest_walks        (no counterpart: TopK, match.cpp:82-98) ... and the first k of them, shortest first; both bound like shortestpath
  *   pgq_udf_walk_count_mode         (no counterpart: path modes, match.cpp:80-108) the admitted walks under TRAIL / ACYCLIC / SIMPLE, up to a limit
  *   pgq_udf_k_shortest_walks_mode   (no counterpart) ... and the first k of them, shortest first; both bound like shortestpath
+ *   pgq_udf_k_shortest_groups       (no counterpart: SHORTEST k GROUP, path_pattern.hpp:22) every walk of the k smallest lengths; bound like shortestpath
  *   pgq_udf_bind_cheapest           CheapestPathLengthBind      src/core/functions/function_data/cheapest_path_length_function_data.cpp:7-32
  *   pgq_udf_cheapest_path_length    CheapestPathLengthFunction   src/core/functions/scalar/cheapest_path_length.cpp:138-163
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
@@ -121,6 +122,15 @@ int pgq_udf_k_shortest_walks_mode(pgq_state_t *, int32_t id, int64_t V, int64_t 
                                   int64_t max_hops, int64_t k, int path_mode, uint64_t *out_first, uint64_t *out_npaths,
                                   uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
                                   uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len);
+/* k_shortest_groups(id, V, src, dst, lower, upper, groups, max_paths, path_mode) -> LIST(LIST(BIGINT)): SHORTEST k GROUP — every walk
+ * of the `groups` smallest distinct lengths in lower..upper that have a walk path_mode admits, in k_shortest_walks' order, cut at
+ * max_paths walks per row (pgq_k_shortest_groups); out_ngroups[i] = the distinct lengths among row i's walks.  Outputs and errors as
+ * pgq_udf_k_shortest_walks_mode; groups < 1 and max_paths < 1 are the device library's PGQ_ERR_INVALID_ARG */
+int pgq_udf_k_shortest_groups(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops,
+                              int64_t max_hops, int64_t groups, int64_t max_paths, int path_mode, uint64_t *out_first,
+                              uint64_t *out_npaths, uint64_t *out_ngroups, uint64_t *out_valid, const uint64_t **out_path_offset,
+                              const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
+                              uint64_t *out_child_len);
 /* *ret_type: PGQ_W_INT64 -> BIGINT result, PGQ_W_DOUBLE -> DOUBLE result */
 int pgq_udf_bind_cheapest(pgq_state_t *, int32_t id, int *ret_type);
 int pgq_udf_cheapest_path_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
