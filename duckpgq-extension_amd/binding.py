@@ -43,6 +43,30 @@ def build_native(force=False):
     subprocess.check_call(args)
 
 
+# The C signatures of the walk family (include/pgq_hip.h, include/pgq_udf.h), in pieces: the rows, the form's scalars, its per-row
+# outputs, and for a list form the nested lists.
+_P, _I = C.c_void_p, C.c_int64
+_CHUNK_ROWS = (_P, _I, _I, Vec, Vec)  # csr, V, n, src, dst (the UDFs: state and id in the handle's place)
+_BULK_ROWS = (_P, _I, _P, _P)  # csr, n, d_src, d_dst
+# out_path_offset, out_path_length, out_path_total, out_child, out_child_len
+_CHUNK_LISTS = (C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P), C.POINTER(C.c_uint64))
+# d_path_offset, d_path_hops, path_cap, d_child, child_cap, paths_used, child_used
+_BULK_LISTS = (_P, _P, _I, _P, _I, C.POINTER(_I), C.POINTER(_I))
+# name -> (scalars, per-row outputs of the chunk form, of the bulk form, a list form?)
+_WALK_FORMS = {"walk_count": ((_I, _I), 2, 1, False),
+               "k_shortest_walks": ((_I, _I, _I), 3, 4, True),
+               "walk_count_mode": ((_I, _I, _I, C.c_int), 2, 1, False),
+               "k_shortest_walks_mode": ((_I, _I, _I, C.c_int), 3, 4, True),
+               "k_shortest_groups": ((_I, _I, _I, _I, C.c_int), 4, 5, True)}
+
+
+def _walk_argtypes(L, prefix, rows, bulk):
+    for name, (scalars, chunk_outs, bulk_outs, lists) in _WALK_FORMS.items():
+        getattr(L, prefix + name).argtypes = list(rows + scalars + (_P,) * chunk_outs + (_CHUNK_LISTS if lists else ()))
+        if bulk:
+            getattr(L, prefix + name + "_bulk_device").argtypes = list(_BULK_ROWS + scalars + (_P,) * bulk_outs + (_BULK_LISTS if lists else ()))
+
+
 _hip = None
 _udf = None
 
@@ -124,32 +148,8 @@ def load_hip():
     L.pgq_all_shortestpaths_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                     C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.pgq_walk_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    L.pgq_walk_count_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-    L.pgq_k_shortest_walks.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
-                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pgq_k_shortest_walks_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.pgq_walk_count_mode.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
-                                      C.c_void_p]
-    L.pgq_walk_count_mode_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                                  C.c_void_p]
-    L.pgq_k_shortest_walks_mode.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
-                                            C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pgq_k_shortest_walks_mode_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    _walk_argtypes(L, "pgq_", _CHUNK_ROWS, True)
     L.pgq_debug_mode_steps.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.pgq_k_shortest_groups.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                        C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pgq_k_shortest_groups_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
-                                                    C.POINTER(C.c_int64)]
     L.pgq_local_clustering_coefficient.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_local_clustering_coefficient_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_pagerank.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, C.c_void_p, C.c_void_p]
@@ -209,19 +209,7 @@ def load_udf():
     L.pgq_udf_all_shortestpaths.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pgq_udf_walk_count.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p,
-                                     C.c_void_p]
-    L.pgq_udf_k_shortest_walks.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                           C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pgq_udf_walk_count_mode.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                          C.c_void_p, C.c_void_p]
-    L.pgq_udf_k_shortest_walks_mode.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                                C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    L.pgq_udf_k_shortest_groups.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                            C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    _walk_argtypes(L, "pgq_udf_", (C.c_void_p, C.c_int32) + _CHUNK_ROWS[1:], False)
     L.pgq_udf_bind_cheapest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
     L.pgq_udf_cheapest_path.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -807,12 +795,15 @@ class DeviceCSR:
     def all_shortestpaths_bulk_ptr(self, n, d_src, d_dst, max_hops, max_paths, d_out_len, d_out_count, d_out_first, d_out_npaths,
                                    d_path_offset, path_cap, d_child, child_cap):
         """(status, paths needed, elements needed): the capacity protocol of shortestpath_bulk_ptr for both buffers."""
+        return self._lists_bulk(self.L.pgq_all_shortestpaths_bulk_device, n, d_src, d_dst, (max_hops, max_paths),
+                                (d_out_len, d_out_count, d_out_first, d_out_npaths, d_path_offset), path_cap, d_child, child_cap)
+
+    def _lists_bulk(self, fn, n, d_src, d_dst, scalars, arrays, path_cap, d_child, child_cap):
+        """A bulk list form: fn(handle, n, d_src, d_dst, the scalars, the device arrays, path_cap, d_child, child_cap, &lists,
+        &elements) -> (status, lists needed, elements needed)."""
         paths, used = C.c_int64(0), C.c_int64(0)
-        rc = self.L.pgq_all_shortestpaths_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(max_hops),
-                                                      int(max_paths), C.c_void_p(d_out_len), C.c_void_p(d_out_count),
-                                                      C.c_void_p(d_out_first), C.c_void_p(d_out_npaths),
-                                                      C.c_void_p(d_path_offset), path_cap, C.c_void_p(d_child), child_cap,
-                                                      C.byref(paths), C.byref(used))
+        rc = fn(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), *[int(x) for x in scalars], *[C.c_void_p(a) for a in arrays], path_cap,
+                C.c_void_p(d_child), child_cap, C.byref(paths), C.byref(used))
         return rc, paths.value, used.value
 
     def walk_count_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, d_out_count):
@@ -822,13 +813,8 @@ class DeviceCSR:
     def k_shortest_walks_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, k, d_out_len, d_out_count, d_out_first, d_out_npaths,
                                   d_path_offset, d_path_hops, path_cap, d_child, child_cap):
         """(status, walks needed, elements needed): the capacity protocol of all_shortestpaths_bulk_ptr."""
-        paths, used = C.c_int64(0), C.c_int64(0)
-        rc = self.L.pgq_k_shortest_walks_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
-                                                     int(k), C.c_void_p(d_out_len), C.c_void_p(d_out_count),
-                                                     C.c_void_p(d_out_first), C.c_void_p(d_out_npaths), C.c_void_p(d_path_offset),
-                                                     C.c_void_p(d_path_hops), path_cap, C.c_void_p(d_child), child_cap,
-                                                     C.byref(paths), C.byref(used))
-        return rc, paths.value, used.value
+        return self._lists_bulk(self.L.pgq_k_shortest_walks_bulk_device, n, d_src, d_dst, (min_hops, max_hops, k),
+                                (d_out_len, d_out_count, d_out_first, d_out_npaths, d_path_offset, d_path_hops), path_cap, d_child, child_cap)
 
     def walk_count_mode_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, limit, path_mode, d_out_count):
         _check(self.L.pgq_walk_count_mode_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
@@ -837,25 +823,16 @@ class DeviceCSR:
     def k_shortest_walks_mode_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, k, path_mode, d_out_len, d_out_count, d_out_first,
                                        d_out_npaths, d_path_offset, d_path_hops, path_cap, d_child, child_cap):
         """(status, walks needed, elements needed): k_shortest_walks_bulk_ptr under a path mode."""
-        paths, used = C.c_int64(0), C.c_int64(0)
-        rc = self.L.pgq_k_shortest_walks_mode_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
-                                                          int(k), int(path_mode), C.c_void_p(d_out_len), C.c_void_p(d_out_count),
-                                                          C.c_void_p(d_out_first), C.c_void_p(d_out_npaths),
-                                                          C.c_void_p(d_path_offset), C.c_void_p(d_path_hops), path_cap,
-                                                          C.c_void_p(d_child), child_cap, C.byref(paths), C.byref(used))
-        return rc, paths.value, used.value
+        return self._lists_bulk(self.L.pgq_k_shortest_walks_mode_bulk_device, n, d_src, d_dst, (min_hops, max_hops, k, path_mode),
+                                (d_out_len, d_out_count, d_out_first, d_out_npaths, d_path_offset, d_path_hops), path_cap, d_child, child_cap)
 
     def k_shortest_groups_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, groups, max_paths, path_mode, d_out_len, d_out_count,
                                    d_out_first, d_out_npaths, d_out_ngroups, d_path_offset, d_path_hops, path_cap, d_child, child_cap):
         """(status, walks needed, elements needed): k_shortest_walks_mode_bulk_ptr with groups and max_paths in k's place and the
         groups per row behind d_out_npaths."""
-        paths, used = C.c_int64(0), C.c_int64(0)
-        rc = self.L.pgq_k_shortest_groups_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
-                                                      int(groups), int(max_paths), int(path_mode), C.c_void_p(d_out_len),
-                                                      C.c_void_p(d_out_count), C.c_void_p(d_out_first), C.c_void_p(d_out_npaths),
-                                                      C.c_void_p(d_out_ngroups), C.c_void_p(d_path_offset), C.c_void_p(d_path_hops),
-                                                      path_cap, C.c_void_p(d_child), child_cap, C.byref(paths), C.byref(used))
-        return rc, paths.value, used.value
+        return self._lists_bulk(self.L.pgq_k_shortest_groups_bulk_device, n, d_src, d_dst, (min_hops, max_hops, groups, max_paths, path_mode),
+                                (d_out_len, d_out_count, d_out_first, d_out_npaths, d_out_ngroups, d_path_offset, d_path_hops), path_cap, d_child,
+                                child_cap)
 
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
@@ -925,11 +902,16 @@ class PgqState:
     def bind_search(self, csr_id):
         self._ck(self.U.pgq_udf_bind_search(self.s, csr_id))
 
-    def _search(self, fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out):
+    @staticmethod
+    def _rows(src, dst, src_valid, dst_valid, src_sel, dst_sel):
+        """(n, the src vector, the dst vector, what keeps their memory alive) of a search call's rows"""
         keep = []
         sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
         dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
-        n = len(src_sel) if src_sel is not None else len(src)
+        return (len(src_sel) if src_sel is not None else len(src)), sv, dv, keep
+
+    def _search(self, fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out):
+        n, sv, dv, _keep = self._rows(src, dst, src_valid, dst_valid, src_sel, dst_sel)
         ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
         self._ck(fn(self.s, csr_id, V, n, sv, dv, _p(out), _p(ov)))
         return unpack_validity(ov, n)
@@ -995,10 +977,7 @@ class PgqState:
 
     def all_shortestpaths(self, csr_id, V, src, dst, max_hops, max_paths, src_valid=None, dst_valid=None, src_sel=None,
                           dst_sel=None, raw=False):
-        keep = []
-        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
-        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
-        n = len(src_sel) if src_sel is not None else len(src)
+        n, sv, dv, _keep = self._rows(src, dst, src_valid, dst_valid, src_sel, dst_sel)
 
         def call(*outs):
             self._ck(self.U.pgq_udf_all_shortestpaths(self.s, csr_id, V, n, sv, dv, int(max_hops), int(max_paths), *outs))
@@ -1023,10 +1002,7 @@ class PgqState:
 
     def k_shortest_walks(self, csr_id, V, src, dst, min_hops, max_hops, k, src_valid=None, dst_valid=None, src_sel=None,
                          dst_sel=None, raw=False, path_mode=None):
-        keep = []
-        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
-        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
-        n = len(src_sel) if src_sel is not None else len(src)
+        n, sv, dv, _keep = self._rows(src, dst, src_valid, dst_valid, src_sel, dst_sel)
 
         def call(*outs):
             if path_mode is not None:
@@ -1038,10 +1014,7 @@ class PgqState:
 
     def k_shortest_groups(self, csr_id, V, src, dst, min_hops, max_hops, groups, max_paths, path_mode=0, src_valid=None,
                           dst_valid=None, src_sel=None, dst_sel=None, raw=False):
-        keep = []
-        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
-        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
-        n = len(src_sel) if src_sel is not None else len(src)
+        n, sv, dv, _keep = self._rows(src, dst, src_valid, dst_valid, src_sel, dst_sel)
 
         def call(*outs):
             self._ck(self.U.pgq_udf_k_shortest_groups(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), int(groups),

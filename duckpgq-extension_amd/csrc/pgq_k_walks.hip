@@ -40,11 +40,12 @@
 //   2. k_walk_pull, behind it: a wavefront per queued n reads n's in-list 64 entries and 64 mask words at a time, ballots the
 //      neighbours with a non-empty M_{t-1}; lane l in M_t[n] saturating-adds W_{t-1}[u][l] where M_{t-1}[u] has bit l.  One plain
 //      store per (vertex, lane), no atomics on W: the same on every run.
-//   3. k_walk_after: for t >= lo a thread per row adds W_t[dst][lane] (0 where the mask bit is clear) to the row's count, notes the
-//      first length, counts the rows still short of k; walk_count: M_{t-1} back to zero over round t-1's queue.
-//   Rounds stop after round K, with an empty queue, and (lists) when no row of the batch is short of k: k = 1 on a pair d apart
+//   3. k_walk_after: for t >= lo a thread per row feeds the row W_t[dst][lane] (0 where the mask bit is clear) by the rule below,
+//      notes the first length, counts the rows still open; walk_count: M_{t-1} back to zero over round t-1's queue.
+//   Rounds stop after round K, with an empty queue, and (lists) when no row of the batch is open: k = 1 on a pair d apart
 //   costs d rounds.  walk_count has no such stop.  The host waits once per round for the counters.
-//   4. k_walk_plan, a thread per row: walks and elements per row from W_t[dst], t = lo..R; two exclusive scans place them.
+//   4. k_walk_plan, a thread per row: walks and elements per row from W_t[dst], t = lo..R, by the same rule; two exclusive scans
+//      place them.
 //   5. k_walk_unrank, a wavefront per emitted walk: its t by the same small loop, then unrank_step (pgq_path_lists.h) per step, with
 //      the weight W_{i-1}[u][l].  A step that finds no parent or no slot, or a walk that does not end on the lane's source, raises
 //      the error flag: PGQ_ERR_HIP.
@@ -53,23 +54,27 @@
 // The call owns its tables, masks and queues (block cache); it does not touch ws->tight_h / tight_mask / tight_q / tight_V, so
 // PathBatches and AspCall find them as they left them.  Lists are staged in ws->tight_stage, rows in ws->asp_rows.
 // Kernel-class time: the rounds are K_PUSH, plan / unranking / gather K_RECON.
-// The path modes TRAIL / ACYCLIC / SIMPLE (pgq_k_shortest_walks_mode, pgq_walk_count_mode) run these rounds with every table kept
-// and k_walk_after's stop by distance, then search each row over the tables: pgq_path_modes.h, included below, has the contract.
-// SHORTEST k GROUP (pgq_k_shortest_groups: every walk of a row's g smallest non-empty lengths, capped at P = max_paths) runs the same
-// rounds with k_walk_after's group rule — per row the groups seen and the saturating sum `cum` of their W_t[dst]; a row is open while
-// groups seen < g and cum <= P — and k_walk_plan's: min(W_t[dst], P - taken) from each non-empty length, a stop behind the g-th,
-// ngroups = the lengths emitted from, count = min(cum, P + 1).  A is a prefix of S, so a rank means the same walk: k_walk_unrank, the
-// staging and k_walk_gather serve as they are.  ngroups has a seventh row array (ListCall::r_ng), reserved for this call alone.
-// Under a mode the rows close by distance (g == 1 or W_d[dst] > P) and k_mode_search carries the group rule.
+// THE RULE.  Every entry point turns its arguments into one WalkQuery (walk_query, at the entry points), and when a row has enough
+// is decided in one place, pgq_walk_rule.h: a row is open while it has been fed fewer than G non-empty lengths and their saturating
+// sum is <= B.  SHORTEST k is G unbounded, B = k - 1; walk_count B = INT64_MAX - 1; SHORTEST k GROUP (pgq_k_shortest_groups: every
+// walk of a row's g smallest non-empty lengths, capped at P = max_paths) G = g, B = P.  k_walk_after feeds a row one round at a
+// time, k_walk_plan all rounds at once and takes min(W_t[dst], what is left of the limit) from each fed length; the groups' count
+// is min(sum, P + 1), their ngroups the lengths emitted from, in a seventh row array (ListCall::r_ng) reserved for that call.  A
+// group list is a prefix of S, so a rank means the same walk: k_walk_unrank, the staging and k_walk_gather serve every form.
+// The path modes TRAIL / ACYCLIC / SIMPLE (pgq_k_shortest_walks_mode, pgq_walk_count_mode, the groups under a mode) run the rounds
+// with every table kept and the rows closed by distance, then search each row over the tables, feeding it by the same rule one
+// admitted walk at a time: pgq_path_modes.h, included below, has the contract.
 // Not built: _multi forms, splitting long in-lists over several wavefronts (a list is walked by the one wavefront that meets it), any
 // change to how the binder's iterativelength filter is emitted; under a mode: an unbounded upper, an unlimited count, a smarter
 // prune than W, several wavefronts per row; for the groups: a count-only form.
+
+#include "pgq_walk_rule.h"
 
 namespace pgq {
 
 struct WalkCounters {
 	u32 nq[2];   // queued vertices by round parity
-	u32 pending; // rows of the batch short of k walks
+	u32 pending; // rows of the batch still open (pgq_walk_rule.h)
 	u32 error;   // unranking: no length / parent (2), no slot (4), not at the source (8)
 	u64 edges;   // adjacency entries the rounds walked
 	u64 steps;   // path modes: the steps of the batch's searches, both passes ...
@@ -164,107 +169,69 @@ __global__ __launch_bounds__(256) void k_walk_pull(const int64_t *__restrict__ r
 	}
 }
 
-// Round t is over: the rows' counts (a row that has k_stop walks adds no more), the rows still short of k_stop; m_zero != null
-// (walk_count's ping-pong): round t-1's mask words back to zero over its queue.
-// by_distance (the path modes): a mode may reject any walk longer than d = dist(src, dst), the first t >= 0 with W_t[dst] > 0, and
-// rejects none of length d.  r_len notes d; a row is closed (r_count = k_stop) when min_hops <= d and W_d[dst] >= k_stop, and every
-// other row stays open to the last round.  The search's counting pass overwrites both arrays.
-// groups > 0 (k_shortest_groups; k_stop is its max_paths P, r_ng the groups seen): a non-empty length t >= min_hops is a group and
-// adds to r_count, the saturating sum `cum`; a row is open while it has seen fewer than `groups` of them and cum <= P — not cum < P:
-// with cum == P on a boundary a later non-empty length still makes the row's count P + 1.  by_distance: the row is closed (r_count =
-// P + 1) at its distance d when min_hops <= d and either groups == 1 or W_d[dst] > P.  k_walk_plan / the search overwrite the arrays.
-__global__ void k_walk_after(int t, int64_t min_hops, int64_t k_stop, bool by_distance, int64_t groups, int64_t lo, int64_t hi, const u32 *__restrict__ skey,
-                             const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst, u32 base_lane, WalkRound cur, int64_t *__restrict__ r_len,
-                             int64_t *__restrict__ r_count, int64_t *__restrict__ r_ng, const int32_t *__restrict__ qprev, u64 *__restrict__ m_zero, int par_prev,
+// Round t is over.  A thread per row of the batch feeds the row W_t[dst] by the rule of pgq_walk_rule.h — state in r_count and,
+// for the groups, r_ng; r_len notes the first length fed — and counts the rows still open.  m_zero != null (walk_count's
+// ping-pong): round t-1's mask words back to zero over its queue.
+// by_distance (the path modes): r_len notes the distance d, the first t >= 0 with W_t[dst] > 0, whether or not d >= min_hops;
+// the row closes there or never (WalkRow::close_at_distance).  k_walk_plan / the search overwrite the arrays they own.
+__global__ void k_walk_after(int t, WalkQuery q, int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx,
+                             const int32_t *__restrict__ sdst, u32 base_lane, WalkRound cur, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count,
+                             int64_t *__restrict__ r_ng, const int32_t *__restrict__ qprev, u64 *__restrict__ m_zero, int par_prev,
                              WalkCounters *__restrict__ tc) {
 	const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (m_zero && tid < (int64_t)tc->nq[par_prev]) m_zero[qprev[tid]] = 0;
 	const int64_t i = lo + tid;
 	bool open = false;
 	if (i < hi) {
+		const WalkRule rule = q.rule();
 		const u32 row = sidx[i];
-		int64_t cnt = r_count[row];
-		if (by_distance) {
-			if (r_len[row] < 0) {
-				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
-				if (w > 0) {
-					r_len[row] = t;
-					if (groups > 0) {
-						if (t >= min_hops && (groups == 1 || w > k_stop)) r_count[row] = cnt = k_stop + 1; // (P <= 2^31)
-					} else if (t >= min_hops && w >= k_stop) {
-						r_count[row] = cnt = k_stop;
-					}
-				}
-			}
-			open = groups > 0 ? cnt <= k_stop : cnt < k_stop;
-		} else if (groups > 0) {
-			int64_t ng = r_ng[row];
-			if (t >= min_hops && ng < groups && cnt <= k_stop) {
-				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
-				if (w > 0) {
-					if (r_len[row] < 0) r_len[row] = t;
-					cnt = asp_sat_add(cnt, w);
-					r_count[row] = cnt;
-					r_ng[row] = ++ng;
-				}
-			}
-			open = ng < groups && cnt <= k_stop;
-		} else {
-			if (t >= min_hops && cnt < k_stop) {
-				const int64_t w = walk_w(cur, sdst[i], skey[i] - base_lane);
-				if (w > 0) {
-					if (r_len[row] < 0) r_len[row] = t;
-					cnt = asp_sat_add(cnt, w);
-					r_count[row] = cnt;
-				}
-			}
-			open = cnt < k_stop;
+		WalkRow s { r_count[row], !q.by_distance() && r_ng ? r_ng[row] : 0 };
+		// not read: by distance once the distance is known; otherwise below min_hops and for a closed row
+		const bool skip = q.by_distance() ? r_len[row] >= 0 : t < q.min_hops || !s.open(rule);
+		const int64_t w = skip ? 0 : walk_w(cur, sdst[i], skey[i] - base_lane);
+		if (w > 0) {
+			if (r_len[row] < 0) r_len[row] = t;
+			if (!q.by_distance()) s.add(w);
+			else if (t >= q.min_hops) s.close_at_distance(w, rule);
+			r_count[row] = s.count; // (by distance: B + 1 <= 2^31 + 1 or the count's limit)
+			if (!q.by_distance() && r_ng) r_ng[row] = s.groups;
 		}
+		open = s.open(rule);
 	}
 	const u64 om = __ballot(open);
 	if (om && (threadIdx.x & 63) == 0) atomicAdd(&tc->pending, (u32)__popcll(om));
 }
 
-// per row of the batch: the walks it emits and their elements; staged per row as [hops of each walk][the walks' elements]
+// per row of the batch: the walks it emits and their elements; staged per row as [hops of each walk][the walks' elements].  The
+// row is fed the lengths lo .. rounds by the rule and takes from each by WalkPlan.  The groups' count and groups are the plan's:
+// min(sum, P + 1) and the lengths emitted from.  SHORTEST k's r_count stays what the rounds left, the walks of lo..T edges.
 __global__ void k_walk_plan(int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx, const int32_t *__restrict__ sdst,
-                            u32 base_lane, const WalkRound *__restrict__ tabs, int64_t min_hops, int rounds, int64_t k, int64_t groups,
-                            int64_t *__restrict__ r_np, int64_t *__restrict__ r_el, int64_t *__restrict__ r_count, int64_t *__restrict__ r_ng,
-                            int64_t *__restrict__ cntp, int64_t *__restrict__ cnte) {
+                            u32 base_lane, const WalkRound *__restrict__ tabs, WalkQuery q, int rounds, int64_t *__restrict__ r_np,
+                            int64_t *__restrict__ r_el, int64_t *__restrict__ r_count, int64_t *__restrict__ r_ng, int64_t *__restrict__ cntp,
+                            int64_t *__restrict__ cnte) {
 	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= hi) return;
 	const int x = sdst[i];
 	const u32 l = skey[i] - base_lane;
 	const u32 row = sidx[i];
-	int64_t rem = k, np = 0, el = 0;
-	if (groups > 0) {
-		// k_shortest_groups, k = max_paths: the first `groups` non-empty lengths, cut at k walks (inside a group too).  The row's
-		// groups are the lengths it emits from; its count the walks of the planned lengths, capped at k + 1.
-		int64_t planned = 0, emitted = 0, cum = 0;
-		for (int64_t t = min_hops; t <= rounds && planned < groups; t++) {
-			const int64_t w = walk_w(tabs[t], x, l);
-			if (w <= 0) continue;
-			planned++;
-			cum = asp_sat_add(cum, w);
-			const int64_t take = min(w, rem);
-			if (take > 0) emitted++;
-			np += take;
-			el += take * (2 * t + 1);
-			rem -= take;
-		}
-		r_count[row] = min(cum, k + 1); // (k <= 2^31)
-		r_ng[row] = emitted;
-	} else {
-		for (int64_t t = min_hops; t <= rounds && rem > 0; t++) {
-			const int64_t take = min(walk_w(tabs[t], x, l), rem);
-			np += take;
-			el += take * (2 * t + 1); // take <= 2^31, 2 t + 1 <= 129
-			rem -= take;
-		}
+	const WalkRule rule = q.rule();
+	WalkRow s;
+	WalkPlan plan;
+	for (int64_t t = q.min_hops; t <= rounds && s.open(rule); t++) { // (SHORTEST k: open is "fewer than k taken")
+		const int64_t w = walk_w(tabs[t], x, l);
+		if (w <= 0) continue;
+		plan.take(s, q.limit, t, w);
+		s.add(w);
 	}
+	if (q.groups > 0) {
+		r_count[row] = min(s.count, rule.bound + 1); // (P <= 2^31)
+		r_ng[row] = plan.ngroups;
+	}
+	const int64_t np = WalkPlan::np(s, q.limit);
 	r_np[row] = np;
-	r_el[row] = el;
+	r_el[row] = plan.el;
 	cntp[i - lo] = np;
-	cnte[i - lo] = np > 0 ? np + el : 0;
+	cnte[i - lo] = np > 0 ? np + plan.el : 0;
 }
 
 // One wavefront per emitted walk (row, rank): its length, then the list, written back to front into the row's staged block.
@@ -272,7 +239,7 @@ __global__ __launch_bounds__(64) void k_walk_unrank(int64_t lo, int64_t m, int64
                                                    u32 base_lane, const int32_t *__restrict__ usrc, const int64_t *__restrict__ off,
                                                    const int32_t *__restrict__ adj, const int64_t *__restrict__ edge_ids,
                                                    const int64_t *__restrict__ roff, const int32_t *__restrict__ radj,
-                                                   const WalkRound *__restrict__ tabs, int64_t min_hops, int rounds,
+                                                   const WalkRound *__restrict__ tabs, WalkQuery q, int rounds,
                                                    const int64_t *__restrict__ ploc, const int64_t *__restrict__ eloc, int64_t stage_base,
                                                    int64_t *__restrict__ stage, int64_t *__restrict__ soff, WalkCounters *__restrict__ tc) {
 	const int lane = threadIdx.x;
@@ -286,7 +253,7 @@ __global__ __launch_bounds__(64) void k_walk_unrank(int64_t lo, int64_t m, int64
 		// the walk's length: the shorter lengths' walks come first
 		int64_t eoff = 0;
 		int t = -1;
-		for (int64_t tt = min_hops; tt <= rounds; tt++) {
+		for (int64_t tt = q.min_hops; tt <= rounds; tt++) {
 			const int64_t w = walk_w(tabs[tt], x, l);
 			if (r < w) {
 				t = (int)tt;
@@ -387,19 +354,17 @@ static ModeSteps &mode_steps() {
 // The walk rounds of the lane batches on ListCall's skeleton (pgq_path_lists.h): its run, emit and layout.
 class WalkCall : ListCall {
 public:
-	// mode: 0 for the walks themselves, or PGQ_MODE_SIMPLE / _TRAIL / _ACYCLIC: then out.limit is k (lists) or the count's limit,
-	// every round's table is kept, the rounds stop by distance and the rows are searched (pgq_path_modes.h)
-	// groups > 0: k_shortest_groups — out.limit is max_paths, out.d_ng is set, the rounds and the search stop by groups
-	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, ListOut &out, int mode = 0,
-	         int64_t groups = 0)
-	    : ListCall(c, ws, n, d_src, d_dst, out, groups ? "k_shortest_groups" : mode ? "k_shortest_walks_mode" : "k_shortest_walks", "walks"), min_hops(min_hops),
-	      max_hops(max_hops), mode(mode), groups(groups), keep_rounds(out.lists || mode != 0), step_cap(std::max(options().mode_step_cap, 0)), temps(ws->stream) {}
+	// q.mode != 0: every round's table is kept, the rounds stop by distance and the rows are searched (pgq_path_modes.h).
+	// q.groups > 0: k_shortest_groups — out.d_ng is set.  The call's limit is q.limit, not out.limit.
+	WalkCall(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const WalkQuery &q, ListOut &out)
+	    : ListCall(c, ws, n, d_src, d_dst, out, q.groups ? "k_shortest_groups" : q.mode ? "k_shortest_walks_mode" : "k_shortest_walks", "walks"), query(q),
+	      keep_rounds(out.lists || q.mode != 0), step_cap(std::max(options().mode_step_cap, 0)), temps(ws->stream) {}
 
 	int run() {
 		return ListCall::run(
 		    true, [&] { return prepare(); }, [&](int64_t lo, int64_t hi, int64_t base, u32 U) { return batch(lo, hi, base, U); },
 		    [&](int nb) {
-			    return layout(nb, min_hops, [&](int64_t lo_t, int64_t lo_n, int64_t *path_off, int64_t *path_len, int64_t *child) {
+			    return layout(nb, query.min_hops, [&](int64_t lo_t, int64_t lo_n, int64_t *path_off, int64_t *path_len, int64_t *child) {
 				    hipLaunchKernelGGL(k_walk_gather, dim3((unsigned)std::min<int64_t>(lo_n, 1 << 20)), dim3(64), 0, st, lo_t, lo_n, ws->sidx.as<u32>(),
 				                       ws->sdst.as<int32_t>(), r_np, r_el, r_first, r_eoff, ws->soff.as<int64_t>(), ws->tight_stage.as<int64_t>(), path_off,
 				                       out.d_path_hops, path_len, child);
@@ -408,9 +373,7 @@ public:
 	}
 
 private:
-	const int64_t min_hops, max_hops;
-	const int mode;
-	const int64_t groups; // 0, or SHORTEST k GROUP's k
+	const WalkQuery query;
 	const bool keep_rounds; // a table per round (the unranking, the search) instead of walk_count's two
 	const int64_t step_cap; // path modes: steps a row's search may take per pass
 	uint64_t steps_seen = 0; // ... the batch's steps already booked
@@ -440,7 +403,7 @@ private:
 	int prepare() {
 		PGQ_TRY(ws->tight_cnt.reserve(std::max(sizeof(WalkCounters), sizeof(TightCounters))));
 		tc = ws->tight_cnt.as<WalkCounters>();
-		if (out.lists || mode == PGQ_MODE_TRAIL) PGQ_TRY(ensure_edge_ids(c));
+		if (out.lists || query.mode == PGQ_MODE_TRAIL) PGQ_TRY(ensure_edge_ids(c));
 		if (keep_rounds) PGQ_TRY(temps.alloc(&d_tabs, (size_t)PGQ_WALK_MAX_HOPS + 1));
 		for (int32_t *&b : q) PGQ_TRY(temps.alloc(&b, Vn));
 		return PGQ_OK;
@@ -450,7 +413,6 @@ private:
 	int batch(int64_t lo, int64_t hi, int64_t base, u32 U) {
 		const int64_t m = hi - lo;
 		const unsigned cus = (unsigned)device_cus();
-		const int64_t k_stop = keep_rounds ? out.limit : kAspMax;
 		const u32 *skey = ws->skey.as<u32>(), *sidx = ws->sidx.as<u32>();
 		const int32_t *sdst = ws->sdst.as<int32_t>();
 		WalkCounters h {};
@@ -462,14 +424,14 @@ private:
 			KernelTimer kt(st, K_PUSH);
 			hipLaunchKernelGGL(k_walk_init, dim3(1), dim3(64), 0, st, ws->usrc.as<int32_t>(), (int64_t)U, base, W[0], M[0], q[0], tc);
 			if (m > 0) hipLaunchKernelGGL(k_walk_rows, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, sidx, r_len, r_count, r_ng);
-			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, min_hops, k_stop, mode != 0, groups, lo, hi, skey, sidx, sdst,
-			                   (u32)base, round_of(0), r_len, r_count, r_ng, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, 1))), dim3(256), 0, st, 0, query, lo, hi, skey, sidx, sdst, (u32)base,
+			                   round_of(0), r_len, r_count, r_ng, (const int32_t *)nullptr, (u64 *)nullptr, 0, tc);
 			kt.stop();
 		}
 		PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 		int par = 0;
 		int rounds = 0;
-		for (int64_t t = 1; t <= max_hops && nq > 0 && m > 0 && !(keep_rounds && h.pending == 0); t++) {
+		for (int64_t t = 1; t <= query.max_hops && nq > 0 && m > 0 && !(keep_rounds && h.pending == 0); t++) {
 			PGQ_TRY(ensure_round(t));
 			KernelTimer kt(st, K_PUSH);
 			const WalkRound prev = round_of(t - 1), cur = round_of(t);
@@ -478,8 +440,8 @@ private:
 			                   q[par ^ 1], tc, par);
 			// (the new queue's fill is not known here: the grid is sized for a queue of any size, its wavefronts stride)
 			hipLaunchKernelGGL(k_walk_pull, dim3(cus * 8), dim3(256), 0, st, c->roff, c->radj, prev.W, prev.M, W[slot_of(t)], cur.M, q[par ^ 1], tc, par ^ 1);
-			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, min_hops, k_stop, mode != 0, groups, lo, hi, skey, sidx, sdst,
-			                   (u32)base, cur, r_len, r_count, r_ng, (const int32_t *)q[par], keep_rounds ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
+			hipLaunchKernelGGL(k_walk_after, dim3(blocks_for(std::max<int64_t>(m, nq))), dim3(256), 0, st, (int)t, query, lo, hi, skey, sidx, sdst, (u32)base,
+			                   cur, r_len, r_count, r_ng, (const int32_t *)q[par], keep_rounds ? (u64 *)nullptr : M[slot_of(t - 1)], par, tc);
 			kt.stop();
 			PGQ_TRY(stage.read_back(&h, tc, sizeof(h)));
 			S.levels++;
@@ -494,16 +456,16 @@ private:
 		h_tabs.assign((size_t)PGQ_WALK_MAX_HOPS + 1, WalkRound { nullptr, nullptr });
 		for (int t = 0; t <= rounds; t++) h_tabs[t] = round_of(t);
 		PGQ_HIP_TRY(hipMemcpyAsync(d_tabs, h_tabs.data(), h_tabs.size() * sizeof(WalkRound), hipMemcpyHostToDevice, st));
-		if (mode) return search(lo, m, (u32)base, rounds);
+		if (query.mode) return search(lo, m, (u32)base, rounds);
 		PGQ_TRY(emit(
 		    m,
 		    [&](int64_t *cntp, int64_t *cnte) {
-			    hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, min_hops, rounds, out.limit, groups,
-			                       r_np, r_el, r_count, r_ng, cntp, cnte);
+			    hipLaunchKernelGGL(k_walk_plan, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, skey, sidx, sdst, (u32)base, d_tabs, query, rounds, r_np,
+			                       r_el, r_count, r_ng, cntp, cnte);
 		    },
 		    [&](int64_t nwalks, const int64_t *ploc, const int64_t *eloc, int64_t at) {
 			    hipLaunchKernelGGL(k_walk_unrank, dim3((unsigned)std::min<int64_t>(nwalks, 1 << 20)), dim3(64), 0, st, lo, m, nwalks, skey, sdst, (u32)base,
-			                       ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, min_hops, rounds, ploc, eloc, at,
+			                       ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, query, rounds, ploc, eloc, at,
 			                       ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
 		    }));
 		PGQ_TRY(stage.read_back(&h, tc, sizeof(h))); // (also: the next batch's memsets and table upload come behind this batch's kernels)
@@ -514,8 +476,8 @@ private:
 	// plan step; the count form ends behind it.
 	template <bool EMIT> void launch_search(int64_t lo, int64_t m, u32 base, int rounds, int64_t *cntp, int64_t *cnte, const int64_t *ploc, const int64_t *eloc, int64_t at) {
 		hipLaunchKernelGGL(k_mode_search<EMIT>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, m, ws->skey.as<u32>(), ws->sidx.as<u32>(),
-		                   ws->sdst.as<int32_t>(), base, ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, mode, min_hops, rounds, out.limit,
-		                   groups, step_cap, r_len, r_count, r_np, r_el, r_ng, cntp, cnte, ploc, eloc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+		                   ws->sdst.as<int32_t>(), base, ws->usrc.as<int32_t>(), c->off, c->adj, c->edge_ids, c->roff, c->radj, d_tabs, query, rounds, step_cap,
+		                   r_len, r_count, r_np, r_el, r_ng, cntp, cnte, ploc, eloc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
 	}
 	// what a pass left in the batch's counters: its steps booked, the step cap and the search's own errors reported
 	int search_status() {
@@ -547,226 +509,193 @@ private:
 	}
 };
 
-} // namespace pgq
-
-using namespace pgq;
-
-extern "C" {
-
-static int walk_check_bounds(int64_t min_hops, int64_t max_hops, const int64_t *k, const char *k_name = "k") {
-	if (min_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "min_hops must not be negative");
-	if (max_hops < min_hops) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be below min_hops");
-	if (k && *k < 1) return fail(PGQ_ERR_INVALID_ARG, std::string(k_name) + " must be at least 1");
-	if (max_hops > PGQ_WALK_MAX_HOPS)
-		return fail(PGQ_ERR_UNSUPPORTED, "walks need an upper bound of at most " + std::to_string(PGQ_WALK_MAX_HOPS) +
-		                                     " edges: in a cyclic graph the number of walks is unbounded");
-	return PGQ_OK;
-}
-
-int pgq_walk_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops,
-                               int64_t *d_out_count) {
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_count, "NULL device array"));
-		return walk_check_bounds(min_hops, max_hops, nullptr);
-	};
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		ListOut out;
-		out.d_count = d_out_count;
-		return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, out).run();
-	});
-}
-
-int pgq_k_shortest_walks_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t k,
-                                     int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths, int64_t *d_path_offset,
-                                     int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used, int64_t *child_used) {
-	if (paths_used) *paths_used = 0;
-	if (child_used) *child_used = 0;
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_len && d_out_count && d_out_first && d_out_npaths && d_path_offset && d_path_hops && d_child,
-		                     "NULL device array"));
-		if (path_cap < 0 || child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
-		return walk_check_bounds(min_hops, max_hops, &k);
-	};
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		ListOut out;
-		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths;
-		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
-		return list_bulk_body(out, k, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o).run(); }, paths_used, child_used);
-	});
-}
-
-int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t *out_count,
-                   uint64_t *out_valid) {
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&] { return count_chunk_check(csr, V, n, out_count, out_valid, [&] { return walk_check_bounds(min_hops, max_hops, nullptr); }); };
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		auto run = [&](ListOut &o, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o).run(); };
-		return count_chunk_body(ws, V, n, src, dst, run, out_count, out_valid);
-	});
-}
-
-int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t k,
-                         uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
-                         uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len };
-	auto check = [&] { return list_chunk_check(csr, V, n, o, [&] { return walk_check_bounds(min_hops, max_hops, &k); }); };
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo).run(); };
-		return list_chunk_body(ws, V, n, src, dst, k, run, o);
-	});
-}
-
-// ---- the path modes ------------------------------------------------------------------------------------------------------------
-
 // min(count, limit) over n counts, -1 (NULL) kept: pgq_walk_count_mode under NONE / WALK
 __global__ void k_walk_clamp(int64_t n, int64_t limit, int64_t *__restrict__ count) {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n && count[i] > limit) count[i] = limit;
 }
 
-static bool mode_is_walk(int path_mode) { return path_mode == PGQ_MODE_NONE || path_mode == PGQ_MODE_WALK; }
-// a NULL handle, the mode's number, then the bounds; an unbounded upper is not built under a mode either
-static int mode_check(const pgq_csr *csr, int path_mode, int64_t min_hops, int64_t max_hops, const int64_t *k, const char *k_name) {
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	if (path_mode < PGQ_MODE_NONE || path_mode > PGQ_MODE_ACYCLIC)
-		return fail(PGQ_ERR_INVALID_ARG, "path_mode must be PGQ_MODE_NONE, _WALK, _SIMPLE, _TRAIL or _ACYCLIC (0 .. 4)");
-	return walk_check_bounds(min_hops, max_hops, k, k_name);
+} // namespace pgq
+
+using namespace pgq;
+
+// ---- the C entry points: each is its argument list, a query and one of the helpers below -----------------------------------------
+
+// what a form's q.limit is, for the error text: k (the list forms), the count's limit, max_paths beside the groups
+enum WalkForm { kWalkK, kWalkLimit, kWalkGroups };
+
+// The call's arguments as the query.  path_mode: null for the entry points that have none.  NONE / WALK become mode 0 here and
+// nowhere else; any other number is kept, for walk_check to refuse.  A call that has a path_mode starts the thread's step counts
+// (pgq_debug_mode_steps) afresh, whatever becomes of it.
+static WalkQuery walk_query(int64_t min_hops, int64_t max_hops, const int *path_mode, int64_t groups, int64_t limit) {
+	if (path_mode) mode_steps() = ModeSteps {};
+	const bool walks = !path_mode || *path_mode == PGQ_MODE_NONE || *path_mode == PGQ_MODE_WALK;
+	return WalkQuery { min_hops, max_hops, groups, limit, walks ? 0 : *path_mode };
 }
-// the count form's run: the search's counting pass, or the walks' count cut at the limit
-static int count_mode_run(pgq_csr *csr, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t limit,
-                          int path_mode, ListOut &o) {
-	if (!mode_is_walk(path_mode)) {
-		o.limit = limit;
-		return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o, path_mode).run();
-	}
-	PGQ_TRY(WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o).run());
+
+// the mode's number, the bounds, the limit, the groups; an unbounded upper is not built under a mode either
+static int walk_check(const WalkQuery &q, WalkForm form) {
+	static const char *const limit_name[] = { "k", "limit", "max_paths" };
+	if (q.mode < 0 || q.mode > PGQ_MODE_ACYCLIC) return fail(PGQ_ERR_INVALID_ARG, "path_mode must be PGQ_MODE_NONE, _WALK, _SIMPLE, _TRAIL or _ACYCLIC (0 .. 4)");
+	if (q.min_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "min_hops must not be negative");
+	if (q.max_hops < q.min_hops) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be below min_hops");
+	if (q.limit < 1) return fail(PGQ_ERR_INVALID_ARG, std::string(limit_name[form]) + " must be at least 1");
+	if (q.max_hops > PGQ_WALK_MAX_HOPS)
+		return fail(PGQ_ERR_UNSUPPORTED, "walks need an upper bound of at most " + std::to_string(PGQ_WALK_MAX_HOPS) +
+		                                     " edges: in a cyclic graph the number of walks is unbounded");
+	if (form == kWalkGroups && q.groups < 1) return fail(PGQ_ERR_INVALID_ARG, "groups must be at least 1");
+	return PGQ_OK;
+}
+
+// The count forms' run.  Under a mode: the search's counting pass.  The walks themselves: their rounds have no limit, the count
+// is cut at q.limit behind them (pgq_walk_count asks with INT64_MAX: nothing to cut).
+static int walk_count_run(pgq_csr *csr, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, WalkQuery q, ListOut &o) {
+	const int64_t limit = q.limit;
+	if (!q.mode) q.limit = kWalkMax;
+	PGQ_TRY(WalkCall(csr, ws, n, d_src, d_dst, q, o).run());
+	if (q.mode || limit == kWalkMax) return PGQ_OK;
 	if (n > 0) hipLaunchKernelGGL(k_walk_clamp, dim3(blocks_for(n)), dim3(256), 0, ws->stream, n, limit, o.d_count);
 	PGQ_HIP_TRY(hipStreamSynchronize(ws->stream));
 	return PGQ_OK;
 }
-
-int pgq_walk_count_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t limit,
-                                    int path_mode, int64_t *d_out_count) {
-	mode_steps() = ModeSteps {};
+static int walk_count_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, const WalkQuery &q, int64_t *d_out_count) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	auto check = [&]() -> int {
 		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_count, "NULL device array"));
-		return mode_check(csr, path_mode, min_hops, max_hops, &limit, "limit");
+		return walk_check(q, kWalkLimit);
 	};
 	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
 		ListOut out;
 		out.d_count = d_out_count;
-		return count_mode_run(csr, ws, n, d_src, d_dst, min_hops, max_hops, limit, path_mode, out);
+		return walk_count_run(csr, ws, n, d_src, d_dst, q, out);
 	});
+}
+static int walk_count_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, const WalkQuery &q, int64_t *out_count, uint64_t *out_valid) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&] { return count_chunk_check(csr, V, n, out_count, out_valid, [&] { return walk_check(q, kWalkLimit); }); };
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		auto run = [&](ListOut &o, const int64_t *d_src, const int64_t *d_dst) { return walk_count_run(csr, ws, n, d_src, d_dst, q, o); };
+		return count_chunk_body(ws, V, n, src, dst, run, out_count, out_valid);
+	});
+}
+
+// The bulk list forms: `out` arrives with the caller's arrays and capacities (d_ng: the groups' form alone).
+static int walk_lists_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, WalkQuery q, WalkForm form, ListOut out, int64_t *paths_used,
+                           int64_t *child_used) {
+	if (paths_used) *paths_used = 0;
+	if (child_used) *child_used = 0;
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	auto check = [&]() -> int {
+		const bool arrays = d_src && d_dst && out.d_len && out.d_count && out.d_first && out.d_np && (out.d_ng || form != kWalkGroups) && out.d_path_off &&
+		                    out.d_path_hops && out.d_child;
+		PGQ_TRY(check_arrays(csr, n, arrays, "NULL device array"));
+		if (out.path_cap < 0 || out.child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
+		return walk_check(q, form);
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		q.limit = std::min<int64_t>(q.limit, 1LL << 31);
+		return list_bulk_body(out, q.limit, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, q, o).run(); }, paths_used, child_used);
+	});
+}
+// the ListOut of a bulk list form's arguments
+static ListOut walk_bulk_out(int64_t *d_len, int64_t *d_count, int64_t *d_first, int64_t *d_np, int64_t *d_ng, int64_t *d_path_off, int64_t *d_path_hops,
+                             int64_t path_cap, int64_t *d_child, int64_t child_cap) {
+	ListOut out;
+	out.d_len = d_len, out.d_count = d_count, out.d_first = d_first, out.d_np = d_np, out.d_ng = d_ng;
+	out.d_path_off = d_path_off, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
+	return out;
+}
+
+// The chunk list forms (o.ngroups: the groups' form alone).
+static int walk_lists_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, WalkQuery q, WalkForm form, ListChunkOut o) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	uint64_t no_rows = 0; // (the groups' form with n == 0: nothing is written through it)
+	const bool no_groups_out = form == kWalkGroups && !o.ngroups;
+	if (no_groups_out) o.ngroups = &no_rows;
+	auto check = [&] {
+		return list_chunk_check(csr, V, n, o, [&]() -> int {
+			if (n > 0 && no_groups_out) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
+			return walk_check(q, form);
+		});
+	};
+	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
+		q.limit = std::min<int64_t>(q.limit, 1LL << 31);
+		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, q, lo).run(); };
+		return list_chunk_body(ws, V, n, src, dst, q.limit, run, o);
+	});
+}
+
+extern "C" {
+
+int pgq_walk_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops,
+                               int64_t *d_out_count) {
+	return walk_count_bulk(csr, n, d_src, d_dst, walk_query(min_hops, max_hops, nullptr, 0, kWalkMax), d_out_count);
+}
+
+int pgq_k_shortest_walks_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t k,
+                                     int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths, int64_t *d_path_offset,
+                                     int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used, int64_t *child_used) {
+	return walk_lists_bulk(csr, n, d_src, d_dst, walk_query(min_hops, max_hops, nullptr, 0, k), kWalkK,
+	                       walk_bulk_out(d_out_len, d_out_count, d_out_first, d_out_npaths, nullptr, d_path_offset, d_path_hops, path_cap, d_child, child_cap),
+	                       paths_used, child_used);
+}
+
+int pgq_walk_count(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t *out_count,
+                   uint64_t *out_valid) {
+	return walk_count_chunk(csr, V, n, src, dst, walk_query(min_hops, max_hops, nullptr, 0, kWalkMax), out_count, out_valid);
+}
+
+int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t k,
+                         uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
+                         uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
+	return walk_lists_chunk(csr, V, n, src, dst, walk_query(min_hops, max_hops, nullptr, 0, k), kWalkK,
+	                        ListChunkOut { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len });
+}
+
+// ---- the path modes ------------------------------------------------------------------------------------------------------------
+
+int pgq_walk_count_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t limit,
+                                    int path_mode, int64_t *d_out_count) {
+	return walk_count_bulk(csr, n, d_src, d_dst, walk_query(min_hops, max_hops, &path_mode, 0, limit), d_out_count);
 }
 
 int pgq_k_shortest_walks_mode_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t k,
                                           int path_mode, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths,
                                           int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap, int64_t *paths_used,
                                           int64_t *child_used) {
-	mode_steps() = ModeSteps {};
-	if (paths_used) *paths_used = 0;
-	if (child_used) *child_used = 0;
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		PGQ_TRY(check_arrays(csr, n, d_src && d_dst && d_out_len && d_out_count && d_out_first && d_out_npaths && d_path_offset && d_path_hops && d_child,
-		                     "NULL device array"));
-		if (path_cap < 0 || child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
-		return mode_check(csr, path_mode, min_hops, max_hops, &k, "k");
-	};
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		ListOut out;
-		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths;
-		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
-		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
-		return list_bulk_body(out, k, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o, mode).run(); }, paths_used, child_used);
-	});
+	return walk_lists_bulk(csr, n, d_src, d_dst, walk_query(min_hops, max_hops, &path_mode, 0, k), kWalkK,
+	                       walk_bulk_out(d_out_len, d_out_count, d_out_first, d_out_npaths, nullptr, d_path_offset, d_path_hops, path_cap, d_child, child_cap),
+	                       paths_used, child_used);
 }
 
 int pgq_walk_count_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t limit, int path_mode,
                         int64_t *out_count, uint64_t *out_valid) {
-	mode_steps() = ModeSteps {};
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&] { return count_chunk_check(csr, V, n, out_count, out_valid, [&] { return mode_check(csr, path_mode, min_hops, max_hops, &limit, "limit"); }); };
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		auto run = [&](ListOut &o, const int64_t *d_src, const int64_t *d_dst) {
-			return count_mode_run(csr, ws, n, d_src, d_dst, min_hops, max_hops, limit, path_mode, o);
-		};
-		return count_chunk_body(ws, V, n, src, dst, run, out_count, out_valid);
-	});
+	return walk_count_chunk(csr, V, n, src, dst, walk_query(min_hops, max_hops, &path_mode, 0, limit), out_count, out_valid);
 }
 
 int pgq_k_shortest_walks_mode(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t k, int path_mode,
                               uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length,
                               uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
-	mode_steps() = ModeSteps {};
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len };
-	auto check = [&] { return list_chunk_check(csr, V, n, o, [&] { return mode_check(csr, path_mode, min_hops, max_hops, &k, "k"); }); };
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
-		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo, mode).run(); };
-		return list_chunk_body(ws, V, n, src, dst, k, run, o);
-	});
+	return walk_lists_chunk(csr, V, n, src, dst, walk_query(min_hops, max_hops, &path_mode, 0, k), kWalkK,
+	                        ListChunkOut { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len });
 }
 
 // ---- SHORTEST k GROUP ----------------------------------------------------------------------------------------------------------
-
-// the path modes' checks with max_paths in k's place, and the groups
-static int groups_check(const pgq_csr *csr, int path_mode, int64_t min_hops, int64_t max_hops, int64_t groups, int64_t max_paths) {
-	PGQ_TRY(mode_check(csr, path_mode, min_hops, max_hops, &max_paths, "max_paths"));
-	if (groups < 1) return fail(PGQ_ERR_INVALID_ARG, "groups must be at least 1");
-	return PGQ_OK;
-}
 
 int pgq_k_shortest_groups_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops, int64_t groups,
                                       int64_t max_paths, int path_mode, int64_t *d_out_len, int64_t *d_out_count, int64_t *d_out_first, int64_t *d_out_npaths,
                                       int64_t *d_out_ngroups, int64_t *d_path_offset, int64_t *d_path_hops, int64_t path_cap, int64_t *d_child, int64_t child_cap,
                                       int64_t *paths_used, int64_t *child_used) {
-	mode_steps() = ModeSteps {};
-	if (paths_used) *paths_used = 0;
-	if (child_used) *child_used = 0;
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	auto check = [&]() -> int {
-		PGQ_TRY(check_arrays(csr, n,
-		                     d_src && d_dst && d_out_len && d_out_count && d_out_first && d_out_npaths && d_out_ngroups && d_path_offset && d_path_hops && d_child,
-		                     "NULL device array"));
-		if (path_cap < 0 || child_cap < 0) return fail(PGQ_ERR_INVALID_ARG, "negative capacity");
-		return groups_check(csr, path_mode, min_hops, max_hops, groups, max_paths);
-	};
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		ListOut out;
-		out.d_len = d_out_len, out.d_count = d_out_count, out.d_first = d_out_first, out.d_np = d_out_npaths, out.d_ng = d_out_ngroups;
-		out.d_path_off = d_path_offset, out.d_path_hops = d_path_hops, out.path_cap = path_cap, out.d_child = d_child, out.child_cap = child_cap;
-		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
-		return list_bulk_body(out, max_paths, [&](ListOut &o) { return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, o, mode, groups).run(); }, paths_used,
-		                      child_used);
-	});
+	return walk_lists_bulk(csr, n, d_src, d_dst, walk_query(min_hops, max_hops, &path_mode, groups, max_paths), kWalkGroups,
+	                       walk_bulk_out(d_out_len, d_out_count, d_out_first, d_out_npaths, d_out_ngroups, d_path_offset, d_path_hops, path_cap, d_child, child_cap),
+	                       paths_used, child_used);
 }
 
 int pgq_k_shortest_groups(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, int64_t groups, int64_t max_paths,
                           int path_mode, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_ngroups, uint64_t *out_valid, const uint64_t **out_path_offset,
                           const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
-	mode_steps() = ModeSteps {};
-	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
-	uint64_t no_rows = 0; // (n == 0: nothing is written through it)
-	const ListChunkOut o { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len, out_ngroups ? out_ngroups : &no_rows };
-	auto check = [&] {
-		return list_chunk_check(csr, V, n, o, [&]() -> int {
-			if (n > 0 && !out_ngroups) return fail(PGQ_ERR_INVALID_ARG, "NULL output");
-			return groups_check(csr, path_mode, min_hops, max_hops, groups, max_paths);
-		});
-	};
-	return c_entry<true>(csr, check, [&](Workspace *ws) -> int {
-		const int mode = mode_is_walk(path_mode) ? 0 : path_mode;
-		auto run = [&](ListOut &lo, const int64_t *d_src, const int64_t *d_dst) {
-			return WalkCall(csr, ws, n, d_src, d_dst, min_hops, max_hops, lo, mode, groups).run();
-		};
-		return list_chunk_body(ws, V, n, src, dst, max_paths, run, o);
-	});
+	return walk_lists_chunk(csr, V, n, src, dst, walk_query(min_hops, max_hops, &path_mode, groups, max_paths), kWalkGroups,
+	                        ListChunkOut { out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total, out_child, out_child_len, out_ngroups });
 }
 
 int pgq_debug_mode_steps(int64_t *total, int64_t *row_max) {
@@ -777,3 +706,4 @@ int pgq_debug_mode_steps(int64_t *total, int64_t *row_max) {
 }
 
 } // extern "C"
+

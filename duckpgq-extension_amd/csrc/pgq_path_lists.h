@@ -203,7 +203,7 @@ private:
 // capacities, or none (chunk form): then the inner entries and the payload land in ws->asp_paths / ws->child, grown to fit.
 struct ListOut {
 	bool lists = false;
-	int64_t limit = 1; // max_paths / k
+	int64_t limit = 1; // AspCall's max_paths (WalkCall reads its WalkQuery's limit)
 	int64_t *d_len = nullptr, *d_count = nullptr, *d_first = nullptr, *d_np = nullptr;
 	int64_t *d_ng = nullptr; // k_shortest_groups only: the groups among a row's lists
 	int64_t *d_path_off = nullptr, *d_path_hops = nullptr, path_cap = 0, *d_child = nullptr, child_cap = 0; // d_path_hops: k_shortest_walks only

@@ -27,10 +27,10 @@
 // Two passes over one device function: EMIT = false counts (r_np / r_el / r_len / r_count and the count arrays of ListCall::emit's
 // plan step, stopping a row at k), EMIT = true repeats the search and writes each admitted walk into the row's staged block in
 // k_walk_unrank's layout, [hops of each walk][elements], for k_walk_gather.  pgq_walk_count_mode runs the first pass only.
-// The group rule (pgq_k_shortest_groups, groups > 0, k = max_paths P): a length counts as a group once it yields an admitted walk, and
-// the row's search ends behind the length that completed group `groups`, or at `want`.  The counting pass runs with want = P + 1, so
-// that r_count = min(|A|, P + 1), and keeps the first min(found, P) walks for the emitting pass (r_np, r_el, the count arrays);
-// r_ng = the lengths among the kept walks.  With groups == 0 — every other caller — the search takes the steps it always took.
+// When a row has enough is pgq_walk_rule.h's rule, fed one admitted walk at a time: a length is a group once it yields an admitted
+// walk, and a length that completes the last group is searched to its end or to B + 1 walks.  For pgq_k_shortest_groups B = P, so
+// that r_count = min(|A|, P + 1); WalkPlan keeps the first P (r_np, r_el, the count arrays; r_ng = the lengths among them) for
+// the emitting pass, which looks for exactly those.
 // Not built: a smarter prune than W (a vertex that W admits may only be reachable through the stack), several wavefronts per row.
 
 namespace pgq {
@@ -44,8 +44,8 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
                                                    const int32_t *__restrict__ sdst, u32 base_lane, const int32_t *__restrict__ usrc,
                                                    const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                    const int64_t *__restrict__ edge_ids, const int64_t *__restrict__ roff,
-                                                   const int32_t *__restrict__ radj, const WalkRound *__restrict__ tabs, int mode, int64_t min_hops,
-                                                   int rounds, int64_t k, int64_t groups, int64_t step_cap, int64_t *__restrict__ r_len,
+                                                   const int32_t *__restrict__ radj, const WalkRound *__restrict__ tabs, WalkQuery q, int rounds,
+                                                   int64_t step_cap, int64_t *__restrict__ r_len,
                                                    int64_t *__restrict__ r_count, int64_t *__restrict__ r_np, int64_t *__restrict__ r_el,
                                                    int64_t *__restrict__ r_ng, int64_t *__restrict__ cntp,
                                                    int64_t *__restrict__ cnte, const int64_t *__restrict__ ploc, const int64_t *__restrict__ eloc,
@@ -55,19 +55,25 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
 	__shared__ u32 scur[PGQ_WALK_MAX_HOPS + 1];   // depth i: the next position of x_i's in-list
 	__shared__ int64_t se[PGQ_WALK_MAX_HOPS + 1]; // e_1 .. e_t
 	const int lane = threadIdx.x;
+	const int mode = q.mode;
 	const bool vertex_mode = mode_is_vertex(mode), trail = mode == PGQ_MODE_TRAIL;
 	for (int64_t a = blockIdx.x; a < m; a += gridDim.x) {
 		const int64_t row_i = lo + a;
 		const u32 l = skey[row_i] - base_lane;
 		const int dst = sdst[row_i], src = usrc[base_lane + l];
-		const int64_t want = EMIT ? ploc[a + 1] - ploc[a] : (groups > 0 ? k + 1 : k); // walks to find (groups: one past the cap, k <= 2^31)
-		const int64_t keep = EMIT || groups <= 0 ? want : k;                        // ... of which the first `keep` are the row's list
-		const int64_t rowbase = EMIT ? stage_base + eloc[a] : 0;                    // the row's staged block ...
-		const int64_t room = EMIT ? eloc[a + 1] - eloc[a] - want : 0;               // ... and the elements it holds behind the hops
-		int64_t found = 0, el = 0, steps = 0, first = -1;
-		int64_t seen = 0, kept = 0; // the lengths that yielded an admitted walk (the group rule), and those among the first `keep` walks
+		// The row is fed its admitted walks one by one (pgq_walk_rule.h): found.count walks, found.groups lengths with one.  The
+		// counting pass looks for B + 1 of them — k, or one past max_paths — and plans the first q.limit; the emitting pass for the
+		// `want` walks that were planned.
+		const int64_t want = EMIT ? ploc[a + 1] - ploc[a] : q.rule().bound + 1;
+		const WalkRule rule { q.rule().groups, want - 1 };
+		const int64_t rowbase = EMIT ? stage_base + eloc[a] : 0;      // the row's staged block ...
+		const int64_t room = EMIT ? eloc[a + 1] - eloc[a] - want : 0; // ... and the elements it holds behind the hops
+		const int64_t keep = EMIT ? want : q.limit;
+		WalkRow found;
+		WalkPlan plan;
+		int64_t steps = 0, first = -1;
 		u32 error = 0;
-		for (int64_t t64 = min_hops; t64 <= rounds && found < want && !error && (groups <= 0 || seen < groups); t64++) {
+		for (int64_t t64 = q.min_hops; t64 <= rounds && found.open(rule) && !error; t64++) {
 			const int t = (int)t64;
 			if (walk_w(tabs[t], dst, l) <= 0) continue;
 			bool fresh = true; // the length has yielded no admitted walk yet
@@ -75,32 +81,28 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
 			sx[t] = dst;
 			scur[t] = 0;
 			// depth i > 0: look for the next parent of x_i; depth 0: an admitted walk, then on at depth 1
-			while (i <= t && found < want && !error) {
+			while (i <= t && found.count < want && !error) { // (a length that counts as the last group is searched to its end)
 				if (i == 0) {
 					if (t > 0 && sx[0] != src) { // (W_0 admits the source alone)
 						error = 8u;
 						break;
 					}
 					if (EMIT) {
-						if (el + 2 * t + 1 > room) { // (the counting pass found less)
+						if (plan.el + 2 * t + 1 > room) { // (the counting pass found less)
 							error = 2u;
 							break;
 						}
-						int64_t *out = stage + rowbase + want + el;
-						if (lane == 0) stage[rowbase + found] = t;
+						int64_t *out = stage + rowbase + want + plan.el;
+						if (lane == 0) stage[rowbase + found.count] = t;
 						for (int j = lane; j <= t; j += 64) {
 							out[2 * j] = j == 0 ? src : sx[j];
 							if (j > 0) out[2 * j - 1] = se[j];
 						}
 					}
 					if (first < 0) first = t;
-					if (fresh) {
-						fresh = false;
-						seen++;
-						if (found < keep) kept++;
-					}
-					if (found < keep) el += 2 * t + 1;
-					found++;
+					plan.take(found, keep, t, 1, fresh);
+					found.add(1, fresh);
+					fresh = false;
 					i = 1; // (t == 0: past the loop)
 					continue;
 				}
@@ -165,16 +167,16 @@ __global__ __launch_bounds__(64) void k_mode_search(int64_t lo, int64_t m, const
 			if (!EMIT) {
 				const u32 row = sidx[row_i];
 				r_len[row] = first;
-				const int64_t np = min(found, keep);
-				r_count[row] = found;
+				const int64_t np = WalkPlan::np(found, keep);
+				r_count[row] = found.count;
 				r_np[row] = np;
-				r_el[row] = el;
-				if (r_ng) r_ng[row] = kept;
+				r_el[row] = plan.el;
+				if (r_ng) r_ng[row] = plan.ngroups;
 				if (cntp) {
 					cntp[a] = np;
-					cnte[a] = np > 0 ? np + el : 0;
+					cnte[a] = np > 0 ? np + plan.el : 0;
 				}
-			} else if (found > 0) {
+			} else if (found.count > 0) {
 				soff[row_i] = rowbase;
 			}
 			if (error) atomicOr(&tc->error, error);

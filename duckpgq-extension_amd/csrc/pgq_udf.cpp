@@ -123,6 +123,18 @@ int search_prologue(pgq_state *s, int32_t id, int64_t V, CsrRef *out, pgq_csr_t 
 	return 0;
 }
 
+// A search UDF: the prologue, call(device CSR) — one call into libpgq_hip — and behind a call that succeeded the CSR noted for
+// deletion at the query's end, as the reference's functions do on their last line.
+template <typename Call> int search_udf(pgq_state *s, int32_t id, int64_t V, const char *what, Call &&call) {
+	CsrRef c;
+	pgq_csr_t *d;
+	if (search_prologue(s, id, V, &c, &d, what)) return -1;
+	if (call(d) != PGQ_OK) return device_fail();
+	std::lock_guard<std::mutex> g(s->csr_lock);
+	s->csr_to_delete.insert(id);
+	return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -275,24 +287,14 @@ int pgq_udf_bind_search(pgq_state_t *s, int32_t id) { // iterative_length_functi
 
 int pgq_udf_iterativelength(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                             int64_t *out, uint64_t *out_valid) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_iterativelength(d, V, n, src, dst, out, out_valid) != PGQ_OK) return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id); // iterativelength.cpp:142
-	return 0;
+	// iterativelength.cpp:142
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_iterativelength(d, V, n, src, dst, out, out_valid); });
 }
 
 int pgq_udf_iterativelength_within(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                                    int64_t max_hops, int64_t *out, uint64_t *out_valid) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_iterativelength_within(d, V, n, src, dst, max_hops, out, out_valid) != PGQ_OK) return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id); // iterativelength.cpp:142
-	return 0;
+	// iterativelength.cpp:142
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_iterativelength_within(d, V, n, src, dst, max_hops, out, out_valid); });
 }
 
 int pgq_udf_iterativelength2(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
@@ -303,119 +305,73 @@ int pgq_udf_iterativelength2(pgq_state_t *s, int32_t id, int64_t V, int64_t n, p
 int pgq_udf_iterativelengthbidirectional(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                                          int64_t *out, uint64_t *out_valid) {
 	// the bidirectional schedule (forward CSR from src, transposed CSR from dst): its own device entry point
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_iterativelength_bidirectional(d, V, n, src, dst, out, out_valid) != PGQ_OK) return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id); // iterativelength_bidirectional.cpp:152
-	return 0;
+	// iterativelength_bidirectional.cpp:152
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_iterativelength_bidirectional(d, V, n, src, dst, out, out_valid); });
 }
 
 int pgq_udf_shortestpath(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst,
                          uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                          uint64_t *out_child_len) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_shortestpath(d, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len) != PGQ_OK)
-		return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id); // shortest_path.cpp:206
-	return 0;
+	// shortest_path.cpp:206
+	return search_udf(s, id, V, "shortest path",
+	                  [&](pgq_csr_t *d) { return pgq_shortestpath(d, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len); });
 }
 
 int pgq_udf_shortestpath_within(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
                                 uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                                 uint64_t *out_child_len) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_shortestpath_within(d, V, n, src, dst, max_hops, out_offset, out_length, out_valid, out_child, out_child_len) != PGQ_OK)
-		return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id); // shortest_path.cpp:206
-	return 0;
+	// shortest_path.cpp:206
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) {
+		return pgq_shortestpath_within(d, V, n, src, dst, max_hops, out_offset, out_length, out_valid, out_child, out_child_len);
+	});
 }
 
 // ALL SHORTEST (no counterpart: match.cpp:82 rejects it): bound through pgq_udf_bind_search, shortestpath's exception texts
 int pgq_udf_shortestpath_count(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
                                int64_t *out, uint64_t *out_valid) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_shortestpath_count(d, V, n, src, dst, max_hops, out, out_valid) != PGQ_OK) return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_shortestpath_count(d, V, n, src, dst, max_hops, out, out_valid); });
 }
 
 int pgq_udf_all_shortestpaths(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
                               int64_t max_paths, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
                               const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
                               const int64_t **out_child, uint64_t *out_child_len) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_all_shortestpaths(d, V, n, src, dst, max_hops, max_paths, out_first, out_npaths, out_valid, out_path_offset, out_path_length,
-	                          out_path_total, out_child, out_child_len) != PGQ_OK)
-		return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) {
+		return pgq_all_shortestpaths(d, V, n, src, dst, max_hops, max_paths, out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total,
+		                             out_child, out_child_len);
+	});
 }
 
 // {lower,upper} walks and SHORTEST k (no counterpart: match.cpp:82-98 rejects TopK): bound through pgq_udf_bind_search
 int pgq_udf_walk_count(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                        int64_t *out, uint64_t *out_valid) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_walk_count(d, V, n, src, dst, min_hops, max_hops, out, out_valid) != PGQ_OK) return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_walk_count(d, V, n, src, dst, min_hops, max_hops, out, out_valid); });
 }
 
 int pgq_udf_k_shortest_walks(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                              int64_t k, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset,
                              const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_k_shortest_walks(d, V, n, src, dst, min_hops, max_hops, k, out_first, out_npaths, out_valid, out_path_offset, out_path_length,
-	                         out_path_total, out_child, out_child_len) != PGQ_OK)
-		return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) {
+		return pgq_k_shortest_walks(d, V, n, src, dst, min_hops, max_hops, k, out_first, out_npaths, out_valid, out_path_offset, out_path_length, out_path_total,
+		                            out_child, out_child_len);
+	});
 }
 
 // ... under a path mode (no counterpart: match.cpp:80-108 rejects every mode but WALK): bound through pgq_udf_bind_search
 int pgq_udf_walk_count_mode(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                             int64_t limit, int path_mode, int64_t *out, uint64_t *out_valid) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_walk_count_mode(d, V, n, src, dst, min_hops, max_hops, limit, path_mode, out, out_valid) != PGQ_OK) return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path",
+	                  [&](pgq_csr_t *d) { return pgq_walk_count_mode(d, V, n, src, dst, min_hops, max_hops, limit, path_mode, out, out_valid); });
 }
 
 int pgq_udf_k_shortest_walks_mode(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                                   int64_t k, int path_mode, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid,
                                   const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
                                   uint64_t *out_child_len) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_k_shortest_walks_mode(d, V, n, src, dst, min_hops, max_hops, k, path_mode, out_first, out_npaths, out_valid, out_path_offset, out_path_length,
-	                              out_path_total, out_child, out_child_len) != PGQ_OK)
-		return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) {
+		return pgq_k_shortest_walks_mode(d, V, n, src, dst, min_hops, max_hops, k, path_mode, out_first, out_npaths, out_valid, out_path_offset, out_path_length,
+		                                 out_path_total, out_child, out_child_len);
+	});
 }
 
 // SHORTEST k GROUP (no counterpart: the parser's PathPattern::group, path_pattern.hpp:22, is rejected with TopK): bound through pgq_udf_bind_search
@@ -423,15 +379,10 @@ int pgq_udf_k_shortest_groups(pgq_state_t *s, int32_t id, int64_t V, int64_t n, 
                               int64_t groups, int64_t max_paths, int path_mode, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_ngroups,
                               uint64_t *out_valid, const uint64_t **out_path_offset, const uint64_t **out_path_length, uint64_t *out_path_total,
                               const int64_t **out_child, uint64_t *out_child_len) {
-	CsrRef c;
-	pgq_csr_t *d;
-	if (search_prologue(s, id, V, &c, &d, "shortest path")) return -1;
-	if (pgq_k_shortest_groups(d, V, n, src, dst, min_hops, max_hops, groups, max_paths, path_mode, out_first, out_npaths, out_ngroups, out_valid,
-	                          out_path_offset, out_path_length, out_path_total, out_child, out_child_len) != PGQ_OK)
-		return device_fail();
-	std::lock_guard<std::mutex> g(s->csr_lock);
-	s->csr_to_delete.insert(id);
-	return 0;
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) {
+		return pgq_k_shortest_groups(d, V, n, src, dst, min_hops, max_hops, groups, max_paths, path_mode, out_first, out_npaths, out_ngroups, out_valid,
+		                             out_path_offset, out_path_length, out_path_total, out_child, out_child_len);
+	});
 }
 
 int pgq_udf_bind_cheapest(pgq_state_t *s, int32_t id, int *ret_type) { // cheapest_path_length_function_data.cpp:7-32
