@@ -54,6 +54,7 @@ _CHUNK_LISTS = (C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_
 _BULK_LISTS = (_P, _P, _I, _P, _I, C.POINTER(_I), C.POINTER(_I))
 # name -> (scalars, per-row outputs of the chunk form, of the bulk form, a list form?)
 _WALK_FORMS = {"walk_count": ((_I, _I), 2, 1, False),
+               "walk_length": ((_I, _I), 2, 1, False),
                "k_shortest_walks": ((_I, _I, _I), 3, 4, True),
                "walk_count_mode": ((_I, _I, _I, C.c_int), 2, 1, False),
                "k_shortest_walks_mode": ((_I, _I, _I, C.c_int), 3, 4, True),
@@ -587,6 +588,16 @@ class DeviceCSR:
                                               _p(ov)))
         return out, unpack_validity(ov, n)
 
+    def walk_length(self, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        """The length of the shortest walk of min_hops..max_hops edges per row; NULL when there is none and for a NULL endpoint.
+        src == dst is not special (include/pgq_hip.h: pgq_walk_length).  `valid` is the filter of {lower,upper} in WALK mode."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        out = np.zeros(n, dtype=np.int64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_walk_length(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
     def k_shortest_walks(self, src, dst, min_hops, max_hops, k, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None,
                          raw=False, path_mode=None):
         """Per row the list of its first k walks of min_hops..max_hops edges, shorter walks first, each [x_0, e_1, x_1, ..., x_t],
@@ -810,6 +821,10 @@ class DeviceCSR:
         _check(self.L.pgq_walk_count_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
                                                  C.c_void_p(d_out_count)))
 
+    def walk_length_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, d_out_len):
+        _check(self.L.pgq_walk_length_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                  C.c_void_p(d_out_len)))
+
     def k_shortest_walks_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, k, d_out_len, d_out_count, d_out_first, d_out_npaths,
                                   d_path_offset, d_path_hops, path_cap, d_child, child_cap):
         """(status, walks needed, elements needed): the capacity protocol of all_shortestpaths_bulk_ptr."""
@@ -996,6 +1011,17 @@ class PgqState:
             if path_mode is not None:
                 return self.U.pgq_udf_walk_count_mode(s, csr_id, V, n, sv, dv, lo, hi, int(limit), int(path_mode), out_p, ov_p)
             return self.U.pgq_udf_walk_count(s, csr_id, V, n, sv, dv, lo, hi, out_p, ov_p)
+
+        ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
+        return out, ok
+
+    def walk_length(self, csr_id, V, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        n = len(src_sel) if src_sel is not None else len(src)
+        out = np.zeros(n, dtype=np.int64)
+        lo, hi = int(min_hops), int(max_hops)
+
+        def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            return self.U.pgq_udf_walk_length(s, csr_id, V, n, sv, dv, lo, hi, out_p, ov_p)
 
         ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
         return out, ok

@@ -193,6 +193,11 @@ struct Options {
 	int ball_sort = 1;          // rows with repeated sources that are NOT grouped are sorted by source first (0: such calls take the older routes)
 	int mode_step_cap = 1 << 24; // k_shortest_walks_mode / walk_count_mode: steps (64-entry in-list trips and descents) one row's search may take per
 	                             // pass before the call fails with PGQ_ERR_UNSUPPORTED.  A safety limit, not a tuned number
+	int walk_length_pull = 2;    // walk_length's bit rounds: 0 always push (k_walk_activate), 1 always pull (k_wl_pull), 2 by the rule below
+	int walk_length_pull_div = 16; // ... dense once the queue's out-edges exceed E / this, and dense from then on (a pull leaves no queue).  Measured
+	                               // (profiles/r21/walk_length_*.json, knows graph, E = 39.9 M): a forced pull round costs 0.31 - 0.34 ms whatever is
+	                               // active, forced push rounds walk 6.2 - 8.0 G out-edges per second (the {3,4} and {2,3} lines), so the two meet at
+	                               // 1.9 - 2.7 M out-edges = E / 21 .. E / 15; 16 lies inside, and automatic beat both forced settings on every line
 	double ball_bias = 1.0;     // the ball runs while ball_bias x its estimated bytes <= the cheaper of the pre-pass and the lane batches
 };
 Options &options();

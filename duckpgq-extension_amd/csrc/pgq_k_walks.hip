@@ -707,3 +707,4 @@ int pgq_debug_mode_steps(int64_t *total, int64_t *row_max) {
 
 } // extern "C"
 
+#include "pgq_walk_length.hip" // walk_length: stage 1 by distance, bit rounds over the rows left, on this file's k_walk_activate and counters

@@ -74,7 +74,7 @@ __global__ void k_bound_pack(int64_t n, int64_t max_hops, int64_t *__restrict__ 
 }
 // The bound a search runs under: V - 1 hops and more reach whatever is reachable — the unbounded search (INT64_MAX is what
 // the binder holds for "no upper bound")
-static int64_t search_bound(const pgq_csr *c, int64_t max_hops) { return max_hops >= c->V - 1 ? -1 : max_hops; }
+int64_t search_bound(const pgq_csr *c, int64_t max_hops) { return max_hops >= c->V - 1 ? -1 : max_hops; }
 
 // Whether the pair-centric pre-pass may run for this call at all, and whether the host-side cost model sends n rows
 // (each taken as a distinct source) to it.  Shared by search_device and the chunk entry point (zero-copy staging).

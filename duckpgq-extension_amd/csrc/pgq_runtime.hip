@@ -343,6 +343,8 @@ static std::vector<OptRef> option_table(Options &o) {
 		{ "meet4_batch_settled", nullptr, nullptr, &g_meet4_batch_settled },
 		{ "meet_trace", &o.meet_trace, nullptr },
 		{ "mode_step_cap", &o.mode_step_cap, nullptr },
+		{ "walk_length_pull", &o.walk_length_pull, nullptr },
+		{ "walk_length_pull_div", &o.walk_length_pull_div, nullptr },
 		{ "meet_layout", &o.meet_layout, nullptr },
 		{ "meet_align", &o.meet_align, nullptr },
 		{ "meet_pack", &o.meet_pack, nullptr },

@@ -487,6 +487,8 @@ int grow_keeping(DevBuf &buf, size_t bytes, size_t keep, hipStream_t st);
 // Answers the call's rows by whichever route pays: the per-row bidirectional search, the source-centric kernel, the
 // pair-centric pre-pass, the lane batches (pgq_route.hip).
 int search_device(pgq_csr *c, Workspace *ws, const SearchCall &call, SearchReport &rep);
+// SearchAsk::max_hops for a pattern's upper bound: V - 1 hops and more reach whatever is reachable, the unbounded search (-1)
+int64_t search_bound(const pgq_csr *c, int64_t max_hops);
 // The lane-batched MS-BFS (pgq_msbfs.hip): lane assignment, the batches, the straggler pass, results back to row order.
 // sampled: the route memo sent the rows here without the pre-pass (the sample rides in the lane assignment's first launch);
 // ahead_wd: the memo's width for stage 2 ahead of the wait (MemoVerdict; -1: not looked up yet).

@@ -348,6 +348,12 @@ int pgq_udf_walk_count(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec
 	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_walk_count(d, V, n, src, dst, min_hops, max_hops, out, out_valid); });
 }
 
+// the filter of a quantified pattern in WALK mode: walk_length(...) IS NOT NULL
+int pgq_udf_walk_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                        int64_t *out, uint64_t *out_valid) {
+	return search_udf(s, id, V, "shortest path", [&](pgq_csr_t *d) { return pgq_walk_length(d, V, n, src, dst, min_hops, max_hops, out, out_valid); });
+}
+
 int pgq_udf_k_shortest_walks(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                              int64_t k, uint64_t *out_first, uint64_t *out_npaths, uint64_t *out_valid, const uint64_t **out_path_offset,
                              const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child, uint64_t *out_child_len) {

@@ -7,6 +7,7 @@
 //   ShortestPathCountFunction      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
 //   AllShortestPathsFunction       (no counterpart) ... the first max_paths of them, LIST(LIST(BIGINT)); bound and max_paths trail the arguments
 //   WalkCountFunction              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
+//   WalkLengthFunction             (no counterpart) the length of the shortest of them: IS NOT NULL is that pattern's filter
 //   KShortestWalksFunction         (no counterpart: TopK, match.cpp:82-98) ... the first k of them, shortest first, LIST(LIST(BIGINT))
 //   WalkCountModeFunction          (no counterpart: path modes, match.cpp:80-108) the walks TRAIL / ACYCLIC / SIMPLE admit, up to a limit
 //   KShortestWalksModeFunction     (no counterpart) ... the first k of them, shortest first, LIST(LIST(BIGINT))
@@ -242,6 +243,23 @@ void WalkCountFunction(DataChunk &args, ExpressionState &state, Vector &result) 
 	validity.Initialize(args.size());
 	if (pgq_walk_count(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper,
 	                   result_data, validity.GetData()) != PGQ_OK)
+		ThrowDevice();
+	in.state->csr_to_delete.insert(in.csr_id);
+}
+
+// walk_length(csr_id, V, src, dst, lower, upper) -> BIGINT: the length of the shortest walk of lower..upper edges, NULL when there is
+// none or an endpoint is NULL.  `walk_length(...) IS NOT NULL` is the filter a quantified pattern -[e]->{lower,upper} needs in WALK
+// mode, in the place of the binder's iterativelength BETWEEN lower AND upper (match.cpp:658-671); emitting it is the binder's
+// change, not this layer's.  Bound like shortestpath, registered beside it.
+void WalkLengthFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	SearchInputs in = Prepare(args, state, "shortest path");
+	const int64_t lower = ConstantArg(args, 4), upper = ConstantArg(args, 5);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto result_data = FlatVector::GetDataMutable<int64_t>(result);
+	ValidityMask &validity = FlatVector::ValidityMutable(result);
+	validity.Initialize(args.size());
+	if (pgq_walk_length(DeviceCSR(*in.state, *in.csr, in.v_size), in.v_size, (int64_t)args.size(), AsVec(in.src), AsVec(in.dst), lower, upper,
+	                    result_data, validity.GetData()) != PGQ_OK)
 		ThrowDevice();
 	in.state->csr_to_delete.insert(in.csr_id);
 }

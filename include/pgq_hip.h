@@ -340,6 +340,31 @@ int pgq_k_shortest_walks(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pg
                          const uint64_t **out_path_length, uint64_t *out_path_total, const int64_t **out_child,
                          uint64_t *out_child_len);
 
+/* walk_length(csr_id, V, src, dst, lower, upper) -> BIGINT: the length of the shortest walk of lower..upper edges — with W_t as
+ * above, the smallest t in [min_hops, max_hops] with W_t[dst] > 0.  `walk_length(...) IS NOT NULL` is the filter a quantified pattern
+ * -[e]->{lower,upper} needs in WALK mode (the reference's iterativelength BETWEEN lower AND upper is wrong for walks, see above).
+ *   - NULL (payload -1) when there is no such t, or when src or dst is NULL.
+ *   - src == dst is not special: 0 when min_hops == 0, otherwise the length of the shortest closed walk of at least min_hops edges.
+ *   - Any CSR; weights are ignored; parallel edges change nothing.
+ * Three identities hold: the result equals pgq_k_shortest_walks_bulk_device(k = 1)'s d_out_len; it is non-NULL exactly where
+ * pgq_walk_count > 0; for min_hops <= dist <= max_hops it equals pgq_iterativelength_within(max_hops), and for min_hops == 0 it
+ * equals that call on every row.
+ * min_hops < 0 or max_hops < min_hops -> PGQ_ERR_INVALID_ARG.  max_hops > PGQ_WALK_MAX_HOPS (INT64_MAX included) ->
+ * PGQ_ERR_UNSUPPORTED with pgq_walk_count's text: a larger or unbounded upper is NOT BUILT.  A NULL handle is answered with
+ * PGQ_ERR_INVALID_ARG ("NULL csr") before any device is asked for; ids out of range fail as in the other walk calls.  A failed
+ * call has written nothing.
+ * How: the distance d first, by pgq_iterativelength_within's routes under max_hops (off the route memo's record): min_hops <= d <=
+ * max_hops answers d, d > max_hops or unreachable answers NULL.  Only the rows with d < min_hops (every src == dst row when
+ * min_hops >= 1) go through rounds, in batches of 64 sources: one 8-byte mask word per vertex and round, two mask arrays and two
+ * queues per batch (24 bytes per vertex; PGQ_ERR_OOM with nothing written when they cannot be had), no visited set.  The rounds
+ * stop behind round max_hops, when no row of the batch is open, or when nothing is active.  Option "walk_length_pull": 0 = every
+ * round top-down (pgq_walk_count's activation kernel), 1 = every round bottom-up over the upload's work partition (hubs slice by
+ * slice), 2 (shipped) = bottom-up once the queue's out-edges exceed E / "walk_length_pull_div", and from then on.  pgq_stats_t:
+ * batches / levels / push_levels / pull_levels / edges_scanned count these rounds alone (not the distance stage's own search).
+ * NOT BUILT: _multi forms, a boolean-only form, the path modes, rounds enqueued ahead of the host. */
+int pgq_walk_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                    int64_t *out_len, uint64_t *out_valid);
+
 /* k_shortest_walks_mode / walk_count_mode: SHORTEST k and a limited count under SQL/PGQ's path modes (the reference's binder rejects
  * every mode but WALK, match.cpp:80-108, and tells its users to pick one when ALL explodes on a cyclic graph, match.cpp:100-104).
  * The modes are numbered as the reference's PGQPathMode (subpath_element.hpp:9); any other value is PGQ_ERR_INVALID_ARG.
@@ -522,6 +547,10 @@ int pgq_all_shortestpaths_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *
  * (d_src[i] < 0). */
 int pgq_walk_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
                                int64_t max_hops, int64_t *d_out_count);
+/* pgq_walk_length without the chunk ceiling: d_out_len[i] = the length, -1 when there is no such walk and for a NULL row
+ * (d_src[i] < 0). */
+int pgq_walk_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                int64_t max_hops, int64_t *d_out_len);
 /* pgq_k_shortest_walks without the chunk ceiling; outputs as pgq_all_shortestpaths_bulk_device with these differences.  The walks
  * of one row differ in length: walk j starts at d_path_offset[j] in d_child and has 2 * d_path_hops[j] + 1 elements (both arrays
  * path_cap entries).  d_out_len[i] = the hops of the row's first walk, -1 if it has none.  d_out_npaths[i] = min(count, k).

@@ -18,6 +18,7 @@
  *   pgq_udf_shortestpath_count      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
  *   pgq_udf_all_shortestpaths       (no counterpart) ... and the first max_paths of them as a list of lists; both bound like shortestpath
  *   pgq_udf_walk_count              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
+ *   pgq_udf_walk_length             (no counterpart: the filter {lower,upper} needs in WALK mode, where match.cpp:658-671 emits iterativelength BETWEEN) the shortest such walk's length
  *   pgq_udf_k_shortest_walks        (no counterpart: TopK, match.cpp:82-98) ... and the first k of them, shortest first; both bound like shortestpath
  *   pgq_udf_walk_count_mode         (no counterpart: path modes, match.cpp:80-108) the admitted walks under TRAIL / ACYCLIC / SIMPLE, up to a limit
  *   pgq_udf_k_shortest_walks_mode   (no counterpart) ... and the first k of them, shortest first; both bound like shortestpath
@@ -101,6 +102,11 @@ int pgq_udf_all_shortestpaths(pgq_state_t *, int32_t id, int64_t V, int64_t n, p
  * PGQ_ERR_INVALID_ARG / PGQ_ERR_UNSUPPORTED (upper > PGQ_WALK_MAX_HOPS: walks need an upper bound) */
 int pgq_udf_walk_count(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
                        int64_t *out, uint64_t *out_valid);
+/* walk_length(id, V, src, dst, lower, upper) -> BIGINT: the length of the shortest walk of lower..upper edges (pgq_walk_length:
+ * src == dst is not special; NULL when there is no such walk and for a NULL endpoint) — `walk_length(...) IS NOT NULL` is the
+ * filter of a quantified pattern in WALK mode.  Bound through pgq_udf_bind_search, errors as for pgq_udf_walk_count */
+int pgq_udf_walk_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                        int64_t *out, uint64_t *out_valid);
 /* k_shortest_walks(id, V, src, dst, lower, upper, k) -> LIST(LIST(BIGINT)): the first k walks of lower..upper edges of every row,
  * shorter walks first, in the contract's order (pgq_k_shortest_walks; for src != dst and lower <= dist <= upper walk 0 is
  * shortestpath's list); outputs as pgq_udf_all_shortestpaths.  Bound through pgq_udf_bind_search, errors as for
