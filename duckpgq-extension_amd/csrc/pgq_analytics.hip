@@ -13,8 +13,16 @@
 //       0.85, stop when the largest change is below 1e-6.  Pull form: in-lists sorted by (source, slot) — a stable radix
 //       sort of the forward slots by destination — and summed left to right by one thread per vertex, i.e. in exactly
 //       the order the reference's `temp_rank[neighbor] += rank_contrib` accumulates, so every partial sum matches bit
-//       for bit; only the dangling-rank total is a two-level sum (1024 ordered slices, then their ordered sum) instead
-//       of one sequential chain, hence a tolerance of 1e-12 relative in the tests.  Computed once per CSR handle.
+//       for bit.  The last update, 0.85 * (sum + correction) + 0.15 / v_size, is ONE rounding: the reference's build
+//       contracts it and its goldens (17 digits) hold the fused bits, the unfused ones match 2 of its 10 values; it is
+//       an explicit fma here and in the oracle, so no compiler's contraction default decides it.
+//       Exact: everything, up to v_size = 1024.  k_pr_dangling adds the dangling ranks in 1024 ordered slices of
+//       ceil(v_size / 1024) entries and then adds the slices in order; with one entry per slice that is the
+//       reference's own chain, because adding +0.0 to a non-negative sum changes nothing.
+//       Not exact: the dangling total above v_size = 1024, where a slice holds several entries and the sum associates
+//       differently from the reference's chain (435 ulp on 2049 equal ranks, a few ulp on graphs with edges; 1e-12
+//       relative is the bound kept on 20,002 entries).  tests/analytics_model.py restates the slicing and predicts
+//       every bit of the result; tests/test_analytics_gpu.py holds the kernels to it.  Computed once per CSR handle.
 //
 //   weakly_connected_component    src/core/functions/scalar/weakly_connected_component.cpp:14-104
 //       the reference's component id is the root its sequential union-find schedule ends in (:14-34,83-90: goldens pin
@@ -222,7 +230,9 @@ __global__ void k_pr_pull(int64_t V, int64_t vs, const int64_t *__restrict__ rof
 		if (n < V)
 			for (int64_t k = roff[n]; k < roff[n + 1]; k++) t += contrib[psrc[k]];
 		const double corr = *dangling / static_cast<double>(vs);
-		const double r = (1 - 0.85) / static_cast<double>(vs) + 0.85 * (t + corr);
+		// ONE rounding of 0.85 * (t + corr) + (1 - 0.85) / vs: the fused update is what the reference's goldens hold,
+		// written out so that no contraction default decides it
+		const double r = fma(0.85, t + corr, (1 - 0.85) / static_cast<double>(vs));
 		next[n] = r;
 		delta = fabs(r - rank[n]);
 	}
