@@ -128,6 +128,7 @@ def load_hip():
     L.pgq_cheapest_path_length_within_multi.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                         C.c_void_p]
     L.pgq_iterativelength_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pgq_iterativelength_bidirectional_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pgq_traversed_edges_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pgq_shortestpath_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -522,6 +523,15 @@ class DeviceCSR:
         _check(self.L.pgq_iterativelength_within(self.h, self.V, n, sv, dv, int(max_hops), _p(out), _p(ov)))
         return out, unpack_validity(ov, n)
 
+    def iterativelength_bidirectional(self, src, dst, src_valid=None, src_sel=None, dst_sel=None):
+        """iterativelength's hop counts by one bidirectional search per row (k_bibfs); rows over its caps go on to the lane batches."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, None, keep)
+        out = np.zeros(n, dtype=np.int64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_iterativelength_bidirectional(self.h, self.V, n, sv, dv, _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
     def shortestpath(self, src, dst, src_valid=None, src_sel=None, dst_sel=None, raw=False, max_hops=None):
         keep = []
         sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, None, keep)
@@ -678,6 +688,10 @@ class DeviceCSR:
     def iterativelength_bulk_ptr(self, n, d_src, d_dst, d_out):
         _check(self.L.pgq_iterativelength_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
                                                       C.c_void_p(d_out)))
+
+    def iterativelength_bidirectional_bulk_ptr(self, n, d_src, d_dst, d_out):
+        _check(self.L.pgq_iterativelength_bidirectional_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
+                                                                    C.c_void_p(d_out)))
 
     def iterativelength_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out):
         _check(self.L.pgq_iterativelength_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),

@@ -982,3 +982,187 @@ def pull_gadgets(part_weight=64, hub_chunk=64):
                        dist=np.array([r[2] for r in rows], dtype=np.int64), tag=np.array([r[3] for r in rows]), gadgets=gadgets,
                        fixed=fixed, pairs=pairs, stale=stale, spread=np.array(spread_rows, dtype=np.int64), negative=negative,
                        part_weight=part_weight, hub_chunk=hub_chunk, n_targets=len(tdeg), spread_sources=[int(real(s)) for s in spread])
+
+
+# ---- gadgets on the queue, list, cap and row limits of k_bibfs ------------------------------------------------------------
+# Every constant the gadgets sit on, and where it was read (test_bibfs_gadgets_cpu.py reads them back from the sources):
+BIBFS_LIMITS = dict(
+    queue_floor=1024,   # pgq_meet.hip, `qcap = std::max(1024, ...bibfs_queue)` in the chain and in meet_bidirectional
+    cap_floor=1,        # launch_bibfs, `std::max(1, options().bibfs_cap)`
+    block=1024,         # `__launch_bounds__(1024) void k_bibfs(`: 16 wavefronts
+    walk_stride=16,     # k_bibfs, `nf[side], wib, 16, xoff, xadj`: wavefront w takes the queue positions w + 16 * lane
+    walk_lanes=64,      # pgq_walk.h, `pb += 64 * stride` and `min(64, (list_n - pb + stride - 1) / stride)`
+    chunk=256,          # pgq_walk.h, `q += 256`: four entries per lane, from `b & ~3`
+    depth=2,            # pgq_meet.hip, `#define PGQ_BIBFS_DEPTH 2`
+    rows=256,           # pgq_internal.h, `int bibfs_rows = 256;`
+    rows_max=16384,     # pgq_internal.h, `int bibfs_rows_max = 16384;`
+    rows_edges=4096,    # the chain, `std::min<int64_t>(opt.bibfs_rows_max, c->E / 4096)`
+    far_rows_start=1)   # pgq_internal.h, `meet_far_rows { 1 }`
+BIBFS_HUB = 2304        # in-edges of the hub behind every guarded destination: more than any forward frontier has work (2049)
+BIBFS_TEST_CAP = 300    # the bibfs_cap the `cap` family is built for
+BIBFS_POSITIONS = {1024: (1, 15, 16, 17, 1007, 1008, 1009, 1023, 1024), 2048: (1025, 2047, 2048)}
+BIBFS_LENGTHS = (1, 2, 3, 4, 5, 255, 256, 257, 511, 512, 513, 769, 1025)
+BIBFS_TIES = (1, 5, 64)
+BIBFS_FAR = (5, 6, 7, 8, 9)
+
+
+class BibfsGadgets:
+    """V, the edge table, and the rows as columns: rs, rd, dist (the builder's claim, -1 = no path; the tests take the oracle's),
+    fam (family), q (the bibfs_queue the row is built for, 0: any), a and b (positions: F, i; slots: gadget, slot or -1 for the
+    decoy row; queue: level size; cap: frontier work; tie: k; far: distance, kind).  slots: per gadget (L, start offset mod 4,
+    frontier vertex, is it the last vertex with edges)."""
+
+    def __init__(self, V, src, dst, rs, rd, dist, fam, q, a, b, slots):
+        self.V, self.src, self.dst, self.rs, self.rd, self.dist, self.fam, self.q, self.a, self.b = V, src, dst, rs, rd, dist, fam, q, a, b
+        self.slots = slots
+
+    def transposed(self):
+        """Every edge and every row reversed: the backward side walks what the forward side walked."""
+        return BibfsGadgets(self.V, self.dst, self.src, self.rd, self.rs, self.dist, self.fam, self.q, self.a, self.b, self.slots)
+
+    def rows_where(self, fam, q=None):
+        return np.flatnonzero((self.fam == fam) & ((self.q == q) if q is not None else True))
+
+    def tag(self, r):
+        return "%s(%d, %d) for bibfs_queue %d" % (self.fam[r], self.a[r], self.b[r], self.q[r])
+
+
+class _Builder:
+    def __init__(self):
+        self.n, self.es, self.ed, self.rows = 0, [], [], []
+
+    def new(self, n=None):
+        at = self.n
+        self.n += 1 if n is None else n
+        return at if n is None else np.arange(at, at + n, dtype=np.int64)
+
+    def edge(self, a, b):
+        a, b = np.broadcast_arrays(np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64))
+        self.es.append(a.ravel()), self.ed.append(b.ravel())
+
+    def n_edges(self):
+        return sum(len(x) for x in self.es)
+
+    def hub(self):
+        """A vertex with BIBFS_HUB in-edges from eight sources nothing leads to: a destination with an in-edge from it has a
+        backward side that costs more than any forward level here once it has been expanded by one level."""
+        g = self.new()
+        self.edge(np.repeat(self.new(8), BIBFS_HUB // 8), g)
+        return g
+
+    def row(self, s, d, dist, fam, q, a, b):
+        self.rows.append((int(s), int(d), dist, fam, q, a, b))
+
+    def finish(self, slots=()):
+        col = lambda k, t: np.array([r[k] for r in self.rows], dtype=t)
+        return BibfsGadgets(self.n, np.concatenate(self.es), np.concatenate(self.ed), col(0, np.int64), col(1, np.int64), col(2, np.int64),
+                            col(3, object), col(4, np.int64), col(5, np.int64), col(6, np.int64), list(slots))
+
+
+def bibfs_gadgets():
+    """One graph, seven families (the `stale` family is bibfs_stale_gadgets: it needs ids of its own).  No family rests on where
+    a vertex lands in the frontier queue: a family asks one row per member, and every queue position or list slot is the only
+    witness of exactly one row.  A guarded destination t has two in-edges, one from its path and one from the hub: the backward
+    side expands t once and is dearer than the forward side from then on, so the forward side walks the level under test and
+    meets the path's last inner vertex there (test_bibfs_gadgets_cpu.py asserts this on the model's trace)."""
+    B = _Builder()
+    g = B.hub()
+    sink = B.new()
+    # positions: s -> f_i -> u_i -> t_i; the row (s, t_i) is met where the walk over the F queue positions reaches f_i's list
+    for q, Fs in sorted(BIBFS_POSITIONS.items()):
+        for F, thirds in [(F, False) for F in Fs] + ([(1024, True)] if q == 1024 else []):
+            s, f, u, t = B.new(), B.new(F), B.new(F), B.new(F)
+            live = np.arange(F) % 3 != 1 if thirds else np.ones(F, dtype=bool)  # every third f_i a dead end between live ones
+            B.edge(s, f), B.edge(f[live], u[live]), B.edge(u, t), B.edge(g, t)
+            for i in range(F):
+                B.row(s, t[i], 3 if live[i] else -1, "positions", q, F + (1 << 20 if thirds else 0), i)
+    # queue: a level of Q new vertices on the only path
+    for q in (1024, 2048):
+        for Q in (q, q + 1):
+            s, f, m, t = B.new(), B.new(Q), B.new(4), B.new()
+            B.edge(s, f), B.edge(f, m[0]), B.edge(m[:-1], m[1:]), B.edge(m[-1], t), B.edge(g, t)
+            B.row(s, t, 6, "queue", q, Q, 0)
+    # cap: the forward side's work is C when a + b = 6, on a path of 8 edges
+    for C in (BIBFS_TEST_CAP, BIBFS_TEST_CAP + 1):
+        s, p, y, m, t = B.new(), B.new(5), B.new(C), B.new(), B.new()
+        B.edge(s, p[0]), B.edge(p[:-1], p[1:]), B.edge(p[-1], y), B.edge(y, m), B.edge(m, t), B.edge(g, t)
+        B.row(s, t, 8, "cap", 0, C, 0)
+    # tie: equal work on both sides and no path; the forward side covers 2 k entries, the backward side k
+    for k in BIBFS_TIES:
+        s, u, v, d, ds = B.new(), B.new(k), B.new(), B.new(), B.new(k)
+        B.edge(s, u), B.edge(u, v), B.edge(ds, d)
+        B.row(s, d, -1, "tie", 0, k, 0)
+    # far: two fans of three joined by a chain
+    ends = []
+    for D in BIBFS_FAR:
+        s, a, m, b, t = B.new(), B.new(3), B.new(D - 3), B.new(3), B.new()
+        B.edge(s, a), B.edge(a, m[0]), B.edge(m[:-1], m[1:]), B.edge(m[-1], b), B.edge(b, t)
+        B.row(s, t, D, "far", 0, D, 0), B.row(t, s, -1, "far", 0, D, 1), B.row(a[1], t, D - 1, "far", 0, D, 2)
+        for s0, t0 in ends:
+            B.row(s, t0, -1, "far", 0, D, 3), B.row(s0, t, -1, "far", 0, D, 3)
+        ends.append((s, t))
+    # slots: s -> f, f's list x_0 .. x_{L-1}, x_j -> t_j.  The lists of [aligner, pad, f, above] stand side by side at the end of
+    # the adjacency: the aligner brings the offset to a multiple of 4, the pad's k entries put f's list at offset k mod 4, and
+    # the pad's and the upper neighbour's entries are the decoy row's destination: an unmasked head or tail meets it
+    todo = [(L, k, False) for L in BIBFS_LENGTHS for k in range(4)] + [(257, 3, True)]
+    low = []
+    for L, k, last in todo:
+        s, x, t, dstar = B.new(), B.new(L), B.new(L), B.new()
+        B.edge(x, t), B.edge(g, t), B.edge(g, dstar)
+        low.append((s, x, t, dstar))
+    at = B.n_edges() + len(todo)  # every edge of a source below the quads, the s -> f edges included
+    slots = []
+    for n, ((L, k, last), (s, x, t, dstar)) in enumerate(zip(todo, low)):
+        al, pad, f = B.new(), B.new(), B.new()
+        B.edge(s, f)
+        B.edge(np.full(-at % 4, al), sink), B.edge(np.full(k, pad), dstar), B.edge(f, x)
+        at += -at % 4 + k
+        assert at % 4 == k
+        at += L
+        if not last:
+            B.edge(np.full(3, B.new()), dstar)
+            at += 3
+        slots.append((L, k, f, last))
+        for j in range(L):
+            B.row(s, t[j], 3, "slots", 0, n, j)
+        B.row(s, dstar, -1, "slots", 0, n, -1)
+    return B.finish(slots)
+
+
+BIBFS_SHIPPED_CAP = 8 << 20  # pgq_internal.h, `int bibfs_cap = 8 << 20;`
+
+
+def bibfs_calls(g):
+    """The calls the families are asked in: (name, family, bibfs_queue, bibfs_cap, row indices)."""
+    out = []
+    for fam, q in (("positions", 1024), ("positions", 2048), ("slots", 0), ("queue", 1024), ("queue", 2048), ("cap", 0), ("tie", 0), ("far", 0)):
+        out.append(("%s_%d" % (fam, q) if q else fam, fam, q or 1024, BIBFS_TEST_CAP if fam == "cap" else BIBFS_SHIPPED_CAP, g.rows_where(fam, q)))
+    return out
+
+
+def bibfs_stale_gadgets(grid, qcap=1024):
+    """Rows that leave a global map dirty, and behind each, on the same workgroup, a row that needs it clean.  Per variant
+    (the dirty row lists qcap - 1, qcap, qcap + 1 words): a -> c_1 .. c_T -> d', every c_i alone in its map word; the dirty row
+    (a, z) has no path and a dear backward side, so the forward side marks every c_i.  Victim (s', d') has no path and a dear
+    forward side: its backward side reaches every c_i and meets nothing, unless a forward bit of the row before is still
+    there.  Victim (s''_w, d') is two hops apart by s''_w -> c_w: a forward bit of c_w left behind drops c_w from its
+    frontier.  d' stands in a's map word, so the last words listed are the c_i's.  Laid out as grid dirty rows, grid victims,
+    grid dirty rows, grid victims of the second kind: workgroup w of a bulk call with `grid` workgroups runs one of each,
+    in this order (the device queues rows per wavefront of 64 in the order their atomics land: a call whose wavefronts land out
+    of order checks less, never wrongly).  Returns the gadgets (a: listed words, b: 0 dirty, 1, 2 the victims) and T per variant."""
+    B = _Builder()
+    dear = 1400  # entries of a dear side: more than T + grid, in lists of four vertices (a level of four)
+    assert qcap - 2 + grid < dear and grid < qcap - 4
+    Ts = {}
+    for listed in (qcap - 1, qcap, qcap + 1):
+        T = listed - 3  # the row's own two words, the c_i's, the spare word of the forward map
+        Ts[listed] = T
+        base = (B.n + 31) // 32 * 32
+        B.n = base + 32 * (T + 2)
+        a, dp, c = base, base + 1, base + 32 * np.arange(1, T + 1, dtype=np.int64)
+        z, sp, s2 = B.new(), B.new(), B.new(grid)
+        B.edge(a, c), B.edge(c, dp), B.edge(np.repeat(B.new(4), dear // 4), z), B.edge(sp, np.repeat(B.new(4), dear // 4)), B.edge(s2, c[:grid])
+        for kind, (ss, dd, dist) in enumerate((([a] * grid, z, -1), ([sp] * grid, dp, -1), ([a] * grid, z, -1), (s2, dp, 2))):
+            for s in ss:
+                B.row(s, dd, dist, "stale", qcap, listed, (0, 1, 0, 2)[kind])
+    return B.finish(), Ts

@@ -4,9 +4,11 @@ band-wise label correcting per row), the packed list walk of the pre-pass (pgq_w
 (pgq_cheapest.hip: rounds over weight-sorted lists under a doubling cap with per-lane bounds).  The models follow the kernels' control flow (side selection, termination tests,
 far-queue refill with band skipping, duplicates in the near queue, arbitrary relaxation order) and are compared with the
 oracle's per-pair BFS / Dijkstra.  They exist to pin the *schedule*; the kernels themselves are checked on the GPU
-(tests/test_gpu_parity.py: test_bibfs_few_open_rows_any_distance, test_weighted_pair_search_bit_exact)."""
+(tests/test_gpu_parity.py: test_bibfs_few_open_rows_any_distance, test_weighted_pair_search_bit_exact;
+tests/test_bibfs_limits_gpu.py).  k_bibfs's model lives in tests/bibfs_model.py, with its caps, queue, bound and list walk."""
 import numpy as np
 
+from bibfs_model import bibfs_model  # k_bibfs restated in full (caps, queue, bound, list walk); here: its side rule and termination
 from oracle.pgq_oracle import OracleCSR
 
 INF = 1 << 62
@@ -25,34 +27,6 @@ def _csr(V, s, d, w=None):
     roff = np.cumsum(roff)
     ww = w[order] if w is not None else None
     return off, adj, roff, radj, ww, (ww[ro] if w is not None else None), order
-
-
-def bibfs_model(off, adj, roff, radj, s, d):
-    """k_bibfs: expand the side whose frontier has fewer adjacency entries; first meeting = a + b + 1."""
-    if s == d:
-        return 0
-    seen = [{s}, {d}]
-    front = [[s], [d]]
-    lvl = [0, 0]
-    X = [(off, adj), (roff, radj)]
-    while True:
-        work = [sum(int(X[k][0][v + 1] - X[k][0][v]) for v in front[k]) for k in (0, 1)]
-        side = 0 if work[0] <= work[1] else 1
-        o, a = X[side]
-        nxt, hit = [], False
-        for v in front[side]:
-            for u in a[o[v]:o[v + 1]].tolist():
-                if u in seen[side ^ 1]:
-                    hit = True
-                if u not in seen[side]:
-                    seen[side].add(u)
-                    nxt.append(u)
-        if hit:
-            return lvl[0] + lvl[1] + 1
-        if not nxt:
-            return None  # this side's closure is complete
-        front[side] = nxt
-        lvl[side] += 1
 
 
 def wbibfs_model(off, adj, w, roff, radj, rw, s, d, delta, rng, prune=False):
