@@ -2,12 +2,12 @@
 // max_paths of them as lists, for SQL/PGQ's ALL SHORTEST.  The reference has no counterpart: its binder rejects the form
 // ("ALL SHORTEST has not been implemented yet", match.cpp:82).  Every list follows shortestpath's layout (shortest_path.cpp:43-207).
 //
-// Part of pgq_cheapest.hip's translation unit (included at the end of pgq_cheapest_path.hip, not compiled on its own): the hop
-// counts live in that file's H table (ws->tight_h, 64 lanes per vertex, "-1 everywhere between calls"), the frontier masks and
-// queues are k_tight_levels', LC and k_fill32 are defined there.  What this call shares with k_shortest_walks (pgq_k_walks.hip) —
-// the saturating add and scan, the pull's inner loop, one step of the unranking, the tails kernel, the list staging, the call
-// skeleton ListCall with its layout, the C entry points' prologues and epilogues — is in pgq_path_lists.h, described there once.
-// Weights are never read: the calls work on any CSR.
+// The root file of pgq_all_shortest.o, compiled on its own.  The hop counts live in cheapest_path's H table (ws->tight_h, 64 lanes
+// per vertex, "-1 everywhere between calls"), the frontier masks and queues are k_tight_levels': workspace fields with their
+// invariants (pgq_search.h), no code of pgq_cheapest_path.o.  From pgq_relax.h: LC and fill32, nothing else.  What this call
+// shares with k_shortest_walks (pgq_k_walks.o) — the saturating add and scan, the pull's inner loop, one step of the unranking,
+// the tails kernel, the list staging, the call skeleton ListCall with its layout, the C entry points' prologues and epilogues —
+// is in pgq_path_lists.h, described there once.  Weights are never read: the calls work on any CSR.
 //
 // The contract, for a row (src, dst).  L[v] = the BFS level of v from src, d = L[dst];
 //   sigma[src] = 1,  sigma[x] = min(INT64_MAX, sum of sigma[u] over the in-slots (u, x) with L[u] = L[x] - 1)
@@ -49,6 +49,8 @@
 // cheapest_path) and sigma (from the block cache for the call).
 // Not built: _multi forms, splitting long in-lists over several wavefronts (a list is walked by the one wavefront that meets
 // it), sharing prefixes between the paths of one row, any change to how shortestpath or iterativelength are routed.
+
+#include "pgq_path_lists.h"
 
 namespace pgq {
 
@@ -293,7 +295,8 @@ private:
 
 	// H as PathBatches::prepare keeps it (shared with cheapest_path: tight_V says for which V "-1 everywhere" holds)
 	int prepare() {
-		PGQ_TRY(ws->tight_cnt.reserve(std::max(sizeof(AspCounters), sizeof(TightCounters))));
+		static_assert(sizeof(AspCounters) <= Workspace::kTightCntBytes, "counter block too small");
+		PGQ_TRY(ws->tight_cnt.reserve(Workspace::kTightCntBytes));
 		tc = ws->tight_cnt.as<AspCounters>();
 		if (out.lists) PGQ_TRY(ensure_edge_ids(c));
 		for (DevBuf &b : ws->tight_mask) PGQ_TRY(b.reserve(Vn * 8));
@@ -304,7 +307,7 @@ private:
 		const bool fresh = ws->tight_h.cap < cells * 4 || ws->tight_V != c->V;
 		ws->tight_V = -1; // stays invalid if the call bails out half-way
 		PGQ_TRY(ws->tight_h.reserve(cells * 4));
-		if (fresh) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, ws->tight_h.as<int32_t>(), (int64_t)cells, -1);
+		if (fresh) fill32(ws->tight_h.as<int32_t>(), (int64_t)cells, -1, st);
 		for (DevBuf &b : ws->tight_mask) PGQ_HIP_TRY(hipMemsetAsync(b.p, 0, Vn * 8, st));
 		return PGQ_OK;
 	}

@@ -21,6 +21,11 @@
 // pgq_cheapest_path_length_within (the cheapest walk of at most K edges: another number, not this one clamped) cannot use these
 // rounds, in which a label travels several edges per launch; its round of exactly one edge is k_hop_snapshot + k_relax_hops
 // under HopBatches, further down.
+//
+// This file is pgq_cheapest.o, alone.  What cheapest_path and cheapest_path_within (pgq_cheapest_path.o) take from it is declared in
+// pgq_relax.h and defined here: LC, Inf, RelaxCounters, the hooks SettledBatch and HopLog, the handle's weight tables
+// (ensure_reverse_weights, ensure_weight_mean), check_weighted, fill32, and the two functions that run the lane batches with a hook
+// (settle_every_label, hop_rounds_logged, at the end of namespace pgq).  Everything else here is this file's own.
 #include <hipcub/hipcub.hpp>
 
 #include <cstddef>
@@ -28,24 +33,13 @@
 #include <limits>
 #include <type_traits>
 
-#include "pgq_search.h"
+#include "pgq_relax.h"
 #include <chrono>
 #include <thread>
 #include <vector>
 #include <string>
 
 namespace pgq {
-
-static constexpr int LC = 64;
-
-template <typename T> struct Inf;
-template <> struct Inf<int64_t> {
-	static constexpr int64_t bits = std::numeric_limits<int64_t>::max() / 2; // cheapest_path_length.cpp:15
-};
-template <> struct Inf<double> {
-	// bit pattern of DBL_MAX / 2 = 0x7FDFFFFFFFFFFFFF
-	static constexpr int64_t bits = 0x7FDFFFFFFFFFFFFFll;
-};
 
 // Label STORAGE of the batched relaxation (round 5): int64 weights whose largest possible path sum fits 31 bits
 // (w_max x V < 2^31 - 1: weights 1..999 on the 448 K-vertex knows graph are at 4.5 x 10^8) keep their labels as int32 —
@@ -73,6 +67,9 @@ __global__ void k_fill32(int32_t *__restrict__ p, int64_t n, int32_t value) {
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	int64_t stride = (int64_t)gridDim.x * blockDim.x;
 	for (; i < n; i += stride) p[i] = value;
+}
+void fill32(int32_t *p, int64_t n, int32_t value, hipStream_t st) {
+	hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, p, n, value);
 }
 __global__ void k_fill64(int64_t *__restrict__ p, int64_t n, int64_t value) {
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -453,19 +450,7 @@ __global__ __launch_bounds__(256) void k_lane_bounds(int64_t lo, int64_t hi, con
 	if (threadIdx.x < 64 && s_b[threadIdx.x] > 0) atomicMax(&bound[threadIdx.x], s_b[threadIdx.x]);
 }
 
-struct RelaxCounters {
-	u32 nq[2];
-	u32 tcount;
-	u32 rounds; // rounds executed by the last k_relax_small launch
-	u64 relaxed_edges;
-	long long min_deferred; // smallest label (bit pattern) a round left for later (k_relax's threshold)
-	u32 relaxed_vertices;   // vertices a round expanded
-	u32 snap_rows;          // label rows k_hop_snapshot copied (hop-bounded rounds; runs on over a batch, like `rounds` there)
-	u64 heavy;              // (entries << 32) | chunks of the round's heavy list (k_relax)
-	long long bound[64];    // per lane: the largest tentative label among its destinations (nothing beyond it matters)
-};
-
-// the start of a round: the next queue's count, the round's statistics, the lanes' bounds
+// the start of a round (RelaxCounters: pgq_relax.h): the next queue's count, the round's statistics, the lanes' bounds
 __global__ void k_round_reset(RelaxCounters *__restrict__ rc, int next_par) {
 	const int t = threadIdx.x;
 	if (t < 64) rc->bound[t] = 0;
@@ -993,7 +978,7 @@ static std::mutex g_rw_lock;
 // in-edge weights in reverse-CSR order + the mean weight, built on first use (a stable sort of the forward slots by
 // destination: the permutation the upload used for radj).  with_mean = false: the weights alone, w_mean stays what it is (the
 // sum below adds the weights as int64: cheapest_path reads the in-edge weights of double CSRs too)
-static int ensure_reverse_weights(pgq_csr *c, Workspace *ws, bool with_mean = true) {
+int ensure_reverse_weights(pgq_csr *c, Workspace *ws, bool with_mean) {
 	std::lock_guard<std::mutex> g(g_rw_lock);
 	if (c->E == 0) return PGQ_OK;
 	// (a copy that cheapest_path built came without the mean: a caller that wants one gets it here, unless the handle has it)
@@ -1089,7 +1074,7 @@ static int ensure_weight_sorted(pgq_csr *c, Workspace *ws) {
 }
 
 // mean edge weight (int64 or double), computed once per CSR: the band width of the ordered relaxation rounds
-static int ensure_weight_mean(pgq_csr *c, Workspace *ws) {
+int ensure_weight_mean(pgq_csr *c, Workspace *ws) {
 	std::lock_guard<std::mutex> g(g_rw_lock);
 	if (c->w_mean > 0 || c->E == 0 || !c->w) return PGQ_OK;
 	hipStream_t st = ws->stream;
@@ -1267,7 +1252,7 @@ template <typename DT> int RelaxSide::prepare(int64_t V, int type_tag, DT inf_la
 	PGQ_TRY(dist.reserve(cells * sizeof(DT)));
 	for (DevBuf &b : dirty) PGQ_TRY(b.reserve(Vn * 8));
 	for (DevBuf *b : { &q[0], &q[1], &touched, &tflag }) PGQ_TRY(b->reserve(Vn * 4));
-	if (fresh && sizeof(DT) == 4) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, dist.as<int32_t>(), (int64_t)cells, (int32_t)inf_label);
+	if (fresh && sizeof(DT) == 4) fill32(dist.as<int32_t>(), (int64_t)cells, (int32_t)inf_label, st);
 	if (fresh && sizeof(DT) == 8) hipLaunchKernelGGL(k_fill64, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, dist.as<int64_t>(), (int64_t)cells, (int64_t)inf_label);
 	for (DevBuf &b : dirty) PGQ_HIP_TRY(hipMemsetAsync(b.p, 0, Vn * 8, st));
 	PGQ_HIP_TRY(hipMemsetAsync(tflag.p, 0, Vn * 4, st));
@@ -1388,14 +1373,7 @@ struct RelaxWorker {
 	}
 };
 
-// What cheapest_path asks of the lane batches (pgq_cheapest_path.hip) instead of the rows' costs: the labels of EVERY vertex a
-// lane reaches settled (no lane stops at its destinations' bound: see k_lane_unbound), and a call per settled batch — rows
-// [lo, hi) of the sorted arrays, lane 0 = distinct source `base` — while the batch's labels are still in place.
-struct SettledBatch {
-	std::function<int(int64_t lo, int64_t hi, int64_t base)> then;
-};
-
-// The lanes' bounds of a round for a driver that needs every label final, not only the destinations': k_lane_bounds prunes a
+// The lanes' bounds of a round for a driver that needs every label final (SettledBatch, pgq_relax.h), not only the destinations': k_lane_bounds prunes a
 // lane at the largest tentative label B among its destinations, which leaves the vertices with a final label of exactly B
 // unexpanded — and what lies behind them over zero-weight edges (final label B as well) unlabelled or too high.  A tight edge
 // into a destination may come from just there.  Without a bound the rounds run to the fixpoint of everything reachable.
@@ -1710,19 +1688,7 @@ template <typename T> static int hop_grid(unsigned *grid) { // relax_grid for k_
 // kHopGroup without a host wait — the kernels read the queue's fill on the device, k_round_reset clears the next one, a
 // round behind an empty queue does nothing — and the counter block comes back once per group.  `snap` and `snapmask`
 // live in the worker's second RelaxSide (labels, first dirty array), whose labels a later two-ended call must not trust.
-//
-// What cheapest_path_within asks of these rounds (pgq_cheapest_path_within.hip) instead of the rows' costs: the snapshot rows
-// of every round KEPT, in a log that grows round by round, and a call per finished batch while the log is in place.
-struct HopLog {
-	// In k_hop_snapshot's place: logs the `nq` vertices of the queue of parity `par` with their label rows as they stand after
-	// `round` rounds, takes their dirty words, and says where these entries' rows and masks lie — what the next k_relax_hops
-	// reads.  The host knows nq: a logged batch waits after every round, so the log has its room before a launch appends to it.
-	std::function<int(int par, u32 nq, int64_t round, const int64_t **snap, const u64 **snapmask)> append;
-	// behind the batch's last round and the log pass of the vertices it changed: rows [lo, hi) of the sorted arrays, lane 0 =
-	// distinct source `base`
-	std::function<int(int64_t lo, int64_t hi, int64_t base)> then;
-};
-
+// With a HopLog (pgq_relax.h) the snapshot rows of every round are kept instead, by the hook, and a batch ends in its `then`.
 template <typename T> class HopBatches : RelaxWorker {
 	using DT = int64_t; // 8-byte labels only
 	static constexpr int kHopGroup = 8;
@@ -2142,7 +2108,7 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	return PGQ_OK;
 }
 
-static int check_weighted(pgq_csr_t *csr) {
+int check_weighted(pgq_csr_t *csr) {
 	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	if (csr->w_type == PGQ_W_NONE || !csr->w)
 		return fail(PGQ_ERR_NOT_WEIGHTED, "Constraint Error: Need to initialize CSR before doing cheapest path");
@@ -2151,9 +2117,19 @@ static int check_weighted(pgq_csr_t *csr) {
 	return PGQ_OK;
 }
 
-} // namespace pgq
+// pgq_relax.h's two entries to the lane batches: one worker on the call's own workspace, every batch, no cost outputs.
+template <typename T> int settle_every_label(pgq_csr *c, Workspace *ws, int nb, u32 U, const SettledBatch &settled) {
+	return RelaxBatches<T, int64_t>(RelaxWorker { c, ws, ws, nb, nullptr, nullptr }, U, false, &settled).run(0, 1);
+}
+template <typename T> int hop_rounds_logged(pgq_csr *c, Workspace *ws, int nb, u32 U, int64_t K, const HopLog &log) {
+	return HopBatches<T>(RelaxWorker { c, ws, ws, nb, nullptr, nullptr }, U, K, &log).run(0, 1);
+}
+template int settle_every_label<int64_t>(pgq_csr *, Workspace *, int, u32, const SettledBatch &);
+template int settle_every_label<double>(pgq_csr *, Workspace *, int, u32, const SettledBatch &);
+template int hop_rounds_logged<int64_t>(pgq_csr *, Workspace *, int, u32, int64_t, const HopLog &);
+template int hop_rounds_logged<double>(pgq_csr *, Workspace *, int, u32, int64_t, const HopLog &);
 
-#include "pgq_cheapest_path.hip" // cheapest_path: the list next to the cost, on this file's relaxation state and k_relax launches
+} // namespace pgq
 
 using namespace pgq;
 

@@ -2,8 +2,11 @@
 // the cost pgq_cheapest_path_length returns.  The reference has no counterpart (its Bellman-Ford keeps no parents,
 // cheapest_path_length.cpp:52-136); the list follows shortestpath's layout (shortest_path.cpp:43-207).
 //
-// Part of pgq_cheapest.hip's translation unit (included at its end, not compiled on its own): the labels are settled by that
-// file's relaxation state (RelaxSide), its lane batches (RelaxBatches) and its k_relax launches, whose instantiations live there.
+// The root file of pgq_cheapest_path.o, with pgq_cheapest_path_within.hip included further down (PathBatches and path_call are
+// theirs and nobody else's).  The labels are settled in pgq_cheapest.o — its relaxation state (RelaxSide), its lane batches and
+// its k_relax launches — through pgq_relax.h: settle_every_label with a SettledBatch hook, LC, Inf, RelaxCounters::tcount,
+// ensure_reverse_weights, ensure_weight_mean, check_weighted, fill32.  From pgq_path_lists.h: ListStage and
+// stage_rows_null_as_minus_one.
 //
 // The contract.  D[v] = the labels pgq_cheapest_path_length defines: the least fixpoint of dist[n] = min(dist[n], dist[v] + w)
 // from dist[src] = 0 under INF = max(T) / 2, in the reference's arithmetic (cheapest_path_length.cpp:29-36), int64 and double.
@@ -21,7 +24,7 @@
 // its predecessor's final write).  Two consequences the tests use: the left-to-right fold of the weights of e_1 .. e_k is
 // pgq_cheapest_path_length's result, bit for bit; with one positive int64 weight on every edge the list is shortestpath's.
 //
-// Per lane batch (at most 64 distinct sources, lane l = search l, LC as in pgq_cheapest.hip):
+// Per lane batch (at most 64 distinct sources, lane l = search l, LC is pgq_relax.h's):
 //   1. D settles through RelaxBatches over the plain, unsorted lists with 8-byte labels and WITHOUT the lanes' destination
 //      bounds (SettledBatch / k_lane_unbound: a pruned lane leaves the labels at its bound unsettled, and a zero-weight tight edge
 //      into a destination comes from exactly there).  The 4-byte labels, the light-edges-first lists, the chain pre-pass and the
@@ -43,10 +46,14 @@
 // pgq_cheapest_path_within.hip, on this file's staging, layout and entry points (PathBatches, path_call).
 // Not built: _multi, the two-ended search, and any speed-up of the level rounds (a long list is walked by the one wavefront
 // that finds it).
-// pgq_path_lists.h is included at this file's head: the staging of a batch's lists (ListStage) that every driver here uses, and
-// what the nested-list calls share.  pgq_all_shortest.hip (shortestpath_count, all_shortestpaths) is included at this file's end:
-// it keeps its BFS levels in H.  pgq_k_walks.hip (walk_count, k_shortest_walks) comes behind it, with tables of its own.
+// H, the frontier masks and the queues (ws->tight_*) also serve pgq_all_shortest.o, which keeps its BFS levels there: the
+// workspace's fields and their invariants (pgq_search.h) are all the two objects share.
+#include <hipcub/hipcub.hpp>
 
+#include <type_traits>
+#include <vector>
+
+#include "pgq_relax.h"
 #include "pgq_path_lists.h"
 
 namespace pgq {
@@ -259,7 +266,8 @@ public:
 	ListStage stage; // the places of a batch's lists and the room for them: also for a driver with a walk-back of its own
 
 	int prepare() {
-		PGQ_TRY(ws->tight_cnt.reserve(sizeof(TightCounters)));
+		static_assert(sizeof(TightCounters) <= Workspace::kTightCntBytes, "counter block too small");
+		PGQ_TRY(ws->tight_cnt.reserve(Workspace::kTightCntBytes));
 		tc = ws->tight_cnt.as<TightCounters>();
 		PGQ_TRY(ensure_reverse_weights(c, ws, false));
 		PGQ_TRY(ensure_edge_ids(c));
@@ -270,7 +278,7 @@ public:
 		const bool fresh = ws->tight_h.cap < cells * 4 || ws->tight_V != c->V;
 		ws->tight_V = -1; // stays invalid if the call bails out half-way
 		PGQ_TRY(ws->tight_h.reserve(cells * 4));
-		if (fresh) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, ws->tight_h.as<int32_t>(), (int64_t)cells, -1);
+		if (fresh) fill32(ws->tight_h.as<int32_t>(), (int64_t)cells, -1, st);
 		for (DevBuf &b : ws->tight_mask) PGQ_HIP_TRY(hipMemsetAsync(b.p, 0, Vn * 8, st));
 		return PGQ_OK;
 	}
@@ -385,7 +393,7 @@ private:
 };
 
 // The rows of one call (device memory, src < 0 = NULL row): lengths, offsets and lists.  One worker: the batches share the
-// staging buffer and the hop counts.  run(paths, worker, U) settles the lane batches and stages their lists through `paths`;
+// staging buffer and the hop counts.  run(paths, nb, U) settles the nb lane batches and stages their lists through `paths`;
 // levels: PathBatches' own tight levels and walk-back are part of it.
 struct PathOut {
 	int64_t *d_len, *d_off, *d_child, child_cap, *child_used;
@@ -408,17 +416,16 @@ static int path_call(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src,
 	PathBatches<T> paths(c, ws, U, out.d_len, levels);
 	if (nb > 0) {
 		PGQ_TRY(paths.prepare());
-		const RelaxWorker w { c, ws, ws, nb, nullptr, nullptr };
-		PGQ_TRY(run(paths, w, U));
+		PGQ_TRY(run(paths, nb, U));
 		paths.settle();
 	}
 	return paths.layout(n, out.d_off, out.d_child, out.child_cap, out.child_used, out.overflow);
 }
 
 template <typename T> static int cheapest_path_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out) {
-	return path_call<T>(c, ws, n, d_src, d_dst, out, true, [&](PathBatches<T> &paths, const RelaxWorker &w, u32 U) {
+	return path_call<T>(c, ws, n, d_src, d_dst, out, true, [&](PathBatches<T> &paths, int nb, u32 U) {
 		const SettledBatch settled { [&](int64_t lo, int64_t hi, int64_t base) { return paths.batch(lo, hi, base); } };
-		return RelaxBatches<T, int64_t>(w, U, false, &settled).run(0, 1);
+		return settle_every_label<T>(c, ws, nb, U, settled);
 	});
 }
 
@@ -518,6 +525,3 @@ int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 }
 
 } // extern "C"
-
-#include "pgq_all_shortest.hip" // shortestpath_count / all_shortestpaths: level rounds on this file's H table, masks and queues; ListCall's skeleton
-#include "pgq_k_walks.hip"      // walk_count / k_shortest_walks: rounds over all walks of lower..upper edges, tables of their own; ListCall's skeleton

@@ -2,8 +2,9 @@
 // list [src, e1, v1, ..., eh, dst], next to the cost pgq_cheapest_path_length_within returns.  The reference has no
 // counterpart; the list follows shortestpath's layout, the tie-breaks are shortestpath's and pgq_cheapest_path's.
 //
-// Part of pgq_cheapest.hip's translation unit (included by pgq_cheapest_path.hip, not compiled on its own): the rounds are
-// HopBatches' (k_relax_hops, one edge per round), the staging, the layout and the child-capacity protocol PathBatches'.
+// Part of pgq_cheapest_path.o: included by pgq_cheapest_path.hip behind PathBatches and path_call, whose staging, layout and
+// child-capacity protocol it uses; not compiled on its own.  The rounds are HopBatches' in pgq_cheapest.o (k_relax_hops, one edge
+// per round), reached through pgq_relax.h: hop_rounds_logged with a HopLog hook, LC, Inf, RelaxCounters::tcount, fill32.
 //
 // The contract.  D_0 .. D_K = the labels of pgq_cheapest_path_length_within for the row's source and K = max_hops (HopBatches'
 // header), INF = max(T) / 2, every sum computed as the relaxation computes it (relax_sum); NaN and +inf weights never relax an
@@ -35,7 +36,7 @@
 //      answers [0, ., 1, ., 2, ., 3].  Both fold to 2^53.  So a large K is NOT forwarded to pgq_cheapest_path: the hop rounds
 //      run until the queue is empty.
 //
-// Per lane batch (one worker; lane l = search l, LC as in pgq_cheapest.hip):
+// Per lane batch (one worker; lane l = search l, LC is pgq_relax.h's):
 //   1. The rounds are HopBatches' with a HopLog: in k_hop_snapshot's place k_hop_log APPENDS the queue's label rows to a log
 //      instead of overwriting last round's.  Entry g: the 512-byte row of its vertex v as it stood after round r (every lane,
 //      changed or not), the mask of the lanes that changed in round r, r, and prev[g], v's entry before this one;
@@ -195,7 +196,7 @@ public:
 		const bool fresh = ws->hop_last.cap < Vn * 4 || ws->hop_last_V != c->V;
 		ws->hop_last_V = -1; // stays invalid if the call bails out half-way
 		PGQ_TRY(ws->hop_last.reserve(Vn * 4));
-		if (fresh) hipLaunchKernelGGL(k_fill32, dim3((unsigned)device_cus() * 8), dim3(256), 0, st, ws->hop_last.as<int32_t>(), (int64_t)Vn, -1);
+		if (fresh) fill32(ws->hop_last.as<int32_t>(), (int64_t)Vn, -1, st);
 		return PGQ_OK;
 	}
 	void settle() { ws->hop_last_V = c->V; } // behind the last batch's reset, waited for
@@ -281,11 +282,10 @@ private:
 // cheapest_path_device's bounded sibling.  Every K takes the hop rounds, K >= V - 1 included (fact 4): they end with the queue.
 template <typename T>
 static int cheapest_path_within_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops, const PathOut &out) {
-	return path_call<T>(c, ws, n, d_src, d_dst, out, false, [&](PathBatches<T> &paths, const RelaxWorker &w, u32 U) -> int {
+	return path_call<T>(c, ws, n, d_src, d_dst, out, false, [&](PathBatches<T> &paths, int nb, u32 U) -> int {
 		HopPathLog<T> log(c, ws, paths, out.d_len);
 		PGQ_TRY(log.prepare());
-		const HopLog hook = log.hook();
-		PGQ_TRY(HopBatches<T>(w, U, max_hops, &hook).run(0, 1));
+		PGQ_TRY(hop_rounds_logged<T>(c, ws, nb, U, max_hops, log.hook()));
 		log.settle();
 		if (getenv("PGQ_RELAX_TRACE")) fprintf(stderr, "hop log: peak %zu bytes in a batch\n", log.peak_bytes());
 		return PGQ_OK;

@@ -4,10 +4,10 @@
 // AND upper (match.cpp:658-671), which drops a pair at distance 1 that also has a walk of 2 edges from {2,3} and never finds a cycle
 // (src == dst is 0 hops there).  Every list follows shortestpath's layout (shortest_path.cpp:43-207).
 //
-// Part of pgq_cheapest.hip's translation unit (included at the end of pgq_cheapest_path.hip behind pgq_all_shortest.hip, not compiled
-// on its own): LC is defined there.  The saturating add, the pull's inner loop, one step of the unranking, the tails kernel, the
-// list staging and the call skeleton ListCall with its layout are all_shortestpaths' too: pgq_path_lists.h, described there once.
-// Weights are never read: the calls work on any CSR.
+// The root file of pgq_k_walks.o, compiled on its own, with pgq_walk_rule.h, pgq_path_modes.h and, at its end, pgq_walk_length.hip.
+// The saturating add, the pull's inner loop, one step of the unranking, the tails kernel, the list staging and the call skeleton
+// ListCall with its layout are all_shortestpaths' too: pgq_path_lists.h, described there once.  Of pgq_relax.h it takes LC (through
+// pgq_path_lists.h) and nothing else.  Weights are never read: the calls work on any CSR.
 //
 // The contract, for a row (src, dst), lo = min_hops, K = max_hops, over the forward CSR's slots (parallel edges are separate slots):
 //   W_0[v] = 1 if v == src else 0
@@ -68,6 +68,7 @@
 // change to how the binder's iterativelength filter is emitted; under a mode: an unbounded upper, an unlimited count, a smarter
 // prune than W, several wavefronts per row; for the groups: a count-only form.
 
+#include "pgq_path_lists.h"
 #include "pgq_walk_rule.h"
 
 namespace pgq {
@@ -401,7 +402,8 @@ private:
 	WalkRound round_of(int64_t t) const { return WalkRound { W[slot_of(t)], M[slot_of(t)] }; }
 
 	int prepare() {
-		PGQ_TRY(ws->tight_cnt.reserve(std::max(sizeof(WalkCounters), sizeof(TightCounters))));
+		static_assert(sizeof(WalkCounters) <= Workspace::kTightCntBytes, "counter block too small");
+		PGQ_TRY(ws->tight_cnt.reserve(Workspace::kTightCntBytes));
 		tc = ws->tight_cnt.as<WalkCounters>();
 		if (out.lists || query.mode == PGQ_MODE_TRAIL) PGQ_TRY(ensure_edge_ids(c));
 		if (keep_rounds) PGQ_TRY(temps.alloc(&d_tabs, (size_t)PGQ_WALK_MAX_HOPS + 1));

@@ -1,6 +1,10 @@
-// pgq_path_lists.h — what the list-producing calls of pgq_cheapest.hip's translation unit share: cheapest_path and
-// cheapest_path_within (one list per row) use the staging helper, all_shortestpaths and k_shortest_walks (a list of lists per row)
-// everything.  Included at the head of pgq_cheapest_path.hip, not compiled on its own: LC and the workspace are defined ahead of it.
+// pgq_path_lists.h — what the list-producing calls share: cheapest_path and cheapest_path_within (one list per row) use the
+// staging helper, all_shortestpaths and k_shortest_walks (a list of lists per row) everything.  A header like any other, included
+// at the head of three translation units (pgq_cheapest_path.hip, pgq_all_shortest.hip, pgq_k_walks.hip); it takes LC from
+// pgq_relax.h and the workspace from pgq_search.h.  Linkage, so that the three objects link: the device functions are
+// __forceinline__ and the host functions are class members or templates, all inline as they stand; the one kernel, k_asp_tails, is
+// `static` (a kernel cannot be `inline`) — internal linkage: each of the three objects holds and registers a copy of its own (a few hundred bytes;
+// pgq_cheapest_path.o never launches its one), and no kernel is launched from an object that does not define it; the one plain host function, stage_rows_null_as_minus_one, is `inline`, one copy in the library.
 //
 // Device side, for pgq_all_shortest.hip and pgq_k_walks.hip (their headers give the contracts):
 //   asp_sat_add, wave_sat_scan   the saturating add and its inclusive scan over a wavefront
@@ -20,6 +24,15 @@
 //               and behind the last batch the tails, the scans in row order, capacities, the gather and the caller's arrays (layout).
 //               Nothing reaches the caller's arrays before layout.
 //   the C entry points' shared checks, prologues and epilogues.
+#pragma once
+
+#include <hipcub/hipcub.hpp>
+
+#include <string>
+#include <vector>
+
+#include "pgq_relax.h"
+#include "pgq_search.h"
 
 namespace pgq {
 
@@ -136,7 +149,7 @@ __device__ __forceinline__ UnrankStep unrank_step(int x, int64_t &r, int lane, c
 // Rows without a lane.  Trivial ([lo_trivial, lo_null)): src == dst — one list, [src], of no hops when min_hops == 0, nothing
 // otherwise; the others: a NULL endpoint (count -1) or a row that cannot have a path (0).  r_np == null: the counts alone.
 // r_ng != null (k_shortest_groups): the row's groups, 1 with the list and 0 without.
-__global__ void k_asp_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, int64_t min_hops, const u32 *__restrict__ sidx, const int64_t *__restrict__ src,
+[[maybe_unused]] static __global__ void k_asp_tails(int64_t lo_trivial, int64_t lo_null, int64_t n, int64_t min_hops, const u32 *__restrict__ sidx, const int64_t *__restrict__ src,
                             const int64_t *__restrict__ dst, int64_t *__restrict__ r_len, int64_t *__restrict__ r_count, int64_t *__restrict__ r_np,
                             int64_t *__restrict__ r_el, int64_t *__restrict__ r_ng) {
 	const int64_t i = lo_trivial + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,7 +354,7 @@ private:
 // ---- the C entry points' shared pieces --------------------------------------------------------------------------------------
 
 // the chunk forms' rows on the device: NULL src or NULL dst -> -1
-static int stage_rows_null_as_minus_one(Workspace *ws, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst) {
+inline int stage_rows_null_as_minus_one(Workspace *ws, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst) {
 	FlatPairs fp;
 	PGQ_TRY(flatten_pairs(V, n, src, dst, fp, true));
 	for (int64_t i = 0; i < n; i++)

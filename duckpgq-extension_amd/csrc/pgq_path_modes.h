@@ -1,6 +1,6 @@
 // pgq_path_modes.h — SHORTEST k under the path modes TRAIL, ACYCLIC and SIMPLE: the search kernel of pgq_k_shortest_walks_mode and
-// pgq_walk_count_mode.  Included into pgq_k_walks.hip behind the walk rounds (WalkRound, walk_w, WalkCounters), not compiled on its
-// own.  The reference's binder rejects every mode but WALK ("Path modes other than WALK have not been implemented yet",
+// pgq_walk_count_mode.  Part of pgq_k_walks.o: included into pgq_k_walks.hip behind the walk rounds (WalkRound, walk_w, WalkCounters;
+// unrank_slot is pgq_path_lists.h's), not compiled on its own.  The reference's binder rejects every mode but WALK ("Path modes other than WALK have not been implemented yet",
 // match.cpp:80-108) and at the same place tells its users to pick one when ALL over a cyclic graph explodes (match.cpp:100-104).
 //
 // The contract, for a row (src, dst), lo = min_hops, K = max_hops.  S = every walk of lo..K edges in k_shortest_walks' order (by

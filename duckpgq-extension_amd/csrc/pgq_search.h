@@ -314,7 +314,10 @@ struct Workspace {
 	void *h_bi = nullptr;  // pinned: the bidirectional relaxation's counter block, copied back once per round
 	// cheapest_path (pgq_cheapest_path.hip): tight hop counts H[V][64] (-1 = none; a batch resets what it set, tight_V says for
 	// which V that holds), the frontier of a tight-level round (lane masks and vertex queues by round parity), its counters, the
-	// lists of the finished batches in batch order
+	// lists of the finished batches in batch order.  tight_cnt is ONE small block that the list-producing drivers overlay their own
+	// counter struct on, one call at a time (TightCounters, AspCounters, WalkCounters): each reserves kTightCntBytes and asserts
+	// that its struct fits
+	static constexpr size_t kTightCntBytes = 64;
 	DevBuf tight_h, tight_mask[2], tight_q[2], tight_cnt, tight_stage;
 	int64_t tight_V = -1;
 	// cheapest_path_within (pgq_cheapest_path_within.hip): the round log of one lane batch — per entry the 512-byte label row,

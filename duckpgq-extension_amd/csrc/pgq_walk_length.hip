@@ -4,8 +4,8 @@
 // walk of 2 edges from {2,3} and never finds a cycle.  walk_count (> 0) and k_shortest_walks(k = 1) answer the same question with a
 // V x 64 table of 8-byte counts per round, every row through whole-graph rounds; this call needs neither.
 //
-// Part of pgq_cheapest.hip's translation unit (included at the end of pgq_k_walks.hip, not compiled on its own): k_walk_activate, the
-// counter block, walk_query / walk_check and the chunk forms' shared pieces are that file's and pgq_path_lists.h's.
+// Part of pgq_k_walks.o: included at the end of pgq_k_walks.hip, not compiled on its own.  k_walk_activate, WalkCounters,
+// walk_query / walk_check and kWalkLimit are that file's; the chunk forms' shared pieces and LC come through pgq_path_lists.h.
 //
 // The contract, with W_t as pgq_k_walks.hip defines it: the smallest t in [lo, K] with W_t[dst] > 0; -1 (NULL) when there is none or
 // an endpoint is NULL.  src == dst is not special.  Weights are never read; parallel edges change nothing.
@@ -259,7 +259,8 @@ private:
 		const int nb = (int)(((int64_t)U + LC - 1) / LC);
 		PGQ_TRY(batch_bounds(ws, m, LC, nb));
 		if (nb == 0) return PGQ_OK; // (closed rows without an out-edge or an in-edge: no walk)
-		PGQ_TRY(ws->tight_cnt.reserve(std::max(sizeof(WalkCounters), sizeof(TightCounters))));
+		static_assert(sizeof(WalkCounters) <= Workspace::kTightCntBytes, "counter block too small");
+		PGQ_TRY(ws->tight_cnt.reserve(Workspace::kTightCntBytes));
 		tc = ws->tight_cnt.as<WalkCounters>();
 		for (u64 *&mk : M) PGQ_TRY(temps.alloc(&mk, Vn));
 		for (int32_t *&b : q) PGQ_TRY(temps.alloc(&b, Vn));

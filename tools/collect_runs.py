@@ -23,8 +23,9 @@ def walk_columns(x, path=()):
     if not isinstance(x, dict):
         return {}
     if "median_ms" in x:
-        return {" ".join(path): {"ms": [round(x[k], 3) for k in ("median_ms", "min_ms", "max_ms")], "recon_ms": round(x["recon_ms"], 3),
-                                 "counts": [x.get(k) for k in WALK_COUNTS]}}
+        recon = x.get("recon_ms", x.get("kernel_ms", {}).get("recon"))  # (the cheapest-path tools keep their classes in kernel_ms)
+        return {" ".join(path): {"ms": [round(x[k], 3) for k in ("median_ms", "min_ms", "max_ms")], "recon_ms": None if recon is None else round(recon, 3),
+                                 "counts": [x.get(k, x.get("emitted_paths") if k == "emitted_walks" else None) for k in WALK_COUNTS]}}
     out = {}
     for k, v in x.items():
         out.update(walk_columns(v, path + (k,)))
