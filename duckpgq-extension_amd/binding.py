@@ -107,6 +107,11 @@ def load_hip():
     L.pgq_csr_pull_layout_sizes.argtypes = [C.c_void_p, C.c_void_p]
     L.pgq_csr_pull_layout.restype = C.c_int
     L.pgq_csr_pull_layout.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    L.pgq_csr_meet_layout_sizes.restype = C.c_int
+    L.pgq_csr_meet_layout_sizes.argtypes = [C.c_void_p, C.c_void_p]
+    L.pgq_csr_meet_layout.restype = C.c_int
+    L.pgq_csr_meet_layout.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    L.pgq_csr_has_prepass_layout.argtypes = [C.c_void_p]
     L.pgq_debug_live_device_blocks.restype = C.c_int64
     L.pgq_debug_live_device_blocks.argtypes = []
     L.pgq_iterativelength.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_void_p, C.c_void_p]
@@ -498,6 +503,48 @@ class DeviceCSR:
         _check(self.L.pgq_csr_pull_layout(self.h, _p(parts), _p(items), _p(hubs), _p(rown), _p(rpk)))
         return dict(parts=parts[:n_parts], hub_items=items[:n_items], hub_vertices=hubs[:n_hubs], rown=rown[:E],
                     rpk=None if rpk is None else rpk[:E])
+
+    @property
+    def has_prepass_layout(self):
+        """1: the upload built the pair-centric layout (pgq_csr_has_prepass_layout), else 0."""
+        return self.L.pgq_csr_has_prepass_layout(self.h)
+
+    def meet_layout_sizes(self):
+        """pgq_csr_meet_layout_sizes as a dict: groups, rgroups, pgroups, prgroups, pack_k, pack_align, pack_order, has_rhead,
+        max_out_degree, max_in_degree, two_hop_mean."""
+        sizes = np.zeros(11, dtype=np.int64)
+        _check(self.L.pgq_csr_meet_layout_sizes(self.h, _p(sizes)))
+        names = ("groups", "rgroups", "pgroups", "prgroups", "pack_k", "pack_align", "pack_order", "has_rhead",
+                 "max_out_degree", "max_in_degree")
+        d = {k: int(v) for k, v in zip(names, sizes)}
+        d["two_hop_mean"] = float(sizes[10:11].view(np.float64)[0])
+        return d
+
+    def meet_layout(self, direction):
+        """What the upload derived for the pair-centric and source-centric kernels in one direction (0: forward, 1: reverse), as
+        a dict of numpy arrays: off [V + 1], adj [E], seg [V, 2] (first group, entries), padded [groups, 4], desc [E, 4], work
+        [V], packed [packed groups, 4], rhead [V, 64] (direction 1), and the scalars of meet_layout_sizes().  None for an array
+        the handle does not have."""
+        s = self.meet_layout_sizes()
+        V, E = self.V, self.num_edges
+        layout = bool(self.has_prepass_layout)
+        groups = s["rgroups" if direction else "groups"]
+        pgroups = s["prgroups" if direction else "pgroups"]
+        off = np.zeros(V + 1, dtype=np.int64)
+        adj = np.zeros(max(E, 1), dtype=np.int32)
+        seg = np.zeros((max(V, 1), 2), dtype=np.uint32) if layout else None
+        padded = np.zeros((max(groups, 1), 4), dtype=np.int32) if layout else None
+        desc = np.zeros((max(E, 1), 4), dtype=np.uint32) if layout else None
+        work = np.zeros(max(V, 1), dtype=np.uint32) if layout else None
+        packed = np.zeros((max(pgroups, 1), 4), dtype=np.uint32) if layout and s["pack_k"] > 4 else None
+        rhead = np.zeros((max(V, 1), 64), dtype=np.uint32) if direction == 1 and s["has_rhead"] else None
+        _check(self.L.pgq_csr_meet_layout(self.h, direction, _p(off), _p(adj), _p(seg), _p(padded), _p(desc), _p(work),
+                                          _p(packed), _p(rhead)))
+        cut = lambda a, n: None if a is None else a[:n]
+        out = dict(off=off, adj=adj[:E], seg=cut(seg, V), padded=cut(padded, groups), desc=cut(desc, E), work=cut(work, V),
+                   packed=cut(packed, pgroups), rhead=cut(rhead, V))
+        out.update(s)
+        return out
 
     # -- chunk form (host arrays) ----------------------------------------------
     def _vecs(self, src, dst, src_valid, src_sel, dst_sel, dst_valid, keep):

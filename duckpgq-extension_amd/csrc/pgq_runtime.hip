@@ -2131,6 +2131,47 @@ int pgq_csr_pull_layout(const pgq_csr_t *c, int32_t *parts, int64_t *hub_items, 
 	if (rpk && c->E > 0) PGQ_TRY(staged_download(rpk, c->rpk, (size_t)c->E * 4, st));
 	return PGQ_OK;
 }
+int pgq_csr_meet_layout_sizes(const pgq_csr_t *c, int64_t *sizes) {
+	if (!c || !sizes) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_meet_layout_sizes: NULL handle or no room");
+	const bool layout = c->fdesc != nullptr;
+	sizes[0] = layout ? c->padj_groups : 0;
+	sizes[1] = layout ? c->rpadj_groups : 0;
+	sizes[2] = layout && c->ppadj ? c->ppadj_groups : 0;
+	sizes[3] = layout && c->prpadj ? c->prpadj_groups : 0;
+	sizes[4] = c->pack_k;
+	sizes[5] = c->pack_align;
+	sizes[6] = c->pack_order;
+	sizes[7] = c->rhead ? 1 : 0;
+	sizes[8] = c->max_out_degree;
+	sizes[9] = c->max_in_degree;
+	memcpy(&sizes[10], &c->two_hop_mean, sizeof(double));
+	return PGQ_OK;
+}
+int pgq_csr_meet_layout(const pgq_csr_t *c, int dir, int64_t *offsets, int32_t *adj, uint32_t *seg, int32_t *padded, uint32_t *desc,
+                        uint32_t *work, uint32_t *packed, uint32_t *rhead) {
+	PGQ_TRY(ensure_init());
+	if (!c || (dir != 0 && dir != 1)) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_meet_layout: NULL handle or direction not 0 / 1");
+	const bool layout = c->fdesc != nullptr;
+	if ((seg || padded || desc || work) && !layout)
+		return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_meet_layout: this CSR has no pair-centric layout");
+	if (packed && !(layout && c->pack_k > 4 && c->ppadj && c->prpadj))
+		return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_meet_layout: this CSR has no packed copy");
+	if (rhead && (dir != 1 || !c->rhead))
+		return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_meet_layout: no fixed-stride in-list heads (reverse direction only, ball_head_mb)");
+	hipStream_t st = nullptr; // the null stream, as pgq_csr_download
+	const size_t V = (size_t)c->V, E = (size_t)c->E;
+	const size_t groups = (size_t)(dir == 0 ? c->padj_groups : c->rpadj_groups);
+	const size_t pgroups = (size_t)(dir == 0 ? c->ppadj_groups : c->prpadj_groups);
+	if (offsets) PGQ_TRY(staged_download(offsets, dir == 0 ? c->off : c->roff, (V + 1) * 8, st));
+	if (adj && E > 0) PGQ_TRY(staged_download(adj, dir == 0 ? c->adj : c->radj, E * 4, st));
+	if (seg && V > 0) PGQ_TRY(staged_download(seg, dir == 0 ? c->fseg : c->rseg, V * 8, st));
+	if (padded && groups > 0) PGQ_TRY(staged_download(padded, dir == 0 ? c->padj : c->rpadj, groups * 16, st));
+	if (desc && E > 0) PGQ_TRY(staged_download(desc, dir == 0 ? c->fdesc : c->rdesc, E * 16, st));
+	if (work && V > 0) PGQ_TRY(staged_download(work, dir == 0 ? c->fwork : c->rwork, V * 4, st));
+	if (packed && pgroups > 0) PGQ_TRY(staged_download(packed, dir == 0 ? c->ppadj : c->prpadj, pgroups * 16, st));
+	if (rhead && V > 0) PGQ_TRY(staged_download(rhead, c->rhead, V * 256, st));
+	return PGQ_OK;
+}
 
 } // extern "C"
 

@@ -149,6 +149,24 @@ int64_t pgq_csr_packed_list(pgq_csr_t *csr, int dir, int64_t v, int32_t *out, in
 int pgq_csr_pull_layout_sizes(const pgq_csr_t *csr, int64_t *sizes);
 int pgq_csr_pull_layout(const pgq_csr_t *csr, int32_t *parts, int64_t *hub_items, int32_t *hub_vertices, uint8_t *rown,
                         uint32_t *rpk);
+/* Debugging / tests: the layout the upload derives for the pair-centric and source-centric kernels, copied to host memory.
+ * pgq_csr_meet_layout_sizes writes sizes[0 .. 10] = {16-byte groups of the forward padded adjacency, of the reverse one, of
+ * the forward packed copy, of the reverse one (all four 0 when the handle has no layout, the packed two 0 without a packed
+ * copy), ids per packed group (pgq_csr_pack_k), groups the packed lists are aligned to, pgq_csr_pack_order, 1 if the
+ * fixed-stride in-list heads exist else 0, the largest out-degree, the largest in-degree, the bit pattern of the double
+ * `mean over the vertices of in-degree x out-degree`}.  pgq_csr_meet_layout fills whichever buffers are not NULL for
+ * direction 0 (forward: out-lists) or 1 (reverse: in-lists): offsets (V + 1); adj (E entries); seg = per vertex (first
+ * group of its padded list, entries), 2 V words; padded = 4 words per group, a list's entries and then its last entry again
+ * up to the end of its last alignment group; desc = per slot (neighbour, the neighbour's first group, its entries, its first
+ * packed group or 0 without a packed copy), 4 E words; work = per vertex the entries of its two-hop walk, saturating at
+ * 2^32 - 1; packed = 4 words per packed group (pgq_csr_packed_list decodes one list of it); rhead (dir 1 only) = 64 words per
+ * vertex: word 31 the in-degree, words 0 .. 30 in-list entries 0 .. 30, words 32 .. 63 entries 31 .. 62, the last entry
+ * repeated past the list's end, all ones for an empty list.  Only these defined parts are copied, not the spare entries the
+ * device arrays carry behind them.  PGQ_ERR_UNSUPPORTED for a buffer whose array this handle does not have (no layout, no
+ * packed copy, no heads, heads of direction 0).  Read-only: no search path and no layout depends on these calls. */
+int pgq_csr_meet_layout_sizes(const pgq_csr_t *csr, int64_t *sizes);
+int pgq_csr_meet_layout(const pgq_csr_t *csr, int dir, int64_t *offsets, int32_t *adj, uint32_t *seg, int32_t *padded,
+                        uint32_t *desc, uint32_t *work, uint32_t *packed, uint32_t *rhead);
 /* Debugging / tests: device blocks the library's block cache has handed out and not got back yet (CSR arrays and build
  * temporaries of every live handle; cached free blocks, workspaces and pinned memory are not counted).  The same figure
  * before a handle is created and after it is freed = the handle left nothing behind. */

@@ -1166,3 +1166,225 @@ def bibfs_stale_gadgets(grid, qcap=1024):
             for s in ss:
                 B.row(s, dd, dist, "stale", qcap, listed, (0, 1, 0, 2)[kind])
     return B.finish(), Ts
+
+
+# ---- graphs for the upload's derived layout (tests/layout_model.py, test_layout_model_cpu.py, test_upload_layout_gpu.py) ------
+# Four upload kernels walk 256 vertices per workgroup with a binary search over 257 LDS offsets (k_slot_sources, k_fill_padded,
+# k_fill_packed<K>, k_two_hop_work); the grid-stride loops of the others take a second trip above LAYOUT_TRIPS.
+LAYOUT_BLOCK_V = (1, 2, 255, 256, 257, 511, 512, 513, 769)
+LAYOUT_LENGTHS = (0, 1, 2, 3, 4, 5, 30, 31, 32, 33, 62, 63, 64, 65, 127, 128, 129)
+LAYOUT_LONG = 700                     # one list longer than two 256-thread trips
+LAYOUT_PREFIX = (0, 64, 63, 129)      # lists of vertices 0 .. 3: see layout_blocks
+LAYOUT_TRIPS = dict(
+    slot_sources_v=2048 * 256,        # k_slot_sources: grid_for(V, 256, 256 * 8) workgroups of 256 rows
+    degree_stats_v=1024 * 256,        # k_degree_stats: grid_for(V, 256, 1024) workgroups of 256 threads
+    slots_e=4096 * 256,               # k_narrow_adj, k_check_rows, k_gather_rows, k_any_negative: grid_for(E) x 256 threads
+    tail_v=257, tail_e=300,
+)
+
+
+class LayoutGraph:
+    """An edge table in slot order of its forward CSR (rows sorted by source, stably)."""
+
+    def __init__(self, name, V, src, dst):
+        self.name, self.V = name, int(V)
+        self.src, self.dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+
+    def transposed(self):
+        return LayoutGraph(self.name + "_T", self.V, self.dst, self.src)
+
+    def csr(self):
+        off, adj, _ = csr_arrays_from_rows(self.V, self.src, self.dst)
+        return off, adj
+
+
+def layout_blocks(V, seed=0):
+    """Family a.  Out- and in-list lengths from LAYOUT_LENGTHS; one out-list and one in-list of LAYOUT_LONG entries; empty
+    lists (both directions) at the first and the last vertex of every block of 256, so vertex 0 and vertex V - 1 have no
+    in-edges and k_row_bounds closes a gap at both ends; at V = 769 the whole block 256 .. 511 is empty between two full ones.
+    Vertices 1, 2, 3 have lists of 64, 63 and 129 entries in both directions: counted from the block's first slot, as
+    k_two_hop_work's wavefront trips are, the first starts on lane 0 and ends on lane 63, the second starts on lane 0, the third
+    starts on lane 63 of one trip and ends on lane 63 of the third.  One slack vertex per direction takes up the difference
+    of the two degree sums (its length is the only one not in the list).  Destinations are a seeded permutation of the in-degree
+    multiset: parallel edges and self loops occur (test_layout_model_cpu.py counts them).  V = 1 and V = 2 cannot have edges
+    AND no in-edges at both ends: they are a vertex with five self loops, and two vertices with lists of 4 and 2."""
+    if V == 1:
+        return LayoutGraph("blocks_1", 1, np.zeros(5), np.zeros(5))
+    if V == 2:
+        return LayoutGraph("blocks_2", 2, [0, 0, 0, 0, 1, 1], [1, 1, 0, 1, 1, 0])
+    rng = np.random.default_rng(1000 * V + seed)
+    v = np.arange(V)
+    edge = (v % 256 == 0) | (v % 256 == 255) | (v == V - 1)
+    if V == 769:
+        edge |= (v >= 256) & (v < 512)
+    free = np.flatnonzero(~edge)
+    free = free[free >= len(LAYOUT_PREFIX)]
+    degs = []
+    for _ in range(2):
+        d = np.zeros(V, dtype=np.int64)
+        d[free] = rng.choice(LAYOUT_LENGTHS, len(free))
+        d[free[:len(LAYOUT_LENGTHS)]] = rng.permutation(LAYOUT_LENGTHS)  # every length at least once
+        d[:len(LAYOUT_PREFIX)] = LAYOUT_PREFIX
+        degs.append(d)
+    out, ind = degs
+    hubs = free[-4:]  # out hub, in hub, out slack, in slack: the last free vertices
+    out[hubs[0]], ind[hubs[1]] = LAYOUT_LONG, LAYOUT_LONG
+    out[hubs[2]] = ind[hubs[3]] = 0
+    diff = int(out.sum() - ind.sum())
+    if diff > 0:
+        ind[hubs[3]] = diff
+    else:
+        out[hubs[2]] = -diff
+    src = np.repeat(v, out)
+    dst = rng.permutation(np.repeat(v, ind))
+    return LayoutGraph("blocks_%d" % V, V, src, dst)
+
+
+def layout_saturation():
+    """Family b.  h has 65,536 parallel slots to w and w has 65,536 slots: h's two-hop walk holds 2^32 entries, its work
+    saturates at 2^32 - 1.  The twin h2 has 65,535 slots to w2, w2 65,536: 2^32 - 65,536, the largest sum below.  w and w2 spread
+    their slots over 32 sinks.  262,143 edges."""
+    h, w, h2, w2, sinks = 1, 2, 3, 4, np.arange(8, 40)
+    n = 1 << 16
+    src = np.concatenate([np.full(n, h), np.full(n, w), np.full(n - 1, h2), np.full(n, w2)])
+    dst = np.concatenate([np.full(n, w), sinks[np.arange(n) % 32], np.full(n - 1, w2), sinks[np.arange(n) % 32]])
+    g = LayoutGraph("saturation", 64, src, dst)
+    g.h, g.h2 = h, h2
+    return g
+
+
+def layout_second_trips(vb=LAYOUT_TRIPS["slot_sources_v"], eb=LAYOUT_TRIPS["slots_e"], tail_v=LAYOUT_TRIPS["tail_v"],
+                        tail_e=LAYOUT_TRIPS["tail_e"]):
+    """Family c.  V = vb + tail_v, E = eb + tail_e (eb = 2 vb): the first vb vertices have two slots each into the first vb
+    vertices (in-degree 2 each), the last tail_v vertices own the last tail_e slots, which point at the last tail_v vertices:
+    most of them at V - 2, which so has the largest in-degree, vertex V - 3 has the largest out-degree, and the very last slot
+    points at V - 1.  A kernel that loses the trip past vb vertices or eb slots leaves exactly these unwritten."""
+    assert eb == 2 * vb and tail_e >= tail_v + 8 and tail_v >= 8
+    V = vb + tail_v
+    a = np.arange(vb, dtype=np.int64)
+    src = np.concatenate([np.repeat(a, 2), vb + np.arange(tail_v), np.full(tail_e - tail_v, V - 3)])
+    dst = np.concatenate([np.stack([(a * 7 + 1) % vb, (a * 11 + 5) % vb], axis=1).ravel(),
+                          np.where(np.arange(tail_v) % 3 == 0, vb + np.arange(tail_v), V - 2),
+                          np.where(np.arange(tail_e - tail_v) % 2 == 0, V - 2, vb + np.arange(tail_e - tail_v) % tail_v)])
+    order = np.argsort(src, kind="stable")
+    src, dst = src[order], dst[order]
+    dst[-1] = V - 1
+    return LayoutGraph("second_trips_%d" % V, V, src, dst)
+
+
+def layout_id_width(V):
+    """Family d.  The top id V - 1 in every position of a 16-byte group of six (V <= 2^21) or five ids: vertex k's list of six
+    has it at position k (the CSR's order, meet_pack_order = 0), vertex 8's list is six parallel edges to it (every position
+    under either order), and the top vertex has a list of its own, so that its id stands in in-lists too.  A few dozen edges."""
+    top = V - 1
+    src, dst = [], []
+    for k in range(6):
+        lst = [100 + 10 * k + j for j in range(6)]
+        lst[k] = top
+        src += [k] * 6
+        dst += lst
+    src += [8] * 6 + [top] * 7
+    dst += [top] * 6 + [0, 1, 2, 3, 100, 101, top]
+    src, dst = np.array(src, dtype=np.int64), np.array(dst, dtype=np.int64)
+    order = np.argsort(src, kind="stable")
+    return LayoutGraph("id_width_%d" % V, V, src[order], dst[order])
+
+
+def layout_end_bit(V, seed=3):
+    """Family d, the radix sorts' end_bit: a random graph on V = 2^k or 2^k + 1 vertices with edges into and out of vertex V - 1."""
+    rng = np.random.default_rng(V + seed)
+    src = np.concatenate([rng.integers(0, V, 6 * V), np.full(9, V - 1), rng.integers(0, V, 9)])
+    dst = np.concatenate([rng.integers(0, V, 6 * V), rng.integers(0, V, 9), np.full(9, V - 1)])
+    order = np.argsort(src, kind="stable")
+    return LayoutGraph("end_bit_%d" % V, V, src[order], dst[order])
+
+
+# ---- rows for k_src_ball (pgq_ball.h) at the line boundary of the fixed-stride in-list heads -----------------------------------
+# rhead keeps a vertex's in-degree in word 31, the last word of its first 128-byte line, entries 0 .. 30 before it and entries
+# 31 .. 62 in the second line; k_src_ball masks word 31 out of its membership test and reads entries 63 and on from rpadj.
+BALL_LINE_DEGREES = (1, 30, 31, 32, 33, 62, 63, 64)
+BALL_LINE_POSITIONS = (0, 30, 31, 61, 62, 63)
+BALL_COUNT_DEGREES = (31, 32, 62, 63, 64)
+_BALL_CORE, _BALL_POOL = 80, 80
+
+
+def ball_line_gadgets():
+    """A sibling of degree_gadgets for the heads.  Two families, each built as it stands and mirrored (every edge and row
+    reversed), so that the graph and its transpose both hold them:
+
+    line   s -> m1 -> m2 -> dst for every in-degree b of BALL_LINE_DEGREES and every position p of BALL_LINE_POSITIONS below b:
+           m2 is entry p of dst's in-list and the only in-neighbour within two hops of s; the other b - 1 are decoys, roots
+           nothing points at, p of them with ids below m2 and the rest above (in-lists are in source-id order).  One s, m1, m2
+           for all of them: distance 3, the rows of one source side by side.
+    count  s2 -> q -> {vertices 31, 32, 62, 63, 64}: the ids that are in-degrees lie in s2's two-hop set.  For every c of
+           BALL_COUNT_DEGREES a destination of in-degree c whose in-neighbours are c decoys (unreachable), and one with c - 1
+           decoys and x_c, where vertex c -> x_c: distance 4.  A kernel that tests the count word as an entry finds `c` in the
+           set and answers 3.  s2's rows to every line destination too (unreachable; five of them have such an in-degree).
+
+    Ids: 0 .. 79 the core (the count family's s2 = 0, q = 1, the five id-named vertices, the mirrored s2 = 2, q = 3, the rest
+    isolated), then the low decoy pools (roots, sinks for the mirrored half), then every other vertex, then the high pools.
+    Returns a Gadgets whose records have kind ('line' / 'count4' / 'count_unreachable'), a, b (the out-degree of the row's source
+    and the in-degree of its destination: a mirrored record carries the degree in a until the graph is transposed), pos and
+    mirrored."""
+    n = [_BALL_CORE + 2 * _BALL_POOL]
+    low = {False: np.arange(_BALL_CORE, _BALL_CORE + _BALL_POOL), True: np.arange(_BALL_CORE + _BALL_POOL, _BALL_CORE + 2 * _BALL_POOL)}
+
+    def new():
+        n[0] += 1
+        return n[0] - 1
+
+    es, ed, rs, rd, dist, tag, gadgets = [], [], [], [], [], [], []
+    pending = []  # in-lists that take high decoys: the pools' ids are known at the end
+
+    def edge(a, b, flip):
+        es.append(b if flip else a), ed.append(a if flip else b)
+
+    def row(a, b, k, t, flip, **rec):
+        rs.append(b if flip else a), rd.append(a if flip else b), dist.append(k), tag.append(t)
+        if rec:  # a, b: out-degree of the row's source, in-degree of its destination, as in degree_gadgets
+            deg = rec.pop("deg")
+            gadgets.append(dict(rec, tag=t, k=k, a=deg if flip else 1, b=1 if flip else deg, src=rs[-1], dst=rd[-1], tie=False,
+                                row=len(rs) - 1, mirrored=flip))
+
+    def in_list(dst, n_low, mid, n_high, flip):
+        for v in low[flip][:n_low]:
+            edge(int(v), dst, flip)
+        if mid is not None:
+            edge(mid, dst, flip)
+        pending.append((dst, n_high, flip))
+
+    for flip in (False, True):
+        m = "_m" if flip else ""
+        s, m1, m2 = new(), new(), new()
+        edge(s, m1, flip), edge(m1, m2, flip)
+        s2, q = (2, 3) if flip else (0, 1)
+        edge(s2, q, flip)
+        for c in BALL_COUNT_DEGREES:
+            edge(q, c, flip)
+        line_dsts = []
+        for b in BALL_LINE_DEGREES:
+            for p in BALL_LINE_POSITIONS:
+                if p >= b:
+                    continue
+                d = new()
+                in_list(d, p, m2, b - 1 - p, flip)
+                row(s, d, 3, "line_b%d_p%d%s" % (b, p, m), flip, kind="line", deg=b, pos=p, paths=[[s, m1, m2, d][::-1 if flip else 1]])
+                line_dsts.append((d, b, p))
+        for c in BALL_COUNT_DEGREES:
+            x, d4, du = new(), new(), new()
+            edge(c, x, flip)
+            in_list(d4, c // 2, x, c - 1 - c // 2, flip)
+            in_list(du, c // 2, None, c - c // 2, flip)
+            row(s2, d4, 4, "count_c%d_far%s" % (c, m), flip, kind="count4", deg=c, pos=c // 2, paths=[[s2, q, c, x, d4][::-1 if flip else 1]])
+            row(s2, du, -1, "count_c%d_unreachable%s" % (c, m), flip, kind="count_unreachable", deg=c, pos=None, paths=[])
+        for d, b, p in line_dsts:
+            row(s2, d, -1, "count_line_b%d_p%d%s" % (b, p, m), flip)
+    high = {False: np.arange(n[0], n[0] + _BALL_POOL), True: np.arange(n[0] + _BALL_POOL, n[0] + 2 * _BALL_POOL)}
+    for dst, n_high, flip in pending:
+        for v in high[flip][:n_high]:
+            edge(int(v), dst, flip)
+    V = n[0] + 2 * _BALL_POOL
+    i64 = lambda a: np.array(a, dtype=np.int64)
+    src, dst = i64(es), i64(ed)
+    order = np.argsort(src, kind="stable")  # table order = slot order
+    return Gadgets(V, src[order], dst[order], i64(rs), i64(rd), i64(dist), np.array(tag), gadgets)

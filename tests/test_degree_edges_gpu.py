@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import duckpgq_extension_amd as pgq
-from helpers import LDS_LIMITS, csr_arrays_from_rows, degree_gadgets, lcc_gadgets, spread_ids
+from helpers import LDS_LIMITS, ball_line_gadgets, csr_arrays_from_rows, degree_gadgets, lcc_gadgets, spread_ids
 from oracle.pgq_oracle import OracleCSR
 from test_within_gpu import Rows, clamp
 
@@ -261,6 +261,43 @@ def test_source_centric_runs(sides):
             ln, ok = st.iterativelength(0, g.V, g.rs, g.rd)
             side.check(ln, ok, "%s, ball = 2, ball_head_mb %d" % (orient(k), head_mb))
             assert pgq.get_stats()["ball_calls"] >= 1
+            st.delete_csr(0)
+
+
+# ---- source-centric: the fixed-stride heads at their line boundary (helpers.ball_line_gadgets) --------------------------------
+def test_source_centric_head_lines():
+    # rhead: word 31 is the in-degree, entries 31 .. 62 sit one word further on, entry 63 and on come from rpadj.  The only witness
+    # of a row is in-list entry 0, 30, 31, 61, 62 or 63 of a destination of in-degree 1, 30 .. 33, 62 .. 64; the count rows have
+    # the vertex whose id IS the in-degree in the source's two-hop set.  Under max_hops = 3 a row whose scan shows no witness is
+    # NULL in k_src_ball itself: a lost entry is a wrong answer there, no kernel behind repairs it
+    g0 = ball_line_gadgets()
+    pgq.set_option("meet", 1)
+    pgq.set_option("meet_bias", 1e9)
+    pgq.set_option("ball", 2)
+    for k, g in enumerate((g0, g0.transposed())):
+        side = Side(g)
+        assert (side.dist == g.dist).all()
+        by_src = np.argsort(g.rs, kind="stable")  # each source's rows side by side
+        ps, pd, dist, tags = g.rs[by_src], g.rd[by_src], side.dist[by_src], g.tag[by_src]
+        for head_mb in (512, 0):
+            pgq.set_option("ball_head_mb", head_mb)  # read at upload and launch
+            st = side.upload()
+            lay = st.device_csr(0).meet_layout_sizes()
+            assert lay["has_rhead"] == (1 if head_mb else 0)
+            for U in (None, 2, 3, 4):
+                pgq.reset_stats()
+                if U is None:
+                    ln, ok = st.iterativelength(0, g.V, ps, pd)
+                    want = dist
+                else:
+                    ln, ok = st.iterativelength_within(0, g.V, ps, pd, U)
+                    want = clamp(dist, np.ones(len(ps), dtype=bool), U)
+                got = np.where(ok, ln, -1)
+                bad = np.flatnonzero(got != want)
+                assert len(bad) == 0, "%s, ball_head_mb %d, max_hops %s: %d of %d rows differ, first: %s got %d, expected %d" % (
+                    orient(k), head_mb, U, len(bad), len(ps), tags[bad[0]], got[bad[0]], want[bad[0]])
+                stats = pgq.get_stats()
+                assert stats["ball_calls"] >= 1 and stats["launches"]["ball"] >= 1, (orient(k), head_mb, U)
             st.delete_csr(0)
 
 

@@ -8,8 +8,9 @@ one; and every (degree, position) cell of the issue's lists exists at each dista
 import numpy as np
 import pytest
 
-from helpers import (GADGET_DEGREES, GADGET_POSITIONS, LCC_DEGREES, LDS_LIMITS, csr_arrays_from_rows, decoy_len, degree_gadgets,
-                     gadget_index, lcc_gadgets, spread_ids)
+from helpers import (BALL_COUNT_DEGREES, BALL_LINE_DEGREES, BALL_LINE_POSITIONS, GADGET_DEGREES, GADGET_POSITIONS, LCC_DEGREES,
+                     LDS_LIMITS, ball_line_gadgets, csr_arrays_from_rows, decoy_len, degree_gadgets, gadget_index, lcc_gadgets,
+                     spread_ids)
 from oracle.pgq_oracle import OracleCSR
 
 
@@ -139,6 +140,59 @@ def test_shifted_gadgets_keep_their_shape(both):
     s = g.shifted(V)
     assert s.V == V and s.src.max() < V and s.rs.max() < V and (s.src - g.src == V - g.V).all()
     assert s.gadgets[5]["paths"][0][0] == g.gadgets[5]["paths"][0][0] + V - g.V
+
+
+# ---- helpers.ball_line_gadgets: the rows for k_src_ball at the line boundary of the in-list heads ----------------------------
+@pytest.fixture(scope="module")
+def lines():
+    g = ball_line_gadgets()
+    return [Built(g), Built(g.transposed())]
+
+
+def two_hop_set(b, s):
+    one = b.out_list(s)
+    two = np.concatenate([b.out_list(v) for v in one]) if len(one) else one
+    return set(one.tolist()) | set(two.tolist()) | {int(s)}
+
+
+def test_ball_line_gadgets(lines):
+    assert (lines[0].g.rs >= 0).all() and lines[0].g.dst.max() < lines[0].g.V < 1000
+    for side, b in enumerate(lines):
+        g = b.g
+        got = oracle_dist(g, g.rs, g.rd)
+        bad = np.flatnonzero(got != g.dist)
+        assert len(bad) == 0, (g.tag[bad[0]], int(got[bad[0]]), int(g.dist[bad[0]]))
+        mine = [x for x in g.gadgets if x["mirrored"] == (side == 1)]  # the half whose in-lists this orientation holds
+        cells, counts = set(), {}
+        for x in mine:
+            inn, ball = b.in_list(x["dst"]), two_hop_set(b, x["src"])
+            assert len(inn) == x["b"], x["tag"]
+            inside = [int(v) for v in inn if int(v) in ball]
+            if x["kind"] == "line":
+                m2 = x["paths"][0][-2]
+                assert inside == [m2] and int(inn[x["pos"]]) == m2 and x["k"] == 3, x["tag"]  # the only witness, at its position
+                assert all(len(b.in_list(v)) == 0 for v in inn if v != m2), x["tag"]       # the rest: roots nothing reaches
+                cells.add((x["b"], x["pos"]))
+            else:
+                assert inside == [] and x["b"] in ball, x["tag"]  # no witness, and the vertex named like the count word is in the set
+                counts.setdefault(x["b"], set()).add(x["kind"])
+                if x["kind"] == "count4":
+                    assert x["k"] == 4 and int(inn[x["pos"]]) == x["paths"][0][-2] and x["paths"][0][2] == x["b"]
+                else:
+                    assert x["k"] == -1
+        assert cells == {(d, p) for d in BALL_LINE_DEGREES for p in BALL_LINE_POSITIONS if p < d}
+        assert counts == {c: {"count4", "count_unreachable"} for c in BALL_COUNT_DEGREES}
+        # s2's rows to the line destinations: unreachable, and every in-degree that is an id of its set occurs
+        s2 = next(x["src"] for x in mine if x["kind"] == "count4")
+        extra = [i for i, t in enumerate(g.tag) if t.startswith("count_line_") and t.endswith("_m") == (side == 1)]
+        assert all(g.rs[i] == s2 and g.dist[i] == -1 for i in extra)
+        assert {len(b.in_list(g.rd[i])) for i in extra} >= set(BALL_COUNT_DEGREES)
+        # without the witness's edge into the destination every line row is unreachable: no other path
+        cut = {(x["paths"][0][-2], x["dst"]) for x in mine if x["kind"] == "line"}
+        keep = ~np.isin(g.src * g.V + g.dst, [s * g.V + d for s, d in cut])
+        assert (~keep).sum() == len(cut)
+        rows = np.array([x["row"] for x in mine if x["kind"] == "line"])
+        assert (oracle_dist(g, g.rs[rows], g.rd[rows], g.src[keep], g.dst[keep]) == -1).all()
 
 
 def test_lcc_gadgets():
