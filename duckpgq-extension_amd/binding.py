@@ -147,6 +147,13 @@ def load_hip():
                                            C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_cheapest_path_within_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.pgq_cheapest_walk_length.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pgq_cheapest_walk_length_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                       C.c_void_p, C.c_void_p]
+    L.pgq_cheapest_walk.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pgq_cheapest_walk_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.pgq_shortestpath_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_void_p, C.c_void_p]
     L.pgq_shortestpath_count_bulk_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.pgq_all_shortestpaths.argtypes = [C.c_void_p, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -224,6 +231,10 @@ def load_udf():
                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.pgq_udf_cheapest_path_length_within.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64,
                                                       C.c_void_p, C.c_void_p]
+    L.pgq_udf_cheapest_walk_length.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_void_p]
+    L.pgq_udf_cheapest_walk.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, Vec, Vec, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     for f in ("pgq_udf_local_clustering_coefficient", "pgq_udf_pagerank", "pgq_udf_weakly_connected_component"):
         getattr(L, f).argtypes = [C.c_void_p, C.c_int32, C.c_int64, Vec, C.c_void_p, C.c_void_p]
     L.pgq_udf_delete_csr.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
@@ -731,6 +742,35 @@ class DeviceCSR:
         cheapest_path_length_within returns, not cheapest_path's list with long rows None (include/pgq_hip.h)."""
         return self.cheapest_path(src, dst, src_valid, dst_valid, src_sel, dst_sel, raw, max_hops=int(max_hops))
 
+    def cheapest_walk_length(self, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        """The cost of the cheapest walk of min_hops..max_hops edges per row; src == dst is not special: its cheapest closed
+        walk when min_hops >= 1 (include/pgq_hip.h: pgq_cheapest_walk_length).  Not a filter around cheapest_path_length_within."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        out = np.zeros(n, dtype=np.int64 if self.w_type == 1 else np.float64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        _check(self.L.pgq_cheapest_walk_length(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), _p(out), _p(ov)))
+        return out, unpack_validity(ov, n)
+
+    def cheapest_walk(self, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None, raw=False):
+        """The cheapest walk of min_hops..max_hops edges per row as cheapest_path's list: the walk whose cost
+        cheapest_walk_length returns (include/pgq_hip.h: pgq_cheapest_walk).  raw=True: offsets, lengths, validity words, child."""
+        keep = []
+        sv, dv, n = self._vecs(src, dst, src_valid, src_sel, dst_sel, dst_valid, keep)
+        off = np.zeros(n, dtype=np.uint64)
+        ln = np.zeros(n, dtype=np.uint64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        child = C.c_void_p()
+        clen = C.c_uint64()
+        _check(self.L.pgq_cheapest_walk(self.h, self.V, n, sv, dv, int(min_hops), int(max_hops), _p(off), _p(ln), _p(ov),
+                                        C.byref(child), C.byref(clen)))
+        ch = np.zeros(0, dtype=np.int64)
+        if clen.value:
+            ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
+        if raw:
+            return off, ln, ov, ch
+        return _lists(off, ln, unpack_validity(ov, n), ch)
+
     # -- bulk form (device pointers; torch tensors supply them) ------------------
     def iterativelength_bulk_ptr(self, n, d_src, d_dst, d_out):
         _check(self.L.pgq_iterativelength_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
@@ -909,6 +949,18 @@ class DeviceCSR:
         return self._lists_bulk(self.L.pgq_k_shortest_groups_bulk_device, n, d_src, d_dst, (min_hops, max_hops, groups, max_paths, path_mode),
                                 (d_out_len, d_out_count, d_out_first, d_out_npaths, d_out_ngroups, d_path_offset, d_path_hops), path_cap, d_child,
                                 child_cap)
+
+    def cheapest_walk_length_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, d_out, d_ok):
+        _check(self.L.pgq_cheapest_walk_length_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops),
+                                                           int(max_hops), C.c_void_p(d_out), C.c_void_p(d_ok)))
+
+    def cheapest_walk_bulk_ptr(self, n, d_src, d_dst, min_hops, max_hops, d_out_len, d_out_off, d_child, child_cap):
+        """(status, elements needed): as cheapest_path_within_bulk_ptr, the cheapest walks of min_hops..max_hops edges."""
+        used = C.c_int64(0)
+        rc = self.L.pgq_cheapest_walk_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst), int(min_hops), int(max_hops),
+                                                  C.c_void_p(d_out_len), C.c_void_p(d_out_off), C.c_void_p(d_child), child_cap,
+                                                  C.byref(used))
+        return rc, used.value
 
     def cheapest_within_bulk_ptr(self, n, d_src, d_dst, max_hops, d_out, d_ok):
         _check(self.L.pgq_cheapest_path_length_within_bulk_device(self.h, n, C.c_void_p(d_src), C.c_void_p(d_dst),
@@ -1158,6 +1210,37 @@ class PgqState:
 
     def cheapest_path_within(self, csr_id, V, src, dst, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
         return self.cheapest_path(csr_id, V, src, dst, src_valid, dst_valid, src_sel, dst_sel, max_hops=int(max_hops))
+
+    def cheapest_walk_length(self, csr_id, V, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None,
+                             dst_sel=None):
+        rt = self.bind_cheapest(csr_id)
+        n = len(src_sel) if src_sel is not None else len(src)
+        out = np.zeros(n, dtype=np.int64 if rt == 1 else np.float64)
+        lo, hi = int(min_hops), int(max_hops)
+
+        def fn(s, csr_id, V, n, sv, dv, out_p, ov_p):
+            return self.U.pgq_udf_cheapest_walk_length(s, csr_id, V, n, sv, dv, lo, hi, out_p, ov_p)
+
+        ok = self._search(fn, csr_id, V, src, dst, src_valid, src_sel, dst_sel, dst_valid, out)
+        return out, ok
+
+    def cheapest_walk(self, csr_id, V, src, dst, min_hops, max_hops, src_valid=None, dst_valid=None, src_sel=None, dst_sel=None):
+        self.bind_cheapest(csr_id)
+        keep = []
+        sv = make_vec(_i64(src), sel=src_sel, valid=src_valid, keep=keep)
+        dv = make_vec(_i64(dst), sel=dst_sel, valid=dst_valid, keep=keep)
+        n = len(src_sel) if src_sel is not None else len(src)
+        off = np.zeros(n, dtype=np.uint64)
+        ln = np.zeros(n, dtype=np.uint64)
+        ov = np.zeros((n + 63) // 64 + 1, dtype=np.uint64)
+        child = C.c_void_p()
+        clen = C.c_uint64()
+        self._ck(self.U.pgq_udf_cheapest_walk(self.s, csr_id, V, n, sv, dv, int(min_hops), int(max_hops), _p(off), _p(ln), _p(ov),
+                                              C.byref(child), C.byref(clen)))
+        ch = np.zeros(0, dtype=np.int64)
+        if clen.value:
+            ch = np.ctypeslib.as_array(C.cast(child, C.POINTER(C.c_int64)), shape=(clen.value,)).copy()
+        return _lists(off, ln, unpack_validity(ov, n), ch)
 
     def _analytics(self, fn, csr_id, src, dtype):
         keep = []

@@ -1148,7 +1148,7 @@ static int weighted_pairs_prepass(pgq_csr *c, Workspace *ws, u32 nd, int64_t *d_
 
 template <typename T>
 static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                           int64_t *d_out, uint8_t *d_ok, bool chain, int64_t max_hops = -1);
+                           int64_t *d_out, uint8_t *d_ok, bool chain, int64_t max_hops = -1, int64_t min_hops = 0);
 
 template <typename T>
 static int cheapest_with_chains(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
@@ -1562,10 +1562,35 @@ private:
 // walk needs no repeated vertex under non-negative weights) and takes the unbounded drivers.
 // Known limits: lists over 128 edges are walked by the wavefront that finds them (correct, only slow: no heavy-list split
 // here yet), and there is no destination-bound pruning — a lane relaxes everything within K edges of its source.
+//
+// With a lower bound (pgq_cheapest_walk_length, lo = min_hops >= 1): the cheapest walk of lo .. K edges.  Rounds 1 .. lo are EXACT,
+//     E_0 = D_0;   E_t[x] = min over the in-slots (u, x) with E_{t-1}[u] < INF of E_{t-1}[u] + w   (INF if none: E_{t-1}[x] is NOT carried)
+//     L_lo = E_lo; L_t[x] = min(L_{t-1}[x], min over the in-slots (u, x) of L_{t-1}[u] + w),  t = lo + 1 .. K  (the recurrence above)
+// and the row's answer is L_K[dst].  An exact round is the round above with ONE difference: k_hop_snapshot TAKES the row — behind
+// the copy to `snap` and the exchange of the dirty word it writes INF into all 64 lanes of dist[v] (`take`, by value: the host
+// knows hop < lo when it enqueues the launch, so groups of rounds are enqueued ahead as ever and may span the phase boundary).
+//   invariant   before exact round t, every label below INF was written by an improving atomicMin of round t-1 (or is the
+//               source's 0 of k_cheapest_init): its vertex is queued and its lane's bit is in the dirty word.  True at t = 1; the
+//               take launch of round t then leaves dist at INF EVERYWHERE (it takes every queued row, whole), the round's atomicMins
+//               build E_t from snap = E_{t-1} into it, and each label they leave was an improvement over INF or over a larger offer
+//               of the same round — queued, bit set: the invariant at t + 1.  The dirty bits of the next parity are exactly the
+//               finite lanes of E_t, so k_relax_hops's "only dirty lanes relax" loses nothing, and the kernel is unchanged.
+//   claim       E_t[x] = the minimum, over the walks src -> x of EXACTLY t edges, of the left-to-right fold of their weights:
+//               t = 0 as above; a walk of t edges into x is a walk P of t-1 edges into some u plus a slot (u, x), and by the
+//               monotonicity of x -> x + w the minimum over P of fold(P) + w is E_{t-1}[u] + w.  (A sum that does not get under
+//               INF labels nothing, as above.)  Then L_t[x] = the minimum over the walks of lo .. t edges, by the k-1 -> k step
+//               above started from L_lo = E_lo instead of D_0 — bit for bit, for int64 and for double.
+// Take and relax stay two launches: with a self-loop or a ring a vertex is source and target of one round, and only the kernel
+// boundary puts every take before every atomicMin.  Taken vertices stay on the touched list (k_reset_touched and the "stopped
+// at the bound" memset cover them like any other).  src == dst is no special row here: it takes a lane (prepare_lanes'
+// closed_rows) and is answered by its cheapest closed walk; the rows that stay trivial there — no out-edge or no in-edge — are NULL.
+// A lower bound takes these rounds for EVERY K, K >= V - 1 included: phase 2 is Bellman-Ford from E_lo, stands still after at
+// most V - 1 rounds and ends with the queue.  lo is capped (PGQ_WALK_MAX_HOPS): in a cyclic graph the exact phase never runs dry.
 template <typename DT>
 __global__ __launch_bounds__(256) void k_hop_snapshot(const int32_t *__restrict__ qcur, const u32 *__restrict__ nq_ptr,
-                                                      u64 *__restrict__ dirty_cur, const DT *__restrict__ dist,
-                                                      DT *__restrict__ snap, u64 *__restrict__ snapmask, u32 *__restrict__ snap_rows) {
+                                                      u64 *__restrict__ dirty_cur, DT *__restrict__ dist,
+                                                      DT *__restrict__ snap, u64 *__restrict__ snapmask, u32 *__restrict__ snap_rows,
+                                                      int take, DT inf_bits, u32 *__restrict__ take_rows) {
 	const int lane = threadIdx.x & 63;
 	const u32 wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
 	const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -1574,8 +1599,12 @@ __global__ __launch_bounds__(256) void k_hop_snapshot(const int32_t *__restrict_
 		const int v = qcur[i];
 		snap[(size_t)i * LC + lane] = dist[(size_t)v * LC + lane];
 		if (lane == 0) snapmask[i] = atomicExch(&dirty_cur[v], 0ull); // consumed: the word is clean for the round after next
+		if (take) dist[(size_t)v * LC + lane] = inf_bits; // an exact round: the row is TAKEN, nothing of E_{t-1} is carried into E_t
 	}
-	if (blockIdx.x == 0 && threadIdx.x == 0) *snap_rows += nq; // (statistics; the batch's launches never overlap)
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		*snap_rows += nq; // (statistics; the batch's launches never overlap)
+		if (take) *take_rows += nq;
+	}
 }
 
 template <typename T>
@@ -1693,7 +1722,7 @@ template <typename T> class HopBatches : RelaxWorker {
 	using DT = int64_t; // 8-byte labels only
 	static constexpr int kHopGroup = 8;
 public:
-	HopBatches(const RelaxWorker &w, u32 U, int64_t K, const HopLog *log = nullptr) : RelaxWorker(w), U(U), K(K), log(log) {}
+	HopBatches(const RelaxWorker &w, u32 U, int64_t lower, int64_t K, const HopLog *log = nullptr) : RelaxWorker(w), U(U), lower(lower), K(K), log(log) {}
 
 	int run(int b0, int bstride) {
 		PGQ_TRY(sd.prepare<DT>(V, relax_label_tag<T, DT>(), (DT)Inf<T>::bits, st));
@@ -1717,13 +1746,13 @@ public:
 	}
 private:
 	const u32 U;
-	const int64_t K;
+	const int64_t lower, K; // rounds 1 .. lower are exact (they take), the rounds behind them carry over
 	const HopLog *const log; // null: the rows' costs (k_cheapest_results)
 	RelaxSide &sd = priv->relax[0], &sn = priv->relax[1];
 	RelaxCounters *d_rc = nullptr, *const h_rc = reinterpret_cast<RelaxCounters *>(priv->h_cnt);
 	int par = 0; // from here on: the batch's (start_batch)
 	int64_t lo = 0, hi = 0, base = 0, hop = 0; // hop: the rounds enqueued so far
-	u32 nq_now = 0, rounds_seen = 0, snap_seen = 0;
+	u32 nq_now = 0, rounds_seen = 0, snap_seen = 0, take_seen = 0;
 	u64 edges = 0;
 
 	int start_batch() {
@@ -1737,7 +1766,7 @@ private:
 		kt.stop();
 		par = 0;
 		nq_now = (u32)std::min<int64_t>(LC, (int64_t)U - base);
-		rounds_seen = snap_seen = 0;
+		rounds_seen = snap_seen = take_seen = 0;
 		edges = 0;
 		hop = 0;
 		return PGQ_OK;
@@ -1749,11 +1778,12 @@ private:
 			const unsigned g = r == 0 ? std::min(grid, std::max(1u, (nq_now + 3) / 4)) : grid;
 			const int64_t *snap = sn.dist.as<DT>();
 			const u64 *snapmask = sn.dirty[0].as<u64>();
-			if (log) PGQ_TRY(log->append(par, nq_now, hop, &snap, &snapmask)); // (a group of one round: nq_now is this round's)
+			const bool take = hop < lower; // known here, handed over by value: a group may span the phase boundary
+			if (log) PGQ_TRY(log->append(par, nq_now, hop, take, &snap, &snapmask)); // (a group of one round: nq_now is this round's)
 			KernelTimer kt(st, K_RELAX);
 			if (!log)
 				hipLaunchKernelGGL(k_hop_snapshot<DT>, dim3(g), dim3(256), 0, st, sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.dirty[par].as<u64>(), sd.dist.as<DT>(),
-				                   sn.dist.as<DT>(), sn.dirty[0].as<u64>(), &d_rc->snap_rows);
+				                   sn.dist.as<DT>(), sn.dirty[0].as<u64>(), &d_rc->snap_rows, take ? 1 : 0, (DT)Inf<T>::bits, &d_rc->take_rows);
 			hipLaunchKernelGGL(k_relax_hops<T>, dim3(g), dim3(256), 0, st, c->off, c->adj, (const T *)c->w, sd.dist.as<DT>(), snap,
 			                   snapmask, sd.dirty[par ^ 1].as<u64>(), sd.q[par].as<int32_t>(), &d_rc->nq[par], sd.q[par ^ 1].as<int32_t>(),
 			                   &d_rc->nq[par ^ 1], sd.tflag.as<u32>(), tepoch, sd.touched.as<int32_t>(), &d_rc->tcount, &d_rc->relaxed_edges, &d_rc->rounds);
@@ -1765,8 +1795,10 @@ private:
 		// the block's counters run on over the batch: what this group added
 		S.levels += h_rc->rounds - rounds_seen;
 		S.algo_bytes[K_RELAX] += (double)(h_rc->snap_rows - snap_seen) * (2.0 * sizeof(DT) * LC + 16.0); // a row read and written, the dirty word exchanged, the mask written
+		S.algo_bytes[K_RELAX] += (double)(h_rc->take_rows - take_seen) * (double)(sizeof(DT) * LC); // the row a take writes back as INF
 		rounds_seen = h_rc->rounds;
 		snap_seen = h_rc->snap_rows;
+		take_seen = h_rc->take_rows;
 		edges = h_rc->relaxed_edges;
 		nq_now = h_rc->nq[par];
 		return PGQ_OK;
@@ -1775,7 +1807,7 @@ private:
 		if (log) { // the vertices the last round changed are logged too, which takes their dirty words: nothing is left queued
 			const int64_t *snap = nullptr;
 			const u64 *snapmask = nullptr;
-			if (nq_now != 0) PGQ_TRY(log->append(par, nq_now, hop, &snap, &snapmask));
+			if (nq_now != 0) PGQ_TRY(log->append(par, nq_now, hop, false, &snap, &snapmask)); // (hop >= lower here, or the queue is empty)
 			PGQ_TRY(log->then(lo, hi, base));
 			end_batch<T, DT>(edges, 1, d_rc);
 			return PGQ_OK;
@@ -2030,8 +2062,9 @@ private:
 // light-edges-first lists, no two-ended batches, no 4-byte labels: none of them knows hops.
 template <typename T>
 static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst,
-                           int64_t *d_out, uint8_t *d_ok, bool chain, int64_t max_hops) {
-	const bool bounded = max_hops >= 0 && max_hops < c->V - 1;
+                           int64_t *d_out, uint8_t *d_ok, bool chain, int64_t max_hops, int64_t min_hops) {
+	// a lower bound never takes the unbounded drivers: their labels are not rounds (and see fact 4 of pgq_cheapest_path_within.hip)
+	const bool bounded = max_hops >= 0 && (min_hops > 0 || max_hops < c->V - 1);
 	if (!bounded && chain && options().chain && n > 0 && n < (1LL << 31)) return cheapest_with_chains<T>(c, ws, n, d_src, d_dst, d_out, d_ok);
 	hipStream_t st = ws->stream;
 	pgq_stats_t &S = tstats().s;
@@ -2039,7 +2072,7 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	if (n == 0) return PGQ_OK;
 	if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
 	u32 U = 0;
-	PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U));
+	PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U, true, min_hops > 0)); // a closed walk of min_hops >= 1 edges needs a lane
 	S.unique_sources += U;
 	const int nb = (int)(((int64_t)U + LC - 1) / LC);
 	PGQ_TRY(batch_bounds(ws, n, LC, nb));
@@ -2082,7 +2115,7 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	}
 	auto run_relax = [&](Workspace *priv, int b0, int bstride) -> int {
 		const RelaxWorker w { c, ws, priv, nb_run, d_out, d_ok };
-		if (bounded) return HopBatches<T>(w, U, max_hops).run(b0, bstride);
+		if (bounded) return HopBatches<T>(w, U, min_hops, max_hops).run(b0, bstride);
 		if constexpr (std::is_same<T, int64_t>::value) {
 			if (bidir) return narrow ? BidirBatches<int32_t>(w, R).run(b0, bstride) : BidirBatches<int64_t>(w, R).run(b0, bstride);
 			if (narrow) return RelaxBatches<T, int32_t>(w, U, light).run(b0, bstride);
@@ -2101,7 +2134,8 @@ static int cheapest_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *
 	if (rc != PGQ_OK) return rc;
 	const int64_t lo_t = bs[nb + 1], lo_n = bs[nb + 2];
 	if (n > lo_t)
-		hipLaunchKernelGGL(k_cheapest_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, lo_n, n,
+		// (min_hops >= 1: the src == dst rows left trivial have no closed walk at all — NULL, not the empty walk's 0)
+		hipLaunchKernelGGL(k_cheapest_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, min_hops > 0 ? lo_t : lo_n, n,
 		                   ws->sidx.as<u32>(), d_out, d_ok);
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
 	KernelTimer::flush();
@@ -2117,17 +2151,27 @@ int check_weighted(pgq_csr_t *csr) {
 	return PGQ_OK;
 }
 
+// cheapest_walk's bounds, for the length call here and the list call in pgq_cheapest_path.o
+int check_walk_bounds(int64_t min_hops, int64_t max_hops) {
+	if (min_hops < 0) return fail(PGQ_ERR_INVALID_ARG, "min_hops must not be negative");
+	if (max_hops < min_hops) return fail(PGQ_ERR_INVALID_ARG, "max_hops must not be below min_hops");
+	if (min_hops > PGQ_WALK_MAX_HOPS)
+		return fail(PGQ_ERR_UNSUPPORTED, "cheapest_walk: a lower bound above " + std::to_string(PGQ_WALK_MAX_HOPS) +
+		                                     " is not supported (every exact round runs over all it reaches)");
+	return PGQ_OK;
+}
+
 // pgq_relax.h's two entries to the lane batches: one worker on the call's own workspace, every batch, no cost outputs.
 template <typename T> int settle_every_label(pgq_csr *c, Workspace *ws, int nb, u32 U, const SettledBatch &settled) {
 	return RelaxBatches<T, int64_t>(RelaxWorker { c, ws, ws, nb, nullptr, nullptr }, U, false, &settled).run(0, 1);
 }
-template <typename T> int hop_rounds_logged(pgq_csr *c, Workspace *ws, int nb, u32 U, int64_t K, const HopLog &log) {
-	return HopBatches<T>(RelaxWorker { c, ws, ws, nb, nullptr, nullptr }, U, K, &log).run(0, 1);
+template <typename T> int hop_rounds_logged(pgq_csr *c, Workspace *ws, int nb, u32 U, int64_t lower, int64_t K, const HopLog &log) {
+	return HopBatches<T>(RelaxWorker { c, ws, ws, nb, nullptr, nullptr }, U, lower, K, &log).run(0, 1);
 }
 template int settle_every_label<int64_t>(pgq_csr *, Workspace *, int, u32, const SettledBatch &);
 template int settle_every_label<double>(pgq_csr *, Workspace *, int, u32, const SettledBatch &);
-template int hop_rounds_logged<int64_t>(pgq_csr *, Workspace *, int, u32, int64_t, const HopLog &);
-template int hop_rounds_logged<double>(pgq_csr *, Workspace *, int, u32, int64_t, const HopLog &);
+template int hop_rounds_logged<int64_t>(pgq_csr *, Workspace *, int, u32, int64_t, int64_t, const HopLog &);
+template int hop_rounds_logged<double>(pgq_csr *, Workspace *, int, u32, int64_t, int64_t, const HopLog &);
 
 } // namespace pgq
 
@@ -2136,8 +2180,9 @@ using namespace pgq;
 extern "C" {
 
 // max_hops: null = unbounded (iterativelength_bulk's convention).  The bounded forms answer a NULL handle before anything else.
+// min_hops > 0: cheapest_walk_length (its bounds are checked by the caller; 0 is forwarded to the _within form).
 static int cheapest_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, void *d_out, uint8_t *d_out_valid,
-                         const int64_t *max_hops) {
+                         const int64_t *max_hops, int64_t min_hops = 0) {
 	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	const bool arrays = d_src && d_dst && d_out && d_out_valid;
 	auto check = [&]() -> int {
@@ -2149,13 +2194,13 @@ static int cheapest_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const 
 	return c_entry<true>(csr, check, [&](Workspace *ws) {
 		const int64_t bound = max_hops ? *max_hops : -1;
 		if (csr->w_type == PGQ_W_INT64)
-			return cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true, bound);
-		return cheapest_device<double>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true, bound);
+			return cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true, bound, min_hops);
+		return cheapest_device<double>(csr, ws, n, d_src, d_dst, (int64_t *)d_out, d_out_valid, true, bound, min_hops);
 	});
 }
 
 static int cheapest_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out, uint64_t *out_valid,
-                          const int64_t *max_hops) {
+                          const int64_t *max_hops, int64_t min_hops = 0) {
 	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	auto check = [&]() -> int {
 		PGQ_TRY(check_weighted(csr));
@@ -2175,8 +2220,8 @@ static int cheapest_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, p
 		const int64_t *d_src = ws->in_src.as<int64_t>(), *d_dst = ws->in_dst.as<int64_t>();
 		const int64_t bound = max_hops ? *max_hops : -1;
 		PGQ_TRY(csr->w_type == PGQ_W_INT64
-		            ? cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true, bound)
-		            : cheapest_device<double>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true, bound));
+		            ? cheapest_device<int64_t>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true, bound, min_hops)
+		            : cheapest_device<double>(csr, ws, n, d_src, d_dst, ws->out_val.as<int64_t>(), ws->out_ok.as<uint8_t>(), true, bound, min_hops));
 		return download_valid(ws, n, out, out_valid);
 	});
 }
@@ -2197,6 +2242,21 @@ int pgq_cheapest_path_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
 int pgq_cheapest_path_length_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, void *out,
                                     uint64_t *out_valid) {
 	return cheapest_chunk(csr, V, n, src, dst, out, out_valid, &max_hops);
+}
+
+// The cheapest walk of min_hops .. max_hops edges (include/pgq_hip.h).  min_hops == 0 IS the _within call; otherwise HopBatches
+// with a lower bound, for every max_hops (INT64_MAX: the rounds end with the queue).
+int pgq_cheapest_walk_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops,
+                                         void *d_out, uint8_t *d_out_valid) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	PGQ_TRY(check_walk_bounds(min_hops, max_hops));
+	return cheapest_bulk(csr, n, d_src, d_dst, d_out, d_out_valid, &max_hops, min_hops);
+}
+int pgq_cheapest_walk_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, void *out,
+                             uint64_t *out_valid) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	PGQ_TRY(check_walk_bounds(min_hops, max_hops));
+	return cheapest_chunk(csr, V, n, src, dst, out, out_valid, &max_hops, min_hops);
 }
 
 } // extern "C"

@@ -261,7 +261,8 @@ __global__ void k_list_gather(int64_t lo_trivial, int64_t lo_null, const u32 *__
 // levels = false: the staging and the layout alone, for a driver with a walk-back of its own (cheapest_path_within).
 template <typename T> class PathBatches {
 public:
-	PathBatches(pgq_csr *c, Workspace *ws, u32 U, int64_t *d_out_len, bool levels = true) : stage(ws), c(c), ws(ws), U(U), d_out_len(d_out_len), levels(levels) {}
+	PathBatches(pgq_csr *c, Workspace *ws, u32 U, int64_t *d_out_len, bool levels = true, bool closed_rows = false)
+	    : stage(ws), c(c), ws(ws), U(U), d_out_len(d_out_len), levels(levels), closed_rows(closed_rows) {}
 
 	ListStage stage; // the places of a batch's lists and the room for them: also for a driver with a walk-back of its own
 
@@ -355,7 +356,8 @@ public:
 		PGQ_TRY(ws->meet_poff.reserve((size_t)(n + 1) * 8 * 2));
 		int64_t *noff = ws->meet_poff.as<int64_t>(), *cnt = noff + (n + 1), total = 0;
 		KernelTimer kt(st, K_RECON);
-		if (n > lo_t) hipLaunchKernelGGL(k_path_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, lo_n, n, ws->sidx.as<u32>(), d_out_len);
+		// (closed_rows: the src == dst rows left trivial have no closed walk — NULL like the rows behind them, no [src])
+		if (n > lo_t) hipLaunchKernelGGL(k_path_tails, dim3(blocks_for(n - lo_t)), dim3(256), 0, st, lo_t, closed_rows ? lo_t : lo_n, n, ws->sidx.as<u32>(), d_out_len);
 		hipLaunchKernelGGL(k_list_counts, dim3(blocks_for(n + 1)), dim3(256), 0, st, n, d_out_len, cnt);
 		PGQ_TRY(cub_run(ws->scan_tmp, [&](void *tmp, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, noff, (int)(n + 1), st); }));
 		PGQ_HIP_TRY(hipMemcpyAsync(d_out_off, noff, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
@@ -385,7 +387,7 @@ private:
 	Workspace *const ws;
 	const u32 U;
 	int64_t *const d_out_len;
-	const bool levels;
+	const bool levels, closed_rows;
 	const hipStream_t st = ws->stream;
 	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
 	pgq_stats_t &S = tstats().s;
@@ -394,13 +396,14 @@ private:
 
 // The rows of one call (device memory, src < 0 = NULL row): lengths, offsets and lists.  One worker: the batches share the
 // staging buffer and the hop counts.  run(paths, nb, U) settles the nb lane batches and stages their lists through `paths`;
-// levels: PathBatches' own tight levels and walk-back are part of it.
+// levels: PathBatches' own tight levels and walk-back are part of it.  closed_rows (cheapest_walk with a lower bound): src == dst
+// rows take a lane like any other, and those that cannot (no out-edge or no in-edge) are NULL.
 struct PathOut {
 	int64_t *d_len, *d_off, *d_child, child_cap, *child_used;
 	bool *overflow;
 };
 template <typename T, typename Run>
-static int path_call(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out, bool levels, Run &&run) {
+static int path_call(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out, bool levels, bool closed_rows, Run &&run) {
 	pgq_stats_t &S = tstats().s;
 	S.pairs += n;
 	*out.child_used = 0;
@@ -408,12 +411,12 @@ static int path_call(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src,
 	if (n == 0) return PGQ_OK;
 	if (n >= (1LL << 31)) return fail(PGQ_ERR_INVALID_ARG, "more than 2^31-1 rows in one call");
 	u32 U = 0;
-	PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U));
+	PGQ_TRY(prepare_lanes(c, ws, n, d_src, d_dst, &U, true, closed_rows));
 	S.unique_sources += U;
 	const int nb = PathBatches<T>::nb_of(U);
 	PGQ_TRY(batch_bounds(ws, n, LC, nb));
 	if (options().relax_delta_div > 0) PGQ_TRY(ensure_weight_mean(c, ws));
-	PathBatches<T> paths(c, ws, U, out.d_len, levels);
+	PathBatches<T> paths(c, ws, U, out.d_len, levels, closed_rows);
 	if (nb > 0) {
 		PGQ_TRY(paths.prepare());
 		PGQ_TRY(run(paths, nb, U));
@@ -423,7 +426,7 @@ static int path_call(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src,
 }
 
 template <typename T> static int cheapest_path_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out) {
-	return path_call<T>(c, ws, n, d_src, d_dst, out, true, [&](PathBatches<T> &paths, int nb, u32 U) {
+	return path_call<T>(c, ws, n, d_src, d_dst, out, true, false, [&](PathBatches<T> &paths, int nb, u32 U) {
 		const SettledBatch settled { [&](int64_t lo, int64_t hi, int64_t base) { return paths.batch(lo, hi, base); } };
 		return settle_every_label<T>(c, ws, nb, U, settled);
 	});
@@ -438,8 +441,9 @@ using namespace pgq;
 extern "C" {
 
 // max_hops: null = unbounded (cheapest_bulk's convention).  The bounded forms answer a NULL handle before anything else.
+// min_hops > 0: cheapest_walk (its bounds are checked by the caller; 0 is forwarded to the _within form).
 static int cheapest_path_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, const int64_t *max_hops, int64_t *d_out_len,
-                              int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+                              int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used, int64_t min_hops = 0) {
 	if (child_used) *child_used = 0;
 	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	const bool arrays = d_src && d_dst && d_out_len && d_out_offset && d_child;
@@ -454,8 +458,8 @@ static int cheapest_path_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, c
 		int64_t used = 0;
 		bool overflow = false;
 		const PathOut out { d_out_len, d_out_offset, d_child, child_cap, &used, &overflow };
-		const int rc = csr->w_type == PGQ_W_INT64 ? cheapest_path_rows<int64_t>(csr, ws, n, d_src, d_dst, out, max_hops)
-		                                          : cheapest_path_rows<double>(csr, ws, n, d_src, d_dst, out, max_hops);
+		const int rc = csr->w_type == PGQ_W_INT64 ? cheapest_path_rows<int64_t>(csr, ws, n, d_src, d_dst, out, max_hops, min_hops)
+		                                          : cheapest_path_rows<double>(csr, ws, n, d_src, d_dst, out, max_hops, min_hops);
 		if (child_used) *child_used = used;
 		if (rc == PGQ_OK && overflow) return fail(PGQ_ERR_INVALID_ARG, "child buffer too small for the path lists (see *child_used)");
 		return rc;
@@ -463,7 +467,7 @@ static int cheapest_path_bulk(pgq_csr_t *csr, int64_t n, const int64_t *d_src, c
 }
 
 static int cheapest_path_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, const int64_t *max_hops, uint64_t *out_offset,
-                               uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+                               uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len, int64_t min_hops = 0) {
 	if (max_hops && !csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
 	auto check = [&]() -> int {
 		PGQ_TRY(check_weighted(csr));
@@ -482,8 +486,8 @@ static int cheapest_path_chunk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t s
 		int64_t used = 0;
 		bool overflow = false;
 		const PathOut out { ws->out_len.as<int64_t>(), ws->out_off.as<int64_t>(), nullptr, 0, &used, &overflow };
-		PGQ_TRY(csr->w_type == PGQ_W_INT64 ? cheapest_path_rows<int64_t>(csr, ws, n, d_src, d_dst, out, max_hops)
-		                                   : cheapest_path_rows<double>(csr, ws, n, d_src, d_dst, out, max_hops));
+		PGQ_TRY(csr->w_type == PGQ_W_INT64 ? cheapest_path_rows<int64_t>(csr, ws, n, d_src, d_dst, out, max_hops, min_hops)
+		                                   : cheapest_path_rows<double>(csr, ws, n, d_src, d_dst, out, max_hops, min_hops));
 		std::vector<int64_t> len(n), off(n);
 		PGQ_TRY(staged_download(len.data(), ws->out_len.p, (size_t)n * 8, ws->stream));
 		PGQ_TRY(staged_download(off.data(), ws->out_off.p, (size_t)n * 8, ws->stream));
@@ -522,6 +526,21 @@ int pgq_cheapest_path(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_v
 int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops, uint64_t *out_offset,
                              uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
 	return cheapest_path_chunk(csr, V, n, src, dst, &max_hops, out_offset, out_length, out_valid, out_child, out_child_len);
+}
+
+// The cheapest walk of min_hops .. max_hops edges as a list (include/pgq_hip.h).  min_hops == 0 IS the _within call.
+int pgq_cheapest_walk_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops, int64_t max_hops,
+                                  int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap, int64_t *child_used) {
+	if (child_used) *child_used = 0;
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	PGQ_TRY(check_walk_bounds(min_hops, max_hops));
+	return cheapest_path_bulk(csr, n, d_src, d_dst, &max_hops, d_out_len, d_out_offset, d_child, child_cap, child_used, min_hops);
+}
+int pgq_cheapest_walk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops, uint64_t *out_offset,
+                      uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "NULL csr");
+	PGQ_TRY(check_walk_bounds(min_hops, max_hops));
+	return cheapest_path_chunk(csr, V, n, src, dst, &max_hops, out_offset, out_length, out_valid, out_child, out_child_len, min_hops);
 }
 
 } // extern "C"

@@ -60,6 +60,36 @@
 //   5. hop_last goes back to "none" through the batch's touched list; the lists are staged and laid out by PathBatches.
 // Kernel-class time: the rounds and the log passes are K_RELAX, lengths / walk-back / gather K_RECON.
 // Not built: _multi, a heavy-list split of the rounds (HopBatches' known limit), more than one worker.
+//
+// cheapest_walk (pgq_cheapest_walk, lo = min_hops >= 1; lo == 0 IS the call above): the cheapest walk of lo .. K edges as a list,
+// on the same log.  E_t and L_t are HopBatches' labels with a lower bound (pgq_cheapest.hip); Λ_i = E_i for i <= lo, L_i for i > lo.
+//   NULL         L_K[dst] == INF, or a NULL src or dst.  src == dst is NOT special: its cheapest closed walk of lo .. K edges.
+//   h            the smallest t in [lo, K] with L_t[dst] == L_K[dst] as bit patterns;  d_out_len = h.
+//   the walk     x_h = dst; for i = h .. 1, x_{i-1} = the SMALLEST u with Λ_{i-1}[u] < INF and a slot (u, x_i) with
+//                relax_sum(Λ_{i-1}[u], w[s]) == Λ_i[x_i], e_i = edge_ids[the FIRST such slot of u's out-list into x_i].
+// The log: k_hop_log TAKES in the rounds below lo (the logged row goes back to INF in the label array, like k_hop_snapshot's take),
+// so for every round r <= lo the log holds one entry per vertex with a finite lane of E_r, and its row is E_r[v] exactly — the
+// lanes not reached are INF, nothing is carried over.  Behind lo the entries are the call's above.  The look-up (hop_entry_at):
+// Λ_j[v] is the row of v's entry of round EXACTLY j when j <= lo; of v's latest entry of round <= j when j > lo, and only if
+// that round is >= lo; INF otherwise.  An entry of an earlier exact round is stale: that label was taken.  k_hop_lengths: dst's
+// latest entry with the row's lane bit gives h; no such entry, or one of a round below lo: NULL.
+// A tight parent exists at every step, and step 0 stands on src:
+//   i - 1 >= lo  fact 1 above, read with L for D and started at L_lo = E_lo.  x_h = dst has an entry of round h with its lane's bit:
+//                h > lo is a strict improvement in round h, h == lo is a finite lane of E_lo (every finite lane of an exact round is
+//                dirty, HopBatches' invariant).  A tight parent u of a vertex that improved strictly in round i > lo has not shown
+//                L_{i-1}[u] in a round j with lo <= j < i - 1 (round j + 1 would have offered it), so u improved in round i - 1
+//                exactly when i - 1 > lo, and has a finite lane of E_lo — hence an entry of round lo — when i - 1 == lo.  One exists:
+//                the round's minimum was offered by some slot.
+//   i <= lo      Λ_i[x_i] = E_i[x_i] < INF is a minimum over the in-slots (u, x_i) with E_{i-1}[u] < INF, and a minimum over a finite,
+//                non-empty set is attained: that u is tight and has an entry of round exactly i - 1.
+//   step 0       Λ_0 = E_0 is finite at src alone, so x_0 = src.  Every step goes down one round: h steps, no loop on zero-weight
+//                cycles.  The fold of the list's weights is L_K[dst] as in fact 2 (Λ_i[x_i] = Λ_{i-1}[x_{i-1}] + w(e_i), Λ_0[src] = 0).
+// Rows the bound does not bind (the _within call's h >= lo) have the _within VALUE; with int64 weights the same list, with doubles
+// an absorbed sum can make the lists differ (README).  A large K is not forwarded to anything: fact 4.
+// Memory: the exact phase logs everything it reaches in EVERY round — lo x reached vertices x 528 bytes per lane batch on top of
+// what the call above logs (which logs a vertex only in the rounds that improve it).
+// Not built for cheapest_walk: _multi forms, a heavy-list split, a destination bound, the path modes, a two-ended search,
+// forwarding upper - lower >= V - 1 to k_relax.
 
 namespace pgq {
 
@@ -70,10 +100,11 @@ struct HopEntry {
 
 // In k_hop_snapshot's place (HopLog::append): entries [log_base, log_base + nq) of the log, one wavefront per queue entry.
 // nq comes from the host, which has made room for exactly that many.
+// take (an exact round of cheapest_walk, round < lo): the logged row goes back to INF in `dist`, as in k_hop_snapshot.
 __global__ __launch_bounds__(256) void k_hop_log(const int32_t *__restrict__ qcur, u32 nq, u64 *__restrict__ dirty_cur,
-                                                 const int64_t *__restrict__ dist, int32_t round, u32 log_base,
+                                                 int64_t *__restrict__ dist, int32_t round, u32 log_base,
                                                  int64_t *__restrict__ row, u64 *__restrict__ mask, HopEntry *__restrict__ ent,
-                                                 int32_t *__restrict__ hop_last) {
+                                                 int32_t *__restrict__ hop_last, int take, int64_t inf_bits) {
 	const int lane = threadIdx.x & 63;
 	const u32 wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
 	const u32 nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -81,6 +112,7 @@ __global__ __launch_bounds__(256) void k_hop_log(const int32_t *__restrict__ qcu
 		const int v = qcur[i];
 		const u32 g = log_base + i;
 		row[(size_t)g * LC + lane] = dist[(size_t)v * LC + lane];
+		if (take) dist[(size_t)v * LC + lane] = inf_bits;
 		if (lane == 0) {
 			mask[g] = atomicExch(&dirty_cur[v], 0ull); // consumed: the word is clean for the round after next, and for the next batch
 			ent[g] = HopEntry { round, hop_last[v] };
@@ -96,22 +128,26 @@ __device__ __forceinline__ int32_t hop_final_entry(int x, u32 l, const int32_t *
 	while (g >= 0 && !((mask[g] >> l) & 1ull)) g = ent[g].prev; // (indices fall along the chain)
 	return g;
 }
-// the entry of vertex u that holds D_j[u] (-1: none, every lane at INF)
-__device__ __forceinline__ int32_t hop_entry_at(int u, int32_t j, const int32_t *__restrict__ hop_last, const HopEntry *__restrict__ ent) {
+// the entry of vertex u that holds D_j[u] (-1: none, every lane at INF).  With a lower bound lo (cheapest_walk; 0 otherwise) the
+// labels are Λ_j: for j <= lo the entry of round EXACTLY j (an exact round carries nothing over: an earlier entry is stale), for
+// j > lo the latest entry of round <= j, and only if that round is >= lo (what an exact round logged was taken afterwards).
+__device__ __forceinline__ int32_t hop_entry_at(int u, int32_t j, int32_t lo, const int32_t *__restrict__ hop_last, const HopEntry *__restrict__ ent) {
 	int32_t g = hop_last[u];
 	while (g >= 0 && ent[g].round > j) g = ent[g].prev;
+	if (g >= 0 && (j <= lo ? ent[g].round != j : ent[g].round < lo)) g = -1;
 	return g;
 }
 
-// out_len[row] = h (-1: no walk of at most K edges), cnt[i - lo] = elements of the row's list
+// out_len[row] = h (-1: no walk of min_hops .. K edges), cnt[i - lo] = elements of the row's list.  A final entry of a round
+// below min_hops is an exact round's: that label was taken, the row is NULL.
 __global__ void k_hop_lengths(int64_t lo, int64_t hi, const u32 *__restrict__ skey, const u32 *__restrict__ sidx,
                               const int32_t *__restrict__ sdst, u32 base_lane, const int32_t *__restrict__ hop_last,
-                              const u64 *__restrict__ mask, const HopEntry *__restrict__ ent, int64_t *__restrict__ out_len,
+                              const u64 *__restrict__ mask, const HopEntry *__restrict__ ent, int32_t min_hops, int64_t *__restrict__ out_len,
                               int64_t *__restrict__ cnt) {
 	const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= hi) return;
 	const int32_t g = hop_final_entry(sdst[i], skey[i] - base_lane, hop_last, mask, ent);
-	const int64_t h = g < 0 ? -1 : ent[g].round;
+	const int64_t h = g < 0 || ent[g].round < min_hops ? -1 : ent[g].round;
 	out_len[sidx[i]] = h;
 	cnt[i - lo] = h < 0 ? 0 : 2 * h + 1;
 }
@@ -123,7 +159,7 @@ __global__ __launch_bounds__(64) void k_hop_walkback(int64_t lo, int64_t hi, con
                                                     const int32_t *__restrict__ adj, const T *__restrict__ w, const int64_t *__restrict__ edge_ids,
                                                     const int64_t *__restrict__ roff, const int32_t *__restrict__ radj, const T *__restrict__ rw,
                                                     const int32_t *__restrict__ hop_last, const u64 *__restrict__ mask,
-                                                    const HopEntry *__restrict__ ent, const int64_t *__restrict__ row,
+                                                    const HopEntry *__restrict__ ent, const int64_t *__restrict__ row, int32_t min_hops,
                                                     const int64_t *__restrict__ loc, int64_t stage_base, int64_t *__restrict__ stage,
                                                     int64_t *__restrict__ soff, TightCounters *__restrict__ tc) {
 	const int lane = threadIdx.x;
@@ -132,7 +168,7 @@ __global__ __launch_bounds__(64) void k_hop_walkback(int64_t lo, int64_t hi, con
 		int x = sdst[i];
 		if (lane == 0) soff[i] = stage_base + loc[i - lo];
 		const int32_t g = hop_final_entry(x, l, hop_last, mask, ent);
-		if (g < 0) continue; // no walk: no list
+		if (g < 0 || ent[g].round < min_hops) continue; // no walk: no list (k_hop_lengths)
 		const int h = ent[g].round;
 		int64_t dx = row[(size_t)g * LC + l];
 		int64_t *out = stage + stage_base + loc[i - lo]; // 2 h + 1 elements (k_hop_lengths)
@@ -144,7 +180,7 @@ __global__ __launch_bounds__(64) void k_hop_walkback(int64_t lo, int64_t hi, con
 			const int64_t rb = roff[x], re = roff[x + 1];
 			for (int64_t j = rb + lane; j < re; j += 64) {
 				const int u = radj[j];
-				const int32_t eu = hop_entry_at(u, t - 1, hop_last, ent);
+				const int32_t eu = hop_entry_at(u, t - 1, min_hops, hop_last, ent);
 				if (eu < 0 || u >= best) continue;
 				const int64_t du = row[(size_t)eu * LC + l];
 				if (du < Inf<T>::bits && relax_sum<T>(du, rw[j]) == dx) best = u;
@@ -156,7 +192,7 @@ __global__ __launch_bounds__(64) void k_hop_walkback(int64_t lo, int64_t hi, con
 				break;
 			}
 			// its first tight slot into x
-			const int64_t du = row[(size_t)hop_entry_at(best, t - 1, hop_last, ent) * LC + l];
+			const int64_t du = row[(size_t)hop_entry_at(best, t - 1, min_hops, hop_last, ent) * LC + l];
 			int64_t slot = -1;
 			const int64_t fb = off[best], fe = off[best + 1];
 			for (int64_t e0 = fb; e0 < fe && slot < 0; e0 += 64) {
@@ -190,7 +226,8 @@ __global__ void k_hop_reset_last(const int32_t *__restrict__ touched, const u32 
 // The round log of one worker's lane batches, and what a finished batch does with it: lengths, walk-back, staging.
 template <typename T> class HopPathLog {
 public:
-	HopPathLog(pgq_csr *c, Workspace *ws, PathBatches<T> &paths, int64_t *d_out_len) : c(c), ws(ws), paths(paths), d_out_len(d_out_len) {}
+	HopPathLog(pgq_csr *c, Workspace *ws, PathBatches<T> &paths, int64_t *d_out_len, int64_t min_hops = 0)
+	    : c(c), ws(ws), paths(paths), d_out_len(d_out_len), min_hops((int32_t)min_hops) {}
 
 	int prepare() {
 		const bool fresh = ws->hop_last.cap < Vn * 4 || ws->hop_last_V != c->V;
@@ -203,7 +240,7 @@ public:
 	size_t peak_bytes() const { return peak * kEntryBytes; }
 
 	HopLog hook() {
-		return HopLog { [this](int par, u32 nq, int64_t round, const int64_t **snap, const u64 **snapmask) { return append(par, nq, round, snap, snapmask); },
+		return HopLog { [this](int par, u32 nq, int64_t round, bool take, const int64_t **snap, const u64 **snapmask) { return append(par, nq, round, take, snap, snapmask); },
 		                [this](int64_t lo, int64_t hi, int64_t base) { return batch(lo, hi, base); } };
 	}
 
@@ -213,14 +250,16 @@ private:
 	Workspace *const ws;
 	PathBatches<T> &paths;
 	int64_t *const d_out_len;
+	const int32_t min_hops; // cheapest_walk's lower bound (<= PGQ_WALK_MAX_HOPS), 0: cheapest_path_within
 	const hipStream_t st = ws->stream;
 	const size_t Vn = (size_t)std::max<int64_t>(c->V, 1);
 	pgq_stats_t &S = tstats().s;
 	size_t count = 0, peak = 0; // entries of the batch's log so far; the most a batch of this call had
+	std::string name() const { return min_hops > 0 ? "cheapest_walk" : "cheapest_path_within"; } // the call an error message names
 
 	// room for `need` entries, the first `count` kept
 	int reserve(size_t need) {
-		if (need >= ((size_t)1 << 31)) return fail(PGQ_ERR_UNSUPPORTED, "cheapest_path_within: the round log of one lane batch would pass 2^31 entries");
+		if (need >= ((size_t)1 << 31)) return fail(PGQ_ERR_UNSUPPORTED, name() + ": the round log of one lane batch would pass 2^31 entries");
 		const size_t cap = ws->hop_mask.cap / 8;
 		if (need <= cap && need * LC * 8 <= ws->hop_row.cap && need * sizeof(HopEntry) <= ws->hop_ent.cap) return PGQ_OK;
 		const size_t grown = std::max<size_t>(std::max(need, 2 * cap), 1024);
@@ -230,20 +269,21 @@ private:
 		return PGQ_OK;
 	}
 
-	int append(int par, u32 nq, int64_t round, const int64_t **snap, const u64 **snapmask) {
-		if (round >= (int64_t)0x7FFFFFFF) return fail(PGQ_ERR_UNSUPPORTED, "cheapest_path_within: more than 2^31-1 rounds");
+	int append(int par, u32 nq, int64_t round, bool take, const int64_t **snap, const u64 **snapmask) {
+		if (round >= (int64_t)0x7FFFFFFF) return fail(PGQ_ERR_UNSUPPORTED, name() + ": more than 2^31-1 rounds");
 		PGQ_TRY(reserve(count + nq));
 		RelaxSide &sd = ws->relax[0];
 		KernelTimer kt(st, K_RELAX);
 		hipLaunchKernelGGL(k_hop_log, dim3(std::min((unsigned)device_cus() * 8, std::max(1u, (nq + 3) / 4))), dim3(256), 0, st, sd.q[par].as<int32_t>(), nq,
 		                   sd.dirty[par].as<u64>(), sd.dist.as<int64_t>(), (int32_t)round, (u32)count, ws->hop_row.as<int64_t>(), ws->hop_mask.as<u64>(),
-		                   ws->hop_ent.as<HopEntry>(), ws->hop_last.as<int32_t>());
+		                   ws->hop_ent.as<HopEntry>(), ws->hop_last.as<int32_t>(), take ? 1 : 0, Inf<T>::bits);
 		kt.stop();
 		*snap = ws->hop_row.as<int64_t>() + count * LC;
 		*snapmask = ws->hop_mask.as<u64>() + count;
 		count += nq;
 		peak = std::max(peak, count);
-		S.algo_bytes[K_RELAX] += (double)nq * (2.0 * 8 * LC + 16.0 + 2.0 * sizeof(HopEntry)); // a row read and written, the dirty word exchanged, mask, entry and hop_last
+		// a row read and written, the dirty word exchanged, mask, entry and hop_last; a take writes the row once more
+		S.algo_bytes[K_RELAX] += (double)nq * (2.0 * 8 * LC + 16.0 + 2.0 * sizeof(HopEntry) + (take ? 8.0 * LC : 0.0));
 		return PGQ_OK;
 	}
 
@@ -258,7 +298,7 @@ private:
 		PGQ_HIP_TRY(hipMemsetAsync(tc, 0, sizeof(TightCounters), st));
 		PGQ_TRY(paths.stage.place(m, [&](int64_t *const *cnt) {
 			hipLaunchKernelGGL(k_hop_lengths, dim3(blocks_for(m)), dim3(256), 0, st, lo, hi, ws->skey.as<u32>(), ws->sidx.as<u32>(), ws->sdst.as<int32_t>(),
-			                   (u32)base, last, mask, ent, d_out_len, cnt[0]);
+			                   (u32)base, last, mask, ent, min_hops, d_out_len, cnt[0]);
 		}, 1, &loc, &total));
 		PGQ_TRY(paths.stage.wait());
 		PGQ_TRY(paths.stage.stage_reserve(total, &at));
@@ -266,7 +306,7 @@ private:
 			KernelTimer kt(st, K_RECON);
 			hipLaunchKernelGGL(k_hop_walkback<T>, dim3((unsigned)std::min<int64_t>(m, 1 << 20)), dim3(64), 0, st, lo, hi, ws->skey.as<u32>(),
 			                   ws->sdst.as<int32_t>(), (u32)base, ws->usrc.as<int32_t>(), c->off, c->adj, (const T *)c->w, c->edge_ids, c->roff, c->radj,
-			                   (const T *)c->rw, last, mask, ent, ws->hop_row.as<int64_t>(), loc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
+			                   (const T *)c->rw, last, mask, ent, ws->hop_row.as<int64_t>(), min_hops, loc, at, ws->tight_stage.as<int64_t>(), ws->soff.as<int64_t>(), tc);
 			kt.stop();
 		}
 		hipLaunchKernelGGL(k_hop_reset_last, dim3((unsigned)device_cus() * 4), dim3(256), 0, st, ws->relax[0].touched.as<int32_t>(),
@@ -274,18 +314,20 @@ private:
 		count = 0;
 		TightCounters h {};
 		PGQ_TRY(paths.stage.read_back(&h, tc, sizeof(h)));
-		if (h.error) return fail(PGQ_ERR_HIP, "cheapest_path_within: internal error: the walk back lost its way (no tight parent, no tight slot, or not at the source)");
+		if (h.error) return fail(PGQ_ERR_HIP, name() + ": internal error: the walk back lost its way (no tight parent, no tight slot, or not at the source)");
 		return PGQ_OK;
 	}
 };
 
 // cheapest_path_device's bounded sibling.  Every K takes the hop rounds, K >= V - 1 included (fact 4): they end with the queue.
+// min_hops >= 1: cheapest_walk — the first min_hops rounds exact, src == dst rows on a lane (path_call's closed_rows).
 template <typename T>
-static int cheapest_path_within_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops, const PathOut &out) {
-	return path_call<T>(c, ws, n, d_src, d_dst, out, false, [&](PathBatches<T> &paths, int nb, u32 U) -> int {
-		HopPathLog<T> log(c, ws, paths, out.d_len);
+static int cheapest_path_within_device(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops, const PathOut &out,
+                                       int64_t min_hops = 0) {
+	return path_call<T>(c, ws, n, d_src, d_dst, out, false, min_hops > 0, [&](PathBatches<T> &paths, int nb, u32 U) -> int {
+		HopPathLog<T> log(c, ws, paths, out.d_len, min_hops);
 		PGQ_TRY(log.prepare());
-		PGQ_TRY(hop_rounds_logged<T>(c, ws, nb, U, max_hops, log.hook()));
+		PGQ_TRY(hop_rounds_logged<T>(c, ws, nb, U, min_hops, max_hops, log.hook()));
 		log.settle();
 		if (getenv("PGQ_RELAX_TRACE")) fprintf(stderr, "hop log: peak %zu bytes in a batch\n", log.peak_bytes());
 		return PGQ_OK;
@@ -294,8 +336,9 @@ static int cheapest_path_within_device(pgq_csr *c, Workspace *ws, int64_t n, con
 
 // max_hops: null = unbounded
 template <typename T>
-static int cheapest_path_rows(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out, const int64_t *max_hops) {
-	return max_hops ? cheapest_path_within_device<T>(c, ws, n, d_src, d_dst, *max_hops, out) : cheapest_path_device<T>(c, ws, n, d_src, d_dst, out);
+static int cheapest_path_rows(pgq_csr *c, Workspace *ws, int64_t n, const int64_t *d_src, const int64_t *d_dst, const PathOut &out, const int64_t *max_hops,
+                             int64_t min_hops = 0) {
+	return max_hops ? cheapest_path_within_device<T>(c, ws, n, d_src, d_dst, *max_hops, out, min_hops) : cheapest_path_device<T>(c, ws, n, d_src, d_dst, out);
 }
 
 } // namespace pgq

@@ -405,9 +405,9 @@ int pgq_udf_bind_cheapest(pgq_state_t *s, int32_t id, int *ret_type) { // cheape
 	return 0;
 }
 
-// max_hops: null = unbounded
+// max_hops: null = unbounded.  min_hops: null = no lower bound, otherwise the cheapest walk of min_hops .. max_hops edges
 static int cheapest_path_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, void *out,
-                                uint64_t *out_valid, const int64_t *max_hops) {
+                                uint64_t *out_valid, const int64_t *max_hops, const int64_t *min_hops = nullptr) {
 	if (!s) return fail("Invalid Input Error: NULL state");
 	CsrRef c = find_csr(s, id);
 	if (!c) return fail("Constraint Error: CSR not found with ID " + std::to_string(id));
@@ -416,8 +416,9 @@ static int cheapest_path_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n
 	if ((int64_t)c->vsize != V + 2) return fail("Invalid Input Error: vertex count does not match the CSR");
 	pgq_csr_t *d = device_csr(s, c, V);
 	if (!d) return device_fail();
-	const int rc = max_hops ? pgq_cheapest_path_length_within(d, V, n, src, dst, *max_hops, out, out_valid)
-	                        : pgq_cheapest_path_length(d, V, n, src, dst, out, out_valid);
+	const int rc = min_hops   ? pgq_cheapest_walk_length(d, V, n, src, dst, *min_hops, *max_hops, out, out_valid)
+	               : max_hops ? pgq_cheapest_path_length_within(d, V, n, src, dst, *max_hops, out, out_valid)
+	                          : pgq_cheapest_path_length(d, V, n, src, dst, out, out_valid);
 	if (rc != PGQ_OK) return device_fail();
 	std::lock_guard<std::mutex> g(s->csr_lock);
 	s->csr_to_delete.insert(id); // cheapest_path_length.cpp:162
@@ -434,9 +435,16 @@ int pgq_udf_cheapest_path_length_within(pgq_state_t *s, int32_t id, int64_t V, i
 	return cheapest_path_length(s, id, V, n, src, dst, out, out_valid, &max_hops);
 }
 
+// a weighted -[e]->{lower,upper} in WALK mode: bound like cheapest_path_length (pgq_udf_bind_cheapest)
+int pgq_udf_cheapest_walk_length(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops,
+                                 int64_t max_hops, void *out, uint64_t *out_valid) {
+	return cheapest_path_length(s, id, V, n, src, dst, out, out_valid, &max_hops, &min_hops);
+}
+
 // bound like cheapest_path_length (pgq_udf_bind_cheapest); the list form of the same search.  max_hops: null = unbounded
 static int cheapest_path(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint64_t *out_offset,
-                         uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len, const int64_t *max_hops) {
+                         uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len, const int64_t *max_hops,
+                         const int64_t *min_hops = nullptr) {
 	if (!s) return fail("Invalid Input Error: NULL state");
 	CsrRef c = find_csr(s, id);
 	if (!c) return fail("Constraint Error: CSR not found with ID " + std::to_string(id));
@@ -445,8 +453,9 @@ static int cheapest_path(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_v
 	if ((int64_t)c->vsize != V + 2) return fail("Invalid Input Error: vertex count does not match the CSR");
 	pgq_csr_t *d = device_csr(s, c, V);
 	if (!d) return device_fail();
-	const int rc = max_hops ? pgq_cheapest_path_within(d, V, n, src, dst, *max_hops, out_offset, out_length, out_valid, out_child, out_child_len)
-	                        : pgq_cheapest_path(d, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len);
+	const int rc = min_hops   ? pgq_cheapest_walk(d, V, n, src, dst, *min_hops, *max_hops, out_offset, out_length, out_valid, out_child, out_child_len)
+	               : max_hops ? pgq_cheapest_path_within(d, V, n, src, dst, *max_hops, out_offset, out_length, out_valid, out_child, out_child_len)
+	                          : pgq_cheapest_path(d, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len);
 	if (rc != PGQ_OK) return device_fail();
 	std::lock_guard<std::mutex> g(s->csr_lock);
 	s->csr_to_delete.insert(id);
@@ -462,6 +471,11 @@ int pgq_udf_cheapest_path_within(pgq_state_t *s, int32_t id, int64_t V, int64_t 
                                  uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                                  uint64_t *out_child_len) {
 	return cheapest_path(s, id, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len, &max_hops);
+}
+
+int pgq_udf_cheapest_walk(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                          uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child, uint64_t *out_child_len) {
+	return cheapest_path(s, id, V, n, src, dst, out_offset, out_length, out_valid, out_child, out_child_len, &max_hops, &min_hops);
 }
 
 int pgq_udf_reachability(pgq_state_t *s, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, uint8_t *out,

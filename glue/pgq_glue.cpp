@@ -4,6 +4,8 @@
 //   ShortestPathFunction           src/core/functions/scalar/shortest_path.cpp:43-207   (ShortestPathWithinFunction: its five-argument overload)
 //   CheapestPathLengthFunction     src/core/functions/scalar/cheapest_path_length.cpp:138-163   (CheapestPathLengthWithinFunction: its five-argument overload)
 //   CheapestPathFunction           (no counterpart) the cheapest path as a list   (CheapestPathWithinFunction: its five-argument overload)
+//   CheapestWalkLengthFunction     (no counterpart: a weighted {lower,upper} in WALK mode) the cost of the cheapest walk of lower..upper edges
+//   CheapestWalkFunction           (no counterpart) ... and that walk as a list
 //   ShortestPathCountFunction      (no counterpart: ALL SHORTEST, match.cpp:82) the number of shortest paths within the upper bound
 //   AllShortestPathsFunction       (no counterpart) ... the first max_paths of them, LIST(LIST(BIGINT)); bound and max_paths trail the arguments
 //   WalkCountFunction              (no counterpart: {lower,upper} in WALK mode) the number of walks of lower..upper edges
@@ -351,8 +353,8 @@ void KShortestWalks(DataChunk &args, ExpressionState &state, Vector &result, con
 } // namespace
 
 namespace {
-// cheapest_path_length with four arguments (upper == nullptr) or five
-void CheapestPathLength(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper) {
+// cheapest_path_length with four arguments (upper == nullptr) or five; cheapest_walk_length with six (lower != nullptr)
+void CheapestPathLength(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper, const int64_t *lower = nullptr) {
 	auto &info = state.expr.Cast<BoundFunctionExpression>().BindInfo()->Cast<CheapestPathLengthFunctionData>();
 	auto duckpgq_state = GetDuckPGQState(info.context);
 	auto entry = duckpgq_state->csr_list.find(info.csr_id);
@@ -372,8 +374,9 @@ void CheapestPathLength(DataChunk &args, ExpressionState &state, Vector &result,
 	void *out = csr.w.empty() ? static_cast<void *>(FlatVector::GetDataMutable<double>(result))
 	                          : static_cast<void *>(FlatVector::GetDataMutable<int64_t>(result));
 	pgq_csr_t *device = DeviceCSR(*duckpgq_state, csr, v_size);
-	const int rc = upper ? pgq_cheapest_path_length_within(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *upper, out, validity.GetData())
-	                     : pgq_cheapest_path_length(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), out, validity.GetData());
+	const int rc = lower   ? pgq_cheapest_walk_length(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *lower, *upper, out, validity.GetData())
+	               : upper ? pgq_cheapest_path_length_within(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *upper, out, validity.GetData())
+	                       : pgq_cheapest_path_length(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), out, validity.GetData());
 	if (rc != PGQ_OK) ThrowDevice();
 	duckpgq_state->csr_to_delete.insert(info.csr_id);
 }
@@ -392,13 +395,26 @@ void CheapestPathLengthWithinFunction(DataChunk &args, ExpressionState &state, V
 	CheapestPathLength(args, state, result, &upper);
 }
 
+// cheapest_walk_length(csr_id, V, src, dst, lower, upper) -> BIGINT / DOUBLE: the cost of the cheapest walk of lower..upper edges,
+// NULL when there is none or an endpoint is NULL; src == dst is not special (pgq_cheapest_walk_length).  What a weighted
+// -[e]->{lower,upper} needs in WALK mode: a filter around the five-argument cheapest_path_length throws away rows whose cheapest
+// walk is too short although a costlier one fits, and answers 0 for src == dst.  Emitting it is the binder's change, not this
+// layer's.  Bound like cheapest_path_length, registered beside it.
+void CheapestWalkLengthFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	UnifiedVectorFormat lower_fmt, upper_fmt; // constants of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), lower_fmt);
+	args.data[5].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t lower = reinterpret_cast<const int64_t *>(lower_fmt.data)[0], upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	CheapestPathLength(args, state, result, &upper, &lower);
+}
+
 // cheapest_path(csr_id, V, src, dst) -> LIST(BIGINT): the cheapest path itself, [src, e1, v1, ..., ek, dst], bound like
 // cheapest_path_length (CheapestPathLengthFunctionData; registered beside it with a LIST(BIGINT) return type).  The reference has no
 // such function: a MATCH over a weighted edge table gets vertices(p) / edges(p) of its cheapest path from this list the way it gets
 // them from shortestpath's.
 namespace {
-// cheapest_path with four arguments (upper == nullptr) or five
-void CheapestPath(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper) {
+// cheapest_path with four arguments (upper == nullptr) or five; cheapest_walk with six (lower != nullptr)
+void CheapestPath(DataChunk &args, ExpressionState &state, Vector &result, const int64_t *upper, const int64_t *lower = nullptr) {
 	auto &info = state.expr.Cast<BoundFunctionExpression>().BindInfo()->Cast<CheapestPathLengthFunctionData>();
 	auto duckpgq_state = GetDuckPGQState(info.context);
 	auto entry = duckpgq_state->csr_list.find(info.csr_id);
@@ -419,10 +435,12 @@ void CheapestPath(DataChunk &args, ExpressionState &state, Vector &result, const
 	uint64_t child_len = 0;
 	vector<uint64_t> offsets(args.size()), lengths(args.size());
 	pgq_csr_t *device = DeviceCSR(*duckpgq_state, csr, v_size);
-	const int rc = upper ? pgq_cheapest_path_within(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *upper, offsets.data(),
-	                                                lengths.data(), validity.GetData(), &child, &child_len)
-	                     : pgq_cheapest_path(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), offsets.data(), lengths.data(),
-	                                         validity.GetData(), &child, &child_len);
+	const int rc = lower   ? pgq_cheapest_walk(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *lower, *upper, offsets.data(),
+	                                           lengths.data(), validity.GetData(), &child, &child_len)
+	               : upper ? pgq_cheapest_path_within(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), *upper, offsets.data(),
+	                                                  lengths.data(), validity.GetData(), &child, &child_len)
+	                       : pgq_cheapest_path(device, v_size, (int64_t)args.size(), AsVec(src), AsVec(dst), offsets.data(), lengths.data(),
+	                                           validity.GetData(), &child, &child_len);
 	if (rc != PGQ_OK) ThrowDevice();
 	ListVector::Reserve(result, child_len);
 	if (child_len) memcpy(FlatVector::GetDataMutable<int64_t>(ListVector::GetEntry(result)), child, child_len * sizeof(int64_t));
@@ -445,6 +463,16 @@ void CheapestPathWithinFunction(DataChunk &args, ExpressionState &state, Vector 
 	args.data[4].ToUnifiedFormat(args.size(), upper_fmt);
 	const int64_t upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
 	CheapestPath(args, state, result, &upper);
+}
+
+// cheapest_walk(csr_id, V, src, dst, lower, upper) -> LIST(BIGINT): the walk whose cost CheapestWalkLengthFunction returns
+// (pgq_cheapest_walk), registered beside cheapest_path.
+void CheapestWalkFunction(DataChunk &args, ExpressionState &state, Vector &result) {
+	UnifiedVectorFormat lower_fmt, upper_fmt; // constants of the pattern
+	args.data[4].ToUnifiedFormat(args.size(), lower_fmt);
+	args.data[5].ToUnifiedFormat(args.size(), upper_fmt);
+	const int64_t lower = reinterpret_cast<const int64_t *>(lower_fmt.data)[0], upper = reinterpret_cast<const int64_t *>(upper_fmt.data)[0];
+	CheapestPath(args, state, result, &upper, &lower);
 }
 
 void LocalClusteringCoefficientFunction(DataChunk &args, ExpressionState &state, Vector &result) {

@@ -280,6 +280,49 @@ int pgq_cheapest_path_within(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src
                              uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                              uint64_t *out_child_len);
 
+/* cheapest_walk_length(csr_id, V, src, dst, lower, upper) -> BIGINT / DOUBLE and cheapest_walk(csr_id, V, src, dst, lower, upper)
+ * -> LIST(BIGINT): the cost and the list of the cheapest WALK of lower..upper edges — what a weighted -[e]->{lower,upper} needs in
+ * WALK mode (the reference has no counterpart).  A filter around the _within calls is wrong twice: a row whose cheapest walk of at
+ * most `upper` edges has fewer than `lower` edges may well have a costlier walk of lower..upper edges, and that walk is the answer;
+ * and src == dst is answered 0 / [src] where the pattern asks for a closed walk.  With lo = min_hops, K = max_hops, INF = max(T) / 2,
+ * every sum computed as the relaxation computes it (`dist[v] + w`, cheapest_path_length.cpp:29-36; it counts only below INF; NaN and
+ * +inf weights never relax an edge and are never tight, -0.0 is accepted):
+ *     E_0[src] = 0, E_0[v] = INF otherwise
+ *     E_t[x]   = min over the in-slots (u, x) with E_{t-1}[u] < INF of E_{t-1}[u] + w     t = 1 .. lo  (INF if none: NO carry-over of E_{t-1}[x])
+ *     L_lo     = E_lo
+ *     L_t[x]   = min(L_{t-1}[x], min over the in-slots (u, x) of L_{t-1}[u] + w)          t = lo + 1 .. K  (the _within recurrence)
+ * E_t[x] is the minimum over the walks of exactly t edges of the left-to-right fold of their weights, L_t[x] that minimum over
+ * the walks of lo..t edges, bit for bit, for int64 and for double (x -> x + w is monotone for a fixed non-negative w).
+ *   pgq_cheapest_walk_length  L_K[dst]; NULL when that is INF or when src or dst is NULL.
+ *   pgq_cheapest_walk         [x_0, e_1, x_1, ..., e_h, x_h] in shortestpath's layout, the empty walk [src]: h = the smallest t in
+ *                             [lo, K] with L_t[dst] == L_K[dst] as bit patterns (the fewest edges among the cheapest walks of lo..K
+ *                             edges).  With Λ_i = E_i for i <= lo and L_i for i > lo: x_h = dst, and for i = h .. 1, x_{i-1} = the
+ *                             smallest u with Λ_{i-1}[u] < INF and a slot (u, x_i) with Λ_{i-1}[u] + w[s] == Λ_i[x_i], e_i =
+ *                             edge_ids[the first such slot of u's out-list into x_i] (shortestpath's min-parent and first-slot rules).
+ * src == dst is NOT special, as in pgq_walk_length: with lo == 0 the row is 0 (+0.0) / [src], otherwise the cheapest closed walk of
+ * lo..K edges; a vertex without an out-edge or without an in-edge gives NULL for lo >= 1.
+ * Identities: (1) lo == 0 is exactly pgq_cheapest_path_length_within(K) / pgq_cheapest_path_within(K) — values, validity, lists and
+ * payload; the calls forward.  (2) The left-to-right fold of the list's edge weights is pgq_cheapest_walk_length's value bit for bit,
+ * and lo <= h <= K.  (3) Where pgq_cheapest_path_within(K)'s h is at least lo, the value is the _within value; with int64 weights
+ * the list is that call's list too, with DOUBLE weights an absorbed sum can make the lists differ (README).  (4) With one positive
+ * int64 weight c on every edge and K <= 64 the value is c x pgq_walk_length(lo, K) with the same NULLs, and the list is walk 0 of
+ * pgq_k_shortest_walks(lo, K, k = 1).
+ * min_hops < 0 or max_hops < min_hops -> PGQ_ERR_INVALID_ARG.  min_hops > PGQ_WALK_MAX_HOPS -> PGQ_ERR_UNSUPPORTED (in a cyclic graph
+ * the exact rounds never run dry, so `lo` rounds over everything reached need a limit).  max_hops may be anything from min_hops
+ * up, INT64_MAX = no upper bound: the rounds behind lo are Bellman-Ford from E_lo, stand still after at most V - 1 of them and end
+ * with the queue; a large max_hops is NOT forwarded to the unbounded search when lo >= 1.  An unweighted CSR, negative weights,
+ * ids out of range and a V mismatch fail as in pgq_cheapest_path_length_within; a NULL handle -> PGQ_ERR_INVALID_ARG ("NULL csr")
+ * before any device is asked for; a failed call has written nothing.  The list call keeps pgq_cheapest_path_within's log errors
+ * (PGQ_ERR_OOM, PGQ_ERR_UNSUPPORTED beyond 2^31 entries), and its log is larger: the exact rounds log everything they reach in every
+ * round (lo x reached vertices x 528 bytes per 64 sources on top).  pgq_stats_t: `levels` counts the rounds of both phases.
+ * Outputs as pgq_cheapest_path_length_within / pgq_cheapest_path_within.  Not built: _multi forms, a heavy-list split, a
+ * destination bound, the path modes, a two-ended search, forwarding upper - lower >= V - 1 to the unbounded rounds. */
+int pgq_cheapest_walk_length(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                             void *out, uint64_t *out_valid);
+int pgq_cheapest_walk(pgq_csr_t *csr, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                      uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                      uint64_t *out_child_len);
+
 /* shortestpath_count(csr_id, V, src, dst, upper) -> BIGINT and all_shortestpaths(csr_id, V, src, dst, upper, max_paths) ->
  * LIST(LIST(BIGINT)): what SQL/PGQ's ALL SHORTEST needs (the reference's binder rejects the form: "ALL SHORTEST has not been
  * implemented yet", match.cpp:82).  Both are hop-bounded: max_hops = INT64_MAX or >= V - 1 means no bound, max_hops < 0 ->
@@ -546,6 +589,16 @@ int pgq_cheapest_path_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_sr
 int pgq_cheapest_path_within_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,
                                          int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
                                          int64_t *child_used);
+/* pgq_cheapest_walk_length without the chunk ceiling: outputs as pgq_cheapest_path_length_within_bulk_device, each row the cost of
+ * its cheapest walk of min_hops..max_hops edges (src == dst rows included: see pgq_cheapest_walk_length). */
+int pgq_cheapest_walk_length_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                         int64_t max_hops, void *d_out, uint8_t *d_out_valid);
+/* pgq_cheapest_walk without the chunk ceiling: d_out_len[i] = h, the edges of the cheapest walk of min_hops..max_hops edges
+ * (0 only for a src == dst row at min_hops == 0), -1 for NULL rows and rows without such a walk; lists and child-capacity
+ * protocol as pgq_cheapest_path_within_bulk_device. */
+int pgq_cheapest_walk_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t min_hops,
+                                  int64_t max_hops, int64_t *d_out_len, int64_t *d_out_offset, int64_t *d_child, int64_t child_cap,
+                                  int64_t *child_used);
 /* pgq_shortestpath_count without the chunk ceiling: d_out_count[i] = sigma[dst] (saturated), 1 for src == dst, 0 for an
  * unreachable row or one farther apart than max_hops, -1 for a NULL row (d_src[i] < 0). */
 int pgq_shortestpath_count_bulk_device(pgq_csr_t *csr, int64_t n, const int64_t *d_src, const int64_t *d_dst, int64_t max_hops,

@@ -28,6 +28,8 @@
  *   pgq_udf_cheapest_path_length_within  CheapestPathLengthFunction with the pattern's upper bound as fifth argument (match.cpp:658-671)
  *   pgq_udf_cheapest_path           (no counterpart) the cheapest path as a list; bound like cheapest_path_length
  *   pgq_udf_cheapest_path_within    (no counterpart) ... of at most the pattern's upper bound of edges, fifth argument
+ *   pgq_udf_cheapest_walk_length    (no counterpart: a weighted {lower,upper} in WALK mode) the cost of the cheapest walk of lower..upper edges
+ *   pgq_udf_cheapest_walk           (no counterpart) ... and that walk as a list; both bound like cheapest_path_length
  *   pgq_udf_delete_csr              DeleteCsrFunction            src/core/functions/scalar/csr_deletion.cpp:10-20
  *   pgq_udf_csr_get_w_type          GetCsrWTypeFunction          src/core/functions/scalar/csr_get_w_type.cpp:16-36
  *   pgq_udf_reachability            ReachabilityFunction         src/core/functions/scalar/reachability.cpp:165-254 (intended semantics)
@@ -157,6 +159,16 @@ int pgq_udf_cheapest_path(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_v
 int pgq_udf_cheapest_path_within(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t max_hops,
                                  uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
                                  uint64_t *out_child_len);
+/* cheapest_walk_length(id, V, src, dst, lower, upper) -> BIGINT / DOUBLE and cheapest_walk(id, V, src, dst, lower, upper) ->
+ * LIST(BIGINT): the cost and the list of the cheapest walk of lower..upper edges (pgq_cheapest_walk_length / pgq_cheapest_walk:
+ * src == dst is not special, NULL when there is no such walk and for a NULL endpoint; NOT a filter around the _within calls).
+ * Bound through pgq_udf_bind_cheapest, outputs as the _within forms, errors as for pgq_udf_cheapest_path_length; bad bounds are the
+ * device library's PGQ_ERR_INVALID_ARG / PGQ_ERR_UNSUPPORTED (lower > PGQ_WALK_MAX_HOPS).  The reference has no such function. */
+int pgq_udf_cheapest_walk_length(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops,
+                                 int64_t max_hops, void *out, uint64_t *out_valid);
+int pgq_udf_cheapest_walk(pgq_state_t *, int32_t id, int64_t V, int64_t n, pgq_vec_t src, pgq_vec_t dst, int64_t min_hops, int64_t max_hops,
+                          uint64_t *out_offset, uint64_t *out_length, uint64_t *out_valid, const int64_t **out_child,
+                          uint64_t *out_child_len);
 /* reachability(id, is_variant, V, src, dst) -> BOOL; the reference's BOOL argument only selects one of its three
  * internal BFS modes (reachability.cpp:154-163) and does not change the result, so it is not part of this call.
  * Boolean reachability with the semantics the reference intends (reachability.cpp:165-254 indexes its inputs
