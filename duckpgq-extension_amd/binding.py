@@ -111,6 +111,10 @@ def load_hip():
     L.pgq_csr_meet_layout_sizes.argtypes = [C.c_void_p, C.c_void_p]
     L.pgq_csr_meet_layout.restype = C.c_int
     L.pgq_csr_meet_layout.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    L.pgq_csr_hub_sizes.restype = C.c_int
+    L.pgq_csr_hub_sizes.argtypes = [C.c_void_p, C.c_void_p]
+    L.pgq_csr_hub_tables.restype = C.c_int
+    L.pgq_csr_hub_tables.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
     L.pgq_csr_has_prepass_layout.argtypes = [C.c_void_p]
     L.pgq_debug_live_device_blocks.restype = C.c_int64
     L.pgq_debug_live_device_blocks.argtypes = []
@@ -554,6 +558,26 @@ class DeviceCSR:
         cut = lambda a, n: None if a is None else a[:n]
         out = dict(off=off, adj=adj[:E], seg=cut(seg, V), padded=cut(padded, groups), desc=cut(desc, E), work=cut(work, V),
                    packed=cut(packed, pgroups), rhead=cut(rhead, V))
+        out.update(s)
+        return out
+
+    def hub_sizes(self):
+        """pgq_csr_hub_sizes as a dict: H (hub bits per table row), hubs (how many of them are in use), words (64-bit words
+        per row).  A handle without hub tables raises PgqError (PGQ_ERR_UNSUPPORTED, -6)."""
+        sizes = np.zeros(3, dtype=np.int64)
+        _check(self.L.pgq_csr_hub_sizes(self.h, _p(sizes)))
+        return dict(H=int(sizes[0]), hubs=int(sizes[1]), words=int(sizes[2]))
+
+    def hub_tables(self, replica=-1):
+        """The hub tables k_meet3 settles distance-3 and distance-4 rows from (pgq_csr_hub_tables), as a dict: ids [H] (the
+        hubs in bit order, -1 in unused slots), hub1_out, hub1_in, hub2_out, hub2_in [V, words] of uint64, and the scalars of
+        hub_sizes().  replica >= 0: the copy that replicate() made for that entry of the enabled device list.  A handle
+        without tables raises PgqError (PGQ_ERR_UNSUPPORTED, -6)."""
+        s = self.hub_sizes()
+        ids = np.zeros(s["H"], dtype=np.int32)
+        t = [np.zeros((max(self.V, 1), s["words"]), dtype=np.uint64) for _ in range(4)]
+        _check(self.L.pgq_csr_hub_tables(self.h, int(replica), _p(ids), *(_p(x) for x in t)))
+        out = dict(ids=ids, hub1_out=t[0][:self.V], hub1_in=t[1][:self.V], hub2_out=t[2][:self.V], hub2_in=t[3][:self.V])
         out.update(s)
         return out
 

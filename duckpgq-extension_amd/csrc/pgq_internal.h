@@ -198,12 +198,20 @@ struct Options {
 	                               // (profiles/r21/walk_length_*.json, knows graph, E = 39.9 M): a forced pull round costs 0.31 - 0.34 ms whatever is
 	                               // active, forced push rounds walk 6.2 - 8.0 G out-edges per second (the {3,4} and {2,3} lines), so the two meet at
 	                               // 1.9 - 2.7 M out-edges = E / 21 .. E / 15; 16 lies inside, and automatic beat both forced settings on every line
+	// Hub tables (pgq_csr::hubt): per vertex, which of the H highest-degree vertices it reaches in one and in two hops, in either
+	// direction.  k_meet3 proves "distance <= 3" and "<= 4" from them with one compare and skips the two-hop walk.  Read at upload
+	int meet_hubs = 1024;          // H: 256, 512 or 1024 hub bits per table row (0: no tables)
+	int meet_hub_min_degree = 128; // a hub has at least this many edges, out-degree + in-degree
+	int meet_hub_min_count = 64;   // ... and the tables are built only if at least this many vertices qualify
+	int meet_hub_mb = 512;         // the four tables (4 x V x H / 8 bytes) fit this many MB: else H is halved down to 256, else no tables
 	double ball_bias = 1.0;     // the ball runs while ball_bias x its estimated bytes <= the cheaper of the pre-pass and the lane batches
 };
 Options &options();
 // rows k_meet4d's batch pass has answered in this process (every handle and thread); read-only entry meet4_batch_settled of the
 // option table: only that pass advances it, so a test can tell that it ran
 extern std::atomic<long long> g_meet4_batch_settled;
+// rows k_meet3 has answered 3 / 4 from the hub tables (read-only entries meet_hub3_settled, meet_hub4_settled)
+extern std::atomic<long long> g_meet_hub3_settled, g_meet_hub4_settled;
 // per-handle options (pgq_csr_set_option): the override a host thread works under, and a scope that installs a
 // handle's for the duration of a C-ABI call
 // Host worker threads that outlive a call (one idle list per device: a worker keeps its HIP events and its device
@@ -307,6 +315,15 @@ struct pgq_csr {
 	int pack_k = 4;
 	int pack_order = 0; // 1: the packed lists are in degree order (option meet_pack_order at upload) and walked in two parts
 	int pack_align = 1; // groups the packed lists were aligned to at upload (pgq_csr_packed_list finds a list by it)
+	// Hub tables (build_hub_tables, pgq_runtime.hip; null when the options or the graph give none).  The hubs are the hub_n <= hub_h
+	// vertices with the most edges (out + in, at least meet_hub_min_degree; ties to the smaller id), hub h = bit h & 63 of 64-bit
+	// word h >> 6 of a row of hub_h / 8 bytes.  hubt holds four tables of V rows one behind the other (kHub*):
+	// hub1_out[v]: edge v -> h; hub1_in[v]: edge h -> v; hub2_out[v] = OR of hub1_out over N_out(v); hub2_in[v] = OR of hub1_in
+	// over N_in(v).  (hub2_out[s] & hub1_in[d]) | (hub1_out[s] & hub2_in[d]) != 0 proves a 3-edge walk s -> d, hub2_out[s] &
+	// hub2_in[d] != 0 a 4-edge walk.
+	uint4 *hubt = nullptr;      // 4 x V x hub_h / 128 groups of 16 bytes
+	int32_t *hub_ids = nullptr; // hub_h: the hubs in bit order, -1 in unused slots
+	int hub_h = 0, hub_n = 0;
 	std::unique_ptr<pgq::Options> opt;   // this handle's own options (pgq_csr_set_option); null: the process-wide set
 	std::atomic<int> meet_far_rows { 1 }; // the last pre-pass call left rows for k_bibfs (it is launched only then; pgq_meet.hip)
 	int64_t hub_threshold = 0;
@@ -410,7 +427,8 @@ struct CsrArray {
 	size_t bytes;
 	CsrArrayKind kind;
 };
-constexpr int kCsrArrays = 29;
+constexpr int kCsrArrays = 31;
+enum { kHub1Out = 0, kHub1In = 1, kHub2Out = 2, kHub2In = 3 }; // the tables of pgq_csr::hubt, in storage order
 inline std::array<CsrArray, kCsrArrays> csr_arrays(pgq_csr *c) {
 	typedef CsrArrayKind K;
 	const size_t V = (size_t)c->V, En = (size_t)(c->E > 0 ? c->E : 1); // (an empty graph still gets one-entry arrays)
@@ -441,6 +459,8 @@ inline std::array<CsrArray, kCsrArrays> csr_arrays(pgq_csr *c) {
 		{ slot(c->fwork), V * 4, K::meet_layout },
 		{ slot(c->rwork), V * 4, K::meet_layout },
 		{ slot(c->rhead), V * 256, K::meet_layout },
+		{ slot(c->hubt), 4 * V * (size_t)(c->hub_h / 8), K::meet_layout },
+		{ slot(c->hub_ids), (size_t)c->hub_h * 4, K::meet_layout },
 		{ slot(c->rw), En * 8, K::lazy },
 		{ slot(c->wadj), adj, K::lazy },
 		{ slot(c->wsorted), En * 8, K::lazy },

@@ -113,12 +113,15 @@ constexpr int kM4Threads = 64 * PGQ_MEET4_WAVES;
 constexpr int kBatchTestCap = 4096; // k_meet4d's batch pass: entries a wavefront may request of the tested side's two-hop lists before its row goes the long way
 constexpr int kMeet4BatchAlways = 0x100; // ... flag beside the batch size in the kernel's `batch` argument: also when few rows are queued
 constexpr int kMeet4TraceWords = 8; // option meet_trace: 64-bit words per workgroup of k_meet4d
+constexpr u32 kHubP3 = 1u, kHubP4 = 2u; // k_meet3's verdict on a row from the hub tables: a 3-edge walk exists / a 4-edge walk exists
 constexpr u32 kMeetKnown4Bit = 0x80000000u; // in the queued row indices: the row is known to be at distance >= 4
 constexpr int kMeetStatSlots = 256; // statistics are spread over slots: 10^4 atomics on one address take longer than the walks
 struct MeetCounters {
 	unsigned long long entries[kMeetStatSlots];  // adjacency entries scanned (both kinds of list)
 	unsigned long long vertices[kMeetStatSlots]; // vertices expanded (offset pairs fetched)
 	unsigned long long walked[kMeetStatSlots];   // ... of the entries: those walked over the packed lists (pgq_pack.h)
+	unsigned long long hub_settled[192];         // k_meet3's slots: rows answered 3 (low word) and 4 (high word) from the hub tables
+	unsigned long long hub_rows[192];            // ... rows that read their four table rows
 	u32 bad;                    // an id outside [0, V)
 	u32 pad[3];
 };
@@ -178,6 +181,7 @@ struct MeetHostBlock { // pinned host memory, written by the last workgroup of t
 	unsigned long long ball_entries, ball_descs;
 	u32 ball_go, ball_nseg, ball_nrun, ball_open;
 	u32 batch_settled, pad; // rows k_meet4d's batch pass answered (read-only option meet4_batch_settled)
+	unsigned long long hub3, hub4, hub_rows; // k_meet3: rows answered 3 / 4 from the hub tables (meet_hub3_settled, meet_hub4_settled), rows that read them
 };
 static_assert(sizeof(MeetHostBlock) <= sizeof(MeetPinned::report), "pinned statistics block too small");
 __device__ __forceinline__ void queue_push(const MeetQueue &q, u32 row, const MeetEntry &e) { // one lane
@@ -224,12 +228,12 @@ __device__ __forceinline__ MeetRow load_row(const MeetQueue &q, u32 pos) {
 __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *fin) {
 	if (!fin) return;
 	__shared__ u32 s_last;
-	__shared__ unsigned long long s_sum[9];
+	__shared__ unsigned long long s_sum[12];
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		__threadfence_system(); // this workgroup's results (possibly in pinned host memory) before its ticket
 		s_last = atomicAdd(&db->ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
-		for (int k = 0; k < 9; k++) s_sum[k] = 0;
+		for (int k = 0; k < 12; k++) s_sum[k] = 0;
 	}
 	__syncthreads();
 	if (!s_last) return;
@@ -247,6 +251,17 @@ __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *f
 		if (e) atomicAdd(&s_sum[2 * st], e);
 		if (v) atomicAdd(&s_sum[2 * st + 1], v);
 		if (pw) atomicAdd(&s_sum[6 + st], pw);
+		if (k < 192) {
+			const unsigned long long hs = __hip_atomic_load(&db->m.hub_settled[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			const unsigned long long hr = __hip_atomic_load(&db->m.hub_rows[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (hr) {
+				db->m.hub_settled[k] = 0;
+				db->m.hub_rows[k] = 0;
+				atomicAdd(&s_sum[9], hs & 0xFFFFFFFFull);
+				atomicAdd(&s_sum[10], hs >> 32);
+				atomicAdd(&s_sum[11], hr);
+			}
+		}
 	}
 	__syncthreads();
 	if (threadIdx.x == 0) {
@@ -255,6 +270,7 @@ __device__ __forceinline__ void meet_finalize(MeetDevBlock *db, MeetHostBlock *f
 			fin->vertices[k] = s_sum[2 * k + 1];
 			fin->walked[k] = s_sum[6 + k];
 		}
+		fin->hub3 = s_sum[9], fin->hub4 = s_sum[10], fin->hub_rows = s_sum[11];
 		fin->bad = __hip_atomic_load(&db->m.bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		for (int k = 0; k < 3; k++) {
 			fin->count[k] = __hip_atomic_load(&db->count[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -357,12 +373,13 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
                                                   int64_t *__restrict__ out, MeetPath *__restrict__ rec, int64_t cap,
                                                   const u32 *__restrict__ go, MeetDevBlock *__restrict__ db, MeetQueue q,
                                                   MeetHostBlock *__restrict__ fin, int bound, bool split, int rows_shift,
-                                                  int tail_rows) {
+                                                  int tail_rows, const uint4 *__restrict__ hubt, int hub_lpr) {
 	static_assert(kMeetWPB == 1, "one wavefront per workgroup: the LDS arrays are addressed statically");
 	static_assert(!PATHS || K == 4, "the path flow walks the 32-bit lists");
 	__shared__ __attribute__((aligned(16))) u32 bm[kFltWords];
 	__shared__ __attribute__((aligned(16))) unsigned char win[64];
 	__shared__ __attribute__((aligned(16))) uint4 hdr[kMeet3RowsMax][2]; // per row of the group: s, d, so, degS | di, degD, workS, workD
+	__shared__ unsigned char hubv[kMeet3RowsMax]; // ... and what the hub tables prove about it: kHubP3 | kHubP4
 	MeetCounters *const mc = &db->m;
 	if ((go && *go == 0) || db->ball.go) { // (a scalar load: one word read by every wavefront through the vector path is a hot spot on one L2
 		meet_finalize(db, fin); // channel — polling it per row while the decision kernel ran beside this one made k_meet3
@@ -378,6 +395,7 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
 	};
 	unsigned long long entries = 0, walked = 0; // wave-uniform
 	u32 vertices = 0;
+	u32 hub3 = 0, hub4 = 0, hub_rows = 0; // wave-uniform: rows answered 3 / 4 from the hub tables, rows that read them
 	const int wave0 = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
 	const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
 	const Meet3Schedule sched((int)n, rows_shift, tail_rows);
@@ -387,31 +405,73 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
 		// The headers of the group's rows in two vector round trips instead of three scalar ones per row: lane r loads row r's ids,
 		// settles the row if it is trivial (the tests of a single row, in their order), loads its offsets and walk sizes and leaves
 		// them in LDS.  Nothing of it stays in a register across a row's walk.  degS == 0 marks a row that is settled.
-		if (lane < nrows) {
-			// (an opaque copy of the lane, and 32-bit offsets from the group's scalar addresses: what the compiler can compute before the
-			// loops from the lane alone — hdr[lane]'s address, the zero above a 64-bit lane — stayed in registers across the walks and spilled)
+		// (an opaque copy of the lane, and 32-bit offsets from the group's scalar addresses: what the compiler can compute before the
+		// loops from the lane alone — hdr[lane]'s address, the zero above a 64-bit lane — stayed in registers across the walks and spilled)
+		{
 			u32 slot = (u32)lane;
 			asm volatile("" : "+v"(slot));
-			const int64_t s = *(const int64_t *)((const char *)(src + i0) + slot * 8u), d = *(const int64_t *)((const char *)(dst + i0) + slot * 8u);
-			uint4 h0 = make_uint4((u32)s, (u32)d, 0u, 0u), h1 = make_uint4(0u, 0u, 0u, 0u);
-			int64_t settled = -1; // what a trivial row is answered with
-			if (s < 0) { // NULL row (iterativelength.cpp:99-101)
-			} else if (s >= V || d < 0 || d >= V) {
-				mc->bad = 1;
-			} else if (s == d) { // iterativelength.cpp:102-103
-				settled = 0;
-			} else {
-				const int so = (int)off[s], se = (int)off[s + 1], di = (int)roff[d], de = (int)roff[d + 1];
-				const u32 workS = fwork[s], workD = rwork[d];
-				const int degS = se - so, degD = de - di;
-				if (degS != 0 && degD != 0) { // (else no path can exist: NULL like an exhausted search, iterativelength.cpp:133-139)
-					h0.z = (u32)so, h0.w = (u32)degS;
-					h1 = make_uint4((u32)di, (u32)degD, workS, workD);
+			int64_t s = -1, d = -1;
+			const bool mine_row = slot < (u32)nrows;
+			if (mine_row) s = *(const int64_t *)((const char *)(src + i0) + slot * 8u), d = *(const int64_t *)((const char *)(dst + i0) + slot * 8u);
+			// (the ids have arrived HERE, on every path: where the first wait for them stood inside the second block below, it also
+			// waited for the table rows requested in between, and the offsets went out a round trip later)
+			asm volatile("" : "+v"(s), "+v"(d));
+			// Hub tables (pgq_csr::hubt): hub_lpr lanes of the 64 / kMeet3RowsMax that belong to a row load 16 bytes each of its four
+			// table rows, in the same round trip as the offsets below, and the row's lanes vote on the two proofs.  Rows the header
+			// settles read nothing.  The verdict goes to LDS: nothing of this is live across a walk.
+			uint4 t2o = make_uint4(0u, 0u, 0u, 0u), t1i = t2o, t1o = t2o, t2i = t2o; // (left undefined for the other lanes, they stayed live around the loop: 16 spilled)
+			bool hub_on = false, hub_lane = false; // hub_on: wave-uniform
+			if constexpr (!PATHS) hub_on = hubt != nullptr;
+			if (hub_on) {
+				constexpr int kLanes = 64 / kMeet3RowsMax;
+				const bool reads = s >= 0 && s < V && d >= 0 && d < V && s != d; // (false in the lanes past the group's rows)
+				hub_rows += (u32)__popcll(__ballot(reads));
+				// (from the opaque copy of the lane, like everything here: see above)
+				const u32 hs = (u32)__shfl((int)(reads ? (u32)s : 0xFFFFFFFFu), (int)(slot / (u32)kLanes)), hd = (u32)__shfl((int)(u32)d, (int)(slot / (u32)kLanes));
+				const u32 col = slot % (u32)kLanes;
+				hub_lane = hs != 0xFFFFFFFFu && col < (u32)hub_lpr;
+				if (hub_lane) {
+					// (a table is below 4 GB, build_hub_tables: a scalar base per table and one 32-bit byte offset per endpoint)
+					const size_t table = (size_t)V * (size_t)hub_lpr * 16u;
+					const u32 os = (hs * (u32)hub_lpr + col) * 16u, od = (hd * (u32)hub_lpr + col) * 16u;
+					const char *const base = (const char *)hubt;
+					t2o = *(const uint4 *)(base + kHub2Out * table + os);
+					t1i = *(const uint4 *)(base + kHub1In * table + od);
+					t1o = *(const uint4 *)(base + kHub1Out * table + os);
+					t2i = *(const uint4 *)(base + kHub2In * table + od);
 				}
 			}
-			if (h0.w == 0) *(int64_t *)((char *)(out + i0) + slot * 8u) = settled;
-			hdr[slot][0] = h0;
-			hdr[slot][1] = h1;
+			if (mine_row) {
+				uint4 h0 = make_uint4((u32)s, (u32)d, 0u, 0u), h1 = make_uint4(0u, 0u, 0u, 0u);
+				int64_t settled = -1; // what a trivial row is answered with
+				if (s < 0) { // NULL row (iterativelength.cpp:99-101)
+				} else if (s >= V || d < 0 || d >= V) {
+					mc->bad = 1;
+				} else if (s == d) { // iterativelength.cpp:102-103
+					settled = 0;
+				} else {
+					const int so = (int)off[s], se = (int)off[s + 1], di = (int)roff[d], de = (int)roff[d + 1];
+					const u32 workS = fwork[s], workD = rwork[d];
+					const int degS = se - so, degD = de - di;
+					if (degS != 0 && degD != 0) { // (else no path can exist: NULL like an exhausted search, iterativelength.cpp:133-139)
+						h0.z = (u32)so, h0.w = (u32)degS;
+						h1 = make_uint4((u32)di, (u32)degD, workS, workD);
+					}
+				}
+				if (h0.w == 0) *(int64_t *)((char *)(out + i0) + slot * 8u) = settled;
+				hdr[slot][0] = h0;
+				hdr[slot][1] = h1;
+			}
+			if constexpr (!PATHS) {
+				bool p3 = false, p4 = false;
+				if (hub_lane) {
+					p3 = (((t2o.x & t1i.x) | (t1o.x & t2i.x)) | ((t2o.y & t1i.y) | (t1o.y & t2i.y)) | ((t2o.z & t1i.z) | (t1o.z & t2i.z)) |
+					      ((t2o.w & t1i.w) | (t1o.w & t2i.w))) != 0u;
+					p4 = ((t2o.x & t2i.x) | (t2o.y & t2i.y) | (t2o.z & t2i.z) | (t2o.w & t2i.w)) != 0u;
+				}
+				const unsigned long long b3 = __ballot(p3), b4 = __ballot(p4), mine = 0xFFull << ((slot & 7u) * 8u); // (no tables: no proof)
+				if (mine_row) hubv[slot] = (unsigned char)(((b3 & mine) ? kHubP3 : 0u) | ((b4 & mine) ? kHubP4 : 0u));
+			}
 		}
 		__builtin_amdgcn_wave_barrier();
 		for (int r = 0; r < nrows; r++) {
@@ -535,6 +595,15 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
 					if (lane == 0) answer(i, -1);
 					continue;
 				}
+				// distances 1 and 2 are excluded, and a hub lies two hops from one endpoint and one from the other: a 3-edge walk
+				// exists and none shorter.  No walk.  (A hop count alone: a path needs the tie-break's witness.)
+				if constexpr (!PATHS) {
+					if (__builtin_amdgcn_readfirstlane((int)hubv[r]) & (int)kHubP3) {
+						if (lane == 0) answer(i, 3);
+						hub3++;
+						continue;
+					}
+				}
 			}
 			// distance 3: the padded lists of the expanded side's vertices, one filter probe per entry (the exact test only for
 			// what the filter lets through), ended by the first pass with a hit.  PATHS: requests are processed in walk order
@@ -595,6 +664,14 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
 					       0.0, (rt1 - rt0) * 0.01, (rt2 - rt1) * 0.01, degS, degD, workS, workD, set_n, exp_n, entries - ent_before, (int)found, (int)capped);
 			}
 #endif
+			// The walk ran to its END without a witness (distance >= 4) and the hub tables show a 4-edge walk: the distance is 4.  A
+			// walk that was cut proves nothing; under a bound of 3 the row is NULL.  (The verdict is read again here, not kept across
+			// the walk.)  Wave-uniform
+			bool far4 = false;
+			if constexpr (!PATHS) {
+				if (!found && !capped && (!BND || bound >= 4)) far4 = (__builtin_amdgcn_readfirstlane((int)hubv[r]) & (int)kHubP4) != 0;
+			}
+			hub4 += far4 ? 1u : 0u;
 			if (lane == 0) {
 				if constexpr (PATHS) {
 					if (found) {
@@ -605,8 +682,8 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
 				// the walk ran to its end without a witness: the distance is at least 4; it was cut short: distances 1 and 2
 				// are excluded and the next stage takes the walk up where it stopped
 				const bool beyond = BND && bound < 4 && !found && !capped; // distance >= 4 proven under a bound of 3
-				out[i] = found ? 3 : (beyond ? -1 : (capped ? kMeetOpen : kMeetOpen4));
-				if (!found && !beyond) {
+				out[i] = found ? 3 : (far4 ? 4 : (beyond ? -1 : (capped ? kMeetOpen : kMeetOpen4)));
+				if (!found && !beyond && !far4) {
 					ent.flags = capped ? (kEntKnown3 | (fwd ? kEntFwd : 0u) | ((u32)resume << kEntResumeShift)) : kEntKnown4;
 					queue_push(q, (u32)i, ent);
 				}
@@ -614,7 +691,13 @@ __global__ __launch_bounds__(64 * kMeetWPB, meet3_waves(PATHS, DEPTH, K, BND)) v
 		}
 		__builtin_amdgcn_wave_barrier(); // (a capped grid: the next group's headers overwrite these)
 	}
-	if (lane == 0) meet_add_stats(mc, 0, entries, (unsigned long long)vertices, walked);
+	if (lane == 0) {
+		meet_add_stats(mc, 0, entries, (unsigned long long)vertices, walked);
+		if (hub_rows) { // (one wavefront per workgroup: the slot is blockIdx's, as above)
+			atomicAdd(&mc->hub_settled[blockIdx.x % 192], (unsigned long long)hub3 | (unsigned long long)hub4 << 32);
+			atomicAdd(&mc->hub_rows[blockIdx.x % 192], (unsigned long long)hub_rows);
+		}
+	}
 	meet_finalize(db, fin);
 }
 
@@ -2255,7 +2338,7 @@ private:
 				if constexpr (meet3_built(PATHS, BIGV, DEPTH, K)) {
 					hipLaunchKernelGGL((k_meet3<PATHS, BIGV, DEPTH, K, BND>), grid, dim3(64 * kMeetWPB), 0, st, n, a.d_src, a.d_dst, c->V, c->off, c->adj,
 					                   c->roff, c->radj, c->fdesc, c->rdesc, xf, xr, c->fwork, c->rwork, a.d_out, rec, cap, d_go, db, q[0], fin, bound, split,
-					                   rows_shift, tail_rows);
+					                   rows_shift, tail_rows, PATHS || a.no_hubs ? (const uint4 *)nullptr : (const uint4 *)c->hubt, c->hubt ? c->hub_h / 128 : 0);
 					launched = true;
 				}
 			};
@@ -2343,6 +2426,9 @@ private:
 		const MeetHostBlock &h = *hb;
 		if (d_trace) PGQ_TRY(print_meet4d_trace(d_trace, grid4, h.count[0], h.count_back));
 		if (h.batch_settled) g_meet4_batch_settled.fetch_add((long long)h.batch_settled, std::memory_order_relaxed);
+		if (h.hub3) g_meet_hub3_settled.fetch_add((long long)h.hub3, std::memory_order_relaxed);
+		if (h.hub4) g_meet_hub4_settled.fetch_add((long long)h.hub4, std::memory_order_relaxed);
+		r->hub_settled = (int64_t)(h.hub3 + h.hub4);
 		if (ball_mode && h.ball_go) return ball_took(h);
 		if (ball_mode) // it looked at the rows (8 B per row, twice) and declined
 			S.algo_bytes[K_BALL] += 16.0 * (double)n;
@@ -2363,7 +2449,8 @@ private:
 			const double pw = (double)std::min(h.walked[k], h.entries[k]);
 			return 4.0 * ((double)h.entries[k] - pw) + (16.0 / (double)std::max(4, c->pack_k)) * pw;
 		};
-		S.algo_bytes[K_MEET] += list_bytes(0) + 16.0 * (double)h.vertices[0] + 64.0 * (double)n;
+		// ... and, where it read the hub tables, four table rows of hub_h / 8 bytes
+		S.algo_bytes[K_MEET] += list_bytes(0) + 16.0 * (double)h.vertices[0] + 64.0 * (double)n + 4.0 * (double)(c->hub_h / 8) * (double)h.hub_rows;
 		S.algo_bytes[K_MEET4] += list_bytes(1) + 16.0 * (double)h.vertices[1] + 56.0 * (double)(h.count[0] + h.count_back);
 		S.algo_bytes[K_BIBFS] += list_bytes(2) + 16.0 * (double)h.vertices[2];
 		tstats().route_bytes += 4.0 * (double)(h.entries[0] + h.entries[1] + h.entries[2]) + 16.0 * (double)(h.vertices[0] + h.vertices[1] + h.vertices[2]) +

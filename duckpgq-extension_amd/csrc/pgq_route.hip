@@ -119,7 +119,11 @@ static int calibrate_prepass(pgq_csr *c) {
 	const pgq_stats_t saved = S; // the caller's statistics are about its own rows
 	const double rb0 = tstats().route_bytes;
 	PrepassResult r;
-	const int rc = meet_prepass(c, w, PrepassArgs { n0, w->in_src.as<int64_t>(), w->in_dst.as<int64_t>(), w->out_len.as<int64_t>() }, &r);
+	// (without the hub tables: the figure is what a row's WALK moves, on a handle with tables as on one without, so that the
+	// tables move no route — they make the pre-pass faster where it runs, the lane batches' model was fitted against the walks)
+	PrepassArgs pa { n0, w->in_src.as<int64_t>(), w->in_dst.as<int64_t>(), w->out_len.as<int64_t>() };
+	pa.no_hubs = true;
+	const int rc = meet_prepass(c, w, pa, &r);
 	const double bytes = tstats().route_bytes - rb0; // at 4 B per list entry (ThreadStats::route_bytes)
 	S = saved;
 	PGQ_TRY(rc);
@@ -339,7 +343,8 @@ private:
 		}
 		if (!r.answered) return PGQ_OK;
 		if (n >= 1024 && !r.ball_took && !bounded) { // what these rows really moved refines the CSR's bytes per row (half the weight to the newest call)
-			const double now = std::max(64.0, (tstats().route_bytes - b0) / (double)n);
+			// (a row answered from the hub tables moved next to nothing: it counts with the estimate it was routed under, see calibrate_prepass)
+			const double now = std::max(64.0, (tstats().route_bytes - b0 + (double)r.hub_settled * prepass_row_bytes(c)) / (double)n);
 			const double old = c->cal.meet_bpr.load(std::memory_order_relaxed);
 			c->cal.meet_bpr.store(old > 0 ? 0.5 * old + 0.5 * now : now, std::memory_order_relaxed);
 		}

@@ -253,6 +253,7 @@ struct OptRef {
 	const std::atomic<long long> *counter = nullptr; // a counter the library keeps: pgq_get_option reads it, nothing sets it
 };
 std::atomic<long long> g_meet4_batch_settled { 0 };
+std::atomic<long long> g_meet_hub3_settled { 0 }, g_meet_hub4_settled { 0 };
 static std::vector<OptRef> option_table(Options &o) {
 	return {
 		{ "words", &o.words, nullptr },
@@ -341,6 +342,12 @@ static std::vector<OptRef> option_table(Options &o) {
 		{ "meet4_grid_mult", &o.meet4_grid_mult, nullptr },
 		{ "meet4_batch", &o.meet4_batch, nullptr },
 		{ "meet4_batch_settled", nullptr, nullptr, &g_meet4_batch_settled },
+		{ "meet_hubs", &o.meet_hubs, nullptr },
+		{ "meet_hub_min_degree", &o.meet_hub_min_degree, nullptr },
+		{ "meet_hub_min_count", &o.meet_hub_min_count, nullptr },
+		{ "meet_hub_mb", &o.meet_hub_mb, nullptr },
+		{ "meet_hub3_settled", nullptr, nullptr, &g_meet_hub3_settled },
+		{ "meet_hub4_settled", nullptr, nullptr, &g_meet_hub4_settled },
 		{ "meet_trace", &o.meet_trace, nullptr },
 		{ "mode_step_cap", &o.mode_step_cap, nullptr },
 		{ "walk_length_pull", &o.walk_length_pull, nullptr },
@@ -1503,6 +1510,128 @@ static int build_meet_layout(pgq_csr *c, hipStream_t st) {
 	return PGQ_OK;
 }
 
+// ---- hub tables (pgq_csr::hubt) ---------------------------------------------------------------------------------------------
+// Sort key of a vertex in the hub selection: most edges (out + in) first, ties to the smaller id; all ones: not a hub.
+__global__ __launch_bounds__(256) void k_hub_keys(int64_t V, const int64_t *__restrict__ off, const int64_t *__restrict__ roff, u32 min_degree,
+                                                  unsigned long long *__restrict__ key) {
+	const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (v >= V) return;
+	const unsigned long long deg = (unsigned long long)(off[v + 1] - off[v]) + (unsigned long long)(roff[v + 1] - roff[v]);
+	const u32 sc = (u32)min(deg, 0xFFFFFFFEull);
+	key[v] = sc >= min_degree ? ((unsigned long long)(0xFFFFFFFFu - sc) << 32 | (unsigned long long)(u32)v) : ~0ull;
+}
+__global__ void k_hub_slots(int n, const int32_t *__restrict__ ids, int32_t *__restrict__ slot) {
+	const int h = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	if (h < n) slot[ids[h]] = h;
+}
+// One wavefront per vertex: the hubs among its list's entries, as bits of a row of `words` 32-bit words (built in LDS).
+__global__ __launch_bounds__(256) void k_hub1(int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                              const int32_t *__restrict__ slot, int words, u32 *__restrict__ out) {
+	__shared__ u32 row[4][32];
+	const int w = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+	const int64_t v = (int64_t)blockIdx.x * 4 + w;
+	if (lane < 32) row[w][lane] = 0;
+	__syncthreads();
+	if (v < V) {
+		const int64_t end = off[v + 1];
+		for (int64_t e = off[v] + lane; e < end; e += 64) {
+			const int h = slot[adj[e]];
+			if (h >= 0) atomicOr(&row[w][h >> 5], 1u << (h & 31));
+		}
+	}
+	__syncthreads();
+	if (v < V && lane < words) out[v * words + lane] = row[w][lane];
+}
+// One wavefront per vertex: the OR of its neighbours' one-hop rows.  LPR = H / 128 lanes load 16 bytes each of a neighbour's
+// row, 64 / LPR neighbours per trip; every lane keeps its own 16 bytes and the lanes of a column are folded at the end.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_hub2(int64_t V, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                              const uint4 *__restrict__ h1, uint4 *__restrict__ h2) {
+	const int lane = (int)threadIdx.x & 63;
+	const int64_t v = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+	if (v >= V) return;
+	const int col = lane % LPR;
+	uint4 acc = make_uint4(0u, 0u, 0u, 0u);
+	const int64_t end = off[v + 1];
+#pragma unroll 4
+	for (int64_t p = off[v] + lane / LPR; p < end; p += 64 / LPR) {
+		const uint4 x = h1[(size_t)adj[p] * LPR + col];
+		acc.x |= x.x, acc.y |= x.y, acc.z |= x.z, acc.w |= x.w;
+	}
+	for (int o = LPR; o < 64; o <<= 1) {
+		acc.x |= (u32)__shfl_xor((int)acc.x, o);
+		acc.y |= (u32)__shfl_xor((int)acc.y, o);
+		acc.z |= (u32)__shfl_xor((int)acc.z, o);
+		acc.w |= (u32)__shfl_xor((int)acc.w, o);
+	}
+	if (lane < LPR) h2[(size_t)v * LPR + lane] = acc;
+}
+static void drop_hub_tables(pgq_csr *c) {
+	dev_free(c->hubt);
+	dev_free(c->hub_ids);
+	c->hubt = nullptr;
+	c->hub_ids = nullptr;
+	c->hub_h = c->hub_n = 0;
+}
+// Picks the hubs and fills the four tables (options meet_hubs, meet_hub_min_degree, meet_hub_min_count, meet_hub_mb).  No
+// tables — the options say so, too few hubs, no room — is not an error: k_meet3 then walks every row as before.
+static int build_hub_tables(pgq_csr *c, hipStream_t st) {
+	c->hub_h = c->hub_n = 0;
+	const Options &o = options();
+	if (!c->fdesc || c->V <= 0 || c->E <= 0) return PGQ_OK;
+	int H = o.meet_hubs >= 1024 ? 1024 : (o.meet_hubs >= 512 ? 512 : (o.meet_hubs >= 256 ? 256 : 0));
+	const size_t budget = (size_t)std::max(0, o.meet_hub_mb) << 20;
+	auto hub_bytes = [&](int h) { return 4 * (size_t)c->V * (size_t)(h / 8) + 4 * (size_t)h; }; // the four tables and the hub ids
+	while (H > 256 && hub_bytes(H) > budget) H >>= 1;
+	if (H == 0 || hub_bytes(H) > budget) return PGQ_OK;
+	if ((size_t)c->V * (size_t)(H / 8) >= (1ull << 32)) return PGQ_OK; // (k_meet3 addresses a table's rows with 32-bit byte offsets)
+	const int64_t V = c->V;
+	const int min_count = std::max(1, o.meet_hub_min_count);
+	DevTemps temps(st);
+	unsigned long long *d_key = nullptr, *d_sorted = nullptr;
+	int32_t *d_slot = nullptr;
+	PGQ_TRY(temps.alloc(&d_key, (size_t)V));
+	PGQ_TRY(temps.alloc(&d_sorted, (size_t)V));
+	hipLaunchKernelGGL(k_hub_keys, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, c->off, c->roff, (u32)std::max(0, o.meet_hub_min_degree), d_key);
+	PGQ_TRY(cub_run(temps, [&](void *tmp, size_t &tb) { return hipcub::DeviceRadixSort::SortKeys(tmp, tb, d_key, d_sorted, (int)V, 0, 64, st); }));
+	std::vector<unsigned long long> head((size_t)std::min<int64_t>(V, std::max(H, min_count)));
+	PGQ_HIP_TRY(hipMemcpyAsync(head.data(), d_sorted, head.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	PGQ_HIP_TRY(hipStreamSynchronize(st));
+	size_t qualify = 0;
+	while (qualify < head.size() && head[qualify] != ~0ull) qualify++;
+	if (qualify < (size_t)min_count) return PGQ_OK;
+	const int n_hubs = (int)std::min<size_t>(qualify, (size_t)H);
+	std::vector<int32_t> ids((size_t)H, -1);
+	for (int h = 0; h < n_hubs; h++) ids[(size_t)h] = (int32_t)(u32)head[(size_t)h];
+	c->hub_h = H; // (csr_arrays sizes the tables from it)
+	if (csr_alloc(c, c->hubt) != PGQ_OK || csr_alloc(c, c->hub_ids) != PGQ_OK) {
+		(void)hipGetLastError();
+		drop_hub_tables(c);
+		return PGQ_OK;
+	}
+	PGQ_TRY(temps.alloc(&d_slot, (size_t)V));
+	PGQ_HIP_TRY(hipMemcpyAsync(c->hub_ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	PGQ_HIP_TRY(hipMemsetAsync(d_slot, 0xFF, (size_t)V * sizeof(int32_t), st));
+	hipLaunchKernelGGL(k_hub_slots, dim3((unsigned)((n_hubs + 255) / 256)), dim3(256), 0, st, n_hubs, c->hub_ids, d_slot);
+	const int lpr = H / 128;
+	const size_t table = (size_t)V * (size_t)lpr; // 16-byte groups per table
+	const dim3 grid((unsigned)((V + 3) / 4));
+	hipLaunchKernelGGL(k_hub1, grid, dim3(256), 0, st, V, c->off, c->adj, d_slot, H / 32, (u32 *)(c->hubt + kHub1Out * table));
+	hipLaunchKernelGGL(k_hub1, grid, dim3(256), 0, st, V, c->roff, c->radj, d_slot, H / 32, (u32 *)(c->hubt + kHub1In * table));
+	auto second = [&](auto l) {
+		constexpr int LPR = decltype(l)::value;
+		hipLaunchKernelGGL(k_hub2<LPR>, grid, dim3(256), 0, st, V, c->off, c->adj, c->hubt + kHub1Out * table, c->hubt + kHub2Out * table);
+		hipLaunchKernelGGL(k_hub2<LPR>, grid, dim3(256), 0, st, V, c->roff, c->radj, c->hubt + kHub1In * table, c->hubt + kHub2In * table);
+	};
+	if (lpr == 8) second(std::integral_constant<int, 8>());
+	else if (lpr == 4) second(std::integral_constant<int, 4>());
+	else second(std::integral_constant<int, 2>());
+	PGQ_HIP_TRY(hipStreamSynchronize(st)); // (ids goes out of scope)
+	PGQ_HIP_TRY(hipGetLastError());
+	c->hub_n = n_hubs;
+	return PGQ_OK;
+}
+
 // Builds everything derived from (off, adj64) that already sit in device memory.
 static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { // d_adj64 == nullptr: c->adj is set
 	const int64_t V = c->V, E = c->E;
@@ -1638,14 +1767,22 @@ static int finish_upload(pgq_csr *c, const int64_t *d_adj64, hipStream_t st) { /
 		c->ppadj_groups = c->prpadj_groups = 0;
 		c->pack_k = 4;
 		c->pack_order = 0;
+		c->hub_h = c->hub_n = 0;
 	}
 	PGQ_HIP_TRY(hipStreamSynchronize(st));
 	tr.mark("padded adjacency + slot descriptors");
+	if (const int hrc = build_hub_tables(c, st); hrc != PGQ_OK) { // (out of memory: no tables, like the layout above)
+		(void)hipStreamSynchronize(st);
+		drop_hub_tables(c);
+		if (hrc != PGQ_ERR_OOM) return hrc;
+		(void)hipGetLastError();
+	}
+	tr.mark("hub tables");
 	calibration_load(c); // (max degrees, E and the layout's pack_k are set above)
 	c->bytes = (V + 1) * 16 + 8 * V + E * (4 + 4 + 1 + (c->rpk ? 4 : 0)) + (c->edge_ids ? E * 8 : 0) + (c->w ? E * 8 : 0) +
 	           n_items * (int64_t)sizeof(HubItem) +
 	           (c->fdesc ? 2 * E * 16 + 2 * V * 12 + (c->padj_groups + c->rpadj_groups + c->ppadj_groups + c->prpadj_groups) * 16 : 0) +
-	           (c->rhead ? V * 256 : 0);
+	           (c->rhead ? V * 256 : 0) + (c->hubt ? 4 * V * (int64_t)(c->hub_h / 8) + (int64_t)c->hub_h * 4 : 0);
 	return PGQ_OK;
 }
 
@@ -1655,13 +1792,14 @@ struct CalEntry {
 	double two_hop_mean;
 	pgq_csr::RouteCalibration::Figures figures;
 	std::vector<uint8_t> level_plan[6];
-	int pack_k, pack_order;
+	int pack_k, pack_order, hub_h;
 };
 static std::mutex g_cal_lock;
 static std::vector<CalEntry> g_cal; // a handful of graph shapes, the most recent last
 static bool cal_same(const CalEntry &e, const pgq_csr *c) {
 	return e.V == c->V && e.E == c->E && e.max_out == c->max_out_degree && e.max_in == c->max_in_degree && e.two_hop_mean == c->two_hop_mean &&
-	       e.pack_k == c->pack_k && e.pack_order == c->pack_order; // the route timings differ between the packed and the 32-bit walks, and with the lists' order
+	       e.pack_k == c->pack_k && e.pack_order == c->pack_order && // the route timings differ between the packed and the 32-bit walks, with the lists' order
+	       e.hub_h == c->hub_h;                                       // ... and with the hub tables, which take most rows off the walk
 }
 void calibration_load(pgq_csr *c) {
 	if (!c || !options().calibration_cache) return;
@@ -1676,7 +1814,7 @@ void calibration_load(pgq_csr *c) {
 }
 void calibration_store(pgq_csr *c) {
 	if (!c || c->is_replica || !options().calibration_cache) return;
-	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {}, c->pack_k, c->pack_order };
+	CalEntry n { c->V, c->E, c->max_out_degree, c->max_in_degree, c->two_hop_mean, c->cal.snapshot(), {}, c->pack_k, c->pack_order, c->hub_h };
 	bool any = n.figures.meet_bpr > 0 || n.figures.ball_open_frac > 0 || n.figures.route_ball_ns > 0;
 	{
 		std::lock_guard<std::mutex> g2(c->plan_lock);
@@ -2009,6 +2147,8 @@ static int clone_csr(const pgq_csr *c, int dev, pgq_csr **out) {
 	r->pack_k = c->pack_k;
 	r->pack_order = c->pack_order;
 	r->pack_align = c->pack_align;
+	r->hub_h = c->hub_h;
+	r->hub_n = c->hub_n;
 	// every array but the ones built on first use (a replica builds its own), at the size it was allocated with
 	const auto from = csr_arrays(const_cast<pgq_csr *>(c)), to = csr_arrays(r);
 	for (int k = 0; k < kCsrArrays; k++) {
@@ -2170,6 +2310,32 @@ int pgq_csr_meet_layout(const pgq_csr_t *c, int dir, int64_t *offsets, int32_t *
 	if (work && V > 0) PGQ_TRY(staged_download(work, dir == 0 ? c->fwork : c->rwork, V * 4, st));
 	if (packed && pgroups > 0) PGQ_TRY(staged_download(packed, dir == 0 ? c->ppadj : c->prpadj, pgroups * 16, st));
 	if (rhead && V > 0) PGQ_TRY(staged_download(rhead, c->rhead, V * 256, st));
+	return PGQ_OK;
+}
+int pgq_csr_hub_sizes(const pgq_csr_t *c, int64_t *sizes) {
+	if (!c || !sizes) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_hub_sizes: NULL handle or no room");
+	if (!c->hubt) return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_hub_sizes: this CSR has no hub tables");
+	sizes[0] = c->hub_h;
+	sizes[1] = c->hub_n;
+	sizes[2] = c->hub_h / 64;
+	return PGQ_OK;
+}
+int pgq_csr_hub_tables(pgq_csr_t *csr, int replica, int32_t *hub_ids, uint64_t *hub1_out, uint64_t *hub1_in, uint64_t *hub2_out, uint64_t *hub2_in) {
+	PGQ_TRY(ensure_init());
+	if (!csr) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_hub_tables: NULL handle");
+	const pgq_csr *c = csr;
+	if (replica >= 0) { // the copy pgq_csr_replicate made for the replica-th enabled device
+		std::lock_guard<std::mutex> g(csr->replica_lock);
+		if ((size_t)replica >= csr->replicas.size() || !csr->replicas[(size_t)replica]) return fail(PGQ_ERR_INVALID_ARG, "pgq_csr_hub_tables: no such replica");
+		c = csr->replicas[(size_t)replica];
+	}
+	if (!c->hubt) return fail(PGQ_ERR_UNSUPPORTED, "pgq_csr_hub_tables: this CSR has no hub tables");
+	hipStream_t st = nullptr; // the null stream, as pgq_csr_download
+	const size_t groups = (size_t)c->V * (size_t)(c->hub_h / 128), bytes = groups * 16;
+	if (hub_ids) PGQ_TRY(staged_download(hub_ids, c->hub_ids, (size_t)c->hub_h * 4, st));
+	uint64_t *const to[4] = { hub1_out, hub1_in, hub2_out, hub2_in }; // kHub1Out, kHub1In, kHub2Out, kHub2In
+	for (int k = 0; k < 4; k++)
+		if (to[k]) PGQ_TRY(staged_download(to[k], c->hubt + (size_t)k * groups, bytes, st));
 	return PGQ_OK;
 }
 

@@ -413,6 +413,7 @@ struct PrepassArgs {
 	DecideMode decide = DecideMode::None;
 	BallMode ball = BallMode::Off;
 	int64_t max_hops = -1; // *_within: >= 0 = rows farther apart are NULL (the kernels' bounded instantiations)
+	bool no_hubs = false;  // k_meet3 does not consult the hub tables: every row is walked (the routing calibration measures the walks)
 };
 struct PrepassResult {
 	u32 n_open = 0;              // rows left in ws->open_src / open_dst / open_idx
@@ -421,6 +422,7 @@ struct PrepassResult {
 	bool ball_took = false;      // ... and took the call: the open rows are what they left
 	double est_sources = -1.0;   // distinct sources: the decision kernel's estimate, or the source runs the ball counted
 	int observed_go = -1;        // DecideMode::Ride: the sample's verdict (1 = the pre-pass pays), -1 when none was taken
+	int64_t hub_settled = 0;     // rows k_meet3 answered from the hub tables instead of walking them
 };
 int meet_prepass(pgq_csr *c, Workspace *ws, const PrepassArgs &a, PrepassResult *r);
 // the pre-pass's sampled decision alone, waited for (*go: the pre-pass pays)

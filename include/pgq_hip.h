@@ -167,6 +167,18 @@ int pgq_csr_pull_layout(const pgq_csr_t *csr, int32_t *parts, int64_t *hub_items
 int pgq_csr_meet_layout_sizes(const pgq_csr_t *csr, int64_t *sizes);
 int pgq_csr_meet_layout(const pgq_csr_t *csr, int dir, int64_t *offsets, int32_t *adj, uint32_t *seg, int32_t *padded,
                         uint32_t *desc, uint32_t *work, uint32_t *packed, uint32_t *rhead);
+/* Debugging / tests: the hub tables the upload built for k_meet3 (options meet_hubs, meet_hub_min_degree, meet_hub_min_count,
+ * meet_hub_mb), copied to host memory.  The hubs are the vertices with the most edges (out-degree + in-degree, at
+ * least meet_hub_min_degree; ties to the smaller id), at most H of them; hub h is bit h & 63 of 64-bit word h >> 6 of a table
+ * row, bits of unused slots are zero.  pgq_csr_hub_sizes writes sizes[0 .. 2] = {H, hubs in use, 64-bit words per row = H / 64}.
+ * pgq_csr_hub_tables fills whichever buffers are not NULL: hub_ids (H entries, the hubs in bit order, -1 in unused slots) and
+ * the four tables of V rows: hub1_out[v] bit h = an edge v -> h exists; hub1_in[v] bit h = an edge h -> v exists; hub2_out[v]
+ * = OR of hub1_out over the out-neighbours of v; hub2_in[v] = OR of hub1_in over the in-neighbours of v.  replica < 0: the
+ * handle's own tables; replica = k: those of the copy pgq_csr_replicate made for the k-th enabled device.
+ * PGQ_ERR_UNSUPPORTED for a handle without tables.  Read-only: no search path depends on these calls. */
+int pgq_csr_hub_sizes(const pgq_csr_t *csr, int64_t *sizes);
+int pgq_csr_hub_tables(pgq_csr_t *csr, int replica, int32_t *hub_ids, uint64_t *hub1_out, uint64_t *hub1_in, uint64_t *hub2_out,
+                       uint64_t *hub2_in);
 /* Debugging / tests: device blocks the library's block cache has handed out and not got back yet (CSR arrays and build
  * temporaries of every live handle; cached free blocks, workspaces and pinned memory are not counted).  The same figure
  * before a handle is created and after it is freed = the handle left nothing behind. */
